@@ -9,9 +9,18 @@ A step = one pass of the hot path over one synthetic batch already resident in H
 -> fused CE + Dice counts -> backward (dgrad + wgrad) -> [RCCL all-reduce of the flat gradient] -> Adam.
 Workload = BASELINE.json configs[2]: MONAI-shaped UNet(3,1,10,(32,64,128,256),(2,2,2,2),num_res_units=2),
 2 x 1 x 512 x 512 x 48 per GPU, bf16 storage / fp32 accumulate (weak scaling: per-GPU batch fixed).
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (encoder-bottleneck Conv3d,
-timed with HIP events around its launches inside the timed steps) and `cpu_baseline` (the oracle step on the
-host cores, bounded sample).
+Rank 0 prints ONE JSON line: `metric`, `value` (volumes/s over the timed steps), `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (wall time of one timed step) and the workload under `config`.  A plain run does only that: set up, warm
+up, time `--steps` steps, print.
+
+    --dump-outputs DIR   after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy
+                         (float32 / float64): `loss`, `mean_dice`, `dice_per_class`, and `params` / `grads` (the weights
+                         after that step's Adam update and that step's gradient, flat, in model.parameters() order).
+                         Inputs and weights are seeded, so two builds run with the same arguments compare output for output.
+    --full               also measure everything besides the headline (N=1 unless noted): `roofline` (encoder-bottleneck
+                         Conv3d, timed with HIP events around its launches inside the timed steps, any N), `cpu_baseline`
+                         (the oracle step on the host cores, bounded sample) with `config.dice_vs_ref`, `config.host`
+                         (host enqueue cost), `config.fp32` (fp32 storage) and `config.drop_in` (the reference's own surface).
 """
 import argparse
 import json
@@ -28,7 +37,7 @@ import torch  # noqa: E402
 
 FILTERS = [32, 64, 128, 256]
 SEED = 12342
-PEAK_BF16_TFLOPS = 2500.0          # dense MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
+PEAK_BF16_TFLOPS = 2500.0          # dense bf16 MFMA peak of the MI355X
 PEAK_F32_TFLOPS = 157.3
 
 
@@ -224,6 +233,33 @@ def exchange_rehearsal(batch, steps, precision):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(model, loss, out_dir):
+    """What the last timed fit_step handed its caller, as DIR/<name>.npy: the returned loss, the logged Dice metric, the
+    parameters after the step's Adam update and the step's gradient (flat, in model.parameters() order).  float64 for the
+    scalars, float32 for the flat arrays; a flat array that would not fit the budget is replaced by a fixed seeded sample."""
+    import numpy as np
+    params = list(model.parameters())
+    store = model.unet.engine().store
+    arrays = {
+        "loss": loss.detach().double().reshape(1),
+        "mean_dice": model.logged["Mean Dice Score (train)"].double().reshape(1),
+        "dice_per_class": model.logged["Dice per class (train)"].double().reshape(-1),
+        "params": torch.cat([p.detach().reshape(-1) for p in params]).float(),
+        "grads": torch.cat([store.grad_view(p).reshape(-1) for p in params]).float(),
+    }
+    share = (DUMP_BUDGET_BYTES - 4096) // 2 // 4          # float32 elements per flat array
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(SEED).choice(a.size, share, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -231,13 +267,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--shape", type=int, nargs=4, default=[2, 512, 512, 48], metavar=("B", "H", "W", "D"))
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: roofline, cpu_baseline + config.dice_vs_ref, "
+                         "config.host, config.fp32, config.drop_in (off: set up, warm up, time --steps steps, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--fp32-steps", type=int, default=5,
-                    help="N=1 only: also time this many steps of the same workload in fp32 storage (the reference's own "
-                         "arithmetic) after the main measurement; reported under config.fp32 (0 = skip)")
+                    help="with --full, N=1 only: also time this many steps of the same workload in fp32 storage (the "
+                         "reference's own arithmetic) after the main measurement; reported under config.fp32 (0 = skip)")
     ap.add_argument("--drop-in-steps", type=int, default=20,
-                    help="N=1 only: also time this many steps of training_step -> loss.backward() -> Adam.step() (the reference's "
-                         "own surface) after the main measurement; reported under config.drop_in (0 = skip)")
+                    help="with --full, N=1 only: also time this many steps of training_step -> loss.backward() -> Adam.step() "
+                         "(the reference's own surface) after the main measurement; reported under config.drop_in (0 = skip)")
     ap.add_argument("--exchange-rehearsal", action="store_true",
                     help="N=1 only: time the step with the data-parallel exchange issued on a one-rank RCCL group "
                          "(both CTSEG_DDP_ALGO values) against the exchange off; reported under config.dp")
@@ -268,7 +309,7 @@ def main():
 
     eng = model.unet.engine()
     plan = eng.last_plan
-    probe_i = find_op(plan, "bottleneck", 256, 256)
+    probe_i = find_op(plan, "bottleneck", 256, 256) if args.full else None
     ev = []
     if probe_i is not None:
         orig_run = plan.run
@@ -306,6 +347,8 @@ def main():
     loss_v = float(loss.item())
     if probe_i is not None:
         plan.run = orig_run          # the event brackets belong to the timed region only
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(model, loss, args.dump_outputs)
 
     baseline_shape = (B, H, W, D) == (2, 512, 512, 48)
     if rank == 0:
@@ -356,18 +399,18 @@ def main():
                 out["roofline"]["step"] = {"flop": step_flop, "ms": ms, "tflops": step_flop / (ms * 1e-3) / 1e12,
                                            "frac_of_mfma_peak": step_flop / (ms * 1e-3) / 1e12 / peak,
                                            "per_layer_roofline_ms": step_roof_ms, "frac_of_per_layer_roofline": step_roof_ms / ms}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 ncpu = len(os.sched_getaffinity(0))
             except AttributeError:
                 ncpu = os.cpu_count() or 1
             out["cpu_baseline"], dvr = cpu_baseline(tuple(args.cpu_shape), max(1, min(ncpu, 16)), dev, args.precision)
             out["config"]["dice_vs_ref"] = dvr
-        if world == 1:
+        if world == 1 and args.full:
             out["config"]["host"] = host_enqueue(model, batch)
-        if world == 1 and args.fp32_steps > 0 and args.precision == "bf16":
+        if world == 1 and args.full and args.fp32_steps > 0 and args.precision == "bf16":
             out["config"]["fp32"] = fp32_line(model, batch, args.fp32_steps)
-        if world == 1 and args.drop_in_steps > 0:
+        if world == 1 and args.full and args.drop_in_steps > 0:
             out["config"]["drop_in"] = drop_in_line(batch, args.drop_in_steps, args.precision)
             out["config"]["drop_in"]["fit_step_ms_per_step"] = ms
         if world == 1 and args.exchange_rehearsal:

@@ -18,7 +18,7 @@ from oracle import metrics as OM
 def emu():
     e = Emulator()
     undo = patch_native(nat, e)
-    orig = plan_mod.Plan.run
+    orig = plan_mod.Plan.__dict__["run"]         # the staticmethod itself: restoring the bare function would bind self
     plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
     yield e
     plan_mod.Plan.run = orig

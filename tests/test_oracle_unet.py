@@ -52,4 +52,13 @@ def test_tiny_step_fixture_reproduces(golden):
         np.testing.assert_allclose(loss.numpy(), g[f"{tag}_loss"], rtol=1e-5)
         np.testing.assert_allclose(m.logged["Mean Dice Score (train)"].numpy(), g[f"{tag}_dice_mean"], atol=1e-6)
         for k, v in m.state_dict().items():
-            np.testing.assert_allclose(v.numpy(), g[f"{tag}_w1:{k}"], rtol=1e-4, atol=2e-4)
+            # Adam's first step is -lr*sign(g): where the fixture's gradient is rounding noise (conv biases feeding an
+            # InstanceNorm have an analytically zero gradient) its sign follows the host's summation order (thread count, CPU),
+            # so those elements are only held to the step bound, 2*lr apart at most, as in test_tiny_step_fixture_fit_step
+            gref, w1 = g[f"{tag}_g:{k}"], g[f"{tag}_w1:{k}"]
+            solid = np.abs(gref) > 1e-3 * max(np.abs(gref).max(), 1e-6)
+            if k.endswith(".bias") and "residual" not in k:
+                solid &= False
+            got = v.numpy()
+            np.testing.assert_allclose(got[solid], w1[solid], rtol=1e-4, atol=2e-4, err_msg=k)
+            np.testing.assert_allclose(got, w1, rtol=0, atol=2.1e-3, err_msg=k)

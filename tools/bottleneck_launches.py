@@ -19,7 +19,7 @@ def main(trace, bench_json=None, steps=10):
     third = d[2::per][-steps:]
     avg = sum(third) / len(third)
     out = {"kernel": f"conv_igemm_ring_kernel<BF16, 256{', false' if per == 3 else ''}> — 3rd of its {per} launches per step = encoder-bottleneck Conv3d 256->256 k3 forward",
-           "source": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline "
+           "source": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline "
                      "--fp32-steps 0 (kernel_trace.csv, per-dispatch end - start)",
            f"durations_ns_last{steps}_steps": third, "average_ns": avg, "tflops": 173946175488.0 / avg / 1e3,
            "frac_of_2500_tflops": 173946175488.0 / avg / 1e3 / 2500.0}

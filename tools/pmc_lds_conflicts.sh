@@ -8,7 +8,7 @@ ROOT=$(pwd)
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 (cd /tmp && CTSEG_SIDE_STREAM=0 timeout -k 10 400 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d "$ROOT/$OUT/run" -- \
-   python3 "$ROOT/bench.py" --no-cpu-baseline --fp32-steps 0 --steps 3 --warmup 2 > "$ROOT/$OUT/run.log" 2>&1)
+   python3 "$ROOT/bench.py" --full --no-cpu-baseline --fp32-steps 0 --steps 3 --warmup 2 > "$ROOT/$OUT/run.log" 2>&1)
 python3 - "$OUT" <<'PY'
 import csv, glob, os, sys
 from collections import defaultdict
