@@ -1,4 +1,6 @@
-// Shared pieces of the implicit-GEMM convolution kernels (generic gather kernel + LDS-halo kernel).
+// Shared pieces of the forward implicit-GEMM convolution kernels: launch arguments (ConvKArgs, BstArgs), the backward-statistics
+// terms, XCD-ordered tile walks, the 2x8 patch lane <-> voxel map of the LDS-halo kernels, the parity-class tap order of the
+// transposed convolutions, the MFMA step and the epilogue of the gather kernels.
 #pragma once
 #include "ctseg_dev.h"
 
@@ -72,6 +74,36 @@ __device__ __forceinline__ int xcd_tile(int L, int total) {
   const int chunk = (total + 7) >> 3, i = L >> 3;
   const int t = (L & 7) * chunk + i;
   return (i < chunk && t < total) ? t : -1;
+}
+
+// Tile sequence first, first + stride, ... (< last) of persistent workgroup `id` of `groups`.  With a multiple of 8 workgroups each
+// XCD (id % 8 shares one) owns a contiguous range of tiles and its workgroups walk it round-robin, so the tiles in flight on one XCD
+// are neighbours and share their halos through that XCD's L2.  `id` is a callable returning the workgroup id, so that blockIdx.x is
+// read in each branch as the hand-written copies did (read once up front, it reorders the kernels' prologues and spill placement).
+struct TileSeq { int first, stride, last; };
+template <class Id> __device__ __forceinline__ TileSeq xcd_tile_seq(Id id, int groups, int total) {
+  if ((groups & 7) == 0) {
+    const int chunk = (total + 7) / 8, xcd = id() & 7;
+    return {int(xcd * chunk + (id() >> 3)), groups >> 3, (xcd + 1) * chunk < total ? (xcd + 1) * chunk : total};
+  }
+  return {int(id()), groups, total};
+}
+
+// r16 -> (dy, z) inside a 2x8 patch:  A = {0,1,2,3,12,13,14,15} -> row0 z0..4, row1 z0..2 ; B = {4..11} -> row0 z5..7, row1 z3..7
+// (the LDS-halo kernels' lane <-> voxel permutation: every ds_read_b128 lane group of an operand read is conflict free)
+__device__ __forceinline__ void patch_voxel(int r16, int& dy, int& z) {
+  dy = (0xEF80u >> r16) & 1;
+  z = (int)((0x2104765437653210ull >> (4 * r16)) & 7ull);
+}
+
+// tap index of shift delta = (dx,dy,dz) in {0,1}^3 inside parity class c = px*4 + py*2 + pz, in the order the host lists a class's taps
+// (capstone_amd/engine.py classes_up: x outermost; a parity-1 axis lists offset +1 before 0) — checked by conv_up_eligible and
+// conv_up8_eligible; -1: the class has no such tap
+constexpr int up_tap_index(int c, int delta) {
+  const int px = (c >> 2) & 1, py = (c >> 1) & 1, pz = c & 1, dx = (delta >> 2) & 1, dy = (delta >> 1) & 1, dz = delta & 1;
+  if (dx > px || dy > py || dz > pz) return -1;
+  const int ix = px ? 1 - dx : 0, iy = py ? 1 - dy : 0, iz = pz ? 1 - dz : 0;
+  return (ix * (1 + py) + iy) * (1 + pz) + iz;
 }
 
 template <typename T> __device__ __forceinline__ void mma16(f32x4& acc, const u32x4& wfrag, const u32x4& xfrag);

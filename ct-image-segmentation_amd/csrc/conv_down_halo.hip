@@ -134,7 +134,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
       // the input is exactly twice the row grid (host-checked): only the -1 taps of the first tile along an axis leave the volume;
       // what a partial tile reads past the grid feeds rows that are not stored (finite, or zero past the end of the sample)
       const int bias = (G.ia + G.ib + G.ic) * P.g_ld * 2, sb = (int)(in_sample * P.g_ld * 2);
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.in) + (int64_t)n * sb - bias, 0, sb + bias, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(P.in + (int64_t)n * sb - bias, sb + bias);
       const int soff = (2 * a0 * G.ia + 2 * b0 * G.ib + 2 * c0 * G.ic) * P.g_ld * 2;
       const int m = (a0 == 0 ? 1 : 0) | (b0 == 0 ? 2 : 0) | (c0 == 0 ? 4 : 0);
 #pragma unroll
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
       const int ai0 = 2 * a0 - 1, bi0 = 2 * b0 - 1, ci0 = 2 * c0 - 1;       // input coordinate of halo (0,0,0)
       // branch-free (plain loads under `if (inside)` were waited for one by one): out-of-volume voxels get an out-of-range offset
       const int bias = (G.ia + G.ib + G.ic) * P.g_ld * 2, sb = (int)(in_sample * P.g_ld * 2);
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.in) + (int64_t)n * sb - bias, 0, sb + bias, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(P.in + (int64_t)n * sb - bias, sb + bias);
       const int soff = (2 * a0 * G.ia + 2 * b0 * G.ib + 2 * c0 * G.ic) * P.g_ld * 2;
 #pragma unroll
       for (int j = 0; j < J; ++j) {
@@ -263,7 +263,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
   u32x4 yq[RT];
   int bst_n = -1;
   auto y_issue = [&](int n, int a0, int b0, int c0) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.bst.y) + (int64_t)n * y_sample_bytes, 0, y_sample_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(P.bst.y + (int64_t)n * y_sample_bytes, y_sample_bytes);
     const int soff = (a0 * G.oa + b0 * G.ob + c0 * G.oc) * P.bst.y_ld * 2;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -313,16 +313,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
     __syncthreads();
   };
 
-  const int GX = gridDim.x;
-  int first, stride, last;
-  if ((GX & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    first = xcd * chunk + (blockIdx.x >> 3);
-    stride = GX >> 3;
-    last = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  } else {
-    first = blockIdx.x; stride = GX; last = total_tiles;
-  }
+  const auto [first, stride, last] = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
 
   constexpr bool RES = CF::RES;
   __syncthreads();

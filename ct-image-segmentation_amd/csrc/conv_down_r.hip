@@ -34,18 +34,6 @@ constexpr int DR_SLOTS = DR_HA * DR_HB * DR_HC;                 // 867 voxel slo
 constexpr int DR_NP = (DR_SLOTS + 15) / 16, DR_PJ = (DR_NP + 7) / 8;   // 55 DMA pieces (16 slots) per tile, <= 7 per wave
 constexpr int DR_HALO = DR_NP * 1024;                           // 56 320 bytes
 
-typedef int32_t dr_i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t __attribute__((address_space(3)))* dr_lds_ptr;
-__device__ void dr_buffer_load_lds(dr_i32x4 rsrc, dr_lds_ptr lds, int size, int voffset, int soffset, int offset,
-                                   int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-__device__ __forceinline__ dr_i32x4 dr_make_rsrc(const void* p, uint32_t bytes) {
-  struct __attribute__((packed)) { const void* ptr; uint32_t range; uint32_t config; } r{p, bytes, 0x00020000u};
-  dr_i32x4 v = __builtin_bit_cast(dr_i32x4, r);
-  v[0] = __builtin_amdgcn_readfirstlane(v[0]); v[1] = __builtin_amdgcn_readfirstlane(v[1]);
-  v[2] = __builtin_amdgcn_readfirstlane(v[2]); v[3] = __builtin_amdgcn_readfirstlane(v[3]);
-  return v;
-}
-
 struct DownRGeom {
   int da, db, dc;            // output (row grid) extents along the tile axes (a = the 1-deep axis)
   int ia, ib, ic;            // input voxel strides of the tile axes
@@ -121,7 +109,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
   auto dma = [&](int t, int buf) {
     int n, a0, b0, c0;
     tile_origin(t, n, a0, b0, c0);
-    const dr_i32x4 rs = dr_make_rsrc(P.in + (int64_t)n * G.in_sample_bytes - hbias, (uint32_t)(G.in_sample_bytes + hbias));
+    const i32x4 rs = make_rsrc(P.in + (int64_t)n * G.in_sample_bytes - hbias, (uint32_t)(G.in_sample_bytes + hbias));
     const int soff = (2 * a0 * G.ia + 2 * b0 * G.ib + 2 * c0 * G.ic) * P.g_ld * 2;
     const int m = (a0 == 0 ? 1 : 0) | (b0 == 0 ? 2 : 0) | (c0 == 0 ? 4 : 0) | 8;
     char* dst = smem + buf * DR_HALO;
@@ -130,7 +118,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
       const int i = wave + 8 * j;
       if (i < DR_NP && !(DR_ABL & 4)) {       // wave-uniform
         const int vo = (dpk[j] & m) == 0 ? (dpk[j] & ~15) : (int)0x80000000;
-        dr_buffer_load_lds(rs, (dr_lds_ptr)(dst + i * 1024), 16, vo, soff, 0, 0);
+        raw_buffer_load_lds(rs, (lds_u32_ptr)(dst + i * 1024), 16, vo, soff, 0, 0);
       }
     }
   };
@@ -209,16 +197,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
     }
   };
 
-  const int GX = gridDim.x;
-  int first, stride, last;
-  if ((GX & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    first = xcd * chunk + (blockIdx.x >> 3);
-    stride = GX >> 3;
-    last = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  } else {
-    first = blockIdx.x; stride = GX; last = total_tiles;
-  }
+  const auto [first, stride, last] = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
 
   int t = first, buf = 0;
   if (t < last) dma(t, 0);
@@ -239,7 +218,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
         bst_consts(n);
       }
       // y of this tile's voxels, ahead of the next tile's DMA pieces (always issued: the counted wait at the loop head)
-      const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.bst.y) + (int64_t)n * y_sample_bytes, 0, y_sample_bytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t yrs = buffer_rsrc(P.bst.y + (int64_t)n * y_sample_bytes, y_sample_bytes);
       const int ysoff = (a0 * G.oa + b0 * G.ob + c0 * G.oc) * P.bst.y_ld * 2;
 #pragma unroll
       for (int rt = 0; rt < 4; ++rt) {
@@ -274,7 +253,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
       }
     }
     // ---- epilogue: lane = (voxel (b, c) of row tile rt, columns col0 + 4 q4 .. + 3); four buffer stores, always issued ---------
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(obase + (int64_t)n * osb, 0, osb, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ors = buffer_rsrc(obase + (int64_t)n * osb, osb);
     const int soff = (a0 * G.oa + b0 * G.ob + c0 * G.oc) * old_ * 2;
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt) {

@@ -24,12 +24,6 @@ constexpr int H_TX = 4, H_TY = 8, H_TZ = 8;
 constexpr int H_HX = H_TX + 2, H_HY = H_TY + 2, H_HZ = H_TZ + 2, H_HV = H_HX * H_HY * H_HZ;  // 600
 constexpr int H_PLANE = H_HV * 16;
 
-// r16 -> (dy, z) inside a 2x8 patch:  A = {0,1,2,3,12,13,14,15} -> row0 z0..4, row1 z0..2 ; B = {4..11} -> row0 z5..7, row1 z3..7
-__device__ __forceinline__ void patch_voxel(int r16, int& dy, int& z) {
-  dy = (0xEF80u >> r16) & 1;
-  z = (int)((0x2104765437653210ull >> (4 * r16)) & 7ull);
-}
-
 template <int VB, int NT> struct HaloCfg {
   // 64-byte voxels: one workgroup per CU (134 KB of LDS) -> 8 waves, two row tiles each, so the MFMAs of one wave cover the
   // LDS latency of another; 32-byte voxels fit three 4-wave workgroups per CU
@@ -287,18 +281,7 @@ __global__ __launch_bounds__((HaloCfg<VB, NT>::NTHR)) void conv_halo_kernel(cons
     }
   };
 
-  // tile sequence of this workgroup: each XCD (blockIdx % 8 shares one) owns a contiguous range of tiles, its workgroups
-  // walk it round-robin, so the ~64 tiles in flight on one XCD are neighbours and share halos through that XCD's L2
-  const int G = gridDim.x;
-  int first, stride, last;
-  if ((G & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    first = xcd * chunk + (blockIdx.x >> 3);
-    stride = G >> 3;
-    last = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  } else {
-    first = blockIdx.x; stride = G; last = total_tiles;
-  }
+  const auto [first, stride, last] = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
   u32x4 r0[J], r1[J];
   int ta = first, tb = first + stride;
   if (ta < last) {

@@ -62,11 +62,6 @@ struct SwGeom {
   int tbn, tcn, tiles;       // tiles along b, c; tiles per sample
 };
 
-__device__ __forceinline__ void sw_patch_voxel(int r16, int& db, int& c) {
-  db = (0xEF80u >> r16) & 1;
-  c = (int)((0x2104765437653210ull >> (4 * r16)) & 7ull);
-}
-
 // BST: backward InstanceNorm statistics of the written gradient (ConvKArgs::bst) on the input-gradient passes (8-class 128 -> 32,
 // single-class 64 -> 64).  After the v_permlane16_swap of the store a lane holds 16-byte chunks (8 consecutive channels) of one
 // voxel: the matching y chunks are requested one class ahead, beside the addend of that class (8 classes), or at the top of the
@@ -200,7 +195,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
 
   // ---- per-lane constants of the MFMA operands and the epilogue -------------------------------------------------------
   int pdb, pc;
-  sw_patch_voxel(r16, pdb, pc);
+  patch_voxel(r16, pdb, pc);
   // row tile rt of wave w: a = wa, b in {2i, 2i+1}, c 0..7 (permuted inside the 2x8 patch)
   int abase[RT], va[RT], vb[RT];
 #pragma unroll
@@ -354,7 +349,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
   auto add_issue = [&](int cls, int n, int a0, int b0, int c0) {        // cls < 0: nothing to fetch (same operation count)
     const int cb = cls >= 0 ? class_base(cls, a0, b0, c0) : 0;
     if (apf) {
-      const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.add) + (int64_t)n * add_sample_bytes, 0, add_sample_bytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t ars = buffer_rsrc(P.add + (int64_t)n * add_sample_bytes, add_sample_bytes);
       const int soff = cb * P.add_ld * ASZ;
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
@@ -366,7 +361,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
       pend += RT * NT;
     }
     if constexpr (BST) {             // the y chunks of the class's voxels
-      const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.bst.y) + (int64_t)n * y_sample_bytes, 0, y_sample_bytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t yrs = buffer_rsrc(P.bst.y + (int64_t)n * y_sample_bytes, y_sample_bytes);
       const int soff = cb * P.bst.y_ld * 2;
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt) {
@@ -378,7 +373,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
   };
   auto epilogue = [&](int cls, int next_cls, int n, int a0, int b0, int c0) {
     const int cb = class_base(cls, a0, b0, c0);
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(P.out + (int64_t)n * out_sample_bytes, 0, out_sample_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ors = buffer_rsrc(P.out + (int64_t)n * out_sample_bytes, out_sample_bytes);
     const int soff = cb * P.o_ld * 2;
     // 16-byte stores: v_permlane16_swap hands the lanes of q4 = 0 / 2 the neighbouring 4 channels of their own 16-column block and the
     // lanes of q4 = 1 / 3 those of the next block, so a lane holds 8 consecutive channels (16-byte chunk {0, 2, 1, 3}[q4] of 32 channels)
@@ -490,8 +485,8 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
   auto epilogue_plain_bst = [&](int n, int a0, int b0, int c0) {
     const ctseg_conv_class& K = P.cls[0];
     const int cb = a0 * G.oa + b0 * G.ob + c0 * G.oc + (K.ox * P.Yo + K.oy) * P.Zo + K.oz;
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(P.out + (int64_t)n * out_sample_bytes, 0, out_sample_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.bst.y) + (int64_t)n * y_sample_bytes, 0, y_sample_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ors = buffer_rsrc(P.out + (int64_t)n * out_sample_bytes, out_sample_bytes);
+    const __amdgpu_buffer_rsrc_t yrs = buffer_rsrc(P.bst.y + (int64_t)n * y_sample_bytes, y_sample_bytes);
     u32x4 yq[RT][NQ];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -531,17 +526,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
     }
   };
 
-  // tile sequence: each XCD owns a contiguous range of tiles (neighbouring halos share that XCD's L2)
-  const int GX = gridDim.x;
-  int first, stride, last;
-  if ((GX & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    first = xcd * chunk + (blockIdx.x >> 3);
-    stride = GX >> 3;
-    last = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  } else {
-    first = blockIdx.x; stride = GX; last = total_tiles;
-  }
+  const auto [first, stride, last] = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
 
   __syncthreads();                                   // tap tables visible
   int t = first;

@@ -36,27 +36,6 @@ constexpr int X_HVP = 648;
 constexpr int X_PLANE = X_HVP * 16;
 constexpr int X_XSTRIDE = X_HY * X_HZ * 16;   // bytes between x planes of the halo
 
-typedef int32_t xi32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t __attribute__((address_space(3)))* x_lds_u32_ptr;
-__device__ void x_raw_buffer_load_lds(xi32x4 rsrc, x_lds_u32_ptr lds, int size, int voffset, int soffset, int offset,
-                                      int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-
-__device__ __forceinline__ xi32x4 x_make_rsrc(const void* p, uint32_t bytes) {
-  struct __attribute__((packed)) { const void* ptr; uint32_t range; uint32_t config; } r{p, bytes, 0x00020000u};
-  xi32x4 v = __builtin_bit_cast(xi32x4, r);
-  v[0] = __builtin_amdgcn_readfirstlane(v[0]);
-  v[1] = __builtin_amdgcn_readfirstlane(v[1]);
-  v[2] = __builtin_amdgcn_readfirstlane(v[2]);
-  v[3] = __builtin_amdgcn_readfirstlane(v[3]);
-  return v;
-}
-
-// r16 -> (dy, z) inside a 2x8 patch (same permutation as conv_halo.hip: every ds_read_b128 lane group is conflict free)
-__device__ __forceinline__ void x_patch_voxel(int r16, int& dy, int& z) {
-  dy = (0xEF80u >> r16) & 1;
-  z = (int)((0x2104765437653210ull >> (4 * r16)) & 7ull);
-}
-
 template <int VB> struct XCfg {
   static constexpr int NPL = VB / 16;                  // 16-byte channel chunks per voxel = LDS planes
   static constexpr int HALO = NPL * X_PLANE;           // one halo buffer
@@ -164,7 +143,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
   const ctseg_conv_class& K = P.cls[0];
   const int col0 = blockIdx.y * (16 * NTA) + ns * 16 * NT;   // first output column of this wave
   int pdy, pz;
-  x_patch_voxel(r16, pdy, pz);
+  patch_voxel(r16, pdy, pz);
 
   // ---- weights -> registers, canonical order W[column block][dx + 1][type] whatever the pass (FLIP: the input-gradient pass
   //      lists its taps with every offset negated, so its group of dx = -1 is the LAST nine taps and type t holds -(canonical)) ----
@@ -235,7 +214,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
         // lanes read back (lane (r16, q4): plane i, chunk 2 ns + (q4 >> 1) at lane slot i * 16 + r16 of piece q4 >> 1)
         static_assert(!A1 || APW == 2, "two chunks per wave group");
         int ady, az;
-        x_patch_voxel(lane & 15, ady, az);
+        patch_voxel(lane & 15, ady, az);
         const int ix = lane >> 4, iy = 2 * yp + ady, iz = az;
         apoff[j] = ((ix * P.Yo + iy) * P.Zo + iz) * P.add_ld * 2 + (blockIdx.y * ACH + 2 * ns + j) * 16;
         aphot[j] = (1u << ix) | (1u << (4 + iy)) | (1u << (12 + iz));
@@ -413,7 +392,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     const uint32_t m = range_mask(1 - o.x0, P.Xi - o.x0, X_HX) | (range_mask(1 - o.y0, P.Yi - o.y0, X_HY) << 6) |
                        (range_mask(1 - o.z0, P.Zi - o.z0, X_HZ) << 16);
     const uint32_t notm = ~m;
-    const xi32x4 rs = x_make_rsrc(P.in + (int64_t)o.n * G.in_sample_bytes - bias_bytes, (uint32_t)(G.in_sample_bytes + bias_bytes));
+    const i32x4 rs = make_rsrc(P.in + (int64_t)o.n * G.in_sample_bytes - bias_bytes, (uint32_t)(G.in_sample_bytes + bias_bytes));
     const int soff = ((o.x0 * P.Yi + o.y0) * P.Zi + o.z0) * P.g_ld * 2;    // halo origin = tile origin - (1,1,1) = this + (rsrc base shift)
     char* dst = smem + buf * CF::HALO;
     if (NWD < NW && wave >= NWD) return;
@@ -422,18 +401,18 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     for (int j = 0; j < PPW; ++j) {
       const int piece = wave + j * NWD;
       const int vo = (live && (phot[j] & notm) == 0u) ? poff[j] : (int)0x80000000;
-      x_raw_buffer_load_lds(rs, (x_lds_u32_ptr)(dst + (piece / X_PIECES) * X_PLANE + (piece % X_PIECES) * 1024), 16, vo, soff, 0, 0);
+      raw_buffer_load_lds(rs, (lds_u32_ptr)(dst + (piece / X_PIECES) * X_PLANE + (piece % X_PIECES) * 1024), 16, vo, soff, 0, 0);
     }
     if constexpr (ADD == 3) {      // the addend of the same tile, consumed (into registers) at the end of its multiplies
       const uint32_t am = range_mask(0, P.Xr - o.x0 - 1, X_TX) | (range_mask(0, P.Yr - o.y0 - 1, 8) << 4) | (range_mask(0, P.Zr - o.z0 - 1, 8) << 12);
       const uint32_t anot = ~am;
-      const xi32x4 ars = x_make_rsrc(P.add + (int64_t)o.n * G.add_sample_bytes, (uint32_t)G.add_sample_bytes);
+      const i32x4 ars = make_rsrc(P.add + (int64_t)o.n * G.add_sample_bytes, (uint32_t)G.add_sample_bytes);
       const int asoff = ((o.x0 * P.Yo + o.y0) * P.Zo + o.z0) * P.add_ld * 2;
 #pragma unroll
       for (int j = 0; j < APW; ++j) {
         const int vo = (live && (aphot[j] & anot) == 0u) ? apoff[j] : (int)0x80000000;
-        if constexpr (A1) x_raw_buffer_load_lds(ars, (x_lds_u32_ptr)(sA + (wave * APW + j) * 1024), 16, vo, asoff, 0, 0);
-        else x_raw_buffer_load_lds(ars, (x_lds_u32_ptr)(sA + buf * ABUF + (wave + j * NW) * 1024), 16, vo, asoff, 0, 0);
+        if constexpr (A1) raw_buffer_load_lds(ars, (lds_u32_ptr)(sA + (wave * APW + j) * 1024), 16, vo, asoff, 0, 0);
+        else raw_buffer_load_lds(ars, (lds_u32_ptr)(sA + buf * ABUF + (wave + j * NW) * 1024), 16, vo, asoff, 0, 0);
       }
     }
   };
@@ -443,8 +422,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     const uint32_t m = range_mask(1 - o.x0, P.Xi - o.x0, X_HX) | (range_mask(1 - o.y0, P.Yi - o.y0, X_HY) << 6) |
                        (range_mask(1 - o.z0, P.Zi - o.z0, X_HZ) << 16);
     const uint32_t notm = ~m;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.in) + (int64_t)o.n * G.in_sample_bytes - bias_bytes, 0,
-                                                                         G.in_sample_bytes + bias_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(P.in + (int64_t)o.n * G.in_sample_bytes - bias_bytes, G.in_sample_bytes + bias_bytes);
     const int soff = ((o.x0 * P.Yi + o.y0) * P.Zi + o.z0) * P.g_ld * 2;
 #pragma unroll
     for (int j = 0; j < R_J; ++j) {
@@ -515,7 +493,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     y.nx = P.Xr - o.x0;
     y.lane_ok = (o.y0 + 2 * yp + pdy < P.Yr) && (o.z0 + pz < P.Zr);
     y.sbase = (int)((((int64_t)o.x0 * P.Yo + o.y0) * P.Zo + o.z0) * P.o_ld * 2);       // y is laid out like the written tensor (host-checked)
-    y.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.bst.y) + (int64_t)o.n * G.y_sample_bytes, 0, G.y_sample_bytes, 0x00020000);
+    y.rs = buffer_rsrc(P.bst.y + (int64_t)o.n * G.y_sample_bytes, G.y_sample_bytes);
   };
   auto y_load = [&](const Yl& y, int i) {
 #pragma unroll
@@ -538,10 +516,9 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     e.lane_ok = (o.y0 + 2 * yp + pdy < P.Yr) && (o.z0 + pz < P.Zr);
     const int64_t tvox = ((int64_t)o.x0 * P.Yo + o.y0) * P.Zo + o.z0;
     e.sbase = (int)(tvox * P.o_ld * OSZ);                        // < 2^31 (host-checked per sample)
-    e.ors = __builtin_amdgcn_make_buffer_rsrc(P.out + (int64_t)o.n * G.out_sample_bytes, 0, G.out_sample_bytes, 0x00020000);
+    e.ors = buffer_rsrc(P.out + (int64_t)o.n * G.out_sample_bytes, G.out_sample_bytes);
     if constexpr (ADD == 2) {
-      const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.add) + (int64_t)o.n * G.add_sample_bytes, 0,
-                                                                            G.add_sample_bytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t ars = buffer_rsrc(P.add + (int64_t)o.n * G.add_sample_bytes, G.add_sample_bytes);
       const int abase = (int)(tvox * P.add_ld * ASZ);
 #pragma unroll
       for (int j = 0; j < NT; ++j)
@@ -788,7 +765,9 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
   auto ce_label = [&](const Org& o) -> int {
     const int xg = o.x0 + q4, yg = o.y0 + 2 * yp + pdy, zg = o.z0 + pz;
     const bool valid = xg < P.Xr && yg < P.Yr && zg < P.Zr;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(E.labels) + (int64_t)o.n * ce_svox, 0, ce_svox, 0x00020000);
+    // the builtin, not buffer_rsrc(): inlined, the helper marks the pointer readnone, and that reschedules the fused-head kernels
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(E.labels) + (int64_t)o.n * ce_svox, 0, ce_svox,
+                                                                         BUF_RSRC_CONFIG);
     const int tbase = (o.x0 * P.Yo + o.y0) * P.Zo + o.z0;
     return (int)__builtin_amdgcn_raw_buffer_load_b8(rs, valid ? ce_vox : (int)0x80000000, tbase, 0);     // out of range: 0
   };
@@ -929,7 +908,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     {
       const bool st_ok = (X_ABL & 16) ? (valid && d[0] + d[5] == 123.f) : valid;
       const int row = E.g_ld * 2;
-      const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(E.dlogits + (int64_t)o.n * ce_svox * row, 0, ce_svox * row, 0x00020000);
+      const __amdgpu_buffer_rsrc_t grs = buffer_rsrc(E.dlogits + (int64_t)o.n * ce_svox * row, ce_svox * row);
       const int gbase = ((o.x0 * P.Yo + o.y0) * P.Zo + o.z0) * row;
       const int gvo = st_ok ? ce_vox * row : (int)0x80000000;
       const u32x4 lo = {pack2<H>(d[0], d[1]), pack2<H>(d[2], d[3]), pack2<H>(d[4], d[5]), pack2<H>(d[6], d[7])};
@@ -946,17 +925,9 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     }
   };
 
-  // ---- tile sequence of this workgroup (as conv_halo.hip: each XCD owns a contiguous range, walked round-robin) -----------------
-  const int Gd = gridDim.x;
-  int first, stride, last;
-  if ((Gd & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    first = xcd * chunk + (blockIdx.x >> 3);
-    stride = Gd >> 3;
-    last = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  } else {
-    first = blockIdx.x; stride = Gd; last = total_tiles;
-  }
+  // ---- tile sequence of this workgroup ------------------------------------------------------------------------------------------
+  const TileSeq seq = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
+  const int first = seq.first, stride = seq.stride, last = seq.last;   // (captured below: no structured bindings)
   // Per tile t: [wait for this wave's DMA pieces of tile t] [barrier: halo[buf] complete, everyone done with halo[buf^1]]
   // [DMA of tile t+1 into halo[buf^1]] [multiplies of tile t from halo[buf], with the epilogue of tile t-1 between its K steps].
   // The X_TX stores of that epilogue are the only vector-memory operations younger than the DMA, so the counted wait at the top

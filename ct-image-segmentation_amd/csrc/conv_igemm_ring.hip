@@ -39,23 +39,6 @@ template <int BN_> struct RingCfgT {
 };
 using RingCfg = RingCfgT<256>;
 
-typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t __attribute__((address_space(3)))* lds_u32_ptr;
-// buffer_load_dwordx4 ... lds: per-lane 32-bit byte offset into a range-checked buffer; an offset past the range
-// delivers zeros (the padding voxels of a tap), so the stage body needs no branch and no zero page
-__device__ void llvm_amdgcn_raw_buffer_load_lds(i32x4 rsrc, lds_u32_ptr lds, int size, int voffset, int soffset, int offset,
-                                                int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-
-__device__ __forceinline__ i32x4 make_rsrc(const void* p, uint32_t bytes) {
-  struct __attribute__((packed)) { const void* ptr; uint32_t range; uint32_t config; } r{p, bytes, 0x00020000u};
-  i32x4 v = __builtin_bit_cast(i32x4, r);
-  v[0] = __builtin_amdgcn_readfirstlane(v[0]);
-  v[1] = __builtin_amdgcn_readfirstlane(v[1]);
-  v[2] = __builtin_amdgcn_readfirstlane(v[2]);
-  v[3] = __builtin_amdgcn_readfirstlane(v[3]);
-  return v;
-}
-
 // NA = 16-row blocks of the gathered operand this wave fetches per stage (12 blocks over 8 waves: 2 for waves 0-3, 1 for 4-7)
 template <typename H, int BN, int NA>
 __device__ __forceinline__ void ring_main(const ConvKArgs& P, const ctseg_conv_class& K, char* smem, const int* sRow, const int* sTap,
@@ -105,11 +88,11 @@ __device__ __forceinline__ void ring_main(const ConvKArgs& P, const ctseg_conv_c
     for (int j = 0; j < NA; ++j) {
       const bool ok = ((vmask[j] >> (dslot & 31)) & 1u) != 0;
       const int vo = ok ? rowoff[j] + tb : (int)0x80000000;
-      llvm_amdgcn_raw_buffer_load_lds(rsA, (lds_u32_ptr)(dst + j * NW * 16 * RB), 16, vo, 0, 0, 0);
+      raw_buffer_load_lds(rsA, (lds_u32_ptr)(dst + j * NW * 16 * RB), 16, vo, 0, 0, 0);
     }
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-      llvm_amdgcn_raw_buffer_load_lds(rsB, (lds_u32_ptr)(dst + BOFF + j * NW * 16 * RB), 16, woff[j], 0, 0, 0);
+      raw_buffer_load_lds(rsB, (lds_u32_ptr)(dst + BOFF + j * NW * 16 * RB), 16, woff[j], 0, 0, 0);
       woff[j] += C::KS * 2;
     }
     dci += C::KS;

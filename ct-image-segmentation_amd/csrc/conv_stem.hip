@@ -24,11 +24,6 @@ constexpr int S_DW = S_PZ / 2, S_NDW = S_IX * S_IY * S_DW;          // 1377 dwor
 constexpr int S_J = (S_NDW + 255) / 256;                           // 6 staging slots per thread
 constexpr int S_SHIFT = 2;                                         // byte offset of patch element (0,0,0) inside the image
 
-__device__ __forceinline__ void stem_patch_voxel(int r16, int& dy, int& z) {
-  dy = (0xEF80u >> r16) & 1;
-  z = (int)((0x2104765437653210ull >> (4 * r16)) & 7ull);
-}
-
 struct StemGeom {
   int tiles, tyn, tzn;
 };
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(const ConvKArgs P, i
   StemStage stg;
   stg.init(tid, P.Yi, P.Zi);
   int pdy, pz;
-  stem_patch_voxel(r16, pdy, pz);
+  patch_voxel(r16, pdy, pz);
   int toff[8], abase[4], ovox[4];
 #pragma unroll
   for (int k = 0; k < 8; ++k) toff[k] = (8 * q4 + k < 27) ? stem_tap_off(8 * q4 + k) * 2 : -1;
@@ -310,7 +305,6 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(const StemWgradArg
   constexpr int DBYTES = CT * DPL, DCH = 256 * CT * 2, JD = DCH / 256;
   constexpr int BUF = S_INB + DBYTES;
   typedef __attribute__((ext_vector_type(8))) short s16x8;
-  typedef s16x4 __attribute__((address_space(3)))* lds_s16x4;
   static_assert(!DYN || ((CT == 2 || CT == 4) && JD % 2 == 0), "DYN: a power-of-two chunk count that divides the thread count");
   constexpr int DYNC = 8 * CT;                         // channels of the norm (the upper half of the columns)
   constexpr int TABB = DYN ? S_DYN_MAXN * DYNC * 16 : 0;

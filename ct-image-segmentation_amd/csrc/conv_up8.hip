@@ -43,28 +43,6 @@ constexpr int U8_STAGE = U8_ST * U8_TAPB, U8_SLOTS = 5, U8_RING = U8_SLOTS * U8_
 constexpr int U8_TOTAL = 2 * U8_HBUF + U8_RING + 8 * 2 * U8_CN * 4 + 64 * 4;
 static_assert(U8_TOTAL <= 160 * 1024, "LDS");
 
-typedef int32_t u8i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t __attribute__((address_space(3)))* u8_lds_u32_ptr;
-__device__ void u8_raw_buffer_load_lds(u8i32x4 rsrc, u8_lds_u32_ptr lds, int size, int voffset, int soffset, int offset,
-                                       int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-
-__device__ __forceinline__ u8i32x4 u8_make_rsrc(const void* p, uint32_t bytes) {
-  struct __attribute__((packed)) { const void* ptr; uint32_t range; uint32_t config; } r{p, bytes, 0x00020000u};
-  u8i32x4 v = __builtin_bit_cast(u8i32x4, r);
-  v[0] = __builtin_amdgcn_readfirstlane(v[0]);
-  v[1] = __builtin_amdgcn_readfirstlane(v[1]);
-  v[2] = __builtin_amdgcn_readfirstlane(v[2]);
-  v[3] = __builtin_amdgcn_readfirstlane(v[3]);
-  return v;
-}
-
-// tap index of shift delta inside parity class c in the host's order (conv_up_halo.hip's up_tap_index; checked by conv_up8_eligible)
-constexpr int u8_tap_index(int c, int delta) {
-  const int px = (c >> 2) & 1, py = (c >> 1) & 1, pz = c & 1, dx = (delta >> 2) & 1, dy = (delta >> 1) & 1, dz = delta & 1;
-  if (dx > px || dy > py || dz > pz) return -1;
-  const int ix = px ? 1 - dx : 0, iy = py ? 1 - dy : 0, iz = pz ? 1 - dz : 0;
-  return (ix * (1 + py) + iy) * (1 + pz) + iz;
-}
 // class groups and their (class, tap) pairs in delta-major order: position -> delta / class slot (index into the group)
 constexpr int u8_ncls(int grp) { return grp == 0 ? 3 : 5; }
 constexpr int u8_gclass(int grp, int i) { return grp == 0 ? (i == 0 ? 0 : i == 1 ? 3 : 7) : (i == 0 ? 1 : i == 1 ? 2 : i == 2 ? 4 : i == 3 ? 5 : 6); }
@@ -89,11 +67,6 @@ struct Up8Geom {
   int gxs;                   // spatial workgroups: the grid is 2 * gxs, workgroup L takes class group L / gxs
 };
 
-__device__ __forceinline__ void u8_patch_voxel(int r16, int& db, int& c) {
-  db = (0xEF80u >> r16) & 1;
-  c = (int)((0x2104765437653210ull >> (4 * r16)) & 7ull);
-}
-
 // ZXY: the tile axes (a, b, c) run along the volume axes (z, x, y) instead of (x, y, z) — compile time, so that the halo offset of a
 // shift is an instruction immediate; GRP: the class group.  (The first version of this kernel spent 165 non-MFMA instructions per
 // stage and wave around 36 MFMAs — 64-bit source addresses of the DMA pieces, bounds tests per chunk, operand address adds.)
@@ -114,7 +87,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
   if (tid < 16) {
     int wo = 0, kp = 0;
     if (tid < NPOS) {
-      const int c = u8_gclass(GRP, u8_pos_find(GRP, tid, 1)), ti = u8_tap_index(c, u8_pos_find(GRP, tid, 0));
+      const int c = u8_gclass(GRP, u8_pos_find(GRP, tid, 1)), ti = up_tap_index(c, u8_pos_find(GRP, tid, 0));
       wo = (int)(P.cls[c].w_off + (int64_t)ti * P.Cg);
       kp = P.cls[c].kpad;
     }
@@ -142,12 +115,12 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
   };
   // per tile: the sample's descriptor, the byte offset of the tile origin and the three per-lane offsets (out of range where the halo
   // voxel lies outside the volume, or there is no such tile); per chunk only the scalar offset moves
-  u8i32x4 h_rs = u8_make_rsrc(P.in, (uint32_t)G.in_sample_bytes);
+  i32x4 h_rs = make_rsrc(P.in, (uint32_t)G.in_sample_bytes);
   int h_soff = 0, h_v[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
   auto halo_tile = [&](int t, bool live) {
     int n, a0, b0, c0;
     tile_origin(live ? t : 0, n, a0, b0, c0);
-    h_rs = u8_make_rsrc(P.in + (int64_t)n * G.in_sample_bytes, (uint32_t)G.in_sample_bytes);
+    h_rs = make_rsrc(P.in + (int64_t)n * G.in_sample_bytes, (uint32_t)G.in_sample_bytes);
     h_soff = (a0 * G.ia + b0 * G.ib + c0 * G.ic) * P.g_ld * 2;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -160,7 +133,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
     for (int r = 0; r < 3; ++r) {
       const int base = ((r == 2 && wave == 7) ? 512 : r * 512) + wave * 64;
       if (U8_ABL & 128) continue;
-      u8_raw_buffer_load_lds(h_rs, (u8_lds_u32_ptr)(sH + buf * U8_HBUF + base * 16), 16, h_v[r], h_soff + kc * 64, 0, 0);
+      raw_buffer_load_lds(h_rs, (lds_u32_ptr)(sH + buf * U8_HBUF + base * 16), 16, h_v[r], h_soff + kc * 64, 0, 0);
     }
   };
 
@@ -172,7 +145,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
   // this is the conflict-free one — 116 TB/s of ds_read_b128 over the chip, as the linear pattern; ^ ((row >> 2) & 3), ^ (row & 3) or
   // none: 75-77 TB/s.  The first layout used (row >> 2): 47 % of its LDS cycles were bank conflicts, all on the weight fragments.)
   const int w_row = (tid & 255) >> 2, w_src = ((tid & 3) ^ ((w_row >> 1) & 3)) * 8;
-  const u8i32x4 w_rs = u8_make_rsrc(P.w, 0x7fffffffu);
+  const i32x4 w_rs = make_rsrc(P.w, 0x7fffffffu);
   __syncthreads();                                   // tables visible
   int w_v[U8_NS][3];
 #pragma unroll
@@ -189,13 +162,13 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
     for (int g = 0; g < 3; ++g) {
       const int ge = (g == 2 && wave >= 4) ? 1 : g;
       if (U8_ABL & 128) continue;
-      u8_raw_buffer_load_lds(w_rs, (u8_lds_u32_ptr)(sW + slot * U8_STAGE + (wave * 64 + ge * 512) * 16), 16, w_v[s][g], kc * 64, 0, 0);
+      raw_buffer_load_lds(w_rs, (lds_u32_ptr)(sW + slot * U8_STAGE + (wave * 64 + ge * 512) * 16), 16, w_v[s][g], kc * 64, 0, 0);
     }
   };
 
   // ---- per-lane constants -----------------------------------------------------------------------------------------------------
   int pdb, pc;
-  u8_patch_voxel(r16, pdb, pc);
+  patch_voxel(r16, pdb, pc);
   const int trip = wave >> 1, ch = wave & 1;                // row-tile triple, column half
   int abase[3], va[3], vb[3];
 #pragma unroll
@@ -312,7 +285,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
     aoff[rt] = (vox * P.add_ld + ch * 32 + 4 * q4) * ASZ;
   }
   auto epilogue = [&](int n, int a0, int b0, int c0) {
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(P.out + (int64_t)n * G.out_sample_bytes, 0, G.out_sample_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ors = buffer_rsrc(P.out + (int64_t)n * G.out_sample_bytes, G.out_sample_bytes);
     bool rv[3];
 #pragma unroll
     for (int rt = 0; rt < 3; ++rt) rv[rt] = (a0 + va[rt] < G.da) && (b0 + vb[rt] < G.db) && (c0 + pc < G.dc);
@@ -324,7 +297,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
       // so their round trips overlap instead of following one another
       f32x4 ad[3][2];
       if (P.add != nullptr) {
-        const __amdgpu_buffer_rsrc_t ars = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.add) + (int64_t)n * G.add_sample_bytes, 0, G.add_sample_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ars = buffer_rsrc(P.add + (int64_t)n * G.add_sample_bytes, G.add_sample_bytes);
         const int asoff = cb * P.add_ld * ASZ;
 #pragma unroll
         for (int rt = 0; rt < 3; ++rt)
@@ -365,18 +338,9 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
     }
   };
 
-  // tile sequence: each XCD owns a contiguous range of tiles (neighbouring halos share that XCD's L2); both class groups walk the
-  // same sequence (workgroups sid and gxs + sid sit on the same XCD when gxs is a multiple of 8: the second reads the halo from L2)
-  const int GX = G.gxs;
-  int first, stride, last;
-  if ((GX & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = sid & 7;
-    first = xcd * chunk + (sid >> 3);
-    stride = GX >> 3;
-    last = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  } else {
-    first = sid; stride = GX; last = total_tiles;
-  }
+  // both class groups walk the same tile sequence (workgroups sid and gxs + sid sit on the same XCD when gxs is a multiple of 8: the
+  // second reads the halo from L2)
+  const auto [first, stride, last] = xcd_tile_seq([=] { return sid; }, G.gxs, total_tiles);
 
   using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
   using N9 = std::integral_constant<int, 9>; using N12 = std::integral_constant<int, 12>;
@@ -485,7 +449,7 @@ bool conv_up8_eligible(const ConvKArgs& a, int dtype, int nclass) {
     taps += k.ntaps;
     if (k.ox != ((c >> 2) & 1) || k.oy != ((c >> 1) & 1) || k.oz != (c & 1)) return false;
     for (int dl = 0; dl < 8; ++dl) {       // the delta-major schedule addresses a class's taps by (dx,dy,dz), in the host's order
-      const int tp = u8_tap_index(c, dl);
+      const int tp = up_tap_index(c, dl);
       if (tp < 0) continue;
       if (tp >= k.ntaps) return false;
       const int t = k.taps[tp];

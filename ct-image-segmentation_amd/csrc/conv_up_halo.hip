@@ -24,21 +24,6 @@ namespace ctseg {
 constexpr int U_HY = 10, U_HZ = 10, U_HV = 600, U_PLANE = U_HV * 16;
 constexpr int U_FV = 5 * 9 * 9;   // voxels actually filled
 
-__device__ __forceinline__ void up_patch_voxel(int r16, int& dy, int& z) {
-  dy = (0xEF80u >> r16) & 1;
-  z = (int)((0x2104765437653210ull >> (4 * r16)) & 7ull);
-}
-
-// tap index of shift delta = (dx,dy,dz) in {0,1}^3 inside parity class c = px*4 + py*2 + pz, in the order the host lists a class's taps
-// (capstone_amd/engine.py classes_up: x outermost; a parity-1 axis lists offset +1 before 0) — checked by conv_up_eligible; -1: the
-// class has no such tap
-constexpr int up_tap_index(int c, int delta) {
-  const int px = (c >> 2) & 1, py = (c >> 1) & 1, pz = c & 1, dx = (delta >> 2) & 1, dy = (delta >> 1) & 1, dz = delta & 1;
-  if (dx > px || dy > py || dz > pz) return -1;
-  const int ix = px ? 1 - dx : 0, iy = py ? 1 - dy : 0, iz = pz ? 1 - dz : 0;
-  return (ix * (1 + py) + iy) * (1 + pz) + iz;
-}
-
 template <int VB> struct UpCfg {
   static constexpr int NPL = VB / 16;
   static constexpr int HALO = NPL * U_PLANE;
@@ -114,7 +99,7 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
   auto gload = [&](int t) {
     int n, x0, y0, z0;
     tile_origin(t, n, x0, y0, z0);
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.in) + (int64_t)n * in_sample_bytes, 0, in_sample_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(P.in + (int64_t)n * in_sample_bytes, in_sample_bytes);
     const int soff = ((x0 * P.Yi + y0) * P.Zi + z0) * P.g_ld * 2;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
@@ -130,7 +115,7 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
   };
 
   int pdy, pz;
-  up_patch_voxel(r16, pdy, pz);
+  patch_voxel(r16, pdy, pz);
   int abase[4], ovox[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {

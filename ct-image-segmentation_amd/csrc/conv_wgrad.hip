@@ -34,20 +34,6 @@ struct WgradKArgs {
 __device__ __attribute__((aligned(16))) unsigned short g_wg_zero16[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 __device__ __attribute__((aligned(16))) unsigned short g_wg_one16[8] = {0x3f80, 0, 0, 0, 0, 0, 0, 0};   // bf16 1.0 on channel 0
 
-typedef int32_t wg_i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t __attribute__((address_space(3)))* wg_lds_u32_ptr;
-__device__ void wg_raw_buffer_load_lds(wg_i32x4 rsrc, wg_lds_u32_ptr lds, int size, int voffset, int soffset, int offset,
-                                       int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-__device__ __forceinline__ wg_i32x4 wg_make_rsrc(const void* p, uint32_t bytes) {
-  struct __attribute__((packed)) { const void* ptr; uint32_t range; uint32_t config; } r{p, bytes, 0x00020000u};
-  wg_i32x4 v = __builtin_bit_cast(wg_i32x4, r);
-  v[0] = __builtin_amdgcn_readfirstlane(v[0]);
-  v[1] = __builtin_amdgcn_readfirstlane(v[1]);
-  v[2] = __builtin_amdgcn_readfirstlane(v[2]);
-  v[3] = __builtin_amdgcn_readfirstlane(v[3]);
-  return v;
-}
-
 template <typename T, int BNW, bool SMALLC> struct WgradCfg {
   static constexpr int SZ = TT<T>::SZ;
   static constexpr bool GLDS = SZ == 2 && !SMALLC && BNW >= 64;
@@ -257,8 +243,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
   // a voxel outside the volume, a row past the split or a column past d_valid is an out-of-range offset (the hardware delivers
   // zeros) -- no zero page, no 64-bit pointer arithmetic, one select per chunk.
   const bool use_buf = GLDS && !P.addr64 && !(kblock * 128 <= ktot && ktot < kblock * 128 + 128);
-  const wg_i32x4 rsA = wg_make_rsrc(inb, (uint32_t)((int64_t)P.Xi * P.Yi * P.Zi * gl));
-  const wg_i32x4 rsD = wg_make_rsrc(dstage, (uint32_t)((int64_t)(mend > mstart ? mend - mstart : 0) * P.d_ld * SZ));
+  const i32x4 rsA = make_rsrc(inb, (uint32_t)((int64_t)P.Xi * P.Yi * P.Zi * gl));
+  const i32x4 rsD = make_rsrc(dstage, (uint32_t)((int64_t)(mend > mstart ? mend - mstart : 0) * P.d_ld * SZ));
   int doffb = dcol_ok ? doff : (int)0x80000000;          // (stays out of range: rows * row bytes < 2^31)
   auto gload_lds_buf = [&](int s, int buf) {
     const int mb = mstart + s * 32;
@@ -278,10 +264,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
       cy[j] -= carry_y ? yrs : 0;
       cx[j] += sxs + (carry_y ? P.sin : 0);
       aoff[j] += o_step + (carry_z ? o_cz : 0) + (carry_y ? o_cy : 0);
-      wg_raw_buffer_load_lds(rsA, (wg_lds_u32_ptr)(a + j * (ARS * PA)), 16, vo, 0, 0, 0);
+      raw_buffer_load_lds(rsA, (lds_u32_ptr)(a + j * (ARS * PA)), 16, vo, 0, 0, 0);
     }
 #pragma unroll
-    for (int j = 0; j < DJ; ++j) wg_raw_buffer_load_lds(rsD, (wg_lds_u32_ptr)(d + j * 4096), 16, doffb + j * d_jstep, 0, 0, 0);
+    for (int j = 0; j < DJ; ++j) raw_buffer_load_lds(rsD, (lds_u32_ptr)(d + j * 4096), 16, doffb + j * d_jstep, 0, 0, 0);
     doffb += d_step;
   };
   auto sstore = [&](int buf) {

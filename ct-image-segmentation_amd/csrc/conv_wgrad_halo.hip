@@ -49,7 +49,6 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_halo_kernel(const WgradHal
   constexpr int XCH = WH_HV * (VB / 16), DCH = WH_TV * (DBY / 16);
   constexpr int JX = (XCH + NTH - 1) / NTH, JD = (DCH + NTH - 1) / NTH;
   typedef __attribute__((ext_vector_type(8))) short s16x8;
-  typedef s16x4 __attribute__((address_space(3)))* lds_s16x4;
 
   // ONE staging buffer: the next tile's operands wait in registers (gload) while this tile is consumed and are written after
   // the barrier that ends it.  Half the LDS of a double buffer -> twice the workgroups per CU, whose phases interleave.
@@ -257,7 +256,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   constexpr int XBYTES = WH_HV * 32, DBYTES = WH_TV * 32, BUF = XBYTES + DBYTES;
   constexpr int XN = WH_HV * NPX, DN = WH_TV * NPD, JX = (XN + 255) / 256, JD = (DN + 255) / 256;
   typedef __attribute__((ext_vector_type(8))) short s16x8;
-  typedef s16x4 __attribute__((address_space(3)))* lds_s16x4;
   __shared__ __attribute__((aligned(16))) char smem[BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -297,10 +295,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int x0 = tx * 4, y0 = ty * 8, z0 = tz * 8;
     const uint32_t xm = ~(range_mask(1 - x0, P.X - x0, 6) | (range_mask(1 - y0, P.Y - y0, 10) << 6) | (range_mask(1 - z0, P.Z - z0, 10) << 16));
     const uint32_t dm = ~(range_mask(0, P.X - x0 - 1, 4) | (range_mask(0, P.Y - y0 - 1, 8) << 4) | (range_mask(0, P.Z - z0 - 1, 8) << 12));
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.in) + (int64_t)n * x_sample_bytes - bias_bytes, 0,
-                                                                         x_sample_bytes + bias_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.dy) + (int64_t)n * d_sample_bytes, 0, d_sample_bytes,
-                                                                         0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(P.in + (int64_t)n * x_sample_bytes - bias_bytes, x_sample_bytes + bias_bytes);
+    const __amdgpu_buffer_rsrc_t dr = buffer_rsrc(P.dy + (int64_t)n * d_sample_bytes, d_sample_bytes);
     const int xs = ((x0 * P.Y + y0) * P.Z + z0) * P.g_ld * 2, dsf = ((x0 * P.Y + y0) * P.Z + z0) * P.d_ld * 2;
 #pragma unroll
     for (int j = 0; j < JX; ++j)
@@ -418,7 +414,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   constexpr int XBYTES = WH_HV * 32, DBYTES = WH_TV * 32, BUF = XBYTES + DBYTES;
   constexpr int XN = WH_HV * NPX, DN = WH_TV * NPD, JX = (XN + 511) / 512, JD = (DN + 511) / 512;
   typedef __attribute__((ext_vector_type(8))) short s16x8;
-  typedef s16x4 __attribute__((address_space(3)))* lds_s16x4;
   __shared__ __attribute__((aligned(16))) char smem[BUF + WH_NRM_MAXN * 128];
   float* const sPar = reinterpret_cast<float*>(smem + BUF);     // per sample: 4 channel quads x (mean x 4, rstd x 4)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -459,10 +454,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int x0 = tx * 4, y0 = ty * 8, z0 = tz * 8;
     const uint32_t xm = ~(range_mask(1 - x0, P.X - x0, 6) | (range_mask(1 - y0, P.Y - y0, 10) << 6) | (range_mask(1 - z0, P.Z - z0, 10) << 16));
     const uint32_t dm = ~(range_mask(0, P.X - x0 - 1, 4) | (range_mask(0, P.Y - y0 - 1, 8) << 4) | (range_mask(0, P.Z - z0 - 1, 8) << 12));
-    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.in) + (int64_t)n * x_sample_bytes - bias_bytes, 0,
-                                                                         x_sample_bytes + bias_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t dr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(P.dy) + (int64_t)n * d_sample_bytes, 0, d_sample_bytes,
-                                                                         0x00020000);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(P.in + (int64_t)n * x_sample_bytes - bias_bytes, x_sample_bytes + bias_bytes);
+    const __amdgpu_buffer_rsrc_t dr = buffer_rsrc(P.dy + (int64_t)n * d_sample_bytes, d_sample_bytes);
     const int xs = ((x0 * P.Y + y0) * P.Z + z0) * P.g_ld * 2, dsf = ((x0 * P.Y + y0) * P.Z + z0) * P.d_ld * 2;
 #pragma unroll
     for (int j = 0; j < JX; ++j)

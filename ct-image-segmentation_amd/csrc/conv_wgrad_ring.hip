@@ -43,20 +43,6 @@ struct WRingKArgs {
   int taps[CTSEG_MAX_TAPS];
 };
 
-typedef int32_t wr_i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t __attribute__((address_space(3)))* wr_lds_u32_ptr;
-__device__ void wr_raw_buffer_load_lds(wr_i32x4 rsrc, wr_lds_u32_ptr lds, int size, int voffset, int soffset, int offset,
-                                       int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-__device__ __forceinline__ wr_i32x4 wr_make_rsrc(const void* p, uint32_t bytes) {
-  struct __attribute__((packed)) { const void* ptr; uint32_t range; uint32_t config; } r{p, bytes, 0x00020000u};
-  wr_i32x4 v = __builtin_bit_cast(wr_i32x4, r);
-  v[0] = __builtin_amdgcn_readfirstlane(v[0]);
-  v[1] = __builtin_amdgcn_readfirstlane(v[1]);
-  v[2] = __builtin_amdgcn_readfirstlane(v[2]);
-  v[3] = __builtin_amdgcn_readfirstlane(v[3]);
-  return v;
-}
-
 // Two transposed LDS reads = one bf16 MFMA operand (rows r and r + 16 of the stage).
 // hipcc waits for EVERY outstanding direct-to-LDS load (vmcnt(0)) in front of a __builtin_amdgcn_ds_read_tr16_b64 (the builtin carries
 // no memory operand it could tell apart from the ring slots being filled), which would empty the ring every step.  The reads are
@@ -167,9 +153,9 @@ __device__ __forceinline__ void wring_main(const WRingKArgs& P, char* smem, f32x
     return e;
   };
   const char* inb = P.in + (int64_t)n * P.Xi * P.Yi * P.Zi * gl;
-  const wr_i32x4 rsA = wr_make_rsrc(inb, (uint32_t)((int64_t)P.Xi * P.Yi * P.Zi * gl));
+  const i32x4 rsA = make_rsrc(inb, (uint32_t)((int64_t)P.Xi * P.Yi * P.Zi * gl));
   const char* dstage = P.dy + ((int64_t)n * P.rows + mstart) * P.d_ld * 2;
-  const wr_i32x4 rsD = wr_make_rsrc(dstage, (uint32_t)((int64_t)(mend > mstart ? mend - mstart : 0) * P.d_ld * 2));
+  const i32x4 rsD = make_rsrc(dstage, (uint32_t)((int64_t)(mend > mstart ? mend - mstart : 0) * P.d_ld * 2));
   // dy: panel p, this thread's row and chunk; a column past d_valid starts (and stays) out of range
   int doff[ND > 0 ? ND : 1];
 #pragma unroll
@@ -192,12 +178,12 @@ __device__ __forceinline__ void wring_main(const WRingKArgs& P, char* smem, f32x
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
       const int vo = ((int)e[0] + tapoff[p]) | __builtin_amdgcn_sbfe((int)e[1], tapbit[p], 1);     // outside the volume: 0xffffffff -> zeros
-      if constexpr ((WR_ABL & 4) == 0) wr_raw_buffer_load_lds(rsA, (wr_lds_u32_ptr)(dst + p * 8192), 16, vo, 0, 0, 0);
+      if constexpr ((WR_ABL & 4) == 0) raw_buffer_load_lds(rsA, (lds_u32_ptr)(dst + p * 8192), 16, vo, 0, 0, 0);
       else asm volatile("" ::"v"(vo));
     }
 #pragma unroll
     for (int p = 0; p < ND; ++p) {
-      if constexpr ((WR_ABL & 8) == 0) wr_raw_buffer_load_lds(rsD, (wr_lds_u32_ptr)(dst + DOFF + p * 8192), 16, doff[p], 0, 0, 0);
+      if constexpr ((WR_ABL & 8) == 0) raw_buffer_load_lds(rsD, (lds_u32_ptr)(dst + DOFF + p * 8192), 16, doff[p], 0, 0, 0);
       doff[p] += d_step;
     }
   };

@@ -23,21 +23,6 @@
 
 namespace ctseg {
 
-typedef int32_t wu_i32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t __attribute__((address_space(3)))* wu_lds_ptr;
-__device__ void wu_buffer_load_lds(wu_i32x4 rsrc, wu_lds_ptr lds, int size, int voffset, int soffset, int offset,
-                                   int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
-
-__device__ __forceinline__ wu_i32x4 wu_make_rsrc(const void* p, uint32_t bytes) {
-  struct __attribute__((packed)) { const void* ptr; uint32_t range; uint32_t config; } r{p, bytes, 0x00020000u};
-  wu_i32x4 v = __builtin_bit_cast(wu_i32x4, r);
-  v[0] = __builtin_amdgcn_readfirstlane(v[0]);
-  v[1] = __builtin_amdgcn_readfirstlane(v[1]);
-  v[2] = __builtin_amdgcn_readfirstlane(v[2]);
-  v[3] = __builtin_amdgcn_readfirstlane(v[3]);
-  return v;
-}
-
 struct WgradUpArgs {
   const char* fine;     // dOut [N][2X][2Y][2Z][16] bf16
   const char* coarse;   // x    [N][X][Y][Z][64]    bf16
@@ -67,7 +52,6 @@ template <int GW>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs P, int total_tiles) {
   constexpr int FS = 32, PB = GW == 16 ? 16 : 12, GB = GW * 2;     // LDS voxel slot, bytes per DMA piece, bytes of a row in memory
   typedef __attribute__((ext_vector_type(8))) short s16x8;
-  typedef s16x4 __attribute__((address_space(3)))* lds_s16x4;
   __shared__ __attribute__((aligned(16))) char smem[WU_FBYTES + WU_CBYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -105,14 +89,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs
     const int ty = r % P.tyn, tx = r / P.tyn;
     const int x0 = tx * WU_TX, y0 = ty * WU_TY, z0 = tz * WU_TZ;
     const int fm = (x0 == 0 ? 1 : 0) | (y0 == 0 ? 2 : 0) | (z0 == 0 ? 4 : 0) | 8;
-    const wu_i32x4 fr = wu_make_rsrc(P.fine + (int64_t)n * P.fine_sample_bytes - fbias, (uint32_t)(P.fine_sample_bytes + fbias));
+    const i32x4 fr = make_rsrc(P.fine + (int64_t)n * P.fine_sample_bytes - fbias, (uint32_t)(P.fine_sample_bytes + fbias));
     const int fso = ((2 * x0 * Yf + 2 * y0) * Zf + 2 * z0) * GB;
 #pragma unroll
     for (int j = 0; j < WU_FJ; ++j) {
       const int vo = (fpk[j] & fm) == 0 ? (int)((unsigned)fpk[j] >> 4 << 2) : (int)0x80000000;
-      wu_buffer_load_lds(fr, (wu_lds_ptr)(smem + (wave + 4 * j) * 1024), PB, vo, fso, 0, 0);
+      raw_buffer_load_lds(fr, (lds_u32_ptr)(smem + (wave + 4 * j) * 1024), PB, vo, fso, 0, 0);
     }
-    const wu_i32x4 cr = wu_make_rsrc(P.coarse + (int64_t)n * P.coarse_sample_bytes, (uint32_t)P.coarse_sample_bytes);
+    const i32x4 cr = make_rsrc(P.coarse + (int64_t)n * P.coarse_sample_bytes, (uint32_t)P.coarse_sample_bytes);
     const uint32_t cnot = ~(range_mask(P.Y - y0 - 1, 4) | (range_mask(P.Z - z0 - 1, 8) << 4));
     const int cvo = (chot & cnot) == 0u ? coff : (int)0x80000000;
     const int cso = ((x0 * P.Y + y0) * P.Z + z0) * 128;
@@ -120,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs
     for (int j = 0; j < WU_CJ; ++j) {
       const int i = wave + 4 * j, nb = i >> 2, p = i & 3;
       const int vo = (x0 + p < P.X) ? cvo : (int)0x80000000;
-      wu_buffer_load_lds(cr, (wu_lds_ptr)(smem + WU_FBYTES + i * 1024), 16, vo, cso + p * P.Y * P.Z * 128 + nb * 32, 0, 0);
+      raw_buffer_load_lds(cr, (lds_u32_ptr)(smem + WU_FBYTES + i * 1024), 16, vo, cso + p * P.Y * P.Z * 128 + nb * 32, 0, 0);
     }
   };
 

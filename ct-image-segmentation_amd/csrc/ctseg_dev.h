@@ -37,6 +37,33 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(4))) int32_t i32x4;
+typedef s16x4 __attribute__((address_space(3)))* lds_s16x4;     // LDS operand of __builtin_amdgcn_ds_read_tr16_b64_v4i16
+typedef uint32_t __attribute__((address_space(3)))* lds_u32_ptr;
+
+// Word 3 of every buffer descriptor here: DATA_FORMAT = 32 (bits 18:15 = 4), untyped dword access, no swizzle, no index stride
+constexpr uint32_t BUF_RSRC_CONFIG = 0x00020000u;
+
+// Descriptor of [base, base + bytes) for the __builtin_amdgcn_raw_buffer_* loads and stores: an offset past the range loads zeros
+// and drops a store.  base and bytes must be wave-uniform.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* base, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, BUF_RSRC_CONFIG);
+}
+
+// buffer_load_dword* ... lds (direct-to-LDS DMA): per-lane 32-bit byte offset into a range-checked buffer; an offset past the range
+// delivers zeros (the padding voxels of a tap), so a staging loop needs no branch and no zero page.  Its descriptor is the i32x4
+// of make_rsrc, its four words read from the first lane so that the compiler holds them in SGPRs.
+__device__ void raw_buffer_load_lds(i32x4 rsrc, lds_u32_ptr lds, int size, int voffset, int soffset, int offset,
+                                    int aux) __asm("llvm.amdgcn.raw.buffer.load.lds");
+__device__ __forceinline__ i32x4 make_rsrc(const void* p, uint32_t bytes) {
+  struct __attribute__((packed)) { const void* ptr; uint32_t range; uint32_t config; } r{p, bytes, BUF_RSRC_CONFIG};
+  i32x4 v = __builtin_bit_cast(i32x4, r);
+  v[0] = __builtin_amdgcn_readfirstlane(v[0]);
+  v[1] = __builtin_amdgcn_readfirstlane(v[1]);
+  v[2] = __builtin_amdgcn_readfirstlane(v[2]);
+  v[3] = __builtin_amdgcn_readfirstlane(v[3]);
+  return v;
+}
 
 struct BF16 {};  // storage tag: 16-bit brain float kept as raw ushort
 struct F16 {};   // storage tag: IEEE half kept as raw ushort (forward / inference passes only)
