@@ -143,6 +143,14 @@ _SIGS = {
     "ctseg_instnorm_prelu_bwd_apply_colsum": (C.c_int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i64, _i32,
                                                         _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "ctseg_colsum": (C.c_int, [_i32, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp]),
+    "ctseg_batchnorm_finalize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctseg_batchnorm_eval_table": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f64, _vp, _vp]),
+    "ctseg_scale_shift_prelu_fwd": (C.c_int, [_i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i64, _i32, _vp]),
+    "ctseg_batchnorm_prelu_bwd_reduce": (C.c_int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32,
+                                                   _vp]),
+    "ctseg_batchnorm_prelu_bwd_finalize": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "ctseg_batchnorm_prelu_bwd_apply": (C.c_int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32,
+                                                  _i64, _i32, _vp, _i32, _vp, _vp]),
     "ctseg_squash_masks": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
     "ctseg_seg_loss": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "ctseg_conv_logits_ce_slots": (C.c_int, [C.POINTER(ConvDesc), _i32]),

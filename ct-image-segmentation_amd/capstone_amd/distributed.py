@@ -185,6 +185,11 @@ def attach(module, group=None, always=False):
     moments are then zeros everywhere) or after rank-local warm-up steps — and the replicas leave it bit-identical.
     Needs ``engine.ensure(device)`` (or any forward) first so the flat buffers exist."""
     eng = module.unet.engine()
+    if getattr(module.unet, "norm", "INSTANCE") == "BATCH" and dist.is_initialized() and dist.get_world_size(group) > 1:
+        # DDP broadcasts the BatchNorm buffers from rank 0 every step; the native gradient exchange moves the flat gradient only,
+        # so the running statistics of the replicas would drift apart
+        raise NotImplementedError("data-parallel training of a UNet with norm='BATCH' is not implemented (the running "
+                                  "statistics are not broadcast); use norm='INSTANCE' or a single process")
     st = eng.store
     assert st is not None, "run engine.ensure(device) (or one forward) before attach()"
     if dist.is_initialized() and dist.get_world_size(group) > 1:

@@ -221,6 +221,56 @@ class ParamStore:
         self.touch()
 
 
+class BufferStore:
+    """running statistics of the BatchNorm layers: one flat fp32 buffer ([running_mean | running_var] per layer) and one int64
+    buffer of num_batches_tracked that the kernels update through raw pointers.  The modules' buffers are views of them (as the
+    Parameters are of ParamStore.flat_p), so ``state_dict()`` shows what the kernels wrote and ``load_state_dict`` (an in-place
+    copy) feeds the next forward; anything that replaces a buffer's storage (``.to()``, ``buf.data = ...``) is copied back in by
+    Engine.ensure before the next plan runs."""
+
+    def __init__(self, norms, device):
+        self.norms = list(norms)
+        self.device = device
+        self.offsets, off = {}, 0
+        for i, m in enumerate(self.norms):
+            self.offsets[id(m)] = (off, i)
+            off += 2 * m.num_features
+        self.flat = torch.zeros(max(off, 4), dtype=torch.float32, device=device)
+        self.nbt = torch.zeros(max(len(self.norms), 1), dtype=torch.int64, device=device)
+        self.copy_in()
+
+    def _views(self, m):
+        o, i = self.offsets[id(m)]
+        C = m.num_features
+        return self.flat[o:o + C], self.flat[o + C:o + 2 * C], self.nbt[i]
+
+    def copy_in(self):
+        """module buffers -> flat buffers, then make the module buffers views again"""
+        with torch.no_grad():
+            for m in self.norms:
+                rm, rv, nb = self._views(m)
+                rm.copy_(m.running_mean.detach().reshape(-1).to(device=self.device, dtype=torch.float32))
+                rv.copy_(m.running_var.detach().reshape(-1).to(device=self.device, dtype=torch.float32))
+                nb.copy_(m.num_batches_tracked.detach().reshape(()).to(device=self.device, dtype=torch.int64))
+        self.attach()
+
+    def attach(self):
+        for m in self.norms:
+            m.running_mean.data, m.running_var.data, m.num_batches_tracked.data = self._views(m)
+
+    def attached(self):
+        for m in self.norms:
+            rm, rv, nb = self._views(m)
+            for a, b in ((m.running_mean, rm), (m.running_var, rv), (m.num_batches_tracked, nb)):
+                if a.data_ptr() != b.data_ptr() or a.device != b.device or a.dtype != b.dtype:
+                    return False
+        return True
+
+    def ptrs(self, m):
+        """(running_mean, running_var, num_batches_tracked) device pointers of one layer"""
+        return tuple(v.data_ptr() for v in self._views(m))
+
+
 # ------------------------------------------------------------------------------------------------
 # one implicit-GEMM layer = one conv module, or a fused pair sharing input and geometry
 # ------------------------------------------------------------------------------------------------
@@ -405,8 +455,8 @@ class GemmLayer:
         """ask the pass that writes the gradient ``out`` to take the backward statistics of ``norm`` (the InstanceNorm + PReLU whose
         output gradient ``out`` is, channels [col0, col0 + C) of the pass) in its epilogue; returns the tensor the statistics
         belong to (``out``, or the second half of a split output) or None when the kernel taking the pass cannot"""
-        if norm is None or os.environ.get("CTSEG_BST", "1") == "0":
-            return None       # (the library declines fp32 storage: its trajectory tests pin a summation order)
+        if norm is None or not norm.fusable or os.environ.get("CTSEG_BST", "1") == "0":
+            return None       # (the library declines fp32 storage: its trajectory tests pin a summation order; BatchNorm: per-sample only)
         y = norm.y
         tgt = out.slice(col0, y.C) if (col0 or isinstance(out, SplitAct)) else out
         if tgt.C != y.C or tgt.dims != y.dims:

@@ -90,6 +90,10 @@ def _engine_of(predictor):
     if not hasattr(net, "engine"):
         raise TypeError("sliding_window_inference runs on the MI355X engine: predictor must be a capstone_amd UNet "
                         "(or a module holding one as .unet); arbitrary callables have no device plan")
+    if net.training and getattr(net, "norm", "INSTANCE") == "BATCH":
+        # MONAI would normalise every window batch with its own statistics (and update the running ones per batch); the device
+        # batch here is regrouped (_device_plan), so those statistics would not be MONAI's either: eval-mode BatchNorm only
+        raise ValueError("sliding_window_inference on a UNet with norm='BATCH' needs the running statistics: call .eval() first")
     return net, net.engine()
 
 

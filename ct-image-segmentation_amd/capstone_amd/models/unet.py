@@ -12,6 +12,10 @@ is no eager / CPU path and a CPU tensor raises.
 Extra keyword (superset of MONAI's signature): ``precision`` = "fp32" (default: fp32 storage,
 v_mfma_f32_16x16x4_f32, reference numerics) or "bf16" (bf16 storage + MFMA, fp32 accumulate, fp32
 logits) — the reference reaches reduced precision only through Lightning's --precision flag.
+
+``norm`` = "INSTANCE" (the reference's) or "BATCH" (MONAI's ``Norm.BATCH``: ``nn.BatchNorm{2,3}d(C)`` with torch's defaults).
+BatchNorm follows ``self.training`` as torch does: ``train()`` normalises with the batch statistics and updates the running ones
+(also under ``torch.no_grad()``), ``eval()`` uses the running statistics; a gradient-enabled forward in ``eval()`` mode is refused.
 """
 from typing import Sequence
 
@@ -30,10 +34,21 @@ def _no_eager(self, *a, **k):
                           "(there is no eager fallback)")
 
 
-class Convolution(nn.Sequential):
-    """conv | transposed conv [-> InstanceNorm -> PReLU]  (children: conv, norm, act)"""
+class _BatchNorm2d(nn.BatchNorm2d):
+    forward = _no_eager
 
-    def __init__(self, dims, cin, cout, strides=1, kernel_size=3, conv_only=False, is_transposed=False):
+
+class _BatchNorm3d(nn.BatchNorm3d):
+    forward = _no_eager
+
+
+_BNORM = {2: _BatchNorm2d, 3: _BatchNorm3d}
+
+
+class Convolution(nn.Sequential):
+    """conv | transposed conv [-> InstanceNorm | BatchNorm -> PReLU]  (children: conv, norm, act)"""
+
+    def __init__(self, dims, cin, cout, strides=1, kernel_size=3, conv_only=False, is_transposed=False, norm="INSTANCE"):
         super().__init__()
         pad = (kernel_size - 1) // 2
         if is_transposed:
@@ -44,14 +59,14 @@ class Convolution(nn.Sequential):
         self.conv_only, self.is_transposed = conv_only, is_transposed
         self.cin, self.cout, self.strides, self.kernel_size = cin, cout, strides, kernel_size
         if not conv_only:
-            self.add_module("norm", _INORM[dims](cout))
+            self.add_module("norm", _BNORM[dims](cout) if norm == "BATCH" else _INORM[dims](cout))
             self.add_module("act", nn.PReLU())
 
     forward = _no_eager
 
 
 class ResidualUnit(nn.Module):
-    def __init__(self, dims, cin, cout, strides=1, kernel_size=3, subunits=2, last_conv_only=False):
+    def __init__(self, dims, cin, cout, strides=1, kernel_size=3, subunits=2, last_conv_only=False, norm="INSTANCE"):
         super().__init__()
         self.conv = nn.Sequential()
         self.residual = nn.Identity()
@@ -60,7 +75,7 @@ class ResidualUnit(nn.Module):
         c, s = cin, strides
         for su in range(subunits):
             only = last_conv_only and su == subunits - 1
-            self.conv.add_module(f"unit{su:d}", Convolution(dims, c, cout, s, kernel_size, conv_only=only))
+            self.conv.add_module(f"unit{su:d}", Convolution(dims, c, cout, s, kernel_size, conv_only=only, norm=norm))
             c, s = cout, 1
         if strides != 1 or cin != cout:
             if strides == 1:
@@ -84,8 +99,8 @@ class UNet(nn.Module):
                  strides: Sequence[int], kernel_size=3, up_kernel_size=3, num_res_units: int = 0,
                  act="PRELU", norm="INSTANCE", dropout=0, *, precision: str = "fp32"):
         super().__init__()
-        if str(act).upper() != "PRELU" or str(norm).upper() != "INSTANCE":
-            raise NotImplementedError("MI355X UNet implements the reference's act='PRELU', norm='INSTANCE' only")
+        if str(act).upper() != "PRELU" or str(norm).upper() not in ("INSTANCE", "BATCH"):
+            raise NotImplementedError("MI355X UNet implements act='PRELU' with norm='INSTANCE' (the reference's) or 'BATCH' only")
         if dropout:
             raise NotImplementedError("dropout > 0 is never used by the reference and is not implemented")
         if kernel_size != 3 or up_kernel_size != 3:
@@ -99,6 +114,7 @@ class UNet(nn.Module):
         self.channels, self.strides = list(channels), list(strides)
         self.kernel_size, self.up_kernel_size, self.num_res_units = kernel_size, up_kernel_size, num_res_units
         self.precision = precision
+        self.norm = str(norm).upper()
 
         def block(inc, outc, chans, strs, is_top):
             c, s = chans[0], strs[0]
@@ -115,14 +131,14 @@ class UNet(nn.Module):
 
     def _down(self, cin, cout, s):
         if self.num_res_units > 0:
-            return ResidualUnit(self.dimensions, cin, cout, s, self.kernel_size, self.num_res_units)
-        return Convolution(self.dimensions, cin, cout, s, self.kernel_size)
+            return ResidualUnit(self.dimensions, cin, cout, s, self.kernel_size, self.num_res_units, norm=self.norm)
+        return Convolution(self.dimensions, cin, cout, s, self.kernel_size, norm=self.norm)
 
     def _up(self, cin, cout, s, is_top):
         conv = Convolution(self.dimensions, cin, cout, s, self.up_kernel_size,
-                           conv_only=is_top and self.num_res_units == 0, is_transposed=True)
+                           conv_only=is_top and self.num_res_units == 0, is_transposed=True, norm=self.norm)
         if self.num_res_units > 0:
-            ru = ResidualUnit(self.dimensions, cout, cout, 1, self.kernel_size, 1, last_conv_only=is_top)
+            ru = ResidualUnit(self.dimensions, cout, cout, 1, self.kernel_size, 1, last_conv_only=is_top, norm=self.norm)
             conv = nn.Sequential(conv, ru)
         return conv
 

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from . import _native as nat
 from ._native import BF16, F32
-from .engine import Act, GemmLayer, Packer, ParamStore, new_act, rup
+from .engine import Act, BufferStore, GemmLayer, Packer, ParamStore, new_act, rup
 
 
 def _is_seq(m):
@@ -37,9 +37,12 @@ def _addend(out, accumulate):
 
 class _NormAct:
     """InstanceNorm + PReLU of one conv output: forward apply and the 3-kernel backward."""
+    fusable = True            # per-sample statistics, no affine: the conv passes may apply / take them on load (in_norm, bst, dyn)
+    needs_stats = True        # the producing conv pass writes (sum, sumsq) partials
 
     def __init__(self, plan, alpha):
         self.plan, self.alpha = plan, alpha
+        self.params = [alpha]
 
     def defer(self, y, stats):
         """statistics only: the apply pass is left to the consumers of ``y`` (operand normalisation on load,
@@ -119,6 +122,93 @@ class _NormAct:
         return dy_out
 
 
+def check_batch_norm(norm):
+    """the BatchNorm configurations the kernels implement (torch's defaults); anything else is refused when a plan is recorded"""
+    if norm.momentum is None:
+        raise NotImplementedError("BatchNorm with momentum=None (cumulative moving average) is not implemented")
+    if not norm.affine:
+        raise NotImplementedError("BatchNorm with affine=False is not implemented")
+    if not norm.track_running_stats or norm.running_mean is None:
+        raise NotImplementedError("BatchNorm with track_running_stats=False is not implemented")
+
+
+class _BatchNormAct:
+    """BatchNorm (affine, running statistics) + PReLU of one conv output.
+
+    Training mode (``plan.bn_train``): the conv epilogue's per-sample partials summed over the samples too
+    (ctseg_batchnorm_finalize: mean / rstd, the scale / shift table, running statistics and num_batches_tracked updated once per
+    forward), then one scale / shift + PReLU pass.  Eval mode: the table comes from the running statistics, recomputed by every
+    forward (ctseg_batchnorm_eval_table) so that load_state_dict or an optimizer step between calls is seen.  The backward is
+    reduce -> finalize (d gamma, d beta into the flat gradient) -> apply (dy, d alpha) over all N*S voxels.
+    None of the InstanceNorm fusions applies (normalisation on load, backward statistics in the dgrad epilogue, dL/dy formed on
+    load in the weight gradient): they assume per-sample statistics and no affine."""
+    fusable = False
+
+    def __init__(self, plan, norm, alpha):
+        check_batch_norm(norm)
+        self.plan, self.norm, self.alpha = plan, norm, alpha
+        self.gamma, self.beta = norm.weight, norm.bias
+        self.eps, self.momentum = float(norm.eps), float(norm.momentum)
+        self.train = plan.bn_train
+        self.needs_stats = self.train
+        self.params = [alpha, norm.weight, norm.bias]
+
+    def emit_fwd(self, y, stats, col0, res, out):
+        plan, st = self.plan, self.plan.store
+        self.y = y
+        N, S, C = y.dims[0], y.S, y.C
+        self.mr = torch.zeros((C, 2), dtype=torch.float32, device=plan.device)
+        ss = torch.zeros((C, 2), dtype=torch.float32, device=plan.device)
+        rm, rv, nbt = plan.engine.bufs.ptrs(self.norm)
+        g_p, b_p = st.p_ptr(self.gamma), st.p_ptr(self.beta)
+        if self.train:
+            plan.emit("ctseg_batchnorm_finalize", stats.partials.data_ptr(), stats.N, stats.tiles, stats.ld, col0, C,
+                      float(N * stats.count), self.eps, self.momentum, g_p, b_p, rm, rv, nbt, self.mr.data_ptr(), ss.data_ptr(),
+                      keep=(stats, self.mr, ss))
+        else:
+            plan.emit("ctseg_batchnorm_eval_table", rm, rv, g_p, b_p, C, self.eps, ss.data_ptr(), keep=(ss,))
+        if out is None:
+            out = new_act(*y.dims, C, plan.dt, plan.device)
+        plan.emit("ctseg_scale_shift_prelu_fwd", plan.dt, y.ptr(), y.ld, ss.data_ptr(), st.p_ptr(self.alpha),
+                  res.ptr() if res is not None else None, res.ld if res is not None else 0, out.ptr(), out.ld, N, S, C,
+                  keep=(y, res, out))
+        return out
+
+    def emit_bwd(self, g, dy_out=None, g_copy=None, colsum_out=None, apply=True):
+        """g = dL/d(activation) -> dL/dy; d gamma, d beta and d alpha go to the flat gradient buffer"""
+        assert self.train and apply and colsum_out is None
+        plan, st, y = self.plan, self.plan.store, self.y
+        N, S, C = y.dims[0], y.S, y.C
+        P = max(1, min(1024, math.ceil(S / 512)))          # row ranges per sample, as the InstanceNorm backward
+        if nat.is16(plan.dt):
+            P = max(P, min(math.ceil(1024 / N), math.ceil(S / 32)))
+        ld = rup(C, 4)
+        if dy_out is None:
+            dy_out = new_act(*y.dims, C, plan.dt, plan.device)
+        g_p, b_p, a_p = st.p_ptr(self.gamma), st.p_ptr(self.beta), st.p_ptr(self.alpha)
+        part = torch.zeros((N, P, 3, ld), dtype=torch.float32, device=plan.device)
+        plan.emit("ctseg_batchnorm_prelu_bwd_reduce", plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), g_p, b_p, a_p,
+                  part.data_ptr(), P, ld, N, S, C, keep=(g, part))
+        sums = torch.zeros((C, 2), dtype=torch.float32, device=plan.device)
+        da_part = torch.zeros(C, dtype=torch.float64, device=plan.device)
+        plan.emit("ctseg_batchnorm_prelu_bwd_finalize", part.data_ptr(), N, P, ld, C, float(N * S), sums.data_ptr(),
+                  st.g_ptr(self.gamma), st.g_ptr(self.beta), da_part.data_ptr(), keep=(sums, da_part))
+        plan.emit("ctseg_batchnorm_prelu_bwd_apply", plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), g_p, b_p, a_p,
+                  sums.data_ptr(), dy_out.ptr(), dy_out.ld, g_copy.ptr() if g_copy is not None else None,
+                  g_copy.ld if g_copy is not None else 0, N, S, C, da_part.data_ptr(), C, st.g_ptr(self.alpha),
+                  keep=(dy_out, g_copy))
+        return dy_out
+
+
+def _norm_act(plan, mod):
+    """the norm + PReLU node of a monai Convolution block (None: conv_only)"""
+    if mod.conv_only:
+        return None
+    if isinstance(mod.norm, nn.modules.batchnorm._BatchNorm):
+        return _BatchNormAct(plan, mod.norm, mod.act.weight)
+    return _NormAct(plan, mod.act.weight)
+
+
 class _ConvBlock:
     """monai Convolution used as a whole layer (the up path's transposed conv; plain down layers when
     num_res_units == 0)."""
@@ -127,16 +217,16 @@ class _ConvBlock:
         self.plan, self.mod = plan, mod
         self.gemm = GemmLayer(plan, name, mod.is_transposed, mod.kernel_size, mod.strides, mod.cin, [_parts(mod.conv)], cg,
                               need_dgrad)
-        self.na = None if mod.conv_only else _NormAct(plan, mod.act.weight)
-        self.params = [mod.conv.weight, mod.conv.bias] + ([] if mod.conv_only else [mod.act.weight])
+        self.na = _norm_act(plan, mod)
+        self.params = [mod.conv.weight, mod.conv.bias] + ([] if mod.conv_only else self.na.params)
 
     def emit_fwd(self, x, out=None, out_f32=False, defer_norm=False):
         self.x = x
         if self.na is None:
             y, _ = self.gemm.emit_fwd(x, out=out, out_f32=out_f32)
             return y
-        y, stats = self.gemm.emit_fwd(x, want_stats=True)
-        if defer_norm and out is None:
+        y, stats = self.gemm.emit_fwd(x, want_stats=self.na.needs_stats)
+        if defer_norm and out is None and self.na.fusable:
             return self.na.defer(y, stats)
         return self.na.emit_fwd(y, stats, 0, None, out)
 
@@ -148,7 +238,8 @@ class _ConvBlock:
         """bst: the _NormAct that consumes the returned gradient (its channels from bst_col0 on) — its backward statistics are taken
         by the pass that writes that gradient where the kernel can (GemmLayer.emit_dgrad)"""
         bias = self.mod.conv.bias
-        fuse_bias = self.na is not None and self.gemm.transposed and bias is not None
+        # (BatchNorm: the transposed conv's bias gradient is a separate ctseg_colsum over dOut)
+        fuse_bias = self.na is not None and self.na.fusable and self.gemm.transposed and bias is not None
         if self.na is None:
             dy = g
         else:   # transposed conv: its bias gradient (sum of dOut over voxels) comes out of the norm's backward pass
@@ -157,7 +248,7 @@ class _ConvBlock:
             # ... except where both consumers take 12-wide rows: the 64 -> <= 12 channel layer of the head (LDS-halo weight gradient
             # conv_wgrad_up_kernel<12> and the stride-2 halo pass staged in 8-byte pieces), a quarter fewer bytes in three passes
             gm = self.gemm
-            narrow = (os.environ.get("CTSEG_NARROW_DOUT", "1") != "0" and self.plan.dt == BF16 and gm.transposed and gm.s == 2 and
+            narrow = (os.environ.get("CTSEG_NARROW_DOUT", "1") != "0" and self.na.fusable and self.plan.dt == BF16 and gm.transposed and gm.s == 2 and
                       gm.cin == 64 and self.x.ld == 64 and getattr(gm, "cgd", 0) == 16)
             dy_wide = new_act(*y.dims, y.C, self.plan.dt, self.plan.device, ld=None if narrow else rup(y.C, nat.epc(self.plan.dt)))
             dy = self.na.emit_bwd(g, dy_out=dy_wide, colsum_out=self.plan.store.g_ptr(bias) if fuse_bias else None)
@@ -191,7 +282,7 @@ class _ResUnit:
         e = nat.epc(plan.dt)
         for i, u in enumerate(units[1:], 1):
             self.gemms.append(GemmLayer(plan, f"{name}.unit{i}", False, k, 1, mod.cout, [_parts(u.conv)], rup(mod.cout, e)))
-        self.nas = [None if u.conv_only else _NormAct(plan, u.act.weight) for u in units]
+        self.nas = [_norm_act(plan, u) for u in units]
 
     def emit_fwd(self, x, out=None, out_f32=False):
         plan, C = self.plan, self.mod.cout
@@ -211,7 +302,7 @@ class _ResUnit:
                 y, _ = g.emit_fwd(cur, out=out, add=res, out_f32=out_f32)
                 self.ys.append(y)
                 return y
-            yfull, stats = g.emit_fwd(cur, want_stats=True, split_at=C if (i == 0 and self.fused is not None) else None)
+            yfull, stats = g.emit_fwd(cur, want_stats=na.needs_stats, split_at=C if (i == 0 and self.fused is not None) else None)
             if i == 0 and self.fused is not None:
                 res, y, col0 = yfull.slice(0, C), yfull.slice(C, C), C
             else:
@@ -231,7 +322,7 @@ class _ResUnit:
         dfused = None
         # first layer of the network (no input gradient wanted): the weight-gradient pass of the fused [residual | unit0] convolution
         # reads d_res = g where it lies and forms d_y0 on load from unit0's norm — no apply pass for that norm, no copy of g
-        dyn = (self.fused is not None and not need_dx and n >= 2 and self.nas[0] is not None and
+        dyn = (self.fused is not None and not need_dx and n >= 2 and self.nas[0] is not None and self.nas[0].fusable and
                self.fused.wgrad_dyn_ok(self.x, g, self.ys[0]))
         if self.fused is not None and not dyn:
             dfused = new_act(*self.ys[0].dims, 2 * C, plan.dt, plan.device)   # [ d_res | d_y0 ]
@@ -255,11 +346,11 @@ class _ResUnit:
             if i == 0:
                 break
             gm.emit_wgrad(self.inputs[i], dy)
-            plan.grads_ready([gm.parts[0][0], gm.parts[0][1]] + ([na.alpha] if na is not None else []))
+            plan.grads_ready([gm.parts[0][0], gm.parts[0][1]] + (na.params if na is not None else []))
             d = gm.emit_dgrad(dy, bst=self.nas[i - 1])
         # ---- unit0 (+ residual branch) ----
         na0 = self.nas[0]
-        alpha0 = [na0.alpha] if na0 is not None else []
+        alpha0 = na0.params if na0 is not None else []
         if self.fused is not None:
             if dyn:
                 self.fused.emit_wgrad(self.x, g, dyn=(d, na0, dyn_sums))
@@ -396,9 +487,10 @@ def _make_side_stream(device):
 
 
 class Plan:
-    def __init__(self, engine, N, X, Y, Z, inference=False, need_input_grad=False, dt=None):
+    def __init__(self, engine, N, X, Y, Z, inference=False, need_input_grad=False, dt=None, bn_train=False):
         net = engine.net
         self.inference = inference        # forward program only: no gradient buffers, no backward program
+        self.bn_train = bn_train          # BatchNorm layers: batch statistics + running-statistics update (else: running statistics)
         self.engine, self.store, self.device = engine, engine.store, engine.device
         self.dt = engine.dt if dt is None else dt        # storage dtype of THIS plan (Engine.train_dt() for training plans)
         if self.dt == nat.F16 and not inference:
@@ -722,6 +814,7 @@ class Engine:
         self.net = net
         self.dt = nat.DT_OF_PRECISION[net.precision]
         self.store = None
+        self.bufs = None               # engine.BufferStore of the BatchNorm running statistics (norm='BATCH')
         self.device = None
         self.plans = {}
         self.last_plan = None
@@ -783,6 +876,8 @@ class Engine:
             old = self.store
             self.device = device
             self.store = ParamStore(self._param_order(), device)
+            norms = self.batch_norms()
+            self.bufs = BufferStore(norms, device) if norms else None
             self.plans = {}
             if self.reducer is not None:
                 # a data-parallel module changed device: the exchange follows the new flat gradient buffer (split points are
@@ -807,7 +902,13 @@ class Engine:
                     self.store.flat_p[o:o + p.numel()].copy_(p.detach().reshape(-1).to(device=device, dtype=torch.float32))
             self.store.attach()
             self.store.touch()       # `p.data = ...` keeps the Parameters' version counters: the packed operands are stale anyway
+        if self.bufs is not None and not self.bufs.attached():
+            self.bufs.copy_in()      # running statistics replaced by .to() / `buf.data = ...`: the kernels write the flat buffers
         return self.store
+
+    def batch_norms(self):
+        """the BatchNorm modules of the network, in module order (empty for norm='INSTANCE')"""
+        return [m for m in self.net.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
 
     def plan_for(self, x, inference=False, need_input_grad=False):
         if x.ndim != self.net.dimensions + 2 or x.shape[1] != self.net.in_channels:
@@ -816,7 +917,15 @@ class Engine:
         return self.plan_for_shape(x.device, x.shape[0], tuple(x.shape[2:]), inference, need_input_grad)
 
     def plan_for_shape(self, device, N, spatial, inference=False, need_input_grad=False):
-        """``inference`` plans hold no backward buffers; an existing training plan of the same shape is reused instead"""
+        """``inference`` plans hold no backward buffers; an existing training plan of the same shape is reused instead.
+        BatchNorm networks: the mode follows ``net.training`` (never grad mode) and is part of the key"""
+        norms = self.batch_norms()
+        for m in norms:
+            check_batch_norm(m)
+        bn_train = bool(norms) and self.net.training
+        if norms and not inference and not bn_train:
+            raise NotImplementedError("a gradient-enabled forward of a UNet with norm='BATCH' in eval() mode (backward through the "
+                                      "running statistics) is not implemented: call .train(), or run under torch.no_grad()")
         self.ensure(device)
         nd = self.net.dimensions
         sp = tuple(spatial) + ((1,) if nd == 2 else ())
@@ -828,19 +937,21 @@ class Engine:
         tdt = self.dt if inference else self.train_dt()
         if tdt != self.dt:
             key = key + ("train-bf16",)     # an fp16 model's training plans (bf16 storage) are never reused for its fp16 inference
+        if norms:
+            key = key + ("bn-train" if bn_train else "bn-eval",)
         if need_input_grad and not inference:
             plan = self.plans.get(key + ("dx",))
             if plan is None:
-                plan = self.plans[key + ("dx",)] = self._record(N, sp, False, True, tdt)
+                plan = self.plans[key + ("dx",)] = self._record(N, sp, False, True, tdt, bn_train)
             self.last_plan = plan
             return plan
         plan = self.plans.get(key) or self.plans.get(key + ("dx",)) or (self.plans.get(key + ("inference",)) if inference else None)
         if plan is None:
-            plan = self.plans[key + (("inference",) if inference else ())] = self._record(N, sp, inference, False, tdt)
+            plan = self.plans[key + (("inference",) if inference else ())] = self._record(N, sp, inference, False, tdt, bn_train)
         self.last_plan = plan
         return plan
 
-    def _record(self, N, sp, inference, need_input_grad=False, dt=None):
+    def _record(self, N, sp, inference, need_input_grad=False, dt=None, bn_train=False):
         """record a Plan; bf16 tensors of 9..12 channels (the class logits' neighbours) are laid out 12 wide when every pass
         that touches them can move such rows (ctseg_conv_narrow_ok / ctseg_wgrad_narrow_ok), 16 wide otherwise"""
         from . import engine as eng
@@ -848,12 +959,12 @@ class Engine:
         if nat.is16(dt) and os.environ.get("CTSEG_NARROW_ROWS", "1") != "0":
             eng.NARROW_ROWS[0] = True
             try:
-                return Plan(self, N, *sp, inference=inference, need_input_grad=need_input_grad, dt=dt)
+                return Plan(self, N, *sp, inference=inference, need_input_grad=need_input_grad, dt=dt, bn_train=bn_train)
             except eng.NarrowUnsupported:
                 pass
             finally:
                 eng.NARROW_ROWS[0] = False
-        return Plan(self, N, *sp, inference=inference, need_input_grad=need_input_grad, dt=dt)
+        return Plan(self, N, *sp, inference=inference, need_input_grad=need_input_grad, dt=dt, bn_train=bn_train)
 
     # ---- raw (no autograd) API used by the native training step, bench and tests ----
     def forward(self, x):

@@ -283,6 +283,36 @@ int ctseg_instnorm_prelu_bwd_apply_colsum(int32_t dtype, const void* g, int32_t 
 int ctseg_colsum(int32_t dtype, const void* x, int32_t ld, int64_t rows, int32_t C, float* partials, int32_t P, float* out,
                  void* stream);
 
+/* BatchNorm{2,3}d(affine=True, track_running_stats=True, eps, momentum) + PReLU(1 scalar), MONAI's Convolution block with
+ * norm=Norm.BATCH.  Per-channel tables are the same for every sample: mean_rstd [C][2], scale_shift [C][2], sums [C][2].
+ * Training forward: partials [N][P][2][ld] as for ctseg_instnorm_finalize, summed over samples AND rows (count = N*S) in fp64,
+ * fixed order.  Writes mean_rstd (biased variance), scale_shift = (gamma*rstd, beta - mean*gamma*rstd), updates
+ * running_mean / running_var in place ((1-m)*r + m*x, unbiased variance var*count/(count-1)) and adds 1 to *num_batches_tracked. */
+int ctseg_batchnorm_finalize(const float* partials, int32_t N, int32_t P, int32_t ld, int32_t col0, int32_t C, double count,
+                             double eps, double momentum, const float* gamma, const float* beta, float* running_mean,
+                             float* running_var, int64_t* num_batches_tracked, float* mean_rstd, float* scale_shift, void* stream);
+/* Eval forward: scale_shift = (gamma/sqrt(running_var+eps), beta - running_mean*gamma/sqrt(running_var+eps)). */
+int ctseg_batchnorm_eval_table(const float* running_mean, const float* running_var, const float* gamma, const float* beta,
+                               int32_t C, double eps, float* scale_shift, void* stream);
+/* out = prelu(y*scale_c + shift_c, alpha) [+ res]; strides and dtypes as ctseg_instnorm_prelu_fwd (CTSEG_F16 accepted). */
+int ctseg_scale_shift_prelu_fwd(int32_t dtype, const void* y, int32_t y_ld, const float* scale_shift, const float* alpha,
+                                const void* res, int32_t res_ld, void* out, int32_t out_ld, int32_t N, int64_t S, int32_t C,
+                                void* stream);
+/* Training backward with z = gamma*xhat + beta, dz = g*prelu'(z).  Pass 1: partials [N][P][3][ld] =
+ * (sum dz, sum dz*xhat, sum over z<=0 of g*z) per (sample, row range). */
+int ctseg_batchnorm_prelu_bwd_reduce(int32_t dtype, const void* g, int32_t g_ld, const void* y, int32_t y_ld,
+                                     const float* mean_rstd, const float* gamma, const float* beta, const float* alpha,
+                                     float* partials, int32_t P, int32_t ld, int32_t N, int64_t S, int32_t C, void* stream);
+/* Pass 2: dbeta[c] = sum dz, dgamma[c] = sum dz*xhat (overwritten), sums[c] = (dbeta/count, dgamma/count), da_part[c] = the
+ * channel's slope-gradient term (C doubles). */
+int ctseg_batchnorm_prelu_bwd_finalize(const float* partials, int32_t N, int32_t P, int32_t ld, int32_t C, double count,
+                                       float* sums, float* dgamma, float* dbeta, double* da_part, void* stream);
+/* Pass 3: dy = gamma*rstd*(dz - s1 - xhat*s2) [g copied to g_copy]; da_part != NULL: dalpha = fixed-order sum of da_part[0..n_da). */
+int ctseg_batchnorm_prelu_bwd_apply(int32_t dtype, const void* g, int32_t g_ld, const void* y, int32_t y_ld,
+                                    const float* mean_rstd, const float* gamma, const float* beta, const float* alpha,
+                                    const float* sums, void* dy, int32_t dy_ld, void* g_copy, int32_t g_copy_ld, int32_t N,
+                                    int64_t S, int32_t C, const double* da_part, int32_t n_da, float* dalpha, void* stream);
+
 /* _squash_masks_3D (capstone/volumetric/utils.py:4-7): masks u8 [B][K][S] -> labels u8 [B][S]
  * (+ optional int64 copy) and per-sample class histogram hist[B][K+1] (int64, must be zeroed by the caller). */
 int ctseg_squash_masks(const uint8_t* masks, int32_t B, int32_t K, int64_t S, uint8_t* labels, int64_t* labels_i64,
