@@ -63,9 +63,23 @@ struct ConvKArgs {
   BstArgs bst;
 };
 
-static inline void fill_bst(const ctseg_conv_desc* d, ConvKArgs& a) {
+// The launch arguments of a descriptor: every field copied.  A query that judges the pass without some field (the partial buffer it
+// sizes, the split output of the un-split pass) clears that field itself.
+static inline ConvKArgs conv_args(const ctseg_conv_desc* d) {
+  ConvKArgs a;
+  a.in = (const char*)d->in; a.w = (const char*)d->w; a.bias = d->bias; a.out = (char*)d->out; a.add = (const char*)d->add;
+  a.stats = d->stats;
+  a.N = d->N; a.Xi = d->Xi; a.Yi = d->Yi; a.Zi = d->Zi; a.Xr = d->Xr; a.Yr = d->Yr; a.Zr = d->Zr; a.Xo = d->Xo; a.Yo = d->Yo; a.Zo = d->Zo;
+  a.Cg = d->Cg; a.Cn = d->Cn; a.Cn_store = d->Cn_store; a.g_ld = d->g_ld; a.o_ld = d->o_ld; a.add_ld = d->add_ld;
+  a.sin = d->sin; a.sout = d->sout; a.rows = d->Xr * d->Yr * d->Zr; a.tiles = 0; a.out_f32 = d->out_f32; a.add_f32 = d->add_f32;
+  a.stats_ld = d->stats_ld; a.stats_tiles = d->stats_tiles; a.stats_tile0 = d->stats_tile0;
+  for (int c = 0; c < CTSEG_MAX_CLASSES; ++c) a.cls[c] = d->cls[c < d->nclass ? c : 0];
+  a.out2 = (char*)d->out2; a.out2_col0 = d->out2_col0; a.o2_ld = d->o2_ld;
+  a.dtype = d->dtype; a.xcd_order = 0;
+  a.in_mr = d->in_mean_rstd; a.in_alpha = d->in_alpha; a.in_C = d->in_norm_C;
   a.bst.y = (const char*)d->bst_y; a.bst.mr = d->bst_mean_rstd; a.bst.alpha = d->bst_alpha; a.bst.part = d->bst_partials;
   a.bst.y_ld = d->bst_y_ld; a.bst.C = d->bst_C; a.bst.col0 = d->bst_col0; a.bst.P = d->bst_P; a.bst.ld = d->bst_ld;
+  return a;
 }
 
 // Workgroups reach the 8 XCDs round-robin by linear id.  Tile = (L & 7) * chunk + (L >> 3) gives every XCD one contiguous
@@ -331,47 +345,54 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& P, const ctseg_co
   }
 }
 
-// LDS-halo kernel (conv_halo.hip): 3x3x3 stride-1 passes with few channels, input tile staged once for all 27 taps
-bool conv_halo_eligible(const ConvKArgs& a, int dtype, int nclass);
-int conv_halo_tiles(const ConvKArgs& a);
-int conv_halo_slots(const ConvKArgs& a, int dtype);   // InstanceNorm partial slots per sample (= workgroups)
-void launch_conv_halo(ConvKArgs& a, int dtype, hipStream_t st);
-// conv_halo_x.hip: the same passes in 16-bit storage with 16-byte-chunked rows: LDS-DMA staging, x-column fragment reuse,
-// weights in registers (taken first where eligible)
+// The forward passes, in the order select_conv_pass (conv_igemm.hip) tries them: the first whose *_eligible holds runs.  Each
+// family's *_slots is its InstanceNorm partial slots per sample (= workgroups), *_bst_slots its backward-statistics rows (0: it
+// cannot take ConvKArgs::bst).
+enum class ConvPass { HALO_X, HALO, UP, STEM, HALO_SW, DOWN_HALO, DOWN_R, UP8, GENERIC };
+
+// HALO_X (conv_halo_x.hip), tried only where HALO is eligible: the 3x3x3 stride-1 passes in 16-bit storage with 16-byte-chunked
+// (or 12-wide) rows: LDS-DMA staging, x-column fragment reuse, weights in registers
 bool conv_halo_x_eligible(const ConvKArgs& a, int dtype, int nclass);
+bool conv_halo_x_in_norm_ok(const ConvKArgs& a);   // a HALO_X pass that can normalise its operand on load
 bool conv_halo_x_stats_ok(const ConvKArgs& a);
-int conv_halo_x_bst_slots(const ConvKArgs& a);   // 0: this pass cannot take ConvKArgs::bst
+int conv_halo_x_bst_slots(const ConvKArgs& a);
 int conv_halo_x_slots(const ConvKArgs& a);
 void launch_conv_halo_x(ConvKArgs& a, hipStream_t st);
-// 8-class stride-2 "up" pass with <= 16 output channels (conv_up_halo.hip): one input tile for all parity classes
+// HALO (conv_halo.hip): 3x3x3 stride-1 passes with few channels, input tile staged once for all 27 taps
+bool conv_halo_eligible(const ConvKArgs& a, int dtype, int nclass);
+int conv_halo_tiles(const ConvKArgs& a);
+int conv_halo_slots(const ConvKArgs& a, int dtype);
+void launch_conv_halo(ConvKArgs& a, int dtype, hipStream_t st);
+// UP (conv_up_halo.hip): 8-class stride-2 "up" pass with <= 16 output channels, one input tile for all parity classes
 bool conv_up_eligible(const ConvKArgs& a, int dtype, int nclass);
 int conv_up_tiles(const ConvKArgs& a);
-int conv_up_slots(const ConvKArgs& a);   // InstanceNorm partial slots per sample (= workgroups)
+int conv_up_slots(const ConvKArgs& a);
 void launch_conv_up(ConvKArgs& a, hipStream_t st);
-// single-channel 3x3x3 stride-2 stem (conv_stem.hip)
+// STEM (conv_stem.hip): single-channel 3x3x3 stride-2 stem
 bool conv_stem_eligible(const ConvKArgs& a, int dtype, int nclass);
 int conv_stem_slots(const ConvKArgs& a);
 void launch_conv_stem(ConvKArgs& a, hipStream_t st);
-// conv_halo_sw.hip: LDS halo + streamed weights, Cg=64->Cn=64 (one class) and Cg=128->Cn=32 (8 parity classes), bf16
-bool conv_halo_x_in_norm_ok(const ConvKArgs& a, int dtype, int nclass);
+// HALO_SW (conv_halo_sw.hip): LDS halo + streamed weights, Cg=64->Cn=64 (one class) and Cg=128->Cn=32 (8 parity classes), bf16
 bool conv_halo_sw_eligible(const ConvKArgs& a, int dtype, int nclass);
 int conv_halo_sw_slots(const ConvKArgs& a);
-int conv_halo_sw_bst_slots(const ConvKArgs& a, int nclass);   // 0: this pass cannot take ConvKArgs::bst
+int conv_halo_sw_bst_slots(const ConvKArgs& a, int nclass);
 void launch_conv_halo_sw(ConvKArgs& a, int nclass, hipStream_t st);
-// conv_up8.hip: 8-class stride-2 passes with >= 128 gathered channels and 64 columns: all classes' accumulators live, K chunked
+// DOWN_HALO (conv_down_halo.hip): stride-2 3x3x3 conv with 16 gathered channels, 64 columns per workgroup, bf16
+bool conv_down_halo_eligible(const ConvKArgs& a, int dtype, int nclass);
+int conv_down_halo_slots(const ConvKArgs& a);
+int conv_down_halo_bst_slots(const ConvKArgs& a);
+void launch_conv_down_halo(ConvKArgs& a, hipStream_t st);
+// DOWN_R (conv_down_r.hip): stride-2 3x3x3 conv 32 -> 128 channels with the weights in registers
+bool conv_down_r_eligible(const ConvKArgs& a, int dtype, int nclass);
+int conv_down_r_slots(const ConvKArgs& a);
+int conv_down_r_bst_slots(const ConvKArgs& a);
+void launch_conv_down_r(ConvKArgs& a, hipStream_t st);
+// UP8 (conv_up8.hip): 8-class stride-2 passes with >= 128 gathered channels and 64 columns: all classes' accumulators live, K chunked
 bool conv_up8_eligible(const ConvKArgs& a, int dtype, int nclass);
 int conv_up8_slots(const ConvKArgs& a);
 void launch_conv_up8(ConvKArgs& a, hipStream_t st);
-// conv_down_halo.hip: stride-2 3x3x3 conv with 16 / 32 gathered channels, 64 columns per workgroup, bf16
-bool conv_down_halo_eligible(const ConvKArgs& a, int dtype, int nclass);
-int conv_down_halo_slots(const ConvKArgs& a);
-int conv_down_halo_bst_slots(const ConvKArgs& a);   // 0: this pass cannot take ConvKArgs::bst
-void launch_conv_down_halo(ConvKArgs& a, hipStream_t st);
-bool conv_down_r_eligible(const ConvKArgs& a, int dtype, int nclass);
-int conv_down_r_slots(const ConvKArgs& a);
-int conv_down_r_bst_slots(const ConvKArgs& a);   // 0: this pass cannot take ConvKArgs::bst
-void launch_conv_down_r(ConvKArgs& a, hipStream_t st);
-// conv_igemm_ring.hip: the 192 x 256 bf16 tile with a five-deep ring of 32-wide K stages (a.tiles already set for 192 rows)
+// GENERIC (conv_igemm.hip), or its 192 x 256 bf16 tile with a five-deep ring of 32-wide K stages (conv_igemm_ring.hip, a.tiles
+// already set for 192 rows)
 bool conv_ring_eligible(const ConvKArgs& a, int dtype, int nclass);
 void launch_conv_ring(const ConvKArgs& a, int nclass, hipStream_t st);
 

@@ -520,7 +520,6 @@ int conv_down_halo_slots(const ConvKArgs& a) {
 
 // ConvKArgs::bst on this pass: the second 32 of its 64 written columns (the sub-block half of the level-0 concat gradient), bf16
 int conv_down_halo_bst_slots(const ConvKArgs& a) {
-  { const char* e = getenv("CTSEG_BST_DOWN"); if (e != nullptr && e[0] == '0') return 0; }   // (A/B switch)
   // (12-wide gathered rows only: the variant staging 16-byte chunks is at the 256-register line without the sums)
   if (a.dtype != CTSEG_BF16 || a.g_ld != 12 || a.stats != nullptr || a.bias != nullptr || a.add != nullptr || a.Cn > DH_CN || a.bst.C != 32 || a.bst.col0 != 32 || a.Cn_store < 64) return 0;
   // 16-byte chunks of 8 channels: the written tensor(s) and y

@@ -310,7 +310,6 @@ static void down_r_geom(const ConvKArgs& a, DownRGeom& g) {
 }
 
 bool conv_down_r_eligible(const ConvKArgs& a, int dtype, int nclass) {
-  if (getenv("CTSEG_NO_DOWN_R") != nullptr) return false;
   if (!is16(dtype) || a.out_f32 || nclass != 1 || a.sin != 2 || a.sout != 1 || a.add != nullptr) return false;
   if (a.Cg != 32 || a.Cn != 128 || a.Cn_store != 128) return false;
   if ((a.g_ld % 8) != 0 || ((uintptr_t)a.in % 16) != 0 || ((uintptr_t)a.w % 16) != 0) return false;
@@ -343,7 +342,6 @@ int conv_down_r_slots(const ConvKArgs& a) {
 
 // ConvKArgs::bst on this pass (bf16, no forward statistics, no bias): whole 16-column blocks of the written columns, y in 8-byte pieces
 int conv_down_r_bst_slots(const ConvKArgs& a) {
-  { const char* e = getenv("CTSEG_BST_DOWN_R"); if (e != nullptr && e[0] == '0') return 0; }   // (A/B switch)
   if (a.dtype != CTSEG_BF16 || a.stats != nullptr || a.bias != nullptr) return 0;
   if (a.bst.C <= 0 || (a.bst.C % 16) != 0 || (a.bst.col0 % 16) != 0 || a.bst.col0 + a.bst.C > 128) return 0;
   if ((a.bst.y_ld % 4) != 0 || a.bst.y_ld < a.bst.C || ((uintptr_t)a.bst.y % 8) != 0) return 0;

@@ -672,7 +672,6 @@ int conv_halo_sw_slots(const ConvKArgs& a) {
 
 // ConvKArgs::bst on this pass: the 8-class 128 -> 32 and the single-class 64 -> 64 input gradients in bf16, all written channels
 int conv_halo_sw_bst_slots(const ConvKArgs& a, int nclass) {
-  { const char* e = getenv("CTSEG_BST_SW"); if (e != nullptr && (e[0] == '0' || (e[0] == '8' && nclass != 8) || (e[0] == '1' && nclass != 1))) return 0; }   // (A/B switch)
   if (a.dtype != CTSEG_BF16 || a.stats != nullptr || a.bias != nullptr) return 0;
   if (!((nclass == 8 && a.Cg == 128) || (nclass == 1 && a.Cg == 64))) return 0;
   if (a.bst.C != a.Cn || a.bst.col0 != 0 || a.Cn_store != a.Cn || (a.o_ld % 8) != 0 || ((uintptr_t)a.out % 16) != 0) return 0;

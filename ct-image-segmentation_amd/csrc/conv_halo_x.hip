@@ -1093,10 +1093,9 @@ bool conv_halo_x_eligible(const ConvKArgs& a, int dtype, int nclass) {
   return true;                                      // (independent of a.stats: sizing queries run before the partial buffer exists)
 }
 
-// operand normalisation on load: the register-staged (12-wide rows) variant, constants of at most X_NRM_MAXN samples in LDS
-bool conv_halo_x_in_norm_ok(const ConvKArgs& a, int dtype, int nclass) {
-  return conv_halo_x_eligible(a, dtype, nclass) && a.g_ld == 12 && a.Cg == 16 && a.N <= X_NRM_MAXN && a.in_C <= 12;
-}
+// operand normalisation on load (of an eligible pass): the register-staged (12-wide rows) variant, constants of at most X_NRM_MAXN
+// samples in LDS
+bool conv_halo_x_in_norm_ok(const ConvKArgs& a) { return a.g_ld == 12 && a.Cg == 16 && a.N <= X_NRM_MAXN && a.in_C <= 12; }
 
 // InstanceNorm partials exist for the forward tap order with 16-bit output and no addend (what the plans record)
 bool conv_halo_x_stats_ok(const ConvKArgs& a) { return x_tap_order(a) == 0 && !a.out_f32 && a.add == nullptr;
@@ -1119,7 +1118,6 @@ static int x_add_kind(const ConvKArgs& a);
 int conv_halo_x_bst_slots(const ConvKArgs& a) {
   if (x_tap_order(a) != 1 || a.out_f32 || a.stats != nullptr || a.bias != nullptr || x_add_kind(a) == 2) return 0;
   if (a.bst.col0 != 0 || a.bst.C > a.Cn_store || a.bst.y_ld != a.o_ld) return 0;      // y laid out like the written gradient
-  { const char* e = getenv("CTSEG_BST_X64"); if (a.Cg * 2 == 64 && a.Cn > 16 && e != nullptr && e[0] == '0') return 0; }   // (A/B switch)
   if ((int64_t)a.Xo * a.Yo * a.Zo * a.bst.y_ld * 2 >= (1ll << 31) - 65536) return 0;
   return x_grid(a);
 }
@@ -1246,24 +1244,17 @@ void launch_conv_halo_x_ce(ConvKArgs& a, const XCe& e, hipStream_t st) {
 
 using namespace ctseg;
 
-static void x_fill(const ctseg_conv_desc* d, ConvKArgs& a) {
-  a.in = (const char*)d->in; a.w = (const char*)d->w; a.bias = d->bias; a.out = (char*)d->out; a.add = (const char*)d->add;
-  a.stats = d->stats;
-  a.N = d->N; a.Xi = d->Xi; a.Yi = d->Yi; a.Zi = d->Zi; a.Xr = d->Xr; a.Yr = d->Yr; a.Zr = d->Zr; a.Xo = d->Xo; a.Yo = d->Yo; a.Zo = d->Zo;
-  a.Cg = d->Cg; a.Cn = d->Cn; a.Cn_store = d->Cn_store; a.g_ld = d->g_ld; a.o_ld = d->o_ld; a.add_ld = d->add_ld;
-  a.sin = d->sin; a.sout = d->sout; a.rows = d->Xr * d->Yr * d->Zr; a.tiles = 0; a.out_f32 = d->out_f32; a.add_f32 = d->add_f32;
-  a.stats_ld = d->stats_ld; a.stats_tiles = d->stats_tiles; a.stats_tile0 = d->stats_tile0;
-  for (int c = 0; c < CTSEG_MAX_CLASSES; ++c) a.cls[c] = d->cls[c < d->nclass ? c : 0];
-  a.out2 = nullptr; a.out2_col0 = 0; a.o2_ld = 0; a.dtype = d->dtype; a.xcd_order = 0;
-  a.in_mr = d->in_mean_rstd; a.in_alpha = d->in_alpha; a.in_C = d->in_norm_C;
+// the fused pass stores the loss terms and the logits gradient only: a split output and backward statistics do not apply to it
+static void clear_ce_unused(ConvKArgs& a) {
+  a.out2 = nullptr; a.out2_col0 = a.o2_ld = 0;
   a.bst = BstArgs{};
 }
 
 extern "C" int ctseg_conv_logits_ce_slots(const ctseg_conv_desc* d, int32_t C) {
   if (!desc_ok(d) || d->nclass != 1) return 0;
-  ConvKArgs a;
-  x_fill(d, a);
-  a.stats = nullptr;
+  ConvKArgs a = conv_args(d);
+  a.stats = nullptr;             // (judged without InstanceNorm partials: the fused pass writes none)
+  clear_ce_unused(a);
   if (!conv_halo_x_ce_eligible(a, d->dtype, d->nclass, C)) return 0;
   return conv_halo_x_ce_slots(a);
 }
@@ -1274,8 +1265,8 @@ extern "C" int ctseg_conv_logits_ce(const ctseg_conv_desc* d, const uint8_t* lab
   CTSEG_REQUIRE_DESC(d, "conv_logits_ce");
   CTSEG_REQUIRE(d->in && d->w && labels && coef && dlogits && part && cnt, "conv_logits_ce: null pointer");
   CTSEG_REQUIRE(d->nclass == 1, "conv_logits_ce: one tap class expected");
-  ConvKArgs a;
-  x_fill(d, a);
+  ConvKArgs a = conv_args(d);
+  clear_ce_unused(a);
   CTSEG_REQUIRE(conv_halo_x_ce_eligible(a, d->dtype, d->nclass, C), "conv_logits_ce: pass not eligible (ask ctseg_conv_logits_ce_slots)");
   const int slots = conv_halo_x_ce_slots(a);
   CTSEG_REQUIRE(P >= slots && R >= 2 && R <= 256, "conv_logits_ce: part needs >= %d slots per sample (P = %d)", slots, P);

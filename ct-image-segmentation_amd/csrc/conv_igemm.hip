@@ -287,13 +287,19 @@ static int launch_cfg(const ConvKArgs& a, bool smallc, int nclass, hipStream_t s
   return 0;
 }
 
-// rows of the row grid one workgroup tile covers.  Cn > 128 in bf16 (never fp32 output there): 192 x 256 tile, 8 waves —
-// the 128 x 128 tile is bound by the L2 -> LDS operand traffic per CU (64 FLOP/B); 192 x 256 moves 110 FLOP/B, and the
+// the gathered operand is not in whole 16-byte chunks: the generic kernel stages it element-wise (its SMALLC instantiation)
+static bool small_operand(const ConvKArgs& a, int dtype) {
+  const int EPC = dtype == CTSEG_F32 ? 4 : 8;
+  return (a.Cg % EPC) != 0 || (a.g_ld % EPC) != 0 || ((uintptr_t)a.in % 16) != 0;
+}
+
+// rows of the row grid one workgroup tile of the generic pass covers.  Cn > 128 in bf16 (never fp32 output there): 192 x 256 tile,
+// 8 waves — the 128 x 128 tile is bound by the L2 -> LDS operand traffic per CU (64 FLOP/B); 192 x 256 moves 110 FLOP/B, and the
 // M of every layer of the reference's volumes (48 / 24 / 12 / 6 deep) is a multiple of 192.
 // 65..128 columns take the 192 x 128 tile of the ring-pipelined kernel where it is eligible (Cg a multiple of 32 ...): 256
 // tiles for the 49152-row layers instead of 384 tiles of 128 rows (1.5 rounds over the 256 CUs).
-static int tile_rows_for(const ConvKArgs& a, int dtype, bool smallc, int nclass) {
-  if (is16(dtype) && !a.out_f32 && !smallc) {
+static int tile_rows_for(const ConvKArgs& a, int dtype, int nclass) {
+  if (is16(dtype) && !a.out_f32 && !small_operand(a, dtype)) {
     if (a.Cn > 128) return 192;
     // (not for 32 gathered channels: those passes are operand-traffic bound with short K loops; measured 0.21 -> 0.24 ms)
     if (a.Cn > 64 && a.Cg >= 64 && conv_ring_eligible(a, dtype, nclass)) return 192;
@@ -301,29 +307,67 @@ static int tile_rows_for(const ConvKArgs& a, int dtype, bool smallc, int nclass)
   return a.Cn <= 32 ? 256 : 128;
 }
 
-// partial rows per sample the pass taking this geometry fills for ConvKArgs::bst (the same kernel selection as the launch); 0: it cannot
-static int bst_slots_for(const ConvKArgs& a, int dtype, int nclass, bool smallc) {
+// The one place that orders the forward passes: the first eligible family runs (GENERIC covers the 192-row ring kernel too).
+// CTSEG_NO_DOWN_R (test / A/B switch, read per call: tests flip it inside one process) skips DOWN_R; CTSEG_NO_HALO_X lives in
+// conv_halo_x_eligible, which the fused cross-entropy pass asks as well.
+static ConvPass select_conv_pass(const ConvKArgs& a, int dtype, int nclass) {
+  if (conv_halo_eligible(a, dtype, nclass)) return conv_halo_x_eligible(a, dtype, nclass) ? ConvPass::HALO_X : ConvPass::HALO;
+  if (conv_up_eligible(a, dtype, nclass)) return ConvPass::UP;
+  if (conv_stem_eligible(a, dtype, nclass)) return ConvPass::STEM;
+  if (conv_halo_sw_eligible(a, dtype, nclass)) return ConvPass::HALO_SW;
+  if (conv_down_halo_eligible(a, dtype, nclass)) return ConvPass::DOWN_HALO;
+  if (getenv("CTSEG_NO_DOWN_R") == nullptr && conv_down_r_eligible(a, dtype, nclass)) return ConvPass::DOWN_R;
+  if (conv_up8_eligible(a, dtype, nclass)) return ConvPass::UP8;
+  return ConvPass::GENERIC;
+}
+
+static const char* const PASS_NAME[] = {"x-column halo", "halo", "up", "stem", "streamed-weight halo", "stride-2 halo",
+                                        "stride-2 register-weight", "many-channel 8-class", "generic"};
+
+// InstanceNorm partial slots per sample (all classes) the pass fills, and the smallest stats_ld it can take
+struct StatsLayout { int slots, ld; };
+static StatsLayout stats_layout(ConvPass p, const ConvKArgs& a, int dtype, int nclass) {
+  const int tc = ctseg_conv_tile_cols(a.Cn), ld_cols = ((a.Cn + tc - 1) / tc) * tc;
+  switch (p) {
+    case ConvPass::HALO_X: return {conv_halo_x_slots(a), ld_cols};
+    case ConvPass::HALO: return {conv_halo_slots(a, dtype), ld_cols};
+    case ConvPass::UP: return {conv_up_slots(a), 16};
+    case ConvPass::STEM: return {conv_stem_slots(a), ((a.Cn + 15) / 16) * 16};
+    case ConvPass::HALO_SW: return {conv_halo_sw_slots(a), a.Cn};
+    case ConvPass::DOWN_HALO: return {conv_down_halo_slots(a), a.Cn};
+    case ConvPass::DOWN_R: return {conv_down_r_slots(a), a.Cn};
+    case ConvPass::UP8: return {conv_up8_slots(a), a.Cn};
+    case ConvPass::GENERIC: break;
+  }
+  const int bm = tile_rows_for(a, dtype, nclass), bn = bm == 192 ? (a.Cn > 128 ? 256 : 128) : tc;
+  return {((a.rows + bm - 1) / bm) * nclass, ((a.Cn + bn - 1) / bn) * bn};
+}
+
+// partial rows per sample the pass fills for ConvKArgs::bst; 0: it cannot
+static int bst_slots(ConvPass p, const ConvKArgs& a, int dtype, int nclass) {
   if (dtype != CTSEG_BF16 || a.out_f32 || a.bst.C <= 0) return 0;      // (training storage: bf16; fp32 keeps its pinned summation order)
-  if (conv_halo_eligible(a, dtype, nclass)) return conv_halo_x_eligible(a, dtype, nclass) ? conv_halo_x_bst_slots(a) : 0;
-  if (conv_up_eligible(a, dtype, nclass) || conv_stem_eligible(a, dtype, nclass)) return 0;
-  if (conv_halo_sw_eligible(a, dtype, nclass)) return conv_halo_sw_bst_slots(a, nclass);
-  if (conv_down_halo_eligible(a, dtype, nclass)) return conv_down_halo_bst_slots(a);
-  if (conv_down_r_eligible(a, dtype, nclass)) return conv_down_r_bst_slots(a);
-  if (conv_up8_eligible(a, dtype, nclass)) return 0;
-  { const char* e = getenv("CTSEG_BST_GENERIC"); if (e != nullptr && e[0] == '0') return 0; }   // (A/B switch)
+  switch (p) {
+    case ConvPass::HALO_X: return conv_halo_x_bst_slots(a);
+    case ConvPass::HALO_SW: return conv_halo_sw_bst_slots(a, nclass);
+    case ConvPass::DOWN_HALO: return conv_down_halo_bst_slots(a);
+    case ConvPass::DOWN_R: return conv_down_r_bst_slots(a);
+    case ConvPass::GENERIC: break;
+    default: return 0;
+  }
   // generic / ring kernels (conv_epilogue): one partial row per (class, tile); whole 16-byte chunks of y beside those of the output
-  if (smallc || a.out2 != nullptr || a.o_ld % 8 != 0 || a.Cn_store % 8 != 0 || a.bst.col0 % 8 != 0 || a.bst.y_ld % 8 != 0 ||
+  if (small_operand(a, dtype) || a.out2 != nullptr || a.o_ld % 8 != 0 || a.Cn_store % 8 != 0 || a.bst.col0 % 8 != 0 || a.bst.y_ld % 8 != 0 ||
       ((uintptr_t)a.bst.y % 16) != 0 || a.bst.col0 + a.bst.C > a.Cn_store)
     return 0;
-  const int bm = tile_rows_for(a, dtype, smallc, nclass);
+  const int bm = tile_rows_for(a, dtype, nclass);
   // (not the 128 x 64 / 256 x 32 / 256 x 16 tiles: the sums cost them a workgroup per CU — 108 -> 180 registers — which is what the
   // reduce pass they would remove costs: 0.121 vs 0.092 + 0.024 ms on the 8-class 256 -> 64 pass)
   if (bm != 192 && a.Cn <= 64) return 0;
   return ((a.rows + bm - 1) / bm) * nclass;
 }
 
-template <typename T> static int launch_dtype(ConvKArgs& a, bool smallc, int nclass, hipStream_t st) {
-  const int bm = tile_rows_for(a, TT<T>::DT, smallc, nclass);
+template <typename T> static int launch_generic(ConvKArgs& a, int nclass, hipStream_t st) {
+  const int bm = tile_rows_for(a, TT<T>::DT, nclass);
+  const bool smallc = small_operand(a, TT<T>::DT);
   a.tiles = (a.rows + bm - 1) / bm;
   // XCD-contiguous tile ranges: measured neutral for single-class passes (their halo re-reads already hit L2 / Infinity Cache),
   // 7-9 % on the 8-class passes (384->64 and 256->64), where every class re-gathers the same input tile
@@ -356,7 +400,7 @@ extern "C" int ctseg_conv_igemm(const ctseg_conv_desc* d, void* stream) {
   CTSEG_REQUIRE_DESC(d, "conv_igemm");
   CTSEG_REQUIRE(d->in && d->w && d->out, "conv_igemm: null pointer");
   CTSEG_REQUIRE(d->dtype == CTSEG_F32 || is16(d->dtype), "conv_igemm: bad dtype %d", d->dtype);
-  const int SZ = d->dtype == CTSEG_F32 ? 4 : 2, EPC = 16 / SZ, BK = 128 / SZ;
+  const int SZ = d->dtype == CTSEG_F32 ? 4 : 2, BK = 128 / SZ;
   const int OSZ = d->out_f32 ? 4 : SZ, EPO = 16 / OSZ;
   CTSEG_REQUIRE(d->nclass >= 1 && d->nclass <= CTSEG_MAX_CLASSES, "conv_igemm: nclass %d", d->nclass);
   CTSEG_REQUIRE(d->N > 0 && d->Cg > 0 && d->Cn > 0 && d->Xr > 0 && d->Yr > 0 && d->Zr > 0, "conv_igemm: empty dims");
@@ -372,7 +416,6 @@ extern "C" int ctseg_conv_igemm(const ctseg_conv_desc* d, void* stream) {
   CTSEG_REQUIRE(d->Cn_store >= d->Cn && d->Cn_store % EPOv == 0 && (d->out2 ? d->out2_col0 : d->Cn_store) <= d->o_ld,
                 "conv_igemm: Cn_store %d", d->Cn_store);
   CTSEG_REQUIRE(d->o_ld % EPOv == 0 && ((uintptr_t)d->out % 16) == 0, "conv_igemm: out not 16-byte chunked");
-  const bool smallc = (d->Cg % EPC) != 0 || (d->g_ld % EPC) != 0 || ((uintptr_t)d->in % 16) != 0;
   CTSEG_REQUIRE(d->g_ld >= d->Cg || n_in, "conv_igemm: g_ld < Cg");
   if (d->add) {
     const int ASZ = d->add_f32 ? 4 : SZ;
@@ -399,161 +442,105 @@ extern "C" int ctseg_conv_igemm(const ctseg_conv_desc* d, void* stream) {
   CTSEG_REQUIRE((int64_t)(d->Xr - 1) * d->sout + mox < d->Xo && (int64_t)(d->Yr - 1) * d->sout + moy < d->Yo &&
                     (int64_t)(d->Zr - 1) * d->sout + moz < d->Zo,
                 "conv_igemm: row grid * sout exceeds written dims");
-  ConvKArgs a;
-  a.in = (const char*)d->in; a.w = (const char*)d->w; a.bias = d->bias; a.out = (char*)d->out;
-  a.add = (const char*)d->add; a.stats = d->stats;
-  a.N = d->N; a.Xi = d->Xi; a.Yi = d->Yi; a.Zi = d->Zi; a.Xr = d->Xr; a.Yr = d->Yr; a.Zr = d->Zr;
-  a.Xo = d->Xo; a.Yo = d->Yo; a.Zo = d->Zo;
-  a.Cg = d->Cg; a.Cn = d->Cn; a.Cn_store = d->Cn_store; a.g_ld = d->g_ld; a.o_ld = d->o_ld; a.add_ld = d->add_ld;
-  a.sin = d->sin; a.sout = d->sout; a.rows = d->Xr * d->Yr * d->Zr; a.tiles = 0;
-  a.out_f32 = d->out_f32; a.add_f32 = d->add_f32;
-  a.stats_ld = d->stats_ld; a.stats_tiles = d->stats_tiles; a.stats_tile0 = d->stats_tile0;
-  for (int c = 0; c < CTSEG_MAX_CLASSES; ++c) a.cls[c] = d->cls[c < d->nclass ? c : 0];
-  a.out2 = (char*)d->out2; a.out2_col0 = d->out2_col0; a.o2_ld = d->o2_ld; a.xcd_order = 0;
-  a.dtype = d->dtype;
-  a.in_mr = d->in_mean_rstd; a.in_alpha = d->in_alpha; a.in_C = d->in_norm_C;
-  fill_bst(d, a);
+  ConvKArgs a = conv_args(d);
+  const ConvPass pass = select_conv_pass(a, d->dtype, d->nclass);
   if (d->bst_partials != nullptr) {
-    const int slots = bst_slots_for(a, d->dtype, d->nclass, smallc);
+    const int slots = bst_slots(pass, a, d->dtype, d->nclass);
     CTSEG_REQUIRE(slots > 0, "conv_igemm: bst_* (backward statistics in the epilogue) is not implemented for this pass (ask ctseg_conv_bwd_stats_slots)");
     CTSEG_REQUIRE(d->bst_y && d->bst_mean_rstd && d->bst_alpha && d->bst_P >= slots && d->bst_ld >= d->bst_C && d->bst_C > 0 &&
                       ((uintptr_t)d->bst_y % 8) == 0,
                   "conv_igemm: bst_* layout (need bst_P >= %d partial rows per sample)", slots);
   }
-  const bool halo = conv_halo_eligible(a, d->dtype, d->nclass);
   if (d->in_mean_rstd != nullptr)
-    CTSEG_REQUIRE(halo && conv_halo_x_in_norm_ok(a, d->dtype, d->nclass) && d->in_alpha != nullptr,
+    CTSEG_REQUIRE(pass == ConvPass::HALO_X && conv_halo_x_in_norm_ok(a) && d->in_alpha != nullptr,
                   "conv_igemm: in_mean_rstd (normalise the operand on load) is not implemented for this pass (ask ctseg_conv_in_norm_ok)");
-  if (halo && d->stats && conv_halo_x_eligible(a, d->dtype, d->nclass))
-    CTSEG_REQUIRE(conv_halo_x_stats_ok(a), "conv_igemm: InstanceNorm partials with an addend / fp32 output / input-gradient taps "
-                                           "are not implemented on the x-column halo pass");
-  const bool up = !halo && conv_up_eligible(a, d->dtype, d->nclass);
-  const bool stem = !halo && !up && conv_stem_eligible(a, d->dtype, d->nclass);
-  const bool sw = !halo && !up && !stem && conv_halo_sw_eligible(a, d->dtype, d->nclass);
-  const bool down = !halo && !up && !stem && !sw && conv_down_halo_eligible(a, d->dtype, d->nclass);
-  const bool downr = !halo && !up && !stem && !sw && !down && conv_down_r_eligible(a, d->dtype, d->nclass);
-  const bool up8 = !halo && !up && !stem && !sw && !down && !downr && conv_up8_eligible(a, d->dtype, d->nclass);
-  if (d->stats && up8) {
-    CTSEG_REQUIRE(d->stats_tile0 + conv_up8_slots(a) <= d->stats_tiles && d->stats_ld >= d->Cn,
-                  "conv_igemm: stats partial layout (many-channel 8-class pass)");
-  } else if (d->stats && downr) {
-    CTSEG_REQUIRE(d->stats_tile0 + conv_down_r_slots(a) <= d->stats_tiles && d->stats_ld >= d->Cn,
-                  "conv_igemm: stats partial layout (stride-2 register-weight pass)");
-  } else if (d->stats && down) {
-    CTSEG_REQUIRE(d->stats_tile0 + conv_down_halo_slots(a) <= d->stats_tiles && d->stats_ld >= d->Cn,
-                  "conv_igemm: stats partial layout (stride-2 halo pass)");
-  } else if (d->stats && sw) {
-    CTSEG_REQUIRE(d->stats_tile0 + conv_halo_sw_slots(a) <= d->stats_tiles && d->stats_ld >= d->Cn,
-                  "conv_igemm: stats partial layout (streamed-weight halo pass)");
-  } else if (d->stats && stem) {
-    CTSEG_REQUIRE(d->stats_tile0 + conv_stem_slots(a) <= d->stats_tiles && d->stats_ld >= ((d->Cn + 15) / 16) * 16,
-                  "conv_igemm: stats partial layout (stem pass)");
-  } else if (d->stats && up) {
-    CTSEG_REQUIRE(d->stats_tile0 + conv_up_slots(a) <= d->stats_tiles && d->stats_ld >= 16, "conv_igemm: stats partial layout (up pass)");
-  } else if (d->stats) {
-    const int bm = tile_rows_for(a, d->dtype, smallc, d->nclass);
-    const int tiles = halo ? conv_halo_slots(a, d->dtype) : (a.rows + bm - 1) / bm;
-    const int bn = bm == 192 ? (d->Cn > 128 ? 256 : 128) : ctseg_conv_tile_cols(d->Cn);
-    CTSEG_REQUIRE(d->stats_tile0 + tiles * d->nclass <= d->stats_tiles && d->stats_ld >= ((d->Cn + bn - 1) / bn) * bn,
-                  "conv_igemm: stats partial layout (need stats_ld >= roundup(Cn, tile cols))");
+  if (d->stats != nullptr) {
+    CTSEG_REQUIRE(pass != ConvPass::HALO_X || conv_halo_x_stats_ok(a),
+                  "conv_igemm: InstanceNorm partials with an addend / fp32 output / input-gradient taps are not implemented on the x-column halo pass");
+    const StatsLayout sl = stats_layout(pass, a, d->dtype, d->nclass);
+    CTSEG_REQUIRE(d->stats_tile0 + sl.slots <= d->stats_tiles && d->stats_ld >= sl.ld,
+                  "conv_igemm: stats partial layout (%s pass: need stats_tile0 + %d <= stats_tiles, stats_ld >= %d)",
+                  PASS_NAME[(int)pass], sl.slots, sl.ld);
   }
+  const bool halo = pass == ConvPass::HALO_X || pass == ConvPass::HALO;
   if (n_out || n_in || n_add)
-    CTSEG_REQUIRE(halo || (up && !n_in) || (down && !n_out && !n_add),
+    CTSEG_REQUIRE(halo || (pass == ConvPass::UP && !n_in) || (pass == ConvPass::DOWN_HALO && !n_out && !n_add),
                   "conv_igemm: 12-wide bf16 rows are moved by the LDS-halo passes only (ask ctseg_conv_narrow_ok)");
   if (d->out2 != nullptr)
-    CTSEG_REQUIRE((stem || down || downr) && d->add == nullptr && d->out2_col0 > 0 && d->out2_col0 % 4 == 0 && d->out2_col0 < d->Cn_store &&
+    CTSEG_REQUIRE((pass == ConvPass::STEM || pass == ConvPass::DOWN_HALO || pass == ConvPass::DOWN_R) && d->add == nullptr &&
+                      d->out2_col0 > 0 && d->out2_col0 % 4 == 0 && d->out2_col0 < d->Cn_store &&
                       d->o2_ld >= d->Cn_store - d->out2_col0 && d->o2_ld % 4 == 0 && ((uintptr_t)d->out2 % 16) == 0,
                   "conv_igemm: out2 (split output) is not supported for this pass (ask ctseg_conv_split_ok first)");
   hipStream_t st = (hipStream_t)stream;
-  if (halo) launch_conv_halo(a, d->dtype, st);
-  else if (up) launch_conv_up(a, st);
-  else if (stem) launch_conv_stem(a, st);
-  else if (sw) launch_conv_halo_sw(a, d->nclass, st);
-  else if (down) launch_conv_down_halo(a, st);
-  else if (downr) launch_conv_down_r(a, st);
-  else if (up8) launch_conv_up8(a, st);
-  else if (d->dtype == CTSEG_F32) launch_dtype<float>(a, smallc, d->nclass, st);
-  else if (d->dtype == CTSEG_F16) launch_dtype<F16>(a, smallc, d->nclass, st);
-  else launch_dtype<BF16>(a, smallc, d->nclass, st);
+  switch (pass) {
+    case ConvPass::HALO_X: launch_conv_halo_x(a, st); break;
+    case ConvPass::HALO: launch_conv_halo(a, d->dtype, st); break;
+    case ConvPass::UP: launch_conv_up(a, st); break;
+    case ConvPass::STEM: launch_conv_stem(a, st); break;
+    case ConvPass::HALO_SW: launch_conv_halo_sw(a, d->nclass, st); break;
+    case ConvPass::DOWN_HALO: launch_conv_down_halo(a, st); break;
+    case ConvPass::DOWN_R: launch_conv_down_r(a, st); break;
+    case ConvPass::UP8: launch_conv_up8(a, st); break;
+    case ConvPass::GENERIC:
+      if (d->dtype == CTSEG_F32) launch_generic<float>(a, d->nclass, st);
+      else if (d->dtype == CTSEG_F16) launch_generic<F16>(a, d->nclass, st);
+      else launch_generic<BF16>(a, d->nclass, st);
+      break;
+  }
   CTSEG_LAUNCH_CHECK("conv_igemm");
   return 0;
 }
 
-static void fill_args(const ctseg_conv_desc* d, ConvKArgs& a) {
-  fill_bst(d, a);
-  a.out2 = nullptr; a.out2_col0 = 0; a.o2_ld = 0; a.xcd_order = 0; a.dtype = d->dtype;
-  a.in_mr = d->in_mean_rstd; a.in_alpha = d->in_alpha; a.in_C = d->in_norm_C;
-  a.w = (const char*)d->w; a.Cn_store = d->Cn_store;
-  a.in = (const char*)d->in; a.N = d->N; a.Xi = d->Xi; a.Yi = d->Yi; a.Zi = d->Zi; a.Xr = d->Xr; a.Yr = d->Yr; a.Zr = d->Zr;
-  a.Cg = d->Cg; a.Cn = d->Cn; a.g_ld = d->g_ld; a.sin = d->sin; a.sout = d->sout; a.rows = d->Xr * d->Yr * d->Zr;
-  // everything a kernel-selection predicate may look at (the same answer at sizing time and at launch time)
-  a.out = (char*)d->out; a.add = (const char*)d->add; a.bias = d->bias; a.stats = nullptr;
-  a.Xo = d->Xo; a.Yo = d->Yo; a.Zo = d->Zo; a.o_ld = d->o_ld; a.add_ld = d->add_ld; a.out_f32 = d->out_f32; a.add_f32 = d->add_f32;
-  a.tiles = 0; a.stats_ld = 0; a.stats_tiles = 0; a.stats_tile0 = 0; a.o2_ld = 0;
-  for (int c = 0; c < CTSEG_MAX_CLASSES; ++c) a.cls[c] = d->cls[c < d->nclass ? c : 0];
-}
+// The queries below answer for the pass the launch would select.  All but ctseg_conv_bwd_stats_slots judge the un-split pass
+// (ctseg_conv_split_ok says whether out2 may be added to it): they clear out2.
+static bool query_ok(const ctseg_conv_desc* d) { return desc_ok(d) && d->nclass >= 1 && d->nclass <= CTSEG_MAX_CLASSES; }
 
 extern "C" int ctseg_conv_split_ok(const ctseg_conv_desc* d) {
   if (!desc_ok(d) || d->nclass != 1 || d->add != nullptr) return 0;
-  ConvKArgs a;
-  fill_args(d, a);
-  a.out_f32 = d->out_f32; a.Xo = d->Xo; a.Yo = d->Yo; a.Zo = d->Zo; a.add = nullptr; a.o_ld = d->o_ld;
-  if (conv_halo_eligible(a, d->dtype, d->nclass) || conv_up_eligible(a, d->dtype, d->nclass)) return 0;
-  if (conv_stem_eligible(a, d->dtype, d->nclass)) return 1;
-  if (conv_halo_sw_eligible(a, d->dtype, d->nclass)) return 0;
-  if (conv_down_halo_eligible(a, d->dtype, d->nclass)) return 1;
-  return (d->out2_col0 % 16 == 0 && conv_down_r_eligible(a, d->dtype, d->nclass)) ? 1 : 0;
+  ConvKArgs a = conv_args(d);
+  a.out2 = nullptr;
+  switch (select_conv_pass(a, d->dtype, 1)) {
+    case ConvPass::STEM:
+    case ConvPass::DOWN_HALO: return 1;
+    case ConvPass::DOWN_R: return d->out2_col0 % 16 == 0 ? 1 : 0;
+    default: return 0;
+  }
 }
 
 extern "C" int ctseg_conv_bwd_stats_slots(const ctseg_conv_desc* d) {
-  if (!desc_ok(d) || !is16(d->dtype) || d->nclass < 1 || d->nclass > CTSEG_MAX_CLASSES || d->bst_C <= 0 || d->out_f32) return 0;
-  ConvKArgs a;
-  fill_args(d, a);
-  a.out2 = (char*)d->out2; a.out2_col0 = d->out2_col0; a.o2_ld = d->o2_ld;
-  const bool smallq = (d->Cg % 8) != 0 || (d->g_ld % 8) != 0 || ((uintptr_t)d->in % 16) != 0;
-  return bst_slots_for(a, d->dtype, d->nclass, smallq);
+  if (!query_ok(d) || !is16(d->dtype) || d->bst_C <= 0 || d->out_f32) return 0;
+  ConvKArgs a = conv_args(d);
+  a.stats = nullptr;      // (sized before the launch knows whether the pass also writes InstanceNorm partials)
+  return bst_slots(select_conv_pass(a, d->dtype, d->nclass), a, d->dtype, d->nclass);
 }
 
 extern "C" int ctseg_conv_in_norm_ok(const ctseg_conv_desc* d) {
-  if (!desc_ok(d) || !is16(d->dtype) || d->nclass < 1 || d->nclass > CTSEG_MAX_CLASSES) return 0;
-  ConvKArgs a;
-  fill_args(d, a);
-  return (conv_halo_eligible(a, d->dtype, d->nclass) && conv_halo_x_in_norm_ok(a, d->dtype, d->nclass)) ? 1 : 0;
+  if (!query_ok(d) || !is16(d->dtype)) return 0;
+  ConvKArgs a = conv_args(d);
+  a.out2 = nullptr;
+  return (select_conv_pass(a, d->dtype, d->nclass) == ConvPass::HALO_X && conv_halo_x_in_norm_ok(a)) ? 1 : 0;
 }
 
 // 1 when this pass may read / write 12-wide bf16 rows (g_ld, o_ld / Cn_store, add_ld of the descriptor): it is taken by
 // the resident-weight LDS-halo kernel (any of them narrow), by the stride-2 "up" kernel (narrow output / addend only) or by the
 // stride-2 "down" halo kernel (narrow gathered operand only)
 extern "C" int ctseg_conv_narrow_ok(const ctseg_conv_desc* d) {
-  if (!desc_ok(d) || !is16(d->dtype) || d->nclass < 1 || d->nclass > CTSEG_MAX_CLASSES) return 0;
-  ConvKArgs a;
-  fill_args(d, a);
-  a.out_f32 = d->out_f32; a.Xo = d->Xo; a.Yo = d->Yo; a.Zo = d->Zo; a.add = (const char*)d->add; a.o_ld = d->o_ld;
-  if (conv_halo_eligible(a, d->dtype, d->nclass)) return 1;
+  if (!query_ok(d) || !is16(d->dtype)) return 0;
+  ConvKArgs a = conv_args(d);
+  a.out2 = nullptr;
+  const ConvPass p = select_conv_pass(a, d->dtype, d->nclass);
+  if (p == ConvPass::HALO_X || p == ConvPass::HALO) return 1;
   if (d->g_ld % 8 != 0) {
     const bool wide_out = d->out_f32 || (d->o_ld % 8 == 0 && d->Cn_store % 8 == 0), wide_add = d->add == nullptr || d->add_f32 || d->add_ld % 8 == 0;
-    return (d->g_ld == 12 && wide_out && wide_add && !conv_up_eligible(a, d->dtype, d->nclass) && !conv_stem_eligible(a, d->dtype, d->nclass) &&
-            !conv_halo_sw_eligible(a, d->dtype, d->nclass) && conv_down_halo_eligible(a, d->dtype, d->nclass)) ? 1 : 0;
+    return (d->g_ld == 12 && wide_out && wide_add && p == ConvPass::DOWN_HALO) ? 1 : 0;
   }
-  return conv_up_eligible(a, d->dtype, d->nclass) ? 1 : 0;
+  return p == ConvPass::UP ? 1 : 0;
 }
 
 // tiles per sample (all classes) a pass with this geometry writes InstanceNorm partials for
 extern "C" int ctseg_conv_num_tiles(const ctseg_conv_desc* d) {
-  if (!desc_ok(d) || d->nclass < 1 || d->nclass > CTSEG_MAX_CLASSES) return -1;
-  ConvKArgs a;
-  fill_args(d, a);
-  if (conv_halo_eligible(a, d->dtype, d->nclass)) return conv_halo_slots(a, d->dtype);
-  a.out_f32 = d->out_f32; a.Xo = d->Xo; a.Yo = d->Yo; a.Zo = d->Zo;
-  if (conv_up_eligible(a, d->dtype, d->nclass)) return conv_up_slots(a);
-  a.add = (const char*)d->add; a.o_ld = d->o_ld;
-  if (conv_stem_eligible(a, d->dtype, d->nclass)) return conv_stem_slots(a);
-  if (conv_halo_sw_eligible(a, d->dtype, d->nclass)) return conv_halo_sw_slots(a);
-  if (conv_down_halo_eligible(a, d->dtype, d->nclass)) return conv_down_halo_slots(a);
-  if (conv_down_r_eligible(a, d->dtype, d->nclass)) return conv_down_r_slots(a);
-  if (conv_up8_eligible(a, d->dtype, d->nclass)) return conv_up8_slots(a);
-  const int SZq = d->dtype == CTSEG_F32 ? 4 : 2, EPCq = 16 / SZq;
-  const bool smallq = (d->Cg % EPCq) != 0 || (d->g_ld % EPCq) != 0 || ((uintptr_t)d->in % 16) != 0;
-  const int bm = tile_rows_for(a, d->dtype, smallq, d->nclass);
-  return ((a.rows + bm - 1) / bm) * d->nclass;
+  if (!query_ok(d)) return -1;
+  ConvKArgs a = conv_args(d);
+  a.out2 = nullptr;
+  return stats_layout(select_conv_pass(a, d->dtype, d->nclass), a, d->dtype, d->nclass).slots;
 }

@@ -431,7 +431,6 @@ static void up8_geom(const ConvKArgs& a, Up8Geom& g) {
 }
 
 bool conv_up8_eligible(const ConvKArgs& a, int dtype, int nclass) {
-  { const char* e = getenv("CTSEG_UP8"); if (e != nullptr && e[0] == '0') return false; }   // (A/B switch)
   if (!is16(dtype) || nclass != 8 || a.sin != 1 || a.sout != 2 || a.out_f32) return false;
   if (a.Cn != U8_CN || a.Cn_store != U8_CN || a.Cg < 128 || (a.Cg % 32) != 0 || a.out2 != nullptr) return false;
   if ((a.g_ld % 8) != 0 || ((uintptr_t)a.in % 16) != 0 || ((uintptr_t)a.w % 16) != 0 || (a.o_ld % 8) != 0 || ((uintptr_t)a.out % 16) != 0) return false;

@@ -496,16 +496,39 @@ bool wgrad_halo_in_norm_ok(const ctseg_wgrad_desc* d);
 void launch_wgrad_halo(const ctseg_wgrad_desc* d, hipStream_t st);
 bool wgrad_ring_eligible(const ctseg_wgrad_desc* d);
 int wgrad_ring_wgs_per_slab(const ctseg_wgrad_desc* d, int32_t* stage_bytes);
-int launch_wgrad_ring(const ctseg_wgrad_desc* d, hipStream_t st);
+void launch_wgrad_ring(const ctseg_wgrad_desc* d, int rows_per_split, hipStream_t st);
+
+enum class WgradPass { HALO, UP, STEM, RING, GENERIC };
+
+// the gathered operand is not in whole 16-byte chunks: the generic kernel stages it element-wise (its SMALLC instantiation)
+static bool wgrad_small_operand(const ctseg_wgrad_desc* d) {
+  const int EPC = d->dtype == CTSEG_F32 ? 4 : 8;
+  return (d->Cg % EPC) != 0 || (d->g_ld % EPC) != 0 || ((uintptr_t)d->in % 16) != 0;
+}
+
+// The one place that orders the weight-gradient passes: the first eligible family runs.  CTSEG_NO_WGRAD_UP and CTSEG_WGRAD_RING=0
+// (test / A/B switches, read per call: tests flip them inside one process) skip UP and RING.
+static WgradPass select_wgrad_pass(const ctseg_wgrad_desc* d) {
+  if (wgrad_halo_eligible(d)) return WgradPass::HALO;
+  if (getenv("CTSEG_NO_WGRAD_UP") == nullptr && wgrad_up_eligible(d)) return WgradPass::UP;
+  if (wgrad_stem_eligible(d)) return WgradPass::STEM;
+  const char* ring = getenv("CTSEG_WGRAD_RING");
+  if (!(ring != nullptr && atoi(ring) == 0) && !wgrad_small_operand(d) && wgrad_ring_eligible(d)) return WgradPass::RING;
+  return WgradPass::GENERIC;
+}
+
+// dY formed on load (ctseg_wgrad_desc::dyn_*): the stem pass of a first layer only
+static bool wgrad_dy_norm_ok(const ctseg_wgrad_desc* d, WgradPass p) {
+  return d->dyn_col0 > 0 && d->in_mean_rstd == nullptr && p == WgradPass::STEM && wgrad_stem_dyn_ok(d);
+}
 
 template <typename T, bool SMALLC> static void launch_wgrad(WgradKArgs& a, hipStream_t st) {
   const int bnw = ctseg_wgrad_tile_cols(a.Cn);
   const int kb = a.kpad_w / 128, cb = a.cn_pad / bnw, zs = a.N * a.splits;
-  static const bool remap = !(getenv("CTSEG_WGRAD_XCD") && atoi(getenv("CTSEG_WGRAD_XCD")) == 0);
   dim3 grid((unsigned)kb, (unsigned)cb, (unsigned)zs);
   a.kblocks = a.cblocks = 0;
   a.addr64 = ((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * (int64_t)sizeof(T) >= ((int64_t)1 << 31) - 4096 || getenv("CTSEG_WGRAD_ADDR64") != nullptr) ? 1 : 0;
-  if (remap && zs % 8 == 0 && kb * cb > 1) {
+  if (zs % 8 == 0 && kb * cb > 1) {
     a.kblocks = kb; a.cblocks = cb;
     grid = dim3((unsigned)(kb * cb * zs), 1u, 1u);
   }
@@ -524,51 +547,56 @@ extern "C" int ctseg_wgrad_tile_cols(int32_t Cn) { return Cn <= 16 ? 16 : Cn <= 
 // number of fp32 slabs [kpad_w][cn_pad] a ctseg_conv_wgrad call with this descriptor writes into `ws`
 extern "C" int ctseg_conv_wgrad_slabs(const ctseg_wgrad_desc* d) {
   if (!desc_ok(d)) return -1;
-  if (wgrad_halo_eligible(d)) return wgrad_halo_slabs(d);
-  if (wgrad_up_eligible(d)) return wgrad_up_slabs(d);
-  if (wgrad_stem_eligible(d)) return wgrad_stem_slabs(d);
-  return d->N * d->splits;
+  switch (select_wgrad_pass(d)) {
+    case WgradPass::HALO: return wgrad_halo_slabs(d);
+    case WgradPass::UP: return wgrad_up_slabs(d);
+    case WgradPass::STEM: return wgrad_stem_slabs(d);
+    default: return d->N * d->splits;
+  }
 }
 
 extern "C" int ctseg_conv_wgrad_wgs_per_slab(const ctseg_wgrad_desc* d, int32_t* per_cu, int32_t* stage_bytes) {
   if (per_cu) *per_cu = 0;
   if (stage_bytes) *stage_bytes = 0;
   if (!desc_ok(d)) return -1;
-  if (wgrad_halo_eligible(d) || wgrad_up_eligible(d) || wgrad_stem_eligible(d)) return 0;
-  const int SZ = d->dtype == CTSEG_F32 ? 4 : 2, EPC = 16 / SZ;
-  const bool smallc = (d->Cg % EPC) != 0 || (d->g_ld % EPC) != 0 || ((uintptr_t)d->in % 16) != 0;
-  if (!smallc && wgrad_ring_eligible(d)) {
-    if (per_cu) *per_cu = 1;
-    return wgrad_ring_wgs_per_slab(d, stage_bytes);
+  switch (select_wgrad_pass(d)) {
+    case WgradPass::RING:
+      if (per_cu) *per_cu = 1;
+      return wgrad_ring_wgs_per_slab(d, stage_bytes);
+    case WgradPass::GENERIC: {
+      const int bnw = ctseg_wgrad_tile_cols(d->Cn);
+      if (per_cu) *per_cu = 4;
+      if (stage_bytes) *stage_bytes = 32 * (128 + bnw) * (d->dtype == CTSEG_F32 ? 4 : 2);
+      return (d->kpad_w / 128) * (d->cn_pad / bnw);
+    }
+    default: return 0;
   }
-  const int bnw = ctseg_wgrad_tile_cols(d->Cn);
-  if (per_cu) *per_cu = 4;
-  if (stage_bytes) *stage_bytes = 32 * (128 + bnw) * SZ;
-  return (d->kpad_w / 128) * (d->cn_pad / bnw);
 }
 
 extern "C" int ctseg_wgrad_in_norm_ok(const ctseg_wgrad_desc* d) { return (desc_ok(d) && d->dtype == CTSEG_BF16 && wgrad_halo_in_norm_ok(d)) ? 1 : 0; }
 
 extern "C" int ctseg_wgrad_dy_norm_ok(const ctseg_wgrad_desc* d) {
   if (!desc_ok(d) || d->dyn_col0 <= 0 || d->in_mean_rstd != nullptr) return 0;
-  if (wgrad_halo_eligible(d) || wgrad_up_eligible(d)) return 0;
-  return (wgrad_stem_eligible(d) && wgrad_stem_dyn_ok(d)) ? 1 : 0;
+  return wgrad_dy_norm_ok(d, select_wgrad_pass(d)) ? 1 : 0;
 }
 
 extern "C" int ctseg_wgrad_narrow_ok(const ctseg_wgrad_desc* d) {
   if (!desc_ok(d)) return 0;
-  if (wgrad_halo_eligible(d)) return 1;
-  return (d->d_ld != 12 && wgrad_up_eligible(d)) ? 1 : 0;      // the stride-2 transposed-conv kernel takes a 12-wide gathered operand
+  const WgradPass p = select_wgrad_pass(d);
+  // the stride-2 transposed-conv kernel takes a 12-wide gathered operand
+  return (p == WgradPass::HALO || (p == WgradPass::UP && d->d_ld != 12)) ? 1 : 0;
 }
 
 extern "C" int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream) {
   CTSEG_REQUIRE_DESC(d, "conv_wgrad");
   CTSEG_REQUIRE(d->in && d->dy && d->ws, "conv_wgrad: null pointer");
   CTSEG_REQUIRE(d->dtype == CTSEG_F32 || d->dtype == CTSEG_BF16, "conv_wgrad: bad dtype");
+  CTSEG_REQUIRE(d->ntaps >= 1 && d->ntaps <= CTSEG_MAX_TAPS && d->splits >= 1, "conv_wgrad: ntaps/splits");
   const int SZ = d->dtype == CTSEG_F32 ? 4 : 2, EPC = 16 / SZ;
-  const bool halo = wgrad_halo_eligible(d);     // also moves 12-wide bf16 rows (ctseg_wgrad_narrow_ok)
+  const WgradPass pass = select_wgrad_pass(d);
+  const bool halo = pass == WgradPass::HALO;     // (also moves 12-wide bf16 rows: ctseg_wgrad_narrow_ok)
   if (d->dyn_g != nullptr)
-    CTSEG_REQUIRE(ctseg_wgrad_dy_norm_ok(d) == 1 && d->dyn_y && d->dyn_mean_rstd && d->dyn_alpha && d->dyn_sums &&
+    CTSEG_REQUIRE(wgrad_dy_norm_ok(d, pass) && d->dyn_y && d->dyn_mean_rstd && d->dyn_alpha && d->dyn_sums &&
                       ((uintptr_t)d->dyn_g % 16) == 0 && ((uintptr_t)d->dyn_y % 16) == 0,
                   "conv_wgrad: dyn_* (dY formed on load) is not implemented for this pass (ask ctseg_wgrad_dy_norm_ok)");
   else
@@ -577,33 +605,37 @@ extern "C" int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream) {
     CTSEG_REQUIRE(halo && wgrad_halo_in_norm_ok(d) && d->in_alpha != nullptr,
                   "conv_wgrad: in_mean_rstd (normalise the operand on load) is not implemented for this pass (ask ctseg_wgrad_in_norm_ok)");
   CTSEG_REQUIRE((d->d_ld % EPC == 0 || halo) && ((uintptr_t)d->dy % 16) == 0, "conv_wgrad: dy must be 16-byte chunked");
-  CTSEG_REQUIRE(halo || wgrad_up_eligible(d) || d->dtype != CTSEG_BF16 || d->g_ld != 12 || d->Cg != 16,
+  CTSEG_REQUIRE(halo || pass == WgradPass::UP || d->dtype != CTSEG_BF16 || d->g_ld != 12 || d->Cg != 16,
                 "conv_wgrad: 12-wide rows need an LDS-halo kernel");
-  const bool smallc = (d->Cg % EPC) != 0 || (d->g_ld % EPC) != 0 || ((uintptr_t)d->in % 16) != 0;
-  CTSEG_REQUIRE(d->ntaps >= 1 && d->ntaps <= CTSEG_MAX_TAPS && d->splits >= 1, "conv_wgrad: ntaps/splits");
   const int bnw = ctseg_wgrad_tile_cols(d->Cn);
   const int ktot = d->ntaps * d->Cg;
-  if (halo) {
-    CTSEG_REQUIRE(d->kpad_w >= ktot + 16 && d->cn_pad >= ((d->Cn + 15) / 16) * 16, "conv_wgrad: slab too small for the halo kernel");
-    launch_wgrad_halo(d, (hipStream_t)stream);
-    CTSEG_LAUNCH_CHECK("conv_wgrad_halo");
-    return 0;
+  hipStream_t st = (hipStream_t)stream;
+  switch (pass) {
+    case WgradPass::HALO:
+      CTSEG_REQUIRE(d->kpad_w >= ktot + 16 && d->cn_pad >= ((d->Cn + 15) / 16) * 16, "conv_wgrad: slab too small for the halo kernel");
+      launch_wgrad_halo(d, st);
+      CTSEG_LAUNCH_CHECK("conv_wgrad_halo");
+      return 0;
+    case WgradPass::UP:
+      launch_wgrad_up(d, st);
+      CTSEG_LAUNCH_CHECK("conv_wgrad_up");
+      return 0;
+    case WgradPass::STEM:
+      launch_wgrad_stem(d, st);
+      CTSEG_LAUNCH_CHECK("conv_wgrad_stem");
+      return 0;
+    default: break;
   }
-  if (wgrad_up_eligible(d)) {
-    launch_wgrad_up(d, (hipStream_t)stream);
-    CTSEG_LAUNCH_CHECK("conv_wgrad_up");
-    return 0;
-  }
-  if (wgrad_stem_eligible(d)) {
-    launch_wgrad_stem(d, (hipStream_t)stream);
-    CTSEG_LAUNCH_CHECK("conv_wgrad_stem");
-    return 0;
-  }
+  // the ring and generic kernels: `splits` row ranges per sample, 32-row aligned, addressed with 32-bit offsets
   CTSEG_REQUIRE(d->kpad_w % 128 == 0 && d->kpad_w >= ktot + 1, "conv_wgrad: kpad_w %d (K=%d)", d->kpad_w, ktot);
   CTSEG_REQUIRE(d->cn_pad % bnw == 0 && d->cn_pad >= d->Cn, "conv_wgrad: cn_pad %d", d->cn_pad);
-  if (!smallc && wgrad_ring_eligible(d)) {
-    const int rc = launch_wgrad_ring(d, (hipStream_t)stream);
-    CTSEG_REQUIRE(rc == 0, "conv_wgrad: the ring kernel cannot take this row grid (%d)", rc);
+  const int64_t rows64 = (int64_t)d->Xr * d->Yr * d->Zr;
+  CTSEG_REQUIRE(rows64 < (1ll << 31) - 4096, "conv_wgrad: row grid too large");
+  int rps = (int)((rows64 + d->splits - 1) / d->splits);
+  rps = ((rps + 31) / 32) * 32;
+  CTSEG_REQUIRE((int64_t)(rps + 64) * d->d_ld * SZ < ((int64_t)1 << 31), "conv_wgrad: rows per split * row bytes exceed 32-bit offsets (raise splits)");
+  if (pass == WgradPass::RING) {
+    launch_wgrad_ring(d, rps, st);
     CTSEG_LAUNCH_CHECK("conv_wgrad_ring");
     return 0;
   }
@@ -611,13 +643,7 @@ extern "C" int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream) {
   a.in = (const char*)d->in; a.dy = (const char*)d->dy; a.ws = d->ws;
   a.N = d->N; a.Xi = d->Xi; a.Yi = d->Yi; a.Zi = d->Zi; a.Xr = d->Xr; a.Yr = d->Yr; a.Zr = d->Zr;
   a.Cg = d->Cg; a.Cn = d->Cn; a.g_ld = d->g_ld; a.d_ld = d->d_ld; a.sin = d->sin; a.ntaps = d->ntaps;
-  const int64_t rows64 = (int64_t)d->Xr * d->Yr * d->Zr;
-  CTSEG_REQUIRE(rows64 < (1ll << 31) - 4096, "conv_wgrad: row grid too large");
-  a.rows = (int)rows64; a.splits = d->splits;
-  int rps = (int)((rows64 + d->splits - 1) / d->splits);
-  rps = ((rps + 31) / 32) * 32;
-  a.rows_per_split = rps;
-  CTSEG_REQUIRE((int64_t)(rps + 64) * d->d_ld * SZ < ((int64_t)1 << 31), "conv_wgrad: rows per split * row bytes exceed 32-bit offsets (raise splits)");
+  a.rows = (int)rows64; a.splits = d->splits; a.rows_per_split = rps;
   a.kpad_w = d->kpad_w; a.cn_pad = d->cn_pad;
   int dv = ((d->Cn + EPC - 1) / EPC) * EPC;
   a.d_valid = dv < d->d_ld ? dv : d->d_ld;
@@ -625,7 +651,7 @@ extern "C" int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream) {
   a.sz = step % d->Zr; step /= d->Zr;
   a.sy = step % d->Yr; a.sx = step / d->Yr;
   for (int i = 0; i < CTSEG_MAX_TAPS; ++i) a.taps[i] = i < d->ntaps ? d->taps[i] : 0;
-  hipStream_t st = (hipStream_t)stream;
+  const bool smallc = wgrad_small_operand(d);
   if (d->dtype == CTSEG_F32) { if (smallc) launch_wgrad<float, true>(a, st); else launch_wgrad<float, false>(a, st); }
   else { if (smallc) launch_wgrad<BF16, true>(a, st); else launch_wgrad<BF16, false>(a, st); }
   CTSEG_LAUNCH_CHECK("conv_wgrad");
@@ -636,8 +662,7 @@ extern "C" int ctseg_conv_wgrad_reduce(const float* ws, int32_t nslabs, int32_t 
                                        int32_t T, int32_t col0, int32_t nb, float* dw, float* db, void* stream) {
   CTSEG_REQUIRE(ws && dw && nslabs >= 1 && A <= AS && T * AS + 1 <= kpad_w && col0 + nb <= cn_pad, "wgrad_reduce: bad arguments");
   const int64_t total = (int64_t)(T * AS + 1) * nb;
-  if ((col0 & 3) == 0 && (cn_pad & 3) == 0 && col0 + ((nb + 3) & ~3) <= cn_pad && ((uintptr_t)ws & 15) == 0 &&
-      getenv("CTSEG_WGRAD_REDUCE_SCALAR") == nullptr) {
+  if (ctseg_conv_wgrad_reduce_batch_ok(ws, cn_pad, col0, nb)) {
     const int total4 = (T * AS + 1) * ((nb + 3) / 4);
     if (nslabs >= 64)
       hipLaunchKernelGGL((wgrad_reduce4_kernel<8, 32>), dim3((unsigned)((total4 + 7) / 8)), dim3(256), 0, (hipStream_t)stream, ws, nslabs, kpad_w,
@@ -661,8 +686,7 @@ extern "C" int ctseg_conv_wgrad_reduce(const float* ws, int32_t nslabs, int32_t 
 }
 
 extern "C" int ctseg_conv_wgrad_reduce_batch_ok(const float* ws, int32_t cn_pad, int32_t col0, int32_t nb) {
-  return ((col0 & 3) == 0 && (cn_pad & 3) == 0 && col0 + ((nb + 3) & ~3) <= cn_pad && ((uintptr_t)ws & 15) == 0 &&
-          getenv("CTSEG_WGRAD_REDUCE_SCALAR") == nullptr) ? 1 : 0;
+  return ((col0 & 3) == 0 && (cn_pad & 3) == 0 && col0 + ((nb + 3) & ~3) <= cn_pad && ((uintptr_t)ws & 15) == 0) ? 1 : 0;
 }
 
 extern "C" int ctseg_conv_wgrad_reduce_batch(const ctseg_reduce_job* jobs, int32_t n_jobs, int32_t total_blocks, void* stream) {

@@ -642,7 +642,7 @@ static int wgrad_halo_grid(const ctseg_wgrad_desc* d) {
   // more workgroups per CU than this measured no faster with the single staging buffer (0.245 / 0.250 / 0.255 ms at 1 / 2 / 3
   // per CU for the 32->32 layer); the smaller LDS footprint is kept for what it leaves to the main stream's kernels
   int per_cu = (vb + db <= 64) ? 2 : 1;
-  if (vb == 32 && db == 32 && getenv("CTSEG_WGRAD_HEAD_OLD") == nullptr && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16))
+  if (vb == 32 && db == 32 && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16))
     per_cu = wgrad_head2(d) ? 1 : 4;      // 27 KB of LDS, 128 registers: four 4-wave or two 8-wave workgroups per CU would fit.
   // ONE 8-wave workgroup per CU for the head kernel: alone it is slower that way (0.43 -> 0.50 ms), inside the step — it runs on the
   // side stream beside the main stream's HBM-bound head passes — faster: 9.94 / 9.90 -> 9.86 / 9.82 ms/step (same box, round 2)
@@ -657,8 +657,7 @@ static bool wgrad_head2(const ctseg_wgrad_desc* d) {
     if ((int)(int8_t)(tp & 0xff) != j / 9 - 1 || (int)(int8_t)((tp >> 8) & 0xff) != (j / 3) % 3 - 1 || (int)(int8_t)((tp >> 16) & 0xff) != j % 3 - 1)
       return false;
   }
-  return vb == 32 && db == 32 && getenv("CTSEG_WGRAD_HEAD_OLD") == nullptr && getenv("CTSEG_WGRAD_HEAD_V1") == nullptr &&
-         (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16);
+  return vb == 32 && db == 32 && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16);
 }
 
 bool wgrad_halo_in_norm_ok(const ctseg_wgrad_desc* d) { return wgrad_halo_eligible(d) && wgrad_head2(d) && d->N <= WH_NRM_MAXN && d->in_norm_C <= 12; }
@@ -683,7 +682,7 @@ void launch_wgrad_halo(const ctseg_wgrad_desc* d, hipStream_t st) {
   }
   const int total = a.tiles * d->N, grid = wgrad_halo_grid(d);
   const int vb = d->Cg * 2, db = ((d->Cn + 15) / 16) * 32;
-  if (vb == 32 && db == 32 && getenv("CTSEG_WGRAD_HEAD_OLD") == nullptr && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16)) {
+  if (vb == 32 && db == 32 && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16)) {
     const int xsb = (int)((int64_t)d->Xi * d->Yi * d->Zi * d->g_ld * 2), dsb = (int)((int64_t)d->Xi * d->Yi * d->Zi * d->d_ld * 2);
     const bool v2 = wgrad_head2(d);
 #define WH_GO(NX, ND)                                                                                                       \
@@ -697,7 +696,6 @@ void launch_wgrad_halo(const ctseg_wgrad_desc* d, hipStream_t st) {
   } else if (vb == 32 && db == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<32, 32, 4>), dim3(grid), dim3(256), 0, st, a, total);
   else if (vb == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<32, 64, 4>), dim3(grid), dim3(256), 0, st, a, total);
   else if (db == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, 32, 4>), dim3(grid), dim3(256), 0, st, a, total);
-  else if (getenv("CTSEG_WGRAD_HALO_4W") != nullptr) hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, 64, 4>), dim3(grid), dim3(256), 0, st, a, total);
   else hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, 64, 8>), dim3(grid), dim3(512), 0, st, a, total);
 }
 

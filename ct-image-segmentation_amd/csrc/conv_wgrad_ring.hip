@@ -432,8 +432,7 @@ using WRingC = WRingCfg<8, 1, 4, 4, 4>;    // 512 x 64
 
 // which tile serves this descriptor: 0 none, 1 = A, 2 = B, 3 = C
 static int wring_kind(const ctseg_wgrad_desc* d) {
-  const char* e = getenv("CTSEG_WGRAD_RING");          // (read per call: the A/B tools and the parity test flip it inside one process)
-  if ((e != nullptr && atoi(e) == 0) || d->dtype != CTSEG_BF16) return 0;
+  if (d->dtype != CTSEG_BF16) return 0;
   if (d->Cg % 8 != 0 || d->g_ld % 8 != 0 || d->d_ld % 8 != 0 || ((uintptr_t)d->in % 16) != 0 || ((uintptr_t)d->dy % 16) != 0) return 0;
   if (d->Cg < 32 || d->Cn < 64 || d->ntaps > 32) return 0;
   for (int t = 0; t < d->ntaps; ++t)                        // the row table keeps one bit per neighbour in {-1, 0, 1}^3
@@ -443,8 +442,7 @@ static int wring_kind(const ctseg_wgrad_desc* d) {
     }
   if (d->dyn_g != nullptr || d->in_mean_rstd != nullptr) return 0;
   if ((int64_t)d->Xi * d->Yi * d->Zi * d->g_ld * 2 >= ((int64_t)1 << 31) - 4096) return 0;      // 32-bit buffer offsets inside a sample
-  const char* ea = getenv("CTSEG_WGRAD_RING_A");       // (A/B: 0 keeps the 256 x 128 tile for the 256-column layers)
-  if (d->cn_pad % 256 == 0 && !(ea != nullptr && atoi(ea) == 0)) return 1;
+  if (d->cn_pad % 256 == 0) return 1;
   if (d->cn_pad % 128 == 0) return 2;
   if (d->cn_pad == 64) return 3;
   return 0;
@@ -467,26 +465,21 @@ template <typename C> static void launch_wring(WRingKArgs& a, hipStream_t st) {
   a.ktiles = (ktot + 1 + C::KB - 1) / C::KB;
   a.ctiles = a.cn_pad / C::BN;
   const int zs = a.N * a.splits, tiles = a.ktiles * a.ctiles;
-  static const bool remap = !(getenv("CTSEG_WGRAD_XCD") && atoi(getenv("CTSEG_WGRAD_XCD")) == 0);
-  a.xcd = (remap && zs % 8 == 0 && tiles > 1) ? 1 : 0;
+  a.xcd = (zs % 8 == 0 && tiles > 1) ? 1 : 0;
   const dim3 grid = a.xcd ? dim3((unsigned)(tiles * zs), 1u, 1u) : dim3((unsigned)tiles, (unsigned)zs, 1u);
   hipLaunchKernelGGL((conv_wgrad_ring_kernel<C>), grid, dim3(512), 0, st, a);
 }
 
-int launch_wgrad_ring(const ctseg_wgrad_desc* d, hipStream_t st) {
+// rows_per_split: checked by the entry point (32-row aligned, its row bytes within 32-bit offsets)
+void launch_wgrad_ring(const ctseg_wgrad_desc* d, int rows_per_split, hipStream_t st) {
   const int kind = wring_kind(d);
   WRingKArgs a;
   a.in = (const char*)d->in; a.dy = (const char*)d->dy; a.ws = d->ws;
   a.N = d->N; a.Xi = d->Xi; a.Yi = d->Yi; a.Zi = d->Zi; a.Xr = d->Xr; a.Yr = d->Yr; a.Zr = d->Zr;
   a.Cg = d->Cg; a.Cn = d->Cn; a.g_ld = d->g_ld; a.d_ld = d->d_ld; a.sin = d->sin; a.ntaps = d->ntaps;
-  const int64_t rows64 = (int64_t)d->Xr * d->Yr * d->Zr;
-  if (rows64 >= (1ll << 31) - 4096) return -1;
-  a.rows = (int)rows64; a.splits = d->splits;
-  int rps = (int)((rows64 + d->splits - 1) / d->splits);
-  rps = ((rps + 31) / 32) * 32;
-  a.rows_per_split = rps;
-  if ((int64_t)(rps + 64) * d->d_ld * 2 >= ((int64_t)1 << 31)) return -2;
-  int nst = rps / 32;
+  a.rows = d->Xr * d->Yr * d->Zr; a.splits = d->splits;
+  a.rows_per_split = rows_per_split;
+  int nst = rows_per_split / 32;
   if (nst < 8) nst = 8;          // >= D + 2 for every ring depth instantiated below
   nst += nst & 1;
   a.nst = nst;
@@ -500,7 +493,6 @@ int launch_wgrad_ring(const ctseg_wgrad_desc* d, hipStream_t st) {
   if (kind == 1) launch_wring<WRingA>(a, st);
   else if (kind == 2) launch_wring<WRingB>(a, st);
   else launch_wring<WRingC>(a, st);
-  return 0;
 }
 
 }  // namespace ctseg

@@ -209,7 +209,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs
 }
 
 bool wgrad_up_eligible(const ctseg_wgrad_desc* d) {
-  if (getenv("CTSEG_NO_WGRAD_UP") != nullptr) return false;
   if (d->dtype != CTSEG_BF16 || d->sin != 2 || d->ntaps != 27 || d->Cg != 16 || (d->g_ld != 16 && d->g_ld != 12) || d->Cn != 64 || d->d_ld != 64) return false;
   if (d->Xi != 2 * d->Xr || d->Yi != 2 * d->Yr || d->Zi != 2 * d->Zr) return false;
   if (d->kpad_w < 27 * 16 || d->cn_pad < 64) return false;

@@ -532,7 +532,7 @@ extern "C" int ctseg_instnorm_finalize(const float* partials, int32_t N, int32_t
   hipStream_t st = (hipStream_t)stream;
   // scratch: N * FIN_GROUPS * 2 * ld doubles of group sums, followed by N zero-initialised counters (one double slot each)
   unsigned int* counter = reinterpret_cast<unsigned int*>(scratch + (int64_t)N * FIN_GROUPS * 2 * ld);
-  if (P <= 8192 && getenv("CTSEG_FINALIZE_TWO_LEVEL") == nullptr) {
+  if (P <= 8192) {
     if (P <= 1024) hipLaunchKernelGGL(instnorm_finalize1_kernel<16>, dim3((C + 7) / 8, N), dim3(256), 0, st, partials, P, ld, col0, C, count, eps, mean_rstd);
     else hipLaunchKernelGGL(instnorm_finalize1_kernel<64>, dim3((C + 7) / 8, N), dim3(1024), 0, st, partials, P, ld, col0, C, count, eps, mean_rstd);
     CTSEG_LAUNCH_CHECK("instnorm_finalize");

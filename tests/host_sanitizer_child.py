@@ -77,6 +77,13 @@ def rand_wgrad():
     d.kpad_w = (d.ntaps * d.Cg + 1 + 127) // 128 * 128
     d.cn_pad = (d.Cn + 127) // 128 * 128
     d.in_, d.dy, d.ws = base, base + 4096, base + 8192
+    if rnd.random() < 0.3:
+        d.in_mean_rstd, d.in_alpha, d.in_norm_C = base, base, rnd.choice([10, 12, 32])
+    if rnd.random() < 0.4:
+        d.dyn_col0 = rnd.choice([0, 16, 32, d.Cn // 2])
+        if rnd.random() < 0.7:
+            d.dyn_g, d.dyn_y, d.dyn_mean_rstd, d.dyn_alpha, d.dyn_sums = base + 12288, base + 16384, base, base, base
+        d.dyn_g_ld, d.dyn_y_ld = rnd.choice([12, 16, 32]), rnd.choice([12, 16, 32])
     return d
 
 
@@ -99,11 +106,15 @@ for _ in range(2000):
     w = rand_wgrad()
     r = ctypes.byref(w)
     L.ctseg_conv_wgrad_slabs(r)
+    per_cu, stage_bytes = ctypes.c_int32(), ctypes.c_int32()
+    L.ctseg_conv_wgrad_wgs_per_slab(r, ctypes.byref(per_cu), ctypes.byref(stage_bytes))
+    L.ctseg_conv_wgrad_wgs_per_slab(r, None, None)
+    L.ctseg_wgrad_dy_norm_ok(r)
     L.ctseg_wgrad_narrow_ok(r)
     L.ctseg_wgrad_in_norm_ok(r)
     w.ws = None
     assert L.ctseg_conv_wgrad(r, None) < 0
-    n += 4
+    n += 7
 for c in (1, 10, 16, 33, 64, 200, 256, 1024):
     L.ctseg_conv_tile_rows(c), L.ctseg_conv_tile_cols(c), L.ctseg_wgrad_tile_cols(c)
 assert L.ctseg_adam_step(None, None, None, None, 10, 1e-3, 0.9, 0.999, 1e-8, 1, 1.0, None) < 0
