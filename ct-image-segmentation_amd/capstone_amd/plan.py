@@ -24,6 +24,16 @@ def _is_seq(m):
     return isinstance(m, nn.Sequential) and not hasattr(m, "conv_only")
 
 
+def _bwd_row_ranges(S, N, dt):
+    """row ranges per sample of a norm backward's reduce pass: 512 rows each on the big levels; on the small ones enough ranges
+    for ~1024 workgroups in all (the 25 MB bottom-level pass ran 96 workgroups: 70 us, 28 us with 1024; not below 32 rows per
+    range)"""
+    P = max(1, min(1024, math.ceil(S / 512)))
+    if nat.is16(dt):      # (fp32 storage keeps its partition: the 40-step fp32 trajectory test pins a summation order)
+        P = max(P, min(math.ceil(1024 / N), math.ceil(S / 32)))
+    return P
+
+
 def _parts(conv):
     return (conv.weight, conv.bias, conv.out_channels)
 
@@ -80,11 +90,7 @@ class _NormAct:
         on load (ctseg_wgrad_desc::dyn_*); returns the finalised sums instead."""
         plan, y = self.plan, self.y
         N, S, C = y.dims[0], y.S, y.C
-        # row ranges per sample: 512 rows each on the big levels; on the small ones enough ranges for ~1024 workgroups in all (the
-        # 25 MB bottom-level pass ran 96 workgroups: 70 us, 28 us with 1024; not below 32 rows per range)
-        P = max(1, min(1024, math.ceil(S / 512)))
-        if nat.is16(plan.dt):      # (fp32 storage keeps its partition: the 40-step fp32 trajectory test pins a summation order)
-            P = max(P, min(math.ceil(1024 / N), math.ceil(S / 32)))
+        P = _bwd_row_ranges(S, N, plan.dt)
         ld = rup(C, 4)
         sums = torch.zeros((N, C, 2), dtype=torch.float32, device=plan.device)
         if dy_out is None and apply:
@@ -179,9 +185,7 @@ class _BatchNormAct:
         assert self.train and apply and colsum_out is None
         plan, st, y = self.plan, self.plan.store, self.y
         N, S, C = y.dims[0], y.S, y.C
-        P = max(1, min(1024, math.ceil(S / 512)))          # row ranges per sample, as the InstanceNorm backward
-        if nat.is16(plan.dt):
-            P = max(P, min(math.ceil(1024 / N), math.ceil(S / 32)))
+        P = _bwd_row_ranges(S, N, plan.dt)
         ld = rup(C, 4)
         if dy_out is None:
             dy_out = new_act(*y.dims, C, plan.dt, plan.device)

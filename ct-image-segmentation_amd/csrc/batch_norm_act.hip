@@ -8,13 +8,12 @@
 //                      -> scale_shift_prelu_fwd
 //   eval forward     : batchnorm_eval_table (scale/shift from the running statistics) -> scale_shift_prelu_fwd
 //   training backward: bn_prelu_bwd_reduce -> bn_prelu_bwd_finalize (d gamma, d beta) -> bn_prelu_bwd_apply (dy, d alpha)
-#include "ctseg_dev.h"
+#include "norm_common.h"
 
 namespace ctseg {
 
-// partials: R = N * P rows of [2][ld] fp32 (sample-major, so the rows of all samples are contiguous).  One block per 8 channels:
-// 16 columns (8 sums, 8 sums of squares) x RL row lanes; lane r adds rows r, r + RL, ... in fp64, the RL sub-sums combine in
-// lane order.  Threads t < 8 then own one channel each: statistics, tables and the running-statistics update.
+// partials: R = N * P rows of [2][ld] fp32 (sample-major, so the rows of all samples are contiguous).  One block per 8 channels
+// (col16_stats); threads t < 8 then own one channel each: statistics, tables and the running-statistics update.
 template <int RL>
 __global__ __launch_bounds__(16 * RL) void bn_finalize_kernel(const float* __restrict__ part, int R, int ld, int col0, int C,
                                                              double count, double eps, double momentum,
@@ -22,26 +21,9 @@ __global__ __launch_bounds__(16 * RL) void bn_finalize_kernel(const float* __res
                                                              float* __restrict__ running_mean, float* __restrict__ running_var,
                                                              int64_t* __restrict__ nbt, float* __restrict__ mean_rstd,
                                                              float* __restrict__ scale_shift) {
-  __shared__ double s_sub[RL][17];
   const int c0 = blockIdx.x * 8, t = threadIdx.x;
-  const int col = t & 15, r = t >> 4;
-  const int c = c0 + (col & 7);
-  double s = 0.0;
-  if (c < C) {
-    const float* p = part + (col >> 3) * ld + col0 + c;
-#pragma unroll 4
-    for (int row = r; row < R; row += RL) s += (double)p[(int64_t)row * 2 * ld];
-  }
-  s_sub[r][col] = s;
-  __syncthreads();
-  if (t < 8 && c0 + t < C) {
-    const int ch = c0 + t;
-    double sm = 0.0, q = 0.0;
-#pragma unroll
-    for (int k = 0; k < RL; ++k) { sm += s_sub[k][t]; q += s_sub[k][8 + t]; }
-    const double mean = sm / count;
-    double var = q / count - mean * mean;
-    if (var < 0.0) var = 0.0;
+  col16_stats<RL>(part, R, ld, col0, C, count, c0, t, [&](int k, double mean, double var) NORM_FN {
+    const int ch = c0 + k;
     const double rstd = 1.0 / sqrt(var + eps);
     const double sc = (double)gamma[ch] * rstd;
     mean_rstd[2 * ch] = (float)mean;
@@ -51,7 +33,7 @@ __global__ __launch_bounds__(16 * RL) void bn_finalize_kernel(const float* __res
     const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
     running_mean[ch] = (float)((1.0 - momentum) * (double)running_mean[ch] + momentum * mean);
     running_var[ch] = (float)((1.0 - momentum) * (double)running_var[ch] + momentum * unbiased);
-  }
+  });
   if (blockIdx.x == 0 && t == 0) nbt[0] = nbt[0] + 1;
 }
 
@@ -73,14 +55,14 @@ __global__ __launch_bounds__(256) void scale_shift_prelu_fwd_kernel(const char* 
                                                                      int res_ld, char* __restrict__ out, int out_ld, int64_t S,
                                                                      int C, int Cv) {
   constexpr int SZ = TT<T>::SZ;
-  extern __shared__ float s_ss[];   // per chunk [EPC][2] + 1 pad word
-  constexpr int TB = 2 * EPC + 1;
+  extern __shared__ float s_ss[];   // tab_row<2, EPC>: (scale, shift) of each channel
   const int n = blockIdx.y;
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) s_ss[((i >> 1) / EPC) * TB + ((i >> 1) % EPC) * 2 + (i & 1)] = scale_shift[i];
+  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) tab_row<2, EPC>(s_ss, i >> 1)[i & 1] = scale_shift[i];
   __syncthreads();
   const float al = alpha[0];
-  const int64_t total = S * Cv;
-  auto body = [&](int64_t v, int cv) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  chunk_sweep_fwd(i0, stride, S, Cv, [&](int64_t v, int cv) {
+    const float* tab = tab_chunk<2, EPC>(s_ss, cv);
     const int64_t vox = (int64_t)n * S + v;
     float x[EPC], r[EPC];
     load_ep<T, EPC>(y + (vox * y_ld + cv * EPC) * SZ, x);
@@ -90,26 +72,14 @@ __global__ __launch_bounds__(256) void scale_shift_prelu_fwd_kernel(const char* 
       const int c = cv * EPC + e;
       float o = 0.f;
       if (c < C) {
-        o = x[e] * s_ss[cv * TB + 2 * e] + s_ss[cv * TB + 2 * e + 1];
+        o = x[e] * tab[2 * e] + tab[2 * e + 1];
         o = o > 0.f ? o : al * o;
         if (res != nullptr) o += r[e];
       }
       x[e] = o;
     }
     store_ep<T, EPC>(out + (vox * out_ld + cv * EPC) * SZ, x);
-  };
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x, i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (stride % Cv == 0) {
-    int64_t v = i0 / Cv;
-    const int cv = (int)(i0 - v * Cv);
-    const int64_t vstep = stride / Cv;
-    for (; v < S; v += vstep) body(v, cv);
-  } else {
-    for (int64_t i = i0; i < total; i += stride) {
-      const int64_t v = i / Cv;
-      body(v, (int)(i - v * Cv));
-    }
-  }
+  });
 }
 
 // backward pass 1, per block (p, n): rows [p*rows_per, ...) of sample n -> partials[n][p][3][ld] =
@@ -120,14 +90,10 @@ __global__ __launch_bounds__(256) void bn_prelu_bwd_reduce_kernel(const char* __
                                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                    const float* __restrict__ alpha, float* __restrict__ partials,
                                                                    int P, int ld, int64_t S, int C, int Cv) {
-  constexpr int SZ = TT<T>::SZ;
-  extern __shared__ float s_tab[];
-  constexpr int TB = 4 * EPC + 1;       // (mean, rstd, gamma, beta) per channel of a chunk + a pad word
-  float* const s_red = s_tab + Cv * TB;
-  const bool pow2 = (Cv & (Cv - 1)) == 0 && Cv <= 64;
-  const int p = blockIdx.x, n = blockIdx.y;
+  extern __shared__ float s_tab[];       // tab_row<4, EPC>: mean, rstd, gamma, beta of each channel, then the reduction scratch
+  const int n = blockIdx.y;
   for (int i = threadIdx.x; i < C; i += blockDim.x) {
-    float* t = s_tab + (i / EPC) * TB + (i % EPC) * 4;
+    float* t = tab_row<4, EPC>(s_tab, i);
     t[0] = mean_rstd[2 * i];
     t[1] = mean_rstd[2 * i + 1];
     t[2] = gamma[i];
@@ -135,75 +101,16 @@ __global__ __launch_bounds__(256) void bn_prelu_bwd_reduce_kernel(const char* __
   }
   __syncthreads();
   const float al = alpha[0];
-  const int64_t rows_per = (S + P - 1) / P;
-  const int64_t v0 = p * rows_per, v1 = (v0 + rows_per < S) ? v0 + rows_per : S;
-  const int nrow_thr = 256 / Cv;
-  const int cv = threadIdx.x % Cv, rsub = threadIdx.x / Cv;
-  float a1[EPC], a2[EPC], a3[EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) a1[e] = a2[e] = a3[e] = 0.f;
-  if (rsub < nrow_thr) {
-    const float* tab = s_tab + cv * TB;
-    for (int64_t v = v0 + rsub; v < v1; v += nrow_thr) {
-      const int64_t vox = (int64_t)n * S + v;
-      float gv[EPC], yv[EPC];
-      load_ep<T, EPC>(g + (vox * g_ld + cv * EPC) * SZ, gv);
-      load_ep<T, EPC>(y + (vox * y_ld + cv * EPC) * SZ, yv);
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) {
-        if (cv * EPC + e < C) {
-          const float xh = (yv[e] - tab[4 * e]) * tab[4 * e + 1];
-          const float z = tab[4 * e + 2] * xh + tab[4 * e + 3];
-          const float dz = gv[e] * (z > 0.f ? 1.f : al);
-          a1[e] += dz;
-          a2[e] += dz * xh;
-          a3[e] += z > 0.f ? 0.f : gv[e] * z;
-        }
-      }
-    }
-  }
-  if (pow2) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int e = 0; e < EPC; ++e)
-      for (int o = 32; o >= Cv; o >>= 1) {
-        a1[e] += __shfl_xor(a1[e], o, 64);
-        a2[e] += __shfl_xor(a2[e], o, 64);
-        a3[e] += __shfl_xor(a3[e], o, 64);
-      }
-    if (lane < Cv) {
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) {
-        s_red[((wave * Cv + lane) * 3 + 0) * EPC + e] = a1[e];
-        s_red[((wave * Cv + lane) * 3 + 1) * EPC + e] = a2[e];
-        s_red[((wave * Cv + lane) * 3 + 2) * EPC + e] = a3[e];
-      }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 3 * C; i += blockDim.x) {
-      const int which = i / C, c = i - which * C;
-      const int ccv = c / EPC, e = c - ccv * EPC;
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) s += s_red[((w * Cv + ccv) * 3 + which) * EPC + e];
-      partials[(((int64_t)n * P + p) * 3 + which) * ld + c] = s;
-    }
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) {
-    s_red[(threadIdx.x * 3 + 0) * EPC + e] = a1[e];
-    s_red[(threadIdx.x * 3 + 1) * EPC + e] = a2[e];
-    s_red[(threadIdx.x * 3 + 2) * EPC + e] = a3[e];
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * C; i += blockDim.x) {
-    const int which = i / C, c = i - which * C;
-    const int ccv = c / EPC, e = c - ccv * EPC;
-    float s = 0.f;
-    for (int r = 0; r < nrow_thr; ++r) s += s_red[((r * Cv + ccv) * 3 + which) * EPC + e];
-    partials[(((int64_t)n * P + p) * 3 + which) * ld + c] = s;
-  }
+  bwd_reduce_rows<T, EPC>(g, g_ld, y, y_ld, partials, tab_chunk<4, EPC>(s_tab, Cv), P, ld, S, C, Cv, blockIdx.x, n, threadIdx.x,
+                          [&](int cv, int e, float gv, float yv, float& a1, float& a2, float& a3) NORM_FN {
+    const float* tab = tab_chunk<4, EPC>(s_tab, cv);
+    const float xh = (yv - tab[4 * e]) * tab[4 * e + 1];
+    const float z = tab[4 * e + 2] * xh + tab[4 * e + 3];
+    const float dz = gv * (z > 0.f ? 1.f : al);
+    a1 += dz;
+    a2 += dz * xh;
+    a3 += z > 0.f ? 0.f : gv * z;
+  });
 }
 
 // backward pass 2, one block per channel: the R = N * P partial rows in a fixed tree -> d beta, d gamma (straight into the flat
@@ -212,27 +119,15 @@ __global__ __launch_bounds__(256) void bn_prelu_bwd_finalize_kernel(const float*
                                                                     float* __restrict__ sums, float* __restrict__ dgamma,
                                                                     float* __restrict__ dbeta, double* __restrict__ da_part) {
   __shared__ double s_acc[3][4];
-  const int c = blockIdx.x, t = threadIdx.x;
-  double s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  for (int row = t; row < R; row += 256) {
-    const float* q = partials + (int64_t)row * 3 * ld + c;
-    s1 += (double)q[0];
-    s2 += (double)q[ld];
-    s3 += (double)q[2 * ld];
-  }
-  s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
-  if ((t & 63) == 0) { s_acc[0][t >> 6] = s1; s_acc[1][t >> 6] = s2; s_acc[2][t >> 6] = s3; }
-  __syncthreads();
-  if (t == 0) {
-    const double db = ((s_acc[0][0] + s_acc[0][1]) + s_acc[0][2]) + s_acc[0][3];
-    const double dg = ((s_acc[1][0] + s_acc[1][1]) + s_acc[1][2]) + s_acc[1][3];
-    const double da = ((s_acc[2][0] + s_acc[2][1]) + s_acc[2][2]) + s_acc[2][3];
+  const int c = blockIdx.x;
+  block_sum3(R, ld, threadIdx.x, s_acc, [&](int row) NORM_FN { return partials + (int64_t)row * 3 * ld + c; },
+             [&](double db, double dg, double da) NORM_FN {
     sums[2 * c] = (float)(db / M);
     sums[2 * c + 1] = (float)(dg / M);
     dbeta[c] = (float)db;
     dgamma[c] = (float)dg;
     da_part[c] = da;
-  }
+  });
 }
 
 // backward pass 3: dy = gamma * rstd * (dz - d beta / M - xhat * d gamma / M) [+ g copied to g_copy]; block (0, 0) also writes
@@ -248,20 +143,11 @@ __global__ __launch_bounds__(256) void bn_prelu_bwd_apply_kernel(const char* __r
                                                                   const double* __restrict__ da_part, int n_da,
                                                                   float* __restrict__ dalpha) {
   constexpr int SZ = TT<T>::SZ;
-  extern __shared__ float s_tab[];   // per chunk [EPC][6] + 1 pad: mean, rstd, gamma, beta, s1, s2
-  if (da_part != nullptr && blockIdx.x == 0 && blockIdx.y == 0) {
-    __shared__ double s_da[4];
-    double a = 0.0;
-    for (int k = threadIdx.x; k < n_da; k += 256) a += da_part[k];
-    a = wave_sum(a);
-    if ((threadIdx.x & 63) == 0) s_da[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) dalpha[0] = (float)(((s_da[0] + s_da[1]) + s_da[2]) + s_da[3]);
-  }
+  extern __shared__ float s_tab[];   // tab_row<6, EPC>: mean, rstd, gamma, beta, s1, s2 of each channel
+  if (da_part != nullptr && blockIdx.x == 0 && blockIdx.y == 0) slope_grad_sum(da_part, n_da, dalpha, threadIdx.x);
   const int n = gridDim.y - 1 - blockIdx.y;
-  constexpr int TB = 6 * EPC + 1;
   for (int i = threadIdx.x; i < C; i += blockDim.x) {
-    float* t = s_tab + (i / EPC) * TB + (i % EPC) * 6;
+    float* t = tab_row<6, EPC>(s_tab, i);
     t[0] = mean_rstd[2 * i];
     t[1] = mean_rstd[2 * i + 1];
     t[2] = gamma[i];
@@ -271,9 +157,9 @@ __global__ __launch_bounds__(256) void bn_prelu_bwd_apply_kernel(const char* __r
   }
   __syncthreads();
   const float al = alpha[0];
-  const int64_t total = S * Cv;
-  auto body = [&](int64_t v, int cv) {
-    const float* tab = s_tab + cv * TB;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, ir0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  chunk_sweep_bwd(ir0, stride, S * Cv, Cv, [&](int64_t v, int cv) {
+    const float* tab = tab_chunk<6, EPC>(s_tab, cv);
     const int64_t vox = (int64_t)n * S + v;
     float gv[EPC], yv[EPC], o[EPC];
     load_ep<T, EPC>(g + (vox * g_ld + cv * EPC) * SZ, gv);
@@ -290,65 +176,14 @@ __global__ __launch_bounds__(256) void bn_prelu_bwd_apply_kernel(const char* __r
       }
       o[e] = r;
     }
-    bool whole_row = false;
-    if constexpr (EPC * SZ == 8) whole_row = cv == Cv - 1 && dy_ld == (Cv + 1) * EPC;
-    if constexpr (EPC * SZ == 8) {
-      if (whole_row) {
-        // 8-byte chunks into rows one chunk wider than the channels: the last chunk and the padding as ONE 16-byte store
-        float o2[2 * EPC];
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) { o2[e] = o[e]; o2[EPC + e] = 0.f; }
-        store_ep<T, 2 * EPC>(dy + (vox * dy_ld + cv * EPC) * SZ, o2);
-      }
-    }
-    if (!whole_row) store_ep<T, EPC>(dy + (vox * dy_ld + cv * EPC) * SZ, o);
+    store_dy_chunk<T, EPC>(dy, dy_ld, vox, cv, Cv, o);
     if (g_copy != nullptr) store_ep<T, EPC>(g_copy + (vox * g_copy_ld + cv * EPC) * SZ, gv);
-  };
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x, ir0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (stride % Cv == 0) {
-    if (ir0 < total) {
-      const int64_t i = total - 1 - ir0;
-      int64_t v = i / Cv;
-      const int cv = (int)(i - v * Cv);
-      const int64_t vstep = stride / Cv;
-      for (; v >= 0; v -= vstep) body(v, cv);
-    }
-  } else {
-    for (int64_t ir = ir0; ir < total; ir += stride) {
-      const int64_t i = total - 1 - ir;
-      const int64_t v = i / Cv;
-      body(v, (int)(i - v * Cv));
-    }
-  }
-}
-
-static inline int bn_blocks_for(int64_t total, int Cv) {
-  int64_t b64 = (total + 255) / 256;
-  int b = (int)(b64 > 4096 ? 4096 : (b64 < 1 ? 1 : b64)), step = Cv;
-  while (step % 2 == 0) step /= 2;          // 256 supplies the twos: blocks * 256 becomes a multiple of Cv
-  if (b >= step) b = b / step * step;
-  return b;
+  });
 }
 
 }  // namespace ctseg
 
 using namespace ctseg;
-
-// EPC_: 16-byte chunks, or 8-byte ones for 16-bit storage when a channel stride is a multiple of 4 but not of 8 (12-wide rows)
-#define BN_CHECK_CL(dtype, C, FWD_ONLY_OK, ...)                                                                      \
-  CTSEG_REQUIRE(dtype == CTSEG_F32 || dtype == CTSEG_BF16 || (FWD_ONLY_OK && dtype == CTSEG_F16),                      \
-                "bad dtype %d (CTSEG_F16 is accepted by the forward pass only)", dtype);                              \
-  int EPC_ = dtype == CTSEG_F32 ? 4 : 8;                                                                              \
-  {                                                                                                                   \
-    const int lds_[] = {__VA_ARGS__};                                                                                 \
-    if (is16(dtype))                                                                                                  \
-      for (int ld_ : lds_) if (ld_ % 8 != 0) EPC_ = 4;                                                                \
-  }                                                                                                                   \
-  const int Cv = (C + EPC_ - 1) / EPC_;                                                                               \
-  {                                                                                                                   \
-    const int lds_[] = {__VA_ARGS__};                                                                                 \
-    for (int ld_ : lds_) CTSEG_REQUIRE(ld_ % EPC_ == 0 && ld_ >= Cv * EPC_, "channel stride %d not chunked for C=%d", ld_, C); \
-  }
 
 extern "C" int ctseg_batchnorm_finalize(const float* partials, int32_t N, int32_t P, int32_t ld, int32_t col0, int32_t C,
                                         double count, double eps, double momentum, const float* gamma, const float* beta,
@@ -382,18 +217,14 @@ extern "C" int ctseg_scale_shift_prelu_fwd(int32_t dtype, const void* y, int32_t
                                            const void* res, int32_t res_ld, void* out, int32_t out_ld, int32_t N, int64_t S,
                                            int32_t C, void* stream) {
   CTSEG_REQUIRE(y && out && scale_shift && alpha && N > 0 && S > 0 && C > 0, "scale_shift_prelu_fwd: bad arguments");
-  BN_CHECK_CL(dtype, C, true, y_ld, out_ld, res ? res_ld : y_ld);
-  dim3 grid(bn_blocks_for(S * Cv, Cv), N);
+  CHECK_CL(dtype, C, true, true, y_ld, out_ld, res ? res_ld : y_ld);
+  dim3 grid(ew_blocks_for(S * Cv, Cv), N);
   const size_t sh = Cv * (2 * EPC_ + 1) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-#define CTSEG_SSF(T, EP)                                                                                                     \
-  hipLaunchKernelGGL((scale_shift_prelu_fwd_kernel<T, EP>), grid, dim3(256), sh, st, (const char*)y, y_ld, scale_shift, alpha, \
-                     (const char*)res, res_ld, (char*)out, out_ld, S, C, Cv)
-  if (dtype == CTSEG_F32) CTSEG_SSF(float, 4);
-  else if (dtype == CTSEG_F16) { if (EPC_ == 8) CTSEG_SSF(F16, 8); else CTSEG_SSF(F16, 4); }
-  else if (EPC_ == 8) CTSEG_SSF(BF16, 8);
-  else CTSEG_SSF(BF16, 4);
-#undef CTSEG_SSF
+  dispatch_chunk<true>(dtype, EPC_, [&](auto t, auto ep) {
+    hipLaunchKernelGGL((scale_shift_prelu_fwd_kernel<decltype(t), ep>), grid, dim3(256), sh, st, (const char*)y, y_ld, scale_shift,
+                       alpha, (const char*)res, res_ld, (char*)out, out_ld, S, C, Cv);
+  });
   CTSEG_LAUNCH_CHECK("scale_shift_prelu_fwd");
   return 0;
 }
@@ -403,18 +234,15 @@ extern "C" int ctseg_batchnorm_prelu_bwd_reduce(int32_t dtype, const void* g, in
                                                 float* partials, int32_t P, int32_t ld, int32_t N, int64_t S, int32_t C, void* stream) {
   CTSEG_REQUIRE(g && y && mean_rstd && gamma && beta && alpha && partials && P > 0 && N > 0 && S > 0 && C > 0 && C <= ld,
                 "batchnorm_prelu_bwd_reduce: bad arguments");
-  BN_CHECK_CL(dtype, C, false, g_ld, y_ld);
+  CHECK_CL(dtype, C, true, false, g_ld, y_ld);
   CTSEG_REQUIRE(Cv <= 256, "batchnorm_prelu_bwd_reduce: too many channels");
   const bool pow2 = (Cv & (Cv - 1)) == 0 && Cv <= 64;
   const size_t sh = (Cv * (4 * EPC_ + 1) + (pow2 ? 4 * Cv * 3 * EPC_ : 256 * 3 * EPC_)) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-#define CTSEG_BRED(T, EP)                                                                                                      \
-  hipLaunchKernelGGL((bn_prelu_bwd_reduce_kernel<T, EP>), dim3(P, N), dim3(256), sh, st, (const char*)g, g_ld, (const char*)y, y_ld, \
-                     mean_rstd, gamma, beta, alpha, partials, P, ld, S, C, Cv)
-  if (dtype == CTSEG_F32) CTSEG_BRED(float, 4);
-  else if (EPC_ == 8) CTSEG_BRED(BF16, 8);
-  else CTSEG_BRED(BF16, 4);
-#undef CTSEG_BRED
+  dispatch_chunk<false>(dtype, EPC_, [&](auto t, auto ep) {
+    hipLaunchKernelGGL((bn_prelu_bwd_reduce_kernel<decltype(t), ep>), dim3(P, N), dim3(256), sh, st, (const char*)g, g_ld, (const char*)y,
+                       y_ld, mean_rstd, gamma, beta, alpha, partials, P, ld, S, C, Cv);
+  });
   CTSEG_LAUNCH_CHECK("batchnorm_prelu_bwd_reduce");
   return 0;
 }
@@ -436,17 +264,14 @@ extern "C" int ctseg_batchnorm_prelu_bwd_apply(int32_t dtype, const void* g, int
   CTSEG_REQUIRE(g && y && mean_rstd && gamma && beta && alpha && sums && dy && N > 0 && S > 0 && C > 0,
                 "batchnorm_prelu_bwd_apply: bad arguments");
   CTSEG_REQUIRE(da_part == nullptr || (dalpha != nullptr && n_da > 0), "batchnorm_prelu_bwd_apply: slope-gradient arguments");
-  BN_CHECK_CL(dtype, C, false, g_ld, y_ld, dy_ld, g_copy ? g_copy_ld : dy_ld);
-  dim3 grid(bn_blocks_for(S * Cv, Cv), N);
+  CHECK_CL(dtype, C, true, false, g_ld, y_ld, dy_ld, g_copy ? g_copy_ld : dy_ld);
+  dim3 grid(ew_blocks_for(S * Cv, Cv), N);
   const size_t sh = Cv * (6 * EPC_ + 1) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-#define CTSEG_BAPPLY(T, EP)                                                                                                    \
-  hipLaunchKernelGGL((bn_prelu_bwd_apply_kernel<T, EP>), grid, dim3(256), sh, st, (const char*)g, g_ld, (const char*)y, y_ld,     \
-                     mean_rstd, gamma, beta, alpha, sums, (char*)dy, dy_ld, (char*)g_copy, g_copy_ld, S, C, Cv, da_part, n_da, dalpha)
-  if (dtype == CTSEG_F32) CTSEG_BAPPLY(float, 4);
-  else if (EPC_ == 8) CTSEG_BAPPLY(BF16, 8);
-  else CTSEG_BAPPLY(BF16, 4);
-#undef CTSEG_BAPPLY
+  dispatch_chunk<false>(dtype, EPC_, [&](auto t, auto ep) {
+    hipLaunchKernelGGL((bn_prelu_bwd_apply_kernel<decltype(t), ep>), grid, dim3(256), sh, st, (const char*)g, g_ld, (const char*)y, y_ld,
+                       mean_rstd, gamma, beta, alpha, sums, (char*)dy, dy_ld, (char*)g_copy, g_copy_ld, S, C, Cv, da_part, n_da, dalpha);
+  });
   CTSEG_LAUNCH_CHECK("batchnorm_prelu_bwd_apply");
   return 0;
 }

@@ -5,7 +5,7 @@
 // Statistics arrive as per-tile (sum, sumsq) partials from the conv epilogue and are combined in
 // fp64 in a fixed order (deterministic).  All passes are HBM-bound: 16-byte vector accesses,
 // per-sample mean/rstd staged in LDS, wave/LDS reductions for the backward sums.
-#include "ctseg_dev.h"
+#include "norm_common.h"
 
 namespace ctseg {
 
@@ -75,35 +75,17 @@ __global__ __launch_bounds__(256) void instnorm_finalize_kernel(const float* __r
 }
 
 // Single-level finalize for P <= 8192 partial rows (the per-workgroup slots of the halo kernels: <= 512; the per-tile slots of the
-// generic kernel: a few thousand): one block per (sample, 8 channels) — 16 columns (8 sums, 8 sums of squares) x RL row lanes; lane r
-// adds rows r, r + RL, ... in fp64, the RL sub-sums combine in lane order: fixed order, no atomics, and no cross-block hand-off.  The two-level kernel above publishes its group sums
+// generic kernel: a few thousand): one block per (sample, 8 channels), col16_stats -- no cross-block hand-off.  The two-level kernel above publishes its group sums
 // with an agent-scope release per block (buffer_wbl2: an L2 write-back walk, serialised per XCD): 64 groups x N samples of them cost
 // 21 us at N = 2 and 262 us at the 48 windows of a sliding-window forward, for 12 MB of partials.
 template <int RL>      // row lanes: 16 (256 threads) up to 1024 partial rows, 64 (1024 threads) up to 8192
 __global__ __launch_bounds__(16 * RL) void instnorm_finalize1_kernel(const float* __restrict__ part, int P, int ld, int col0, int C, double count,
                                                                      double eps, float* __restrict__ mean_rstd) {
-  __shared__ double s_sub[RL][17];
-  const int n = blockIdx.y, c0 = blockIdx.x * 8, t = threadIdx.x;
-  const int col = t & 15, r = t >> 4;                 // col < 8: sum of channel c0 + col; col >= 8: sum of squares of channel c0 + col - 8
-  const int c = c0 + (col & 7);
-  double s = 0.0;
-  if (c < C) {
-    const float* p = part + (int64_t)n * P * 2 * ld + (col >> 3) * ld + col0 + c;
-#pragma unroll 4
-    for (int row = r; row < P; row += RL) s += (double)p[(int64_t)row * 2 * ld];
-  }
-  s_sub[r][col] = s;
-  __syncthreads();
-  if (t < 8 && c0 + t < C) {
-    double sm = 0.0, q = 0.0;
-#pragma unroll
-    for (int k = 0; k < RL; ++k) { sm += s_sub[k][t]; q += s_sub[k][8 + t]; }
-    const double mean = sm / count;
-    double var = q / count - mean * mean;
-    if (var < 0.0) var = 0.0;
+  const int n = blockIdx.y, c0 = blockIdx.x * 8;
+  col16_stats<RL>(part + (int64_t)n * P * 2 * ld, P, ld, col0, C, count, c0, threadIdx.x, [&](int t, double mean, double var) NORM_FN {
     mean_rstd[((int64_t)n * C + c0 + t) * 2] = (float)mean;
     mean_rstd[((int64_t)n * C + c0 + t) * 2 + 1] = (float)(1.0 / sqrt(var + eps));
-  }
+  });
 }
 
 template <typename T, int EPC>
@@ -113,15 +95,15 @@ __global__ __launch_bounds__(256) void instnorm_prelu_fwd_kernel(const char* __r
                                                                   int res_ld, char* __restrict__ out, int out_ld, int64_t S,
                                                                   int C, int Cv) {
   constexpr int SZ = TT<T>::SZ;   // EPC: elements per chunk (a row is Cv chunks of EPC elements)
-  extern __shared__ float s_mr[];  // per chunk [EPC][2] + 1 pad word (consecutive lanes read consecutive chunks: conflict-free)
-  constexpr int TB = 2 * EPC + 1;
+  extern __shared__ float s_mr[];  // tab_row<2, EPC>: (mean, rstd) of each channel
   const int n = blockIdx.y;
   if (mean_rstd != nullptr)
-    for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) s_mr[((i >> 1) / EPC) * TB + ((i >> 1) % EPC) * 2 + (i & 1)] = mean_rstd[(int64_t)n * C * 2 + i];
+    for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) tab_row<2, EPC>(s_mr, i >> 1)[i & 1] = mean_rstd[(int64_t)n * C * 2 + i];
   __syncthreads();
   const float al = alpha != nullptr ? alpha[0] : 1.f;
-  const int64_t total = S * Cv;
-  auto body = [&](int64_t v, int cv) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  chunk_sweep_fwd(i0, stride, S, Cv, [&](int64_t v, int cv) {
+    const float* tab = tab_chunk<2, EPC>(s_mr, cv);
     const int64_t vox = (int64_t)n * S + v;
     float x[EPC], r[EPC];
     load_ep<T, EPC>(y + (vox * y_ld + cv * EPC) * SZ, x);
@@ -133,7 +115,7 @@ __global__ __launch_bounds__(256) void instnorm_prelu_fwd_kernel(const char* __r
       if (c < C) {
         o = x[e];
         if (mean_rstd != nullptr) {
-          o = (o - s_mr[cv * TB + 2 * e]) * s_mr[cv * TB + 2 * e + 1];
+          o = (o - tab[2 * e]) * tab[2 * e + 1];
           o = o > 0.f ? o : al * o;
         }
         if (res != nullptr) o += r[e];
@@ -141,24 +123,10 @@ __global__ __launch_bounds__(256) void instnorm_prelu_fwd_kernel(const char* __r
       x[e] = o;
     }
     store_ep<T, EPC>(out + (vox * out_ld + cv * EPC) * SZ, x);
-  };
-  // a thread keeps its channel chunk when the grid stride is a multiple of Cv (the launcher arranges it): no 64-bit
-  // division per element, and the per-channel constants stay in registers
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x, i0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (stride % Cv == 0) {
-    int64_t v = i0 / Cv;
-    const int cv = (int)(i0 - v * Cv);
-    const int64_t vstep = stride / Cv;
-    for (; v < S; v += vstep) body(v, cv);
-  } else {
-    for (int64_t i = i0; i < total; i += stride) {
-      const int64_t v = i / Cv;
-      body(v, (int)(i - v * Cv));
-    }
-  }
+  });
 }
 
-// backward pass 1: per block (p, n): rows [p*rows_per, ...) of sample n -> partials[n][p][3][ld]
+// backward pass 1: per block (p, n): rows [p*rows_per, ...) of sample n -> partials[n][p][3][ld] (bwd_reduce_rows)
 template <typename T, int EPC>
 __global__ __launch_bounds__(256) void instnorm_prelu_bwd_reduce_kernel(const char* __restrict__ g, int g_ld,
                                                                          const char* __restrict__ y, int y_ld,
@@ -166,114 +134,33 @@ __global__ __launch_bounds__(256) void instnorm_prelu_bwd_reduce_kernel(const ch
                                                                          const float* __restrict__ alpha,
                                                                          float* __restrict__ partials, int P, int ld, int64_t S,
                                                                          int C, int Cv) {
-  constexpr int SZ = TT<T>::SZ;   // EPC: elements per chunk (a row is Cv chunks of EPC elements)
-  // dynamic LDS: [2*C] mean/rstd, then the cross-thread reduction scratch -- 4 waves x Cv x 3 x EPC floats when Cv is a power
-  // of two <= 64 (wave butterflies first), else one slot per thread.  The footprint matters: this pass shares the CUs with
-  // the weight-gradient kernels of the side stream, and at 24 KB per block few of its blocks found room beside them.
-  extern __shared__ float s_mr[];
-  constexpr int TB = 2 * EPC + 1;       // (mean, rstd) of a chunk's channels + a pad word: conflict-free across consecutive chunks
-  float* const s_red = s_mr + Cv * TB;
-  const bool pow2 = (Cv & (Cv - 1)) == 0 && Cv <= 64;
-  const int p = blockIdx.x, n = blockIdx.y;
-  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) s_mr[((i >> 1) / EPC) * TB + ((i >> 1) % EPC) * 2 + (i & 1)] = mean_rstd[(int64_t)n * C * 2 + i];
+  extern __shared__ float s_mr[];       // tab_row<2, EPC>: (mean, rstd) of each channel, then the reduction scratch
+  const int n = blockIdx.y;
+  for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) tab_row<2, EPC>(s_mr, i >> 1)[i & 1] = mean_rstd[(int64_t)n * C * 2 + i];
   __syncthreads();
   const float al = alpha[0];
-  const int64_t rows_per = (S + P - 1) / P;
-  const int64_t v0 = p * rows_per, v1 = (v0 + rows_per < S) ? v0 + rows_per : S;
-  const int nrow_thr = 256 / Cv;  // threads along rows
-  const int cv = threadIdx.x % Cv, rsub = threadIdx.x / Cv;
-  float a1[EPC], a2[EPC], a3[EPC];
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) a1[e] = a2[e] = a3[e] = 0.f;
-  if (rsub < nrow_thr) {
-    for (int64_t v = v0 + rsub; v < v1; v += nrow_thr) {
-      const int64_t vox = (int64_t)n * S + v;
-      float gv[EPC], yv[EPC];
-      load_ep<T, EPC>(g + (vox * g_ld + cv * EPC) * SZ, gv);
-      load_ep<T, EPC>(y + (vox * y_ld + cv * EPC) * SZ, yv);
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) {
-        const int c = cv * EPC + e;
-        if (c < C) {
-          const float xh = (yv[e] - s_mr[cv * TB + 2 * e]) * s_mr[cv * TB + 2 * e + 1];
-          const float dxh = gv[e] * (xh > 0.f ? 1.f : al);
-          a1[e] += dxh;
-          a2[e] += dxh * xh;
-          a3[e] += xh > 0.f ? 0.f : gv[e] * xh;
-        }
-      }
-    }
-  }
-  if (pow2) {
-    // lanes l, l + Cv, l + 2 Cv ... of a wave hold the same channel chunk (64 % Cv == 0): xor butterfly, then 4 waves via LDS
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int e = 0; e < EPC; ++e)
-      for (int o = 32; o >= Cv; o >>= 1) {
-        a1[e] += __shfl_xor(a1[e], o, 64);
-        a2[e] += __shfl_xor(a2[e], o, 64);
-        a3[e] += __shfl_xor(a3[e], o, 64);
-      }
-    if (lane < Cv) {
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) {
-        s_red[((wave * Cv + lane) * 3 + 0) * EPC + e] = a1[e];
-        s_red[((wave * Cv + lane) * 3 + 1) * EPC + e] = a2[e];
-        s_red[((wave * Cv + lane) * 3 + 2) * EPC + e] = a3[e];
-      }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 3 * C; i += blockDim.x) {
-      const int which = i / C, c = i - which * C;
-      const int ccv = c / EPC, e = c - ccv * EPC;
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) s += s_red[((w * Cv + ccv) * 3 + which) * EPC + e];
-      partials[(((int64_t)n * P + p) * 3 + which) * ld + c] = s;
-    }
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < EPC; ++e) {
-    s_red[(threadIdx.x * 3 + 0) * EPC + e] = a1[e];
-    s_red[(threadIdx.x * 3 + 1) * EPC + e] = a2[e];
-    s_red[(threadIdx.x * 3 + 2) * EPC + e] = a3[e];
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < 3 * C; i += blockDim.x) {
-    const int which = i / C, c = i - which * C;
-    const int ccv = c / EPC, e = c - ccv * EPC;
-    float s = 0.f;
-    for (int r = 0; r < nrow_thr; ++r) s += s_red[((r * Cv + ccv) * 3 + which) * EPC + e];
-    partials[(((int64_t)n * P + p) * 3 + which) * ld + c] = s;
-  }
+  bwd_reduce_rows<T, EPC>(g, g_ld, y, y_ld, partials, tab_chunk<2, EPC>(s_mr, Cv), P, ld, S, C, Cv, blockIdx.x, n, threadIdx.x,
+                          [&](int cv, int e, float gv, float yv, float& a1, float& a2, float& a3) NORM_FN {
+    const float* tab = tab_chunk<2, EPC>(s_mr, cv);
+    const float xh = (yv - tab[2 * e]) * tab[2 * e + 1];
+    const float dxh = gv * (xh > 0.f ? 1.f : al);
+    a1 += dxh;
+    a2 += dxh * xh;
+    a3 += xh > 0.f ? 0.f : gv * xh;
+  });
 }
 
 __global__ __launch_bounds__(256) void instnorm_prelu_bwd_finalize_kernel(const float* __restrict__ partials, int P, int ld, int C,
                                                                            double S, float* __restrict__ sums,
                                                                            double* __restrict__ da_part, float* __restrict__ dalpha) {
-  // one block per (n, c): 256 strided sub-sums over the P partial rows, combined by a fixed tree (deterministic): wave
-  // butterflies, then the four wave sums in order -- a few bytes of LDS, so the block fits on a CU whatever else runs there
+  // one block per (n, c): the P partial rows of the sample in block_sum3's fixed tree (deterministic)
   __shared__ double s_acc[3][4];
   const int i = blockIdx.x, n = i / C, c = i - n * C, t = threadIdx.x;
-  double s1 = 0.0, s2 = 0.0, s3 = 0.0;
-  for (int p = t; p < P; p += 256) {
-    const float* q = partials + ((int64_t)n * P + p) * 3 * ld + c;
-    s1 += (double)q[0];
-    s2 += (double)q[ld];
-    s3 += (double)q[2 * ld];
-  }
-  s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
-  if ((t & 63) == 0) { s_acc[0][t >> 6] = s1; s_acc[1][t >> 6] = s2; s_acc[2][t >> 6] = s3; }
-  __syncthreads();
-  if (t == 0) {
-    const double r1 = ((s_acc[0][0] + s_acc[0][1]) + s_acc[0][2]) + s_acc[0][3];
-    const double r2 = ((s_acc[1][0] + s_acc[1][1]) + s_acc[1][2]) + s_acc[1][3];
-    const double r3 = ((s_acc[2][0] + s_acc[2][1]) + s_acc[2][2]) + s_acc[2][3];
+  block_sum3(P, ld, t, s_acc, [&](int p) NORM_FN { return partials + ((int64_t)n * P + p) * 3 * ld + c; }, [&](double r1, double r2, double r3) NORM_FN {
     sums[(int64_t)i * 2] = (float)(r1 / S);
     sums[(int64_t)i * 2 + 1] = (float)(r2 / S);
     da_part[i] = r3;
-  }
+  });
   if (dalpha == nullptr) return;
   // PReLU slope gradient = fixed-order sum of every block's third partial: done by whichever block finishes last (a counter
   // in the slot behind the gridDim.x partials, reset for the next call) -- no extra launch.  A separate one-block kernel on
@@ -324,30 +211,14 @@ __global__ __launch_bounds__(256) void instnorm_prelu_bwd_apply_kernel(const cha
                                                                         int pld, const double* __restrict__ da_part, int n_da,
                                                                         float* __restrict__ dalpha) {
   constexpr int SZ = TT<T>::SZ;   // EPC: elements per chunk (a row is Cv chunks of EPC elements)
-  extern __shared__ float s_tab[];  // per chunk [EPC][4] + 1 pad: mean, rstd, s1, s2  (+ [256][EPC] column-sum scratch when COLSUM)
+  extern __shared__ float s_tab[];  // tab_row<4, EPC>: mean, rstd, s1, s2 of each channel (+ [256][EPC] column-sum scratch when COLSUM)
   float cs[EPC];
 #pragma unroll
   for (int e = 0; e < EPC; ++e) cs[e] = 0.f;
-  // PReLU slope gradient = fixed-order sum of the finalize pass's per-(n, c) terms: one block of this launch does it on the
-  // side (no launch of its own, no atomics -- a same-address counter in the finalize cost ~40 ns per block, 20 us at C = 256)
-  if (da_part != nullptr && blockIdx.x == 0 && blockIdx.y == 0) {
-    __shared__ double s_da[4];
-    double a = 0.0;
-    for (int k = threadIdx.x; k < n_da; k += 256) a += da_part[k];
-    a = wave_sum(a);
-    if ((threadIdx.x & 63) == 0) s_da[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) dalpha[0] = (float)(((s_da[0] + s_da[1]) + s_da[2]) + s_da[3]);
-  }
-  // the reduce pass that precedes this one streamed (g, y) front to back: walk BACKWARDS (last sample first, last voxel
-  // first) so the most recently read part of both tensors is re-read while it still sits in L2 / Infinity Cache
-  const int n = gridDim.y - 1 - blockIdx.y;
-  // table layout: the 4 constants of the EPC channels of chunk cv at cv * (4 * EPC + 1): consecutive lanes read consecutive chunks,
-  // and without the pad word their addresses are 4 * EPC floats apart — a 32-way bank conflict on every read at C = 256 (the
-  // 25 MB bottom-level pass took 91 us, the 151 MB level-1 pass 47)
-  constexpr int TB = 4 * EPC + 1;
+  if (da_part != nullptr && blockIdx.x == 0 && blockIdx.y == 0) slope_grad_sum(da_part, n_da, dalpha, threadIdx.x);
+  const int n = gridDim.y - 1 - blockIdx.y;      // last sample first: chunk_sweep_bwd
   for (int i = threadIdx.x; i < C; i += blockDim.x) {
-    float* t = s_tab + (i / EPC) * TB + (i % EPC) * 4;
+    float* t = tab_row<4, EPC>(s_tab, i);
     t[0] = mean_rstd[((int64_t)n * C + i) * 2];
     t[1] = mean_rstd[((int64_t)n * C + i) * 2 + 1];
     t[2] = sums[((int64_t)n * C + i) * 2];
@@ -356,8 +227,9 @@ __global__ __launch_bounds__(256) void instnorm_prelu_bwd_apply_kernel(const cha
   __syncthreads();
   const float al = alpha[0];
   const int64_t total = S * Cv;
-  auto body = [&](int64_t v, int cv) {
-    const float* tab = s_tab + cv * TB;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x, ir0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  chunk_sweep_bwd(ir0, stride, total, Cv, [&](int64_t v, int cv) {
+    const float* tab = tab_chunk<4, EPC>(s_tab, cv);
     const int64_t vox = (int64_t)n * S + v;
     float gv[EPC], yv[EPC], o[EPC];
     load_ep<T, EPC>(g + (vox * g_ld + cv * EPC) * SZ, gv);
@@ -370,43 +242,13 @@ __global__ __launch_bounds__(256) void instnorm_prelu_bwd_apply_kernel(const cha
       o[e] = r;
       if (COLSUM) cs[e] += r;
     }
-    bool whole_row = false;
-    if constexpr (EPC * SZ == 8) whole_row = cv == Cv - 1 && dy_ld == (Cv + 1) * EPC;
-    if constexpr (EPC * SZ == 8) {
-      if (whole_row) {
-      // 8-byte chunks into rows one chunk wider than the channels (12-wide inputs, 16-wide dy): the last chunk and the
-      // padding go out as ONE 16-byte store, so every 32-byte row is written whole (no partial sectors at the memory side)
-      float o2[2 * EPC];
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) { o2[e] = o[e]; o2[EPC + e] = 0.f; }
-        store_ep<T, 2 * EPC>(dy + (vox * dy_ld + cv * EPC) * SZ, o2);
-      }
-    }
-    if (!whole_row) store_ep<T, EPC>(dy + (vox * dy_ld + cv * EPC) * SZ, o);
+    store_dy_chunk<T, EPC>(dy, dy_ld, vox, cv, Cv, o);
     if (g_copy != nullptr) store_ep<T, EPC>(g_copy + (vox * g_copy_ld + cv * EPC) * SZ, gv);
-  };
-  {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, ir0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (stride % Cv == 0) {       // fixed channel chunk per thread: no 64-bit division per element
-      if (ir0 < total) {
-        const int64_t i = total - 1 - ir0;
-        int64_t v = i / Cv;
-        const int cv = (int)(i - v * Cv);
-        const int64_t vstep = stride / Cv;
-        for (; v >= 0; v -= vstep) body(v, cv);
-      }
-    } else {
-      for (int64_t ir = ir0; ir < total; ir += stride) {
-        const int64_t i = total - 1 - ir;
-        const int64_t v = i / Cv;
-        body(v, (int)(i - v * Cv));
-      }
-    }
-  }
+  });
   if constexpr (COLSUM) {
     // (gridDim.x * 256) % Cv == 0: thread t handled the same chunk column in every iteration (the sweep runs backwards from
     // total - 1, total = S * Cv); fixed-order sums of the threads of each column
-    float* s_cs = s_tab + Cv * TB;
+    float* s_cs = tab_chunk<4, EPC>(s_tab, Cv);
     const int64_t lead = (int64_t)blockIdx.x * 256;
     if ((Cv & (Cv - 1)) == 0 && Cv <= 64) {
       // power-of-two Cv: lanes l, l + Cv, l + 2 Cv, ... of a wave share the column -> xor butterfly, then 4 waves through LDS
@@ -489,41 +331,9 @@ __global__ __launch_bounds__(1024) void colsum_final_kernel(const float* __restr
   }
 }
 
-static inline int ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
-}
-// grid whose stride (blocks * 256) is a multiple of Cv, so that a thread keeps one channel chunk (256 supplies the twos)
-static inline int ew_blocks_for(int64_t total, int Cv) {
-  int b = ew_blocks(total), step = Cv;
-  while (step % 2 == 0) step /= 2;
-  if (b >= step) b = b / step * step;
-  return b;
-}
-
 }  // namespace ctseg
 
 using namespace ctseg;
-
-// EPC_ = elements per chunk the launch works in: 16-byte chunks, or 8-byte ones for bf16 when some tensor's channel stride
-// is a multiple of 4 but not of 8 (10 classes stored 12 wide); every stride must then be a multiple of 4
-#define CHECK_CL_(dtype, C, ALLOW_HALF, FWD_ONLY_OK, ...)                                                               \
-  CTSEG_REQUIRE(dtype == CTSEG_F32 || dtype == CTSEG_BF16 || (FWD_ONLY_OK && dtype == CTSEG_F16),           \
-                "bad dtype %d (CTSEG_F16 is accepted by the forward pass only)", dtype);                   \
-  int EPC_ = dtype == CTSEG_F32 ? 4 : 8;                                                                   \
-  {                                                                                                        \
-    const int lds_[] = {__VA_ARGS__};                                                                      \
-    if (ALLOW_HALF && is16(dtype))                                                                         \
-      for (int ld_ : lds_) if (ld_ % 8 != 0) EPC_ = 4;                                                     \
-  }                                                                                                        \
-  const int Cv = (C + EPC_ - 1) / EPC_;                                                                    \
-  {                                                                                                        \
-    const int lds_[] = {__VA_ARGS__};                                                                      \
-    for (int ld_ : lds_) CTSEG_REQUIRE(ld_ % EPC_ == 0 && ld_ >= Cv * EPC_, "channel stride %d not chunked for C=%d", ld_, C); \
-  }
-#define CHECK_CL(dtype, C, ...) CHECK_CL_(dtype, C, false, false, __VA_ARGS__)
-#define CHECK_CL_HALF(dtype, C, ...) CHECK_CL_(dtype, C, true, false, __VA_ARGS__)
-#define CHECK_CL_HALF_FWD(dtype, C, ...) CHECK_CL_(dtype, C, true, true, __VA_ARGS__)
 
 extern "C" int ctseg_instnorm_finalize(const float* partials, int32_t N, int32_t P, int32_t ld, int32_t col0, int32_t C,
                                        double count, double eps, double* scratch, float* mean_rstd, void* stream) {
@@ -550,19 +360,15 @@ extern "C" int ctseg_instnorm_prelu_fwd(int32_t dtype, const void* y, int32_t y_
                                         const void* res, int32_t res_ld, void* out, int32_t out_ld, int32_t N, int64_t S,
                                         int32_t C, void* stream) {
   CTSEG_REQUIRE(y && out && N > 0 && S > 0 && C > 0, "instnorm_prelu_fwd: bad arguments");
-  CHECK_CL_HALF_FWD(dtype, C, y_ld, out_ld, res ? res_ld : y_ld);
+  CHECK_CL(dtype, C, true, true, y_ld, out_ld, res ? res_ld : y_ld);
   CTSEG_REQUIRE(mean_rstd == nullptr || alpha != nullptr, "instnorm_prelu_fwd: alpha missing");
   dim3 grid(ew_blocks_for(S * Cv, Cv), N);
   const size_t sh = Cv * (2 * EPC_ + 1) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-#define CTSEG_FWD(T, EP)                                                                                                      \
-  hipLaunchKernelGGL((instnorm_prelu_fwd_kernel<T, EP>), grid, dim3(256), sh, st, (const char*)y, y_ld, mean_rstd, alpha,     \
-                     (const char*)res, res_ld, (char*)out, out_ld, S, C, Cv)
-  if (dtype == CTSEG_F32) CTSEG_FWD(float, 4);
-  else if (dtype == CTSEG_F16) { if (EPC_ == 8) CTSEG_FWD(F16, 8); else CTSEG_FWD(F16, 4); }
-  else if (EPC_ == 8) CTSEG_FWD(BF16, 8);
-  else CTSEG_FWD(BF16, 4);
-#undef CTSEG_FWD
+  dispatch_chunk<true>(dtype, EPC_, [&](auto t, auto ep) {
+    hipLaunchKernelGGL((instnorm_prelu_fwd_kernel<decltype(t), ep>), grid, dim3(256), sh, st, (const char*)y, y_ld, mean_rstd, alpha,
+                       (const char*)res, res_ld, (char*)out, out_ld, S, C, Cv);
+  });
   CTSEG_LAUNCH_CHECK("instnorm_prelu_fwd");
   return 0;
 }
@@ -571,20 +377,17 @@ extern "C" int ctseg_instnorm_prelu_bwd_reduce(int32_t dtype, const void* g, int
                                                const float* mean_rstd, const float* alpha, float* partials, int32_t P,
                                                int32_t ld, int32_t N, int64_t S, int32_t C, void* stream) {
   CTSEG_REQUIRE(g && y && mean_rstd && alpha && partials && P > 0 && N > 0 && C <= ld, "instnorm_prelu_bwd_reduce: bad arguments");
-  CHECK_CL_HALF(dtype, C, g_ld, y_ld);
+  CHECK_CL(dtype, C, true, false, g_ld, y_ld);
   CTSEG_REQUIRE(Cv <= 256, "instnorm_prelu_bwd_reduce: too many channels");
   const bool pow2 = (Cv & (Cv - 1)) == 0 && Cv <= 64;
   // reduction scratch: 4 waves x Cv chunks (butterfly path) or one slot per thread; padding it to the old 24 KB measured
   // 12.45 -> 12.49 ms/step (fewer of these blocks fit beside the side stream's weight-gradient workgroups)
   const size_t sh = (Cv * (2 * EPC_ + 1) + (pow2 ? 4 * Cv * 3 * EPC_ : 256 * 3 * EPC_)) * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-#define CTSEG_RED(T, EP)                                                                                                     \
-  hipLaunchKernelGGL((instnorm_prelu_bwd_reduce_kernel<T, EP>), dim3(P, N), dim3(256), sh, st, (const char*)g, g_ld,         \
-                     (const char*)y, y_ld, mean_rstd, alpha, partials, P, ld, S, C, Cv)
-  if (dtype == CTSEG_F32) CTSEG_RED(float, 4);
-  else if (EPC_ == 8) CTSEG_RED(BF16, 8);
-  else CTSEG_RED(BF16, 4);
-#undef CTSEG_RED
+  dispatch_chunk<false>(dtype, EPC_, [&](auto t, auto ep) {
+    hipLaunchKernelGGL((instnorm_prelu_bwd_reduce_kernel<decltype(t), ep>), dim3(P, N), dim3(256), sh, st, (const char*)g, g_ld,
+                       (const char*)y, y_ld, mean_rstd, alpha, partials, P, ld, S, C, Cv);
+  });
   CTSEG_LAUNCH_CHECK("instnorm_prelu_bwd_reduce");
   return 0;
 }
@@ -611,29 +414,24 @@ static int bwd_apply_launch(int32_t dtype, const void* g, int32_t g_ld, const vo
                             float* dalpha, void* stream) {
   CTSEG_REQUIRE(g && y && mean_rstd && alpha && sums && dy && N > 0, "instnorm_prelu_bwd_apply: bad arguments");
   CTSEG_REQUIRE(da_part == nullptr || (dalpha != nullptr && n_da > 0), "instnorm_prelu_bwd_apply: slope-gradient arguments");
-  CHECK_CL_HALF(dtype, C, g_ld, y_ld, dy_ld, g_copy ? g_copy_ld : dy_ld);
+  CHECK_CL(dtype, C, true, false, g_ld, y_ld, dy_ld, g_copy ? g_copy_ld : dy_ld);
   int gx = ew_blocks_for(S * Cv, Cv);
   const bool colsum = cs_part != nullptr;
   const int pld = Cv * EPC_;
   if (colsum) {
     CTSEG_REQUIRE(cs_out != nullptr && Cv * EPC_ <= 256 && P_cap >= N, "instnorm_prelu_bwd_apply_colsum: partial buffer");
-    if (gx > P_cap / N) gx = P_cap / N;
-    // a thread must see the same channel chunk in every grid-stride iteration: (gx * 256) % Cv == 0
-    int step = Cv;
-    while (step % 2 == 0) step /= 2;          // 256 supplies every factor of two
-    gx = gx / step * step;
+    // a thread must see the same channel chunk in every grid-stride iteration, and each block writes a partial row
+    gx = ew_blocks_for(S * Cv, Cv, true, P_cap / N);
     CTSEG_REQUIRE(gx >= 1, "instnorm_prelu_bwd_apply_colsum: partial buffer too small for C=%d", C);
   }
   dim3 grid(gx, N);
   const size_t sh = (Cv * (4 * EPC_ + 1) + (colsum ? 256 * EPC_ : 0)) * sizeof(float);       // padded constant table (+ column-sum scratch)
   hipStream_t st = (hipStream_t)stream;
-#define CTSEG_APPLY(T, EP, CS)                                                                                                      \
-  hipLaunchKernelGGL((instnorm_prelu_bwd_apply_kernel<T, EP, CS>), grid, dim3(256), sh, st, (const char*)g, g_ld, (const char*)y, y_ld, \
-                     mean_rstd, alpha, sums, (char*)dy, dy_ld, (char*)g_copy, g_copy_ld, S, C, Cv, cs_part, pld, da_part, n_da, dalpha)
-  if (dtype == CTSEG_F32) { if (colsum) CTSEG_APPLY(float, 4, true); else CTSEG_APPLY(float, 4, false); }
-  else if (EPC_ == 8) { if (colsum) CTSEG_APPLY(BF16, 8, true); else CTSEG_APPLY(BF16, 8, false); }
-  else { if (colsum) CTSEG_APPLY(BF16, 4, true); else CTSEG_APPLY(BF16, 4, false); }
-#undef CTSEG_APPLY
+  dispatch_chunk<false>(dtype, EPC_, [&](auto t, auto ep) {
+    auto* k = colsum ? instnorm_prelu_bwd_apply_kernel<decltype(t), ep, true> : instnorm_prelu_bwd_apply_kernel<decltype(t), ep, false>;
+    hipLaunchKernelGGL(k, grid, dim3(256), sh, st, (const char*)g, g_ld, (const char*)y, y_ld, mean_rstd, alpha, sums, (char*)dy, dy_ld,
+                       (char*)g_copy, g_copy_ld, S, C, Cv, cs_part, pld, da_part, n_da, dalpha);
+  });
   if (colsum) hipLaunchKernelGGL(colsum_final_kernel, dim3(1), dim3(1024), 0, st, cs_part, gx * N, pld, C, cs_out);
   CTSEG_LAUNCH_CHECK("instnorm_prelu_bwd_apply");
   return 0;
@@ -660,7 +458,7 @@ extern "C" int ctseg_instnorm_prelu_bwd_apply_colsum(int32_t dtype, const void* 
 extern "C" int ctseg_colsum(int32_t dtype, const void* x, int32_t ld, int64_t rows, int32_t C, float* partials, int32_t P,
                             float* out, void* stream) {
   CTSEG_REQUIRE(x && partials && out && rows > 0 && C > 0 && P > 0, "colsum: bad arguments");
-  CHECK_CL(dtype, C, ld);
+  CHECK_CL(dtype, C, false, false, ld);
   CTSEG_REQUIRE(Cv <= 256, "colsum: too many channels");
   const int pld = Cv * EPC_;
   hipStream_t st = (hipStream_t)stream;

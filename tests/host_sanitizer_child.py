@@ -118,4 +118,66 @@ for _ in range(2000):
 for c in (1, 10, 16, 33, 64, 200, 256, 1024):
     L.ctseg_conv_tile_rows(c), L.ctseg_conv_tile_cols(c), L.ctseg_wgrad_tile_cols(c)
 assert L.ctseg_adam_step(None, None, None, None, 10, 1e-3, 0.9, 0.999, 1e-8, 1, 1.0, None) < 0
+
+
+def rejects(fn, fragment, *args):
+    assert getattr(L, fn)(*args) < 0, fn
+    err = L.ctseg_last_error().decode()
+    assert fragment in err, (fn, fragment, err)
+
+
+# norm / column-sum entry points: one shared channel-chunk check (dtype, chunk width, strides), grid sizing and argument checks
+p = base
+F16_BWD = "bad dtype %d (CTSEG_F16 is accepted by the forward pass only)" % nat.F16
+STRIDE = "channel stride 10 not chunked for C=16"
+rejects("ctseg_instnorm_finalize", "instnorm_finalize: bad arguments", None, 2, 8, 16, 0, 16, 1.0, 1e-5, p, p, None)
+for dt, frag in ((7, "bad dtype 7"), (nat.F32, STRIDE)):
+    rejects("ctseg_instnorm_prelu_fwd", frag, dt, p, 10, p, p, None, 0, p, 16, 2, 64, 16, None)
+    rejects("ctseg_scale_shift_prelu_fwd", frag, dt, p, 10, p, p, None, 0, p, 16, 2, 64, 16, None)
+rejects("ctseg_instnorm_prelu_fwd", "instnorm_prelu_fwd: bad arguments", nat.BF16, None, 16, p, p, None, 0, p, 16, 2, 64, 16, None)
+rejects("ctseg_instnorm_prelu_fwd", "instnorm_prelu_fwd: alpha missing", nat.F16, p, 16, p, None, None, 0, p, 16, 2, 64, 16, None)
+rejects("ctseg_instnorm_prelu_fwd", "channel stride 18 not chunked", nat.F16, p, 16, None, None, p, 18, p, 16, 2, 64, 16, None)
+rejects("ctseg_scale_shift_prelu_fwd", "scale_shift_prelu_fwd: bad arguments", nat.F32, p, 16, None, p, None, 0, p, 16, 2, 64, 16, None)
+for dt, C, g_ld, frag in ((7, 16, 16, "bad dtype 7"), (nat.F16, 16, 16, F16_BWD), (nat.F32, 16, 10, STRIDE),
+                          (nat.F32, 2048, 2048, "too many channels")):
+    rejects("ctseg_instnorm_prelu_bwd_reduce", frag, dt, p, g_ld, p, C, p, p, p, 8, C, 2, 4096, C, None)
+    rejects("ctseg_batchnorm_prelu_bwd_reduce", frag, dt, p, g_ld, p, C, p, p, p, p, p, 8, C, 2, 4096, C, None)
+    if C <= 256:
+        args = (dt, p, g_ld, p, C, p, p, p, p, C, None, 0, 2, 4096, C)
+        rejects("ctseg_instnorm_prelu_bwd_apply", frag, *args, None, 0, None, None)
+        rejects("ctseg_instnorm_prelu_bwd_apply_colsum", frag, *args, p, 64, p, None, 0, None, None)
+        rejects("ctseg_batchnorm_prelu_bwd_apply", frag, dt, p, g_ld, p, C, p, p, p, p, p, p, C, None, 0, 2, 4096, C, None, 0, None,
+                None)
+    rejects("ctseg_colsum", frag if dt != nat.F16 else "bad dtype 4", dt, p, g_ld, 4096, C, p, 8, p, None)
+rejects("ctseg_instnorm_prelu_bwd_reduce", "instnorm_prelu_bwd_reduce: bad arguments", nat.F32, None, 16, p, 16, p, p, p, 8, 16, 2,
+        4096, 16, None)
+rejects("ctseg_batchnorm_prelu_bwd_reduce", "batchnorm_prelu_bwd_reduce: bad arguments", nat.F32, p, 16, p, 16, p, None, p, p, p, 8,
+        16, 2, 4096, 16, None)
+# 16-bit storage in 12-wide rows: 8-byte chunks where the pass allows them, rejected by the column sum (16-byte chunks only)
+rejects("ctseg_colsum", "channel stride 12 not chunked for C=10", nat.BF16, p, 12, 4096, 10, p, 8, p, None)
+rejects("ctseg_instnorm_prelu_bwd_apply", "instnorm_prelu_bwd_apply: bad arguments", nat.F32, p, 16, p, 16, p, p, p, None, 16, None,
+        0, 2, 4096, 16, None, 0, None, None)
+rejects("ctseg_instnorm_prelu_bwd_apply", "instnorm_prelu_bwd_apply: slope-gradient arguments", nat.F32, p, 16, p, 16, p, p, p, p, 16,
+        None, 0, 2, 4096, 16, p, 8, None, None)
+rejects("ctseg_batchnorm_prelu_bwd_apply", "batchnorm_prelu_bwd_apply: bad arguments", nat.F32, p, 16, p, 16, p, p, p, p, p, p, 16,
+        None, 0, 2, 0, 16, None, 0, None, None)
+rejects("ctseg_batchnorm_prelu_bwd_apply", "batchnorm_prelu_bwd_apply: slope-gradient arguments", nat.F32, p, 16, p, 16, p, p, p, p,
+        p, p, 16, None, 0, 2, 4096, 16, p, 0, p, None)
+ca = (nat.F32, p, 16, p, 16, p, p, p, p, 16, None, 0, 2, 4096)
+rejects("ctseg_instnorm_prelu_bwd_apply_colsum", "instnorm_prelu_bwd_apply_colsum: partial buffer", *ca, 16, None, 64, p, None, 0,
+        None, None)
+rejects("ctseg_instnorm_prelu_bwd_apply_colsum", "instnorm_prelu_bwd_apply_colsum: partial buffer", *ca, 16, p, 1, p, None, 0, None,
+        None)
+rejects("ctseg_instnorm_prelu_bwd_apply_colsum", "instnorm_prelu_bwd_apply_colsum: partial buffer", nat.F32, p, 512, p, 512, p, p, p,
+        p, 512, None, 0, 2, 4096, 512, p, 64, p, None, 0, None, None)
+# C = 12: Cv = 3 and a grid stride that is a multiple of 3 needs at least 3 blocks per sample
+rejects("ctseg_instnorm_prelu_bwd_apply_colsum", "partial buffer too small for C=12", nat.F32, p, 12, p, 12, p, p, p, p, 12, None, 0,
+        2, 4096, 12, p, 5, p, None, 0, None, None)
+rejects("ctseg_colsum", "colsum: bad arguments", nat.F32, p, 16, 4096, 16, None, 8, p, None)
+rejects("ctseg_instnorm_prelu_bwd_finalize", "instnorm_prelu_bwd_finalize: bad arguments", p, 2, 8, 16, 16, 4096.0, None, p, None, None)
+rejects("ctseg_instnorm_prelu_dalpha", "instnorm_prelu_dalpha: bad arguments", p, 32, None, None)
+rejects("ctseg_batchnorm_finalize", "batchnorm_finalize: bad arguments", p, 2, 8, 16, 0, 16, 1.0, 1e-5, 0.1, p, p, p, p, None, p, p, None)
+rejects("ctseg_batchnorm_eval_table", "batchnorm_eval_table: bad arguments", p, p, p, None, 16, 1e-5, p, None)
+rejects("ctseg_batchnorm_prelu_bwd_finalize", "batchnorm_prelu_bwd_finalize: bad arguments", p, 2, 8, 16, 16, 8192.0, p, p, p, None, None)
+n += 1
 print("SANITIZER-CHILD-OK", n)
