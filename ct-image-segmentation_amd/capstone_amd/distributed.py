@@ -144,10 +144,9 @@ class GradAllReducer:
         records a different program: its readiness marks sit at other indices), cached on the plan"""
         if plan is None or self.sizes is None:
             return self.points
-        pts = getattr(plan, "_ddp_points", None)
-        if pts is None:
-            pts = plan._ddp_points = split_points(plan.ready_marks, self.sizes, self.n) if plan.ready_marks else []
-        return pts
+        if plan._ddp_points is None:
+            plan._ddp_points = split_points(plan.ready_marks, self.sizes, self.n) if plan.ready_marks else []
+        return plan._ddp_points
 
     def hooks(self, plan=None):
         """{backward program index: callable} — fired by Plan.backward between ops"""

@@ -77,6 +77,7 @@ class SplitAct:
     def __init__(self, a, b):
         self.a, self.b = a, b
         self.dims, self.C, self.dt = a.dims, a.C + b.C, a.dt
+        self.pending_norm = self.bst = None     # (as Act's; the marks of a split activation live on its two halves)
 
     def slice(self, c0, C):
         if c0 == 0 and C == self.a.C:
@@ -90,20 +91,24 @@ class NarrowUnsupported(Exception):
     """a pass of the plan being built cannot move 12-wide rows: the plan is rebuilt with 16-byte chunked rows"""
 
 
-NARROW_ROWS = [False]     # set while a Plan is being recorded (Engine.plan_for_shape)
-
-
-def default_ld(C, dt):
-    """channel stride of a fresh activation: 16-byte chunks; bf16 tensors of 9..12 channels 12 wide while NARROW_ROWS"""
-    if NARROW_ROWS[0] and nat.is16(dt) and rup(C, 4) == 12:
+def default_ld(C, dt, narrow=False):
+    """channel stride of a fresh activation: 16-byte chunks; ``narrow`` (Plan.narrow_rows): 16-bit tensors of 9..12 channels 12 wide"""
+    if narrow and nat.is16(dt) and rup(C, 4) == 12:
         return 12
     return rup(C, nat.epc(dt))
 
 
-def new_act(N, X, Y, Z, C, dt, device, ld=None, zero=True):
-    ld = ld if ld is not None else default_ld(C, dt)
+def new_act(N, X, Y, Z, C, dt, device, ld=None, zero=True, narrow=False):
+    ld = ld if ld is not None else default_ld(C, dt, narrow)
     f = torch.zeros if zero else torch.empty
     return Act(f((N, X, Y, Z, ld), dtype=nat.torch_dtype(dt), device=device), C, 0, dt)
+
+
+def plan_act(plan, dims, C, dt=None, ld=None):
+    """a fresh activation of the plan being recorded: its device and row layout, its storage dtype unless ``dt`` says otherwise.
+    ``plan`` may be a duck-typed stand-in that drives single layers (the op-level tests' one-layer plan) and knows nothing of the
+    row layout: it gets 16-byte chunked rows"""
+    return new_act(*dims, C, plan.dt if dt is None else dt, plan.device, ld=ld, narrow=getattr(plan, "narrow_rows", False))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -167,6 +172,7 @@ class ParamStore:
         self.flat_g = torch.zeros(self.n_pad, dtype=torch.float32, device=device)
         self.adam_m = self.adam_v = None
         self.step = 0
+        self._grad_views = None       # per-parameter views of flat_g, made once (grad_views)
         # bumped by every write to flat_p that bypasses the Parameters' own version counters (ctseg_adam_step writes through raw
         # pointers; broadcasts and re-attach copies write the flat buffer): EVERY plan's Packer compares it, so a plan of another
         # shape (validation, sliding window, a short last batch) never runs on packed weights from before the update
@@ -199,6 +205,12 @@ class ParamStore:
     def grad_view(self, p):
         o = self.offsets[id(p)]
         return self.flat_g[o:o + p.numel()].view(p.shape)
+
+    def grad_views(self):
+        """grad_view of every parameter, cached: ``p.grad`` is handed the same tensor every step"""
+        if self._grad_views is None:
+            self._grad_views = [self.grad_view(p) for p in self.params]
+        return self._grad_views
 
     def version(self):
         return (self.generation, sum(p._version for p in self.params))
@@ -360,6 +372,21 @@ class GemmLayer:
             f = lambda v: (v + 2 * p - self.k) // self.s + 1
         return (N, f(X), f(Y), f(Z) if self.dims == 3 else 1)
 
+    def _grid(self, kind, xd, yd):
+        """(row grid, gather stride, scatter stride) of the "fwd" / "dgrad" / "wgrad" pass; xd, yd: dims of the layer's input / output"""
+        up = self.transposed and self.s == 2
+        if kind == "fwd":
+            return (xd[1:], 1, 2) if up else (yd[1:], 1 if self.transposed else self.s, 1)
+        if kind == "wgrad":       # rows of dY; of x for a transposed conv, whose weight gradient gathers dY
+            return (xd[1:], 2, 1) if self.transposed else (yd[1:], self.s, 1)
+        if up:                    # strided conv over dOut
+            return xd[1:], 2, 1
+        if self.s == 2:           # 8-class pass over dY
+            assert all(a == 2 * b for a, b in zip(xd[1:1 + self.dims], yd[1:1 + self.dims])), \
+                "stride-2 convolutions need even input sizes (as MONAI's UNet does for the skip concat)"
+            return yd[1:], 1, 2
+        return xd[1:], 1, 1
+
     def _desc(self, pack, classes, gathered, out, rowgrid, sin, sout, Cn, cg, bias_ptr, add, stats, out_f32, out2=None):
         plan = self.plan
         d = nat.ConvDesc()
@@ -399,15 +426,13 @@ class GemmLayer:
 
     def _try_split(self, d, od, split_at):
         """two dense outputs instead of one [split_at | rest] buffer where the kernel taking this pass can (stem, stride-2 halo)"""
-        if split_at is None or os.environ.get("CTSEG_SPLIT_OUT", "1") == "0":
+        if split_at is None:
             return None
         d.out2_col0 = split_at
         if nat.query("ctseg_conv_split_ok", d) != 1:
             d.out2_col0 = 0
             return None
-        plan = self.plan
-        a = new_act(*od, split_at, plan.dt, plan.device)
-        b = new_act(*od, d.Cn - split_at, plan.dt, plan.device)
+        a, b = plan_act(self.plan, od, split_at), plan_act(self.plan, od, d.Cn - split_at)
         d.out, d.o_ld = a.ptr(), a.ld
         d.out2, d.o2_ld = b.ptr(), b.ld
         return SplitAct(a, b)
@@ -418,16 +443,12 @@ class GemmLayer:
         od = self.out_dims(x.dims)
         own_out = out is None
         if out is None:
-            dt = F32 if out_f32 else plan.dt
-            out = new_act(*od, self.Cn, dt, plan.device)
+            out = plan_act(plan, od, self.Cn, F32 if out_f32 else None)
         assert out.dims == od and out.C == self.Cn, (self.name, out.dims, od)
-        if self.transposed and self.s == 2:
-            rowgrid, sin, sout = x.dims[1:], 1, 2
-        else:
-            rowgrid, sin, sout = od[1:], (1 if self.transposed else self.s), 1
+        rowgrid, sin, sout = self._grid("fwd", x.dims, od)
         stats = None
         bias_ptr = plan.packer.bias_ptr(self.bias_off)
-        pend = getattr(x, "pending_norm", None)
+        pend = x.pending_norm
         d = self._desc(self.fwd_pack, self.fwd_classes, x, out, rowgrid, sin, sout, self.Cn, self.cg, bias_ptr, add, None, out_f32)
         if pend is not None:
             # the producing layer's InstanceNorm + PReLU is applied to the operand on its way into this pass (the activation is
@@ -484,16 +505,9 @@ class GemmLayer:
         xd = self.x_dims
         own_out = out is None
         if out is None:
-            out = new_act(*xd, self.cin, plan.dt, plan.device)
+            out = plan_act(plan, xd, self.cin)
         assert out.dims == xd and out.C == self.cin and dy.C == self.Cn
-        if self.transposed and self.s == 2:       # strided conv over dOut
-            rowgrid, sin, sout = xd[1:], 2, 1
-        elif (not self.transposed) and self.s == 2:  # 8-class pass over dY
-            assert all(a == 2 * b for a, b in zip(xd[1:1 + self.dims], dy.dims[1:1 + self.dims])), \
-                "stride-2 convolutions need even input sizes (as MONAI's UNet does for the skip concat)"
-            rowgrid, sin, sout = dy.dims[1:], 1, 2
-        else:
-            rowgrid, sin, sout = xd[1:], 1, 1
+        rowgrid, sin, sout = self._grid("dgrad", xd, dy.dims)
         d = self._desc(self.dg_pack, self.dg_classes, dy, out, rowgrid, sin, sout, self.cin, self.cgd, None, add, None, False)
         if own_out and add is None:
             sp = self._try_split(d, xd, split_at)
@@ -503,19 +517,30 @@ class GemmLayer:
         plan.emit("ctseg_conv_igemm", d, keep=(dy, out, add, marked.bst[1] if marked is not None else None, bst.y if marked is not None else None))
         return out
 
+    def _wgrad_desc(self, x, dy, yd):
+        """the weight-gradient descriptor (operands, dims, taps, padded sizes; one split, no workspace yet) of layer input ``x`` and
+        output gradient ``dy`` (output dims ``yd``).  Returns (desc, gathered, dY operand): a transposed conv gathers dY"""
+        if not self.transposed:
+            gathered, dyy, cg, cn = x, dy, self.cg, self.Cn
+        else:
+            assert self.s == 2, "stride-1 transposed conv wgrad not implemented"
+            gathered, dyy, cg, cn = dy, x, self.cgd, self.cin
+        d = nat.WgradDesc()
+        d.in_, d.dy, d.dtype = gathered.ptr(), dyy.ptr(), self.plan.dt
+        d.N, d.Xi, d.Yi, d.Zi = gathered.dims
+        (d.Xr, d.Yr, d.Zr), d.sin, _ = self._grid("wgrad", x.dims, yd)
+        d.Cg, d.Cn, d.g_ld, d.d_ld, d.ntaps = cg, cn, gathered.ld, dyy.ld, self.T
+        for j, (_, off) in enumerate(self.wg_taps):
+            d.taps[j] = off
+        d.splits, d.kpad_w, d.cn_pad = 1, rup(self.T * cg + 1, 128), rup(cn, nat.lib().ctseg_wgrad_tile_cols(cn))
+        return d, gathered, dyy
+
     def wgrad_dyn_ok(self, x, dy_lo, y):
         """can this layer's weight-gradient pass form the upper columns of dY on load (ctseg_wgrad_desc::dyn_*)?  ``dy_lo``: the
         gradient of the lower column block, ``y``: the forward output of the upper one (the norm's input)"""
         if self.transposed or self.Cn != dy_lo.C + y.C or os.environ.get("CTSEG_WGRAD_DYN", "1") == "0":
             return False
-        d = nat.WgradDesc()
-        d.in_, d.dy, d.dtype = x.ptr(), dy_lo.ptr(), self.plan.dt
-        d.N, d.Xi, d.Yi, d.Zi = x.dims
-        d.Xr, d.Yr, d.Zr = y.dims[1:]
-        d.Cg, d.Cn, d.g_ld, d.d_ld, d.sin, d.ntaps = self.cg, self.Cn, x.ld, dy_lo.ld, self.s, self.T
-        for j, (_, off) in enumerate(self.wg_taps):
-            d.taps[j] = off
-        d.splits, d.kpad_w, d.cn_pad = 1, rup(self.T * self.cg + 1, 128), rup(self.Cn, nat.lib().ctseg_wgrad_tile_cols(self.Cn))
+        d, _, _ = self._wgrad_desc(x, dy_lo, y.dims)
         d.dyn_col0, d.dyn_g, d.dyn_y = dy_lo.C, y.ptr(), y.ptr()
         d.dyn_g_ld, d.dyn_y_ld = rup(y.C, nat.epc(self.plan.dt)), y.ld
         return nat.query("ctseg_wgrad_dy_norm_ok", d) == 1
@@ -559,41 +584,22 @@ class GemmLayer:
         holds the lower column block only; the upper one is the InstanceNorm + PReLU backward of ``g`` through ``norm``, formed on
         load by the pass (wgrad_dyn_ok)."""
         plan, st = self.plan, self.plan.store
-        lib = nat.lib()
+        d, gathered, dyy = self._wgrad_desc(x, dy, dy.dims if dyn is None else dyn[1].y.dims)
+        cg, cn, kpad_w, cn_pad = d.Cg, d.Cn, d.kpad_w, d.cn_pad
+        A = self.Cn if self.transposed else self.cin       # rows of the reduced gradient
         if dyn is not None:
-            assert not self.transposed
-            gathered, dyy, cg, A, cn = x, dy, self.cg, self.cin, self.Cn
-            rowgrid, sin = dyn[1].y.dims[1:], self.s
-            assert dy.C + dyn[0].C == cn and dyn[1].y.C == dyn[0].C
-        elif not self.transposed:
-            gathered, dyy, cg, A, cn = x, dy, self.cg, self.cin, self.Cn
-            rowgrid, sin = dy.dims[1:], self.s
+            assert not self.transposed and dy.C + dyn[0].C == cn and dyn[1].y.C == dyn[0].C
         else:
-            assert self.s == 2, "stride-1 transposed conv wgrad not implemented"
-            gathered, dyy, cg, A, cn = dy, x, self.cgd, self.Cn, self.cin
-            rowgrid, sin = x.dims[1:], 2
-        assert dyn is not None or dyy.C == cn, (self.name, dyy.C, cn)
-        N = gathered.dims[0]
-        rows = rowgrid[0] * rowgrid[1] * rowgrid[2]
-        bnw = lib.ctseg_wgrad_tile_cols(cn)
-        kpad_w, cn_pad = rup(self.T * cg + 1, 128), rup(cn, bnw)
-        d = nat.WgradDesc()
-        d.in_, d.dy, d.dtype = gathered.ptr(), dyy.ptr(), plan.dt
-        d.N, d.Xi, d.Yi, d.Zi = gathered.dims
-        d.Xr, d.Yr, d.Zr = rowgrid
-        d.Cg, d.Cn, d.g_ld, d.d_ld, d.sin = cg, cn, gathered.ld, dyy.ld, sin
-        d.ntaps = self.T
-        for j, (_, off) in enumerate(self.wg_taps):
-            d.taps[j] = off
-        d.splits, d.kpad_w, d.cn_pad = 1, kpad_w, cn_pad
-        splits = self._wgrad_splits(d, N, rows, dyn is not None or getattr(gathered, "pending_norm", None) is not None)
-        d.splits = splits
+            assert dyy.C == cn, (self.name, dyy.C, cn)
+        pend = gathered.pending_norm
+        # (the split count is chosen before the pending-norm fallback below can turn the pass back into a plain one: asking after
+        # it would change the split count recorded under CTSEG_NORM_ON_LOAD=1, so it is left for a change of its own)
+        d.splits = self._wgrad_splits(d, d.N, d.Xr * d.Yr * d.Zr, dyn is not None or pend is not None)
         if dyn is not None:
             g_up, norm, sums = dyn
             d.dyn_col0, d.dyn_g, d.dyn_g_ld, d.dyn_y, d.dyn_y_ld = dy.C, g_up.ptr(), g_up.ld, norm.y.ptr(), norm.y.ld
             d.dyn_mean_rstd, d.dyn_alpha, d.dyn_sums = norm.mr.data_ptr(), st.p_ptr(norm.alpha), sums.data_ptr()
             assert nat.query("ctseg_wgrad_dy_norm_ok", d) == 1, self.name
-        pend = getattr(gathered, "pending_norm", None)
         if pend is not None:
             assert not self.transposed
             d.in_mean_rstd, d.in_alpha, d.in_norm_C = pend.mr.data_ptr(), st.p_ptr(pend.alpha), gathered.C
@@ -604,7 +610,7 @@ class GemmLayer:
                 d.in_, d.g_ld = gathered.ptr(), gathered.ld
         if plan.dt == BF16 and (gathered.ld == 12 or dyy.ld == 12) and nat.query("ctseg_wgrad_narrow_ok", d) != 1:
             raise NarrowUnsupported(self.name + " (weight gradient)")
-        nslabs = lib.ctseg_conv_wgrad_slabs(d)     # N*splits, or one per persistent workgroup (LDS-halo kernel)
+        nslabs = nat.lib().ctseg_conv_wgrad_slabs(d)     # N*splits, or one per persistent workgroup (LDS-halo kernel)
         assert nslabs > 0
         ws = torch.zeros(nslabs * kpad_w * cn_pad, dtype=torch.float32, device=plan.device)
         d.ws = ws.data_ptr()
@@ -648,9 +654,16 @@ class Packer:
         self.descs = []       # the same blocks as ctseg_pack_block descriptions
         self.total = 0
         self.bias_blocks, self.bias_total = [], 0
-        self.buf = self.idx = self.bias_buf = self.bias_idx = None
-        self.dirty = True
-        self.version = None
+        self.first = (0, 0)   # [lo, hi) of the packed buffer: the operand of the first forward pass (set by the plan before finalize)
+        # ---- made by finalize() ----
+        self.buf = self.bias_buf = None               # packed operands (storage dtype) and biases (fp32)
+        self.idx = self.bias_idx = None               # flat-parameter index of every element of buf / bias_buf (ctseg_gather_cast)
+        self.n_idx = self.n_bidx = 0                  # their lengths
+        self.pack_blocks = self.pack_rows = None      # structured description (ctseg_pack_weights): blocks, (block, row) pairs
+        self.n_pack_blocks = self.n_pack_rows = 0
+        self.n_first_rows = 0                         # leading pairs of pack_rows that belong to ``first``
+        self.dirty = True     # buf does not hold the current parameters
+        self.version = None   # ParamStore.version() of the last complete re-layout
 
     def add(self, layer, mode):
         dt = self.plan.dt
@@ -676,14 +689,13 @@ class Packer:
             parts = layer.src_parts(mode)
             desc = {"dst_off": self.total, "kpad": kpad, "gs": gs, "ntaps": nt, "T": layer.T, "taps": [t for t, _ in taps],
                     "parts": parts, "rows": rows}
-            if os.environ.get("CTSEG_PACK_CHECK", "1") != "0":
-                chk = np.full((rows_pad, kpad), zero, dtype=np.int64)
-                for (o, n_lo, n_hi, g_lo, g_hi, SN, SG) in parts:
-                    nn, gg = np.arange(n_lo, min(n_hi, rows)), np.arange(g_lo, min(g_hi, gs))
-                    for j, t in enumerate(desc["taps"]):
-                        chk[n_lo:n_lo + len(nn), j * gs + g_lo:j * gs + g_lo + len(gg)] = \
-                            o + (nn[:, None] - n_lo) * SN + (gg[None, :] - g_lo) * SG + t
-                assert np.array_equal(chk, blk), f"{layer.name} {mode}: structured pack description disagrees with the index"
+            chk = np.full((rows_pad, kpad), zero, dtype=np.int64)
+            for (o, n_lo, n_hi, g_lo, g_hi, SN, SG) in parts:
+                nn, gg = np.arange(n_lo, min(n_hi, rows)), np.arange(g_lo, min(g_hi, gs))
+                for j, t in enumerate(desc["taps"]):
+                    chk[n_lo:n_lo + len(nn), j * gs + g_lo:j * gs + g_lo + len(gg)] = \
+                        o + (nn[:, None] - n_lo) * SN + (gg[None, :] - g_lo) * SG + t
+            assert np.array_equal(chk, blk), f"{layer.name} {mode}: structured pack description disagrees with the index"
             self.descs.append(desc)
             self.total += rows_pad * kpad
         info["size"] = self.total - info["base"]
@@ -725,11 +737,11 @@ class Packer:
         self.bias_idx = torch.from_numpy(bidx).to(dev)
         self.n_idx, self.n_bidx = self.total, max(self.bias_total, 4)
         self.dirty = True
-        # structured re-layout (ctseg_pack_weights) where every block's source region fits its LDS staging buffer
-        self.pack_blocks = self.pack_rows = None
+        # structured re-layout (ctseg_pack_weights) where every block's source region fits its LDS staging buffer; the index
+        # gather otherwise
         fits = all(sum((min(gh, d["gs"]) - gl) * d["T"] for (_, _, _, gl, gh, _, _) in d["parts"]) <= nat.PACK_LDS_FLOATS and
                    len(d["parts"]) <= 2 for d in self.descs)
-        if self.descs and fits and os.environ.get("CTSEG_PACK_STRUCTURED", "1") != "0":
+        if self.descs and fits:
             arr = (nat.PackBlock * len(self.descs))()
             rows = []
             for b, d in enumerate(self.descs):
@@ -741,12 +753,11 @@ class Packer:
                     P = B.part[k]
                     P.o, P.n_lo, P.n_hi, P.g_lo, P.g_hi, P.SN, P.SG = o, n_lo, n_hi, g_lo, min(g_hi, d["gs"]), SN, SG
                 rows += [(b, n) for n in range(d["rows"])]
-            import ctypes
             raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
             self.pack_blocks = raw.to(dev)
             # rows of the blocks of the FIRST forward pass first (Packer.first = its pack): refresh(part="first") rebuilds them alone,
             # the next step's first convolution waits for nothing else
-            lo, hi = self.first if getattr(self, "first", None) else (0, 0)
+            lo, hi = self.first
             head = [(b, n) for (b, n) in rows if lo <= self.descs[b]["dst_off"] < hi]
             rest = [(b, n) for (b, n) in rows if not (lo <= self.descs[b]["dst_off"] < hi)]
             self.n_first_rows = len(head)
@@ -755,7 +766,7 @@ class Packer:
 
     def can_split(self):
         """True when refresh(part="first") / refresh(part="rest") can rebuild the first forward pass's operands on their own"""
-        return self.pack_blocks is not None and getattr(self, "n_first_rows", 0) > 0
+        return self.pack_blocks is not None and self.n_first_rows > 0
 
     def stale(self):
         """True when refresh() (no force) would rebuild the operands: the parameters changed since the last complete re-layout"""

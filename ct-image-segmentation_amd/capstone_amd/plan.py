@@ -9,14 +9,13 @@ except ``Plan.run``.
 """
 import math
 import os
-import sys
 
 import torch
 import torch.nn as nn
 
 from . import _native as nat
 from ._native import BF16, F32
-from .engine import Act, BufferStore, GemmLayer, Packer, ParamStore, new_act, rup
+from .engine import Act, BufferStore, GemmLayer, NarrowUnsupported, Packer, ParamStore, plan_act, rup
 
 
 def _is_seq(m):
@@ -38,50 +37,67 @@ def _parts(conv):
     return (conv.weight, conv.bias, conv.out_channels)
 
 
-def _addend(out, accumulate):
-    """accumulate: False | True (add the current content of ``out``) | an Act (add that tensor, ``out`` may be fresh)"""
-    if accumulate is True:
-        return out
-    return accumulate if accumulate else None
+def _ptr_ld(act):
+    """(pointer, channel stride) of an optional operand"""
+    return (act.ptr(), act.ld) if act is not None else (None, 0)
 
 
-class _NormAct:
+class _NormBase:
+    """what the norm + PReLU nodes of a conv output share.  The conv nodes ask ``fusable`` (per-sample statistics, no affine: the conv
+    passes may apply / take them on load — in_norm, bst, dyn) and ``needs_stats`` (the producing conv pass writes (sum, sumsq)
+    partials)."""
+
+    def __init__(self, plan, alpha, params):
+        self.plan, self.alpha, self.params = plan, alpha, params
+        self.y = None         # the raw conv output this node normalises (set by the forward)
+        self.mr = None        # its (mean, rstd) table
+
+    def _bwd_buffers(self, dy_out, mark=None, apply=True):
+        """(partials, P, ld, dy_out) of a backward: P row ranges per sample with (N, P, 3, ld) partial sums — or those of ``mark``,
+        which the pass that wrote the gradient left (Act.bst) — and the tensor that receives dL/dy"""
+        plan, y = self.plan, self.y
+        if dy_out is None and apply:
+            dy_out = plan_act(plan, y.dims, y.C)
+        if mark is not None:
+            return (*mark[1:], dy_out)
+        P, ld = _bwd_row_ranges(y.S, y.dims[0], plan.dt), rup(y.C, 4)
+        return torch.zeros((y.dims[0], P, 3, ld), dtype=torch.float32, device=plan.device), P, ld, dy_out
+
+
+class _NormAct(_NormBase):
     """InstanceNorm + PReLU of one conv output: forward apply and the 3-kernel backward."""
-    fusable = True            # per-sample statistics, no affine: the conv passes may apply / take them on load (in_norm, bst, dyn)
-    needs_stats = True        # the producing conv pass writes (sum, sumsq) partials
+    fusable = True
+    needs_stats = True
 
     def __init__(self, plan, alpha):
-        self.plan, self.alpha = plan, alpha
-        self.params = [alpha]
+        super().__init__(plan, alpha, [alpha])
+        self._applied = None  # the applied activation of a deferred norm, once a consumer needed it (materialise)
 
     def defer(self, y, stats):
         """statistics only: the apply pass is left to the consumers of ``y`` (operand normalisation on load,
         ctseg_conv_desc::in_mean_rstd); ``materialise`` records it for a consumer that cannot"""
         self.y = y
         self.mr = stats.emit_finalize(0, y.C)
-        self._applied = None
         y.pending_norm = self
         return y
 
     def materialise(self, y):
         if self._applied is None:
-            plan = self.plan
-            out = new_act(*y.dims, y.C, plan.dt, plan.device)
-            plan.emit("ctseg_instnorm_prelu_fwd", plan.dt, y.ptr(), y.ld, self.mr.data_ptr(), plan.store.p_ptr(self.alpha),
-                      None, 0, out.ptr(), out.ld, y.dims[0], y.S, y.C, keep=(y, out))
-            self._applied = out
+            self._applied = self._apply(y, None, None)
         return self._applied
 
-    def emit_fwd(self, y, stats, col0, res, out):
+    def _apply(self, y, res, out):
         plan = self.plan
+        if out is None:
+            out = plan_act(plan, y.dims, y.C)
+        plan.emit("ctseg_instnorm_prelu_fwd", plan.dt, y.ptr(), y.ld, self.mr.data_ptr(), plan.store.p_ptr(self.alpha),
+                  *_ptr_ld(res), out.ptr(), out.ld, y.dims[0], y.S, y.C, keep=(y, res, out))
+        return out
+
+    def emit_fwd(self, y, stats, col0, res, out):
         self.y = y
         self.mr = stats.emit_finalize(col0, y.C)
-        if out is None:
-            out = new_act(*y.dims, y.C, plan.dt, plan.device)
-        plan.emit("ctseg_instnorm_prelu_fwd", plan.dt, y.ptr(), y.ld, self.mr.data_ptr(), plan.store.p_ptr(self.alpha),
-                  res.ptr() if res is not None else None, res.ld if res is not None else 0, out.ptr(), out.ld,
-                  y.dims[0], y.S, y.C, keep=(y, res, out))
-        return out
+        return self._apply(y, res, out)
 
     def emit_bwd(self, g, dy_out=None, g_copy=None, colsum_out=None, apply=True):
         """g = dL/d(activation). Returns dL/dy (raw conv output); alpha's gradient goes to the flat buffer.
@@ -90,22 +106,16 @@ class _NormAct:
         on load (ctseg_wgrad_desc::dyn_*); returns the finalised sums instead."""
         plan, y = self.plan, self.y
         N, S, C = y.dims[0], y.S, y.C
-        P = _bwd_row_ranges(S, N, plan.dt)
-        ld = rup(C, 4)
         sums = torch.zeros((N, C, 2), dtype=torch.float32, device=plan.device)
-        if dy_out is None and apply:
-            dy_out = new_act(*y.dims, C, plan.dt, plan.device)
         a_ptr = plan.store.p_ptr(self.alpha)
-        mark = getattr(g, "bst", None)
-        fused = mark is not None and mark[0] is self
-        rec = getattr(plan, "norm_bwd", None)      # (tests: the statistics of every norm's backward, and where they came from)
+        # the pass that wrote g took the three sums in its epilogue (ctseg_conv_desc::bst_*): no reduce pass, no second read of g
+        fused = g.bst is not None and g.bst[0] is self
+        # (tests: the statistics of every norm's backward, and where they came from; a duck-typed one-layer plan keeps no record)
+        rec = getattr(plan, "norm_bwd", None)
         if rec is not None:
             rec.append((sums, fused))
-        if fused:
-            # the pass that wrote g took the three sums in its epilogue (ctseg_conv_desc::bst_*): no reduce pass, no second read of g
-            _, part, P, ld = mark
-        else:
-            part = torch.zeros((N, P, 3, ld), dtype=torch.float32, device=plan.device)
+        part, P, ld, dy_out = self._bwd_buffers(dy_out, g.bst if fused else None, apply)
+        if not fused:
             plan.emit("ctseg_instnorm_prelu_bwd_reduce", plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), a_ptr,
                       part.data_ptr(), P, ld, N, S, C, keep=(g, part))
         da_part = torch.zeros(N * C + 1, dtype=torch.float64, device=plan.device)
@@ -116,7 +126,7 @@ class _NormAct:
             plan.emit("ctseg_instnorm_prelu_dalpha", da_part.data_ptr(), N * C, plan.store.g_ptr(self.alpha), keep=(da_part,))
             return sums
         args = (plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), a_ptr, sums.data_ptr(), dy_out.ptr(), dy_out.ld,
-                g_copy.ptr() if g_copy is not None else None, g_copy.ld if g_copy is not None else 0, N, S, C)
+                *_ptr_ld(g_copy), N, S, C)
         slope = (da_part.data_ptr(), N * C, plan.store.g_ptr(self.alpha))
         if colsum_out is None:
             plan.emit("ctseg_instnorm_prelu_bwd_apply", *args, *slope, keep=(dy_out, g_copy))
@@ -138,7 +148,7 @@ def check_batch_norm(norm):
         raise NotImplementedError("BatchNorm with track_running_stats=False is not implemented")
 
 
-class _BatchNormAct:
+class _BatchNormAct(_NormBase):
     """BatchNorm (affine, running statistics) + PReLU of one conv output.
 
     Training mode (``plan.bn_train``): the conv epilogue's per-sample partials summed over the samples too
@@ -152,12 +162,11 @@ class _BatchNormAct:
 
     def __init__(self, plan, norm, alpha):
         check_batch_norm(norm)
-        self.plan, self.norm, self.alpha = plan, norm, alpha
-        self.gamma, self.beta = norm.weight, norm.bias
+        super().__init__(plan, alpha, [alpha, norm.weight, norm.bias])
+        self.norm, self.gamma, self.beta = norm, norm.weight, norm.bias
         self.eps, self.momentum = float(norm.eps), float(norm.momentum)
         self.train = plan.bn_train
         self.needs_stats = self.train
-        self.params = [alpha, norm.weight, norm.bias]
 
     def emit_fwd(self, y, stats, col0, res, out):
         plan, st = self.plan, self.plan.store
@@ -174,10 +183,9 @@ class _BatchNormAct:
         else:
             plan.emit("ctseg_batchnorm_eval_table", rm, rv, g_p, b_p, C, self.eps, ss.data_ptr(), keep=(ss,))
         if out is None:
-            out = new_act(*y.dims, C, plan.dt, plan.device)
+            out = plan_act(plan, y.dims, C)
         plan.emit("ctseg_scale_shift_prelu_fwd", plan.dt, y.ptr(), y.ld, ss.data_ptr(), st.p_ptr(self.alpha),
-                  res.ptr() if res is not None else None, res.ld if res is not None else 0, out.ptr(), out.ld, N, S, C,
-                  keep=(y, res, out))
+                  *_ptr_ld(res), out.ptr(), out.ld, N, S, C, keep=(y, res, out))
         return out
 
     def emit_bwd(self, g, dy_out=None, g_copy=None, colsum_out=None, apply=True):
@@ -185,12 +193,8 @@ class _BatchNormAct:
         assert self.train and apply and colsum_out is None
         plan, st, y = self.plan, self.plan.store, self.y
         N, S, C = y.dims[0], y.S, y.C
-        P = _bwd_row_ranges(S, N, plan.dt)
-        ld = rup(C, 4)
-        if dy_out is None:
-            dy_out = new_act(*y.dims, C, plan.dt, plan.device)
+        part, P, ld, dy_out = self._bwd_buffers(dy_out)
         g_p, b_p, a_p = st.p_ptr(self.gamma), st.p_ptr(self.beta), st.p_ptr(self.alpha)
-        part = torch.zeros((N, P, 3, ld), dtype=torch.float32, device=plan.device)
         plan.emit("ctseg_batchnorm_prelu_bwd_reduce", plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), g_p, b_p, a_p,
                   part.data_ptr(), P, ld, N, S, C, keep=(g, part))
         sums = torch.zeros((C, 2), dtype=torch.float32, device=plan.device)
@@ -198,8 +202,7 @@ class _BatchNormAct:
         plan.emit("ctseg_batchnorm_prelu_bwd_finalize", part.data_ptr(), N, P, ld, C, float(N * S), sums.data_ptr(),
                   st.g_ptr(self.gamma), st.g_ptr(self.beta), da_part.data_ptr(), keep=(sums, da_part))
         plan.emit("ctseg_batchnorm_prelu_bwd_apply", plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), g_p, b_p, a_p,
-                  sums.data_ptr(), dy_out.ptr(), dy_out.ld, g_copy.ptr() if g_copy is not None else None,
-                  g_copy.ld if g_copy is not None else 0, N, S, C, da_part.data_ptr(), C, st.g_ptr(self.alpha),
+                  sums.data_ptr(), dy_out.ptr(), dy_out.ld, *_ptr_ld(g_copy), N, S, C, da_part.data_ptr(), C, st.g_ptr(self.alpha),
                   keep=(dy_out, g_copy))
         return dy_out
 
@@ -221,6 +224,7 @@ class _ConvBlock:
         self.plan, self.mod = plan, mod
         self.gemm = GemmLayer(plan, name, mod.is_transposed, mod.kernel_size, mod.strides, mod.cin, [_parts(mod.conv)], cg,
                               need_dgrad)
+        self.first_gemm = self.gemm       # the GEMM that reads the node's input (as _ResUnit's)
         self.na = _norm_act(plan, mod)
         self.params = [mod.conv.weight, mod.conv.bias] + ([] if mod.conv_only else self.na.params)
 
@@ -238,9 +242,10 @@ class _ConvBlock:
         """the norm whose backward consumes the gradient handed to emit_bwd first (None: a convolution does)"""
         return self.na
 
-    def emit_bwd(self, g, out=None, accumulate=False, need_dx=True, split_at=None, bst=None, bst_col0=0):
-        """bst: the _NormAct that consumes the returned gradient (its channels from bst_col0 on) — its backward statistics are taken
-        by the pass that writes that gradient where the kernel can (GemmLayer.emit_dgrad)"""
+    def emit_bwd(self, g, out=None, accumulate=None, need_dx=True, split_at=None, bst=None, bst_col0=0):
+        """accumulate: an Act that is added to the returned gradient.  bst: the _NormAct that consumes the returned gradient (its
+        channels from bst_col0 on) — its backward statistics are taken by the pass that writes that gradient where the kernel can
+        (GemmLayer.emit_dgrad)"""
         bias = self.mod.conv.bias
         # (BatchNorm: the transposed conv's bias gradient is a separate ctseg_colsum over dOut)
         fuse_bias = self.na is not None and self.na.fusable and self.gemm.transposed and bias is not None
@@ -252,15 +257,15 @@ class _ConvBlock:
             # ... except where both consumers take 12-wide rows: the 64 -> <= 12 channel layer of the head (LDS-halo weight gradient
             # conv_wgrad_up_kernel<12> and the stride-2 halo pass staged in 8-byte pieces), a quarter fewer bytes in three passes
             gm = self.gemm
-            narrow = (os.environ.get("CTSEG_NARROW_DOUT", "1") != "0" and self.na.fusable and self.plan.dt == BF16 and gm.transposed and gm.s == 2 and
-                      gm.cin == 64 and self.x.ld == 64 and getattr(gm, "cgd", 0) == 16)
-            dy_wide = new_act(*y.dims, y.C, self.plan.dt, self.plan.device, ld=None if narrow else rup(y.C, nat.epc(self.plan.dt)))
+            narrow = (self.na.fusable and self.plan.dt == BF16 and gm.transposed and gm.s == 2 and gm.cin == 64 and self.x.ld == 64 and
+                      gm.cgd == 16)
+            dy_wide = plan_act(self.plan, y.dims, y.C, ld=None if narrow else rup(y.C, nat.epc(self.plan.dt)))
             dy = self.na.emit_bwd(g, dy_out=dy_wide, colsum_out=self.plan.store.g_ptr(bias) if fuse_bias else None)
         self.gemm.emit_wgrad(self.x, dy, bias_done=fuse_bias)
         self.plan.grads_ready(self.params)
         if not need_dx:
             return None
-        return self.gemm.emit_dgrad(dy, out=out, add=_addend(out, accumulate), split_at=split_at, bst=bst, bst_col0=bst_col0)
+        return self.gemm.emit_dgrad(dy, out=out, add=accumulate, split_at=split_at, bst=bst, bst_col0=bst_col0)
 
 
 class _ResUnit:
@@ -286,7 +291,9 @@ class _ResUnit:
         e = nat.epc(plan.dt)
         for i, u in enumerate(units[1:], 1):
             self.gemms.append(GemmLayer(plan, f"{name}.unit{i}", False, k, 1, mod.cout, [_parts(u.conv)], rup(mod.cout, e)))
+        self.first_gemm = self.gemms[0]
         self.nas = [_norm_act(plan, u) for u in units]
+        self.x = self.inputs = self.ys = None     # the node's input, every unit's input and raw conv output (set by the forward)
 
     def emit_fwd(self, x, out=None, out_f32=False):
         plan, C = self.plan, self.mod.cout
@@ -318,8 +325,8 @@ class _ResUnit:
     def first_bwd_norm(self):
         return self.nas[-1]
 
-    def emit_bwd(self, g, out=None, accumulate=False, need_dx=True, bst=None):
-        """g = dL/d(out).  out = last_activation + res  =>  both receive g.  bst: see _ConvBlock.emit_bwd."""
+    def emit_bwd(self, g, out=None, accumulate=None, need_dx=True, bst=None):
+        """g = dL/d(out).  out = last_activation + res  =>  both receive g.  accumulate, bst: see _ConvBlock.emit_bwd."""
         plan, C = self.plan, self.mod.cout
         n = len(self.units)
         d = g
@@ -329,7 +336,7 @@ class _ResUnit:
         dyn = (self.fused is not None and not need_dx and n >= 2 and self.nas[0] is not None and self.nas[0].fusable and
                self.fused.wgrad_dyn_ok(self.x, g, self.ys[0]))
         if self.fused is not None and not dyn:
-            dfused = new_act(*self.ys[0].dims, 2 * C, plan.dt, plan.device)   # [ d_res | d_y0 ]
+            dfused = plan_act(plan, self.ys[0].dims, 2 * C)   # [ d_res | d_y0 ]
         for i in range(n - 1, -1, -1):
             na, gm = self.nas[i], self.gemms[i]
             last = i == n - 1
@@ -363,7 +370,7 @@ class _ResUnit:
             plan.grads_ready([p for w, b, _ in self.fused.parts for p in (w, b)] + alpha0)
             if not need_dx:
                 return None
-            return self.fused.emit_dgrad(dfused, out=out, add=_addend(out, accumulate), bst=bst)
+            return self.fused.emit_dgrad(dfused, out=out, add=accumulate, bst=bst)
         g0 = self.gemms[0]
         g0.emit_wgrad(self.x, dy)
         ready = [g0.parts[0][0], g0.parts[0][1]] + alpha0
@@ -374,21 +381,26 @@ class _ResUnit:
         if not need_dx:
             return None
         if self.identity:
-            if not accumulate:
+            if accumulate is None:
                 return g0.emit_dgrad(dy, out=out, add=g, bst=bst)        # dx = g + dgrad(dy)
             # identity residual AND an accumulated target (a bottom block with equal channel counts under a dense skip gradient):
             # dx = g + dgrad(dy) into a fresh tensor, then one elementwise pass adds the accumulated term
             tmp = g0.emit_dgrad(dy, add=g)
-            acc = _addend(out, accumulate)
             if out is None:
-                out = new_act(*tmp.dims, tmp.C, plan.dt, plan.device)
-            plan.emit("ctseg_instnorm_prelu_fwd", plan.dt, tmp.ptr(), tmp.ld, None, None, acc.ptr(), acc.ld, out.ptr(), out.ld,
-                      tmp.dims[0], tmp.S, tmp.C, keep=(tmp, acc, out))       # mean_rstd = NULL: out = tmp + acc
+                out = plan_act(plan, tmp.dims, tmp.C)
+            plan.emit("ctseg_instnorm_prelu_fwd", plan.dt, tmp.ptr(), tmp.ld, None, None, accumulate.ptr(), accumulate.ld, out.ptr(),
+                      out.ld, tmp.dims[0], tmp.S, tmp.C, keep=(tmp, accumulate, out))       # mean_rstd = NULL: out = tmp + accumulate
             return out
         if self.res_gemm is None:
-            return g0.emit_dgrad(dy, out=out, add=_addend(out, accumulate), bst=bst)
-        dx = g0.emit_dgrad(dy, out=out, add=_addend(out, accumulate))
+            return g0.emit_dgrad(dy, out=out, add=accumulate, bst=bst)
+        dx = g0.emit_dgrad(dy, out=out, add=accumulate)
         return self.res_gemm.emit_dgrad(g, out=dx, add=dx, bst=bst)      # += dgrad of the 1x1 residual conv (the pass that completes dx)
+
+
+def _block(plan, mod, name, cg, need_dgrad=True):
+    """the node of a monai ResidualUnit / Convolution.  Both kinds offer ``first_gemm``, ``params``, ``emit_fwd``, ``emit_bwd`` and
+    ``first_bwd_norm`` to the level above"""
+    return (_ResUnit if hasattr(mod, "residual") else _ConvBlock)(plan, mod, name, cg, need_dgrad)
 
 
 class _Level:
@@ -398,7 +410,6 @@ class _Level:
         self.plan, self.is_top = plan, is_top
         down, skip, up = seq[0], seq[1], seq[2]
         e = nat.epc(plan.dt)
-        mk = lambda m, nm, c, nd=True: (_ResUnit if hasattr(m, "residual") else _ConvBlock)(plan, m, nm, c, nd)
         # construction order = MONAI's (sub, down, up); gradient-readiness order is up, sub, down
         sub = skip.submodule
         self.c1 = down.cout
@@ -406,9 +417,10 @@ class _Level:
             self.sub = _Level(plan, sub, name + ".1.submodule", rup(self.c1, e), False)
             self.c2 = sub[2][0].cout if _is_seq(sub[2]) else sub[2].cout
         else:
-            self.sub = mk(sub, name + ".1.submodule", rup(self.c1, e))
+            self.sub = _block(plan, sub, name + ".1.submodule", rup(self.c1, e))
             self.c2 = sub.cout
-        self.down = mk(down, name + ".0", cg, not is_top or plan.need_input_grad)
+        self.down = _block(plan, down, name + ".0", cg, not is_top or plan.need_input_grad)
+        self.cat = None           # the skip-concat buffer [down output | sub output] (set by the forward)
         ccat = self.c1 + self.c2
         if _is_seq(up):
             self.up0 = _ConvBlock(plan, up[0], name + ".2.0", rup(ccat, e))
@@ -422,8 +434,7 @@ class _Level:
 
     def emit_fwd(self, x, out=None, out_f32=False):
         plan = self.plan
-        od = self.down.gemms[0].out_dims(x.dims) if hasattr(self.down, "gemms") else self.down.gemm.out_dims(x.dims)
-        self.cat = new_act(*od, self.c1 + self.c2, plan.dt, plan.device)
+        self.cat = plan_act(plan, self.down.first_gemm.out_dims(x.dims), self.c1 + self.c2)
         xd = self.down.emit_fwd(x, out=self.cat.slice(0, self.c1))
         self.sub.emit_fwd(xd, out=self.cat.slice(self.c1, self.c2))
         if self.up1 is None:
@@ -441,60 +452,25 @@ class _Level:
     def first_bwd_norm(self):
         return self.up1.first_bwd_norm() if self.up1 is not None else self.up0.first_bwd_norm()
 
-    def emit_bwd(self, g, out=None, accumulate=False, need_dx=True, depth=0, bst=None):
-        plan = self.plan
-        # The head's weight gradients (HBM-bound, 1.2 ms of side-stream work) are not queued beside the head's own HBM-bound
-        # input-gradient / norm-backward passes but when the backward reaches level `defer_to`, whose passes are MFMA-bound:
-        # same-box 12.48 -> 12.41 ms/step at 2, 12.44 at 1, 12.69 at 3 (the side stream's tail grows).
-        # Round 2: with the head's weight gradients at 0.63 ms (x-column reuse, LDS-halo transposed-conv kernel) instead of 1.2 ms the
-        # deferral no longer pays: not deferred 9.69 / 9.70 ms/step, level 1 9.90, level 2 9.79 / 9.83, level 3 10.00 (same box).
-        defer_to = int(os.environ.get("CTSEG_DEFER_HEAD_WGRAD", "0"))   # 0 = off
-        if self.is_top and defer_to > 0:
-            plan._defer = []
-        if depth == defer_to and depth > 0 and getattr(plan, "_stash", None):
-            plan._defer, plan._stash = plan._stash, None
-            plan.flush_deferred()
+    def emit_bwd(self, g, out=None, accumulate=None, need_dx=True, bst=None):
+        # (Queueing the head's weight gradients only when the backward reaches a deeper, MFMA-bound level paid while they took 1.2 ms
+        # (round 1: 12.48 -> 12.41 ms/step); at 0.63 ms it costs 0.1 - 0.3 ms/step (round 2, and the round-4 knob sweep).  Removed.)
         if self.up1 is not None:
             g = self.up1.emit_bwd(g, bst=self.up0.first_bwd_norm())
         # [d(skip) | d(sub output)], as two dense tensors where the kernel can; the second half feeds the sub-block's last norm
         gcat = self.up0.emit_bwd(g, split_at=self.c1, bst=self.sub.first_bwd_norm(), bst_col0=self.c1)
-        if self.is_top and defer_to > 0:
-            plan._stash, plan._defer = plan._defer, None     # only the head's weight gradients wait
         # d(skip) = gcat[:, :c1] + d(sub input).  The sum goes to a DENSE tensor (the addend is read from the concat-gradient
         # slice): the norm-backward passes of the down block then stream full cache lines instead of half of every line
-        if os.environ.get("CTSEG_DENSE_SKIP_GRAD", "1") != "0":
-            kw = {"depth": depth + 1} if isinstance(self.sub, _Level) else {}
-            gskip = self.sub.emit_bwd(gcat.slice(self.c1, self.c2), out=None, accumulate=gcat.slice(0, self.c1),
-                                      bst=self.down.first_bwd_norm(), **kw)
-        else:
-            self.sub.emit_bwd(gcat.slice(self.c1, self.c2), out=gcat.slice(0, self.c1), accumulate=True)
-            gskip = gcat.slice(0, self.c1)
-        if self.is_top and getattr(plan, "_stash", None):     # never flushed below (fewer levels than asked for)
-            plan._defer, plan._stash = plan._stash, None
-            plan.flush_deferred()
+        gskip = self.sub.emit_bwd(gcat.slice(self.c1, self.c2), accumulate=gcat.slice(0, self.c1), bst=self.down.first_bwd_norm())
         return self.down.emit_bwd(gskip, out=out, accumulate=accumulate, need_dx=need_dx, bst=bst)
 
 
-def _make_side_stream(device):
-    """the weight-gradient stream.  CTSEG_SIDE_PRIORITY=low|high: a HIP stream of the least / greatest priority the device offers
-    (hipStreamCreateWithPriority through the runtime library torch already loaded), wrapped for torch; default: a plain stream."""
-    want = os.environ.get("CTSEG_SIDE_PRIORITY", "")
-    if want in ("low", "high"):
-        # created by torch itself, i.e. in the HIP runtime torch has loaded (a second libamdhip64 bound by soname could be the
-        # system's copy beside the wheel's: a stream handle of one runtime is invalid in the other).  torch: lower number = higher
-        # priority; 0 is the default, negative values are clamped to the device's greatest priority.
-        prio = 0 if want == "low" else -1
-        if os.environ.get("CTSEG_SIDE_PRIORITY_VERBOSE"):
-            print(f"side stream priority {prio} (torch convention: -1 = high, 0 = default / lowest)", file=sys.stderr)
-        return torch.cuda.Stream(device=device, priority=prio)
-    return torch.cuda.Stream(device=device)
-
-
 class Plan:
-    def __init__(self, engine, N, X, Y, Z, inference=False, need_input_grad=False, dt=None, bn_train=False):
+    def __init__(self, engine, N, X, Y, Z, inference=False, need_input_grad=False, dt=None, bn_train=False, narrow_rows=False):
         net = engine.net
         self.inference = inference        # forward program only: no gradient buffers, no backward program
         self.bn_train = bn_train          # BatchNorm layers: batch statistics + running-statistics update (else: running statistics)
+        self.narrow_rows = narrow_rows    # fresh 16-bit activations of 9..12 channels are laid out 12 wide (engine.default_ld)
         self.engine, self.store, self.device = engine, engine.store, engine.device
         self.dt = engine.dt if dt is None else dt        # storage dtype of THIS plan (Engine.train_dt() for training plans)
         if self.dt == nat.F16 and not inference:
@@ -509,26 +485,37 @@ class Plan:
         # of the U-Net, capstone/training/base_trainer.py:53,81-85); the stem then gets an input-gradient operand
         self.need_input_grad = need_input_grad and not inference
         self.packer = Packer(self)
-        self.fwd, self.bwd, self._cur = [], [], None
-        self._defer = None
-        self._keep = []
-        self.ready_marks = []          # (program index in bwd, flat offset end) for gradient all-reduce overlap
+        self.fwd, self.bwd = [], []    # the recorded programs: (name, cfunc, args) per op
+        self._cur = None               # the program being recorded (None once recording is over)
+        self._keep = []                # everything the recorded pointers point into
+        self.ready_marks = []          # (program index in bwd, flat offsets of the gradients final there) for all-reduce overlap
+        self.norm_bwd = []             # (sums, statistics came from the producing pass) of every InstanceNorm backward, for the tests
+        # slab reduces collected for the next batched launch (_batch_reduce), the gradients that become final with it, and how many
+        # of distributed.SPLIT_FRACTIONS the ready prefix has crossed
+        self._pending_reduce, self._pending_ready, self._reduce_frac = [], [], 0
         self.fwd_gen = 0               # forwards run on this plan's (single) set of activation buffers
+        self.logits_current = True     # False after a forward that stopped before the logits convolution (skip_head)
+        self.dlogits_is_current = False   # a fused loss wrote d loss / d logits of the last forward and no backward consumed it yet
+        self.dlogits = self.dx = None  # gradient buffers of the logits / the input (training plans; dx: need_input_grad)
+        self._head_ce = None           # (n_classes, slots, logits conv descriptor): head_ce_slots' answer, cached
+        self._repack_ev = self._repack_ev2 = None   # side-stream events of repack_after_update: first pass's operand / the rest
+        self._side = self._side_edges = self._side_ev = self._join_ev = None   # weight-gradient stream and its events (_side_setup)
+        self._ddp_points = None        # distributed.GradAllReducer.points_for: split points of this plan's backward, cached
+        self._ctseg_loss = None        # the trainers' loss engine for this plan's shape
         self.shape = (N, X, Y, Z)
         cin = net.in_channels
         self.root = _Level(self, net.model, "model", cin, True)
         # the pack of the first forward pass (the stem): rebuilt first after an optimizer step, see repack_after_update
-        first = self.root.down.gemms[0] if hasattr(self.root.down, "gemms") else self.root.down.gemm
-        self.packer.first = (first.fwd_pack["base"], first.fwd_pack["base"] + first.fwd_pack["size"])
+        first = self.root.down.first_gemm.fwd_pack
+        self.packer.first = (first["base"], first["base"] + first["size"])
         self.packer.finalize()
-        self.norm_bwd = []
         # ---- record programs ----
         self.x = Act(torch.zeros((N, X, Y, Z, cin), dtype=nat.torch_dtype(self.dt), device=self.device), cin, 0, self.dt)
         self._cur = self.fwd
         self.logits = self.root.emit_fwd(self.x, out_f32=True)
         assert self.logits.t.dtype == torch.float32
         if not inference:
-            self.dlogits = new_act(*self.logits.dims, net.out_channels, self.dt, self.device)
+            self.dlogits = plan_act(self, self.logits.dims, net.out_channels)
             self._cur = self.bwd
             self.dx = self.root.emit_bwd(self.dlogits, need_dx=self.need_input_grad)
             self._flush_reduces()
@@ -536,22 +523,10 @@ class Plan:
 
     # ---- recording ----
     def emit(self, name, *args, keep=()):
-        fn = getattr(nat.lib(), name)
-        conv = []
-        for a in args:
-            if isinstance(a, (nat.ConvDesc, nat.WgradDesc)):
-                self._keep.append(a)
-                conv.append(a)      # ctypes passes byref through the POINTER argtype
-            else:
-                conv.append(a)
         self._keep.append(keep)
-        if name == "ctseg_conv_wgrad_reduce" and self._batch_reduce(conv):
+        if name == "ctseg_conv_wgrad_reduce" and self._batch_reduce(args):
             return
-        op = (name, fn, tuple(conv))
-        if self._defer is not None and self._cur is self.bwd and name in self.SIDE_OPS:
-            self._defer.append(op)        # head weight gradients: queued later, beside the MFMA-bound deep levels
-        else:
-            self._cur.append(op)
+        self._cur.append((name, getattr(nat.lib(), name), args))      # (descriptors: ctypes passes byref through the POINTER argtype)
 
     def emit_colsum(self, x, out_ptr):
         rows = x.dims[0] * x.S
@@ -567,14 +542,11 @@ class Plan:
     # (ctseg_conv_wgrad_reduce_batch, bit-identical sums) per gradient chunk: where the ready prefix of the flat gradient crosses the
     # split fractions of the data-parallel exchange (distributed.split_points: 60 %, 92 %) and at the end.  CTSEG_REDUCE_BATCH=0: off.
     def _batch_reduce(self, args):
-        if (self._cur is not self.bwd or self._defer is not None or getattr(self, "_stash", None) or
-                os.environ.get("CTSEG_REDUCE_BATCH", "1") == "0"):
+        if self._cur is not self.bwd or os.environ.get("CTSEG_REDUCE_BATCH", "1") == "0":
             return False
         ws, nslabs, kpad_w, cn_pad, A, AS, T, col0, nb, dw, db = args
         if nat.lib().ctseg_conv_wgrad_reduce_batch_ok(ws, cn_pad, col0, nb) != 1:
             return False
-        if not hasattr(self, "_pending_reduce"):
-            self._pending_reduce, self._pending_ready, self._reduce_frac = [], [], 0
         self._pending_reduce.append(args)
         return True
 
@@ -590,7 +562,7 @@ class Plan:
         return prefix
 
     def _flush_reduces(self, only_if_chunk=False):
-        jobs = getattr(self, "_pending_reduce", None)
+        jobs = self._pending_reduce
         if not jobs:
             return
         if only_if_chunk:
@@ -616,25 +588,15 @@ class Plan:
             self.ready_marks.append((len(self.bwd), ready))
 
     def grads_ready(self, params):
-        if self._cur is self.bwd:
-            offs = [self.store.off(p) for p in params if p is not None]
-            if self._defer is not None:
-                self._defer.append(("ready", offs))
-            elif getattr(self, "_pending_reduce", None):
-                # (some of) these gradients come out of reduces that are still collected: final when the batch is issued
-                self._pending_ready.extend(offs)
-                self._flush_reduces(only_if_chunk=True)
-            else:
-                self.ready_marks.append((len(self.bwd), offs))
-
-    def flush_deferred(self):
-        """append the deferred side-stream ops (and their gradient-readiness marks) to the backward program"""
-        ops, self._defer = self._defer, None
-        for op in ops or ():
-            if op[0] == "ready":
-                self.ready_marks.append((len(self.bwd), op[1]))
-            else:
-                self.bwd.append(op)
+        if self._cur is not self.bwd:
+            return
+        offs = [self.store.off(p) for p in params if p is not None]
+        if self._pending_reduce:
+            # (some of) these gradients come out of reduces that are still collected: final when the batch is issued
+            self._pending_ready.extend(offs)
+            self._flush_reduces(only_if_chunk=True)
+        else:
+            self.ready_marks.append((len(self.bwd), offs))
 
     # ---- running ----
     @staticmethod
@@ -658,13 +620,13 @@ class Plan:
         the re-layout (0.07 ms, nothing else to overlap it with at the head of the next step) runs there, beside the loss
         bookkeeping and the next batch's input conversion; the next forward waits for its event."""
         side = self.side_stream()
-        if side is None or os.environ.get("CTSEG_REPACK_SIDE", "1") == "0":
+        if side is None:
             self.packer.dirty = True
             return
         main = torch.cuda.current_stream(self.device)
         side.wait_stream(main)
         with torch.cuda.stream(side):
-            if self.packer.can_split() and os.environ.get("CTSEG_REPACK_SPLIT", "1") != "0":
+            if self.packer.can_split():
                 # the next step's first convolution needs its own operand and the biases only: everything else is rebuilt BESIDE
                 # that convolution (the whole re-layout sat on the critical path between two steps: Adam -> repack -> stem)
                 self.packer.refresh(force=True, part="first")
@@ -678,12 +640,11 @@ class Plan:
     def head_ce_slots(self, n_classes):
         """partial-sum slots per sample of ctseg_conv_logits_ce for this plan's logits convolution (0: not eligible — the
         convolution and the loss then run as two passes)"""
-        cache = getattr(self, "_head_ce", None)
+        cache = self._head_ce
         if cache is None or cache[0] != n_classes:
             slots = 0
             name, _, args = self.fwd[-1]
-            if (name == "ctseg_conv_igemm" and not self.inference and args[0].out == self.logits.ptr() and
-                    os.environ.get("CTSEG_FUSED_HEAD_CE", "1") != "0"):
+            if name == "ctseg_conv_igemm" and not self.inference and args[0].out == self.logits.ptr():
                 slots = nat.lib().ctseg_conv_logits_ce_slots(args[0], n_classes)
             cache = self._head_ce = (n_classes, max(slots, 0), args[0])
         return cache[1]
@@ -693,26 +654,23 @@ class Plan:
         logits convolution (the caller runs it fused with the loss: ctseg_conv_logits_ce); ``self.logits`` is then NOT updated."""
         if x is not None:
             self.load_input(x)
-        ev = getattr(self, "_repack_ev", None)
-        if ev is not None:
-            torch.cuda.current_stream(self.device).wait_event(ev)
+        if self._repack_ev is not None:
+            torch.cuda.current_stream(self.device).wait_event(self._repack_ev)
             self._repack_ev = None
         if self.packer.stale():
             # the parameters changed since repack_after_update queued its two-part re-layout (load_state_dict, a broadcast, a
             # foreign optimizer): refresh() is about to rewrite the packed buffer on THIS stream while the side stream's "rest" part
             # may still be reading the flat buffer and writing the same operands — order it behind that part first
-            ev2 = getattr(self, "_repack_ev2", None)
-            if ev2 is not None:
-                torch.cuda.current_stream(self.device).wait_event(ev2)
+            if self._repack_ev2 is not None:
+                torch.cuda.current_stream(self.device).wait_event(self._repack_ev2)
                 self._repack_ev2 = None
         self.packer.refresh()
         self.fwd_gen += 1
         # a d loss / d logits left by a fused loss whose backward never ran (skipped step, exception) belongs to the OLD batch
         self.dlogits_is_current = False
         end = len(self.fwd) - 1 if skip_head else None
-        ev2 = getattr(self, "_repack_ev2", None)
+        ev2, self._repack_ev2 = self._repack_ev2, None
         if ev2 is not None:
-            self._repack_ev2 = None
             self.run(self.fwd, nat.stream_ptr(), 0, 1)           # the first pass (its operand is ready: _repack_ev)
             torch.cuda.current_stream(self.device).wait_event(ev2)
             self.run(self.fwd, nat.stream_ptr(), 1, end)
@@ -735,8 +693,10 @@ class Plan:
         return self._side
 
     def _side_setup(self):
-        if getattr(self, "_side", None) is None:
-            self._side = _make_side_stream(self.device)
+        if self._side is None:
+            # (a plain stream: one of the device's least or greatest priority measured the same, 10.60 / 10.63 / 10.67 ms/step,
+            # DESIGN.md 3.6)
+            self._side = torch.cuda.Stream(device=self.device)
             self._side_edges = [i for i in range(len(self.bwd) + 1)
                                 if i == 0 or i == len(self.bwd) or
                                 (self.bwd[i][0] in self.SIDE_OPS) != (self.bwd[i - 1][0] in self.SIDE_OPS)]
@@ -793,8 +753,6 @@ class Plan:
                     hooks[a]()
                 busy = True
             if self.bwd[a][0] in self.SIDE_OPS:
-                if os.environ.get("CTSEG_TIMING_SKIP_SIDE") == "1":      # timing-only: what the weight-gradient stream costs the step
-                    continue
                 ev = self._side_ev.get(a)
                 if ev is None:
                     ev = self._side_ev[a] = torch.cuda.Event()
@@ -958,16 +916,13 @@ class Engine:
     def _record(self, N, sp, inference, need_input_grad=False, dt=None, bn_train=False):
         """record a Plan; bf16 tensors of 9..12 channels (the class logits' neighbours) are laid out 12 wide when every pass
         that touches them can move such rows (ctseg_conv_narrow_ok / ctseg_wgrad_narrow_ok), 16 wide otherwise"""
-        from . import engine as eng
         dt = self.dt if dt is None else dt
         if nat.is16(dt) and os.environ.get("CTSEG_NARROW_ROWS", "1") != "0":
-            eng.NARROW_ROWS[0] = True
             try:
-                return Plan(self, N, *sp, inference=inference, need_input_grad=need_input_grad, dt=dt, bn_train=bn_train)
-            except eng.NarrowUnsupported:
+                return Plan(self, N, *sp, inference=inference, need_input_grad=need_input_grad, dt=dt, bn_train=bn_train,
+                            narrow_rows=True)
+            except NarrowUnsupported:
                 pass
-            finally:
-                eng.NARROW_ROWS[0] = False
         return Plan(self, N, *sp, inference=inference, need_input_grad=need_input_grad, dt=dt, bn_train=bn_train)
 
     # ---- raw (no autograd) API used by the native training step, bench and tests ----
@@ -976,7 +931,7 @@ class Engine:
 
     def logits_view(self, plan=None):
         plan = plan or self.last_plan
-        if not getattr(plan, "logits_current", True):
+        if not plan.logits_current:
             # the last forward on this plan stopped before the logits convolution (fit_step(keep_logits=False): the cross-entropy
             # ran in that convolution's epilogue and the fp32 logits were never written): what the buffer holds is an older step's
             raise nat.NativeError("the logits of the last step were not materialised (fit_step(keep_logits=False) fuses the "
@@ -1010,10 +965,7 @@ class _GradHandOff:
 
     def __init__(self, store):
         self.store = store
-        views = getattr(store, "_grad_views", None)
-        if views is None:
-            views = store._grad_views = [store.grad_view(p) for p in store.params]
-        self.views = views
+        self.views = store.grad_views()
         base = store.flat_g.data_ptr()
         self.kept = None
         self.aliased = []
@@ -1076,7 +1028,7 @@ class _StepLossFn(torch.autograd.Function):
         if plan.fwd_gen != ctx.gen:
             raise RuntimeError("the activations of this step were overwritten by a later forward on the same input shape "
                                "(one set of activation buffers per shape): call backward() before the next training forward")
-        if not getattr(plan, "dlogits_is_current", False):
+        if not plan.dlogits_is_current:
             raise RuntimeError("backward() ran twice on the same training step (its buffers are consumed by the first)")
         plan.dlogits_is_current = False
         dl = plan.dlogits.t
@@ -1104,8 +1056,7 @@ class _UNetFn(torch.autograd.Function):
         if plan.fwd_gen != ctx.gen:
             raise RuntimeError("the activations of this forward were overwritten by a later forward on the same input shape "
                                "(one set of activation buffers per shape): call backward() before the next training forward")
-        fused = getattr(plan, "dlogits_is_current", False)
-        if not fused:
+        if not plan.dlogits_is_current:       # (else: a fused loss already wrote d loss / d logits)
             C = engine.net.out_channels
             gv = g if engine.net.dimensions == 3 else g.unsqueeze(-1)
             plan.dlogits.t[..., :C].copy_(gv.permute(0, 2, 3, 4, 1))
