@@ -82,6 +82,38 @@ static inline ConvKArgs conv_args(const ctseg_conv_desc* d) {
   return a;
 }
 
+// ---- Statistics in the epilogue -----------------------------------------------------------------------------------------------
+// A persistent workgroup keeps its InstanceNorm sums (forward: two; backward, BstArgs: three) in registers across its tiles and
+// writes them once per (workgroup, sample) — one partial row per workgroup instead of one per tile: no per-tile shuffles or barrier,
+// and the finalize pass that follows reads 30-48x fewer rows.  Every total is formed in a FIXED order — the xor 8, 4, 2, 1 butterfly
+// over the 16 voxel lanes of an MFMA tile, then the waves that share a column in ascending order, no atomics — and lands in a slot
+// that depends on the launch geometry alone: a run is bit-reproducible.  Every thread of the workgroup calls a kernel's flush (two
+// barriers).  Staging and wave totals are spelled out per kernel (each names what a shared templated flush cost it); conv_epilogue
+// is per tile and uses sum16 and stats_slot only.
+// sum of each argument over the 16 voxel lanes (lane & 15) that hold the same columns of an MFMA tile; every lane gets the totals
+template <class... F> __device__ __forceinline__ void sum16(F&... v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) ((v += __shfl_xor(v, o, 64)), ...);
+}
+
+// Index of column 0 of partial row `which` of slot `slot` (a workgroup: blockIdx.x; the generic kernels: a tile) of sample n,
+// in P.stats (forward sums) and in B.part (BST sums)
+__device__ __forceinline__ int64_t stats_slot(const ConvKArgs& P, int n, int64_t slot, int which) { return (((int64_t)n * P.stats_tiles + P.stats_tile0 + slot) * 2 + which) * P.stats_ld; }
+__device__ __forceinline__ int64_t bst_slot(const BstArgs& B, int n, int64_t slot, int which) { return (((int64_t)n * B.P + slot) * 3 + which) * B.ld; }
+
+// The sample whose sums the accumulators hold.  enter(n, flush) at the top of every tile: on a change of sample the sums of the
+// previous one (if any) are flushed — true: n is new, per-sample constants are due; finish(flush) after the tile loop.
+struct SampleRun {
+  int cur = -1;
+  template <class Flush> __device__ __forceinline__ bool enter(int n, Flush flush) {
+    if (n == cur) return false;
+    if (cur >= 0) flush(cur);
+    cur = n;
+    return true;
+  }
+  template <class Flush> __device__ __forceinline__ void finish(Flush flush) { if (cur >= 0) flush(cur); }
+};
+
 // Workgroups reach the 8 XCDs round-robin by linear id.  Tile = (L & 7) * chunk + (L >> 3) gives every XCD one contiguous
 // range of row tiles, so the halo rows neighbouring tiles share are fetched by ONE L2 instead of by all eight.  -1: no tile.
 __device__ __forceinline__ int xcd_tile(int L, int total) {
@@ -184,14 +216,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& P, const ctseg_co
       }
     }
   }
-  if (P.stats != nullptr) {
+  if (P.stats != nullptr) {       // (not persistent: one partial slot per TILE, staged per wave row wm)
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = ssum[j][e], b = ssq[j][e];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        sum16(a, b);
         if (r16 == 0) {
           const int c = wn * WTN + j * 16 + 4 * q4 + e;
           sStats[(wm * 2 + 0) * BN + c] = a;
@@ -205,8 +236,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& P, const ctseg_co
     float a = 0.f;
 #pragma unroll
     for (int m = 0; m < WGM; ++m) a += sStats[(m * 2 + which) * BN + c];
-    const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + (int64_t)cls_index * P.tiles + tile;
-    P.stats[(slot_t * 2 + which) * P.stats_ld + col0 + c] = a;
+    P.stats[stats_slot(P, n, (int64_t)cls_index * P.tiles + tile, which) + col0 + c] = a;
   }
   // backward InstanceNorm statistics of the stored gradient (ConvKArgs::bst): a thread keeps ONE 8-channel chunk column through the
   // store loop below (NTHR is a multiple of the chunks per row), so its 8 + 8 + 1 sums stay in registers for the whole tile
@@ -315,7 +345,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& P, const ctseg_co
   }
   if (bst) {
     // lanes l, l + cpr, l + 2 cpr ... of a wave hold the same chunk column (cpr = BN / 8 divides 64): butterflies, then the waves
-    // in order through LDS (the transposed tile is dead once every thread has left the store loop) — fixed order, no atomics
+    // in order through LDS (the transposed tile is dead once every thread has left the store loop) — fixed order, no atomics.
+    // (the lanes that share a column are cpr apart: a butterfly from 32 down to CPR, not sum16; only the slot index is the shared bst_slot)
     constexpr int CPR = BN / 8, NW = WGM * WGN;
     float qv[17];
 #pragma unroll
@@ -339,8 +370,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvKArgs& P, const ctseg_co
       for (int w = 0; w < NW; ++w) s += red[(w * CPR + cc) * 17 + k];
       const int which = k < 8 ? 0 : (k < 16 ? 1 : 2);
       const int c = col0 + cc * 8 + (k & 7) * (k < 16 ? 1 : 0) - P.bst.col0;
-      const int64_t slot = (int64_t)n * P.bst.P + (int64_t)cls_index * P.tiles + tile;
-      if (c >= 0 && c < P.bst.C) P.bst.part[(slot * 3 + which) * P.bst.ld + c] = s;
+      if (c >= 0 && c < P.bst.C) P.bst.part[bst_slot(P.bst, n, (int64_t)cls_index * P.tiles + tile, which) + c] = s;
     }
   }
 }

@@ -213,7 +213,9 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
   for (int j = 0; j < NT; ++j)
 #pragma unroll
     for (int e = 0; e < 4; ++e) { wsum[j][e] = 0.f; wsq[j][e] = 0.f; }
-  int stat_n = -1;
+  // Own staging and wave totals: the templated flush took the statistics variants from 24 / 28 to 76 / 88 bytes of scratch per lane,
+  // the BST ones 227 -> 235 VGPRs
+  SampleRun stat_run;
   auto flush_stats = [&](int n) {
     // each (channel) column is owned by the waves with the same jn0: VB = 32 all 8 waves; VB = 64 the 4 waves of a column half
 #pragma unroll
@@ -221,8 +223,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = wsum[j][e], b = wsq[j][e];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        sum16(a, b);
         if (r16 == 0) {
           const int c = (jn0 + j) * 16 + 4 * q4 + e;
           sStats[(wave * 2 + 0) * DH_CN + c] = a;
@@ -243,8 +244,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
 #pragma unroll
         for (int w = 0; w < 4; ++w) a += sStats[((2 * w + par) * 2 + which) * DH_CN + c];
       }
-      const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + blockIdx.x;
-      if (col0 + c < P.stats_ld) P.stats[(slot_t * 2 + which) * P.stats_ld + col0 + c] = a;
+      if (col0 + c < P.stats_ld) P.stats[stats_slot(P, n, blockIdx.x, which) + col0 + c] = a;
     }
     __syncthreads();
   };
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) yoff[rt] = BST ? ((va[rt] * G.oa + vb[rt] * G.ob + pc * G.oc) * P.bst.y_ld + 8 * ychunk) * 2 : 0;
   u32x4 yq[RT];
-  int bst_n = -1;
+  SampleRun bst_run;
   auto y_issue = [&](int n, int a0, int b0, int c0) {
     const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(P.bst.y + (int64_t)n * y_sample_bytes, y_sample_bytes);
     const int soff = (a0 * G.oa + b0 * G.ob + c0 * G.oc) * P.bst.y_ld * 2;
@@ -285,8 +285,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         float a = q1[h][e], b = q2[h][e];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        sum16(a, b);
         if (r16 == 0) {
           sStats[(wave * 3 + 0) * 32 + ychunk * 8 + 2 * h + e] = a;
           sStats[(wave * 3 + 1) * 32 + ychunk * 8 + 2 * h + e] = b;
@@ -295,8 +294,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
       }
     {
       float c = q3;
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+      sum16(c);
       if (r16 == 0) sStats[(wave * 3 + 2) * 32 + ychunk * 8] = c;      // the slope term: only its total over the channels matters
       q3 = 0.f;
     }
@@ -308,7 +306,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
 #pragma unroll
         for (int w = 0; w < DH_NTHR / 64; ++w) a += sStats[(w * 3 + which) * 32 + c];
       }
-      P.bst.part[(((int64_t)n * P.bst.P + blockIdx.x) * 3 + which) * P.bst.ld + c] = a;
+      P.bst.part[bst_slot(P.bst, n, blockIdx.x, which) + c] = a;
     }
     __syncthreads();
   };
@@ -337,16 +335,9 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
     const int tn = t + stride;
     int n, a0, b0, c0;
     tile_origin(t, n, a0, b0, c0);
-    if (STATS && n != stat_n) {
-      if (stat_n >= 0) flush_stats(stat_n);
-      stat_n = n;
-    }
+    if (STATS) stat_run.enter(n, flush_stats);
     if constexpr (BST) {
-      if (n != bst_n) {
-        if (bst_n >= 0) flush_bst(bst_n);
-        bst_n = n;
-        bst_consts(n);
-      }
+      if (bst_run.enter(n, flush_bst)) bst_consts(n);
       y_issue(n, a0, b0, c0);
     }
     f32x4 acc[RT][NT];
@@ -462,8 +453,8 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
       __syncthreads();
     }
   }
-  if (STATS && stat_n >= 0) flush_stats(stat_n);
-  if constexpr (BST) { if (bst_n >= 0) flush_bst(bst_n); }
+  if (STATS) stat_run.finish(flush_stats);
+  if constexpr (BST) bst_run.finish(flush_bst);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------

@@ -145,17 +145,15 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
   const int osb = second ? G.out2_sample_bytes : G.out_sample_bytes;
 
   float wsum[4] = {0.f, 0.f, 0.f, 0.f}, wsq[4] = {0.f, 0.f, 0.f, 0.f};
-  int stat_n = -1;
+  SampleRun stat_run;
   auto flush_stats = [&](int n) {       // the wave owns its 16 columns: butterfly over the 16 voxel lanes, no LDS, no barrier
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float a = wsum[e], b = wsq[e];
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+      sum16(a, b);
       if (r16 == 0) {
-        const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + blockIdx.x;
-        P.stats[(slot_t * 2 + 0) * P.stats_ld + col0 + 4 * q4 + e] = a;
-        P.stats[(slot_t * 2 + 1) * P.stats_ld + col0 + 4 * q4 + e] = b;
+        P.stats[stats_slot(P, n, blockIdx.x, 0) + col0 + 4 * q4 + e] = a;
+        P.stats[stats_slot(P, n, blockIdx.x, 1) + col0 + 4 * q4 + e] = b;
       }
       wsum[e] = 0.f;
       wsq[e] = 0.f;
@@ -168,7 +166,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
   const float bal = BST ? P.bst.alpha[0] : 1.f;
   float brs[4] = {0.f, 0.f, 0.f, 0.f}, bnm[4] = {0.f, 0.f, 0.f, 0.f};                      // rstd, -mean * rstd of the lane's channels
   float b1[4] = {0.f, 0.f, 0.f, 0.f}, b2[4] = {0.f, 0.f, 0.f, 0.f}, b3 = 0.f;
-  int bst_n = -1;
+  SampleRun bst_run;
   const int y_sample_bytes = BST ? (int)((int64_t)P.Xo * P.Yo * P.Zo * P.bst.y_ld * 2) : 0;   // < 2^31 (host-checked)
   auto bst_consts = [&](int n) {
     if (ywave) {
@@ -185,11 +183,11 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = b1[e], b = b2[e], c = e == 0 ? b3 : 0.f;        // (one PReLU slope: only the total of the third sum matters)
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); c += __shfl_xor(c, o, 64); }
+        sum16(a, b, c);
         if (r16 == 0) {
-          float* row = P.bst.part + ((int64_t)n * P.bst.P + blockIdx.x) * 3 * P.bst.ld + ych + e;
-          row[0] = a; row[P.bst.ld] = b; row[2 * P.bst.ld] = c;
+          P.bst.part[bst_slot(P.bst, n, blockIdx.x, 0) + ych + e] = a;
+          P.bst.part[bst_slot(P.bst, n, blockIdx.x, 1) + ych + e] = b;
+          P.bst.part[bst_slot(P.bst, n, blockIdx.x, 2) + ych + e] = c;
         }
         b1[e] = 0.f; b2[e] = 0.f;
       }
@@ -212,11 +210,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
     tile_origin(t, n, a0, b0, c0);
     u32x2 yv[4] = {u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}};
     if constexpr (BST) {
-      if (n != bst_n) {
-        if (bst_n >= 0) flush_bst(bst_n);
-        bst_n = n;
-        bst_consts(n);
-      }
+      if (bst_run.enter(n, flush_bst)) bst_consts(n);
       // y of this tile's voxels, ahead of the next tile's DMA pieces (always issued: the counted wait at the loop head)
       const __amdgpu_buffer_rsrc_t yrs = buffer_rsrc(P.bst.y + (int64_t)n * y_sample_bytes, y_sample_bytes);
       const int ysoff = (a0 * G.oa + b0 * G.ob + c0 * G.oc) * P.bst.y_ld * 2;
@@ -227,10 +221,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
       }
     }
     if (t + stride < last) dma(t + stride, buf ^ 1);
-    if (STATS && n != stat_n) {
-      if (stat_n >= 0) flush_stats(stat_n);
-      stat_n = n;
-    }
+    if (STATS) stat_run.enter(n, flush_stats);
     f32x4 acc[4];
 #pragma unroll
     for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -283,8 +274,8 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
     }
     stores_in_flight = true;
   }
-  if (STATS && stat_n >= 0) flush_stats(stat_n);
-  if constexpr (BST) { if (bst_n >= 0) flush_bst(bst_n); }
+  if (STATS) stat_run.finish(flush_stats);
+  if constexpr (BST) bst_run.finish(flush_bst);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------

@@ -147,13 +147,14 @@ __global__ __launch_bounds__((HaloCfg<VB, NT>::NTHR)) void conv_halo_kernel(cons
       bias[j][e] = (P.bias != nullptr && ch < P.Cn) ? P.bias[ch] : 0.f;
     }
 
-  // InstanceNorm partial sums are kept in registers across the workgroup's tiles and written once per (workgroup, sample):
-  // one partial slot per workgroup instead of one per tile (no per-tile barrier, 30x fewer partials to finalize)
+  // InstanceNorm partial sums, one slot per (workgroup, sample): conv_common.h "Statistics in the epilogue"
   float wsum[NT][4], wsq[NT][4];
 #pragma unroll
   for (int j = 0; j < NT; ++j)
 #pragma unroll
     for (int e = 0; e < 4; ++e) { wsum[j][e] = 0.f; wsq[j][e] = 0.f; }
+  // Own staging and wave totals: the templated flush took this kernel 182 -> 193 VGPRs (64-byte voxels, 32 columns) and 252 -> 264
+  // (32-byte); own sample-change stanza: SampleRun took it 252 -> 248 and 182 -> 180
   int stat_n = -1;
   auto flush_stats = [&](int n) {
 #pragma unroll
@@ -161,8 +162,7 @@ __global__ __launch_bounds__((HaloCfg<VB, NT>::NTHR)) void conv_halo_kernel(cons
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = wsum[j][e], b = wsq[j][e];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        sum16(a, b);
         if (r16 == 0) {
           const int c = j * 16 + 4 * q4 + e;
           sStats[(wave * 2 + 0) * BN + c] = a;
@@ -177,8 +177,7 @@ __global__ __launch_bounds__((HaloCfg<VB, NT>::NTHR)) void conv_halo_kernel(cons
       float a = 0.f;
 #pragma unroll
       for (int w = 0; w < NW; ++w) a += sStats[(w * 2 + which) * BN + c];
-      const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + blockIdx.x;
-      P.stats[(slot_t * 2 + which) * P.stats_ld + col0 + c] = a;
+      P.stats[stats_slot(P, n, blockIdx.x, which) + col0 + c] = a;
     }
     __syncthreads();
   };

@@ -220,6 +220,8 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
   for (int j = 0; j < NT; ++j)
 #pragma unroll
     for (int e = 0; e < 4; ++e) { wsum[j][e] = 0.f; wsq[j][e] = 0.f; }
+  // Own staging and wave totals: the templated flush took the 128 -> 32 statistics variant from 36 to 112 bytes of scratch per lane;
+  // own sample-change stanza: with SampleRun the F16 256 -> 64 statistics variant spilled 12 bytes
   int stat_n = -1;
   auto flush_stats = [&](int n) {                    // called by every thread (contains barriers)
 #pragma unroll
@@ -227,8 +229,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = wsum[j][e], b = wsq[j][e];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        sum16(a, b);
         if (r16 == 0) {
           const int c = j * 16 + 4 * q4 + e;
           sStats[(wave * 2 + 0) * CN + c] = a;
@@ -243,8 +244,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
       float a = 0.f;
 #pragma unroll
       for (int w = 0; w < 8; ++w) a += sStats[(w * 2 + which) * CN + c];
-      const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + blockIdx.x;
-      P.stats[(slot_t * 2 + which) * P.stats_ld + c] = a;
+      P.stats[stats_slot(P, n, blockIdx.x, which) + c] = a;
     }
     __syncthreads();
   };
@@ -314,8 +314,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           float a = q1[jp][h][e], b = q2[jp][h][e];
-#pragma unroll
-          for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+          sum16(a, b);
           if (r16 == 0) {
             sStats[(wave * 3 + 0) * CN + jp * 32 + ychunk * 8 + 2 * h + e] = a;
             sStats[(wave * 3 + 1) * CN + jp * 32 + ychunk * 8 + 2 * h + e] = b;
@@ -324,8 +323,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
         }
     {
       float c = q3;
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+      sum16(c);
       if (r16 == 0) sStats[(wave * 3 + 2) * CN + ychunk * 8] = c;      // the slope term: only its total over the channels matters
       q3 = 0.f;
     }
@@ -337,7 +335,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
 #pragma unroll
         for (int w = 0; w < 8; ++w) a += sStats[(w * 3 + which) * CN + c];
       }
-      P.bst.part[(((int64_t)n * P.bst.P + blockIdx.x) * 3 + which) * P.bst.ld + c] = a;
+      P.bst.part[bst_slot(P.bst, n, blockIdx.x, which) + c] = a;
     }
     __syncthreads();
   };

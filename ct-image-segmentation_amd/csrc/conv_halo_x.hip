@@ -282,6 +282,8 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
   for (int j = 0; j < NT; ++j)
 #pragma unroll
     for (int e = 0; e < 4; ++e) { wsum[j][e] = 0.f; wsq[j][e] = 0.f; }
+  // Own staging and wave totals: the templated flush moved 15 instantiations (BST 64-byte voxels 169 -> 177 VGPRs, 296 + 40 -> 298 + 42
+  // AGPRs); own sample-change stanza: SampleRun moved 6 (207 -> 203, 292 -> 291)
   int stat_n = -1;
   auto flush_stats = [&](int n) {
 #pragma unroll
@@ -289,8 +291,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = wsum[j][e], b = wsq[j][e];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        sum16(a, b);
         if (r16 == 0) {
           sStats[(wave * 2 + 0) * 16 * NT + j * 16 + 4 * q4 + e] = a;
           sStats[(wave * 2 + 1) * 16 * NT + j * 16 + 4 * q4 + e] = b;
@@ -304,8 +305,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
       float a = 0.f;
 #pragma unroll
       for (int w = 0; w < 4; ++w) a += sStats[((grp * 4 + w) * 2 + which) * 16 * NT + cc];
-      const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + blockIdx.x;
-      P.stats[(slot_t * 2 + which) * P.stats_ld + blockIdx.y * (16 * NTA) + c] = a;
+      P.stats[stats_slot(P, n, blockIdx.x, which) + blockIdx.y * (16 * NTA) + c] = a;
     }
     __syncthreads();
   };
@@ -347,8 +347,8 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = b1[j][e], b = b2[j][e], c = e == 0 ? b3[j] : 0.f;
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); if (e == 0) c += __shfl_xor(c, o, 64); }
+        sum16(a, b);
+        if (e == 0) sum16(c);
         if (r16 == 0) {
           sStats[(wave * 3 + 0) * 16 * NT + j * 16 + 4 * q4 + e] = a;
           sStats[(wave * 3 + 1) * 16 * NT + j * 16 + 4 * q4 + e] = b;
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
 #pragma unroll
       for (int w = 0; w < 4; ++w) a += sStats[((grp * 4 + w) * 3 + which) * 16 * NT + cc];
       const int ch = blockIdx.y * (16 * NTA) + c - P.bst.col0;
-      if (ch >= 0 && ch < P.bst.C) P.bst.part[(((int64_t)n * P.bst.P + blockIdx.x) * 3 + which) * P.bst.ld + ch] = a;
+      if (ch >= 0 && ch < P.bst.C) P.bst.part[bst_slot(P.bst, n, blockIdx.x, which) + ch] = a;
     }
     __syncthreads();
   };

@@ -116,15 +116,15 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(const ConvKArgs P, i
   for (int j = 0; j < NT; ++j)
 #pragma unroll
     for (int e = 0; e < 2; ++e) { wsum2[j][e] = f32x2{0.f, 0.f}; wsq2[j][e] = f32x2{0.f, 0.f}; }
-  int stat_n = -1;
+  // Own staging and wave totals: the templated flush changed every instantiation's VGPR count (104 -> 96 ... 204 -> 196)
+  SampleRun stat_run;
   auto flush_stats = [&](int n) {
 #pragma unroll
     for (int j = 0; j < NT; ++j)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = wsum2[j][e >> 1][e & 1], b = wsq2[j][e >> 1][e & 1];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        sum16(a, b);
         if (r16 == 0) {
           sStats[(wave * 2 + 0) * BN + j * 16 + 4 * q4 + e] = a;
           sStats[(wave * 2 + 1) * BN + j * 16 + 4 * q4 + e] = b;
@@ -137,8 +137,7 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(const ConvKArgs P, i
       const int which = tid / BN, c = tid % BN;
       const float a = sStats[(0 * 2 + which) * BN + c] + sStats[(1 * 2 + which) * BN + c] + sStats[(2 * 2 + which) * BN + c] +
                       sStats[(3 * 2 + which) * BN + c];
-      const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + blockIdx.x;
-      P.stats[(slot_t * 2 + which) * P.stats_ld + c] = a;
+      P.stats[stats_slot(P, n, blockIdx.x, which) + c] = a;
     }
     __syncthreads();
   };
@@ -162,10 +161,7 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(const ConvKArgs P, i
       stg.load(in_base(n, x0, y0, z0), x0, y0, z0, P.Xi, P.Yi, P.Zi, rg);
     }
     origin(t, n, x0, y0, z0);
-    if (STATS && n != stat_n) {
-      if (stat_n >= 0) flush_stats(stat_n);
-      stat_n = n;
-    }
+    if (STATS) stat_run.enter(n, flush_stats);
     const char* h = smem + cur * S_INB + S_SHIFT;
     const int64_t vb = (((int64_t)n * P.Xo + x0) * P.Yo + y0) * P.Zo + z0;
     const bool xok = x0 + wave < P.Xr, zok = z0 + pz < P.Zr;
@@ -228,7 +224,7 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(const ConvKArgs P, i
     __syncthreads();
     cur ^= 1;
   }
-  if (STATS && stat_n >= 0) flush_stats(stat_n);
+  if (STATS) stat_run.finish(flush_stats);
 }
 
 bool conv_stem_eligible(const ConvKArgs& a, int dtype, int nclass) {

@@ -198,6 +198,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
   for (int j = 0; j < 2; ++j)
 #pragma unroll
     for (int e = 0; e < 4; ++e) { wsum[j][e] = 0.f; wsq[j][e] = 0.f; }
+  // Own staging, wave totals and sample-change stanza: the templated flush and SampleRun each took the statistics variants 241 -> 243 VGPRs
   int stat_n = -1;
   auto flush_stats = [&](int n) {                    // called by every thread (contains barriers)
 #pragma unroll
@@ -205,8 +206,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float a = wsum[j][e], b = wsq[j][e];
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+        sum16(a, b);
         if (r16 == 0) {
           const int c = (ch * 2 + j) * 16 + 4 * q4 + e;
           sStats[(wave * 2 + 0) * U8_CN + c] = a;
@@ -221,8 +221,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
       float a = 0.f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) a += sStats[((2 * k + half) * 2 + which) * U8_CN + c];      // the four waves of the column half
-      const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + blockIdx.x;
-      P.stats[(slot_t * 2 + which) * P.stats_ld + c] = a;
+      P.stats[stats_slot(P, n, blockIdx.x, which) + c] = a;
     }
     __syncthreads();
   };

@@ -130,17 +130,15 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
   for (int e = 0; e < 4; ++e) bias[e] = (P.bias != nullptr && 4 * q4 + e < P.Cn) ? P.bias[4 * q4 + e] : 0.f;
   const int ch = 4 * q4;
 
-  // InstanceNorm partial sums stay in registers across the workgroup's tiles and are written once per (workgroup, sample):
-  // one partial slot per workgroup instead of one per tile (12 288 tiles per sample at 256x256x24 -> 256 slots: no per-tile
-  // shuffles / barrier, and the finalize that sits between this pass and its norm pass reads 48x fewer rows)
+  // InstanceNorm partial sums, one slot per (workgroup, sample), see conv_common.h: 12 288 tiles per sample at 256x256x24 -> 256 slots
   float wsum[4] = {0.f, 0.f, 0.f, 0.f}, wsq[4] = {0.f, 0.f, 0.f, 0.f};
-  int stat_n = -1;
+  // Own staging and wave totals: the templated flush took this kernel 199 -> 205 VGPRs and from 0 to 16 bytes of scratch per lane
+  SampleRun stat_run;
   auto flush_stats = [&](int n) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float a = wsum[e], b = wsq[e];
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+      sum16(a, b);
       if (r16 == 0) {
         sStats[(wave8 * 2 + 0) * 16 + 4 * q4 + e] = a;
         sStats[(wave8 * 2 + 1) * 16 + 4 * q4 + e] = b;
@@ -154,8 +152,7 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
       float a = 0.f;
 #pragma unroll
       for (int w = 0; w < 8; ++w) a += sStats[(w * 2 + which) * 16 + c];
-      const int64_t slot_t = (int64_t)n * P.stats_tiles + P.stats_tile0 + blockIdx.x;
-      P.stats[(slot_t * 2 + which) * P.stats_ld + c] = a;
+      P.stats[stats_slot(P, n, blockIdx.x, which) + c] = a;
     }
     __syncthreads();
   };
@@ -163,10 +160,7 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
   auto compute_tile = [&](int t) {
     int n, x0, y0, z0;
     tile_origin(t, n, x0, y0, z0);
-    if (P.stats != nullptr && n != stat_n) {
-      if (stat_n >= 0) flush_stats(stat_n);
-      stat_n = n;
-    }
+    if (P.stats != nullptr) stat_run.enter(n, flush_stats);
     const int64_t vb = (((int64_t)n * P.Xo + 2 * x0) * P.Yo + 2 * y0) * P.Zo + 2 * z0;
     const bool xok = x0 + wave < P.Xr, zok = z0 + pz < P.Zr;
     bool rv[4];
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
     if (tn < last) sstore();
     __syncthreads();
   }
-  if (P.stats != nullptr && stat_n >= 0) flush_stats(stat_n);
+  if (P.stats != nullptr) stat_run.finish(flush_stats);
 }
 
 bool conv_up_eligible(const ConvKArgs& a, int dtype, int nclass) {

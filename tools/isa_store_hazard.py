@@ -255,8 +255,8 @@ def scan_library_untracked_lds_reads(lib_path=DEFAULT_LIB):
 
 
 def kernel_resources(lib_path=DEFAULT_LIB):
-    """{demangled-ish kernel symbol: {"scratch": bytes per lane, "vgpr": n, "spills": n, "lds": bytes}} from the code objects'
-    AMDGPU metadata notes — DESIGN.md section 3.2f: a 112 B/lane spill was invisible in the kernel's own timing and cost +0.9 GB of
+    """{demangled-ish kernel symbol: {"scratch": bytes per lane, "vgpr": n, "agpr": n, "sgpr": n, "spills": n, "lds": bytes}} from
+    the code objects' AMDGPU metadata notes — DESIGN.md section 3.2f: a 112 B/lane spill was invisible in the kernel's own timing and cost +0.9 GB of
     HBM traffic per launch, so ScratchSize is part of the check list"""
     out = {}
     for bi, obj in code_objects(lib_path):
@@ -266,7 +266,9 @@ def kernel_resources(lib_path=DEFAULT_LIB):
             notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", f.name], text=True)
         for blk in notes.split("- .agpr_count")[1:]:
             g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
+            assert g("name") not in out, "two kernels named " + g("name")
             out[g("name")] = {"scratch": int(g("private_segment_fixed_size")), "vgpr": int(g("vgpr_count")),
+                              "agpr": int(blk.split("\n")[0].split(":")[1]), "sgpr": int(g("sgpr_count")),
                               "spills": int(g("vgpr_spill_count")), "lds": int(g("group_segment_fixed_size"))}
     return out
 
