@@ -121,6 +121,7 @@ _SIGS = {
     "ctseg_wgrad_narrow_ok": (C.c_int, [C.POINTER(WgradDesc)]),
     "ctseg_conv_in_norm_ok": (C.c_int, [C.POINTER(ConvDesc)]),
     "ctseg_conv_bwd_stats_slots": (C.c_int, [C.POINTER(ConvDesc)]),
+    "ctseg_conv_pass_name": (C.c_char_p, [C.POINTER(ConvDesc)]),
     "ctseg_wgrad_in_norm_ok": (C.c_int, [C.POINTER(WgradDesc)]),
     "ctseg_wgrad_dy_norm_ok": (C.c_int, [C.POINTER(WgradDesc)]),
     "ctseg_conv_igemm": (C.c_int, [C.POINTER(ConvDesc), _vp]),

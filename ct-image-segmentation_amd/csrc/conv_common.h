@@ -424,6 +424,7 @@ void launch_conv_up8(ConvKArgs& a, hipStream_t st);
 // GENERIC (conv_igemm.hip), or its 192 x 256 bf16 tile with a five-deep ring of 32-wide K stages (conv_igemm_ring.hip, a.tiles
 // already set for 192 rows)
 bool conv_ring_eligible(const ConvKArgs& a, int dtype, int nclass);
+int conv_ring_cols(const ConvKArgs& a);       // columns of its 192-row tile: 128 or 256
 void launch_conv_ring(const ConvKArgs& a, int nclass, hipStream_t st);
 
 }  // namespace ctseg

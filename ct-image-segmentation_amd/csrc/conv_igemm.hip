@@ -307,6 +307,16 @@ static int tile_rows_for(const ConvKArgs& a, int dtype, int nclass) {
   return a.Cn <= 32 ? 256 : 128;
 }
 
+// The tile of the generic family's pass: rows x columns of one workgroup, and whether the ring-pipelined kernel runs it.  The one
+// place that decides it: launch_generic dispatches on it, the partial-slot sizing and ctseg_conv_pass_name report it.
+struct GenericTile { int bm, bn; bool ring; };
+static GenericTile generic_tile(const ConvKArgs& a, int dtype, int nclass) {
+  const int bm = tile_rows_for(a, dtype, nclass);
+  if (bm != 192) return {bm, ctseg_conv_tile_cols(a.Cn), false};
+  const bool ring = conv_ring_eligible(a, dtype, nclass);
+  return {192, ring ? conv_ring_cols(a) : 256, ring};
+}
+
 // The one place that orders the forward passes: the first eligible family runs (GENERIC covers the 192-row ring kernel too).
 // CTSEG_NO_DOWN_R (test / A/B switch, read per call: tests flip it inside one process) skips DOWN_R; CTSEG_NO_HALO_X lives in
 // conv_halo_x_eligible, which the fused cross-entropy pass asks as well.
@@ -339,8 +349,8 @@ static StatsLayout stats_layout(ConvPass p, const ConvKArgs& a, int dtype, int n
     case ConvPass::UP8: return {conv_up8_slots(a), a.Cn};
     case ConvPass::GENERIC: break;
   }
-  const int bm = tile_rows_for(a, dtype, nclass), bn = bm == 192 ? (a.Cn > 128 ? 256 : 128) : tc;
-  return {((a.rows + bm - 1) / bm) * nclass, ((a.Cn + bn - 1) / bn) * bn};
+  const GenericTile t = generic_tile(a, dtype, nclass);
+  return {((a.rows + t.bm - 1) / t.bm) * nclass, ((a.Cn + t.bn - 1) / t.bn) * t.bn};
 }
 
 // partial rows per sample the pass fills for ConvKArgs::bst; 0: it cannot
@@ -358,7 +368,7 @@ static int bst_slots(ConvPass p, const ConvKArgs& a, int dtype, int nclass) {
   if (small_operand(a, dtype) || a.out2 != nullptr || a.o_ld % 8 != 0 || a.Cn_store % 8 != 0 || a.bst.col0 % 8 != 0 || a.bst.y_ld % 8 != 0 ||
       ((uintptr_t)a.bst.y % 16) != 0 || a.bst.col0 + a.bst.C > a.Cn_store)
     return 0;
-  const int bm = tile_rows_for(a, dtype, nclass);
+  const int bm = generic_tile(a, dtype, nclass).bm;
   // (not the 128 x 64 / 256 x 32 / 256 x 16 tiles: the sums cost them a workgroup per CU — 108 -> 180 registers — which is what the
   // reduce pass they would remove costs: 0.121 vs 0.092 + 0.024 ms on the 8-class 256 -> 64 pass)
   if (bm != 192 && a.Cn <= 64) return 0;
@@ -366,9 +376,9 @@ static int bst_slots(ConvPass p, const ConvKArgs& a, int dtype, int nclass) {
 }
 
 template <typename T> static int launch_generic(ConvKArgs& a, int nclass, hipStream_t st) {
-  const int bm = tile_rows_for(a, TT<T>::DT, nclass);
+  const GenericTile t = generic_tile(a, TT<T>::DT, nclass);
   const bool smallc = small_operand(a, TT<T>::DT);
-  a.tiles = (a.rows + bm - 1) / bm;
+  a.tiles = (a.rows + t.bm - 1) / t.bm;
   // XCD-contiguous tile ranges: measured neutral for single-class passes (their halo re-reads already hit L2 / Infinity Cache),
   // 7-9 % on the 8-class passes (384->64 and 256->64), where every class re-gathers the same input tile
   a.xcd_order = nclass > 1 ? 1 : 0;
@@ -378,14 +388,14 @@ template <typename T> static int launch_generic(ConvKArgs& a, int nclass, hipStr
     for (int i = 1; i < nclass; ++i)
       for (int j = i; j > 0 && a.cls[j].ntaps > a.cls[j - 1].ntaps; --j) std::swap(a.cls[j], a.cls[j - 1]);
   if constexpr (TT<T>::SZ == 2) {
-    if (bm == 192) {
-      if (conv_ring_eligible(a, TT<T>::DT, nclass)) { launch_conv_ring(a, nclass, st); return 0; }
+    if (t.bm == 192) {
+      if (t.ring) { launch_conv_ring(a, nclass, st); return 0; }
       return launch_cfg<T, 192, 256, 2, 4>(a, false, nclass, st);
     }
   }
-  if (a.Cn <= 16) return launch_cfg<T, 256, 16, 4, 1>(a, smallc, nclass, st);
-  if (a.Cn <= 32) return launch_cfg<T, 256, 32, 4, 1>(a, smallc, nclass, st);
-  if (a.Cn <= 64) return launch_cfg<T, 128, 64, 2, 2>(a, smallc, nclass, st);
+  if (t.bn == 16) return launch_cfg<T, 256, 16, 4, 1>(a, smallc, nclass, st);
+  if (t.bn == 32) return launch_cfg<T, 256, 32, 4, 1>(a, smallc, nclass, st);
+  if (t.bn == 64) return launch_cfg<T, 128, 64, 2, 2>(a, smallc, nclass, st);
   return launch_cfg<T, 128, 128, 2, 2>(a, smallc, nclass, st);
 }
 
@@ -535,6 +545,25 @@ extern "C" int ctseg_conv_narrow_ok(const ctseg_conv_desc* d) {
     return (d->g_ld == 12 && wide_out && wide_add && p == ConvPass::DOWN_HALO) ? 1 : 0;
   }
   return p == ConvPass::UP ? 1 : 0;
+}
+
+// The kernel family a launch of this descriptor runs (PASS_NAME of select_conv_pass; the generic family with its tile, as
+// launch_generic picks it), for tests that must know a shape still lands on the kernel they were written for.  NULL: rejected.
+extern "C" const char* ctseg_conv_pass_name(const ctseg_conv_desc* d) {
+  if (!query_ok(d) || (d->dtype != CTSEG_F32 && !is16(d->dtype))) return nullptr;
+  if (d->N <= 0 || d->Cg <= 0 || d->Cn <= 0 || d->Xr <= 0 || d->Yr <= 0 || d->Zr <= 0) return nullptr;
+  ConvKArgs a = conv_args(d);
+  const ConvPass p = select_conv_pass(a, d->dtype, d->nclass);
+  if (p != ConvPass::GENERIC) return PASS_NAME[(int)p];
+  // every tile launch_generic and launch_conv_ring can pick (generic_tile); a tile outside the table has no name: rejected
+  static const struct { int bm, bn; bool ring; const char* name; } NAMES[] = {
+      {256, 16, false, "generic 256x16"},  {256, 32, false, "generic 256x32"},      {128, 64, false, "generic 128x64"},
+      {128, 128, false, "generic 128x128"}, {192, 256, false, "generic 192x256"},    {192, 128, true, "generic ring 192x128"},
+      {192, 256, true, "generic ring 192x256"}};
+  const GenericTile t = generic_tile(a, d->dtype, d->nclass);
+  for (const auto& e : NAMES)
+    if (e.bm == t.bm && e.bn == t.bn && e.ring == t.ring) return e.name;
+  return nullptr;
 }
 
 // tiles per sample (all classes) a pass with this geometry writes InstanceNorm partials for

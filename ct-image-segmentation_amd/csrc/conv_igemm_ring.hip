@@ -226,9 +226,11 @@ bool conv_ring_eligible(const ConvKArgs& a, int dtype, int nclass) {
   return true;
 }
 
+int conv_ring_cols(const ConvKArgs& a) { return a.Cn > 128 ? 256 : 128; }
+
 void launch_conv_ring(const ConvKArgs& a, int nclass, hipStream_t st) {
   const int gx = a.xcd_order ? 8 * ((a.tiles * a.N + 7) / 8) : a.tiles * a.N;
-  if (a.Cn > 128) {
+  if (conv_ring_cols(a) == 256) {
     dim3 grid((unsigned)gx, (unsigned)((a.Cn + 255) / 256), (unsigned)nclass);
     if (a.dtype == CTSEG_F16) hipLaunchKernelGGL((conv_igemm_ring_kernel<F16, 256>), grid, dim3(512), 0, st, a);
     else if (a.bst.part != nullptr) hipLaunchKernelGGL((conv_igemm_ring_kernel<BF16, 256, true>), grid, dim3(512), 0, st, a);

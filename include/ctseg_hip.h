@@ -132,6 +132,13 @@ int ctseg_conv_in_norm_ok(const ctseg_conv_desc* d);
  * fields (run ctseg_instnorm_prelu_bwd_reduce instead).  bst_y_ld, bst_C, bst_col0 must be set; pointers other than in / out /
  * out2 / add (which select the kernel) are ignored. */
 int ctseg_conv_bwd_stats_slots(const ctseg_conv_desc* d);
+/* Name of the kernel family the launch of this descriptor would run, in the order the library tries them: "x-column halo", "halo",
+ * "up", "stem", "streamed-weight halo", "stride-2 halo", "stride-2 register-weight", "many-channel 8-class", or "generic" followed
+ * by its tile ("generic 256x16", "generic 256x32", "generic 128x64", "generic 128x128", "generic 192x256", "generic ring 192x128",
+ * "generic ring 192x256").  Host-only like the sizing queries above (pointers select the kernel by their alignment and by being set,
+ * nothing is dereferenced); a static string, NULL for a descriptor the queries reject.  For tests and tools: a shape that an
+ * eligibility change moved to another kernel is seen by name instead of silently testing something else. */
+const char* ctseg_conv_pass_name(const ctseg_conv_desc* d);
 int ctseg_conv_igemm(const ctseg_conv_desc* d, void* stream);
 
 /* Weight gradient: R[tap*Cg+a][b] = sum_rows in[row*sin+d(tap)][a] * dy[row][b]; row K=ntaps*Cg of R is

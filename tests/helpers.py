@@ -79,6 +79,53 @@ def run_conv_module(mod, x, gy, dt, device):
     return from_cl(y, dims == 2), gx, gw, gb
 
 
+class ConvPassDriver:
+    """One GemmLayer in a MiniPlan, driven one pass at a time with the extras of ctseg_conv_desc (statistics, addend, fp32 / split
+    output, backward statistics, a pending norm on the operand).  Every recorded pass is checked against the kernel family the
+    caller names (ctseg_conv_pass_name of the recorded descriptor) BEFORE it runs: a shape that an eligibility change moved to
+    another kernel fails instead of passing on something else."""
+
+    def __init__(self, mod, dt, device, extra_params=(), cg=None):
+        """cg: gathered channel stride of the input when it is not the default (16 for a <= 12-channel input in 12-wide rows)"""
+        self.mod, self.dt, self.device = mod, dt, device
+        transposed = isinstance(mod, (torch.nn.ConvTranspose2d, torch.nn.ConvTranspose3d))
+        self.plan = MiniPlan([mod.weight, mod.bias, *extra_params], device, dt, 3)
+        e = nat.epc(dt)
+        cin = mod.in_channels
+        self.layer = GemmLayer(self.plan, "t", transposed, mod.kernel_size[0], mod.stride[0], cin,
+                               [(mod.weight, mod.bias, mod.out_channels)], cg or (cin if cin % e else rup(cin, e)),
+                               need_dgrad=(cin % e == 0))
+        self.plan.packer.finalize()
+        self.desc = None
+
+    def act(self, x, ld=None):
+        cin = x.shape[1]
+        return to_cl(x, self.dt, self.device, ld=ld if ld is not None else (cin if cin == 1 else None))
+
+    def _go(self, family):
+        self.desc = self.plan.prog[-1][2][0]
+        name = nat.lib().ctseg_conv_pass_name(self.desc)
+        assert name is not None and name.decode() == family, (name, family)
+        self.plan.run()
+        torch.cuda.synchronize()
+
+    def fwd(self, family, xa, **extras):
+        """-> (output Act or SplitAct, NormStats or None); extras: want_stats, add, out_f32, split_at, out"""
+        out, stats = self.layer.emit_fwd(xa, **extras)
+        self._go(family)
+        return out, stats
+
+    def set_input_dims(self, dims):
+        self.layer.x_dims = tuple(dims)
+
+    def dgrad(self, family, ga, **extras):
+        """-> the written gradient (Act or SplitAct); extras: add, bst, bst_col0, split_at, out.  Needs the input dims of a forward
+        (a forward pass recorded before, or set_input_dims)"""
+        out = self.layer.emit_dgrad(ga, **extras)
+        self._go(family)
+        return out
+
+
 def rel_err(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-12))

@@ -136,3 +136,93 @@ def test_weight_gradient_sizing_query_and_the_split_model():
     # the generic rule is untouched (fp32 storage: 2048 workgroups aimed for, slabs in multiples of 8)
     stub32 = types.SimpleNamespace(plan=types.SimpleNamespace(dt=nat.F32))
     assert GemmLayer._wgrad_splits(stub32, desc(64, 64, (128, 128, 12), dt=nat.F32), 2, 128 * 128 * 12, False) == 72
+
+
+def _conv_desc(dt, cg, cn, rows, kind="plain", g_ld=None):
+    """a hand-filled forward descriptor (no memory behind the pointers: the host queries look at their alignment only).
+    kind: "plain" 3x3x3 stride 1, "down" 3x3x3 stride 2, "up" the 8 parity classes of a stride-2 transposed convolution"""
+    from capstone_amd.engine import classes_plain, classes_up
+    e, bk = nat.epc(dt), 128 // nat.elsize(dt)
+    d = nat.ConvDesc()
+    d.in_, d.w, d.out, d.dtype = 4096, 1 << 20, 1 << 24, dt
+    d.N = 2
+    d.Xr, d.Yr, d.Zr = rows
+    sin, sout = (2, 1) if kind == "down" else (1, 2) if kind == "up" else (1, 1)
+    d.Xi, d.Yi, d.Zi = [r * sin for r in rows]
+    d.Xo, d.Yo, d.Zo = [r * sout for r in rows]
+    d.sin, d.sout = sin, sout
+    d.Cg, d.Cn, d.Cn_store = cg, cn, -(-cn // e) * e
+    d.g_ld, d.o_ld = g_ld or cg, d.Cn_store
+    classes = classes_up(3, 3) if kind == "up" else classes_plain(3, 3, lambda t: t - 1)
+    d.nclass = len(classes)
+    rows_pad, off = -(-cn // 128) * 128, 0
+    for i, ((ox, oy, oz), taps) in enumerate(classes):
+        c = d.cls[i]
+        c.ntaps, c.kpad, c.w_off = len(taps), -(-len(taps) * cg // bk) * bk, off
+        c.ox, c.oy, c.oz = ox, oy, oz
+        for j, (_, o) in enumerate(taps):
+            c.taps[j] = o
+        off += rows_pad * c.kpad
+    return d
+
+
+PASS_NAME_CASES = [
+    # one descriptor per kernel family, in the order the library tries them ...
+    ("x-column halo", nat.BF16, 16, 16, (9, 11, 13), "plain", None),
+    ("halo", nat.F32, 16, 16, (9, 11, 13), "plain", None),
+    ("up", nat.BF16, 64, 10, (7, 9, 5), "up", None),
+    ("stem", nat.BF16, 1, 32, (5, 6, 10), "down", None),
+    ("streamed-weight halo", nat.BF16, 64, 64, (9, 20, 13), "plain", None),
+    ("streamed-weight halo", nat.BF16, 128, 32, (9, 20, 12), "up", None),
+    ("stride-2 halo", nat.BF16, 16, 64, (18, 10, 12), "down", None),
+    ("stride-2 register-weight", nat.BF16, 32, 128, (9, 20, 12), "down", None),
+    ("many-channel 8-class", nat.BF16, 256, 64, (9, 20, 12), "up", None),
+    # ... and one per tile of the generic family
+    ("generic 256x16", nat.BF16, 40, 12, (7, 9, 11), "plain", None),
+    ("generic 256x32", nat.BF16, 40, 24, (7, 9, 11), "plain", None),
+    ("generic 128x64", nat.BF16, 40, 48, (7, 9, 11), "plain", None),
+    ("generic 128x128", nat.BF16, 40, 96, (7, 9, 11), "plain", None),
+    ("generic 192x256", nat.BF16, 40, 160, (7, 9, 11), "plain", None),
+    ("generic ring 192x128", nat.BF16, 128, 128, (7, 9, 11), "plain", None),
+    ("generic ring 192x256", nat.BF16, 256, 256, (5, 6, 7), "plain", None),
+    # what moves a shape off its family: storage, size, row layout
+    ("generic 256x32", nat.F32, 32, 32, (5, 9, 13), "plain", None),             # fp32 voxels of 128 bytes: not the halo kernel
+    ("generic 128x64", nat.BF16, 256, 64, (5, 9, 6), "up", None),               # < 2048 rows: not the many-channel 8-class kernel
+    ("generic 256x32", nat.BF16, 128, 32, (6, 10, 7), "up", None),              # < 2048 rows: not the streamed-weight halo kernel
+    ("x-column halo", nat.BF16, 16, 10, (7, 11, 13), "plain", 12),              # 12-wide gathered rows
+    ("generic 128x64", nat.F32, 24, 48, (7, 9, 11), "plain", None),
+]
+
+
+@pytest.mark.parametrize("name,dt,cg,cn,rows,kind,g_ld", PASS_NAME_CASES, ids=[f"{c[0]} {c[2]}->{c[3]} {c[5]}" + (" fp32" if c[1] == nat.F32 else "") for c in PASS_NAME_CASES])
+def test_conv_pass_name_per_family_and_generic_tile(name, dt, cg, cn, rows, kind, g_ld):
+    L = nat.lib()
+    d = _conv_desc(dt, cg, cn, rows, kind, g_ld)
+    got = L.ctseg_conv_pass_name(ctypes.byref(d))
+    assert got is not None and got.decode() == name
+
+
+def test_conv_pass_name_follows_the_extras_and_rejects_bad_descriptors(monkeypatch):
+    L = nat.lib()
+    d = _conv_desc(nat.BF16, 32, 128, (9, 20, 12), "down")
+    assert L.ctseg_conv_pass_name(ctypes.byref(d)) == b"stride-2 register-weight"
+    d.add, d.add_ld = 1 << 26, 128               # that kernel takes no addend: the launch (and the name) move on
+    assert L.ctseg_conv_pass_name(ctypes.byref(d)) == b"generic 128x128"
+    d.add = None
+    monkeypatch.setenv("CTSEG_NO_DOWN_R", "1")   # the selector's own switch is honoured: the name is what WOULD run
+    assert L.ctseg_conv_pass_name(ctypes.byref(d)) == b"generic 128x128"
+    monkeypatch.delenv("CTSEG_NO_DOWN_R")
+    x = _conv_desc(nat.BF16, 16, 10, (7, 11, 13), "plain")
+    x.out_f32, x.Cn_store, x.o_ld = 1, 12, 12
+    assert L.ctseg_conv_pass_name(ctypes.byref(x)) == b"x-column halo"
+    assert L.ctseg_conv_pass_name(ctypes.byref(nat.ConvDesc())) is None          # empty dims
+    assert L.ctseg_conv_pass_name(None) is None
+    bad = _conv_desc(nat.BF16, 16, 16, (9, 11, 13))
+    bad.struct_size -= 8
+    assert L.ctseg_conv_pass_name(ctypes.byref(bad)) is None
+    bad = _conv_desc(nat.BF16, 16, 16, (9, 11, 13))
+    bad.nclass = 9
+    assert L.ctseg_conv_pass_name(ctypes.byref(bad)) is None
+    bad = _conv_desc(nat.BF16, 16, 16, (9, 11, 13))
+    bad.dtype = nat.U8
+    assert L.ctseg_conv_pass_name(ctypes.byref(bad)) is None

@@ -1,0 +1,673 @@
+"""GPU: the epilogue "extras" of ctseg_conv_igemm, per kernel family, at op level against a float64 reference.
+
+Every case names the family it is written for; helpers.ConvPassDriver asserts ctseg_conv_pass_name of the recorded descriptor
+before it launches, so a later eligibility change cannot move a shape to another kernel unnoticed.
+
+Reference: operands rounded to the storage type (x, weight, addend, y of the backward statistics), convolution in float64 on the
+CPU.  What the statistics are taken of, read from each family's epilogue:
+  * forward (sum, sumsq) partials: the fp32 result (accumulator + bias) BEFORE it is rounded to the storage type, in every family
+    (x-column halo, halo, up, stem, streamed-weight halo, stride-2 halo, stride-2 register-weight, many-channel 8-class, generic
+    and ring) -> the reference sums the unrounded float64 result;
+  * backward statistics (bst_*): the STORED gradient (after the addend, rounded to bf16), in every family that takes them -> the
+    reference sums are formed from the gradient read back from the device.
+
+Tolerances.  Outputs: rel_err < 2e-5 (fp32 storage) / 2.5e-2 (16-bit).  Sums: per case, the error of a plain float32 evaluation
+(float32 torch convolution of the same rounded operands, float32 sums) against float64 is measured on the CPU, normalised by
+sum|y| (sums) or sum y^2 (sums of squares), worst (sample, channel); the kernel is allowed 16x that (its lanes add chains of up to
+256 rows where torch adds pairwise).  The bound must stay below 1 / (4 * voxels per sample) — asserted — so one dropped or doubled
+row fails.  (mean, rstd): the same bounds carried through mean = S/n, var = Q/n - mean^2, rstd = (var + eps)^-1/2, plus fp32
+rounding of the stored pair.
+
+Measured on an MI355X, worst over the uncapped run and CTSEG_MAX_WG = 1, 3 (every test prints its figures before it asserts):
+  forward partials, normalised error of the sum / of the sum of squares (bound of the case in brackets)
+    x-column halo             3.5e-08 (4.5e-07) / 1.7e-07 (1.8e-06);  bias 4: 1.5e-07 (2.1e-06) / 1.4e-07 (1.8e-06)
+    halo (fp32)               4.5e-08 (6.3e-07) / 1.8e-07 (2.8e-06)
+    up                        2.9e-08 (4.4e-07) / 1.5e-07 (1.6e-06)
+    stem                      7.9e-08 (9.5e-07) / 1.4e-07 (2.6e-06)
+    streamed-weight halo      3.5e-08 (2.8e-07) / 1.7e-07 (1.8e-06)      (one class / eight classes)
+    stride-2 halo             3.0e-08 (4.8e-07) / 1.3e-07 (2.5e-06)
+    stride-2 register-weight  3.3e-08 (4.5e-07) / 1.9e-07 (2.6e-06)
+    many-channel 8-class      2.5e-08 (3.0e-07) / 1.0e-07 (1.7e-06)
+    generic, all tiles, ring  5.5e-08 (1.0e-06) / 1.5e-07 (2.5e-06);  bias 4: 4.4e-08 (2.1e-06) / 6.3e-08 (2.7e-06)
+    (mean, rstd) after ctseg_instnorm_finalize: at most 0.13 / 0.06 of their propagated tolerance
+  backward statistics, error as a fraction of the case's bound (sum dxhat, sum dxhat * xhat, slope term)
+    x-column halo 0.06 0.05 0.16;  streamed-weight halo 0.08 0.09 0.16;  stride-2 register-weight 0.11 0.11 0.11;  ring 0.04 0.08 0.06
+    stride-2 halo (12-wide dY) 0.10 0.06 0.08;  generic 128x128 0.04 0.03 0.04;  generic 192x256 0.05 0.04 0.04
+  column sums of dy from the InstanceNorm apply pass, error / sum |dy| (bound): 2.6e-08 (1.6e-07 .. 5.2e-07) with the norm's own mean
+    (the sum is zero by construction), 3.8e-08 (2.9e-07 .. 6.8e-07) with the mean moved (column sums 6e-04 .. 2e-03 of sum |dy|)
+  outputs: 16-bit storage 2.3e-03 .. 4.4e-03, fp32 storage and fp32 output 2.0e-07 .. 4.5e-07
+
+Not covered, with the reason the library gives:
+  * statistics together with an addend / fp32 output on the x-column halo pass: the launch refuses ("InstanceNorm partials with an
+    addend / fp32 output / input-gradient taps are not implemented on the x-column halo pass"), asserted below;
+  * an addend on the stem and on the stride-2 register-weight pass: conv_stem_eligible / conv_down_r_eligible turn the pass down, the
+    selector runs the generic kernel instead (the 32 -> 128 case with an addend is tested there, by name);
+  * backward statistics on "halo", "up", "stem", "many-channel 8-class" and the 256x16 / 256x32 / 128x64 generic tiles:
+    ctseg_conv_bwd_stats_slots is 0 by design (bst_slots in conv_igemm.hip).  Every other family and tile is a case below; the
+    stride-2 halo pass takes them only for 12-wide gathered rows with the norm on columns 32..63 of 64, which is its case;
+  * an input gradient with an addend on the stride-2 register-weight pass: conv_down_r_eligible turns a pass with an addend down,
+    as for the forward; on the stem: the layer has no input gradient; on the many-channel 8-class pass:
+    test_many_channel_8_class_kernel_statistics_and_addend has it; on the stride-2 halo pass: not a case here;
+  * a norm narrower than the pass at bst_col0 == 0: GemmLayer._try_bst only asks when the column range equals the norm.
+"""
+import ctypes
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+from capstone_amd import _native as nat  # noqa: E402
+from capstone_amd._native import BF16, F32  # noqa: E402
+from capstone_amd.engine import Act, GemmLayer, SplitAct, rup  # noqa: E402
+from capstone_amd.plan import _NormAct  # noqa: E402
+from helpers import ConvPassDriver, MiniPlan, from_cl, rel_err, to_cl  # noqa: E402
+
+DEV = "cuda:0"
+TOL = {F32: 2e-5, BF16: 2.5e-2}
+EPS = 1e-5
+
+HALO_X, HALO, UP, STEM, HALO_SW = "x-column halo", "halo", "up", "stem", "streamed-weight halo"
+DOWN_HALO, DOWN_R, UP8 = "stride-2 halo", "stride-2 register-weight", "many-channel 8-class"
+
+# ---- the layer under test and its float64 / float32 references ---------------------------------------------------------------
+def _module(kind, cin, cout, k=3):
+    if kind == "convT":
+        return torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1)
+    return torch.nn.Conv3d(cin, cout, k, 2 if kind == "conv_s2" else 1, (k - 1) // 2)
+
+
+def _conv(kind, k, x, w, b):
+    if kind == "convT":
+        return F.conv_transpose3d(x, w, b, stride=2, padding=1, output_padding=1)
+    return F.conv3d(x, w, b, stride=2 if kind == "conv_s2" else 1, padding=(k - 1) // 2)
+
+
+def _dgrad(kind, k, gy, w, x_shape):
+    """input gradient of the same layer: the transposed operator, no bias"""
+    if kind == "convT":
+        return F.conv3d(gy, w, None, stride=2, padding=1)
+    s = 2 if kind == "conv_s2" else 1
+    p = (k - 1) // 2
+    op = tuple(x_shape[2 + i] - ((gy.shape[2 + i] - 1) * s - 2 * p + k) for i in range(3))
+    return F.conv_transpose3d(gy, w, None, stride=s, padding=p, output_padding=op)
+
+
+def _rounded(t, dt):
+    return t.detach().to(nat.torch_dtype(dt)).float()
+
+
+class _Layer:
+    """a seeded layer with the CPU copies of its rounded operands (the driver moves the module's parameters to the device)"""
+
+    def __init__(self, kind, cin, cout, shape, dt, k=3, bias_shift=0.0):
+        self.key = (kind, cin, cout, shape, dt, k, bias_shift)
+        torch.manual_seed(7 * cin + cout + shape[2])
+        self.kind, self.k, self.dt, self.cin, self.cout, self.shape = kind, k, dt, cin, cout, shape
+        self.mod = _module(kind, cin, cout, k)
+        with torch.no_grad():
+            self.mod.bias.add_(bias_shift)
+        self.x = _rounded(torch.randn(shape[0], cin, *shape[1:]), dt)
+        self.w, self.b = _rounded(self.mod.weight, dt), self.mod.bias.detach().clone()      # (the bias stays fp32 on the device)
+
+    def y(self):
+        """(float64 result, float32 result) of the forward convolution: computed once per configuration (the layer is seeded, so
+        every test of one configuration builds the same operands) and never written to"""
+        if self.key not in _FWD_REF:
+            with torch.no_grad():
+                _FWD_REF[self.key] = (_conv(self.kind, self.k, self.x.double(), self.w.double(), self.b.double()),
+                                      _conv(self.kind, self.k, self.x, self.w, self.b))
+        return _FWD_REF[self.key]
+
+    def driver(self, extra_params=(), cg=None):
+        return ConvPassDriver(self.mod, self.dt, DEV, extra_params=extra_params, cg=cg)
+
+
+_FWD_REF = {}      # configuration -> CPU reference results only; modules, parameters and plans are made afresh by every test
+
+
+def _desc_probe(drv, xa, **extras):
+    """the descriptor a forward pass with these extras records, without running it"""
+    drv.layer.emit_fwd(xa, **extras)
+    return drv.plan.prog.pop()[2][0]
+
+
+def _bst_partials(gx):
+    """the raw backward-statistics partial buffer the pass that wrote ``gx`` filled (GemmLayer._try_bst leaves it on the written
+    activation): (N, P, 3, ld) on the CPU"""
+    mark = gx.bst
+    if mark[0] == "slice":
+        mark = mark[3]
+    return mark[1].cpu()
+
+
+def _cap(monkeypatch, max_wg):
+    if max_wg is None:
+        monkeypatch.delenv("CTSEG_MAX_WG", raising=False)
+    else:
+        monkeypatch.setenv("CTSEG_MAX_WG", max_wg)
+
+
+CAPS = [None, "1", "3"]
+CAP_IDS = ["uncapped", "max_wg1", "max_wg3"]
+
+
+# ---- sums against float64 with the measured float32 bound --------------------------------------------------------------------
+def _sum_bounds(v64, v32, voxels):
+    """v64 / v32: (N, C, voxels...) float64 / float32 evaluations of the summed quantity.  Returns the float64 sums and the bound
+    (16 x the worst normalised float32 error) for the plain sum and the sum of squares, after checking the bound against the cap."""
+    dims = tuple(range(2, v64.ndim))
+    s64, q64, a64 = v64.sum(dims), (v64 * v64).sum(dims), v64.abs().sum(dims)
+    s32, q32 = v32.sum(dims).double(), (v32 * v32).sum(dims).double()
+    bs = 16.0 * float(((s32 - s64).abs() / a64).max())
+    bq = 16.0 * float(((q32 - q64).abs() / q64).max())
+    cap = 1.0 / (4.0 * voxels)
+    assert 0.0 < bs < cap and 0.0 < bq < cap, ("float32 reference error x 16 is not under 1 / (4 * voxels): shrink the shape", bs, bq, cap)
+    return s64, q64, a64, bs, bq
+
+
+def _check_forward_stats(tag, lay, drv, out, stats):
+    y64, y32 = lay.y()
+    N, Cn = y64.shape[:2]
+    voxels = y64[0, 0].numel()
+    s64, q64, a64, bs, bq = _sum_bounds(y64, y32, voxels)
+    part = stats.partials.cpu()
+    tot = part.double().sum(1)
+    es = float(((tot[:, 0, :Cn] - s64).abs() / a64).max())
+    eq = float(((tot[:, 1, :Cn] - q64).abs() / q64).max())
+    print(f"{tag}: sum err {es:.3e} (bound {bs:.3e}), sumsq err {eq:.3e} (bound {bq:.3e}), cap {1 / (4 * voxels):.3e}")
+    assert rel_err(from_cl(out), y64) < TOL[lay.dt], "forward output"
+    assert es <= bs, ("sum partials", es, bs)
+    assert eq <= bq, ("sum-of-squares partials", eq, bq)
+    assert stats.ld == part.shape[-1] and (stats.ld == Cn or float(part[..., Cn:].abs().max()) == 0.0), "columns [Cn, stats_ld) stay zero"
+    # finalize: (mean, rstd) with the bounds above carried through
+    mr = stats.emit_finalize(0, Cn, EPS)
+    drv.plan.run()
+    torch.cuda.synchronize()
+    mr = mr.cpu().double()
+    mean64, ey2, eabs = s64 / voxels, q64 / voxels, a64 / voxels
+    var64 = ey2 - mean64 * mean64
+    rstd64 = (var64 + EPS).rsqrt()
+    f32 = 2.0 ** -23
+    tol_mean = bs * eabs + f32 * mean64.abs()
+    tol_var = bq * ey2 + 2.0 * mean64.abs() * bs * eabs + (bs * eabs) ** 2
+    tol_rstd = rstd64 * (0.5 * tol_var / (var64 + EPS) + 4 * f32)
+    em, er = (mr[..., 0] - mean64).abs(), (mr[..., 1] - rstd64).abs()
+    print(f"{tag}: mean err / tol {float((em / tol_mean).max()):.3f}, rstd err / tol {float((er / tol_rstd).max()):.3f}, "
+          f"max |mean| / std {float((mean64.abs() * rstd64).max()):.2f}")
+    assert bool((em <= tol_mean).all()), "mean"
+    assert bool((er <= tol_rstd).all()), "rstd"
+
+
+# (id, family, kind, cin, cout, k, (N, X, Y, Z), storage, bias shift): two samples, ragged tiles on every tiled axis
+STATS_CASES = [
+    ("halo_x 16->16", HALO_X, "conv", 16, 16, 3, (2, 9, 11, 13), BF16, 0.0),
+    ("halo_x 32->32", HALO_X, "conv", 32, 32, 3, (2, 5, 9, 13), BF16, 0.0),
+    ("halo_x 16->10", HALO_X, "conv", 16, 10, 3, (2, 7, 11, 13), BF16, 0.0),
+    ("halo_x 16->16 bias 4", HALO_X, "conv", 16, 16, 3, (2, 9, 11, 13), BF16, 4.0),
+    ("halo fp32 16->16", HALO, "conv", 16, 16, 3, (2, 9, 11, 13), F32, 0.0),
+    ("halo fp32 16->10", HALO, "conv", 16, 10, 3, (2, 7, 11, 13), F32, 0.0),
+    ("up 64->10", UP, "convT", 64, 10, 3, (2, 7, 9, 5), BF16, 0.0),
+    ("up 32->16", UP, "convT", 32, 16, 3, (2, 7, 9, 5), BF16, 0.0),
+    ("stem 1->32", STEM, "conv_s2", 1, 32, 3, (2, 10, 12, 20), BF16, 0.0),
+    ("stem 1->64", STEM, "conv_s2", 1, 64, 3, (2, 10, 12, 10), BF16, 0.0),
+    ("halo_sw 64->64", HALO_SW, "conv", 64, 64, 3, (2, 9, 20, 13), BF16, 0.0),
+    ("halo_sw 8-class 128->32", HALO_SW, "convT", 128, 32, 3, (2, 9, 20, 12), BF16, 0.0),
+    ("down_halo 16->64", DOWN_HALO, "conv_s2", 16, 64, 3, (2, 36, 20, 24), BF16, 0.0),
+    ("down_r 32->128", DOWN_R, "conv_s2", 32, 128, 3, (2, 18, 40, 24), BF16, 0.0),
+    ("up8 256->64", UP8, "convT", 256, 64, 3, (2, 9, 20, 12), BF16, 0.0),
+    ("generic 256x16 40->12", "generic 256x16", "conv", 40, 12, 3, (2, 7, 9, 11), BF16, 0.0),
+    ("generic 256x32 40->24", "generic 256x32", "conv", 40, 24, 3, (2, 7, 9, 11), BF16, 0.0),
+    ("generic 128x64 40->48", "generic 128x64", "conv", 40, 48, 3, (2, 7, 9, 11), BF16, 0.0),
+    ("generic 128x64 40->48 bias 4", "generic 128x64", "conv", 40, 48, 3, (2, 7, 9, 11), BF16, 4.0),
+    ("generic 128x128 40->96", "generic 128x128", "conv", 40, 96, 3, (2, 7, 9, 11), BF16, 0.0),
+    ("generic 192x256 40->160", "generic 192x256", "conv", 40, 160, 3, (2, 7, 9, 11), BF16, 0.0),
+    ("generic ring 128->128", "generic ring 192x128", "conv", 128, 128, 3, (2, 7, 9, 11), BF16, 0.0),
+    ("generic fp32 128x64 24->48", "generic 128x64", "conv", 24, 48, 3, (2, 7, 9, 11), F32, 0.0),
+]
+
+
+@pytest.mark.parametrize("max_wg", CAPS, ids=CAP_IDS)
+@pytest.mark.parametrize("tag,family,kind,cin,cout,k,shape,dt,shift", STATS_CASES, ids=[c[0] for c in STATS_CASES])
+def test_forward_statistics(monkeypatch, max_wg, tag, family, kind, cin, cout, k, shape, dt, shift):
+    _cap(monkeypatch, max_wg)
+    lay = _Layer(kind, cin, cout, shape, dt, k=k, bias_shift=shift)
+    drv = lay.driver()
+    out, stats = drv.fwd(family, drv.act(lay.x), want_stats=True)
+    _check_forward_stats(f"{tag} [{max_wg}]", lay, drv, out, stats)
+
+
+# ---- addend -----------------------------------------------------------------------------------------------------------------
+# (id, family the pass lands on WITH this addend, kind, cin, cout, k, shape, storage, addend kind)
+ADD_CASES = [
+    ("halo_x 32->32 + bf16", HALO_X, "conv", 32, 32, 3, (2, 5, 9, 13), BF16, "st"),
+    ("halo_x 32->32 + x", HALO_X, "conv", 32, 32, 3, (2, 5, 9, 13), BF16, "x"),
+    ("halo_x 16->16 + bf16", HALO_X, "conv", 16, 16, 3, (2, 9, 11, 13), BF16, "st"),
+    ("halo_x 16->16 + x", HALO_X, "conv", 16, 16, 3, (2, 9, 11, 13), BF16, "x"),
+    ("halo_x 16->10 + fp32", HALO_X, "conv", 16, 10, 3, (2, 7, 11, 13), BF16, "f32"),
+    ("halo fp32 16->16 + fp32", HALO, "conv", 16, 16, 3, (2, 9, 11, 13), F32, "st"),
+    ("halo fp32 16->16 + x", HALO, "conv", 16, 16, 3, (2, 9, 11, 13), F32, "x"),
+    ("halo_sw 64->64 + bf16", HALO_SW, "conv", 64, 64, 3, (2, 9, 20, 13), BF16, "st"),
+    ("halo_sw 64->64 + x", HALO_SW, "conv", 64, 64, 3, (2, 9, 20, 13), BF16, "x"),
+    ("halo_sw 64->64 + fp32", HALO_SW, "conv", 64, 64, 3, (2, 9, 20, 13), BF16, "f32"),
+    ("up 64->10 + bf16", UP, "convT", 64, 10, 3, (2, 7, 9, 5), BF16, "st"),
+    ("up 64->10 + fp32", UP, "convT", 64, 10, 3, (2, 7, 9, 5), BF16, "f32"),
+    ("generic 256x16 + bf16", "generic 256x16", "conv", 40, 12, 3, (2, 7, 9, 11), BF16, "st"),
+    ("generic 256x32 + fp32", "generic 256x32", "conv", 40, 24, 3, (2, 7, 9, 11), BF16, "f32"),
+    ("generic 128x64 + x", "generic 128x64", "conv", 48, 48, 3, (2, 7, 9, 11), BF16, "x"),
+    ("generic 128x128 + bf16", "generic 128x128", "conv", 40, 96, 3, (2, 7, 9, 11), BF16, "st"),
+    ("generic 192x256 + bf16", "generic 192x256", "conv", 40, 160, 3, (2, 7, 9, 11), BF16, "st"),
+    ("generic ring + x", "generic ring 192x128", "conv", 128, 128, 3, (2, 7, 9, 11), BF16, "x"),
+    # the stride-2 register-weight kernel takes no addend (conv_down_r_eligible): the selector hands the 32 -> 128 layer with one to
+    # the generic kernel, whose 128 x 128 tile adds it
+    ("down_r shape + bf16 -> generic", "generic 128x128", "conv_s2", 32, 128, 3, (2, 18, 40, 24), BF16, "st"),
+]
+
+
+def _addend(kind, lay, drv, xa, shape_nc):
+    """(device addend Act, its CPU value as stored)"""
+    if kind == "x":
+        return xa, lay.x
+    torch.manual_seed(99)
+    a = torch.randn(*shape_nc)
+    if kind == "f32" and lay.dt != F32:
+        aa = to_cl(a, F32, DEV, ld=rup(shape_nc[1], 8))
+        return aa, a
+    return to_cl(a, lay.dt, DEV), _rounded(a, lay.dt)
+
+
+@pytest.mark.parametrize("tag,family,kind,cin,cout,k,shape,dt,addk", ADD_CASES, ids=[c[0] for c in ADD_CASES])
+def test_forward_addend(tag, family, kind, cin, cout, k, shape, dt, addk):
+    lay = _Layer(kind, cin, cout, shape, dt, k=k)
+    y64, _ = lay.y()
+    drv = lay.driver()
+    xa = drv.act(lay.x)
+    aa, acpu = _addend(addk, lay, drv, xa, tuple(y64.shape))
+    out, _ = drv.fwd(family, xa, add=aa)
+    err = rel_err(from_cl(out), y64 + acpu.double())
+    print(f"{tag}: rel err {err:.3e}")
+    assert err < TOL[dt]
+    assert (drv.desc.add_f32 == 1) == (addk == "f32" and dt != F32)
+
+
+# (id, family of the input-gradient pass, kind, cin, cout, shape of x, storage): the pass writes cin columns and gathers cout
+DGRAD_ADD_CASES = [
+    ("halo_x dgrad 16->16", HALO_X, "conv", 16, 16, (2, 9, 11, 13), BF16),
+    ("halo fp32 dgrad 16->16", HALO, "conv", 16, 16, (2, 9, 11, 13), F32),
+    ("halo_sw dgrad 64->64", HALO_SW, "conv", 64, 64, (2, 9, 20, 13), BF16),
+    ("halo_sw 8-class dgrad of 32->128 s2", HALO_SW, "conv_s2", 32, 128, (2, 18, 40, 24), BF16),
+    ("up dgrad of 16->64 s2", UP, "conv_s2", 16, 64, (2, 8, 10, 12), BF16),
+    ("ring dgrad 128->128", "generic ring 192x128", "conv", 128, 128, (2, 7, 9, 11), BF16),
+    ("generic 256x16 dgrad 16->40", "generic 256x16", "conv", 16, 40, (2, 7, 9, 11), BF16),
+    ("generic 256x32 dgrad 24->40", "generic 256x32", "conv", 24, 40, (2, 7, 9, 11), BF16),
+    ("generic 128x64 dgrad 40->96", "generic 128x64", "conv", 40, 96, (2, 7, 9, 11), BF16),
+    ("generic 128x128 dgrad 96->40", "generic 128x128", "conv", 96, 40, (2, 7, 9, 11), BF16),
+    ("generic 192x256 dgrad 160->40", "generic 192x256", "conv", 160, 40, (2, 7, 9, 11), BF16),
+    ("generic fp32 128x64 dgrad 48->24", "generic 128x64", "conv", 48, 24, (2, 7, 9, 11), F32),
+]
+
+
+@pytest.mark.parametrize("tag,family,kind,cin,cout,shape,dt", DGRAD_ADD_CASES, ids=[c[0] for c in DGRAD_ADD_CASES])
+def test_input_gradient_addend(tag, family, kind, cin, cout, shape, dt):
+    lay = _Layer(kind, cin, cout, shape, dt)
+    torch.manual_seed(17)
+    drv = lay.driver()
+    od = drv.layer.out_dims((shape[0],) + tuple(shape[1:]))
+    gy = _rounded(torch.randn(od[0], cout, *od[1:]), dt)
+    add = _rounded(torch.randn(*lay.x.shape), dt)
+    with torch.no_grad():
+        ref = _dgrad(kind, 3, gy.double(), lay.w.double(), lay.x.shape) + add.double()
+    drv.set_input_dims((shape[0],) + tuple(shape[1:]))
+    gx = drv.dgrad(family, to_cl(gy, dt, DEV), add=to_cl(add, dt, DEV))
+    err = rel_err(from_cl(gx), ref)
+    print(f"{tag}: rel err {err:.3e}")
+    assert err < TOL[dt]
+
+
+def test_halo_x_refuses_statistics_with_an_addend():
+    lay = _Layer("conv", 16, 16, (2, 9, 11, 13), BF16)
+    drv = lay.driver()
+    xa = drv.act(lay.x)
+    with pytest.raises(nat.NativeError, match="InstanceNorm partials with an addend"):
+        drv.fwd(HALO_X, xa, want_stats=True, add=xa)
+    drv.plan.prog = []
+
+
+# ---- fp32 output -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag,family,cin,cout,shape,ld", [
+    ("logits 10(16)->10, 12-wide rows", HALO_X, 10, 10, (2, 7, 11, 13), 12),
+    ("logits 16->10", HALO_X, 16, 10, (2, 7, 11, 13), None),
+    ("generic 256x16 40->12", "generic 256x16", 40, 12, (2, 7, 9, 11), None),
+])
+def test_fp32_output_under_bf16_storage(tag, family, cin, cout, shape, ld):
+    lay = _Layer("conv", cin, cout, shape, BF16)
+    y64, _ = lay.y()
+    drv = lay.driver(cg=16 if ld == 12 else None)
+    xa = drv.act(lay.x, ld=ld)
+    if ld == 12:
+        assert nat.query("ctseg_conv_narrow_ok", _desc_probe(drv, xa, out_f32=True)) == 1
+    out, _ = drv.fwd(family, xa, out_f32=True)
+    assert out.t.dtype == torch.float32 and drv.desc.out_f32 == 1 and drv.desc.g_ld == (ld or cin)
+    err = rel_err(from_cl(out), y64)
+    print(f"{tag}: rel err {err:.3e}")
+    assert err < TOL[F32]
+
+
+# ---- split output ------------------------------------------------------------------------------------------------------------
+SPLIT_CASES = [
+    ("stem 1->32 at 16", STEM, 1, 32, (2, 10, 12, 20), 16),
+    ("down_halo 16->64 at 32", DOWN_HALO, 16, 64, (2, 36, 20, 24), 32),
+    ("down_r 32->128 at 64", DOWN_R, 32, 128, (2, 18, 40, 24), 64),
+]
+
+
+@pytest.mark.parametrize("tag,family,cin,cout,shape,at", SPLIT_CASES, ids=[c[0] for c in SPLIT_CASES])
+def test_split_output(tag, family, cin, cout, shape, at):
+    lay = _Layer("conv_s2", cin, cout, shape, BF16)
+    y64, _ = lay.y()
+    drv = lay.driver()
+    xa = drv.act(lay.x)
+    whole, st_w = drv.fwd(family, xa, want_stats=True)
+    split, st_s = drv.fwd(family, xa, want_stats=True, split_at=at)
+    assert isinstance(split, SplitAct) and drv.desc.out2 and drv.desc.out2_col0 == at
+    w = from_cl(whole)
+    a, b = from_cl(split.a), from_cl(split.b)
+    assert torch.equal(a, w[:, :at]) and torch.equal(b, w[:, at:]), "halves are the column slices of the unsplit run"
+    assert rel_err(a, y64[:, :at]) < TOL[BF16] and rel_err(b, y64[:, at:]) < TOL[BF16]
+    assert torch.equal(st_w.partials, st_s.partials), "statistics partials of the split run"
+    assert float(st_w.partials.abs().max()) > 0
+
+
+def test_split_output_is_refused_where_the_family_cannot():
+    lay = _Layer("conv", 16, 16, (2, 9, 11, 13), BF16)
+    drv = lay.driver()
+    xa = drv.act(lay.x)
+    out, _ = drv.fwd(HALO_X, xa, split_at=8)
+    assert isinstance(out, Act), "no split on the x-column halo pass"
+    d = drv.desc
+    d.out2_col0 = 8
+    assert nat.lib().ctseg_conv_split_ok(ctypes.byref(d)) == 0
+    other = torch.zeros_like(out.t)
+    d.out2, d.o2_ld = other.data_ptr(), other.shape[-1]
+    assert nat.lib().ctseg_conv_igemm(ctypes.byref(d), nat.stream_ptr()) < 0
+    assert b"out2 (split output) is not supported for this pass" in nat.lib().ctseg_last_error()
+    torch.cuda.synchronize()
+
+
+# ---- backward statistics -----------------------------------------------------------------------------------------------------
+def _norm_for(drv, alpha, N, C, dims, seed):
+    """a _NormAct with a real forward output y (storage-rounded, no element within 1e-3 of its mean in units of the standard
+    deviation: the sign of xhat decides a PReLU branch, and float32 and float64 must agree on it) and its real (mean, rstd)"""
+    torch.manual_seed(seed)
+    y = _rounded(torch.randn(N, C, *dims) * 1.3 + 0.4, BF16)
+    mean = y.double().mean((2, 3, 4), keepdim=True)
+    rstd = (y.double().var((2, 3, 4), unbiased=False, keepdim=True) + EPS).rsqrt()
+    mr32 = torch.stack([mean.float().reshape(N, C), rstd.float().reshape(N, C)], -1).contiguous()
+    m32, r32 = mr32[..., 0].double().reshape(N, C, 1, 1, 1), mr32[..., 1].double().reshape(N, C, 1, 1, 1)
+    for _ in range(3):
+        near = ((y.double() - m32) * r32).abs() < 1e-3
+        y = _rounded(torch.where(near, y + 0.25, y), BF16)
+    assert float(((y.double() - m32) * r32).abs().min()) >= 1e-3
+    na = _NormAct(drv.plan, alpha)
+    na.y = to_cl(y, BF16, DEV)
+    na.mr = mr32.to(DEV)
+    return na, y, m32, r32
+
+
+def _bst_reference(g, y, m, r, alpha, f32):
+    """the three sums of the header's formula, float64 (f32=False) or plain float32 torch"""
+    if f32:
+        g, y, m, r = g.float(), y.float(), m.float(), r.float()
+    else:
+        g, y = g.double(), y.double()
+    xh = (y - m) * r
+    dxh = g * torch.where(xh > 0, torch.ones_like(xh), torch.full_like(xh, alpha))
+    return dxh, dxh * xh, g * xh.clamp(max=0)
+
+
+# (id, family of the input-gradient pass, kind, cin, cout, shape of x, norm channels, bst_col0, with addend, row width of dY)
+BST_CASES = [
+    ("halo_x dgrad 16->16", HALO_X, "conv", 16, 16, (2, 9, 11, 13), 16, 0, False, None),
+    ("halo_x dgrad 32->32 + addend", HALO_X, "conv", 32, 32, (2, 5, 9, 13), 32, 0, True, None),
+    ("halo_sw 1-class dgrad 64->64", HALO_SW, "conv", 64, 64, (2, 9, 20, 13), 64, 0, False, None),
+    ("halo_sw 8-class dgrad of 32->128 s2", HALO_SW, "conv_s2", 32, 128, (2, 18, 40, 24), 32, 0, False, None),
+    # the head's transposed 64 -> 10 layer: dY in 12-wide rows (16 gathered), 64 written columns, the norm on columns 32..63
+    ("down_halo dgrad of 64->10 convT, 12-wide dY, norm on columns 32..63", DOWN_HALO, "convT", 64, 10, (2, 18, 10, 13), 32, 32,
+     False, 12),
+    ("down_r dgrad of 128->32 convT", DOWN_R, "convT", 128, 32, (2, 9, 20, 12), 128, 0, False, None),
+    ("down_r, norm on columns 64..127", DOWN_R, "convT", 128, 32, (2, 9, 20, 12), 64, 64, False, None),
+    ("generic 128x128 dgrad 96->40", "generic 128x128", "conv", 96, 40, (2, 7, 9, 11), 96, 0, False, None),
+    ("generic 192x256 dgrad 160->40, norm on columns 96..159 + addend", "generic 192x256", "conv", 160, 40, (2, 7, 9, 11), 64, 96,
+     True, None),
+    ("ring 192x128 dgrad 128->128", "generic ring 192x128", "conv", 128, 128, (2, 7, 9, 11), 128, 0, False, None),
+    ("ring 192x128, norm on columns 64..127 + addend", "generic ring 192x128", "conv", 128, 128, (2, 7, 9, 11), 64, 64, True, None),
+]
+
+
+@pytest.mark.parametrize("max_wg", CAPS, ids=CAP_IDS)
+@pytest.mark.parametrize("tag,family,kind,cin,cout,shape,C,col0,with_add,gy_ld", BST_CASES, ids=[c[0] for c in BST_CASES])
+def test_backward_statistics(monkeypatch, max_wg, tag, family, kind, cin, cout, shape, C, col0, with_add, gy_ld):
+    _cap(monkeypatch, max_wg)
+    lay = _Layer(kind, cin, cout, shape, BF16)
+    alpha = torch.nn.Parameter(torch.tensor([0.2]))
+    drv = lay.driver(extra_params=[alpha])
+    N, dims = shape[0], tuple(shape[1:])
+    na, y, m, r = _norm_for(drv, alpha, N, C, dims, seed=cin + C + col0)
+    od = drv.layer.out_dims((N,) + dims)
+    torch.manual_seed(23)
+    gy = _rounded(torch.randn(od[0], cout, *od[1:]), BF16)
+    drv.set_input_dims((N,) + dims)
+    add = _rounded(torch.randn(*lay.x.shape), BF16) if with_add else None
+    extras = {"add": to_cl(add, BF16, DEV)} if with_add else {}
+    gx = drv.dgrad(family, to_cl(gy, BF16, DEV, ld=gy_ld), bst=na, bst_col0=col0, **extras)
+    assert drv.desc.g_ld == (gy_ld or cout)
+    assert drv.desc.bst_partials and drv.desc.bst_C == C and drv.desc.bst_col0 == col0, "the pass took the backward statistics"
+    P, ld = drv.desc.bst_P, drv.desc.bst_ld
+    assert P == nat.lib().ctseg_conv_bwd_stats_slots(ctypes.byref(drv.desc)) > 0
+    part = _bst_partials(gx)
+    assert tuple(part.shape) == (N, P, 3, ld)
+    # the gradient itself: asking for the statistics selects kernel instantiations of their own
+    with torch.no_grad():
+        ref = _dgrad(kind, 3, gy.double(), lay.w.double(), lay.x.shape)
+    err = rel_err(from_cl(gx), ref + add.double() if with_add else ref)
+    assert err < TOL[BF16], ("input gradient of the pass that takes the statistics", err)
+    g = from_cl(gx)[:, col0:col0 + C]                     # the STORED gradient
+    voxels = g[0, 0].numel()
+    t64, t32 = _bst_reference(g, y, m, r, 0.2, False), _bst_reference(g, y, m, r, 0.2, True)
+    dims3 = (2, 3, 4)
+    tot = part.double().sum(1)                            # (N, 3, ld)
+    figs = []
+    for i in (0, 1):
+        s64, a64 = t64[i].sum(dims3), t64[i].abs().sum(dims3)
+        b = 16.0 * float(((t32[i].sum(dims3).double() - s64).abs() / a64).max())
+        assert 0 < b < 1.0 / (4 * voxels), (i, b, "float32 reference error x 16 is not under the cap")
+        e = float(((tot[:, i, :C] - s64).abs() / a64).max())
+        figs.append((e, b))
+    # the slope term: one parameter, and a lane of the conv kernels keeps ONE accumulator for it over all its channels
+    # (conv_common.h), so which column of the third row a voxel's term lands in is not defined: the finalize pass adds the row's
+    # columns [0, C), and that total is what is compared.  Nothing may land beyond them.
+    assert ld == C or float(part[..., C:].abs().max()) == 0.0, "columns [C, bst_ld) stay zero"
+    s64, a64 = t64[2].sum((1, 2, 3, 4)), t64[2].abs().sum((1, 2, 3, 4))
+    b = 16.0 * float(((t32[2].sum(dims3).sum(1).double() - s64).abs() / a64).max())
+    assert 0 < b < 1.0 / (4 * voxels)
+    figs.append((float(((tot[:, 2, :C].sum(-1) - s64).abs() / a64).max()), b))
+    # the stand-alone reduce pass over the same stored gradient: summation order only
+    P2 = 8
+    part2 = torch.zeros((N, P2, 3, ld), dtype=torch.float32, device=DEV)
+    gs = gx.slice(col0, C) if (col0 or C != gx.C) else gx
+    nat.call("ctseg_instnorm_prelu_bwd_reduce", BF16, gs.ptr(), gs.ld, na.y.ptr(), na.y.ld, na.mr.data_ptr(),
+             drv.plan.store.p_ptr(alpha), part2.data_ptr(), P2, ld, N, voxels, C)
+    torch.cuda.synchronize()
+    tot2 = part2.cpu().double().sum(1)
+    r01 = [float(((tot[:, i, :C] - tot2[:, i, :C]).abs() / t64[i].abs().sum(dims3)).max()) for i in (0, 1)]
+    r2 = float(((tot[:, 2, :C].sum(-1) - tot2[:, 2, :C].sum(-1)).abs() / a64).max())
+    print(f"{tag} [{max_wg}]: (err, bound) dxhat {figs[0][0]:.3e} {figs[0][1]:.3e}; dxhat*xhat {figs[1][0]:.3e} {figs[1][1]:.3e}; "
+          f"slope {figs[2][0]:.3e} {figs[2][1]:.3e}; vs reduce pass {r01[0]:.3e} {r01[1]:.3e} {r2:.3e}; P = {P}")
+    for (e, b), what in zip(figs, ("sum dxhat", "sum dxhat * xhat", "sum g * min(xhat, 0)")):
+        assert e <= b, (what, e, b)
+    for e, (_, b), what in zip(r01 + [r2], figs, ("sum dxhat", "sum dxhat * xhat", "slope")):
+        assert e <= 2 * b, ("against ctseg_instnorm_prelu_bwd_reduce", what, e, b)
+
+
+# ---- operand normalisation on load -------------------------------------------------------------------------------------------
+def test_norm_on_load_equals_the_materialised_activation():
+    """x-column halo pass over 12-wide rows, 10 (16 gathered) -> 10 channels, two samples: the pending InstanceNorm + PReLU applied on
+    load gives bit for bit the output of the pass over the activation ctseg_instnorm_prelu_fwd wrote"""
+    N, C, dims = 2, 10, (7, 11, 13)
+    lay = _Layer("conv", C, 10, (N,) + dims, BF16)
+    alpha = torch.nn.Parameter(torch.tensor([0.2]))
+    drv = lay.driver(extra_params=[alpha], cg=16)
+    drv.plan.narrow_rows = True
+    na, y, m, r = _norm_for(drv, alpha, N, C, dims, seed=3)
+    ya = to_cl(y, BF16, DEV, ld=12)
+    na.y = ya
+    xm = na._apply(ya, None, None)                          # the materialised activation (12-wide rows as well)
+    assert xm.ld == 12
+    plain, _ = drv.fwd(HALO_X, xm)
+    assert not drv.desc.in_mean_rstd
+    ya.pending_norm = na
+    fused, _ = drv.fwd(HALO_X, ya)
+    assert drv.desc.in_mean_rstd and drv.desc.in_norm_C == C and drv.desc.in_ == ya.ptr(), "the pass normalised on load"
+    assert torch.equal(fused.t, plain.t)
+    xh = (y.double() - m) * r
+    act = torch.where(xh > 0, xh, 0.2 * xh)
+    with torch.no_grad():
+        ref = _conv("conv", 3, act, lay.w.double(), lay.b.double())
+    err = rel_err(from_cl(fused), ref)
+    print(f"norm on load: rel err {err:.3e}")
+    assert err < TOL[BF16]
+
+
+# ---- InstanceNorm + PReLU op sweep -------------------------------------------------------------------------------------------
+_SENTINEL = -12345.0
+
+
+def _instnorm_prelu_dy(g, y, mr, alpha):
+    """dL/dy of InstanceNorm + PReLU from the header's formula, in the precision of the arguments; mr: (N, C, 2) mean, rstd"""
+    N, C = y.shape[:2]
+    m, r = mr[..., 0].reshape(N, C, 1, 1, 1), mr[..., 1].reshape(N, C, 1, 1, 1)
+    xh = (y - m) * r
+    dxh = g * torch.where(xh > 0, torch.ones_like(xh), torch.full_like(xh, alpha))
+    return r * (dxh - dxh.mean((2, 3, 4), keepdim=True) - xh * (dxh * xh).mean((2, 3, 4), keepdim=True)), xh
+
+
+def _check_colsum(tag, colsum, y, g, mr, alpha, C, nonzero=False):
+    """colsum_out of the apply pass against the float64 column sum of dy, error normalised by sum |dy| of the column.  Bound: 16 x
+    the error of the plain float32 evaluation of the same formula, which must stay under 1 / (4 * rows summed)."""
+    dy64, xh = _instnorm_prelu_dy(g.double(), y.double(), mr, alpha)
+    dy32, _ = _instnorm_prelu_dy(g, y, mr.float(), alpha)
+    assert float(xh.abs().min()) > 1e-5, "an element on the PReLU kink: float32 and float64 may take different branches"
+    dims = (0, 2, 3, 4)
+    s64, a64 = dy64.sum(dims), dy64.abs().sum(dims)
+    rows = dy64[:, 0].numel()
+    bound = 16.0 * float(((dy32.sum(dims).double() - s64).abs() / a64).max())
+    assert 0.0 < bound < 1.0 / (4 * rows), (bound, rows)
+    got = colsum.cpu().double()
+    assert bool((got[:C] != _SENTINEL).all()), "every column sum was written"
+    assert bool((got[C:] == _SENTINEL).all()), "nothing written beyond the C columns"
+    err = float(((got[:C] - s64).abs() / a64).max())
+    size = float((s64.abs() / a64).min())
+    print(f"{tag}: error / sum |dy| = {err:.3e} (bound {bound:.3e}), smallest |column sum| / sum |dy| = {size:.3e}")
+    if nonzero:
+        assert size > 100 * bound, "the moved mean leaves column sums far above the bound"
+    assert err <= bound, ("column sums of dy", err, bound)
+    return dy64
+def _in_op(dt, N, C, residual, shape=(12, 16, 8), variant="g_copy"):
+    """ctseg_instnorm_prelu_fwd and the 3-kernel backward against float64 InstanceNorm3d + PReLU on the storage-rounded input.
+    variant: "g_copy" (the gradient copied out beside dy), "colsum" (column sums of dy from the apply pass), "no_apply"
+    (statistics and slope gradient only: ctseg_instnorm_prelu_dalpha)"""
+    torch.manual_seed(C + 7 * N + shape[0])
+    x = _rounded(torch.randn(N, C, *shape) * 1.5 + 0.3, dt)
+    gy = _rounded(torch.randn(N, C, *shape), dt)
+    res = _rounded(torch.randn(N, C, *shape), dt) if residual else None
+    conv = torch.nn.Conv3d(C, C, 1)          # identity 1x1x1 conv: the statistics come out of the conv epilogue as in the network
+    alpha = torch.nn.Parameter(torch.tensor([0.2]))
+    with torch.no_grad():
+        conv.weight.copy_(torch.eye(C).reshape(C, C, 1, 1, 1))
+        conv.bias.zero_()
+    ref = torch.nn.Sequential(torch.nn.InstanceNorm3d(C, eps=EPS), torch.nn.PReLU()).double()
+    with torch.no_grad():
+        ref[1].weight.fill_(0.2)
+    xr = x.double().requires_grad_(True)
+    yr = ref(xr)
+    if residual:
+        yr = yr + res.double()
+    yr.backward(gy.double())
+    plan = MiniPlan([conv.weight, conv.bias, alpha], DEV, dt, 3)
+    layer = GemmLayer(plan, "id", False, 1, 1, C, [(conv.weight, conv.bias, C)], C)
+    plan.packer.finalize()
+    y, stats = layer.emit_fwd(to_cl(x, dt, DEV), want_stats=True)
+    na = _NormAct(plan, alpha)
+    out = na.emit_fwd(y, stats, 0, to_cl(res, dt, DEV) if residual else None, None)
+    plan.run()
+    tol = TOL[dt]
+    assert rel_err(from_cl(out), yr.detach()) < tol, "forward"
+    ga = to_cl(gy, dt, DEV)
+    da_ref = float(ref[1].weight.grad)
+    da_tol = max(tol, 1e-5) * max(1.0, abs(da_ref))
+    if variant == "no_apply":
+        na.emit_bwd(ga, apply=False)
+        plan.run()
+        torch.cuda.synchronize()
+        da_alone = float(plan.store.grad_view(alpha).cpu())
+        assert abs(da_alone - da_ref) < da_tol, "d alpha (ctseg_instnorm_prelu_dalpha)"
+        plan.store.flat_g.zero_()
+        na.emit_bwd(ga)
+        plan.run()
+        torch.cuda.synchronize()
+        da_applied = float(plan.store.grad_view(alpha).cpu())
+        assert abs(da_alone - da_applied) <= 2.0 ** -22 * abs(da_applied), ("d alpha of the two paths", da_alone, da_applied)
+        return
+    extras = {}
+    if variant == "g_copy":
+        extras["g_copy"] = gcopy = to_cl(torch.zeros_like(gy), dt, DEV)
+    else:
+        colsum = torch.full((rup(C, 4),), _SENTINEL, dtype=torch.float32, device=DEV)     # (the pass overwrites columns [0, C))
+        extras["colsum_out"] = colsum.data_ptr()
+    dy = na.emit_bwd(ga, **extras)
+    plan.run()
+    torch.cuda.synchronize()
+    assert rel_err(from_cl(dy), xr.grad) < max(tol, 3e-5), "dx"
+    assert abs(float(plan.store.grad_view(alpha).cpu()) - da_ref) < da_tol, "d alpha"
+    if variant == "g_copy":
+        assert torch.equal(from_cl(gcopy), from_cl(ga)), "g copy"
+    else:
+        # The apply pass sums the fp32 dy BEFORE it is rounded to the storage type (norm_act.hip).  With the norm's own mean the
+        # column sum of dy is zero by construction (sum dy = -rstd * mean(dxhat * xhat) * sum xhat), so this comparison alone sees
+        # only that the columns were written and hold no more than summation error ...
+        mr = na.mr.cpu().double()
+        _check_colsum(f"colsum C={C} dt={dt}", colsum, x, gy, mr, 0.2, C)
+        # ... and the pass runs again with a mean moved by 0.625 standard deviations: xhat no longer sums to zero, the column sum is
+        # of the order of sum |dy|, and a wrong column, a dropped row or a dropped sample shows.  The kernels are functions of
+        # (g, y, mean, rstd, alpha); the reference is the same formula in float64.
+        na.mr[..., 0] += 0.625 / na.mr[..., 1]
+        colsum.fill_(_SENTINEL)
+        plan.store.flat_g.zero_()
+        dy2 = na.emit_bwd(ga, **extras)
+        plan.run()
+        torch.cuda.synchronize()
+        mr = na.mr.cpu().double()
+        ref_dy = _check_colsum(f"colsum, moved mean C={C} dt={dt}", colsum, x, gy, mr, 0.2, C, nonzero=True)
+        assert rel_err(from_cl(dy2), ref_dy) < max(tol, 3e-5), "dy with the moved mean"
+
+
+@pytest.mark.parametrize("dt", [F32, BF16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("residual", [False, True], ids=["plain", "residual"])
+@pytest.mark.parametrize("N", [1, 2])
+@pytest.mark.parametrize("C", [10, 16, 32, 64, 256])
+def test_instnorm_prelu_op_fwd_bwd(dt, residual, N, C):
+    _in_op(dt, N, C, residual)
+
+
+@pytest.mark.parametrize("max_wg", ["1", "3"])
+@pytest.mark.parametrize("dt,N,C", [(BF16, 2, 32), (F32, 2, 64), (BF16, 1, 256)])
+def test_instnorm_prelu_op_with_capped_grids(monkeypatch, max_wg, dt, N, C):
+    monkeypatch.setenv("CTSEG_MAX_WG", max_wg)
+    _in_op(dt, N, C, True, shape=(16, 12, 24))
+
+
+@pytest.mark.parametrize("variant", ["g_copy", "colsum", "no_apply"])
+@pytest.mark.parametrize("dt,N,C", [(BF16, 2, 10), (F32, 2, 32), (BF16, 1, 64)])
+def test_instnorm_prelu_op_variants_on_an_odd_voxel_count(dt, N, C, variant):
+    _in_op(dt, N, C, variant != "colsum", shape=(7, 9, 5), variant=variant)
