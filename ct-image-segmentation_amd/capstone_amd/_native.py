@@ -153,6 +153,9 @@ _SIGS = {
     "ctseg_batchnorm_prelu_bwd_apply": (C.c_int, [_i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32,
                                                   _i64, _i32, _vp, _i32, _vp, _vp]),
     "ctseg_squash_masks": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "ctseg_squash_masks_present": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ctseg_mixup_images": (C.c_int, [_vp, _vp, _i32, _i64, _f64, _vp, _vp]),
+    "ctseg_seg_loss_pair": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "ctseg_seg_loss": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
     "ctseg_conv_logits_ce_slots": (C.c_int, [C.POINTER(ConvDesc), _i32]),
     "ctseg_conv_logits_ce": (C.c_int, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),

@@ -20,17 +20,17 @@ WEIGHT = dict(zip(["Background", "BrainStem", "Chiasm", "Mandible", "OpticNerve_
 LOSSES = {name: name for name in segloss.LOSS_NAMES}  # registry keys as in models/losses.py:160-167 (minus Boundary)
 
 
-def _engine_for(logits):
+def _engine_for(logits, cls=segloss.SegLossEngine, attr="_ctseg_loss"):
     """SegLossEngine cached on the producing plan (or built ad hoc for a foreign tensor)."""
     B, C = logits.shape[:2]
     S = logits[0, 0].numel()
     plan = getattr(logits, "_ctseg_plan", None)
     holder = plan if plan is not None else logits
-    eng = getattr(holder, "_ctseg_loss", None)
+    eng = getattr(holder, attr, None)
     if eng is None or (eng.B, eng.S, eng.C) != (B, S, C) or eng.device != logits.device:
-        eng = segloss.SegLossEngine(logits.device, B, S, C)
+        eng = cls(logits.device, B, S, C)
         if plan is not None:
-            plan._ctseg_loss = eng
+            setattr(plan, attr, eng)
     return eng, plan
 
 
@@ -75,6 +75,46 @@ class _SegLossFn(torch.autograd.Function):
             eng.grad(ptr, ld, buf.data_ptr(), ldn, nat.F32)
             g = buf[..., :C].permute(0, 2, 1).reshape(ctx.shape)
         return g, None, None, None, None, None
+
+
+class _SegLossPairFn(torch.autograd.Function):
+    """lambda * loss(x, y) + (1 - lambda) * loss(x, y[index]) per requested loss, through ONE node: the two terms share the
+    statistics pass, and backward writes the gradient of their sum once (two _SegLossFn nodes on one prediction would share
+    one engine and one ``dlogits`` buffer: the second overwrites the first's tables and its gradient)."""
+
+    @staticmethod
+    def forward(ctx, logits, eng, plan, names, exclude_missing, indicators, lambda_):
+        ptr, ld, keep = _as_cl(logits)
+        eng.stats_pair(ptr, ld, weighted_too="WeightedCrossEntropy" in names)
+        vals, ctx.w = [], []
+        for s in (0, 1):
+            with eng.side(s):
+                vals.append(eng.loss_values(names, exclude_missing, indicators[s]))
+                ctx.w.append(eng._w)
+        ctx.eng, ctx.plan, ctx.names, ctx.cl, ctx.lambda_ = eng, plan, names, (ptr, ld, keep), lambda_
+        ctx.shape = logits.shape
+        return tuple(lambda_ * vals[0][n] + (1 - lambda_) * vals[1][n] for n in names)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        eng, plan = ctx.eng, ctx.plan
+        ptr, ld, _ = ctx.cl
+        for s, lam in ((0, ctx.lambda_), (1, 1 - ctx.lambda_)):     # lambda enters through the upstream gradients only
+            with eng.side(s):
+                eng._w = ctx.w[s]
+                eng.build_coef({n: (g * lam if g is not None else 0.0) for n, g in zip(ctx.names, gs)})
+        if plan is not None:
+            dl = plan.dlogits
+            eng.grad_pair(ptr, ld, dl.ptr(), dl.ld, plan.dt)
+            plan.dlogits_is_current = True
+            g = torch.zeros((), dtype=torch.float32, device=eng.device).expand(ctx.shape)
+        else:
+            B, C = ctx.shape[:2]
+            ldn = (C + 3) // 4 * 4
+            buf = torch.zeros((B, eng.S, ldn), dtype=torch.float32, device=eng.device)
+            eng.grad_pair(ptr, ld, buf.data_ptr(), ldn, nat.F32)
+            g = buf[..., :C].permute(0, 2, 1).reshape(ctx.shape)
+        return g, None, None, None, None, None, None
 
 
 class _SegLossTableFn(torch.autograd.Function):
@@ -155,6 +195,27 @@ class MultipleLossWrapper(nn.Module):
         if mask_indicator is not None:
             mask_indicator = mask_indicator.type_as(input)
         vals = _SegLossFn.apply(input, eng, plan, tuple(self.names), self.exclude_missing, mask_indicator)
+        return dict(zip(self.names, vals))
+
+    def forward_mixed(self, input, target, index, lambda_, mask_indicator=None):
+        """The mixup step's two calls in one (capstone/training/mixup_trainer.py:63-81): dict name ->
+        ``lambda_ * loss(input, target) + (1 - lambda_) * loss(input, target[index])``, side B under ``mask_indicator[index]``.
+        ``index``: (B,) integer device tensor, ``lambda_``: host float.  Two plain ``forward`` calls on one prediction are NOT
+        equivalent here (they share one engine and one gradient buffer): this is the supported route.
+        ``last_mixed_counts`` = the (B, 2, 3, C) Dice counts of both sides, valid until the next call."""
+        nat.require_gpu(input, "MultipleLossWrapper.forward_mixed")
+        eng, plan = _engine_for(input, segloss.SegLossPairEngine, "_ctseg_loss_pair")
+        stash = getattr(target, "_ctseg_labels", None)
+        if stash is None:
+            eng.set_labels_from_i64(target)
+            stash = (eng.labels, eng.hist)
+        eng.set_pair(stash[0], stash[1], index)
+        indicators = (None, None)
+        if mask_indicator is not None:
+            mask_indicator = mask_indicator.type_as(input)
+            indicators = (mask_indicator, mask_indicator[index.long()])
+        vals = _SegLossPairFn.apply(input, eng, plan, tuple(self.names), self.exclude_missing, indicators, float(lambda_))
+        self.last_mixed_counts = eng.cnt2
         return dict(zip(self.names, vals))
 
 

@@ -6,6 +6,7 @@ per-(sample, class) closed forms are then a handful of ops on (B, 10) device ten
 pass writes d(loss)/d(logits).  CE-only (the reference's 3-D default, base_trainer.py:28) is a single
 fused pass.
 """
+import contextlib
 import math
 
 import torch
@@ -39,13 +40,16 @@ def cl_logits(t):
     return ld
 
 
-def squash_masks(masks, n_classes=N_CLASSES, want_i64=True):
-    """_squash_masks_3D / _squash_masks on device: (B,K,*sp) uint8 -> labels u8 (B,S), int64 (B,*sp), hist (B,K+1)."""
+def squash_masks(masks, n_classes=N_CLASSES, want_i64=True, want_present=False):
+    """_squash_masks_3D / _squash_masks on device: (B,K,*sp) uint8 -> labels u8 (B,S), int64 (B,*sp), hist (B,K+1);
+    want_present: a fourth result, present (B,K) int32 = any(masks[b,k] == 1), from the same read of the masks."""
     nat.require_gpu(masks, "_squash_masks")
     pre = getattr(masks, "_ctseg_labels", None)
-    if pre is not None and masks.dtype == torch.uint8:
-        # label maps squashed by the device input pipeline (volumetric/datasets.collate_3d): nothing left to do
-        return pre[0], (masks.long() if want_i64 else None), pre[1]
+    if pre is not None and not want_present and (masks.dtype == torch.uint8 or len(pre) == 3):
+        # label maps squashed by the device input pipeline (volumetric/datasets.collate_3d), or raw masks that weighted_mixup
+        # squashed already (it stashes the int64 map as a third entry): nothing left to do
+        lab64 = pre[2] if len(pre) == 3 else (masks.long() if want_i64 else None)
+        return pre[0], lab64, pre[1]
     if masks.dtype != torch.uint8:
         masks = masks.to(torch.uint8)
     masks = masks.contiguous()
@@ -55,6 +59,11 @@ def squash_masks(masks, n_classes=N_CLASSES, want_i64=True):
     lab = torch.empty((B, S), dtype=torch.uint8, device=masks.device)
     lab64 = torch.empty((B,) + tuple(masks.shape[2:]), dtype=torch.int64, device=masks.device) if want_i64 else None
     hist = torch.zeros((B, K + 1), dtype=torch.int64, device=masks.device)
+    if want_present:
+        present = torch.zeros((B, K), dtype=torch.int32, device=masks.device)
+        nat.call("ctseg_squash_masks_present", masks.data_ptr(), B, K, S, lab.data_ptr(), nat.ptr(lab64), hist.data_ptr(),
+                 present.data_ptr())
+        return lab, lab64, hist, present
     nat.call("ctseg_squash_masks", masks.data_ptr(), B, K, S, lab.data_ptr(), nat.ptr(lab64), hist.data_ptr())
     return lab, lab64, hist
 
@@ -280,6 +289,62 @@ class SegLossEngine:
         n_ok = ok.sum(dim=0)
         per_class = torch.where(n_ok > 0, score.sum(dim=0) / n_ok, torch.zeros_like(n_ok))   # "mean_batch"
         return per_class.mean(), per_class
+
+
+class SegLossPairEngine(SegLossEngine):
+    """One prediction, two targets (the mixup step, capstone/training/mixup_trainer.py:63-81): side 0 of sample b is
+    ``labels[b]``, side 1 is ``labels[perm[b]]``.  ctseg_seg_loss_pair takes one softmax per voxel for both sides' sums and
+    writes the summed gradient once; the closed forms of the base class run once per side on views of the pair tables."""
+
+    def __init__(self, device, B, S, C=N_CLASSES):
+        super().__init__(device, B, S, C)
+        if 2 * self.R > 64:
+            raise nat.NativeError(f"pair loss pass: {C} classes need reduced records of {2 * self.R} > 64 doubles")
+        f64 = dict(dtype=torch.float64, device=device)
+        self.part2 = torch.zeros((B, self.P, 2, self.R), **f64)
+        self.red2 = torch.zeros((B, 2, self.R), **f64)
+        self.red2_w = torch.zeros((B, 2, self.R), **f64)
+        self.cnt2 = torch.zeros((B, 2, 3, C), dtype=torch.int64, device=device)
+        self.coef2 = torch.zeros((B, 2, 1 + 3 * C), dtype=torch.float32, device=device)
+        self.cw2 = torch.ones((2, C), dtype=torch.float32, device=device)
+        self.cw2_stats = self.cw[None, :].repeat(2, 1)
+        self.perm = self.hist2 = None
+
+    def set_pair(self, labels_u8, hist, index):
+        """index: (B,) integer device tensor; it never visits the host"""
+        self.labels = labels_u8
+        self.perm = index.to(torch.int32).contiguous()
+        self.hist2 = (hist, hist[index.long()])
+
+    @contextlib.contextmanager
+    def side(self, s):
+        """the base class's tables (red, red_w, hist, cnt, coef, cw_eff) stand for side ``s`` inside the block"""
+        keep = (self.red, self.red_w, self.hist, self.cnt, self.coef, self.cw_eff)
+        self.red, self.red_w, self.hist = self.red2[:, s], self.red2_w[:, s], self.hist2[s]
+        self.cnt, self.coef, self.cw_eff = self.cnt2[:, s], self.coef2[:, s], self.cw2[s]
+        try:
+            yield self
+        finally:
+            self.red, self.red_w, self.hist, self.cnt, self.coef, self.cw_eff = keep
+
+    def _pass_pair(self, logits_ptr, ld, cw, do_grad, dl_ptr=None, g_ld=0, gdt=F32):
+        nat.call("ctseg_seg_loss_pair", logits_ptr, ld, self.labels.data_ptr(), self.perm.data_ptr(), self.B, self.S, self.C,
+                 nat.ptr(cw), int(do_grad), self.part2.data_ptr(), self.P, self.cnt2.data_ptr(), self.coef2.data_ptr(), dl_ptr,
+                 g_ld, gdt)
+
+    def stats_pair(self, logits_ptr, ld, weighted_too=False):
+        self.cnt2.zero_()
+        self._pass_pair(logits_ptr, ld, None, False)
+        nat.call("ctseg_reduce_partials_f64", self.part2.data_ptr(), self.B, self.P, 2 * self.R, self.red2.data_ptr())
+        if weighted_too:
+            keep = self.cnt2.clone()
+            self._pass_pair(logits_ptr, ld, self.cw2_stats, False)
+            nat.call("ctseg_reduce_partials_f64", self.part2.data_ptr(), self.B, self.P, 2 * self.R, self.red2_w.data_ptr())
+            self.cnt2.copy_(keep)
+
+    def grad_pair(self, logits_ptr, ld, dl_ptr, g_ld, gdt):
+        """d(sum over both sides)/d(logits) from coef2 / cw2, which build_coef filled inside ``side(0)`` and ``side(1)``"""
+        self._pass_pair(logits_ptr, ld, self.cw2, True, dl_ptr, g_ld, gdt)
 
 
 def dice_counts(pred_u8, true_u8, C=N_CLASSES):

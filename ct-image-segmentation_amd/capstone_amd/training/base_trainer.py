@@ -7,8 +7,8 @@ engine with Z = 1 (9-tap convolutions, 4-class transposed convs); no 2-D-specifi
 
 ``--downsample`` (reference :53,81-85: a trainable 3->1 ``conv1x1`` in front of the U-Net) is carried: the channel mix is three
 elementwise multiply-adds on the input image and the engine records an input-gradient pass for the stem when its input requires grad.
-Not carried over (outside the hot path): the Boundary loss (CPU distance maps), mixup and the W&B logger patch.  They
-raise instead of silently doing something else.
+Not carried over (outside the hot path): the Boundary loss (CPU distance maps) and the W&B logger patch.  They
+raise instead of silently doing something else.  Mixup is ``training/mixup_trainer.py``.
 """
 from argparse import ArgumentParser
 from typing import List

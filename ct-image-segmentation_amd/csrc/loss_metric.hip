@@ -13,12 +13,18 @@ namespace ctseg {
 
 constexpr int CMAX = 16;
 
+// PRESENT: also present[b][k] |= any(masks[b][k] == 1), from the same read (weighted_mixup's structure indicator, capstone/training/
+// utils.py:27: per RAW mask — a structure wholly covered by a higher-numbered one is absent from the squashed labels' histogram)
+template <bool PRESENT>
 __global__ __launch_bounds__(256) void squash_masks_kernel(const uint8_t* __restrict__ masks, int K, int64_t S,
                                                            uint8_t* __restrict__ labels, int64_t* __restrict__ labels_i64,
-                                                           unsigned long long* __restrict__ hist) {
+                                                           unsigned long long* __restrict__ hist, int* __restrict__ present) {
   __shared__ unsigned int s_h[32];
+  __shared__ unsigned int s_pres;
   const int b = blockIdx.y;
   if (threadIdx.x < 32) s_h[threadIdx.x] = 0;
+  if (PRESENT && threadIdx.x == 0) s_pres = 0u;
+  unsigned int pres = 0u;                      // bit k: this thread saw masks[b][k] == 1
   __syncthreads();
   const uint8_t* mb = masks + (int64_t)b * K * S;
   int bg = 0;
@@ -32,6 +38,12 @@ __global__ __launch_bounds__(256) void squash_masks_kernel(const uint8_t* __rest
     if (vec) {
       for (int k = 0; k < K; ++k) {
         const u32x4 m = *reinterpret_cast<const u32x4*>(mb + (int64_t)k * S + v0);
+        if constexpr (PRESENT) {
+          unsigned int hit = 0u;               // a zero byte of (word ^ 0x01010101) is a mask byte equal to 1
+#pragma unroll
+          for (int w = 0; w < 4; ++w) { const uint32_t z = m[w] ^ 0x01010101u; hit |= (z - 0x01010101u) & ~z & 0x80808080u; }
+          if (hit) pres |= 1u << k;
+        }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const int val = (int)((m[i >> 2] >> (8 * (i & 3))) & 0xffu) * (k + 1);
@@ -49,7 +61,9 @@ __global__ __launch_bounds__(256) void squash_masks_kernel(const uint8_t* __rest
         if (v0 + i >= S) break;
         int l = 0;
         for (int k = 0; k < K; ++k) {
-          const int val = (int)mb[(int64_t)k * S + v0 + i] * (k + 1);
+          const int mv = (int)mb[(int64_t)k * S + v0 + i];
+          if (PRESENT && mv == 1) pres |= 1u << k;
+          const int val = mv * (k + 1);
           l = val > l ? val : l;
         }
         lab[i] = l;
@@ -74,6 +88,13 @@ __global__ __launch_bounds__(256) void squash_masks_kernel(const uint8_t* __rest
   __syncthreads();
   if (threadIdx.x <= K && hist != nullptr && s_h[threadIdx.x] != 0)
     atomicAdd(&hist[(int64_t)b * (K + 1) + threadIdx.x], (unsigned long long)s_h[threadIdx.x]);
+  if constexpr (PRESENT) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pres |= __shfl_xor(pres, o, 64);
+    if ((threadIdx.x & 63) == 0 && pres) atomicOr(&s_pres, pres);
+    __syncthreads();
+    if (threadIdx.x < K && ((s_pres >> threadIdx.x) & 1u)) atomicOr(&present[(int64_t)b * K + threadIdx.x], 1);
+  }
 }
 
 // One pass over fp32 channels-last logits.  Block (p, b) covers voxels [p*vp, (p+1)*vp) of sample b.
@@ -323,15 +344,33 @@ extern "C" int ctseg_loss_dice_summary(const double* red, int32_t B, int32_t R, 
   return 0;
 }
 
-extern "C" int ctseg_squash_masks(const uint8_t* masks, int32_t B, int32_t K, int64_t S, uint8_t* labels, int64_t* labels_i64,
-                                  int64_t* hist, void* stream) {
-  CTSEG_REQUIRE(masks && labels && B > 0 && K > 0 && K < 32 && S > 0, "squash_masks: bad arguments");
+static int squash_masks_launch(const uint8_t* masks, int32_t B, int32_t K, int64_t S, uint8_t* labels, int64_t* labels_i64,
+                               int64_t* hist, int32_t* present, void* stream) {
   const int64_t nchunk = (S + 15) / 16;
   int64_t blocks = (nchunk + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(squash_masks_kernel, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, masks, K, S, labels,
-                     labels_i64, (unsigned long long*)hist);
+  if (present)
+    hipLaunchKernelGGL(squash_masks_kernel<true>, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, masks, K, S, labels,
+                       labels_i64, (unsigned long long*)hist, present);
+  else
+    hipLaunchKernelGGL(squash_masks_kernel<false>, dim3((unsigned)blocks, B), dim3(256), 0, (hipStream_t)stream, masks, K, S, labels,
+                       labels_i64, (unsigned long long*)hist, (int*)nullptr);
+  return 0;
+}
+
+extern "C" int ctseg_squash_masks(const uint8_t* masks, int32_t B, int32_t K, int64_t S, uint8_t* labels, int64_t* labels_i64,
+                                  int64_t* hist, void* stream) {
+  CTSEG_REQUIRE(masks && labels && B > 0 && K > 0 && K < 32 && S > 0, "squash_masks: bad arguments");
+  squash_masks_launch(masks, B, K, S, labels, labels_i64, hist, nullptr, stream);
   CTSEG_LAUNCH_CHECK("squash_masks");
+  return 0;
+}
+
+extern "C" int ctseg_squash_masks_present(const uint8_t* masks, int32_t B, int32_t K, int64_t S, uint8_t* labels, int64_t* labels_i64,
+                                          int64_t* hist, int32_t* present, void* stream) {
+  CTSEG_REQUIRE(masks && labels && present && B > 0 && K > 0 && K < 32 && S > 0, "squash_masks_present: bad arguments");
+  squash_masks_launch(masks, B, K, S, labels, labels_i64, hist, present, stream);
+  CTSEG_LAUNCH_CHECK("squash_masks_present");
   return 0;
 }
 

@@ -324,6 +324,16 @@ int ctseg_batchnorm_prelu_bwd_apply(int32_t dtype, const void* g, int32_t g_ld, 
  * (+ optional int64 copy) and per-sample class histogram hist[B][K+1] (int64, must be zeroed by the caller). */
 int ctseg_squash_masks(const uint8_t* masks, int32_t B, int32_t K, int64_t S, uint8_t* labels, int64_t* labels_i64,
                        int64_t* hist, void* stream);
+/* The same squash (same labels, int64 copy and histogram) plus, from the same read of the masks, present[B][K] (int32, zeroed by
+ * the caller) = any(masks[b][k] == 1): the structure indicator of weighted_mixup (capstone/training/utils.py:27), taken per RAW
+ * mask — a structure wholly covered by a higher-numbered one is missing from the squashed labels' histogram. */
+int ctseg_squash_masks_present(const uint8_t* masks, int32_t B, int32_t K, int64_t S, uint8_t* labels, int64_t* labels_i64,
+                               int64_t* hist, int32_t* present, void* stream);
+/* mixup_tensors(x, x[perm], lambda) (capstone/training/utils.py:40,55-56) on fp32 rows [B][n]:
+ *   out[b] = (float)lambda * x[b] + (float)(1 - lambda) * x[perm[b]]
+ * with 1 - lambda formed in double and both products and the sum rounded separately (no FMA): bit-equal to the torch expression.
+ * perm: int32 [B] on the device, entries outside [0, B) are clamped; out must not overlap x. */
+int ctseg_mixup_images(const float* x, const int32_t* perm, int32_t B, int64_t n, double lambda, float* out, void* stream);
 
 /* Fused loss / metric pass over channels-last fp32 logits [B][S][ld], C classes (C <= 16).
  * Replaces F.cross_entropy (capstone/models/losses.py:53,68), softmax->argmax (capstone/training/utils.py:19-20),
@@ -337,6 +347,16 @@ int ctseg_squash_masks(const uint8_t* masks, int32_t B, int32_t K, int64_t S, ui
 int ctseg_seg_loss(const float* logits, int32_t ld, const uint8_t* labels, int32_t B, int64_t S, int32_t C,
                    const float* class_weight, int32_t do_stats, double* part, int32_t P, int64_t* cnt, int32_t do_grad,
                    const float* coef, void* dlogits, int32_t g_ld, int32_t gdtype, uint8_t* pred_out, void* stream);
+/* ctseg_seg_loss's soft path against TWO targets of one prediction: side A of sample b is labels[b], side B is
+ * labels[perm[b]] (perm int32 [B] on the device, clamped to [0, B); no gathered label map exists).  The mixup step
+ * (capstone/training/mixup_trainer.py:63-81) calls its loss wrapper once per target; here the softmax is taken once per voxel.
+ * do_grad = 0: part[B][P][2][2+3C] (each side laid out as ctseg_seg_loss's record: ctseg_reduce_partials_f64 with R = 2*(2+3C)
+ *   reduces both) and cnt[B][2][3][C] (zeroed by the caller); sum p and |pred==c| are computed once and written to both sides.
+ * do_grad = 1: dlogits = d_A + d_B, each term ctseg_seg_loss's gradient with coef[B][2][1+3C]; lambda is folded into coef by
+ *   the caller.  class_weight: [2][C] (one row per side) or NULL.  Same dlogits row widths as ctseg_seg_loss. */
+int ctseg_seg_loss_pair(const float* logits, int32_t ld, const uint8_t* labels, const int32_t* perm, int32_t B, int64_t S,
+                        int32_t C, const float* class_weight, int32_t do_grad, double* part, int32_t P, int64_t* cnt,
+                        const float* coef, void* dlogits, int32_t g_ld, int32_t gdtype, void* stream);
 /* The logits convolution of the U-Net's head with the cross-entropy of the training step fused into its epilogue: the fp32 logits
  * (1.2 GB per step at 2 x 512 x 512 x 48) are never written or re-read.  Replaces, for the native training step, the pair
  *   ctseg_conv_igemm(d) [monai UNet model.2.1.conv.unit0 + identity residual]  +  ctseg_seg_loss(do_stats = do_grad = 2)

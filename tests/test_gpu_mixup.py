@@ -1,0 +1,229 @@
+"""GPU: mixup training on the MI355X — ctseg_mixup_images, ctseg_squash_masks_present, ctseg_seg_loss_pair at op level,
+MultipleLossWrapper.forward_mixed and MixupUNet2D against the CPU oracle (oracle.losses / oracle.metrics / oracle.monai_unet).
+The expected value everywhere is  lambda * L(x, y) + (1 - lambda) * L(x, y[index]),  differentiated by autograd in float64 for
+the op-level checks.  A gradient adds two terms that may cancel, so its bound is stated per term:
+|got - ref| <= 1e-3 * (|g_A| + |g_B|) + 1e-8 (the project's loss-gradient tolerance, tests/test_gpu_parity.py), plus one bf16
+rounding of ref (2^-8 |ref|) where the gradient is stored in bf16."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from capstone_amd import _native as nat  # noqa: E402
+from capstone_amd import segloss  # noqa: E402
+from capstone_amd._native import BF16, F32  # noqa: E402
+
+DEV = "cuda:0"
+NAMES = ["CrossEntropy", "Dice", "Focal", "GeneralizedDice", "WeightedCrossEntropy"]
+B, C, LD = 3, 10, 12
+INDEX = [1, 1, 0]            # a partner drawn twice and a fixed point: what multinomial with replacement hands out
+
+
+@pytest.mark.parametrize("lam", [0.0, 1.0, 0.3, 1e-9])
+def test_mixup_images_is_bit_equal_to_the_torch_expression(lam):
+    from capstone_amd.training.utils import _mixup_images
+    x = torch.randn(3, 1, 67, 63, generator=torch.Generator().manual_seed(2))     # n = 4221: odd rows, scalar head and tail
+    index = torch.tensor([2, 1, 0])
+    got = _mixup_images(x.to(DEV), index.to(DEV), lam).cpu()
+    assert torch.equal(got, lam * x + (1 - lam) * x[index])
+
+
+def test_squash_masks_present_equals_the_squash_and_finds_covered_structures():
+    g = torch.Generator().manual_seed(3)
+    for shape in ((3, 9, 67, 63), (2, 9, 32, 48)):                                # scalar path, 16-byte path
+        masks = (torch.rand(*shape, generator=g) < 0.02).to(torch.uint8)
+        masks[0] = 0                                                              # a sample that holds nothing
+        masks[1, 1] = 0
+        masks[1, 1, 4:8, 4:8] = 1
+        masks[1, 5, 2:12, 2:12] = 1                                               # structure 2 wholly under structure 6
+        md = masks.to(DEV)
+        lab, lab64, hist = segloss.squash_masks(md, 10)
+        lab2, lab64_2, hist2, present = segloss.squash_masks(md, 10, want_present=True)
+        assert torch.equal(lab, lab2) and torch.equal(lab64, lab64_2) and torch.equal(hist, hist2)
+        assert torch.equal(present.bool().cpu(), (masks == 1).flatten(2).any(2))
+        assert present[1, 1] == 1 and hist[1, 2] == 0 and present[0].sum() == 0
+
+
+_CASE = {}
+
+
+def _pair_case(S):
+    """logits (B, S, LD) fp32, labels, the two single-target runs of the existing pass, coefficient tables and the float64 reference
+    gradient terms: computed once per S and shared"""
+    if S in _CASE:
+        return _CASE[S]
+    g = torch.Generator().manual_seed(100 + S)
+    x = torch.zeros(B, S, LD)
+    x[..., :C] = torch.randn(B, S, C, generator=g) * 2.0
+    labels = torch.randint(0, C, (B, S), generator=g).to(torch.uint8)
+    labels[0][labels[0] == 4] = 0
+    coef = torch.zeros(B, 2, 1 + 3 * C)
+    coef[..., 0] = 1.0
+    coef[..., 1:] = (torch.rand(B, 2, 3 * C, generator=g) - 0.5) * 2e-3
+    cw = torch.rand(2, C, generator=g) * 1e-3
+    idx = torch.tensor(INDEX)
+    single = []
+    xd = x.to(DEV)
+    for lab in (labels, labels[idx]):
+        eng = segloss.SegLossEngine(torch.device(DEV), B, S, C)
+        eng.set_labels(lab.to(DEV).contiguous(), None)
+        eng.stats(xd.data_ptr(), LD)
+        single.append((eng.cnt.cpu().clone(), eng.red.cpu().clone()))
+    # float64 reference of each side's gradient: the scalar whose derivative the kernel's formula is
+    terms = []
+    for s, lab in enumerate((labels, labels[idx])):
+        xr = x[..., :C].double().requires_grad_(True)
+        p = torch.softmax(xr, -1)
+        oh = torch.nn.functional.one_hot(lab.long(), C).double()
+        logp = torch.log_softmax(xr, -1)
+        pt, logpt = (p * oh).sum(-1), (logp * oh).sum(-1)
+        cf = coef[:, s].double()
+        a, b_, f = cf[:, None, 1:1 + C], cf[:, None, 1 + C:1 + 2 * C], cf[:, None, 1 + 2 * C:]
+        w = cw[s].double()[lab.long()]
+        L = (cf[:, None, 0] * w * -logpt).sum() + ((a * oh + b_) * p).sum() + ((f * oh).sum(-1) * -(1 - pt) ** 2 * logpt).sum()
+        terms.append(torch.autograd.grad(L, xr)[0])
+    _CASE[S] = dict(x=x, xd=xd, labels=labels, coef=coef, cw=cw, single=single, terms=terms)
+    return _CASE[S]
+
+
+def _pair_engine(S, case):
+    eng = segloss.SegLossPairEngine(torch.device(DEV), B, S, C)
+    eng.set_pair(case["labels"].to(DEV).contiguous(), torch.zeros(B, C, dtype=torch.int64, device=DEV), torch.tensor(INDEX, device=DEV))
+    return eng
+
+
+@pytest.mark.parametrize("S", [4221, 100])
+def test_pair_statistics_equal_two_single_target_runs(S):
+    case = _pair_case(S)
+    eng = _pair_engine(S, case)
+    assert eng.P == (3 if S == 4221 else 1)
+    eng.stats_pair(case["xd"].data_ptr(), LD)
+    for s in (0, 1):
+        cnt, red = case["single"][s]
+        assert torch.equal(eng.cnt2[:, s].cpu(), cnt), s
+        np.testing.assert_allclose(eng.red2[:, s].cpu().numpy(), red.numpy(), rtol=1e-6, atol=0, err_msg=str(s))
+    assert torch.equal(eng.cnt2[:, 0, 1], eng.cnt2[:, 1, 1])                      # the predicted class is one per voxel
+
+
+@pytest.mark.parametrize("gdt,g_ld", [(F32, 12), (BF16, 12), (BF16, 16)], ids=["fp32-12", "bf16-12", "bf16-16"])
+@pytest.mark.parametrize("S", [4221, 100])
+def test_pair_gradient_vs_float64_oracle(S, gdt, g_ld):
+    case = _pair_case(S)
+    eng = _pair_engine(S, case)
+    eng.coef2.copy_(case["coef"].to(DEV))
+    eng.cw2.copy_(case["cw"].to(DEV))
+    dl = torch.full((B, S, g_ld), 7.0, dtype=nat.torch_dtype(gdt), device=DEV)
+    eng.grad_pair(case["xd"].data_ptr(), LD, dl.data_ptr(), g_ld, gdt)
+    got = dl.float().cpu().double()
+    ga, gb = case["terms"]
+    ref = ga + gb
+    bound = 1e-3 * (ga.abs() + gb.abs()) + 1e-8
+    if gdt == BF16:
+        bound = bound + ref.abs() * 2.0 ** -8
+    err = (got[..., :C] - ref).abs()
+    worst = float((err / bound).max())
+    print(f"pair gradient S={S} g_ld={g_ld} dtype={gdt}: worst error / bound = {worst:.3e}, max |ref| = {float(ref.abs().max()):.3e}")
+    assert bool((err <= bound).all()), worst
+    assert float(got[..., C:].abs().max()) == 0.0                                  # the row padding is written as zeros
+
+
+def _oracle_mixed(logits64, target, ind, index, lam, exclude_missing):
+    """values and the two gradient terms of lambda * L(x, y) + (1 - lambda) * L(x, y[index]) summed over NAMES, float64"""
+    from oracle import losses as OL
+    ol = OL.MultipleLoss(NAMES, exclude_missing=exclude_missing)
+    x = logits64.clone().requires_grad_(True)
+    ra, rb = ol(x, target, ind.double()), ol(x, target[index], ind[index].double())
+    ga = torch.autograd.grad(lam * torch.stack(list(ra.values())).sum(), x, retain_graph=True)[0]
+    gb = torch.autograd.grad((1 - lam) * torch.stack(list(rb.values())).sum(), x)[0]
+    return {n: (lam * ra[n] + (1 - lam) * rb[n]).item() for n in NAMES}, ga, gb
+
+
+@pytest.mark.parametrize("exclude_missing", [False, True])
+def test_forward_mixed_on_a_leaf_tensor_vs_oracle(exclude_missing):
+    from capstone_amd.models.losses import MultipleLossWrapper
+    g = torch.Generator().manual_seed(7)
+    logits = torch.randn(3, 10, 67, 63, generator=g)
+    target = torch.randint(0, 10, (3, 67, 63), generator=g)
+    target[0][target[0] == 4] = 0
+    ind = torch.ones(3, 9)
+    ind[1, 3] = 0                                                                  # a class missing on one sample only
+    index, lam = torch.tensor(INDEX), 0.3
+    vals_ref, ga, gb = _oracle_mixed(logits.double(), target, ind, index, lam, exclude_missing)
+    x = logits.to(DEV).requires_grad_(True)
+    wrap = MultipleLossWrapper(NAMES, exclude_missing=exclude_missing)
+    vals = wrap.forward_mixed(x, target.to(DEV), index.to(DEV), lam, mask_indicator=ind.to(DEV))
+    for n in NAMES:
+        print(f"{n}: {vals[n].item():.9g} vs {vals_ref[n]:.9g}")
+        np.testing.assert_allclose(vals[n].item(), vals_ref[n], rtol=1e-5, err_msg=n)
+    torch.stack(list(vals.values())).sum().backward()
+    err = (x.grad.cpu().double() - (ga + gb)).abs()
+    bound = 1e-3 * (ga.abs() + gb.abs()) + 1e-8
+    print(f"forward_mixed gradient: worst error / bound = {float((err / bound).max()):.3e}")
+    assert bool((err <= bound).all())
+    # lambda = 1 with any index: the plain wrapper's values
+    plain = wrap(input=logits.to(DEV), target=target.to(DEV), mask_indicator=ind.to(DEV))
+    plain = {n: plain[n].item() for n in NAMES}
+    one = wrap.forward_mixed(logits.to(DEV), target.to(DEV), index.to(DEV), 1.0, mask_indicator=ind.to(DEV))
+    for n in NAMES:
+        np.testing.assert_allclose(one[n].item(), plain[n], rtol=1e-6, err_msg=n)
+
+
+def test_mixup_module_step_vs_oracle(monkeypatch):
+    from capstone_amd.training import mixup_trainer as MT
+    from capstone_amd.training.base_trainer import BaseUNet2D
+    from capstone_amd.training.utils import weighted_mixup
+    from oracle import losses as OL, metrics as OM
+    from oracle.monai_unet import UNet as OracleUNet
+    torch.manual_seed(5)
+    filters = [8, 16, 32, 64, 128]
+    ref = OracleUNet(2, 1, 10, filters, (2, 2, 2, 2), num_res_units=1)
+    m = MT.MixupUNet2D(filters=list(filters), use_res_units=True, loss_fx=["Focal", "Dice"], transform_degree=0)
+    m.unet.load_state_dict(ref.state_dict())
+    m.to(DEV)
+    g = torch.Generator().manual_seed(6)
+    images = torch.randn(3, 1, 64, 64, generator=g)
+    masks = torch.zeros(3, 9, 64, 64, dtype=torch.uint8)
+    for b, ks in enumerate(((0, 1, 2, 3), (2, 3, 4, 5, 6), (6, 7, 8))):           # three different structure sets
+        for k in ks:
+            masks[b, k, 6 * k + 3:6 * k + 11, 8 + 4 * b:56] = 1
+    ind = torch.ones(3, 9)
+    index, lam = torch.tensor([1, 2, 0]), 0.3
+    monkeypatch.setattr(MT, "weighted_mixup", functools.partial(weighted_mixup, index=index.to(DEV), lambda_=lam))
+    labels = OM.squash_masks(masks, 10)
+    y_ref = ref(lam * images + (1 - lam) * images[index])
+    ol = OL.MultipleLoss(["Dice", "Focal"])
+    ra, rb = ol(y_ref, labels, ind), ol(y_ref, labels[index], ind[index])
+    total_ref = torch.stack([lam * ra[n] + (1 - lam) * rb[n] for n in ra]).sum()
+    total_ref.backward()
+    batch = (images.to(DEV), masks.to(DEV), ind.to(DEV))
+    loss = m.training_step(batch)
+    loss.backward()
+    np.testing.assert_allclose(loss.item(), total_ref.item(), rtol=1e-4)
+    pred = OM.squash_predictions(y_ref.detach())
+    odice = lam * OM.DiceMetric()(pred, labels)[0] + (1 - lam) * OM.DiceMetric()(pred, labels[index])[0]
+    assert abs(m.logged["Mean Dice Score (train)"].item() - odice.item()) <= 0.002
+    for (k, p), q in zip(ref.named_parameters(), m.unet.parameters()):
+        a, b = q.grad.cpu().flatten().double(), p.grad.flatten().double()
+        if b.norm() > 1e-5:
+            assert float(torch.dot(a, b) / (a.norm() * b.norm())) > 0.9999, k
+    with pytest.raises(AssertionError):
+        m._shared_step(batch, prefix="val")
+    # validation is the base class's step: same network, same weights -> same logged values
+    base = BaseUNet2D(filters=list(filters), use_res_units=True, loss_fx=["Focal", "Dice"], transform_degree=0)
+    base.unet = m.unet
+    base.to(DEV)
+    with torch.no_grad():
+        m.validation_step(batch)
+        base.validation_step(batch)
+    for key in ("Dice Loss (val)", "Focal Loss (val)", "Mean Dice Score (val)"):
+        np.testing.assert_allclose(m.logged[key].item(), base.logged[key].item(), rtol=1e-6, atol=1e-7, err_msg=key)
+    opt = m.configure_optimizers()["optimizer"]
+    for _ in range(2):
+        opt.zero_grad()
+        loss = m.training_step(batch)
+        loss.backward()
+        opt.step()
+        assert np.isfinite(loss.item())
