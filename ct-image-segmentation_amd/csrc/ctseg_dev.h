@@ -91,7 +91,9 @@ template <> __device__ __forceinline__ float h2f<F16>(uint32_t u16) {
 template <typename H> __device__ __forceinline__ uint32_t f2h(float x);
 template <> __device__ __forceinline__ uint32_t f2h<BF16>(float x) { return f2bf(x); }
 template <> __device__ __forceinline__ uint32_t f2h<F16>(float x) {
-  const _Float16 h = (_Float16)__builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);   // RNE; NaN passes through fmed3 as NaN
+  // RNE.  The clamp is IEEE-754 minimum / maximum (v_minimum3_f32, v_maximum3_f32), which hand a NaN on: NaN stays NaN.  (v_med3_f32
+  // drops a NaN operand: it stored a NaN as -65504, a signalling one as +65504.  A select around it spills in conv_halo_sw_kernel.)
+  const _Float16 h = (_Float16)__builtin_elementwise_maximum(__builtin_elementwise_minimum(x, 65504.f), -65504.f);
   return (uint32_t)__builtin_bit_cast(unsigned short, h);
 }
 template <typename H> __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f2h<H>(lo) | (f2h<H>(hi) << 16); }
