@@ -83,6 +83,8 @@ class SegLossEngine:
         self.cw_eff = torch.ones(C, dtype=torch.float32, device=device)
         self.labels = self.hist = None
         self.own_dlogits = {}
+        self._ce_ready = None        # the `weighted` that prepare_fused_ce last set the tables up for, until a pass uses them
+        self._part_head = None       # head_ce's partial records (B, slots, R)
 
     # ---- targets ----
     def set_labels(self, labels_u8, hist):
@@ -121,11 +123,15 @@ class SegLossEngine:
         self.coef[:, 0] = (1.0 / denom).float()
         self._ce_ready = weighted
 
-    def fused_ce(self, logits_ptr, ld, dl_ptr, g_ld, gdt, weighted=False):
-        """CrossEntropy (or WeightedCrossEntropy) alone: stats + gradient in ONE pass (upstream gradient 1)."""
-        if getattr(self, "_ce_ready", None) is not weighted:
+    def _take_ce_tables(self, weighted):
+        """the tables of prepare_fused_ce for this ``weighted``, prepared now unless the side stream did; one pass uses them up"""
+        if self._ce_ready is not weighted:
             self.prepare_fused_ce(weighted)
         self._ce_ready = None
+
+    def fused_ce(self, logits_ptr, ld, dl_ptr, g_ld, gdt, weighted=False):
+        """CrossEntropy (or WeightedCrossEntropy) alone: stats + gradient in ONE pass (upstream gradient 1)."""
+        self._take_ce_tables(weighted)
         self._pass(logits_ptr, ld, self.cw if weighted else None, 2, 2, self.coef, dl_ptr, g_ld, gdt)
         nat.call("ctseg_reduce_partials_f64", self.part.data_ptr(), self.B, self.P, self.R,
                  (self.red_w if weighted else self.red).data_ptr())
@@ -133,10 +139,8 @@ class SegLossEngine:
     def head_ce(self, desc, slots, dl_ptr, g_ld, weighted=False):
         """the logits convolution and the cross-entropy (loss sums, Dice counts, d loss / d logits) in ONE launch: ``desc`` is the
         recorded descriptor of the plan's last forward op, ``slots`` = plan.head_ce_slots().  Same tables as fused_ce."""
-        if getattr(self, "_ce_ready", None) is not weighted:
-            self.prepare_fused_ce(weighted)
-        self._ce_ready = None
-        part = getattr(self, "_part_head", None)
+        self._take_ce_tables(weighted)
+        part = self._part_head
         if part is None or part.shape[1] != slots:
             part = self._part_head = torch.zeros((self.B, slots, self.R), dtype=torch.float64, device=self.device)
         nat.call("ctseg_conv_logits_ce", desc, self.labels.data_ptr(), self.C, nat.ptr(self.cw if weighted else None),

@@ -6,12 +6,11 @@
 //                         configured at capstone/volumetric/losses.py:72-77,107) and d(loss)/d(logits).
 // The reference materialises softmax, two 1 GB one-hots and their product; here one pass reads the logits
 // once, keeps everything in registers and reduces with wave shuffles -> per-workgroup fp64 partials
-// (summed later in fixed order: deterministic) and exact int64 counts.
-#include "ctseg_dev.h"
+// (summed later in fixed order: deterministic) and exact int64 counts.  The per-voxel pieces of that pass live in
+// loss_common.h, which the two-target pass of mixup.hip shares.
+#include "loss_common.h"
 
 namespace ctseg {
-
-constexpr int CMAX = 16;
 
 // PRESENT: also present[b][k] |= any(masks[b][k] == 1), from the same read (weighted_mixup's structure indicator, capstone/training/
 // utils.py:27: per RAW mask — a structure wholly covered by a higher-numbered one is absent from the squashed labels' histogram)
@@ -107,22 +106,14 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
                                                        double* __restrict__ part, int P, unsigned long long* __restrict__ cnt,
                                                        int do_grad, const float* __restrict__ coef, char* __restrict__ dlogits,
                                                        int g_ld, uint8_t* __restrict__ pred_out) {
-  constexpr int GSZ = TT<GT>::SZ, GEPC = TT<GT>::EPC;
   __shared__ float s_coef[1 + 3 * CMAX];
   __shared__ float s_cw[CMAX];
-  __shared__ double s_part[4][2 + 3 * CMAX];
+  __shared__ double s_part[4][LOSS_RM];
   __shared__ unsigned int s_cnt[3 * CMAX];
   const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < CMAX) s_cw[tid] = (class_weight != nullptr && tid < C) ? class_weight[tid] : 1.f;
-  if (tid < 1 + 3 * CMAX) s_coef[tid] = 0.f;
-  if (tid < 3 * CMAX) s_cnt[tid] = 0u;
+  init_tables<1>(tid, C, class_weight, s_cw, s_coef, s_cnt);
   __syncthreads();
-  if (do_grad && tid < 1 + 3 * C) {
-    // coef[b] = (ce_scale, a[C], b[C], f[C]) -> padded to CMAX per table
-    const float v = coef[(int64_t)b * (1 + 3 * C) + tid];
-    if (tid == 0) s_coef[0] = v;
-    else { const int t = (tid - 1) / C, c = (tid - 1) % C; s_coef[1 + t * CMAX + c] = v; }
-  }
+  if (do_grad && tid < 1 + 3 * C) fill_coef_row(s_coef, coef + (int64_t)b * (1 + 3 * C), tid, C);
   __syncthreads();
   const int64_t vp = (S + P - 1) / P;
   const int64_t v0 = p * vp, v1 = (v0 + vp < S) ? v0 + vp : S;
@@ -137,14 +128,9 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
   for (int64_t v = v0 + tid; v < v1; v += 256) {
     const int64_t vox = (int64_t)b * S + v;
     float x[CP];
-    const f32x4* lp = reinterpret_cast<const f32x4*>(logits + vox * ld);
-#pragma unroll
-    for (int q = 0; q < CP / 4; ++q) {
-      f32x4 t = {0.f, 0.f, 0.f, 0.f};
-      if (q < nld4) t = lp[q];
-      x[4 * q] = t[0]; x[4 * q + 1] = t[1]; x[4 * q + 2] = t[2]; x[4 * q + 3] = t[3];
-    }
+    load_logits_row<CP>(logits + vox * ld, nld4, x);
     const int t = (int)labels[vox];
+    // spelled out here and in seg_loss_pair_kernel (mixup.hip), the same text: as an inlined helper it changed both kernels' VGPR counts
     float m = x[0];
 #pragma unroll
     for (int c = 1; c < CP; ++c) if (c < C) m = fmaxf(m, x[c]);
@@ -160,9 +146,8 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
       if (c < C && pr[c] > best) { best = pr[c]; pred = c; }
     }
     const float lse = m + logf(ssum);
-    float xt = 0.f, pt = 0.f;
-#pragma unroll
-    for (int c = 0; c < CP; ++c) if (c == t) { xt = x[c]; pt = pr[c]; }
+    float xt, pt;
+    target_terms<CP>(x, pr, t, xt, pt);
     const float logpt = xt - lse;
     const float w = s_cw[t < CMAX ? t : 0];
     if (pred_out != nullptr) pred_out[vox] = (uint8_t)pred;
@@ -182,11 +167,12 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
     }
     if (do_grad) {
       const float ce_scale = s_coef[0] * w;
-      // soft-Dice: dL/dp_c = a_c*[c==t] + b_c ; through softmax: p_k (g_k - sum_j g_j p_j)
       float d[CMAX];
 #pragma unroll
       for (int c = CP; c < CMAX; ++c) d[c] = 0.f;
       if constexpr (SOFT) {
+        // soft-Dice: dL/dp_c = a_c*[c==t] + b_c ; through softmax: p_k (g_k - sum_j g_j p_j).  Spelled out here and in
+        // seg_loss_pair_kernel, the same expressions: as an inlined helper it changed both kernels' VGPR counts
         float gk[CP], dot = 0.f;
 #pragma unroll
         for (int c = 0; c < CP; ++c) {
@@ -205,25 +191,13 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
 #pragma unroll
         for (int c = 0; c < CP; ++c) d[c] = (c < C) ? ce_scale * (pr[c] - ((c == t) ? 1.f : 0.f)) : 0.f;
       }
-      char* gp = dlogits + vox * g_ld * GSZ;
-      if (GSZ == 2 && (g_ld & 7) != 0) {
-        // bf16 rows 12 wide (24 bytes, 8-byte aligned): 8-byte pieces
-        if constexpr (GSZ == 2) {
-#pragma unroll
-          for (int u = 0; u < CP / 4; ++u)
-            if (u * 4 < g_ld) store_ep<GT, 4>(gp + u * 8, d + u * 4);
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < CMAX / GEPC; ++q)
-          if (q * GEPC < g_ld) store_chunk<GT>(gp + q * 16, d + q * GEPC);
-      }
+      store_grad_row<GT, CP>(dlogits + vox * g_ld * TT<GT>::SZ, g_ld, d);
     }
   }
 
   if (do_stats) {
     // wave shuffle reduction (fp64) -> LDS -> one partial record per workgroup
-    double rec[2 + 3 * CMAX];
+    double rec[LOSS_RM];
     rec[0] = a_ce; rec[1] = a_w;
 #pragma unroll
     for (int c = 0; c < CMAX; ++c) {
@@ -232,16 +206,14 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
       rec[2 + 2 * CMAX + c] = c < CP ? a_fo[c < CP ? c : 0] : 0.f;
     }
 #pragma unroll
-    for (int i = 0; i < 2 + 3 * CMAX; ++i) {
+    for (int i = 0; i < LOSS_RM; ++i) {
       double s = 0.0;
       if (SOFT || i < 2) s = wave_sum(rec[i]);
       if (lane == 0) s_part[wave][i] = s;
     }
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
-      unsigned int a = c_in[c], bq = c_pr[c], cq = c_tr[c];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); bq += __shfl_xor(bq, o, 64); cq += __shfl_xor(cq, o, 64); }
+      const unsigned int a = wave_count(c_in[c]), bq = wave_count(c_pr[c]), cq = wave_count(c_tr[c]);
       if (lane == 0 && c < C) {
         if (a) atomicAdd(&s_cnt[c], a);
         if (bq) atomicAdd(&s_cnt[CMAX + c], bq);
@@ -249,18 +221,7 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
       }
     }
     __syncthreads();
-    const int R = 2 + 3 * C;
-    if (tid < R) {
-      int src = tid;
-      if (tid >= 2) { const int t = (tid - 2) / C, c = (tid - 2) % C; src = 2 + t * CMAX + c; }
-      const double s = s_part[0][src] + s_part[1][src] + s_part[2][src] + s_part[3][src];
-      part[((int64_t)b * P + p) * R + tid] = s;
-    }
-    if (tid < 3 * C) {
-      const int t = tid / C, c = tid % C;
-      const unsigned int v = s_cnt[t * CMAX + c];
-      if (v) atomicAdd(&cnt[((int64_t)b * 3 + t) * C + c], (unsigned long long)v);
-    }
+    flush_records<1>(tid, b, p, P, C, &s_part[0][0], s_cnt, part, cnt);
   }
 }
 
@@ -455,31 +416,17 @@ extern "C" int ctseg_seg_loss(const float* logits, int32_t ld, const uint8_t* la
                               const float* class_weight, int32_t do_stats, double* part, int32_t P, int64_t* cnt,
                               int32_t do_grad, const float* coef, void* dlogits, int32_t g_ld, int32_t gdtype, uint8_t* pred_out,
                               void* stream) {
-  CTSEG_REQUIRE(logits && labels && B > 0 && S > 0 && C >= 2 && C <= CMAX, "seg_loss: bad arguments (C <= 16)");
-  CTSEG_REQUIRE(ld % 4 == 0 && ld >= C && ld <= CMAX && ((uintptr_t)logits % 16) == 0, "seg_loss: logits stride %d", ld);
-  CTSEG_REQUIRE(P > 0 && (!do_stats || (part && cnt)), "seg_loss: stats buffers");
-  if (do_grad) {
-    CTSEG_REQUIRE(coef && dlogits && (gdtype == CTSEG_F32 || gdtype == CTSEG_BF16), "seg_loss: grad buffers");
-    // bf16 gradients: 16-byte chunked rows, or 12 wide (8-byte pieces) for the <= 12 class case
-    CTSEG_REQUIRE(g_ld % 4 == 0 && (gdtype == CTSEG_F32 || g_ld % 8 == 0 || g_ld == 12) && g_ld >= C && g_ld <= CMAX &&
-                      ((uintptr_t)dlogits % 16) == 0,
-                  "seg_loss: dlogits stride %d", g_ld);
-  }
-  hipStream_t st = (hipStream_t)stream;
+  if (check_loss_args("seg_loss", logits, ld, labels, B, S, C, P, do_stats != 0, part, cnt, do_grad, coef, dlogits, g_ld, gdtype)) return -1;
   const bool lite = (do_stats == 2 || do_stats == 0) && (do_grad == 2 || do_grad == 0);   // cross-entropy only
   const bool gbf = do_grad && gdtype == CTSEG_BF16;
-#define CTSEG_LOSS_LAUNCH2(GT, SOFT, CP)                                                                                         \
-  hipLaunchKernelGGL((seg_loss_kernel<GT, SOFT, CP>), dim3(P, B), dim3(256), 0, st, logits, ld, labels, S, C, class_weight, do_stats, \
-                     part, P, (unsigned long long*)cnt, do_grad, coef, (char*)dlogits, g_ld, pred_out)
-#define CTSEG_LOSS_LAUNCH(GT, SOFT)                                       \
-  do {                                                                    \
-    if (C <= 12 && ld <= 12) CTSEG_LOSS_LAUNCH2(GT, SOFT, 12);            \
-    else CTSEG_LOSS_LAUNCH2(GT, SOFT, 16);                                \
-  } while (0)
-  if (gbf) { if (lite) CTSEG_LOSS_LAUNCH(BF16, false); else CTSEG_LOSS_LAUNCH(BF16, true); }
-  else { if (lite) CTSEG_LOSS_LAUNCH(float, false); else CTSEG_LOSS_LAUNCH(float, true); }
-#undef CTSEG_LOSS_LAUNCH2
-#undef CTSEG_LOSS_LAUNCH
+  auto launch = [&](auto gt, auto soft) {
+    dispatch_cp(C, ld, [&](auto cp) {
+      hipLaunchKernelGGL((seg_loss_kernel<decltype(gt), soft, cp>), dim3(P, B), dim3(256), 0, (hipStream_t)stream, logits, ld, labels, S, C,
+                         class_weight, do_stats, part, P, (unsigned long long*)cnt, do_grad, coef, (char*)dlogits, g_ld, pred_out);
+    });
+  };
+  if (gbf) { if (lite) launch(BF16(), std::false_type()); else launch(BF16(), std::true_type()); }
+  else { if (lite) launch(float(), std::false_type()); else launch(float(), std::true_type()); }
   CTSEG_LAUNCH_CHECK("seg_loss");
   return 0;
 }

@@ -5,11 +5,9 @@
 //                         softmax per voxel feeds both sides' sums; the gradient pass writes d_A + d_B once.
 // Both are HBM-bound streaming passes, one voxel (or one 16-byte piece) per lane.  A perm entry outside [0, B) is clamped: the
 // index lives on the device and no launch may read out of bounds for it.
-#include "ctseg_dev.h"
+#include "loss_common.h"
 
 namespace ctseg {
-
-constexpr int CMAX = 16;
 
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // a 16-byte access at a 4-byte aligned address
 
@@ -53,8 +51,9 @@ __global__ __launch_bounds__(256) void mixup_images_kernel(const float* __restri
   }
 }
 
-// Per-voxel arithmetic, thread -> voxel assignment and summation order are those of seg_loss_kernel<GT, true, CP>: the counts
-// of each side equal a single-target run's exactly and its sums agree to the last bits.
+// The per-voxel functions of seg_loss_kernel<GT, true, CP> (loss_common.h; softmax and the soft gradient: the same text, see
+// there), its thread -> voxel assignment and its summation order: the counts of each side equal a single-target run's exactly
+// and its sums agree to the last bits.
 // GRAD = false: statistics.  part [B][P][2][R] (R = 2 + 3C, each side laid out as seg_loss_kernel's record), cnt [B][2][3][C].
 // GRAD = true : dlogits = d_A + d_B, each term seg_loss_kernel's formula with its own coef row [b][side] and class weights [side].
 template <typename GT, int CP, bool GRAD>
@@ -63,26 +62,16 @@ __global__ __launch_bounds__(256) void seg_loss_pair_kernel(const float* __restr
                                                             const float* __restrict__ class_weight, double* __restrict__ part, int P,
                                                             unsigned long long* __restrict__ cnt, const float* __restrict__ coef,
                                                             char* __restrict__ dlogits, int g_ld) {
-  constexpr int GSZ = TT<GT>::SZ, GEPC = TT<GT>::EPC;
-  constexpr int RM = 2 + 3 * CMAX;
   __shared__ float s_coef[2][1 + 3 * CMAX];
   __shared__ float s_cw[2][CMAX];
-  __shared__ double s_part[GRAD ? 1 : 4][2][RM];
+  __shared__ double s_part[GRAD ? 1 : 4][2][LOSS_RM];
   __shared__ unsigned int s_cnt[2][3 * CMAX];
   const int p = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (tid < 2 * CMAX) {
-    const int s = tid / CMAX, c = tid % CMAX;
-    s_cw[s][c] = (class_weight != nullptr && c < C) ? class_weight[s * C + c] : 1.f;
-  }
-  if (tid < 2 * (1 + 3 * CMAX)) (&s_coef[0][0])[tid] = 0.f;
-  if (tid < 2 * 3 * CMAX) (&s_cnt[0][0])[tid] = 0u;
+  init_tables<2>(tid, C, class_weight, &s_cw[0][0], &s_coef[0][0], &s_cnt[0][0]);
   __syncthreads();
   if (GRAD && tid < 2 * (1 + 3 * C)) {
-    // coef[b][side] = (ce_scale, a[C], b[C], f[C]) -> padded to CMAX per table
-    const int s = tid / (1 + 3 * C), i = tid % (1 + 3 * C);
-    const float v = coef[((int64_t)b * 2 + s) * (1 + 3 * C) + i];
-    if (i == 0) s_coef[s][0] = v;
-    else { const int t = (i - 1) / C, c = (i - 1) % C; s_coef[s][1 + t * CMAX + c] = v; }
+    const int s = tid / (1 + 3 * C);
+    fill_coef_row(s_coef[s], coef + ((int64_t)b * 2 + s) * (1 + 3 * C), tid % (1 + 3 * C), C);
   }
   __syncthreads();
   const int64_t vp = (S + P - 1) / P;
@@ -104,14 +93,9 @@ __global__ __launch_bounds__(256) void seg_loss_pair_kernel(const float* __restr
   for (int64_t v = v0 + tid; v < v1; v += 256) {
     const int64_t vox = (int64_t)b * S + v;
     float x[CP];
-    const f32x4* lp = reinterpret_cast<const f32x4*>(logits + vox * ld);
-#pragma unroll
-    for (int q = 0; q < CP / 4; ++q) {
-      f32x4 t = {0.f, 0.f, 0.f, 0.f};
-      if (q < nld4) t = lp[q];
-      x[4 * q] = t[0]; x[4 * q + 1] = t[1]; x[4 * q + 2] = t[2]; x[4 * q + 3] = t[3];
-    }
+    load_logits_row<CP>(logits + vox * ld, nld4, x);
     const int tt[2] = {(int)lab_a[v], (int)lab_b[v]};
+    // spelled out here and in seg_loss_kernel (loss_metric.hip), the same text: as an inlined helper it changed both kernels' VGPR counts
     float m = x[0];
 #pragma unroll
     for (int c = 1; c < CP; ++c) if (c < C) m = fmaxf(m, x[c]);
@@ -139,9 +123,8 @@ __global__ __launch_bounds__(256) void seg_loss_pair_kernel(const float* __restr
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int t = tt[s];
-      float xt = 0.f, pt = 0.f;
-#pragma unroll
-      for (int c = 0; c < CP; ++c) if (c == t) { xt = x[c]; pt = pr[c]; }
+      float xt, pt;
+      target_terms<CP>(x, pr, t, xt, pt);
       const float logpt = xt - lse;
       const float w = s_cw[s][t < CMAX ? t : 0];
       const float om = 1.f - pt;
@@ -158,7 +141,8 @@ __global__ __launch_bounds__(256) void seg_loss_pair_kernel(const float* __restr
         }
       } else {
         const float ce_scale = s_coef[s][0] * w;
-        // soft-Dice: dL/dp_c = a_c*[c==t] + b_c ; through softmax: p_k (g_k - sum_j g_j p_j)
+        // soft-Dice: dL/dp_c = a_c*[c==t] + b_c ; through softmax: p_k (g_k - sum_j g_j p_j).  Spelled out here and in
+        // seg_loss_kernel, the same expressions: as an inlined helper it changed both kernels' VGPR counts
         float gk[CP], dot = 0.f;
 #pragma unroll
         for (int c = 0; c < CP; ++c) {
@@ -175,21 +159,7 @@ __global__ __launch_bounds__(256) void seg_loss_pair_kernel(const float* __restr
         }
       }
     }
-    if constexpr (GRAD) {
-      char* gp = dlogits + vox * g_ld * GSZ;
-      if (GSZ == 2 && (g_ld & 7) != 0) {
-        // bf16 rows 12 wide (24 bytes, 8-byte aligned): 8-byte pieces
-        if constexpr (GSZ == 2) {
-#pragma unroll
-          for (int u = 0; u < CP / 4; ++u)
-            if (u * 4 < g_ld) store_ep<GT, 4>(gp + u * 8, d + u * 4);
-        }
-      } else {
-#pragma unroll
-        for (int q = 0; q < CMAX / GEPC; ++q)
-          if (q * GEPC < g_ld) store_chunk<GT>(gp + q * 16, d + q * GEPC);
-      }
-    }
+    if constexpr (GRAD) store_grad_row<GT, CP>(dlogits + vox * g_ld * TT<GT>::SZ, g_ld, d);
   }
 
   if constexpr (!GRAD) {
@@ -212,35 +182,18 @@ __global__ __launch_bounds__(256) void seg_loss_pair_kernel(const float* __restr
     }
 #pragma unroll
     for (int c = 0; c < CP; ++c) {
-      unsigned int bq = c_pr[c], a0 = c_in[0][c], a1 = c_in[1][c], t0 = c_tr[0][c], t1 = c_tr[1][c];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        bq += __shfl_xor(bq, o, 64);
-        a0 += __shfl_xor(a0, o, 64); a1 += __shfl_xor(a1, o, 64);
-        t0 += __shfl_xor(t0, o, 64); t1 += __shfl_xor(t1, o, 64);
-      }
+      const unsigned int bq = wave_count(c_pr[c]), a0 = wave_count(c_in[0][c]), a1 = wave_count(c_in[1][c]),
+                         t0 = wave_count(c_tr[0][c]), t1 = wave_count(c_tr[1][c]);
       if (lane == 0 && c < C) {
         if (a0) atomicAdd(&s_cnt[0][c], a0);
         if (a1) atomicAdd(&s_cnt[1][c], a1);
-        if (bq) { atomicAdd(&s_cnt[0][CMAX + c], bq); atomicAdd(&s_cnt[1][CMAX + c], bq); }
+        if (bq) { atomicAdd(&s_cnt[0][CMAX + c], bq); atomicAdd(&s_cnt[1][CMAX + c], bq); }   // one predicted class per voxel
         if (t0) atomicAdd(&s_cnt[0][2 * CMAX + c], t0);
         if (t1) atomicAdd(&s_cnt[1][2 * CMAX + c], t1);
       }
     }
     __syncthreads();
-    const int R = 2 + 3 * C;
-    if (tid < 2 * R) {
-      const int s = tid / R, i = tid % R;
-      int src = i;
-      if (i >= 2) { const int t = (i - 2) / C, c = (i - 2) % C; src = 2 + t * CMAX + c; }
-      const double sum = s_part[0][s][src] + s_part[1][s][src] + s_part[2][s][src] + s_part[3][s][src];
-      part[(((int64_t)b * P + p) * 2 + s) * R + i] = sum;
-    }
-    if (tid < 2 * 3 * C) {
-      const int s = tid / (3 * C), t = (tid % (3 * C)) / C, c = tid % C;
-      const unsigned int v = s_cnt[s][t * CMAX + c];
-      if (v) atomicAdd(&cnt[(((int64_t)b * 2 + s) * 3 + t) * C + c], (unsigned long long)v);
-    }
+    flush_records<2>(tid, b, p, P, C, &s_part[0][0][0], &s_cnt[0][0], part, cnt);
   }
 }
 
@@ -264,30 +217,17 @@ extern "C" int ctseg_mixup_images(const float* x, const int32_t* perm, int32_t B
 extern "C" int ctseg_seg_loss_pair(const float* logits, int32_t ld, const uint8_t* labels, const int32_t* perm, int32_t B, int64_t S,
                                    int32_t C, const float* class_weight, int32_t do_grad, double* part, int32_t P, int64_t* cnt,
                                    const float* coef, void* dlogits, int32_t g_ld, int32_t gdtype, void* stream) {
-  CTSEG_REQUIRE(logits && labels && perm && B > 0 && S > 0 && C >= 2 && C <= CMAX, "seg_loss_pair: bad arguments (C <= 16)");
-  CTSEG_REQUIRE(ld % 4 == 0 && ld >= C && ld <= CMAX && ((uintptr_t)logits % 16) == 0, "seg_loss_pair: logits stride %d", ld);
-  CTSEG_REQUIRE(P > 0 && (do_grad || (part && cnt)), "seg_loss_pair: stats buffers");
-  if (do_grad) {
-    CTSEG_REQUIRE(coef && dlogits && (gdtype == CTSEG_F32 || gdtype == CTSEG_BF16), "seg_loss_pair: grad buffers");
-    // the row widths of ctseg_seg_loss: 16-byte chunked rows, or bf16 12 wide (8-byte pieces) for the <= 12 class case
-    CTSEG_REQUIRE(g_ld % 4 == 0 && (gdtype == CTSEG_F32 || g_ld % 8 == 0 || g_ld == 12) && g_ld >= C && g_ld <= CMAX &&
-                      ((uintptr_t)dlogits % 16) == 0,
-                  "seg_loss_pair: dlogits stride %d", g_ld);
-  }
-  hipStream_t st = (hipStream_t)stream;
-#define CTSEG_PAIR_LAUNCH2(GT, CP, GRAD)                                                                                           \
-  hipLaunchKernelGGL((seg_loss_pair_kernel<GT, CP, GRAD>), dim3(P, B), dim3(256), 0, st, logits, ld, labels, perm, B, S, C, class_weight, \
-                     part, P, (unsigned long long*)cnt, coef, (char*)dlogits, g_ld)
-#define CTSEG_PAIR_LAUNCH(GT, GRAD)                                       \
-  do {                                                                    \
-    if (C <= 12 && ld <= 12) CTSEG_PAIR_LAUNCH2(GT, 12, GRAD);            \
-    else CTSEG_PAIR_LAUNCH2(GT, 16, GRAD);                                \
-  } while (0)
-  if (!do_grad) CTSEG_PAIR_LAUNCH(float, false);
-  else if (gdtype == CTSEG_BF16) CTSEG_PAIR_LAUNCH(BF16, true);
-  else CTSEG_PAIR_LAUNCH(float, true);
-#undef CTSEG_PAIR_LAUNCH2
-#undef CTSEG_PAIR_LAUNCH
+  CTSEG_REQUIRE(perm, "seg_loss_pair: bad arguments (C <= 16)");
+  if (check_loss_args("seg_loss_pair", logits, ld, labels, B, S, C, P, !do_grad, part, cnt, do_grad, coef, dlogits, g_ld, gdtype)) return -1;
+  auto launch = [&](auto gt, auto grad) {
+    dispatch_cp(C, ld, [&](auto cp) {
+      hipLaunchKernelGGL((seg_loss_pair_kernel<decltype(gt), cp, grad>), dim3(P, B), dim3(256), 0, (hipStream_t)stream, logits, ld, labels,
+                         perm, B, S, C, class_weight, part, P, (unsigned long long*)cnt, coef, (char*)dlogits, g_ld);
+    });
+  };
+  if (!do_grad) launch(float(), std::false_type());
+  else if (gdtype == CTSEG_BF16) launch(BF16(), std::true_type());
+  else launch(float(), std::true_type());
   CTSEG_LAUNCH_CHECK("seg_loss_pair");
   return 0;
 }

@@ -130,6 +130,31 @@ def test_pair_gradient_vs_float64_oracle(S, gdt, g_ld):
     assert float(got[..., C:].abs().max()) == 0.0                                  # the row padding is written as zeros
 
 
+@pytest.mark.parametrize("gdt,g_ld", [(F32, 12), (BF16, 12), (BF16, 16)], ids=["fp32-12", "bf16-12", "bf16-16"])
+@pytest.mark.parametrize("S", [4221, 100])
+def test_single_target_soft_gradient_vs_float64_oracle(S, gdt, g_ld):
+    """seg_loss_kernel<..., true, 12>'s gradient through the three branches of the row store, against side 0 of the pair case:
+    one term, so the bound is 1e-3 * |g| + 1e-8 (+ one bf16 rounding of the reference where the row is bf16)"""
+    case = _pair_case(S)
+    eng = segloss.SegLossEngine(torch.device(DEV), B, S, C)
+    assert eng.P == (3 if S == 4221 else 1)
+    eng.set_labels(case["labels"].to(DEV).contiguous(), None)
+    eng.coef.copy_(case["coef"][:, 0].to(DEV))
+    eng.cw_eff.copy_(case["cw"][0].to(DEV))
+    dl = torch.full((B, S, g_ld), 7.0, dtype=nat.torch_dtype(gdt), device=DEV)
+    eng.grad(case["xd"].data_ptr(), LD, dl.data_ptr(), g_ld, gdt)
+    got = dl.float().cpu().double()
+    ref = case["terms"][0]
+    bound = 1e-3 * ref.abs() + 1e-8
+    if gdt == BF16:
+        bound = bound + ref.abs() * 2.0 ** -8
+    err = (got[..., :C] - ref).abs()
+    worst = float((err / bound).max())
+    print(f"single gradient S={S} g_ld={g_ld} dtype={gdt}: worst error / bound = {worst:.3e}, max |ref| = {float(ref.abs().max()):.3e}")
+    assert bool((err <= bound).all()), worst
+    assert float(got[..., C:].abs().max()) == 0.0                                  # the row padding is written as zeros
+
+
 def _oracle_mixed(logits64, target, ind, index, lam, exclude_missing):
     """values and the two gradient terms of lambda * L(x, y) + (1 - lambda) * L(x, y[index]) summed over NAMES, float64"""
     from oracle import losses as OL
