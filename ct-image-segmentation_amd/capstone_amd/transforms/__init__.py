@@ -1,0 +1,2 @@
+"""Device-side 2-D transforms: drop-in names of reference capstone/transforms (transforms_2d.py, predefined.py)."""
+from .pipeline2d import BatchPipeline2D, SliceStore2D  # noqa: F401

@@ -413,6 +413,34 @@ int ctseg_resize3d_to_hwd(const void* image, int32_t image_dtype, const uint8_t*
                           int32_t Do, int32_t Ho, int32_t Wo, int32_t window, float win_lo, float win_hi, float* image_out,
                           uint8_t* masks_out, uint8_t* labels_out, int64_t* hist, void* stream);
 
+/* 2-D input pipeline on the device, a whole batch in one launch: the presets of capstone/transforms/predefined.py that are
+ * per-pixel and index arithmetic (windowed_degree_1, windowed_degree_2, every "test" side):
+ *   window     apply_window (capstone/transforms/transforms_2d.py:97-107) per window c: lo = win_lo[c], hi = win_hi[c] (HOST
+ *              arrays of C <= 4 ints), clip(v, lo, hi) and with shift (clipped - lo) / (hi - lo + 1e-8); integer input is
+ *              evaluated in float64, fp32 input in fp32 (numpy's result for a float32 array); the value is then held as float64
+ *   geometry   mode 0 CROP:   Cr = x[y0:y0+Ho, x0:x0+Wo], R = np.rot90(Cr, k), out = R[:, ::-1] if flip else R, the same
+ *                             indices for image and masks (k odd needs Ho == Wo)
+ *              mode 1 RESIZE: image bilinear with half-pixel centres on the windowed float64 values, per axis
+ *                             f = (float)((d + 0.5) * (In / Out) - 0.5), s = floor(f), w = f - s in float32, s < 0 -> (0, 0),
+ *                             s >= In - 1 -> (In - 1, 0), a * (1 - w) + b * w in float64 with 1 - w formed in float32,
+ *                             horizontal pass first; masks nearest, s = min(floor(d * (In / Out)), In - 1) in float64
+ *                             (y0, x0, k, flip are not read)
+ *   normalize  (float)v, then - mean[c], then * denom[c] (HOST arrays of C floats, denom = 1 / std formed by the caller): two
+ *              fp32 roundings; mean == denom == NULL: the cast alone
+ * Nothing is contracted into an FMA.  image_store holds the raw slices (image_dtype CTSEG_I16 / CTSEG_U8 / CTSEG_F32,
+ * image_elems elements), mask_store their masks as u8 planes [K][H][W] (mask_bytes bytes; K <= 15).  table (DEVICE) and
+ * table_host (its HOST copy, which is validated before the launch) are int64 [B][8] rows
+ *   image_off (elements into image_store), mask_off (bytes into mask_store), H, W, y0, x0, k, flip
+ * so slices of different sizes share one launch.  Outputs, each optional: image_out fp32 [B][C][Ho][Wo], masks_out u8
+ * [B][K][Ho][Wo] (the raw bytes), labels_out u8 [B][Ho][Wo] (highest set class wins: ctseg_squash_masks' rule), hist int64
+ * [B][K+1] (needs labels_out) and present int32 [B][K] = any(output mask == 1) per RAW mask (ctseg_squash_masks_present's
+ * meaning); hist and present are zeroed by the caller.  image_store or mask_store may be NULL. */
+int ctseg_pipeline2d_batch(const void* image_store, int32_t image_dtype, int64_t image_elems, const uint8_t* mask_store,
+                           int64_t mask_bytes, const int64_t* table, const int64_t* table_host, int32_t B, int32_t K, int32_t mode,
+                           int32_t Ho, int32_t Wo, int32_t C, const int32_t* win_lo, const int32_t* win_hi, int32_t shift,
+                           const float* mean, const float* denom, float* image_out, uint8_t* masks_out, uint8_t* labels_out,
+                           int64_t* hist, int32_t* present, void* stream);
+
 /* Sliding-window inference (BASELINE.json configs[4]).  The reference has no inferer (grep: 0 hits); the
  * semantics are those of MONAI 0.3 `monai.inferers.sliding_window_inference`, the companion of the `monai.networks.nets.UNet`
  * the reference builds at capstone/volumetric/base_trainer.py:65-72.
