@@ -512,6 +512,19 @@ static int wgrad_stem_grid(const ctseg_wgrad_desc* d) {
 }
 int wgrad_stem_slabs(const ctseg_wgrad_desc* d) { return 4 * wgrad_stem_grid(d); }
 
+// The instantiation conv_stem_wgrad_kernel<ct, dyn> of an eligible descriptor: the one place that decides it (the launcher
+// dispatches on it, ctseg_wgrad_pass_name reports it).  dyn follows dyn_g being set (wgrad_stem_dyn_ok checked by the entry point).
+struct WgradStemVariant { int ct; bool dyn; };
+static WgradStemVariant wgrad_stem_variant(const ctseg_wgrad_desc* d) { return {d->Cn / 16, d->dyn_g != nullptr}; }
+
+const char* wgrad_stem_name(const ctseg_wgrad_desc* d) {
+  static const char* const PLAIN[] = {"stem 16", "stem 32", "stem 48", "stem 64"};
+  const WgradStemVariant v = wgrad_stem_variant(d);
+  if (v.ct < 1 || v.ct > 4) return nullptr;
+  if (v.dyn) return v.ct == 2 ? "stem 32 dyn" : v.ct == 4 ? "stem 64 dyn" : nullptr;
+  return PLAIN[v.ct - 1];
+}
+
 void launch_wgrad_stem(const ctseg_wgrad_desc* d, hipStream_t st) {
   StemWgradArgs a;
   a.in = (const char*)d->in; a.dy = (const char*)d->dy; a.ws = d->ws;
@@ -519,17 +532,17 @@ void launch_wgrad_stem(const ctseg_wgrad_desc* d, hipStream_t st) {
   a.d_ld = d->d_ld; a.kpad_w = d->kpad_w; a.cn_pad = d->cn_pad;
   a.G.tiles = stem_tiles(d->Xr, d->Yr, d->Zr); a.G.tyn = (d->Yr + 7) / 8; a.G.tzn = (d->Zr + 7) / 8;
   const int total = a.G.tiles * d->N, grid = wgrad_stem_grid(d);
-  const int ct = d->Cn / 16;
+  const WgradStemVariant v = wgrad_stem_variant(d);
   a.dyn_g = (const char*)d->dyn_g; a.dyn_y = (const char*)d->dyn_y; a.dyn_mr = d->dyn_mean_rstd; a.dyn_alpha = d->dyn_alpha;
   a.dyn_sums = d->dyn_sums; a.dyn_g_ld = d->dyn_g_ld; a.dyn_y_ld = d->dyn_y_ld;
-  if (d->dyn_g != nullptr) {      // (wgrad_stem_dyn_ok checked by the entry point)
-    if (ct == 2) hipLaunchKernelGGL((conv_stem_wgrad_kernel<2, true>), dim3(grid), dim3(256), 0, st, a, total);
+  if (v.dyn) {
+    if (v.ct == 2) hipLaunchKernelGGL((conv_stem_wgrad_kernel<2, true>), dim3(grid), dim3(256), 0, st, a, total);
     else hipLaunchKernelGGL((conv_stem_wgrad_kernel<4, true>), dim3(grid), dim3(256), 0, st, a, total);
     return;
   }
-  if (ct == 1) hipLaunchKernelGGL((conv_stem_wgrad_kernel<1>), dim3(grid), dim3(256), 0, st, a, total);
-  else if (ct == 2) hipLaunchKernelGGL((conv_stem_wgrad_kernel<2>), dim3(grid), dim3(256), 0, st, a, total);
-  else if (ct == 3) hipLaunchKernelGGL((conv_stem_wgrad_kernel<3>), dim3(grid), dim3(256), 0, st, a, total);
+  if (v.ct == 1) hipLaunchKernelGGL((conv_stem_wgrad_kernel<1>), dim3(grid), dim3(256), 0, st, a, total);
+  else if (v.ct == 2) hipLaunchKernelGGL((conv_stem_wgrad_kernel<2>), dim3(grid), dim3(256), 0, st, a, total);
+  else if (v.ct == 3) hipLaunchKernelGGL((conv_stem_wgrad_kernel<3>), dim3(grid), dim3(256), 0, st, a, total);
   else hipLaunchKernelGGL((conv_stem_wgrad_kernel<4>), dim3(grid), dim3(256), 0, st, a, total);
 }
 

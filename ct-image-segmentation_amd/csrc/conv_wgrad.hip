@@ -486,17 +486,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) void wgra
 bool wgrad_up_eligible(const ctseg_wgrad_desc* d);
 int wgrad_up_slabs(const ctseg_wgrad_desc* d);
 void launch_wgrad_up(const ctseg_wgrad_desc* d, hipStream_t st);
+const char* wgrad_up_name(const ctseg_wgrad_desc* d);
 bool wgrad_stem_eligible(const ctseg_wgrad_desc* d);
 bool wgrad_stem_dyn_ok(const ctseg_wgrad_desc* d);
 int wgrad_stem_slabs(const ctseg_wgrad_desc* d);
 void launch_wgrad_stem(const ctseg_wgrad_desc* d, hipStream_t st);
+const char* wgrad_stem_name(const ctseg_wgrad_desc* d);
 bool wgrad_halo_eligible(const ctseg_wgrad_desc* d);
 int wgrad_halo_slabs(const ctseg_wgrad_desc* d);
 bool wgrad_halo_in_norm_ok(const ctseg_wgrad_desc* d);
 void launch_wgrad_halo(const ctseg_wgrad_desc* d, hipStream_t st);
+const char* wgrad_halo_name(const ctseg_wgrad_desc* d);
 bool wgrad_ring_eligible(const ctseg_wgrad_desc* d);
 int wgrad_ring_wgs_per_slab(const ctseg_wgrad_desc* d, int32_t* stage_bytes);
 void launch_wgrad_ring(const ctseg_wgrad_desc* d, int rows_per_split, hipStream_t st);
+const char* wgrad_ring_name(const ctseg_wgrad_desc* d);
 
 enum class WgradPass { HALO, UP, STEM, RING, GENERIC };
 
@@ -522,8 +526,41 @@ static bool wgrad_dy_norm_ok(const ctseg_wgrad_desc* d, WgradPass p) {
   return d->dyn_col0 > 0 && d->in_mean_rstd == nullptr && p == WgradPass::STEM && wgrad_stem_dyn_ok(d);
 }
 
-template <typename T, bool SMALLC> static void launch_wgrad(WgradKArgs& a, hipStream_t st) {
-  const int bnw = ctseg_wgrad_tile_cols(a.Cn);
+// The instantiation conv_wgrad_kernel<T, bnw, ., ., smallc> of the generic family: the one place that decides it (the entry point
+// dispatches on it, ctseg_conv_wgrad_wgs_per_slab sizes by it, ctseg_wgrad_pass_name reports it)
+struct WgradGenericTile { int bnw; bool smallc; };
+static WgradGenericTile wgrad_generic_tile(const ctseg_wgrad_desc* d) { return {ctseg_wgrad_tile_cols(d->Cn), wgrad_small_operand(d)}; }
+
+// 12-wide bf16 rows of a 16-channel gathered operand: the LDS-halo and stride-2 transposed kernels only
+static bool wgrad_rows12_ok(const ctseg_wgrad_desc* d, WgradPass p) {
+  return p == WgradPass::HALO || p == WgradPass::UP || d->dtype != CTSEG_BF16 || d->g_ld != 12 || d->Cg != 16;
+}
+
+// What the entry point refuses apart from null operands and slab sizes, as the message it reports; NULL: nothing.  Shared with
+// ctseg_wgrad_pass_name, which names only what the launch would run.  _early: before a pass can be selected.
+static const char* wgrad_refusal_early(const ctseg_wgrad_desc* d) {
+  if (d->dtype != CTSEG_F32 && d->dtype != CTSEG_BF16) return "conv_wgrad: bad dtype";
+  if (!(d->ntaps >= 1 && d->ntaps <= CTSEG_MAX_TAPS && d->splits >= 1)) return "conv_wgrad: ntaps/splits";
+  return nullptr;
+}
+static const char* wgrad_refusal(const ctseg_wgrad_desc* d, WgradPass pass) {
+  const int EPC = d->dtype == CTSEG_F32 ? 4 : 8;
+  const bool halo = pass == WgradPass::HALO;     // (also moves 12-wide bf16 rows: ctseg_wgrad_narrow_ok)
+  if (d->dyn_g != nullptr) {
+    if (!(wgrad_dy_norm_ok(d, pass) && d->dyn_y && d->dyn_mean_rstd && d->dyn_alpha && d->dyn_sums &&
+          ((uintptr_t)d->dyn_g % 16) == 0 && ((uintptr_t)d->dyn_y % 16) == 0))
+      return "conv_wgrad: dyn_* (dY formed on load) is not implemented for this pass (ask ctseg_wgrad_dy_norm_ok)";
+  } else if (d->dyn_col0 != 0) {
+    return "conv_wgrad: dyn_col0 without dyn_g";
+  }
+  if (d->in_mean_rstd != nullptr && !(halo && wgrad_halo_in_norm_ok(d) && d->in_alpha != nullptr))
+    return "conv_wgrad: in_mean_rstd (normalise the operand on load) is not implemented for this pass (ask ctseg_wgrad_in_norm_ok)";
+  if (!((d->d_ld % EPC == 0 || halo) && ((uintptr_t)d->dy % 16) == 0)) return "conv_wgrad: dy must be 16-byte chunked";
+  if (!wgrad_rows12_ok(d, pass)) return "conv_wgrad: 12-wide rows need an LDS-halo kernel";
+  return nullptr;
+}
+
+template <typename T, bool SMALLC> static void launch_wgrad(WgradKArgs& a, int bnw, hipStream_t st) {
   const int kb = a.kpad_w / 128, cb = a.cn_pad / bnw, zs = a.N * a.splits;
   dim3 grid((unsigned)kb, (unsigned)cb, (unsigned)zs);
   a.kblocks = a.cblocks = 0;
@@ -564,7 +601,7 @@ extern "C" int ctseg_conv_wgrad_wgs_per_slab(const ctseg_wgrad_desc* d, int32_t*
       if (per_cu) *per_cu = 1;
       return wgrad_ring_wgs_per_slab(d, stage_bytes);
     case WgradPass::GENERIC: {
-      const int bnw = ctseg_wgrad_tile_cols(d->Cn);
+      const int bnw = wgrad_generic_tile(d).bnw;
       if (per_cu) *per_cu = 4;
       if (stage_bytes) *stage_bytes = 32 * (128 + bnw) * (d->dtype == CTSEG_F32 ? 4 : 2);
       return (d->kpad_w / 128) * (d->cn_pad / bnw);
@@ -587,27 +624,42 @@ extern "C" int ctseg_wgrad_narrow_ok(const ctseg_wgrad_desc* d) {
   return (p == WgradPass::HALO || (p == WgradPass::UP && d->d_ld != 12)) ? 1 : 0;
 }
 
+// The kernel a launch of this descriptor runs, by the helper its launcher dispatches on (wgrad_halo_variant, wgrad_up_width,
+// wgrad_stem_variant, wring_kind, wgrad_generic_tile), for tests that must know a shape still lands on the kernel they were
+// written for.  NULL: rejected, or refused by the checks the launch shares with it (wgrad_refusal_early, wgrad_refusal).
+extern "C" const char* ctseg_wgrad_pass_name(const ctseg_wgrad_desc* d) {
+  if (!desc_ok(d) || wgrad_refusal_early(d) != nullptr) return nullptr;
+  if (d->N <= 0 || d->Cg <= 0 || d->Cn <= 0 || d->Xr <= 0 || d->Yr <= 0 || d->Zr <= 0) return nullptr;
+  const WgradPass p = select_wgrad_pass(d);
+  if (wgrad_refusal(d, p) != nullptr) return nullptr;
+  switch (p) {
+    case WgradPass::HALO: return wgrad_halo_name(d);
+    case WgradPass::UP: return wgrad_up_name(d);
+    case WgradPass::STEM: return wgrad_stem_name(d);
+    case WgradPass::RING: return wgrad_ring_name(d);
+    case WgradPass::GENERIC: break;
+  }
+  static const struct { int bnw; bool smallc; const char* name; } NAMES[] = {
+      {16, false, "generic 16"},  {32, false, "generic 32"},  {64, false, "generic 64"},  {128, false, "generic 128"},
+      {16, true, "generic 16 element-wise"}, {32, true, "generic 32 element-wise"}, {64, true, "generic 64 element-wise"},
+      {128, true, "generic 128 element-wise"}};
+  const WgradGenericTile t = wgrad_generic_tile(d);
+  for (const auto& e : NAMES)
+    if (e.bnw == t.bnw && e.smallc == t.smallc) return e.name;
+  return nullptr;
+}
+
 extern "C" int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream) {
   CTSEG_REQUIRE_DESC(d, "conv_wgrad");
   CTSEG_REQUIRE(d->in && d->dy && d->ws, "conv_wgrad: null pointer");
-  CTSEG_REQUIRE(d->dtype == CTSEG_F32 || d->dtype == CTSEG_BF16, "conv_wgrad: bad dtype");
-  CTSEG_REQUIRE(d->ntaps >= 1 && d->ntaps <= CTSEG_MAX_TAPS && d->splits >= 1, "conv_wgrad: ntaps/splits");
+  const char* why = wgrad_refusal_early(d);
+  CTSEG_REQUIRE(why == nullptr, "%s", why);
   const int SZ = d->dtype == CTSEG_F32 ? 4 : 2, EPC = 16 / SZ;
   const WgradPass pass = select_wgrad_pass(d);
-  const bool halo = pass == WgradPass::HALO;     // (also moves 12-wide bf16 rows: ctseg_wgrad_narrow_ok)
-  if (d->dyn_g != nullptr)
-    CTSEG_REQUIRE(wgrad_dy_norm_ok(d, pass) && d->dyn_y && d->dyn_mean_rstd && d->dyn_alpha && d->dyn_sums &&
-                      ((uintptr_t)d->dyn_g % 16) == 0 && ((uintptr_t)d->dyn_y % 16) == 0,
-                  "conv_wgrad: dyn_* (dY formed on load) is not implemented for this pass (ask ctseg_wgrad_dy_norm_ok)");
-  else
-    CTSEG_REQUIRE(d->dyn_col0 == 0, "conv_wgrad: dyn_col0 without dyn_g");
-  if (d->in_mean_rstd != nullptr)
-    CTSEG_REQUIRE(halo && wgrad_halo_in_norm_ok(d) && d->in_alpha != nullptr,
-                  "conv_wgrad: in_mean_rstd (normalise the operand on load) is not implemented for this pass (ask ctseg_wgrad_in_norm_ok)");
-  CTSEG_REQUIRE((d->d_ld % EPC == 0 || halo) && ((uintptr_t)d->dy % 16) == 0, "conv_wgrad: dy must be 16-byte chunked");
-  CTSEG_REQUIRE(halo || pass == WgradPass::UP || d->dtype != CTSEG_BF16 || d->g_ld != 12 || d->Cg != 16,
-                "conv_wgrad: 12-wide rows need an LDS-halo kernel");
-  const int bnw = ctseg_wgrad_tile_cols(d->Cn);
+  why = wgrad_refusal(d, pass);
+  CTSEG_REQUIRE(why == nullptr, "%s", why);
+  const WgradGenericTile gt = wgrad_generic_tile(d);
+  const int bnw = gt.bnw;
   const int ktot = d->ntaps * d->Cg;
   hipStream_t st = (hipStream_t)stream;
   switch (pass) {
@@ -651,9 +703,8 @@ extern "C" int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream) {
   a.sz = step % d->Zr; step /= d->Zr;
   a.sy = step % d->Yr; a.sx = step / d->Yr;
   for (int i = 0; i < CTSEG_MAX_TAPS; ++i) a.taps[i] = i < d->ntaps ? d->taps[i] : 0;
-  const bool smallc = wgrad_small_operand(d);
-  if (d->dtype == CTSEG_F32) { if (smallc) launch_wgrad<float, true>(a, st); else launch_wgrad<float, false>(a, st); }
-  else { if (smallc) launch_wgrad<BF16, true>(a, st); else launch_wgrad<BF16, false>(a, st); }
+  if (d->dtype == CTSEG_F32) { if (gt.smallc) launch_wgrad<float, true>(a, bnw, st); else launch_wgrad<float, false>(a, bnw, st); }
+  else { if (gt.smallc) launch_wgrad<BF16, true>(a, bnw, st); else launch_wgrad<BF16, false>(a, bnw, st); }
   CTSEG_LAUNCH_CHECK("conv_wgrad");
   return 0;
 }

@@ -635,34 +635,56 @@ bool wgrad_halo_eligible(const ctseg_wgrad_desc* d) {
   return true;
 }
 
-static bool wgrad_head2(const ctseg_wgrad_desc* d);
+// Which kernel of this file serves an eligible descriptor, and its instantiation: the one place that decides it.  The launcher
+// dispatches on it; the grid / slab sizing, ctseg_wgrad_in_norm_ok and ctseg_wgrad_pass_name report it.
+enum class WhKernel { HALO, HEAD, HEAD2 };      // conv_wgrad_halo_kernel<a, b, .> (plane bytes), conv_wgrad_head_kernel / head2<a, b> (8-byte pieces per row)
+struct WgradHaloVariant { WhKernel k; int a, b; };
+static WgradHaloVariant wgrad_halo_variant(const ctseg_wgrad_desc* d) {
+  const int vb = d->Cg * 2, db = ((d->Cn + 15) / 16) * 32;
+  if (!(vb == 32 && db == 32 && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16))) return {WhKernel::HALO, vb, db};
+  bool canonical = true;
+  for (int j = 0; j < 27; ++j) {      // the x-column reuse indexes taps as dx * 9 + (dy, dz): canonical order only
+    const int tp = d->taps[j];
+    if ((int)(int8_t)(tp & 0xff) != j / 9 - 1 || (int)(int8_t)((tp >> 8) & 0xff) != (j / 3) % 3 - 1 || (int)(int8_t)((tp >> 16) & 0xff) != j % 3 - 1)
+      canonical = false;
+  }
+  return {canonical ? WhKernel::HEAD2 : WhKernel::HEAD, d->g_ld / 4, d->d_ld / 4};
+}
+
 static int wgrad_halo_grid(const ctseg_wgrad_desc* d) {
   const int tiles = ((d->Xr + 3) / 4) * ((d->Yr + 7) / 8) * ((d->Zr + 7) / 8) * d->N;
-  const int vb = d->Cg * 2, db = ((d->Cn + 15) / 16) * 32;
+  const WgradHaloVariant v = wgrad_halo_variant(d);
   // more workgroups per CU than this measured no faster with the single staging buffer (0.245 / 0.250 / 0.255 ms at 1 / 2 / 3
   // per CU for the 32->32 layer); the smaller LDS footprint is kept for what it leaves to the main stream's kernels
-  int per_cu = (vb + db <= 64) ? 2 : 1;
-  if (vb == 32 && db == 32 && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16))
-    per_cu = wgrad_head2(d) ? 1 : 4;      // 27 KB of LDS, 128 registers: four 4-wave or two 8-wave workgroups per CU would fit.
+  int per_cu = (v.a + v.b <= 64) ? 2 : 1;
+  if (v.k != WhKernel::HALO)
+    per_cu = v.k == WhKernel::HEAD2 ? 1 : 4;      // 27 KB of LDS, 128 registers: four 4-wave or two 8-wave workgroups per CU would fit.
   // ONE 8-wave workgroup per CU for the head kernel: alone it is slower that way (0.43 -> 0.50 ms), inside the step — it runs on the
   // side stream beside the main stream's HBM-bound head passes — faster: 9.94 / 9.90 -> 9.86 / 9.82 ms/step (same box, round 2)
   if (const char* e = getenv("CTSEG_WH_PER_CU")) per_cu = atoi(e);
   return persistent_grid(CTSEG_NUM_CU * per_cu, tiles);
 }
 
-static bool wgrad_head2(const ctseg_wgrad_desc* d) {
-  const int vb = d->Cg * 2, db = ((d->Cn + 15) / 16) * 32;
-  for (int j = 0; j < 27; ++j) {      // the x-column reuse indexes taps as dx * 9 + (dy, dz): canonical order only
-    const int tp = d->taps[j];
-    if ((int)(int8_t)(tp & 0xff) != j / 9 - 1 || (int)(int8_t)((tp >> 8) & 0xff) != (j / 3) % 3 - 1 || (int)(int8_t)((tp >> 16) & 0xff) != j % 3 - 1)
-      return false;
-  }
-  return vb == 32 && db == 32 && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16);
-}
+static bool wgrad_head2(const ctseg_wgrad_desc* d) { return wgrad_halo_variant(d).k == WhKernel::HEAD2; }
 
 bool wgrad_halo_in_norm_ok(const ctseg_wgrad_desc* d) { return wgrad_halo_eligible(d) && wgrad_head2(d) && d->N <= WH_NRM_MAXN && d->in_norm_C <= 12; }
 
 int wgrad_halo_slabs(const ctseg_wgrad_desc* d) { return wgrad_head2(d) ? 2 * wgrad_halo_grid(d) : wgrad_halo_grid(d); }
+
+// name of the kernel launch_wgrad_halo runs (ctseg_wgrad_pass_name); a variant outside the table has no kernel: NULL
+const char* wgrad_halo_name(const ctseg_wgrad_desc* d) {
+  static const struct { WhKernel k; int a, b; const char* name; } NAMES[] = {
+      {WhKernel::HEAD2, 3, 3, "x-column head 12/12"}, {WhKernel::HEAD2, 3, 4, "x-column head 12/16"},
+      {WhKernel::HEAD2, 4, 3, "x-column head 16/12"}, {WhKernel::HEAD2, 4, 4, "x-column head 16/16"},
+      {WhKernel::HEAD, 3, 3, "head 12/12"},           {WhKernel::HEAD, 3, 4, "head 12/16"},
+      {WhKernel::HEAD, 4, 3, "head 16/12"},           {WhKernel::HEAD, 4, 4, "head 16/16"},
+      {WhKernel::HALO, 32, 32, "halo 32x32"},         {WhKernel::HALO, 32, 64, "halo 32x64"},
+      {WhKernel::HALO, 64, 32, "halo 64x32"},         {WhKernel::HALO, 64, 64, "halo 64x64"}};
+  const WgradHaloVariant v = wgrad_halo_variant(d);
+  for (const auto& e : NAMES)
+    if (e.k == v.k && e.a == v.a && e.b == v.b) return e.name;
+  return nullptr;
+}
 
 void launch_wgrad_halo(const ctseg_wgrad_desc* d, hipStream_t st) {
   WgradHaloArgs a;
@@ -681,21 +703,21 @@ void launch_wgrad_halo(const ctseg_wgrad_desc* d, hipStream_t st) {
     a.delta[j] = v;
   }
   const int total = a.tiles * d->N, grid = wgrad_halo_grid(d);
-  const int vb = d->Cg * 2, db = ((d->Cn + 15) / 16) * 32;
-  if (vb == 32 && db == 32 && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16)) {
+  const WgradHaloVariant v = wgrad_halo_variant(d);
+  if (v.k != WhKernel::HALO) {
     const int xsb = (int)((int64_t)d->Xi * d->Yi * d->Zi * d->g_ld * 2), dsb = (int)((int64_t)d->Xi * d->Yi * d->Zi * d->d_ld * 2);
-    const bool v2 = wgrad_head2(d);
+    const bool v2 = v.k == WhKernel::HEAD2;
 #define WH_GO(NX, ND)                                                                                                       \
   do {                                                                                                                      \
     if (v2) hipLaunchKernelGGL((conv_wgrad_head2_kernel<NX, ND>), dim3(grid), dim3(512), 0, st, a, total, xsb, dsb);    \
     else hipLaunchKernelGGL((conv_wgrad_head_kernel<NX, ND>), dim3(grid), dim3(256), 0, st, a, total, xsb, dsb);             \
   } while (0)
-    if (d->g_ld == 12) { if (d->d_ld == 12) WH_GO(3, 3); else WH_GO(3, 4); }
-    else { if (d->d_ld == 12) WH_GO(4, 3); else WH_GO(4, 4); }
+    if (v.a == 3) { if (v.b == 3) WH_GO(3, 3); else WH_GO(3, 4); }
+    else { if (v.b == 3) WH_GO(4, 3); else WH_GO(4, 4); }
 #undef WH_GO
-  } else if (vb == 32 && db == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<32, 32, 4>), dim3(grid), dim3(256), 0, st, a, total);
-  else if (vb == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<32, 64, 4>), dim3(grid), dim3(256), 0, st, a, total);
-  else if (db == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, 32, 4>), dim3(grid), dim3(256), 0, st, a, total);
+  } else if (v.a == 32 && v.b == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<32, 32, 4>), dim3(grid), dim3(256), 0, st, a, total);
+  else if (v.a == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<32, 64, 4>), dim3(grid), dim3(256), 0, st, a, total);
+  else if (v.b == 32) hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, 32, 4>), dim3(grid), dim3(256), 0, st, a, total);
   else hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, 64, 8>), dim3(grid), dim3(512), 0, st, a, total);
 }
 

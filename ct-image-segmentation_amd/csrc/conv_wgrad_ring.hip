@@ -450,6 +450,11 @@ static int wring_kind(const ctseg_wgrad_desc* d) {
 
 bool wgrad_ring_eligible(const ctseg_wgrad_desc* d) { return wring_kind(d) != 0; }
 
+const char* wgrad_ring_name(const ctseg_wgrad_desc* d) {
+  static const char* const NAMES[] = {nullptr, "ring 256x256", "ring 256x128", "ring 512x64"};
+  return NAMES[wring_kind(d)];
+}
+
 // workgroups one slab (sample x split) takes; bytes a workgroup stages per 32 rows
 int wgrad_ring_wgs_per_slab(const ctseg_wgrad_desc* d, int32_t* stage_bytes) {
   const int kind = wring_kind(d);

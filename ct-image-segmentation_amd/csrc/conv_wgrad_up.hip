@@ -234,6 +234,11 @@ static int wgrad_up_grid(const ctseg_wgrad_desc* d) {
 
 int wgrad_up_slabs(const ctseg_wgrad_desc* d) { return wgrad_up_grid(d); }
 
+// row width GW of conv_wgrad_up_kernel<GW> for an eligible descriptor (12 or 16): the launcher and ctseg_wgrad_pass_name use it
+static int wgrad_up_width(const ctseg_wgrad_desc* d) { return d->g_ld == 12 ? 12 : 16; }
+
+const char* wgrad_up_name(const ctseg_wgrad_desc* d) { return wgrad_up_width(d) == 12 ? "up 12" : "up 16"; }
+
 void launch_wgrad_up(const ctseg_wgrad_desc* d, hipStream_t st) {
   WgradUpArgs a;
   a.fine = (const char*)d->in; a.coarse = (const char*)d->dy; a.ws = d->ws;
@@ -243,7 +248,7 @@ void launch_wgrad_up(const ctseg_wgrad_desc* d, hipStream_t st) {
   a.tiles = ((d->Xr + WU_TX - 1) / WU_TX) * a.tyn * a.tzn;
   a.fine_sample_bytes = (int)((int64_t)d->Xi * d->Yi * d->Zi * d->g_ld * 2);
   a.coarse_sample_bytes = (int)((int64_t)d->Xr * d->Yr * d->Zr * 128);
-  if (d->g_ld == 12) hipLaunchKernelGGL(conv_wgrad_up_kernel<12>, dim3(wgrad_up_grid(d)), dim3(256), 0, st, a, a.tiles * d->N);
+  if (wgrad_up_width(d) == 12) hipLaunchKernelGGL(conv_wgrad_up_kernel<12>, dim3(wgrad_up_grid(d)), dim3(256), 0, st, a, a.tiles * d->N);
   else hipLaunchKernelGGL(conv_wgrad_up_kernel<16>, dim3(wgrad_up_grid(d)), dim3(256), 0, st, a, a.tiles * d->N);
 }
 

@@ -144,6 +144,9 @@ int ctseg_conv_igemm(const ctseg_conv_desc* d, void* stream);
 /* Weight gradient: R[tap*Cg+a][b] = sum_rows in[row*sin+d(tap)][a] * dy[row][b]; row K=ntaps*Cg of R is
  * sum_rows dy[row][b] (the bias gradient).  Written as `splits` fp32 slabs [N*splits][kpad_w][cn_pad]
  * into `ws`, then ctseg_conv_wgrad_reduce sums them in fixed order (deterministic) into torch layout.
+ * `ws` need not be initialised: of each of the ctseg_conv_wgrad_slabs() slabs the pass writes every element the reduce reads
+ * (rows [0, ntaps*Cg] x columns [0, roundup(Cn, 4)), pad channels, the bias row, an empty last split and the slabs of a capped
+ * persistent grid included), so a recorded plan may replay over its own stale slabs (tests/test_gpu_wgrad.py poisons them).
  * Replaces autograd's conv weight/bias backward for the same modules as above. */
 typedef struct ctseg_wgrad_desc {
   int32_t struct_size;   /* sizeof(ctseg_wgrad_desc) of the caller's header (ABI 2) */
@@ -196,6 +199,15 @@ int ctseg_wgrad_narrow_ok(const ctseg_wgrad_desc* d);
 int ctseg_wgrad_in_norm_ok(const ctseg_wgrad_desc* d);
 /* 1 when this weight-gradient pass can form the upper columns of dY on load (dyn_*): the single-channel stride-2 first layer */
 int ctseg_wgrad_dy_norm_ok(const ctseg_wgrad_desc* d);
+/* Name of the kernel the launch of this descriptor would run, precise to the instantiation: "x-column head GW/DW" and "head GW/DW"
+ * (16 -> <= 16 channels; GW / DW = row widths 12 or 16 of `in` / `dy`; "head" when the taps are not in canonical order),
+ * "halo 32x32" / "halo 32x64" / "halo 64x32" / "halo 64x64" (bytes per voxel of the gathered / dY LDS planes), "up 12" / "up 16",
+ * "stem 16" .. "stem 64", "stem 32 dyn" / "stem 64 dyn", "ring 256x256" / "ring 256x128" / "ring 512x64", or "generic 16" ..
+ * "generic 128" (column tile) with " element-wise" appended when the gathered operand is staged element by element.  Host-only like
+ * the sizing queries (pointers select the kernel by their alignment and by being set, nothing is dereferenced); a static string,
+ * NULL for a descriptor the queries reject and for dyn_g / in_mean_rstd on a pass that refuses them.  CTSEG_NO_WGRAD_UP and
+ * CTSEG_WGRAD_RING=0 are honoured as the launch honours them. */
+const char* ctseg_wgrad_pass_name(const ctseg_wgrad_desc* d);
 int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream);
 /* dw[(b*A + a)*T + t] = sum_s ws[s][t*Astride + a][col0 + b]  for a < A, b < nb;
  * db[b] = sum_s ws[s][T*Astride][col0+b] (db may be NULL).  Astride = the pass's (padded) Cg. */

@@ -85,11 +85,12 @@ class ConvPassDriver:
     caller names (ctseg_conv_pass_name of the recorded descriptor) BEFORE it runs: a shape that an eligibility change moved to
     another kernel fails instead of passing on something else."""
 
-    def __init__(self, mod, dt, device, extra_params=(), cg=None):
-        """cg: gathered channel stride of the input when it is not the default (16 for a <= 12-channel input in 12-wide rows)"""
+    def __init__(self, mod, dt, device, extra_params=(), cg=None, dims=3, guard_params=()):
+        """cg: gathered channel stride of the input when it is not the default (16 for a <= 12-channel input in 12-wide rows);
+        guard_params: a (before, after) pair of parameters laid around the layer's own in the flat buffers"""
         self.mod, self.dt, self.device = mod, dt, device
         transposed = isinstance(mod, (torch.nn.ConvTranspose2d, torch.nn.ConvTranspose3d))
-        self.plan = MiniPlan([mod.weight, mod.bias, *extra_params], device, dt, 3)
+        self.plan = MiniPlan([*guard_params[:1], mod.weight, mod.bias, *guard_params[1:], *extra_params], device, dt, dims)
         e = nat.epc(dt)
         cin = mod.in_channels
         self.layer = GemmLayer(self.plan, "t", transposed, mod.kernel_size[0], mod.stride[0], cin,
@@ -124,6 +125,92 @@ class ConvPassDriver:
         out = self.layer.emit_dgrad(ga, **extras)
         self._go(family)
         return out
+
+
+GRAD_SENTINEL = -12345.0
+
+
+class WgradPassDriver(ConvPassDriver):
+    """The weight-gradient pass of one GemmLayer (emit_wgrad: the pass, its slab reduce, the column sum of a transposed layer's
+    bias), checked by name (ctseg_wgrad_pass_name of the recorded descriptor) BEFORE anything runs.  The flat gradient buffer is
+    filled with a sentinel first and the layer's parameters lie between two guard parameters in it, so a write outside the
+    layer's weight and bias views shows; the slab buffer the descriptor records can be poisoned, and the recorded program can be
+    run again over its own stale slabs (replay) after new operands were copied into the same tensors."""
+
+    def __init__(self, mod, dt, device, cg=None, extra_params=()):
+        self.guards = (torch.nn.Parameter(torch.zeros(8)), torch.nn.Parameter(torch.zeros(8)))
+        super().__init__(mod, dt, device, extra_params=extra_params, cg=cg, dims=3 if mod.weight.ndim == 5 else 2,
+                         guard_params=self.guards)
+        self.prog = self.ws = None
+
+    def act(self, x, ld=None):
+        """operand with rows ``ld`` wide (default: 16-byte chunked)"""
+        return to_cl(x, self.dt, self.device, ld=ld)
+
+    def record(self, family, xa, ga, splits=None, **extras):
+        """records emit_wgrad(xa, ga, **extras) and asserts the family; ``splits`` overrides the mirror's split rule (the C ABI takes
+        any count: an empty last split is not reachable through GemmLayer._wgrad_splits)"""
+        if splits is not None:
+            self.layer._wgrad_splits = lambda *a: splits
+        n0 = len(self.plan.prog)
+        self.layer.emit_wgrad(xa, ga, **extras)
+        idx = [i for i in range(n0, len(self.plan.prog)) if self.plan.prog[i][0] == "ctseg_conv_wgrad"]
+        assert len(idx) == 1
+        self.desc = self.plan.prog[idx[0]][2][0]
+        name = nat.lib().ctseg_wgrad_pass_name(self.desc)
+        assert name is not None and name.decode() == family, (name, family)
+        self.ws = [k for a, k in self.plan._keep if a and a[0] is self.desc][0][2]
+        assert self.ws.data_ptr() == self.desc.ws
+        return self.desc
+
+    def go(self, poison=None):
+        """fills the flat gradient with the sentinel (and the slabs with ``poison``), runs what is recorded
+        -> (gw, gb, desc, flat_g) on the CPU"""
+        if self.plan.prog:
+            self.prog = list(self.plan.prog)
+            self.plan.prog = []
+            self.plan.packer.refresh(force=True)
+        if poison is not None:
+            self.ws.fill_(poison)
+        st = self.plan.store
+        st.flat_g.fill_(GRAD_SENTINEL)
+        Plan.run(self.prog, nat.stream_ptr())
+        torch.cuda.synchronize()
+        return (st.grad_view(self.mod.weight).cpu().clone(), st.grad_view(self.mod.bias).cpu().clone(), self.desc, st.flat_g.cpu().clone())
+
+    def outside_untouched(self, flat_g):
+        """no entry of the flat gradient outside the layer's weight and bias views changed from the sentinel"""
+        return self.outside_untouched_but(flat_g)
+
+    def outside_untouched_but(self, flat_g, *also):
+        """the same, with further parameters (``also``) whose gradient the recorded program may write"""
+        st = self.plan.store
+        keep = torch.ones(flat_g.numel(), dtype=torch.bool)
+        for p in (self.mod.weight, self.mod.bias, *also):
+            keep[st.off(p):st.off(p) + p.numel()] = False
+        return int(keep.sum()) >= 16 and bool((flat_g[keep] == GRAD_SENTINEL).all())
+
+
+def norm_for(drv, alpha, N, C, dims, seed, eps=1e-5):
+    """a _NormAct with a real forward output y (bf16-rounded, no element within 1e-3 of its mean in units of the standard
+    deviation: the sign of xhat decides a PReLU branch, and float32 and float64 must agree on it) and its real (mean, rstd)
+    -> (norm, y, mean, rstd); mean / rstd: the float32 table values as float64, shaped (N, C, 1, 1, 1)"""
+    def rounded(t):
+        return t.detach().to(torch.bfloat16).float()
+    torch.manual_seed(seed)
+    y = rounded(torch.randn(N, C, *dims) * 1.3 + 0.4)
+    mean = y.double().mean((2, 3, 4), keepdim=True)
+    rstd = (y.double().var((2, 3, 4), unbiased=False, keepdim=True) + eps).rsqrt()
+    mr32 = torch.stack([mean.float().reshape(N, C), rstd.float().reshape(N, C)], -1).contiguous()
+    m32, r32 = mr32[..., 0].double().reshape(N, C, 1, 1, 1), mr32[..., 1].double().reshape(N, C, 1, 1, 1)
+    for _ in range(3):
+        near = ((y.double() - m32) * r32).abs() < 1e-3
+        y = rounded(torch.where(near, y + 0.25, y))
+    assert float(((y.double() - m32) * r32).abs().min()) >= 1e-3
+    na = _NormAct(drv.plan, alpha)
+    na.y = to_cl(y, nat.BF16, drv.device)
+    na.mr = mr32.to(drv.device)
+    return na, y, m32, r32
 
 
 def rel_err(a, b):

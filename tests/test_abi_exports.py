@@ -226,3 +226,169 @@ def test_conv_pass_name_follows_the_extras_and_rejects_bad_descriptors(monkeypat
     bad = _conv_desc(nat.BF16, 16, 16, (9, 11, 13))
     bad.dtype = nat.U8
     assert L.ctseg_conv_pass_name(ctypes.byref(bad)) is None
+
+
+def _wgrad_desc(dt, cg, cn, rows, sin=1, g_ld=None, d_ld=None, k=3, dims=3, N=2):
+    """a hand-filled weight-gradient descriptor (no memory behind the pointers: null `in` / `dy` are 16-byte aligned).  For a
+    transposed convolution the caller passes the gathered side (dOut: cg = its channel stride) and cn = the layer's input channels"""
+    from capstone_amd.engine import classes_plain
+    L = nat.lib()
+    d = nat.WgradDesc()
+    d.dtype, d.N = dt, N
+    d.Xr, d.Yr, d.Zr = rows
+    d.Xi, d.Yi, d.Zi = [r * sin if i < dims else 1 for i, r in enumerate(rows)]
+    d.Cg, d.Cn, d.g_ld, d.d_ld, d.sin = cg, cn, g_ld or cg, d_ld or -(-cn // nat.epc(dt)) * nat.epc(dt), sin
+    taps = classes_plain(k, dims, lambda t: t - (k - 1) // 2)[0][1]
+    d.ntaps = len(taps)
+    for j, (_, off) in enumerate(taps):
+        d.taps[j] = off
+    bnw = L.ctseg_wgrad_tile_cols(cn)
+    d.splits, d.kpad_w, d.cn_pad = 1, -(-(d.ntaps * cg + 1) // 128) * 128, -(-cn // bnw) * bnw
+    return d
+
+
+def _wgrad_name(d):
+    got = nat.lib().ctseg_wgrad_pass_name(ctypes.byref(d))
+    return None if got is None else got.decode()
+
+
+B, F = nat.BF16, nat.F32
+WGRAD_NAME_CASES = [
+    # (name, dtype, Cg, Cn, rows, keyword arguments of _wgrad_desc)
+    ("x-column head 12/12", B, 16, 10, (5, 9, 13), dict(g_ld=12, d_ld=12)),
+    ("x-column head 12/16", B, 16, 10, (5, 9, 13), dict(g_ld=12, d_ld=16)),
+    ("x-column head 16/12", B, 16, 10, (5, 9, 13), dict(g_ld=16, d_ld=12)),
+    ("x-column head 16/16", B, 16, 16, (5, 9, 13), {}),
+    ("x-column head 16/16", B, 16, 16, (5, 9, 4), {}),                       # Z = 4: the eligibility edge
+    ("generic 16", B, 16, 16, (5, 9, 3), {}),                                # Z = 3: below it
+    ("halo 32x32", B, 16, 16, (5, 9, 13), dict(g_ld=24)),                    # rows neither 12 nor 16 wide
+    ("halo 32x64", B, 16, 32, (5, 9, 13), {}),
+    ("halo 64x32", B, 32, 16, (5, 9, 13), {}),
+    ("halo 64x32", B, 32, 10, (5, 9, 13), {}),
+    ("halo 64x64", B, 32, 32, (5, 9, 13), {}),
+    ("halo 64x64", B, 32, 24, (4, 8, 8), dict(d_ld=32)),                     # pad columns inside a 16-column block ...
+    ("generic 32", B, 32, 24, (4, 8, 8), {}),                                # ... but dY rows of 24 are narrower than its planes
+    ("up 16", B, 16, 64, (5, 6, 9), dict(sin=2)),
+    ("up 12", B, 16, 64, (1, 2, 3), dict(sin=2, g_ld=12)),
+    ("stem 16", B, 1, 16, (4, 6, 4), dict(sin=2)),
+    ("stem 32", B, 1, 32, (4, 6, 4), dict(sin=2)),
+    ("stem 48", B, 1, 48, (5, 10, 12), dict(sin=2)),
+    ("stem 64", B, 1, 64, (5, 10, 12), dict(sin=2)),
+    ("ring 256x256", B, 64, 256, (6, 6, 6), {}),
+    ("ring 256x128", B, 32, 128, (6, 8, 4), dict(sin=2)),
+    ("ring 512x64", B, 64, 64, (7, 10, 6), {}),
+    ("generic 16", B, 8, 8, (5, 9, 13), {}),
+    ("generic 32", B, 24, 24, (5, 9, 13), {}),
+    ("generic 64", B, 48, 48, (5, 9, 13), {}),
+    ("generic 64", B, 96, 40, (5, 9, 13), {}),
+    ("generic 128", B, 24, 160, (5, 9, 13), {}),                             # (96 -> 160 in bf16 is the ring's)
+    ("ring 256x256", B, 96, 160, (5, 9, 13), {}),
+    ("generic 16", F, 8, 8, (5, 9, 13), {}),
+    ("generic 32", F, 24, 24, (5, 9, 13), {}),
+    ("generic 64", F, 48, 48, (5, 9, 13), {}),
+    ("generic 64", F, 96, 40, (5, 9, 13), {}),
+    ("generic 128", F, 96, 160, (5, 9, 13), {}),
+    ("generic 32", F, 16, 32, (5, 9, 13), {}),                               # fp32 storage: never an LDS-halo kernel
+    ("generic 32", B, 48, 24, (5, 9, 13), dict(k=1)),                        # 1x1x1
+    ("generic 32", B, 16, 32, (8, 8, 1), dict(sin=2, k=3, dims=2)),          # Conv2d 16 -> 32 s2
+    ("generic 32", B, 16, 32, (4, 4, 1), dict(sin=2, k=3, dims=2)),          # ConvTranspose2d 32 -> 16 s2: gathers dOut, 32 columns
+    ("generic 16 element-wise", B, 3, 16, (9, 13, 1), dict(dims=2)),         # Conv2d 3 -> 16: gathered rows of 6 bytes
+    ("generic 16 element-wise", F, 1, 16, (4, 6, 4), dict(sin=2)),           # fp32 first layer: not the (bf16) stem kernel
+    ("generic 16 element-wise", F, 6, 8, (5, 9, 13), {}),
+    ("generic 32 element-wise", B, 3, 32, (9, 13, 1), dict(dims=2)),
+    ("generic 64 element-wise", B, 3, 40, (9, 13, 1), dict(dims=2)),
+    ("generic 128 element-wise", F, 6, 96, (5, 9, 13), {}),
+]
+
+
+@pytest.mark.parametrize("name,dt,cg,cn,rows,kw", WGRAD_NAME_CASES,
+                         ids=[f"{c[0]} {c[2]}->{c[3]} {c[4]}" + (" fp32" if c[1] == nat.F32 else "") for c in WGRAD_NAME_CASES])
+def test_wgrad_pass_name_per_instantiation(name, dt, cg, cn, rows, kw):
+    assert _wgrad_name(_wgrad_desc(dt, cg, cn, rows, **kw)) == name
+
+
+def test_wgrad_pass_name_of_the_non_canonical_head_and_the_on_load_variants():
+    """conv_wgrad_head_kernel (the head kernel without the x-column reuse) serves only taps out of canonical order, which no layer of
+    the host mirror records: reachable by a hand-made descriptor alone.  The dyn variants of the stem kernel follow dyn_g."""
+    for gw in (12, 16):
+        for dw in (12, 16):
+            d = _wgrad_desc(B, 16, 10, (5, 9, 13), g_ld=gw, d_ld=dw)
+            d.taps[0], d.taps[26] = d.taps[26], d.taps[0]
+            assert _wgrad_name(d) == f"head {gw}/{dw}"
+            assert nat.lib().ctseg_wgrad_in_norm_ok(ctypes.byref(d)) == 0
+    for cn in (32, 64):
+        d = _wgrad_desc(B, 1, cn, (4, 6, 4), sin=2, d_ld=cn // 2)
+        d.dyn_col0, d.dyn_g, d.dyn_y, d.dyn_g_ld, d.dyn_y_ld = cn // 2, 1 << 20, 1 << 21, cn // 2, cn // 2
+        d.dyn_mean_rstd = d.dyn_alpha = d.dyn_sums = 1 << 22
+        assert nat.lib().ctseg_wgrad_dy_norm_ok(ctypes.byref(d)) == 1
+        assert _wgrad_name(d) == f"stem {cn} dyn"
+        d.N = 9                                     # the launch refuses it: no name
+        assert _wgrad_name(d) is None
+    d = _wgrad_desc(B, 1, 48, (4, 6, 4), sin=2, d_ld=24)
+    d.dyn_col0, d.dyn_g, d.dyn_y, d.dyn_g_ld, d.dyn_y_ld = 24, 1 << 20, 1 << 21, 24, 24
+    assert _wgrad_name(d) is None
+    d = _wgrad_desc(B, 1, 32, (4, 6, 4), sin=2)
+    d.dyn_col0 = 16                                 # dyn_col0 without dyn_g
+    assert _wgrad_name(d) is None
+    # in_mean_rstd: the x-column head kernel only
+    d = _wgrad_desc(B, 16, 10, (5, 9, 13), g_ld=12, d_ld=12)
+    d.in_mean_rstd, d.in_alpha, d.in_norm_C = 1 << 20, 1 << 21, 10
+    assert _wgrad_name(d) == "x-column head 12/12"
+    d = _wgrad_desc(B, 32, 32, (5, 9, 13))
+    d.in_mean_rstd, d.in_alpha, d.in_norm_C = 1 << 20, 1 << 21, 10
+    assert _wgrad_name(d) is None
+    # what the launch refuses beyond the queries has no name either (the two share wgrad_refusal)
+    d = _wgrad_desc(B, 16, 10, (5, 9, 13), g_ld=12, d_ld=12)
+    d.in_mean_rstd, d.in_norm_C = 1 << 20, 10       # no in_alpha
+    assert _wgrad_name(d) is None
+    d = _wgrad_desc(B, 1, 32, (4, 6, 4), sin=2, d_ld=16)
+    d.dyn_col0, d.dyn_g, d.dyn_y, d.dyn_g_ld, d.dyn_y_ld = 16, 1 << 20, 1 << 21, 16, 16      # no table pointers
+    assert _wgrad_name(d) is None
+    d.dyn_mean_rstd = d.dyn_alpha = d.dyn_sums = 1 << 22
+    d.dyn_g = (1 << 20) + 8                         # dyn_g not 16-byte aligned
+    assert _wgrad_name(d) is None
+    d = _wgrad_desc(B, 48, 48, (5, 9, 13), d_ld=52)  # dY rows not 16-byte chunked
+    assert _wgrad_name(d) is None
+    d = _wgrad_desc(B, 48, 48, (5, 9, 13))
+    d.splits = 0
+    assert _wgrad_name(d) is None
+
+
+def test_wgrad_pass_name_honours_the_switches_and_rejects_bad_descriptors(monkeypatch):
+    L = nat.lib()
+    up = _wgrad_desc(B, 16, 64, (5, 6, 9), sin=2)
+    up12 = _wgrad_desc(B, 16, 64, (5, 6, 9), sin=2, g_ld=12)
+    ring = _wgrad_desc(B, 64, 256, (6, 6, 6))
+    assert (_wgrad_name(up), _wgrad_name(up12), _wgrad_name(ring)) == ("up 16", "up 12", "ring 256x256")
+    monkeypatch.setenv("CTSEG_NO_WGRAD_UP", "1")
+    assert _wgrad_name(up) == "generic 64"
+    assert _wgrad_name(up12) is None                # 12-wide rows on the generic kernel: the launch refuses
+    assert L.ctseg_wgrad_narrow_ok(ctypes.byref(up12)) == 0
+    monkeypatch.delenv("CTSEG_NO_WGRAD_UP")
+    monkeypatch.setenv("CTSEG_WGRAD_RING", "0")
+    assert _wgrad_name(ring) == "generic 128"
+    assert _wgrad_name(_wgrad_desc(B, 64, 64, (7, 10, 6))) == "generic 64"
+    monkeypatch.setenv("CTSEG_WGRAD_RING", "1")
+    assert _wgrad_name(ring) == "ring 256x256"
+    monkeypatch.delenv("CTSEG_WGRAD_RING")
+    assert _wgrad_name(nat.WgradDesc()) is None                                # empty dims
+    assert L.ctseg_wgrad_pass_name(None) is None
+    bad = _wgrad_desc(B, 16, 16, (5, 9, 13))
+    bad.struct_size -= 8
+    assert _wgrad_name(bad) is None
+    bad = _wgrad_desc(B, 16, 16, (5, 9, 13))
+    bad.dtype = nat.F16                                                        # no weight-gradient kernels for IEEE half
+    assert _wgrad_name(bad) is None
+    bad = _wgrad_desc(B, 16, 16, (5, 9, 13))
+    bad.ntaps = 28
+    assert _wgrad_name(bad) is None
+
+
+def test_wgrad_reduce_batch_ok_conditions():
+    L = nat.lib()
+    ok = L.ctseg_conv_wgrad_reduce_batch_ok
+    assert ok(4096, 16, 0, 10) == 1 and ok(4096, 32, 16, 14) == 1
+    assert ok(4096, 16, 2, 10) == 0                 # col0 % 4
+    assert ok(4096, 18, 0, 10) == 0                 # cn_pad % 4
+    assert ok(4100, 16, 0, 10) == 0                 # ws at a 4-byte offset
+    assert ok(4096, 16, 8, 10) == 0                 # col0 + roundup(nb, 4) > cn_pad

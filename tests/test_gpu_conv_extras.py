@@ -62,7 +62,7 @@ from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd._native import BF16, F32  # noqa: E402
 from capstone_amd.engine import Act, GemmLayer, SplitAct, rup  # noqa: E402
 from capstone_amd.plan import _NormAct  # noqa: E402
-from helpers import ConvPassDriver, MiniPlan, from_cl, rel_err, to_cl  # noqa: E402
+from helpers import ConvPassDriver, MiniPlan, from_cl, norm_for, rel_err, to_cl  # noqa: E402
 
 DEV = "cuda:0"
 TOL = {F32: 2e-5, BF16: 2.5e-2}
@@ -397,22 +397,7 @@ def test_split_output_is_refused_where_the_family_cannot():
 
 # ---- backward statistics -----------------------------------------------------------------------------------------------------
 def _norm_for(drv, alpha, N, C, dims, seed):
-    """a _NormAct with a real forward output y (storage-rounded, no element within 1e-3 of its mean in units of the standard
-    deviation: the sign of xhat decides a PReLU branch, and float32 and float64 must agree on it) and its real (mean, rstd)"""
-    torch.manual_seed(seed)
-    y = _rounded(torch.randn(N, C, *dims) * 1.3 + 0.4, BF16)
-    mean = y.double().mean((2, 3, 4), keepdim=True)
-    rstd = (y.double().var((2, 3, 4), unbiased=False, keepdim=True) + EPS).rsqrt()
-    mr32 = torch.stack([mean.float().reshape(N, C), rstd.float().reshape(N, C)], -1).contiguous()
-    m32, r32 = mr32[..., 0].double().reshape(N, C, 1, 1, 1), mr32[..., 1].double().reshape(N, C, 1, 1, 1)
-    for _ in range(3):
-        near = ((y.double() - m32) * r32).abs() < 1e-3
-        y = _rounded(torch.where(near, y + 0.25, y), BF16)
-    assert float(((y.double() - m32) * r32).abs().min()) >= 1e-3
-    na = _NormAct(drv.plan, alpha)
-    na.y = to_cl(y, BF16, DEV)
-    na.mr = mr32.to(DEV)
-    return na, y, m32, r32
+    return norm_for(drv, alpha, N, C, dims, seed, eps=EPS)      # (shared with the weight-gradient tests: helpers.norm_for)
 
 
 def _bst_reference(g, y, m, r, alpha, f32):
