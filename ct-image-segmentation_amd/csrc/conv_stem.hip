@@ -8,6 +8,7 @@
 //   forward : out[v][n] = bias[n] + sum_t in[2v + t - 1] * W[n][t]            (+ InstanceNorm partial sums per workgroup)
 //   wgrad   : R[t][b] = sum_v in[2v + t - 1] * dy[v][b],  R[27][b] = sum_v dy[v][b]   -> 4 slabs per workgroup
 #include "conv_common.h"
+#include "wgrad_common.h"
 
 #ifndef STEM_ABL
 #define STEM_ABL 0     // timing-only ablation bits (tools/ablate_stem.sh): 1 no MFMAs, 2 no LDS operand reads, 4 no patch loads, 8 no stores, 16 no stats
@@ -233,10 +234,9 @@ bool conv_stem_eligible(const ConvKArgs& a, int dtype, int nclass) {
   if (a.cls[0].ntaps != 27 || a.cls[0].kpad != 64 || a.Cn > 64 || a.Cn % 16 != 0 || a.Zr < 4) return false;
   if (a.Xi != 2 * a.Xr || a.Yi != 2 * a.Yr || a.Zi != 2 * a.Zr) return false;
   if ((int64_t)a.Xi * a.Yi * a.Zi >= (1ll << 31) || (int64_t)a.Xo * a.Yo * a.Zo * a.o_ld * 2 >= (1ll << 31)) return false;
-  for (int j = 0; j < 27; ++j) {   // taps must be the plain conv's, in torch order: offset = t - 1 per axis
+  for (int j = 0; j < 27; ++j) {   // taps must be the plain conv's, in torch order (taps_canonical_27, on the forward's own descriptor)
     const int tp = a.cls[0].taps[j];
-    const int ex = j / 9 - 1, ey = (j / 3) % 3 - 1, ez = j % 3 - 1;
-    if ((int)(int8_t)(tp & 0xff) != ex || (int)(int8_t)((tp >> 8) & 0xff) != ey || (int)(int8_t)((tp >> 16) & 0xff) != ez) return false;
+    if (tap_dx(tp) != j / 9 - 1 || tap_dy(tp) != (j / 3) % 3 - 1 || tap_dz(tp) != j % 3 - 1) return false;
   }
   return true;
 }
@@ -337,18 +337,10 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(const StemWgradArg
     }
   }
   const float dyn_al = DYN ? P.dyn_alpha[0] : 1.f;
-  auto origin = [&](int t, int& n, int& x0, int& y0, int& z0) {
-    n = t / P.G.tiles;
-    int r = t - n * P.G.tiles;
-    const int tz = r % P.G.tzn; r /= P.G.tzn;
-    const int ty = r % P.G.tyn; const int tx = r / P.G.tyn;
-    x0 = tx * 4; y0 = ty * 8; z0 = tz * 8;
-  };
   uint32_t rg[S_J];
   u32x4 rd[JD], ry[DYN ? JD / 2 : 1];
   auto gload = [&](int t) {
-    int n, x0, y0, z0;
-    origin(t, n, x0, y0, z0);
+    const auto [n, x0, y0, z0] = tile_origin<4, 8, 8>(t, P.G.tiles, P.G.tyn, P.G.tzn);
     const unsigned short* ib = reinterpret_cast<const unsigned short*>(P.in) + (((int64_t)n * P.Xi + 2 * x0) * P.Yi + 2 * y0) * P.Zi + 2 * z0;
     stg.load(ib, x0, y0, z0, P.Xi, P.Yi, P.Zi, rg);
     const int64_t tv0 = (((int64_t)n * P.Xr + x0) * P.Yr + y0) * P.Zr + z0;
@@ -381,8 +373,7 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(const StemWgradArg
   };
   // DYN: the staged (g, y) chunks of tile t -> the dY chunks the apply pass would have stored (bf16 rounding included)
   auto convert = [&](int t) {
-    int n, x0, y0, z0;
-    origin(t, n, x0, y0, z0);
+    const auto [n, x0, y0, z0] = tile_origin<4, 8, 8>(t, P.G.tiles, P.G.tyn, P.G.tzn);
     const float* tab = sDyn + (n * DYNC + (c_thr & (CT - 1)) * 8) * 4;
     f32x4 k4[8];
 #pragma unroll
@@ -445,10 +436,7 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(const StemWgradArg
 #pragma unroll
       for (int b = 0; b < CT; ++b) {
         const char* p0 = ds + b * DPL + (((x * 8) + (yb + ly)) * 8 + lz0 + tq) * 32 + tp * 8;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + 2 * 8 * 32));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        df[b] = __builtin_bit_cast(bf16x8, v);
+        df[b] = tr16_frag(p0, 2 * 8 * 32);
       }
 #pragma unroll
       for (int a = 0; a < 2; ++a) {
@@ -499,12 +487,7 @@ bool wgrad_stem_eligible(const ctseg_wgrad_desc* d) {
   if (d->Xi != 2 * d->Xr || d->Yi != 2 * d->Yr || d->Zi != 2 * d->Zr || d->Zr < 4) return false;
   if (d->kpad_w < 32 || d->cn_pad < d->Cn) return false;
   if ((int64_t)d->Xi * d->Yi * d->Zi >= (1ll << 31) || (int64_t)d->Xr * d->Yr * d->Zr * d->d_ld * 2 >= (1ll << 31)) return false;
-  for (int j = 0; j < 27; ++j) {
-    const int tp = d->taps[j];
-    const int ex = j / 9 - 1, ey = (j / 3) % 3 - 1, ez = j % 3 - 1;
-    if ((int)(int8_t)(tp & 0xff) != ex || (int)(int8_t)((tp >> 8) & 0xff) != ey || (int)(int8_t)((tp >> 16) & 0xff) != ez) return false;
-  }
-  return true;
+  return taps_canonical_27(d);
 }
 
 static int wgrad_stem_grid(const ctseg_wgrad_desc* d) {

@@ -9,22 +9,13 @@
 // sample (split-K); partial tiles go to fp32 slabs that ctseg_conv_wgrad_reduce sums in fixed order
 // (deterministic) straight into the torch weight layout.  K index ntaps*Cg is a virtual all-ones
 // gathered channel, so its row of R is the bias gradient.
-#include "ctseg_dev.h"
+#include "wgrad_common.h"
 
 namespace ctseg {
 
-struct WgradKArgs {
-  const char* in;
-  const char* dy;
-  float* ws;
-  int N, Xi, Yi, Zi, Xr, Yr, Zr;
-  int Cg, Cn, g_ld, d_ld, sin, ntaps;
-  int rows, splits, rows_per_split;
-  int kpad_w, cn_pad, d_valid;
-  int sx, sy, sz;  // mixed-radix decomposition of a 32-row step
-  int kblocks, cblocks;   // > 0: 1-D grid, workgroup -> (K block, column block, slab) decoded so that one XCD owns a slab
+struct WgradKArgs : WgradGeom {   // step: 32 rows
+  int kblocks, cblocks;   // > 0: flat grid, workgroup -> (K block, column block, slab) by slab_xcd_decode
   int addr64;             // 1: a sample of the gathered operand is >= 2 GiB (or CTSEG_WGRAD_ADDR64): 64-bit address chain per chunk
-  int taps[CTSEG_MAX_TAPS];
 };
 
 // GLDS (bf16, 16-byte-chunked gather, >= 64 columns): operands go global -> LDS directly (global_load_lds, no VGPR staging,
@@ -63,17 +54,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
   __syncthreads();
   const int wk = wave / WC, wc = wave % WC;
   const int r16 = lane & 15, q4 = lane >> 4;
-  // Workgroups go to the 8 XCDs round-robin by linear id.  With the plain 3-D grid the K / column blocks of one slab (the
-  // same rows of `in` and `dy`) land on different XCDs and each XCD's L2 fetches its own copy.  1-D grid: ids L, L+8, L+16, ...
-  // inside a group of 8 * kblocks * cblocks are the blocks of ONE slab -> same XCD, dispatched together, one fetch.
   int kblock, cblock, zslab;
   if (P.kblocks > 0) {
-    const int kc = P.kblocks * P.cblocks, G = 8 * kc;
-    const int L = blockIdx.x, g = L / G, r = L - g * G;
-    const int q = r >> 3;
-    zslab = g * 8 + (r & 7);
-    kblock = q % P.kblocks;
-    cblock = q / P.kblocks;
+    const SlabTile st = slab_xcd_decode(blockIdx.x, P.kblocks * P.cblocks);
+    zslab = st.zslab;
+    kblock = st.tile % P.kblocks;
+    cblock = st.tile / P.kblocks;
   } else {
     kblock = blockIdx.x; cblock = blockIdx.y; zslab = blockIdx.z;
   }
@@ -95,7 +81,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
   int dx = 0, dy_ = 0, dz = 0;
   if (kvalid) {
     const int tp = sTap[slot & 31];
-    dx = (int)(int8_t)(tp & 0xff); dy_ = (int)(int8_t)((tp >> 8) & 0xff); dz = (int)(int8_t)((tp >> 16) & 0xff);
+    dx = tap_dx(tp); dy_ = tap_dy(tp); dz = tap_dz(tp);
   }
   int cx[AJ], cy[AJ], cz[AJ];
 #pragma unroll
@@ -127,8 +113,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
             if (kp < ktot) {
               const int sl = kp / P.Cg, c = kp - sl * P.Cg;
               const int tp = sTap[sl & 31];
-              const int xi = cx[j] * P.sin + (int)(int8_t)(tp & 0xff), yi = cy[j] * P.sin + (int)(int8_t)((tp >> 8) & 0xff),
-                        zi = cz[j] * P.sin + (int)(int8_t)((tp >> 16) & 0xff);
+              const int xi = cx[j] * P.sin + tap_dx(tp), yi = cy[j] * P.sin + tap_dy(tp), zi = cz[j] * P.sin + tap_dz(tp);
               if ((unsigned)xi < (unsigned)P.Xi && (unsigned)yi < (unsigned)P.Yi && (unsigned)zi < (unsigned)P.Zi) {
                 const int64_t vox = ((nbase + xi) * P.Yi + yi) * P.Zi + zi;
                 const char* p = P.in + (vox * P.g_ld + c) * SZ;
@@ -159,9 +144,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
       }
       ra[j] = v;
       // advance this chunk's row by 32 (mixed radix z,y,x)
-      cz[j] += P.sz; if (cz[j] >= P.Zr) { cz[j] -= P.Zr; ++cy[j]; }
-      cy[j] += P.sy; if (cy[j] >= P.Yr) { cy[j] -= P.Yr; ++cx[j]; }
-      cx[j] += P.sx;
+      cz[j] += P.step.sz; if (cz[j] >= P.Zr) { cz[j] -= P.Zr; ++cy[j]; }
+      cy[j] += P.step.sy; if (cy[j] >= P.Yr) { cy[j] -= P.Yr; ++cx[j]; }
+      cx[j] += P.step.sx;
     }
 #pragma unroll
     for (int j = 0; j < DJ; ++j) {
@@ -184,20 +169,16 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
   const int d_chunk = (d_c32 << 1) | (d_pos & 1);
   // GLDS addressing without multiplies (the 64-bit voxel -> byte chain of gload() above is ~12 quarter-rate multiplies per chunk and
   // stage; with two chunks and 16 MFMAs per stage the address code, not the matrix pipe, bounded the kernel at ~30 % MFMA):
-  // a chunk keeps its row's SCALED coordinates (x sin, y sin, z sin), its 32-bit byte offset inside the sample and advances all
-  // four by uniform per-stage constants plus two carry corrections.  Samples >= 2 GiB keep the 64-bit chain (P.addr64).
+  // a chunk walks its rows with a RowWalk, 32 rows per stage.  Samples >= 2 GiB keep the 64-bit chain (P.addr64).
   const int gl = P.g_ld * SZ;
   const char* inb = P.in + (int64_t)n * P.Xi * P.Yi * P.Zi * gl;
-  const int zrs = P.Zr * P.sin, yrs = P.Yr * P.sin;                         // scaled extents of the row grid
-  const int szs = P.sz * P.sin, sys_ = P.sy * P.sin, sxs = P.sx * P.sin;    // scaled 32-row step
-  const int o_step = (szs + (sys_ + sxs * P.Yi) * P.Zi) * gl;               // byte step of 32 rows without carries
-  const int o_cz = P.sin * gl * (P.Zi - P.Zr), o_cy = P.sin * gl * P.Zi * (P.Yi - P.Yr);   // a z carry / a y carry
-  int aoff[AJ];
-  if constexpr (GLDS) {       // (this path keeps the rows' SCALED coordinates in cx / cy / cz)
+  const RowStepK K = row_step_k(P, gl);
+  RowWalk aw[AJ];             // (off: of THIS chunk, its tap and channel included)
+  if constexpr (GLDS) {
 #pragma unroll
     for (int j = 0; j < AJ; ++j) {
-      cx[j] *= P.sin; cy[j] *= P.sin; cz[j] *= P.sin;
-      aoff[j] = (((cx[j] + dx) * P.Yi + cy[j] + dy_) * P.Zi + cz[j] + dz) * gl + ci * SZ;
+      aw[j] = RowWalk{cx[j] * P.sin, cy[j] * P.sin, cz[j] * P.sin, 0};
+      aw[j].off = (((aw[j].x + dx) * P.Yi + aw[j].y + dy_) * P.Zi + aw[j].z + dz) * gl + ci * SZ;
     }
   }
   const bool dcol_ok = col0 + d_chunk * EPC < P.d_valid;
@@ -212,23 +193,16 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
     for (int j = 0; j < AJ; ++j) {
       const int m = mb + arow0 + j * ARS;
       const char* src = reinterpret_cast<const char*>(g_wg_zero16);
-      const int xi = cx[j] + dx, yi = cy[j] + dy_, zi = cz[j] + dz;
+      const int xi = aw[j].x + dx, yi = aw[j].y + dy_, zi = aw[j].z + dz;
       const bool inside = (unsigned)xi < (unsigned)P.Xi && (unsigned)yi < (unsigned)P.Yi && (unsigned)zi < (unsigned)P.Zi;
       if (m < mend) {
         if (kvalid) {
-          if (inside) src = P.addr64 ? P.in + ((((nbase + xi) * P.Yi + yi) * P.Zi + zi) * P.g_ld + ci) * SZ : inb + (uint32_t)aoff[j];
+          if (inside) src = P.addr64 ? P.in + ((((nbase + xi) * P.Yi + yi) * P.Zi + zi) * P.g_ld + ci) * SZ : inb + (uint32_t)aw[j].off;
         } else if (kones) {
           src = reinterpret_cast<const char*>(g_wg_one16);
         }
       }
-      cz[j] += szs;
-      const bool carry_z = cz[j] >= zrs;
-      cz[j] -= carry_z ? zrs : 0;
-      cy[j] += sys_ + (carry_z ? P.sin : 0);
-      const bool carry_y = cy[j] >= yrs;
-      cy[j] -= carry_y ? yrs : 0;
-      cx[j] += sxs + (carry_y ? P.sin : 0);
-      aoff[j] += o_step + (carry_z ? o_cz : 0) + (carry_y ? o_cy : 0);
+      aw[j].advance(K);
       __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(a + j * (ARS * PA)), 16, 0, 0);
     }
 #pragma unroll
@@ -253,17 +227,10 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
 #pragma unroll
     for (int j = 0; j < AJ; ++j) {
       const int m = mb + arow0 + j * ARS;
-      const bool ok = m < mend && kvalid && (unsigned)(cx[j] + dx) < (unsigned)P.Xi && (unsigned)(cy[j] + dy_) < (unsigned)P.Yi &&
-                      (unsigned)(cz[j] + dz) < (unsigned)P.Zi;
-      const int vo = ok ? aoff[j] : (int)0x80000000;
-      cz[j] += szs;
-      const bool carry_z = cz[j] >= zrs;
-      cz[j] -= carry_z ? zrs : 0;
-      cy[j] += sys_ + (carry_z ? P.sin : 0);
-      const bool carry_y = cy[j] >= yrs;
-      cy[j] -= carry_y ? yrs : 0;
-      cx[j] += sxs + (carry_y ? P.sin : 0);
-      aoff[j] += o_step + (carry_z ? o_cz : 0) + (carry_y ? o_cy : 0);
+      const bool ok = m < mend && kvalid && (unsigned)(aw[j].x + dx) < (unsigned)P.Xi && (unsigned)(aw[j].y + dy_) < (unsigned)P.Yi &&
+                      (unsigned)(aw[j].z + dz) < (unsigned)P.Zi;
+      const int vo = ok ? aw[j].off : (int)0x80000000;
+      aw[j].advance(K);
       raw_buffer_load_lds(rsA, (lds_u32_ptr)(a + j * (ARS * PA)), 16, vo, 0, 0, 0);
     }
 #pragma unroll
@@ -312,21 +279,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradKArgs P) {
       for (int i = 0; i < KT; ++i) {
         const char* p = GLDS ? a + mrow * PA + ((((wk * KT + i) ^ (mrow & 7)) << 5) + (pc << 1))
                              : a + mrow * PA + (((wk * KT + i) * 16 + pc) << 1);
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p + 16 * PA));
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        s16x8 t = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        af[i] = __builtin_bit_cast(bf16x8, t);
+        af[i] = tr16_frag(p, 16 * PA);
       }
 #pragma unroll
       for (int j = 0; j < CT; ++j) {
         const char* p = GLDS ? d + mrow * PD + ((((wc * CT + j) ^ (BNW == 128 ? (mrow & 7) : ((mrow >> 1) & 3))) << 5) + (pc << 1))
                              : d + mrow * PD + (((wc * CT + j) * 16 + pc) << 1);
-        s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p));
-        s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p + 16 * PD));
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        s16x8 t = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        df[j] = __builtin_bit_cast(bf16x8, t);
+        df[j] = tr16_frag(p, 16 * PD);
       }
 #pragma unroll
       for (int i = 0; i < KT; ++i)
@@ -406,15 +365,14 @@ __global__ __launch_bounds__(32 * NSUB) void wgrad_reduce_kernel(const float* __
 // the reference's network.)  col0 a multiple of 4; columns nb .. roundup(nb, 4) are pad columns of the slab (read, not written).
 // <= 32 registers (modest unrolling): a block then fits beside the persistent one-workgroup-per-CU halo kernels of the main stream
 // (2 x 240 of a SIMD's 512 registers, <= 154 KB of LDS) instead of waiting for them to end; same summation order.
-template <int LW, int NSUB>      // LW lanes x float4 along a slab row, NSUB strided sub-sums: (8, 32) for many slabs, (32, 8) for few
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) void wgrad_reduce4_kernel(const float* __restrict__ ws, int nslabs, int kpad_w, int cn_pad, int A, int AS, int T,
-                                                            int col0, int nb, float* __restrict__ dw, float* __restrict__ db) {
-  static_assert(LW * NSUB == 256, "256 threads");
-  __shared__ f32x4 s_part[NSUB][LW];
+// One body for the single call (LW a template argument) and the batched one (LW read from the job).
+__device__ __forceinline__ void reduce4_core(f32x4* s_part, int LW, int block, const float* __restrict__ ws, int nslabs, int kpad_w, int cn_pad,
+                                             int A, int AS, int T, int col0, int nb, float* __restrict__ dw, float* __restrict__ db) {
+  const int NSUB = 256 / LW;        // s_part[sub * LW + el]
   const int nb4 = (nb + 3) >> 2, total4 = (T * AS + 1) * nb4;
   const int64_t slab = (int64_t)kpad_w * cn_pad;
   const int el = threadIdx.x % LW, sub = threadIdx.x / LW;
-  const int i4 = blockIdx.x * LW + el;
+  const int i4 = block * LW + el;
   const int k = i4 / nb4, b0 = (i4 - k * nb4) * 4;
   f32x4 s = {0.f, 0.f, 0.f, 0.f};
   if (i4 < total4) {
@@ -422,12 +380,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) void wgra
 #pragma unroll 2
     for (int q = sub; q < nslabs; q += NSUB) s += *reinterpret_cast<const f32x4*>(p + q * slab);
   }
-  s_part[sub][el] = s;
+  s_part[sub * LW + el] = s;
   __syncthreads();
   if (sub == 0 && i4 < total4) {
     f32x4 t = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll 4
-    for (int q = 0; q < NSUB; ++q) t += s_part[q][el];
+    for (int q = 0; q < NSUB; ++q) t += s_part[q * LW + el];
     if (k == T * AS) {
       if (db != nullptr)
 #pragma unroll
@@ -443,44 +401,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) void wgra
   }
 }
 
-// wgrad_reduce4_kernel for a table of passes: block -> job by a scan of the (few) block0 entries, then exactly the arithmetic of
-// wgrad_reduce4_kernel<LW, 256 / LW> with LW = job.lanes (8 or 32): the same strided sub-sums, the same combine order.
+template <int LW, int NSUB>      // LW lanes x float4 along a slab row, NSUB strided sub-sums: (8, 32) for many slabs, (32, 8) for few
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) void wgrad_reduce4_kernel(const float* __restrict__ ws, int nslabs, int kpad_w, int cn_pad, int A, int AS, int T,
+                                                            int col0, int nb, float* __restrict__ dw, float* __restrict__ db) {
+  static_assert(LW * NSUB == 256, "256 threads");
+  __shared__ f32x4 s_part[256];
+  reduce4_core(s_part, LW, blockIdx.x, ws, nslabs, kpad_w, cn_pad, A, AS, T, col0, nb, dw, db);
+}
+
+// wgrad_reduce4_kernel for a table of passes: block -> job by a scan of the (few) block0 entries, then reduce4_core with
+// LW = job.lanes (8 or 32): the same strided sub-sums, the same combine order.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) void wgrad_reduce_batch_kernel(const ctseg_reduce_job* __restrict__ jobs, int n_jobs) {
   __shared__ f32x4 s_part[256];
   int j = 0;
   while (j + 1 < n_jobs && (int)blockIdx.x >= jobs[j + 1].block0) ++j;       // (uniform: scalar loads)
   const ctseg_reduce_job J = jobs[j];
-  const int LW = J.lanes, NSUB = 256 / LW;
-  const int nb4 = (J.nb + 3) >> 2, total4 = (J.T * J.Astride + 1) * nb4;
-  const int64_t slab = (int64_t)J.kpad_w * J.cn_pad;
-  const int el = threadIdx.x % LW, sub = threadIdx.x / LW;
-  const int i4 = ((int)blockIdx.x - J.block0) * LW + el;
-  const int k = i4 / nb4, b0 = (i4 - k * nb4) * 4;
-  f32x4 s = {0.f, 0.f, 0.f, 0.f};
-  if (i4 < total4) {
-    const float* p = J.ws + (int64_t)k * J.cn_pad + J.col0 + b0;
-#pragma unroll 2
-    for (int q = sub; q < J.nslabs; q += NSUB) s += *reinterpret_cast<const f32x4*>(p + q * slab);
-  }
-  s_part[sub * LW + el] = s;
-  __syncthreads();
-  if (sub == 0 && i4 < total4) {
-    f32x4 t = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (int q = 0; q < NSUB; ++q) t += s_part[q * LW + el];
-    if (k == J.T * J.Astride) {
-      if (J.db != nullptr)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (b0 + e < J.nb) J.db[b0 + e] = t[e];
-    } else {
-      const int tt = k / J.Astride, a = k - tt * J.Astride;
-      if (a < J.A)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (b0 + e < J.nb) J.dw[((int64_t)(b0 + e) * J.A + a) * J.T + tt] = t[e];
-    }
-  }
+  reduce4_core(s_part, J.lanes, (int)blockIdx.x - J.block0, J.ws, J.nslabs, J.kpad_w, J.cn_pad, J.A, J.Astride, J.T, J.col0, J.nb, J.dw, J.db);
 }
 
 bool wgrad_up_eligible(const ctseg_wgrad_desc* d);
@@ -565,7 +501,7 @@ template <typename T, bool SMALLC> static void launch_wgrad(WgradKArgs& a, int b
   dim3 grid((unsigned)kb, (unsigned)cb, (unsigned)zs);
   a.kblocks = a.cblocks = 0;
   a.addr64 = ((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * (int64_t)sizeof(T) >= ((int64_t)1 << 31) - 4096 || getenv("CTSEG_WGRAD_ADDR64") != nullptr) ? 1 : 0;
-  if (zs % 8 == 0 && kb * cb > 1) {
+  if (slab_grid_is_flat(zs, kb * cb)) {
     a.kblocks = kb; a.cblocks = cb;
     grid = dim3((unsigned)(kb * cb * zs), 1u, 1u);
   }
@@ -654,7 +590,7 @@ extern "C" int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream) {
   CTSEG_REQUIRE(d->in && d->dy && d->ws, "conv_wgrad: null pointer");
   const char* why = wgrad_refusal_early(d);
   CTSEG_REQUIRE(why == nullptr, "%s", why);
-  const int SZ = d->dtype == CTSEG_F32 ? 4 : 2, EPC = 16 / SZ;
+  const int SZ = d->dtype == CTSEG_F32 ? 4 : 2;
   const WgradPass pass = select_wgrad_pass(d);
   why = wgrad_refusal(d, pass);
   CTSEG_REQUIRE(why == nullptr, "%s", why);
@@ -692,17 +628,8 @@ extern "C" int ctseg_conv_wgrad(const ctseg_wgrad_desc* d, void* stream) {
     return 0;
   }
   WgradKArgs a;
-  a.in = (const char*)d->in; a.dy = (const char*)d->dy; a.ws = d->ws;
-  a.N = d->N; a.Xi = d->Xi; a.Yi = d->Yi; a.Zi = d->Zi; a.Xr = d->Xr; a.Yr = d->Yr; a.Zr = d->Zr;
-  a.Cg = d->Cg; a.Cn = d->Cn; a.g_ld = d->g_ld; a.d_ld = d->d_ld; a.sin = d->sin; a.ntaps = d->ntaps;
-  a.rows = (int)rows64; a.splits = d->splits; a.rows_per_split = rps;
-  a.kpad_w = d->kpad_w; a.cn_pad = d->cn_pad;
-  int dv = ((d->Cn + EPC - 1) / EPC) * EPC;
-  a.d_valid = dv < d->d_ld ? dv : d->d_ld;
-  int step = 32;
-  a.sz = step % d->Zr; step /= d->Zr;
-  a.sy = step % d->Yr; a.sx = step / d->Yr;
-  for (int i = 0; i < CTSEG_MAX_TAPS; ++i) a.taps[i] = i < d->ntaps ? d->taps[i] : 0;
+  wgrad_geom_fill(a, d, rps);
+  a.step = radix_step(32, d->Zr, d->Yr);
   if (d->dtype == CTSEG_F32) { if (gt.smallc) launch_wgrad<float, true>(a, bnw, st); else launch_wgrad<float, false>(a, bnw, st); }
   else { if (gt.smallc) launch_wgrad<BF16, true>(a, bnw, st); else launch_wgrad<BF16, false>(a, bnw, st); }
   CTSEG_LAUNCH_CHECK("conv_wgrad");

@@ -10,10 +10,11 @@
 // channels-last tensors: ds_read_b64_tr_b16 transposes 4 voxels x 16 channels per 16-lane group; the LDS images are
 // planes of 16 channels (32 B per voxel) and a k-step is 4 z-rows of 8 voxels, so each 32-lane half reads 8
 // contiguous 32-byte rows (256 B): bank-conflict free.  One fp32 slab per workgroup -> ctseg_conv_wgrad_reduce.
-#include "ctseg_dev.h"
+#include "conv_common.h"
+#include "wgrad_common.h"
 
 #ifndef WH_ABL
-#define WH_ABL 0     // timing-only ablation of conv_wgrad_head_kernel: 1 = no MFMAs, 2 = no LDS operand reads, 4 = no global loads, 8 = no LDS staging stores
+#define WH_ABL 0     // timing-only ablation of the two head kernels (tools/ablate_wgrad_head*.sh; results are garbage): 1 = no MFMAs, 2 = no LDS operand reads, 4 = no global loads, 8 = no LDS staging stores
 #endif
 
 namespace ctseg {
@@ -48,7 +49,6 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_halo_kernel(const WgradHal
   constexpr int XBYTES = PA * XPL, DBYTES = PB * DPL, BUF = XBYTES + DBYTES;
   constexpr int XCH = WH_HV * (VB / 16), DCH = WH_TV * (DBY / 16);
   constexpr int JX = (XCH + NTH - 1) / NTH, JD = (DCH + NTH - 1) / NTH;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
 
   // ONE staging buffer: the next tile's operands wait in registers (gload) while this tile is consumed and are written after
   // the barrier that ends it.  Half the LDS of a double buffer -> twice the workgroups per CU, whose phases interleave.
@@ -86,16 +86,8 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_halo_kernel(const WgradHal
     if (!w12) return *reinterpret_cast<const u32x4*>(p);
     return load_row12_chunk(p, second);
   };
-  auto origin = [&](int t, int& n, int& x0, int& y0, int& z0) {
-    n = t / P.tiles;
-    int r = t - n * P.tiles;
-    const int tz = r % P.tzn; r /= P.tzn;
-    const int ty = r % P.tyn; const int tx = r / P.tyn;
-    x0 = tx * 4; y0 = ty * 8; z0 = tz * 8;
-  };
   auto gload = [&](int t) {
-    int n, x0, y0, z0;
-    origin(t, n, x0, y0, z0);
+    const auto [n, x0, y0, z0] = tile_origin<4, 8, 8>(t, P.tiles, P.tyn, P.tzn);
     const int64_t vb = (((int64_t)n * P.X + x0) * P.Y + y0) * P.Z + z0;
     const char* xb = P.in + vb * P.g_ld * 2;
     const char* db = P.dy + vb * P.d_ld * 2;
@@ -136,21 +128,10 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_halo_kernel(const WgradHal
 
   // this lane's voxel inside a k-step for the two transposed reads: y-row 2r + (q4>>1), z = 4*(q4&1) + tq
   const int lz = 4 * (q4 & 1) + tq, ly = q4 >> 1;
-  s16x8 ones;
-  {
-    const short o = (r16 == 0) ? (short)0x3f80 : (short)0;
-    ones = s16x8{o, o, o, o, o, o, o, o};
-  }
+  const bf16x8 ones = bias_ones_frag(r16);
 
-  // tile sequence: each XCD (blockIdx % 8 shares one) owns a contiguous range of tiles and its workgroups walk it round-robin,
-  // so the tiles in flight on one XCD are neighbours and share their halos through that XCD's L2
-  int t = blockIdx.x, tstride = gridDim.x, tlast = total_tiles;
-  if ((gridDim.x & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    t = xcd * chunk + (blockIdx.x >> 3);
-    tstride = gridDim.x >> 3;
-    tlast = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  }
+  const auto [first, tstride, tlast] = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
+  int t = first;
   if (t < tlast) {
     gload(t);
     sstore(0);
@@ -167,13 +148,8 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_halo_kernel(const WgradHal
       // dy fragments of this k-step (shared by the wave's 7 taps)
       bf16x8 df[PB];
 #pragma unroll
-      for (int b = 0; b < PB; ++b) {
-        const char* p0 = ds + b * DPL + (((x * 8) + (yb + ly)) * 8 + lz) * 32 + tp * 8;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + 2 * 8 * 32));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        df[b] = __builtin_bit_cast(bf16x8, v);
-      }
+      for (int b = 0; b < PB; ++b)
+        df[b] = tr16_frag(ds + b * DPL + (((x * 8) + (yb + ly)) * 8 + lz) * 32 + tp * 8, 2 * 8 * 32);
       const int hbase = (((x + 1) * 10) + (yb + ly + 1)) * 10 + (lz + 1);
       // taps wave, wave+4, ..., wave+20 always exist: fetch all their operands first, then issue the MFMAs back to back
       // (branch-free, so the LDS latency of one tap hides behind the others); tap wave+24 may be the pseudo tap 27
@@ -182,13 +158,7 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_halo_kernel(const WgradHal
       for (int ti = 0; ti < TFULL; ++ti) {
         const int h = hbase + P.delta[wave + NW * ti];
 #pragma unroll
-        for (int a = 0; a < PA; ++a) {
-          const char* p0 = xs + a * XPL + h * 32 + tp * 8;
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + 2 * 10 * 32));
-          const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          af[ti][a] = __builtin_bit_cast(bf16x8, v);
-        }
+        for (int a = 0; a < PA; ++a) af[ti][a] = tr16_frag(xs + a * XPL + h * 32 + tp * 8, 2 * 10 * 32);
       }
 #pragma unroll
       for (int ti = 0; ti < TFULL; ++ti)
@@ -203,18 +173,14 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_halo_kernel(const WgradHal
           const int h = hbase + P.delta[tap];
 #pragma unroll
           for (int a = 0; a < PA; ++a) {
-            const char* p0 = xs + a * XPL + h * 32 + tp * 8;
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + 2 * 10 * 32));
-            const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            const bf16x8 a6 = __builtin_bit_cast(bf16x8, v);
+            const bf16x8 a6 = tr16_frag(xs + a * XPL + h * 32 + tp * 8, 2 * 10 * 32);
 #pragma unroll
             for (int b = 0; b < PB; ++b) acc[TFULL][a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a6, df[b], acc[TFULL][a][b], 0, 0, 0);
           }
         } else if (tap == 27) {  // pseudo tap 27: x == 1 on channel row 0 -> row 0 of the tile accumulates sum(dy) (bias gradient)
 #pragma unroll
           for (int b = 0; b < PB; ++b)
-            acc[TFULL][0][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ones), df[b], acc[TFULL][0][b], 0, 0, 0);
+            acc[TFULL][0][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, df[b], acc[TFULL][0][b], 0, 0, 0);
         }
       }
     }
@@ -245,109 +211,141 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_halo_kernel(const WgradHal
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The 16 -> <= 16 channel layer at full resolution (the logits convolution of the head: 25 M voxels, 1.2 GB of operands, 348 GFLOP of
-// padded MFMA work) is HBM-latency bound in the kernel above: a tile's loads are issued one tile (~900 cycles of multiplies) before
-// they are written to LDS, against ~3 us of memory latency, and two workgroups per CU keep 54 KB in flight (0.65 ms; 1.10 ms with one
-// workgroup per CU).  This variant keeps TWO tiles of loads in flight per workgroup in two register sets (tile t+2 is requested at
-// the top of iteration t and written to LDS at the end of iteration t+1), moves rows in 8-byte pieces with raw buffer loads — 12-wide
-// (24-byte) and 16-wide rows alike, a voxel outside the volume is an out-of-range offset selected by one v_and / v_cmp / v_cndmask —
-// and has no per-load branches.  The multiplies are those of conv_wgrad_halo_kernel<32, 32>.
-template <int NPX, int NPD>      // 8-byte pieces per x / dy voxel row: 3 (12 wide) or 4 (16 wide)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv_wgrad_head_kernel(const WgradHaloArgs P, int total_tiles, int x_sample_bytes, int d_sample_bytes) {
-  constexpr int XBYTES = WH_HV * 32, DBYTES = WH_TV * 32, BUF = XBYTES + DBYTES;
-  constexpr int XN = WH_HV * NPX, DN = WH_TV * NPD, JX = (XN + 255) / 256, JD = (DN + 255) / 256;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  __shared__ __attribute__((aligned(16))) char smem[BUF];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r16 = lane & 15, q4 = lane >> 4;
-  const int tq = r16 >> 2, tp = r16 & 3;
-  const int YZ = P.Y * P.Z;
+// padded MFMA work) is HBM-latency bound in the kernel above.  The two head kernels below share one staging scheme (HeadStage): rows
+// move in 8-byte pieces with raw buffer loads — 12-wide (24-byte) and 16-wide rows alike, a voxel outside the volume is an
+// out-of-range offset selected by one v_and / v_cmp / v_cndmask — with no per-load branches, ONE register set of loads in flight per
+// workgroup and 128 registers per lane: the phases of a workgroup (loads -> multiplies -> barrier -> LDS stores -> barrier) do not
+// overlap inside it; they overlap with those of the other workgroups on its CU.
+__device__ __forceinline__ bf16x8 wh_frag(const char* p0, int hi_off) {
+  if constexpr ((WH_ABL & 2) != 0) {      // (timing only)
+    typedef __attribute__((ext_vector_type(8))) short s16x8;
+    const short v0 = (short)(uintptr_t)p0;
+    return __builtin_bit_cast(bf16x8, s16x8{v0, v0, v0, v0, v0, v0, v0, v0});
+  }
+  return tr16_frag(p0, hi_off);
+}
 
+template <int NPX, int NPD, int NTH>      // 8-byte pieces per x / dy voxel row: 3 (12 wide) or 4 (16 wide); threads
+struct HeadStage {
+  static constexpr int XBYTES = WH_HV * 32, DBYTES = WH_TV * 32, BUF = XBYTES + DBYTES;
+  static constexpr int XN = WH_HV * NPX, DN = WH_TV * NPD, JX = (XN + NTH - 1) / NTH, JD = (DN + NTH - 1) / NTH;
+  // per-thread constants of the staging slots: byte offset from the halo / tile origin, one-hot (x, y, z) position inside the halo /
+  // tile (bit 31: no such piece), byte offset in LDS.  Piece j of a thread holds channel quad (tid + j * NTH) % NPX.
   int xo[JX], xl[JX], dof[JD], dl[JD];
   uint32_t xh[JX], dh[JD];
+  int bias_bytes;                           // the halo origin lies one voxel per axis before the tile's
+  __device__ __forceinline__ HeadStage(const WgradHaloArgs& P, int tid) {
+    const int YZ = P.Y * P.Z;
 #pragma unroll
-  for (int j = 0; j < JX; ++j) {
-    const int idx = tid + j * 256, hv = idx / NPX, part = idx - hv * NPX;
-    const int hx = hv / 100, rem = hv - hx * 100, hy = rem / 10, hz = rem - hy * 10;
-    xo[j] = (hx * YZ + hy * P.Z + hz) * P.g_ld * 2 + part * 8;
-    xh[j] = idx < XN ? ((1u << hx) | (1u << (6 + hy)) | (1u << (16 + hz))) : 0x80000000u;
-    xl[j] = hv * 32 + part * 8;
-  }
+    for (int j = 0; j < JX; ++j) {
+      const int idx = tid + j * NTH, hv = idx / NPX, part = idx - hv * NPX;
+      const int hx = hv / 100, rem = hv - hx * 100, hy = rem / 10, hz = rem - hy * 10;
+      xo[j] = (hx * YZ + hy * P.Z + hz) * P.g_ld * 2 + part * 8;
+      xh[j] = idx < XN ? ((1u << hx) | (1u << (6 + hy)) | (1u << (16 + hz))) : 0x80000000u;
+      xl[j] = hv * 32 + part * 8;
+    }
 #pragma unroll
-  for (int j = 0; j < JD; ++j) {
-    const int idx = tid + j * 256, tv = idx / NPD, part = idx - tv * NPD;
-    const int tx = tv >> 6, ty = (tv >> 3) & 7, tz = tv & 7;
-    dof[j] = (tx * YZ + ty * P.Z + tz) * P.d_ld * 2 + part * 8;
-    dh[j] = idx < DN ? ((1u << tx) | (1u << (4 + ty)) | (1u << (12 + tz))) : 0x80000000u;
-    dl[j] = XBYTES + tv * 32 + part * 8;
+    for (int j = 0; j < JD; ++j) {
+      const int idx = tid + j * NTH, tv = idx / NPD, part = idx - tv * NPD;
+      const int tx = tv >> 6, ty = (tv >> 3) & 7, tz = tv & 7;
+      dof[j] = (tx * YZ + ty * P.Z + tz) * P.d_ld * 2 + part * 8;
+      dh[j] = idx < DN ? ((1u << tx) | (1u << (4 + ty)) | (1u << (12 + tz))) : 0x80000000u;
+      dl[j] = XBYTES + tv * 32 + part * 8;
+    }
+    bias_bytes = (YZ + P.Z + 1) * P.g_ld * 2;
   }
-  const int bias_bytes = (YZ + P.Z + 1) * P.g_ld * 2;
-  auto range_mask = [](int lo, int hi, int nbits) -> uint32_t {
+  static __device__ __forceinline__ uint32_t range_mask(int lo, int hi, int nbits) {      // bits lo .. hi, clamped to [0, nbits)
     lo = lo < 0 ? 0 : lo;
     hi = hi > nbits - 1 ? nbits - 1 : hi;
     return hi < lo ? 0u : ((2u << hi) - (1u << lo));
-  };
-  auto gload = [&](int t, u32x2 (&rx)[JX], u32x2 (&rd)[JD]) {
-    const int n = t / P.tiles;
-    int r = t - n * P.tiles;
-    const int tz = r % P.tzn; r /= P.tzn;
-    const int ty = r % P.tyn, tx = r / P.tyn;
-    const int x0 = tx * 4, y0 = ty * 8, z0 = tz * 8;
-    const uint32_t xm = ~(range_mask(1 - x0, P.X - x0, 6) | (range_mask(1 - y0, P.Y - y0, 10) << 6) | (range_mask(1 - z0, P.Z - z0, 10) << 16));
-    const uint32_t dm = ~(range_mask(0, P.X - x0 - 1, 4) | (range_mask(0, P.Y - y0 - 1, 8) << 4) | (range_mask(0, P.Z - z0 - 1, 8) << 12));
-    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(P.in + (int64_t)n * x_sample_bytes - bias_bytes, x_sample_bytes + bias_bytes);
-    const __amdgpu_buffer_rsrc_t dr = buffer_rsrc(P.dy + (int64_t)n * d_sample_bytes, d_sample_bytes);
-    const int xs = ((x0 * P.Y + y0) * P.Z + z0) * P.g_ld * 2, dsf = ((x0 * P.Y + y0) * P.Z + z0) * P.d_ld * 2;
+  }
+  // one-hot positions (as in xh / dh) of the tile at `o` that lie OUTSIDE the volume
+  static __device__ __forceinline__ uint32_t x_outside(const WgradHaloArgs& P, const TileOrigin& o) {
+    return ~(range_mask(1 - o.x0, P.X - o.x0, 6) | (range_mask(1 - o.y0, P.Y - o.y0, 10) << 6) | (range_mask(1 - o.z0, P.Z - o.z0, 10) << 16));
+  }
+  static __device__ __forceinline__ uint32_t d_outside(const WgradHaloArgs& P, const TileOrigin& o) {
+    return ~(range_mask(0, P.X - o.x0 - 1, 4) | (range_mask(0, P.Y - o.y0 - 1, 8) << 4) | (range_mask(0, P.Z - o.z0 - 1, 8) << 12));
+  }
+  __device__ __forceinline__ void gload(const WgradHaloArgs& P, int t, int x_sample_bytes, int d_sample_bytes, u32x2 (&rx)[JX], u32x2 (&rd)[JD]) const {
+    const TileOrigin o = tile_origin<4, 8, 8>(t, P.tiles, P.tyn, P.tzn);
+    const uint32_t xm = x_outside(P, o), dm = d_outside(P, o);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(P.in + (int64_t)o.n * x_sample_bytes - bias_bytes, x_sample_bytes + bias_bytes);
+    const __amdgpu_buffer_rsrc_t dr = buffer_rsrc(P.dy + (int64_t)o.n * d_sample_bytes, d_sample_bytes);
+    const int xs = ((o.x0 * P.Y + o.y0) * P.Z + o.z0) * P.g_ld * 2, dsf = ((o.x0 * P.Y + o.y0) * P.Z + o.z0) * P.d_ld * 2;
 #pragma unroll
     for (int j = 0; j < JX; ++j)
       rx[j] = (WH_ABL & 4) ? u32x2{(uint32_t)xs, 0u} : __builtin_amdgcn_raw_buffer_load_b64(xr, (xh[j] & xm) == 0u ? xo[j] : (int)0x80000000, xs, 0);
 #pragma unroll
     for (int j = 0; j < JD; ++j)
       rd[j] = (WH_ABL & 4) ? u32x2{(uint32_t)dsf, 0u} : __builtin_amdgcn_raw_buffer_load_b64(dr, (dh[j] & dm) == 0u ? dof[j] : (int)0x80000000, dsf, 0);
-  };
-  auto sstore = [&](const u32x2 (&rx)[JX], const u32x2 (&rd)[JD]) {
-    if (WH_ABL & 8) { if (rx[0][0] == 0x12345u && rd[0][0] == 0x54321u) smem[tid] = 1; return; }
+  }
+  // rows narrower than 32 bytes: the pad bytes of every slot are zero for the whole launch
+  static __device__ __forceinline__ void zero_pads(char* smem, int tid) {
+    if (NPX < 4) for (int i = tid; i < WH_HV; i += NTH) *reinterpret_cast<u32x2*>(smem + i * 32 + 24) = u32x2{0u, 0u};
+    if (NPD < 4) for (int i = tid; i < WH_TV; i += NTH) *reinterpret_cast<u32x2*>(smem + XBYTES + i * 32 + 24) = u32x2{0u, 0u};
+  }
+  // (WH_ABL & 8, timing only: a store that never happens but keeps its operands alive)
+  __device__ __forceinline__ void store_x(char* smem, int tid, const u32x2 (&rx)[JX]) const {
 #pragma unroll
     for (int j = 0; j < JX; ++j)
-      if (JX * 256 == XN || tid + j * 256 < XN) *reinterpret_cast<u32x2*>(smem + xl[j]) = rx[j];
+      if ((JX * NTH == XN || tid + j * NTH < XN) && (!(WH_ABL & 8) || rx[j][0] == 0x12345u)) *reinterpret_cast<u32x2*>(smem + xl[j]) = rx[j];
+  }
+  __device__ __forceinline__ void store_d(char* smem, int tid, const u32x2 (&rd)[JD]) const {
 #pragma unroll
     for (int j = 0; j < JD; ++j)
-      if (JD * 256 == DN || tid + j * 256 < DN) *reinterpret_cast<u32x2*>(smem + dl[j]) = rd[j];
-  };
+      if ((JD * NTH == DN || tid + j * NTH < DN) && (!(WH_ABL & 8) || rd[j][0] == 0x54321u)) *reinterpret_cast<u32x2*>(smem + dl[j]) = rd[j];
+  }
+};
+
+// The tile loop of both head kernels: the loads of the next tile wait in registers while this one multiplies and are written to the
+// single LDS buffer behind the barrier that ends it.  The callables come by reference: copies of the closures changed the head kernel's
+// register allocation (24 -> 44 bytes of scratch per lane).
+template <class Load, class Compute, class Store>
+__device__ __forceinline__ void head_tile_loop(const TileSeq seq, const Load& load, const Compute& compute, const Store& store) {
+  int t = seq.first;
+  const int tstride = seq.stride, tlast = seq.last;
+  if (t < tlast) {
+    load(t);
+    store(t);
+  }
+  __syncthreads();
+  for (; t < tlast; t += tstride) {
+    if (t + tstride < tlast) load(t + tstride);
+    compute();
+    __syncthreads();
+    if (t + tstride < tlast) store(t + tstride);
+    __syncthreads();
+  }
+}
+
+// Four waves split the 27 taps + the pseudo tap as conv_wgrad_halo_kernel<32, 32, 4> does (its multiplies); FOUR workgroups per CU.
+// Serves taps in any order.
+template <int NPX, int NPD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv_wgrad_head_kernel(const WgradHaloArgs P, int total_tiles, int x_sample_bytes, int d_sample_bytes) {
+  using ST = HeadStage<NPX, NPD, 256>;
+  __shared__ __attribute__((aligned(16))) char smem[ST::BUF];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r16 = lane & 15, q4 = lane >> 4;
+  const int tq = r16 >> 2, tp = r16 & 3;
+  const ST stg(P, tid);
 
   f32x4 acc[7];
 #pragma unroll
   for (int t = 0; t < 7; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int lz = 4 * (q4 & 1) + tq, ly = q4 >> 1;
-  s16x8 ones;
-  {
-    const short o = (r16 == 0) ? (short)0x3f80 : (short)0;
-    ones = s16x8{o, o, o, o, o, o, o, o};
-  }
+  const bf16x8 ones = bias_ones_frag(r16);
   auto compute = [&]() {
     const char* xs = smem;
-    const char* ds = xs + XBYTES;
+    const char* ds = xs + ST::XBYTES;
 #pragma unroll 2
     for (int s = 0; s < 8; ++s) {
       const int x = s >> 1, yb = 4 * (s & 1);
-      bf16x8 df;
-      {
-        const char* p0 = ds + (((x * 8) + (yb + ly)) * 8 + lz) * 32 + tp * 8;
-        const s16x4 lo = (WH_ABL & 2) ? s16x4{(short)s, 1, 2, 3} : __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-        const s16x4 hi = (WH_ABL & 2) ? s16x4{(short)s, 1, 2, 3} : __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + 2 * 8 * 32));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        df = __builtin_bit_cast(bf16x8, v);
-      }
+      const bf16x8 df = wh_frag(ds + (((x * 8) + (yb + ly)) * 8 + lz) * 32 + tp * 8, 2 * 8 * 32);
       const int hbase = (((x + 1) * 10) + (yb + ly + 1)) * 10 + (lz + 1);
       bf16x8 af[6];
 #pragma unroll
-      for (int ti = 0; ti < 6; ++ti) {
-        const char* p0 = xs + (hbase + P.delta[wave + 4 * ti]) * 32 + tp * 8;
-        const s16x4 lo = (WH_ABL & 2) ? s16x4{(short)(s + tp), 1, 2, 3} : __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-        const s16x4 hi = (WH_ABL & 2) ? s16x4{(short)(s + tp), 1, 2, 3} : __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + 2 * 10 * 32));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        af[ti] = __builtin_bit_cast(bf16x8, v);
-      }
+      for (int ti = 0; ti < 6; ++ti) af[ti] = wh_frag(xs + (hbase + P.delta[wave + 4 * ti]) * 32 + tp * 8, 2 * 10 * 32);
 #pragma unroll
       for (int ti = 0; ti < 6; ++ti) {
         if constexpr ((WH_ABL & 1) != 0) acc[ti][0] += __builtin_bit_cast(f32x4, af[ti])[0] * __builtin_bit_cast(f32x4, df)[1];
@@ -355,42 +353,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
       const int tap = wave + 24;
       if (tap < 27) {
-        const char* p0 = xs + (hbase + P.delta[tap]) * 32 + tp * 8;
-        const s16x4 lo = (WH_ABL & 2) ? s16x4{(short)(s + tp), 1, 2, 3} : __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-        const s16x4 hi = (WH_ABL & 2) ? s16x4{(short)(s + tp), 1, 2, 3} : __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + 2 * 10 * 32));
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        acc[6] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, v), df, acc[6], 0, 0, 0);
+        acc[6] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh_frag(xs + (hbase + P.delta[tap]) * 32 + tp * 8, 2 * 10 * 32), df, acc[6], 0, 0, 0);
       } else {   // pseudo tap 27: row 0 accumulates sum(dy) (bias gradient)
-        acc[6] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ones), df, acc[6], 0, 0, 0);
+        acc[6] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, df, acc[6], 0, 0, 0);
       }
     }
   };
 
-  int t = blockIdx.x, tstride = gridDim.x, tlast = total_tiles;
-  if ((gridDim.x & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    t = xcd * chunk + (blockIdx.x >> 3);
-    tstride = gridDim.x >> 3;
-    tlast = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  }
-  // rows narrower than 32 bytes: the pad bytes of every slot are zero for the whole launch
-  if (NPX < 4) for (int i = tid; i < WH_HV; i += 256) *reinterpret_cast<u32x2*>(smem + i * 32 + 24) = u32x2{0u, 0u};
-  if (NPD < 4) for (int i = tid; i < WH_TV; i += 256) *reinterpret_cast<u32x2*>(smem + XBYTES + i * 32 + 24) = u32x2{0u, 0u};
-  // ONE register set of loads in flight per workgroup, FOUR workgroups per CU (128 registers each): the phases of a workgroup
-  // (loads -> multiplies -> barrier -> LDS stores -> barrier) do not overlap inside it; they overlap with the other three's.
-  u32x2 rxA[JX], rdA[JD];
-  if (t < tlast) {
-    gload(t, rxA, rdA);
-    sstore(rxA, rdA);
-  }
-  __syncthreads();
-  for (; t < tlast; t += tstride) {
-    if (t + tstride < tlast) gload(t + tstride, rxA, rdA);
-    compute();
-    __syncthreads();
-    if (t + tstride < tlast) sstore(rxA, rdA);
-    __syncthreads();
-  }
+  const TileSeq seq = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
+  ST::zero_pads(smem, tid);
+  u32x2 rx[ST::JX], rd[ST::JD];
+  head_tile_loop(
+      seq, [&](int t) { stg.gload(P, t, x_sample_bytes, d_sample_bytes, rx, rd); }, compute,
+      [&](int) {
+        stg.store_x(smem, tid, rx);
+        stg.store_d(smem, tid, rd);
+      });
 
   float* slab = P.ws + (int64_t)blockIdx.x * P.kpad_w * P.cn_pad;
 #pragma unroll
@@ -411,61 +389,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 // four dy fragments of its half — 280 transposed reads per tile instead of 512.  The two k halves accumulate into two slabs.
 template <int NPX, int NPD>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv_wgrad_head2_kernel(const WgradHaloArgs P, int total_tiles, int x_sample_bytes, int d_sample_bytes) {
-  constexpr int XBYTES = WH_HV * 32, DBYTES = WH_TV * 32, BUF = XBYTES + DBYTES;
-  constexpr int XN = WH_HV * NPX, DN = WH_TV * NPD, JX = (XN + 511) / 512, JD = (DN + 511) / 512;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  __shared__ __attribute__((aligned(16))) char smem[BUF + WH_NRM_MAXN * 128];
-  float* const sPar = reinterpret_cast<float*>(smem + BUF);     // per sample: 4 channel quads x (mean x 4, rstd x 4)
+  using ST = HeadStage<NPX, NPD, 512>;
+  constexpr int JX = ST::JX, XN = ST::XN;
+  __shared__ __attribute__((aligned(16))) char smem[ST::BUF + WH_NRM_MAXN * 128];
+  float* const sPar = reinterpret_cast<float*>(smem + ST::BUF);     // per sample: 4 channel quads x (mean x 4, rstd x 4)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, q4 = lane >> 4;
   const int tq = r16 >> 2, tp = r16 & 3;
-  const int YZ = P.Y * P.Z;
+  const ST stg(P, tid);
+  u32x2 rx[JX], rd[ST::JD];
 
-  int xo[JX], xl[JX], dof[JD], dl[JD];
-  uint32_t xh[JX], dh[JD];
-#pragma unroll
-  for (int j = 0; j < JX; ++j) {
-    const int idx = tid + j * 512, hv = idx / NPX, part = idx - hv * NPX;
-    const int hx = hv / 100, rem = hv - hx * 100, hy = rem / 10, hz = rem - hy * 10;
-    xo[j] = (hx * YZ + hy * P.Z + hz) * P.g_ld * 2 + part * 8;
-    xh[j] = idx < XN ? ((1u << hx) | (1u << (6 + hy)) | (1u << (16 + hz))) : 0x80000000u;
-    xl[j] = hv * 32 + part * 8;
-  }
-#pragma unroll
-  for (int j = 0; j < JD; ++j) {
-    const int idx = tid + j * 512, tv = idx / NPD, part = idx - tv * NPD;
-    const int tx = tv >> 6, ty = (tv >> 3) & 7, tz = tv & 7;
-    dof[j] = (tx * YZ + ty * P.Z + tz) * P.d_ld * 2 + part * 8;
-    dh[j] = idx < DN ? ((1u << tx) | (1u << (4 + ty)) | (1u << (12 + tz))) : 0x80000000u;
-    dl[j] = XBYTES + tv * 32 + part * 8;
-  }
-  const int bias_bytes = (YZ + P.Z + 1) * P.g_ld * 2;
-  auto range_mask = [](int lo, int hi, int nbits) -> uint32_t {
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > nbits - 1 ? nbits - 1 : hi;
-    return hi < lo ? 0u : ((2u << hi) - (1u << lo));
-  };
-  auto gload = [&](int t, u32x2 (&rx)[JX], u32x2 (&rd)[JD]) {
-    const int n = t / P.tiles;
-    int r = t - n * P.tiles;
-    const int tz = r % P.tzn; r /= P.tzn;
-    const int ty = r % P.tyn, tx = r / P.tyn;
-    const int x0 = tx * 4, y0 = ty * 8, z0 = tz * 8;
-    const uint32_t xm = ~(range_mask(1 - x0, P.X - x0, 6) | (range_mask(1 - y0, P.Y - y0, 10) << 6) | (range_mask(1 - z0, P.Z - z0, 10) << 16));
-    const uint32_t dm = ~(range_mask(0, P.X - x0 - 1, 4) | (range_mask(0, P.Y - y0 - 1, 8) << 4) | (range_mask(0, P.Z - z0 - 1, 8) << 12));
-    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(P.in + (int64_t)n * x_sample_bytes - bias_bytes, x_sample_bytes + bias_bytes);
-    const __amdgpu_buffer_rsrc_t dr = buffer_rsrc(P.dy + (int64_t)n * d_sample_bytes, d_sample_bytes);
-    const int xs = ((x0 * P.Y + y0) * P.Z + z0) * P.g_ld * 2, dsf = ((x0 * P.Y + y0) * P.Z + z0) * P.d_ld * 2;
-#pragma unroll
-    for (int j = 0; j < JX; ++j)
-      rx[j] = (WH_ABL & 4) ? u32x2{(uint32_t)xs, 0u} : __builtin_amdgcn_raw_buffer_load_b64(xr, (xh[j] & xm) == 0u ? xo[j] : (int)0x80000000, xs, 0);
-#pragma unroll
-    for (int j = 0; j < JD; ++j)
-      rd[j] = (WH_ABL & 4) ? u32x2{(uint32_t)dsf, 0u} : __builtin_amdgcn_raw_buffer_load_b64(dr, (dh[j] & dm) == 0u ? dof[j] : (int)0x80000000, dsf, 0);
-  };
   // operand normalisation on load (the arithmetic of instnorm_prelu_fwd_kernel, rounded to bf16 as that pass rounds): x pieces only;
-  // halo voxels outside the volume and channels >= in_C stay 0.  Piece j holds channel quad (tid + j * 512) % NPX.
+  // halo voxels outside the volume and channels >= in_C stay 0.
   const bool nrm = P.in_mr != nullptr;
   const float nrm_al = nrm ? P.in_alpha[0] : 1.f;
   if (nrm)
@@ -473,23 +409,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       const int n = i >> 5, k = i & 31, c = (k >> 3) * 4 + (k & 3);
       sPar[i] = c < P.in_C ? P.in_mr[((int64_t)n * P.in_C + c) * 2 + ((k >> 2) & 1)] : 0.f;
     }
-  auto xmask = [&](int t, int& n) -> uint32_t {
-    n = t / P.tiles;
-    int r = t - n * P.tiles;
-    const int tz = r % P.tzn; r /= P.tzn;
-    const int ty = r % P.tyn, tx = r / P.tyn;
-    const int x0 = tx * 4, y0 = ty * 8, z0 = tz * 8;
-    return ~(range_mask(1 - x0, P.X - x0, 6) | (range_mask(1 - y0, P.Y - y0, 10) << 6) | (range_mask(1 - z0, P.Z - z0, 10) << 16));
-  };
-  auto sstore = [&](int t, const u32x2 (&rx)[JX], const u32x2 (&rd)[JD]) {
+  auto sstore = [&](int t) {
     if (!nrm) {
-#pragma unroll
-      for (int j = 0; j < JX; ++j)
-        if ((JX * 512 == XN || tid + j * 512 < XN) && (!(WH_ABL & 8) || rx[j][0] == 0x12345u)) *reinterpret_cast<u32x2*>(smem + xl[j]) = rx[j];
+      stg.store_x(smem, tid, rx);
     } else {
-      int n;
-      const uint32_t xm = xmask(t, n);
-      const float* par = sPar + n * 32;
+      const TileOrigin o = tile_origin<4, 8, 8>(t, P.tiles, P.tyn, P.tzn);
+      const uint32_t xm = ST::x_outside(P, o);
+      const float* par = sPar + o.n * 32;
 #pragma unroll
       for (int j = 0; j < JX; ++j) {
         const int part = (tid + j * 512) % NPX;
@@ -500,13 +426,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
           const float a = (v[e] - mean[e]) * rstd[e];
           v[e] = a > 0.f ? a : nrm_al * a;
         }
-        const u32x2 w = (xh[j] & xm) == 0u ? u32x2{pack2<BF16>(v[0], v[1]), pack2<BF16>(v[2], v[3])} : u32x2{0u, 0u};
-        if (JX * 512 == XN || tid + j * 512 < XN) *reinterpret_cast<u32x2*>(smem + xl[j]) = w;
+        const u32x2 w = (stg.xh[j] & xm) == 0u ? u32x2{pack2<BF16>(v[0], v[1]), pack2<BF16>(v[2], v[3])} : u32x2{0u, 0u};
+        if (JX * 512 == XN || tid + j * 512 < XN) *reinterpret_cast<u32x2*>(smem + stg.xl[j]) = w;
       }
     }
-#pragma unroll
-    for (int j = 0; j < JD; ++j)
-      if (JD * 512 == DN || tid + j * 512 < DN) *reinterpret_cast<u32x2*>(smem + dl[j]) = rd[j];
+    stg.store_d(smem, tid, rd);
   };
   const int kh = wave >> 2, cg = wave & 3;               // k half, combo group
   // first (dy,dz) combo of the group, how many.  Waves w and w + 4 (the two k halves of one combo group) share a SIMD: with the same
@@ -520,25 +444,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int dxi = 0; dxi < 3; ++dxi) acc[ci][dxi] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int lz = 4 * (q4 & 1) + tq, ly = q4 >> 1;
-  s16x8 ones;
-  {
-    const short o = (r16 == 0) ? (short)0x3f80 : (short)0;
-    ones = s16x8{o, o, o, o, o, o, o, o};
-  }
-  auto tr_frag = [&](const char* p0, int hi_off) -> bf16x8 {
-    if constexpr ((WH_ABL & 2) != 0) { const short v0 = (short)(uintptr_t)p0; return __builtin_bit_cast(bf16x8, s16x8{v0, v0, v0, v0, v0, v0, v0, v0}); }   // (timing only)
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + hi_off));
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  const bf16x8 ones = bias_ones_frag(r16);
   auto compute = [&]() {
     const char* xs = smem;
-    const char* ds = xs + XBYTES;
+    const char* ds = xs + ST::XBYTES;
     const int yb = 4 * kh;
     bf16x8 df[4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) df[p] = tr_frag(ds + (((p * 8) + (yb + ly)) * 8 + lz) * 32 + tp * 8, 2 * 8 * 32);
+    for (int p = 0; p < 4; ++p) df[p] = wh_frag(ds + (((p * 8) + (yb + ly)) * 8 + lz) * 32 + tp * 8, 2 * 8 * 32);
     const int hb0 = (yb + ly + 1) * 10 + (lz + 1);          // halo voxel of this lane in plane 0, before the (dy,dz) shift
 #pragma unroll
     for (int ci = 0; ci < 3; ++ci) {
@@ -546,7 +459,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         const int dyz = P.delta[9 + c0 + ci];                // taps 9..17 are the dx = 0 group: delta = dy * 10 + dz
         bf16x8 xf[6];
 #pragma unroll
-        for (int q = 0; q < 6; ++q) xf[q] = tr_frag(xs + (q * 100 + hb0 + dyz) * 32 + tp * 8, 2 * 10 * 32);
+        for (int q = 0; q < 6; ++q) xf[q] = wh_frag(xs + (q * 100 + hb0 + dyz) * 32 + tp * 8, 2 * 10 * 32);
 #pragma unroll
         for (int dxi = 0; dxi < 3; ++dxi)
 #pragma unroll
@@ -558,36 +471,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
     if (cg == 3) {       // pseudo tap 27: row 0 accumulates sum(dy) (bias gradient)
 #pragma unroll
-      for (int p = 0; p < 4; ++p) acc_ps = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ones), df[p], acc_ps, 0, 0, 0);
+      for (int p = 0; p < 4; ++p) acc_ps = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, df[p], acc_ps, 0, 0, 0);
     }
   };
 
-  int t = blockIdx.x, tstride = gridDim.x, tlast = total_tiles;
-  if ((gridDim.x & 7) == 0) {
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    t = xcd * chunk + (blockIdx.x >> 3);
-    tstride = gridDim.x >> 3;
-    tlast = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  }
-  // rows narrower than 32 bytes: the pad bytes of every slot are zero for the whole launch
-  if (NPX < 4) for (int i = tid; i < WH_HV; i += 512) *reinterpret_cast<u32x2*>(smem + i * 32 + 24) = u32x2{0u, 0u};
-  if (NPD < 4) for (int i = tid; i < WH_TV; i += 512) *reinterpret_cast<u32x2*>(smem + XBYTES + i * 32 + 24) = u32x2{0u, 0u};
-  // ONE register set of loads in flight per workgroup, FOUR workgroups per CU (128 registers each): the phases of a workgroup
-  // (loads -> multiplies -> barrier -> LDS stores -> barrier) do not overlap inside it; they overlap with the other three's.
-  u32x2 rxA[JX], rdA[JD];
+  const TileSeq seq = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
+  ST::zero_pads(smem, tid);
   __syncthreads();          // the operand-normalisation table is written
-  if (t < tlast) {
-    gload(t, rxA, rdA);
-    sstore(t, rxA, rdA);
-  }
-  __syncthreads();
-  for (; t < tlast; t += tstride) {
-    if (t + tstride < tlast) gload(t + tstride, rxA, rdA);
-    compute();
-    __syncthreads();
-    if (t + tstride < tlast) sstore(t + tstride, rxA, rdA);
-    __syncthreads();
-  }
+  head_tile_loop(seq, [&](int t) { stg.gload(P, t, x_sample_bytes, d_sample_bytes, rx, rd); }, compute, sstore);
 
   float* slab = P.ws + ((int64_t)blockIdx.x * 2 + kh) * P.kpad_w * P.cn_pad;       // one slab per k half
 #pragma unroll
@@ -627,12 +518,7 @@ bool wgrad_halo_eligible(const ctseg_wgrad_desc* d) {
   if (d->d_ld % 8 == 0 && d->d_ld < db / 2) return false;
   if (d->cn_pad < db / 2) return false;
   if ((int64_t)d->Xi * d->Yi * d->Zi * (d->g_ld > d->d_ld ? d->g_ld : d->d_ld) * 2 >= (1ll << 31)) return false;  // 32-bit per-sample byte offsets
-  for (int j = 0; j < 27; ++j)
-    for (int s = 0; s < 24; s += 8) {
-      const int v = (int)(int8_t)((d->taps[j] >> s) & 0xff);
-      if (v < -1 || v > 1) return false;
-    }
-  return true;
+  return taps_within_unit_cube(d);
 }
 
 // Which kernel of this file serves an eligible descriptor, and its instantiation: the one place that decides it.  The launcher
@@ -642,13 +528,8 @@ struct WgradHaloVariant { WhKernel k; int a, b; };
 static WgradHaloVariant wgrad_halo_variant(const ctseg_wgrad_desc* d) {
   const int vb = d->Cg * 2, db = ((d->Cn + 15) / 16) * 32;
   if (!(vb == 32 && db == 32 && (d->g_ld == 12 || d->g_ld == 16) && (d->d_ld == 12 || d->d_ld == 16))) return {WhKernel::HALO, vb, db};
-  bool canonical = true;
-  for (int j = 0; j < 27; ++j) {      // the x-column reuse indexes taps as dx * 9 + (dy, dz): canonical order only
-    const int tp = d->taps[j];
-    if ((int)(int8_t)(tp & 0xff) != j / 9 - 1 || (int)(int8_t)((tp >> 8) & 0xff) != (j / 3) % 3 - 1 || (int)(int8_t)((tp >> 16) & 0xff) != j % 3 - 1)
-      canonical = false;
-  }
-  return {canonical ? WhKernel::HEAD2 : WhKernel::HEAD, d->g_ld / 4, d->d_ld / 4};
+  // the x-column reuse indexes taps as dx * 9 + (dy, dz): canonical order only
+  return {taps_canonical_27(d) ? WhKernel::HEAD2 : WhKernel::HEAD, d->g_ld / 4, d->d_ld / 4};
 }
 
 static int wgrad_halo_grid(const ctseg_wgrad_desc* d) {
@@ -698,7 +579,7 @@ void launch_wgrad_halo(const ctseg_wgrad_desc* d, hipStream_t st) {
     int v = 0;
     if (j < 27) {
       const int tp = d->taps[j];
-      v = ((int)(int8_t)(tp & 0xff) * 10 + (int)(int8_t)((tp >> 8) & 0xff)) * 10 + (int)(int8_t)((tp >> 16) & 0xff);
+      v = (tap_dx(tp) * 10 + tap_dy(tp)) * 10 + tap_dz(tp);
     }
     a.delta[j] = v;
   }

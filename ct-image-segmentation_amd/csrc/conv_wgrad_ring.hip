@@ -21,7 +21,7 @@
 // number of stages whatever its split holds.
 #include <type_traits>
 
-#include "ctseg_dev.h"
+#include "wgrad_common.h"
 
 #ifndef WR_ABL
 #define WR_ABL 0     // timing-only ablation builds (tools/ablate_wgrad_ring.sh; results are garbage): 1 no MFMAs, 2 no transposed fragment reads, 4 no gathered-operand loads, 8 no dy loads, 16 no step barrier, 32 no bounds tests / coordinate carries
@@ -29,18 +29,10 @@
 
 namespace ctseg {
 
-struct WRingKArgs {
-  const char* in;
-  const char* dy;
-  float* ws;
-  int N, Xi, Yi, Zi, Xr, Yr, Zr;
-  int Cg, Cn, g_ld, d_ld, sin, ntaps;
-  int rows, splits, rows_per_split, nst;   // nst: stages every workgroup runs (even, >= 4)
-  int kpad_w, cn_pad, d_valid;
-  int cx5, cy5, cz5;                       // mixed-radix decomposition of a 512-row step (one chunk of the row table)
-  int ktiles, ctiles;                      // workgroup -> (tile, slab): ids L, L+8, ... of a group of 8*ktiles*ctiles share a slab (one XCD)
-  int xcd;                                 // 1: that order; 0: tile = blockIdx.x, slab = blockIdx.y
-  int taps[CTSEG_MAX_TAPS];
+struct WRingKArgs : WgradGeom {           // step: 512 rows (one chunk of the row table)
+  int nst;                                 // stages every workgroup runs (even, >= 4)
+  int ktiles, ctiles;
+  int xcd;                                 // 1: flat grid, workgroup -> (tile, slab) by slab_xcd_decode; 0: tile = blockIdx.x, slab = blockIdx.y
 };
 
 // Two transposed LDS reads = one bf16 MFMA operand (rows r and r + 16 of the stage).
@@ -100,7 +92,7 @@ __device__ __forceinline__ void wring_main(const WRingKArgs& P, char* smem, f32x
     int t = 0;      // (a select chain over the kernel-argument table: once per thread and panel, and the table stays in SGPRs)
 #pragma unroll
     for (int q = 0; q < CTSEG_MAX_TAPS; ++q) t = (q == slot) ? P.taps[q] : t;
-    const int dx = (int)(int8_t)(t & 0xff), dy = (int)(int8_t)((t >> 8) & 0xff), dz = (int)(int8_t)((t >> 16) & 0xff);
+    const int dx = tap_dx(t), dy = tap_dy(t), dz = tap_dz(t);
     tapoff[p] = ((dx * P.Yi + dy) * P.Zi + dz) * gl + ci * 2;
     tapbit[p] = kval ? (dx + 1) * 9 + (dy + 1) * 3 + (dz + 1) : 31;
   }
@@ -115,34 +107,23 @@ __device__ __forceinline__ void wring_main(const WRingKArgs& P, char* smem, f32x
   // coordinates from chunk to chunk (carries, no division) and writes {offset, ~mask27}; mask27 = the product of three 3-bit axis
   // masks spread to bit strides 9, 3 and 1 (no carries between them).  A request then costs a bit-field extract, an add and an OR.
   u32x2* const tab = reinterpret_cast<u32x2*>(smem + C::RING);
-  int tx, ty, tz, toff;          // scaled coordinates and byte offset of row mstart + 512 c + tid
+  RowWalk tw;                    // row mstart + 512 c + tid
   {
-    const int m = mstart + tid;
-    tz = m % P.Zr; const int t = m / P.Zr;
-    ty = t % P.Yr; tx = t / P.Yr;
-    tx *= P.sin; ty *= P.sin; tz *= P.sin;
-    toff = ((tx * P.Yi + ty) * P.Zi + tz) * gl;
+    const int m = mstart + tid, t = m / P.Zr;
+    tw = RowWalk{t / P.Yr * P.sin, t % P.Yr * P.sin, m % P.Zr * P.sin, 0};
+    tw.off = ((tw.x * P.Yi + tw.y) * P.Zi + tw.z) * gl;
   }
-  const int zrs = P.Zr * P.sin, yrs = P.Yr * P.sin, xrs = P.Xr * P.sin;
-  const int c5z = P.cz5 * P.sin, c5y = P.cy5 * P.sin, c5x = P.cx5 * P.sin;
-  const int o5 = (c5z + (c5y + c5x * P.Yi) * P.Zi) * gl;
-  const int o_cz = P.sin * gl * (P.Zi - P.Zr), o_cy = P.sin * gl * P.Zi * (P.Yi - P.Yr);
+  const int xrs = P.Xr * P.sin;
+  const RowStepK K = row_step_k(P, gl);
   auto table_chunk = [&](int c) {
     auto axis = [&](int v, int lim, int stride) -> uint32_t {           // bits 0, stride, 2 stride: v-1, v, v+1 inside [0, lim)
       return ((unsigned)(v - 1) < (unsigned)lim ? 1u : 0u) | ((unsigned)v < (unsigned)lim ? 1u << stride : 0u) |
              ((unsigned)(v + 1) < (unsigned)lim ? 1u << (2 * stride) : 0u);
     };
-    uint32_t m27 = axis(tz, P.Zi, 1) * axis(ty, P.Yi, 3) * axis(tx, P.Xi, 9);
-    if (tx >= xrs) m27 = 0u;                                            // a row past the end of the sample
-    tab[(c & 1) * 512 + tid] = u32x2{(uint32_t)toff, ~m27};
-    tz += c5z;
-    const bool carry_z = tz >= zrs;
-    tz -= carry_z ? zrs : 0;
-    ty += c5y + (carry_z ? P.sin : 0);
-    const bool carry_y = ty >= yrs;
-    ty -= carry_y ? yrs : 0;
-    tx += c5x + (carry_y ? P.sin : 0);
-    toff += o5 + (carry_z ? o_cz : 0) + (carry_y ? o_cy : 0);
+    uint32_t m27 = axis(tw.z, P.Zi, 1) * axis(tw.y, P.Yi, 3) * axis(tw.x, P.Xi, 9);
+    if (tw.x >= xrs) m27 = 0u;                                          // a row past the end of the sample
+    tab[(c & 1) * 512 + tid] = u32x2{(uint32_t)tw.off, ~m27};
+    tw.advance(K);
   };
   // the entry of this thread's row in stage q (inline assembly like the fragment reads: the step's own lgkmcnt(0) covers it)
   const uint32_t tab0 = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char*)smem) + C::RING + srow * 8;
@@ -388,10 +369,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_ring_kernel(const WRingKArgs P
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int tile, zslab;
   if (P.xcd) {
-    const int kc = P.ktiles * P.ctiles, G = 8 * kc;
-    const int L = blockIdx.x, g = L / G, r = L - g * G;
-    zslab = g * 8 + (r & 7);
-    tile = r >> 3;
+    const SlabTile st = slab_xcd_decode(blockIdx.x, P.ktiles * P.ctiles);
+    tile = st.tile; zslab = st.zslab;
   } else {
     tile = blockIdx.x; zslab = blockIdx.y;
   }
@@ -435,11 +414,7 @@ static int wring_kind(const ctseg_wgrad_desc* d) {
   if (d->dtype != CTSEG_BF16) return 0;
   if (d->Cg % 8 != 0 || d->g_ld % 8 != 0 || d->d_ld % 8 != 0 || ((uintptr_t)d->in % 16) != 0 || ((uintptr_t)d->dy % 16) != 0) return 0;
   if (d->Cg < 32 || d->Cn < 64 || d->ntaps > 32) return 0;
-  for (int t = 0; t < d->ntaps; ++t)                        // the row table keeps one bit per neighbour in {-1, 0, 1}^3
-    for (int sh = 0; sh < 24; sh += 8) {
-      const int o = (int)(int8_t)((d->taps[t] >> sh) & 0xff);
-      if (o < -1 || o > 1) return 0;
-    }
+  if (!taps_within_unit_cube(d)) return 0;                  // the row table keeps one bit per neighbour in {-1, 0, 1}^3
   if (d->dyn_g != nullptr || d->in_mean_rstd != nullptr) return 0;
   if ((int64_t)d->Xi * d->Yi * d->Zi * d->g_ld * 2 >= ((int64_t)1 << 31) - 4096) return 0;      // 32-bit buffer offsets inside a sample
   if (d->cn_pad % 256 == 0) return 1;
@@ -470,31 +445,20 @@ template <typename C> static void launch_wring(WRingKArgs& a, hipStream_t st) {
   a.ktiles = (ktot + 1 + C::KB - 1) / C::KB;
   a.ctiles = a.cn_pad / C::BN;
   const int zs = a.N * a.splits, tiles = a.ktiles * a.ctiles;
-  a.xcd = (zs % 8 == 0 && tiles > 1) ? 1 : 0;
+  a.xcd = slab_grid_is_flat(zs, tiles) ? 1 : 0;
   const dim3 grid = a.xcd ? dim3((unsigned)(tiles * zs), 1u, 1u) : dim3((unsigned)tiles, (unsigned)zs, 1u);
   hipLaunchKernelGGL((conv_wgrad_ring_kernel<C>), grid, dim3(512), 0, st, a);
 }
 
-// rows_per_split: checked by the entry point (32-row aligned, its row bytes within 32-bit offsets)
 void launch_wgrad_ring(const ctseg_wgrad_desc* d, int rows_per_split, hipStream_t st) {
   const int kind = wring_kind(d);
   WRingKArgs a;
-  a.in = (const char*)d->in; a.dy = (const char*)d->dy; a.ws = d->ws;
-  a.N = d->N; a.Xi = d->Xi; a.Yi = d->Yi; a.Zi = d->Zi; a.Xr = d->Xr; a.Yr = d->Yr; a.Zr = d->Zr;
-  a.Cg = d->Cg; a.Cn = d->Cn; a.g_ld = d->g_ld; a.d_ld = d->d_ld; a.sin = d->sin; a.ntaps = d->ntaps;
-  a.rows = d->Xr * d->Yr * d->Zr; a.splits = d->splits;
-  a.rows_per_split = rows_per_split;
+  wgrad_geom_fill(a, d, rows_per_split);
+  a.step = radix_step(512, d->Zr, d->Yr);
   int nst = rows_per_split / 32;
   if (nst < 8) nst = 8;          // >= D + 2 for every ring depth instantiated below
   nst += nst & 1;
   a.nst = nst;
-  a.kpad_w = d->kpad_w; a.cn_pad = d->cn_pad;
-  const int dv = ((d->Cn + 7) / 8) * 8;
-  a.d_valid = dv < d->d_ld ? dv : d->d_ld;
-  int step = 512;
-  a.cz5 = step % d->Zr; step /= d->Zr;
-  a.cy5 = step % d->Yr; a.cx5 = step / d->Yr;
-  for (int i = 0; i < CTSEG_MAX_TAPS; ++i) a.taps[i] = i < d->ntaps ? d->taps[i] : 0;
   if (kind == 1) launch_wring<WRingA>(a, st);
   else if (kind == 2) launch_wring<WRingB>(a, st);
   else launch_wring<WRingC>(a, st);

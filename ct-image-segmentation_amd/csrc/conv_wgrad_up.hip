@@ -19,7 +19,8 @@
 // tile along an axis) are zero; fine voxels past a partial tile meet zero coarse operands (finite x 0).
 // Row 27 * 16 of the result is the column sum of the row operand (ctseg_conv_wgrad's bias-gradient row): the same geometry serves a
 // plain stride-2 Conv3d 16 -> 64.  One fp32 slab per workgroup -> ctseg_conv_wgrad_reduce.  Two workgroups (60 KB of LDS each) per CU alternate load and multiply.
-#include "ctseg_dev.h"
+#include "conv_common.h"
+#include "wgrad_common.h"
 
 namespace ctseg {
 
@@ -51,7 +52,6 @@ static_assert(WU_FINSTR % 4 == 0, "every wave issues the same number of DMA inst
 template <int GW>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs P, int total_tiles) {
   constexpr int FS = 32, PB = GW == 16 ? 16 : 12, GB = GW * 2;     // LDS voxel slot, bytes per DMA piece, bytes of a row in memory
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
   __shared__ __attribute__((aligned(16))) char smem[WU_FBYTES + WU_CBYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -83,11 +83,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs
     return hi < 0 ? 0u : ((2u << hi) - 1u);
   };
   auto dma = [&](int t) {
-    const int n = t / P.tiles;
-    int r = t - n * P.tiles;
-    const int tz = r % P.tzn; r /= P.tzn;
-    const int ty = r % P.tyn, tx = r / P.tyn;
-    const int x0 = tx * WU_TX, y0 = ty * WU_TY, z0 = tz * WU_TZ;
+    const auto [n, x0, y0, z0] = tile_origin<WU_TX, WU_TY, WU_TZ>(t, P.tiles, P.tyn, P.tzn);
     const int fm = (x0 == 0 ? 1 : 0) | (y0 == 0 ? 2 : 0) | (z0 == 0 ? 4 : 0) | 8;
     const i32x4 fr = make_rsrc(P.fine + (int64_t)n * P.fine_sample_bytes - fbias, (uint32_t)(P.fine_sample_bytes + fbias));
     const int fso = ((2 * x0 * Yf + 2 * y0) * Zf + 2 * z0) * GB;
@@ -116,17 +112,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) acc[ci][tx][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto tr_frag = [&](const char* p0, int hi_off) -> bf16x8 {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + hi_off));
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, v);
-  };
-  s16x8 ones;
-  {
-    const short o = (r16 == 0) ? (short)0x3f80 : (short)0;
-    ones = s16x8{o, o, o, o, o, o, o, o};
-  }
+  const bf16x8 ones = bias_ones_frag(r16);
   const char* abase = smem + ((2 * ly) * WU_HZ + lz) * FS + tp * 8;                      // fine halo (plane 0, row 2 ly, entry lz)
   const char* bbase = smem + WU_FBYTES + (2 * nh) * 4096 + (ly * 8 + lz) * 32 + tp * 8;   // coarse block 2 nh, plane 0
   auto compute = [&]() {
@@ -134,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs
 #pragma unroll
     for (int p = 0; p < 4; ++p)
 #pragma unroll
-      for (int nb = 0; nb < 2; ++nb) bf[p][nb] = tr_frag(bbase + nb * 4096 + p * 1024, 2 * 8 * 32);
+      for (int nb = 0; nb < 2; ++nb) bf[p][nb] = tr16_frag(bbase + nb * 4096 + p * 1024, 2 * 8 * 32);
 #pragma unroll
     for (int ci = 0; ci < 5; ++ci) {
       if (ci < nco) {                                  // wave-uniform
@@ -143,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs
         const char* ab = abase + (ty * WU_HZ + ez) * FS;
 #pragma unroll
         for (int f = 0; f < WU_HX; ++f) {
-          const bf16x8 af = tr_frag(ab + f * (WU_HY * WU_HZ * FS), 4 * WU_HZ * FS);       // second half: coarse y + 2 = fine row + 4
+          const bf16x8 af = tr16_frag(ab + f * (WU_HY * WU_HZ * FS), 4 * WU_HZ * FS);       // second half: coarse y + 2 = fine row + 4
 #pragma unroll
           for (int tx = 0; tx < 3; ++tx) {
             if ((f - tx) % 2 != 0 || f - tx < 0 || f - tx > 6) continue;                  // fine plane f = 2 p + tx
@@ -158,17 +144,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_up_kernel(const WgradUpArgs
 #pragma unroll
       for (int p = 0; p < 4; ++p)
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) acc[4][0][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ones), bf[p][nb], acc[4][0][nb], 0, 0, 0);
+        for (int nb = 0; nb < 2; ++nb) acc[4][0][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, bf[p][nb], acc[4][0][nb], 0, 0, 0);
     }
   };
 
-  int t = blockIdx.x, tstride = gridDim.x, tlast = total_tiles;
-  if ((gridDim.x & 7) == 0) {          // each XCD walks one contiguous eighth of the tiles: neighbouring halos meet in its L2
-    const int chunk = (total_tiles + 7) / 8, xcd = blockIdx.x & 7;
-    t = xcd * chunk + (blockIdx.x >> 3);
-    tstride = gridDim.x >> 3;
-    tlast = (xcd + 1) * chunk < total_tiles ? (xcd + 1) * chunk : total_tiles;
-  }
+  const auto [first, tstride, tlast] = xcd_tile_seq([] { return blockIdx.x; }, gridDim.x, total_tiles);
+  int t = first;
   if constexpr (GW == 12) {       // the 4-byte gaps behind every 12-byte piece are never written again
     for (int i = tid; i < WU_FBYTES / 16; i += 256) *reinterpret_cast<uint32_t*>(smem + i * 16 + 12) = 0u;
     __syncthreads();
@@ -217,12 +198,7 @@ bool wgrad_up_eligible(const ctseg_wgrad_desc* d) {
   const int64_t fb = ((int64_t)d->Xi * d->Yi * d->Zi + (int64_t)d->Yi * d->Zi + d->Zi + 1) * d->g_ld * 2, cb = (int64_t)d->Xr * d->Yr * d->Zr * 128;
   if (fb >= (1ll << 29)) return false;      // piece offsets are kept shifted left by 2 beside their flags
   if (fb >= (1ll << 31) || cb >= (1ll << 31)) return false;
-  for (int j = 0; j < 27; ++j) {       // taps are indexed tx * 9 + ty * 3 + tz
-    const int tp = d->taps[j];
-    if ((int)(int8_t)(tp & 0xff) != j / 9 - 1 || (int)(int8_t)((tp >> 8) & 0xff) != (j / 3) % 3 - 1 || (int)(int8_t)((tp >> 16) & 0xff) != j % 3 - 1)
-      return false;
-  }
-  return true;
+  return taps_canonical_27(d);         // taps are indexed tx * 9 + ty * 3 + tz
 }
 
 static int wgrad_up_grid(const ctseg_wgrad_desc* d) {

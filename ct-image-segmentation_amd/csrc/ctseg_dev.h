@@ -165,6 +165,16 @@ __device__ __forceinline__ u32x4 load_row12_chunk(const char* p, bool second) {
   return u32x4{lo[0], lo[1], hi[0], hi[1]};
 }
 
+// One bf16 MFMA operand whose contraction index is the SLOW axis of the LDS image (voxels of a channels-last tile): two transposed
+// reads (ds_read_b64_tr_b16: 4 rows x 16 columns per 16-lane group) at p0 and p0 + hi_off, the second 16 rows further on.
+__device__ __forceinline__ bf16x8 tr16_frag(const char* p0, int hi_off) {
+  typedef __attribute__((ext_vector_type(8))) short s16x8;
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4)(p0 + hi_off));
+  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8, v);
+}
+
 // n consecutive elements, fp32 or 16-bit kind H by a runtime flag -> floats (n = 4 or 8; pointer aligned to n*size)
 template <typename H = BF16> __device__ __forceinline__ void load_n_as_float(const char* p, bool is_f32, int n, float* v) {
   if (is_f32) {

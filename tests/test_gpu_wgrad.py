@@ -35,9 +35,10 @@ Shapes that differ from the plain list, and why:
     any split count, so the case forces splits = 12 over 585 rows (64-row ranges: range 9 holds 9 rows, ranges 10 and 11 none).
 
 Not covered, with the reason the library gives:
-  * "head 12/12" .. "head 16/16" (conv_wgrad_head_kernel, the head kernel without the x-column reuse): wgrad_halo_variant picks it
-    only for taps out of canonical order, which GemmLayer never records; named on the CPU from a hand-made descriptor
-    (tests/test_abi_exports.py);
+  * "head 12/16" and "head 16/12" (conv_wgrad_head_kernel, the head kernel without the x-column reuse): wgrad_halo_variant picks
+    that kernel only for taps out of canonical order, which GemmLayer never records; "head 16/16" and "head 12/12" run below from
+    a recorded descriptor with its taps reversed, the mixed widths are the same staging template with one operand of each and are
+    named on the CPU from a hand-made descriptor (tests/test_abi_exports.py);
   * "halo 32x32": 16 -> <= 16 channels with rows neither 12 nor 16 wide (g_ld = 24, ...), which no activation of the host mirror
     has; named on the CPU likewise;
   * "generic 32/64/128 element-wise": named on the CPU; the element-wise staging code is the same template branch as the 16-column
@@ -303,6 +304,47 @@ def test_up_kernel_writes_the_bias_row_of_the_tightest_slab(monkeypatch):
     rw, _ = _grads(case.kind, case.k, x, dy, wshape, torch.float64)              # [ci][co][tap]
     assert torch.equal(tot[:432].view(27, 16, d.cn_pad)[:, :10, :64], rw.reshape(64, 10, 27).permute(2, 1, 0).float())
     assert torch.equal(tot[432, :64], x.sum((0, 2, 3, 4)))
+
+
+# ---- conv_wgrad_head_kernel: taps out of canonical order, called directly ----------------------------------------------------
+# 16 input channels do not fit a 12-wide row: "head 12/12" is the 10 -> 10 layer of HEAD_CASES (Cg = 16) with both rows 12 wide
+HEAD_REVERSED = [("head 16/16", _Case("x-column head 16/16", "conv", 16, 10, S1)),
+                 ("head 12/12", _Case("x-column head 12/12", "conv", 10, 10, S1, cg=16, x_ld=12, dy_ld=12))]
+
+
+@pytest.mark.parametrize("cap", [None, "3"], ids=["uncapped", "max_wg3"])
+@pytest.mark.parametrize("name,case", HEAD_REVERSED, ids=[c[0].replace(" ", "_") for c in HEAD_REVERSED])
+def test_head_kernel_on_reversed_taps_equals_the_x_column_kernel(name, case, cap, monkeypatch):
+    """The recorded descriptor of the canonical-order case with its 27 taps in reverse order runs conv_wgrad_head_kernel (taps in
+    any order); its reduced gradient over NaN-poisoned slabs is the x-column kernel's with the tap axis reversed, bit for bit (the
+    operands are integers: exact in any order), and the bias gradient is the same.  CTSEG_MAX_WG=3: several tiles per workgroup."""
+    case.setenv(monkeypatch, cap)
+    xs, ys, _ = case.sizes()
+    gen = torch.Generator().manual_seed(case.seed)
+    drv = case.driver()
+    xa, ga = case.acts(drv, _ints(xs, gen), _ints(ys, gen))          # (stay alive: the reversed descriptor reads them too)
+    d0 = drv.record(case.name, xa, ga)
+    gw, gb, _, _ = drv.go(poison=float("nan"))
+    assert bool((gw != 0).any()) and bool((gb != 0).any())
+    L = nat.lib()
+    d = type(d0).from_buffer_copy(d0)
+    assert d.ntaps == 27
+    for j in range(27):
+        d.taps[j] = d0.taps[26 - j]
+    assert L.ctseg_wgrad_pass_name(ctypes.byref(d)) == name.encode()
+    nslabs = L.ctseg_conv_wgrad_slabs(ctypes.byref(d))
+    assert nslabs > 0
+    ws = torch.full((nslabs, d.kpad_w, d.cn_pad), float("nan"), device=DEV)
+    d.ws = ws.data_ptr()
+    co, ci = gw.shape[:2]
+    dw = torch.full((co * ci * 27 + 8,), GRAD_SENTINEL, device=DEV)
+    db = torch.full((co + 8,), GRAD_SENTINEL, device=DEV)
+    nat.call("ctseg_conv_wgrad", d)
+    nat.call("ctseg_conv_wgrad_reduce", ws.data_ptr(), nslabs, d.kpad_w, d.cn_pad, ci, d.Cg, 27, 0, co, dw.data_ptr(), db.data_ptr())
+    torch.cuda.synchronize()
+    assert torch.equal(dw[:co * ci * 27].cpu().view(co, ci, 27), gw.reshape(co, ci, 27).flip(-1)), (name, cap, "weight gradient")
+    assert torch.equal(db[:co].cpu(), gb), (name, cap, "bias gradient")
+    assert bool((dw[co * ci * 27:] == GRAD_SENTINEL).all()) and bool((db[co:] == GRAD_SENTINEL).all())
 
 
 # ---- Oracle B ----------------------------------------------------------------------------------------------------------------
