@@ -20,6 +20,8 @@ DEGREE = {
     3: predefined.windowed_degree_3,
     4: predefined.windowed_degree_4,
 }
+# device_warps=True: the degrees whose "train" side warps take their device restatement
+WARPED_DEGREE = {0: predefined.warped["degree_0"], 3: predefined.warped["windowed_degree_3"], 4: predefined.warped["windowed_degree_4"]}
 
 
 def _cat_masks(parts):
@@ -62,11 +64,11 @@ class DeviceBatches:
 
 class MiccaiDataModule2D(pl.LightningDataModule if pl is not None else object):
     def __init__(self, batch_size, transform_degree: int = None, enhanced=False, root: str = "storage", device="cuda",
-                 generator=None, **kwargs):
+                 generator=None, device_warps=False, **kwargs):
         super().__init__()
         self.batch_size = batch_size
         assert transform_degree in DEGREE.keys(), "Invalid transform degree passed"
-        self.transform = DEGREE[transform_degree]
+        self.transform = WARPED_DEGREE[transform_degree] if device_warps and transform_degree in WARPED_DEGREE else DEGREE[transform_degree]
         self.enhanced = enhanced
         self.root, self.device = root, device
         self.generator = generator                 # numpy Generator: the shuffle and the random crop / rot90 / flip

@@ -9,65 +9,11 @@
 // mask byte once for masks, labels, hist and present.
 // The arithmetic is the reference's, operation by operation (float64 where numpy holds float64), so nothing here may be contracted:
 #pragma clang fp contract(off)
-#include "ctseg_dev.h"
+#include "pipeline2d_common.h"
 
 namespace ctseg {
 
-constexpr int P2_KMAX = 15, P2_CMAX = 4, P2_COLS = 8;
 enum { P2_CROP = 0, P2_RESIZE = 1 };
-// table row of one sample (int64 each): image_off (elements into the image store), mask_off (bytes into the mask store; planes
-// [K][H][W]), H, W, y0, x0, k, flip
-enum { P2_IMG, P2_MSK, P2_H, P2_W, P2_Y0, P2_X0, P2_ROT, P2_FLIP };
-
-struct Pipe2dWin {
-  double lo[P2_CMAX], hi[P2_CMAX], den[P2_CMAX];      // den = hi - lo + 1e-8, formed in double as Python forms it
-  float mean[P2_CMAX], denom[P2_CMAX];
-  int C, shift, normalize;
-};
-
-template <typename T> struct Vec4;                     // 4 consecutive elements at the alignment of ONE element
-template <> struct Vec4<uint8_t> { typedef uint8_t type __attribute__((ext_vector_type(4), aligned(1))); };
-template <> struct Vec4<short> { typedef short type __attribute__((ext_vector_type(4), aligned(2))); };
-template <> struct Vec4<float> { typedef float type __attribute__((ext_vector_type(4), aligned(4))); };
-
-// v[q] = p[q * step], q < n.  step = +-1 with all four wanted: one vector load (from p - 3 and reversed for -1)
-template <typename T> __device__ __forceinline__ void load4(const T* p, int64_t step, int n, T* v) {
-  using V = typename Vec4<T>::type;
-  if (n == 4 && step == 1) {
-    const V t = *reinterpret_cast<const V*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else if (n == 4 && step == -1) {
-    const V t = *reinterpret_cast<const V*>(p - 3);
-    v[0] = t[3]; v[1] = t[2]; v[2] = t[1]; v[3] = t[0];
-  } else {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) v[q] = q < n ? p[q * step] : T(0);
-  }
-}
-
-// apply_window (transforms_2d.py:97-107) as numpy evaluates it: a float32 array stays float32 (bounds and divisor cast to float32),
-// an integer array goes through float64.  The caller holds the result as float64 (WindowedChannels writes into a float64 array).
-template <typename TI> __device__ __forceinline__ double window_value(TI raw, const Pipe2dWin& w, int c) {
-  if constexpr (sizeof(TI) == 4) {
-    float v = fminf(fmaxf((float)raw, (float)w.lo[c]), (float)w.hi[c]);
-    if (w.shift) v = (v - (float)w.lo[c]) / (float)w.den[c];
-    return (double)v;
-  } else {
-    double v = fmin(fmax((double)raw, w.lo[c]), w.hi[c]);
-    if (w.shift) v = (v - w.lo[c]) / w.den[c];
-    return v;
-  }
-}
-
-// A.Normalize: astype(float32), -= mean, *= reciprocal(std): two fp32 roundings
-__device__ __forceinline__ float normalize_value(double v, const Pipe2dWin& w, int c) {
-  float f = (float)v;
-  if (w.normalize) {
-    f = f - w.mean[c];
-    f = f * w.denom[c];
-  }
-  return f;
-}
 
 // bilinear source of one axis (half-pixel centres): first tap s and the float32 weight of tap s + 1
 __device__ __forceinline__ void lin_src(int d, double scale, int in, int& s, float& wt) {
@@ -121,14 +67,10 @@ __global__ __launch_bounds__(256) void pipeline2d_kernel(const TI* __restrict__ 
   int64_t base = 0, si = 0, sj = 0;
   if (MODE == P2_CROP) {
     const int64_t Hc = (rot & 1) ? Wo : Ho, Wc = (rot & 1) ? Ho : Wo;
-    int64_t cy0, cx0, yi, yj, xi, xj;                  // crop row = cy0 + yi*i + yj*j', crop column = cx0 + xi*i + xj*j'
-    if (rot == 0) { cy0 = 0; yi = 1; yj = 0; cx0 = 0; xi = 0; xj = 1; }
-    else if (rot == 1) { cy0 = 0; yi = 0; yj = 1; cx0 = Wc - 1; xi = -1; xj = 0; }
-    else if (rot == 2) { cy0 = Hc - 1; yi = -1; yj = 0; cx0 = Wc - 1; xi = 0; xj = -1; }
-    else { cy0 = Hc - 1; yi = 0; yj = -1; cx0 = 0; xi = 1; xj = 0; }
-    base = (y0 + cy0) * W64 + (x0 + cx0);
-    si = yi * W64 + xi;
-    sj = yj * W64 + xj;
+    const RotWalk r = rot_walk(rot, Hc, Wc);
+    base = (y0 + r.cy0) * W64 + (x0 + r.cx0);
+    si = r.yi * W64 + r.xi;
+    sj = r.yj * W64 + r.xj;
     if (flip) { base += (int64_t)(Wo - 1) * sj; sj = -sj; }
   }
   const double scy = (double)H / (double)Ho, scx = (double)W / (double)Wo;      // RESIZE: In / Out per axis
@@ -139,8 +81,7 @@ __global__ __launch_bounds__(256) void pipeline2d_kernel(const TI* __restrict__ 
   const bool want_lab = labels_out != nullptr || hist != nullptr;
   const int gpr = (Wo + 3) / 4;                          // groups per output row
   const int64_t ngroups = (int64_t)Ho * gpr, So = (int64_t)Ho * Wo;
-  unsigned int pres = 0u;
-  int bg = 0;
+  MaskTally tally;
 
   for (int64_t g = blockIdx.x * (int64_t)blockDim.x + tid; g < ngroups; g += (int64_t)gridDim.x * blockDim.x) {
     const int oy = (int)(g / gpr), ox0 = (int)(g % gpr) * 4;
@@ -184,16 +125,7 @@ __global__ __launch_bounds__(256) void pipeline2d_kernel(const TI* __restrict__ 
 #pragma unroll
       for (int c = 0; c < P2_CMAX; ++c) {
         if (c < win.C) {
-          float* o = image_out + ((int64_t)b * win.C + c) * So + dst;
-          f32x4 r;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) r[q] = normalize_value(val[c][q], win, c);
-          if (img_vec) {
-            *reinterpret_cast<f32x4*>(o) = r;
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) if (q < n) o[q] = r[q];
-          }
+          store_image4(image_out + ((int64_t)b * win.C + c) * So + dst, val[c], win, c, n, img_vec);
         }
       }
     }
@@ -217,57 +149,17 @@ __global__ __launch_bounds__(256) void pipeline2d_kernel(const TI* __restrict__ 
 #pragma unroll
           for (int q = 0; q < 4; ++q) m[q] = p[sxm[q]];
         }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (q < n) {
-            if (m[q] == 1) pres |= 1u << k;
-            const int val = (int)m[q] * (k + 1);
-            lab[q] = val > lab[q] ? val : lab[q];
-          }
-        }
-        if (masks_out != nullptr) {
-          uint8_t* o = masks_out + ((int64_t)b * K + k) * So + dst;
-          if (msk_vec) {
-            *reinterpret_cast<uint32_t*>(o) = (uint32_t)m[0] | ((uint32_t)m[1] << 8) | ((uint32_t)m[2] << 16) | ((uint32_t)m[3] << 24);
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) if (q < n) o[q] = m[q];
-          }
-        }
+        tally.plane(m, n, k, lab);
+        if (masks_out != nullptr) store_bytes4(masks_out + ((int64_t)b * K + k) * So + dst, m[0], m[1], m[2], m[3], n, msk_vec);
       }
       if (want_lab) {
-        if (labels_out != nullptr) {
-          uint8_t* o = labels_out + (int64_t)b * So + dst;
-          if (msk_vec) {
-            *reinterpret_cast<uint32_t*>(o) = (uint32_t)(lab[0] & 0xff) | ((uint32_t)(lab[1] & 0xff) << 8) |
-                                              ((uint32_t)(lab[2] & 0xff) << 16) | ((uint32_t)(lab[3] & 0xff) << 24);
-          } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) if (q < n) o[q] = (uint8_t)lab[q];
-          }
-        }
-        // background is nearly all of a CT slice, and 64 lanes adding to ONE LDS word serialise: count it per thread
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (q < n) {
-            if (lab[q] == 0) ++bg;
-            else if (lab[q] <= K) atomicAdd(&s_h[lab[q]], 1u);
-          }
-        }
+        if (labels_out != nullptr) store_bytes4(labels_out + (int64_t)b * So + dst, lab[0], lab[1], lab[2], lab[3], n, msk_vec);
+        tally.count(lab, n, K, s_h);
       }
     }
   }
 
-  // wave reduction, then one atomic per workgroup and class (squash_masks_kernel's pattern)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { bg += __shfl_xor(bg, o, 64); pres |= __shfl_xor(pres, o, 64); }
-  if ((tid & 63) == 0) {
-    if (bg) atomicAdd(&s_h[0], (unsigned)bg);
-    if (pres) atomicOr(&s_pres, pres);
-  }
-  __syncthreads();
-  if (hist != nullptr && tid <= K && s_h[tid] != 0u) atomicAdd(&hist[(int64_t)b * (K + 1) + tid], (unsigned long long)s_h[tid]);
-  if (present != nullptr && tid < K && ((s_pres >> tid) & 1u)) atomicOr(&present[(int64_t)b * K + tid], 1);
+  tally.flush(s_h, &s_pres, K, tid, hist ? hist + (int64_t)b * (K + 1) : nullptr, present ? present + (int64_t)b * K : nullptr);
 }
 
 // the host's copy of the table, row by row: what the kernel would skip is an error here
@@ -314,17 +206,8 @@ extern "C" int ctseg_pipeline2d_batch(const void* image_store, int32_t image_dty
   CTSEG_REQUIRE(((uintptr_t)image_out % 4) == 0 && ((uintptr_t)image_store % (image_dtype == CTSEG_F32 ? 4 : image_dtype == CTSEG_I16 ? 2 : 1)) == 0,
                 "pipeline2d_batch: unaligned image pointer");
   if (check_table(table_host, B, K, mode, Ho, Wo, image_store != nullptr, image_elems, mask_store != nullptr, mask_bytes)) return -1;
-  Pipe2dWin w = {};
-  w.C = image_store ? C : 0;
-  w.shift = shift != 0;
-  w.normalize = mean != nullptr;
-  for (int c = 0; c < w.C; ++c) {
-    CTSEG_REQUIRE(win_hi[c] > win_lo[c], "pipeline2d_batch: window %d is empty", c);
-    w.lo[c] = (double)win_lo[c];
-    w.hi[c] = (double)win_hi[c];
-    w.den[c] = (double)(win_hi[c] - win_lo[c]) + 1e-8;
-    if (mean) { w.mean[c] = mean[c]; w.denom[c] = denom[c]; }
-  }
+  Pipe2dWin w;
+  if (fill_windows(w, "pipeline2d_batch", image_store ? C : 0, win_lo, win_hi, shift, mean, denom)) return -1;
   const int64_t ngroups = (int64_t)Ho * ((Wo + 3) / 4);
   int64_t blocks = (ngroups + 255) / 256;
   if (blocks > 64) blocks = 64;

@@ -453,6 +453,35 @@ int ctseg_pipeline2d_batch(const void* image_store, int32_t image_dtype, int64_t
                            const float* mean, const float* denom, float* image_out, uint8_t* masks_out, uint8_t* labels_out,
                            int64_t* hist, int32_t* present, void* stream);
 
+/* The warping presets (degree_0, windowed_degree_3, windowed_degree_4 "train") on the device, three launches per batch:
+ * window -> A.RandomCrop -> A.ElasticTransform or A.GridDistortion -> rot90 / flip -> normalize, with ctseg_pipeline2d_batch's
+ * window, normalize and mask-side arithmetic and its outputs.  table / table_host are int64 [B][19] rows: the 8 columns of
+ * ctseg_pipeline2d_batch (the crop is always Ho x Wo at (y0, x0); k and flip turn the WARPED crop), then
+ *   kind (0 NONE, 1 ELASTIC, 2 GRID), seed, the INVERSE 2x3 affine matrix M00 M01 M02 M10 M11 M12 as float64 bit patterns,
+ *   xx_off, yy_off (elements into xx / yy: Wo and Ho float32 map values of a GRID sample), slot (ELASTIC: index of the sample's
+ *   fields, rising from 0 below n_slots)
+ *   fields  per ELASTIC sample and field f (0: dx, 1: dy): noise(i, j) = 2 u - 1, u = (z >> 11) * 2^-53 with z the splitmix64 mix
+ *           of seed + ((f << 40 | i << 20 | j) + 1) * 0x9E3779B97F4A7C15; separable blur in float64, axis 0 then axis 1, border
+ *           "reflect" (d c b a | a b c d, any distance), out[l] = in[l] w[0] + sum_{k=1..radius} (in[l-k] + in[l+k]) w[k] in that
+ *           order; fields[slot][f] = (float)(blur * alpha).  gauss_w: DEVICE float64 [radius + 1], normalised by the caller.
+ *           field_tmp: float64 [n_slots][2][Ho][Wo], fields: float32 of the same shape.
+ *   pass 1  inter = float64 [B][C][Ho][Wo] windowed crop, then u8 [B][K][Ho][Wo] mask bytes.  ELASTIC: cv2.warpAffine of the crop,
+ *           border REFLECT_101 on the crop: X = (lrint((M01 y + M02) 1024) + 16 + lrint(M00 x 1024)) >> 5 (Y from M10, M11, M12;
+ *           lrint saturates to int32), sx = X >> 5, fx = (X & 31) / 32; masks nearest with + 512 and >> 10.
+ *   pass 2  cv2.remap of inter, border REFLECT_101: ELASTIC map_x = (float)(c + dx[r][c]), map_y = (float)(r + dy[r][c]); GRID
+ *           map_x = xx[c], map_y = yy[r]; NONE a copy.  Bilinear: sx = lrint(map_x * 32) in float32 (half to even), ix = sx >> 5,
+ *           fx = (sx & 31) / 32; nearest: lrint(map_x).  Both bilinear steps: float32 weights (1-fx)(1-fy), fx(1-fy), (1-fx)fy,
+ *           fx fy, v = s00 w0 + s01 w1 + s10 w2 + s11 w3 in float64, left to right.
+ * Ho, Wo <= 256 and max(Ho, Wo) + 2 radius <= 6144.  launches: bit 0 fields, bit 1 pass 1, bit 2 pass 2 (7: all of them).  The
+ * host table is validated before any launch; the kernels repeat the range checks and leave a refused sample untouched. */
+int ctseg_pipeline2d_warp_batch(const void* image_store, int32_t image_dtype, int64_t image_elems, const uint8_t* mask_store,
+                                int64_t mask_bytes, const int64_t* table, const int64_t* table_host, int32_t B, int32_t K, int32_t Ho,
+                                int32_t Wo, int32_t C, const int32_t* win_lo, const int32_t* win_hi, int32_t shift, const float* mean,
+                                const float* denom, const double* gauss_w, int32_t radius, double alpha, const float* xx,
+                                int64_t xx_elems, const float* yy, int64_t yy_elems, float* fields, double* field_tmp, int32_t n_slots,
+                                void* inter, int64_t inter_bytes, float* image_out, uint8_t* masks_out, uint8_t* labels_out,
+                                int64_t* hist, int32_t* present, int32_t launches, void* stream);
+
 /* Sliding-window inference (BASELINE.json configs[4]).  The reference has no inferer (grep: 0 hits); the
  * semantics are those of MONAI 0.3 `monai.inferers.sliding_window_inference`, the companion of the `monai.networks.nets.UNet`
  * the reference builds at capstone/volumetric/base_trainer.py:65-72.

@@ -9,6 +9,13 @@ Bytes are algorithmic: every source byte the outputs depend on, once, plus every
 the whole raw slice for the bilinear image, one byte per output pixel and mask for the nearest masks).
 
   python tools/bench_input_pipeline2d.py --with-3d --out profiles/pipeline2d.json
+
+--warped-out FILE also times the warping presets (predefined.warped: degree_0, windowed_degree_3, windowed_degree_4 "train";
+ctseg_pipeline2d_warp_batch) under the same conditions, with the CROP preset alternating in the same rounds as the yardstick: the
+whole call of three launches and each launch alone (bit 0 fields, bit 1 pass 1, bit 2 pass 2; each figure includes the table and
+map-table uploads of a call, the intermediate is allocated once), and the share of samples of each kind in the drawn batch.
+
+  python tools/bench_input_pipeline2d.py --warped-out profiles/pipeline2d_warp.json
 """
 import argparse
 import json
@@ -24,7 +31,51 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "ct-image-segmentation_amd"))
 
 from capstone_amd.transforms import predefined  # noqa: E402
+from capstone_amd.transforms import warp2d  # noqa: E402
 from capstone_amd.transforms.pipeline2d import CROP, SliceStore2D, pipeline2d_batch  # noqa: E402
+
+
+def bench_warped(a, store, idx, timed, crop_variant):
+    """the warped presets and the CROP yardstick, alternating; ms per batch (median round) of the three launches and of each alone"""
+    jobs = {}
+    for name, preset in predefined.warped.items():
+        pipe = preset["train"]
+        rows = store.table[idx]
+        params = pipe.draw_params(rows[:, 2:4], np.random.default_rng(1))
+        table, xx, yy = pipe.build_table(rows, params)
+        el = pipe.elastic
+        kw = dict(sigma=el.sigma, alpha=el.alpha, xx=xx, yy=yy, want_masks=True, want_present=True)
+        args = (store, table, pipe.size, pipe.windows, pipe.shift, pipe.mean, pipe.denom)
+        buffers = warp2d.pipeline2d_warp_batch(*args, **kw)[5]
+        kinds = np.bincount(table[:, 8], minlength=3) / len(table)
+        jobs[name] = (args, kw, buffers, {"none": kinds[0], "elastic": kinds[1], "grid": kinds[2]})
+    parts = {"three_launches": 7, "fields": warp2d.FIELDS, "pass1": warp2d.PASS1, "pass2": warp2d.PASS2}
+
+    def run(job, launches):
+        args, kw, buffers, _ = job
+        return warp2d.pipeline2d_warp_batch(*args, launches=launches, buffers=buffers, **kw)
+
+    for job in jobs.values():
+        for _ in range(a.warmup):
+            for launches in parts.values():
+                run(job, launches)
+    torch.cuda.synchronize()
+    times = {name: {part: [] for part in parts} for name in jobs}
+    crop_ms = []
+    for _ in range(a.rounds):
+        crop_ms.append(timed(crop_variant[0], crop_variant[1], crop_variant[2]))
+        for name, job in jobs.items():
+            for part, launches in parts.items():
+                times[name][part].append(timed(lambda j, l: run(j, l), job, launches))
+    res = {"crop_masks9_ms_per_batch_launch": statistics.median(crop_ms), "crop_ms_min_max": [min(crop_ms), max(crop_ms)], "presets": {}}
+    for name, job in jobs.items():
+        r = {"kind_share": job[3]}
+        for part in parts:
+            r[f"ms_{part}"] = statistics.median(times[name][part])
+            r[f"ms_{part}_min_max"] = [min(times[name][part]), max(times[name][part])]
+        r["times_crop"] = r["ms_three_launches"] / res["crop_masks9_ms_per_batch_launch"]
+        res["presets"][name] = r
+    return res
 
 
 def main():
@@ -37,6 +88,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--with-3d", action="store_true", help="run tools/bench_input_pipeline.py (the 3-D kernel) in a child process too")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--warped-out", default=None, help="also time the warping presets and write their figures here")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     rng = np.random.default_rng(12342)
@@ -97,6 +149,11 @@ def main():
         out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_input_pipeline.py")], check=True, capture_output=True,
                              text=True, timeout=300).stdout
         res["resize3d_to_hwd_same_box"] = json.loads(out.strip().splitlines()[-1])
+    if a.warped_out:
+        p, table, _ = variants["crop_masks9"]
+        res["warped"] = bench_warped(a, store, idx, timed, (bare, p, table))
+        with open(a.warped_out, "w") as f:
+            f.write(json.dumps({"workload": res["workload"], **res["warped"]}) + "\n")
     line = json.dumps(res)
     print(line)
     if a.out:
