@@ -97,7 +97,7 @@ class ConvPassDriver:
                                [(mod.weight, mod.bias, mod.out_channels)], cg or (cin if cin % e else rup(cin, e)),
                                need_dgrad=(cin % e == 0))
         self.plan.packer.finalize()
-        self.desc = None
+        self.desc = self.prog = None
 
     def act(self, x, ld=None):
         cin = x.shape[1]
@@ -107,7 +107,13 @@ class ConvPassDriver:
         self.desc = self.plan.prog[-1][2][0]
         name = nat.lib().ctseg_conv_pass_name(self.desc)
         assert name is not None and name.decode() == family, (name, family)
+        self.prog = list(self.plan.prog)
         self.plan.run()
+        torch.cuda.synchronize()
+
+    def replay(self):
+        """runs the program of the last pass again, as recorded (same descriptor, same buffers)"""
+        Plan.run(self.prog, nat.stream_ptr())
         torch.cuda.synchronize()
 
     def fwd(self, family, xa, **extras):
@@ -125,6 +131,29 @@ class ConvPassDriver:
         out = self.layer.emit_dgrad(ga, **extras)
         self._go(family)
         return out
+
+
+ACT_SENTINEL = -12288.0      # -3 * 2^12: exact in bf16, fp16 and fp32
+
+
+def sentinel_act(dims, C, dt, device, ld, c0=0):
+    """an output Act the caller prepares: ``C`` channels from column ``c0`` of rows ``ld`` wide, every element of the buffer set to
+    ACT_SENTINEL (what a pass leaves of it shows which columns it wrote)"""
+    buf = new_act(*dims, ld, dt, device, ld=ld)
+    buf.t.fill_(ACT_SENTINEL)
+    return buf.slice(c0, C) if (c0 or C != ld) else buf
+
+
+def wide_act(x, dt, device, c0, tail, fill):
+    """(N,C,*sp) cpu tensor -> Act that is the column slice [c0, c0 + C) of a buffer c0 + C + tail wide whose other columns hold
+    ``fill``: an operand as a pass gathers it from a wider tensor (a half of the skip concat)"""
+    if x.ndim == 4:
+        x = x.unsqueeze(-1)
+    N, C = x.shape[:2]
+    buf = new_act(N, x.shape[2], x.shape[3], x.shape[4], c0 + C + tail, dt, device, ld=c0 + C + tail)
+    buf.t.fill_(fill)
+    buf.t[..., c0:c0 + C].copy_(x.permute(0, 2, 3, 4, 1).to(device))
+    return buf.slice(c0, C)
 
 
 GRAD_SENTINEL = -12345.0
