@@ -1,8 +1,18 @@
 // Shared pieces of the forward implicit-GEMM convolution kernels: launch arguments (ConvKArgs, BstArgs), the backward-statistics
 // terms, XCD-ordered tile walks, the 2x8 patch lane <-> voxel map of the LDS-halo kernels, the parity-class tap order of the
 // transposed convolutions, the MFMA step and the epilogue of the gather kernels.
+// Host geometry and launch plumbing of the LDS-halo families: TileAxes (base of SwGeom, DownGeom, DownRGeom, Up8Geom) with its host
+// fill tile_axes_fill (the one place that holds the padding rule choosing the tile axes) and its tile walk tile_origin_abc;
+// sample_bytes (every 32-bit per-sample byte count and the limit checks on it; each check keeps its own threshold); with_storage /
+// with_flags (run-time dtype and flags -> template arguments of a launch).  Packed taps (tap_dx/dy/dz, taps_within,
+// taps_canonical_27) and tile_origin<TX,TY,TZ> of the (x, y, z)-ordered kernels are in ctseg_dev.h, shared with wgrad_common.h.
+// Left per kernel: staging loops, LDS layouts, MFMA loops, epilogues and the statistics flushes (their comments record what sharing
+// cost them in registers); the generic and ring kernels' row tables; x_launch's X_GO / X_BST ladders in conv_halo_x.hip (their legal
+// combinations are sparse: every arm carries its own `if constexpr` guard).
 #pragma once
 #include "ctseg_dev.h"
+
+#include <type_traits>
 
 namespace ctseg {
 
@@ -133,6 +143,75 @@ template <class Id> __device__ __forceinline__ TileSeq xcd_tile_seq(Id id, int g
     return {int(xcd * chunk + (id() >> 3)), groups >> 3, (xcd + 1) * chunk < total ? (xcd + 1) * chunk : total};
   }
   return {int(id()), groups, total};
+}
+
+// ---- tile axes of the LDS-halo kernels that may permute them -----------------------------------------------------------------------
+// A tile is ta x 8 x 8 voxels of the row grid along the tile axes (a, b, c), which run along the volume axes (pa, pb, pc).  The
+// leading fields of SwGeom, DownGeom, DownRGeom and Up8Geom.
+struct TileAxes {
+  int da, db, dc;            // extents of the row grid along the tile axes (a = the short axis)
+  int ia, ib, ic;            // gathered-tensor voxel strides of the tile axes
+  int oa, ob, oc;            // written-tensor voxel strides of the tile axes (already multiplied by sout)
+  int pa, pb, pc;            // which volume axis (0 = x, 1 = y, 2 = z) each tile axis runs along
+  int tbn, tcn, tiles;       // tiles along b, c; tiles per sample
+};
+
+// Candidate orders in the kernels' preference: (x,y,z) keeps z innermost; (z,x,y) puts the short tile axis along a shallow z; (y,x,z)
+// is the third choice of a 1-deep tile (conv_down_r.hip), which looks for the best 8 x 8 face.
+constexpr int TILE_ORDERS[3][3] = {{0, 1, 2}, {2, 0, 1}, {1, 0, 2}};
+
+// The first of the `norders` orders stands unless a later one pads the row grid to a strictly smaller volume.  (Padded volumes are
+// multiples of 64 voxels of a grid below 2^31: two different ones differ by 3e-8 of the grid or more; the 1e-9 only absorbs rounding.)
+static inline void tile_axes_fill(TileAxes& g, const ConvKArgs& a, int ta, int norders) {
+  const int dims[3] = {a.Xr, a.Yr, a.Zr};
+  const int istr[3] = {a.Yi * a.Zi, a.Zi, 1};
+  const int ostr[3] = {a.Yo * a.Zo * a.sout, a.Zo * a.sout, a.sout};
+  auto waste = [&](const int* p) {
+    const double full = (double)dims[0] * dims[1] * dims[2];
+    const double padded = (double)((dims[p[0]] + ta - 1) / ta * ta) * ((dims[p[1]] + 7) / 8 * 8) * ((dims[p[2]] + 7) / 8 * 8);
+    return padded / full;
+  };
+  const int* p = TILE_ORDERS[0];
+  double best = waste(p);
+  for (int i = 1; i < norders; ++i)
+    if (waste(TILE_ORDERS[i]) < best - 1e-9) { p = TILE_ORDERS[i]; best = waste(p); }
+  g.pa = p[0]; g.pb = p[1]; g.pc = p[2];
+  g.da = dims[g.pa]; g.db = dims[g.pb]; g.dc = dims[g.pc];
+  g.ia = istr[g.pa]; g.ib = istr[g.pb]; g.ic = istr[g.pc];
+  g.oa = ostr[g.pa]; g.ob = ostr[g.pb]; g.oc = ostr[g.pc];
+  g.tbn = (g.db + 7) / 8; g.tcn = (g.dc + 7) / 8;
+  g.tiles = ((g.da + ta - 1) / ta) * g.tbn * g.tcn;
+}
+
+// Tile id -> sample and first row-grid voxel (a0, b0, c0) of a TA x 8 x 8 tile: c fastest, or (A_FAST, TA = 1) the 1-deep axis fastest
+template <int TA, bool A_FAST = false> __device__ __forceinline__ TileOrigin tile_origin_abc(int t, const TileAxes& G) {
+  const int n = t / G.tiles;
+  int r = t - n * G.tiles;
+  if constexpr (A_FAST) {
+    const int ta = r % G.da; r /= G.da;
+    const int tc = r % G.tcn, tb = r / G.tcn;
+    return {n, ta * TA, tb * 8, tc * 8};
+  } else {
+    const int tc = r % G.tcn; r /= G.tcn;
+    const int tb = r % G.tbn, ta = r / G.tbn;
+    return {n, ta * TA, tb * 8, tc * 8};
+  }
+}
+
+// Bytes of one sample of an X x Y x Z tensor with rows of ld elements of esz bytes.  The kernels hold them in 32 bits: every
+// *_eligible / *_bst_slots compares this with its kernel's own limit before a launch narrows it.
+__host__ __device__ __forceinline__ int64_t sample_bytes(int X, int Y, int Z, int ld, int esz) { return (int64_t)X * Y * Z * ld * esz; }
+
+// Run-time storage kind (16-bit: F16, else BF16) and flags -> arguments of a generic lambda: f(BF16{} / F16{}, std::true_type{} /
+// std::false_type{} ...), one per flag in order, so that a launcher names its instantiation once: decltype(flag)::value.
+template <class F> static inline void with_flags(F&& f) { f(); }
+template <class F, class... B> static inline void with_flags(F&& f, bool b, B... rest) {
+  if (b) with_flags([&](auto... r) { f(std::true_type{}, r...); }, rest...);
+  else with_flags([&](auto... r) { f(std::false_type{}, r...); }, rest...);
+}
+template <class F, class... B> static inline void with_storage(int dtype, F&& f, B... flags) {
+  if (dtype == CTSEG_F16) with_flags([&](auto... r) { f(F16{}, r...); }, flags...);
+  else with_flags([&](auto... r) { f(BF16{}, r...); }, flags...);
 }
 
 // r16 -> (dy, z) inside a 2x8 patch:  A = {0,1,2,3,12,13,14,15} -> row0 z0..4, row1 z0..2 ; B = {4..11} -> row0 z5..7, row1 z3..7

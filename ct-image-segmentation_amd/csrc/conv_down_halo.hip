@@ -40,13 +40,8 @@ template <int VB> struct DownCfg {
   static constexpr int TOTAL = HALO + WRING + 8 * 2 * DH_CN * 4 + 64 * 4 + 64 * 4;      // ... + tap table + BST constants
 };
 
-struct DownGeom {
-  int da, db, dc;            // output (row grid) extents along the tile axes
+struct DownGeom : TileAxes {
   int xa, xb, xc;            // input extents along the tile axes
-  int ia, ib, ic;            // input voxel strides of the tile axes
-  int oa, ob, oc;            // output voxel strides of the tile axes
-  int pa, pb, pc;            // volume axis of each tile axis
-  int tbn, tcn, tiles;
 };
 
 // R12: the gathered rows are 12 elements wide (24 bytes: the <= 12-channel gradient of the head's transposed conv): staged in
@@ -89,7 +84,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
     int da1 = 1, db1 = 1, dc1 = 1;                          // phantom taps (zero weights) read the centre voxel
     if (tid < 27) {
       const int tp = K.taps[tid];
-      const int dv[3] = {(int)(int8_t)(tp & 0xff), (int)(int8_t)((tp >> 8) & 0xff), (int)(int8_t)((tp >> 16) & 0xff)};
+      const int dv[3] = {tap_dx(tp), tap_dy(tp), tap_dz(tp)};
       da1 = dv[G.pa] + 1; db1 = dv[G.pb] + 1; dc1 = dv[G.pc] + 1;
     }
     sTab[tid] = ((da1 * DH_HB + db1) * DH_HC + dc1) * 16;
@@ -115,21 +110,13 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
       g_lds[j] = pl * PLANE + slot16;
     }
   }
-  auto tile_origin = [&](int t, int& n, int& a0, int& b0, int& c0) {
-    n = t / G.tiles;
-    int r = t - n * G.tiles;
-    const int tc = r % G.tcn; r /= G.tcn;
-    const int tb = r % G.tbn; const int ta = r / G.tbn;
-    a0 = ta * TA; b0 = tb * 8; c0 = tc * 8;
-  };
   const int64_t in_sample = (int64_t)P.Xi * P.Yi * P.Zi, out_sample = (int64_t)P.Xo * P.Yo * P.Zo;
   RH rh[J];
   if constexpr (R12) {
     for (int i = tid; i < CF::HV; i += DH_NTHR) *reinterpret_cast<u32x2*>(sH + PLANE + i * 16 + 8) = u32x2{0u, 0u};
   }
   auto gload = [&](int t) {
-    int n, a0, b0, c0;
-    tile_origin(t, n, a0, b0, c0);
+    const auto [n, a0, b0, c0] = tile_origin_abc<TA>(t, G);
     if constexpr (R12) {
       // the input is exactly twice the row grid (host-checked): only the -1 taps of the first tile along an axis leave the volume;
       // what a partial tile reads past the grid feeds rows that are not stored (finite, or zero past the end of the sample)
@@ -333,8 +320,7 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
   __syncthreads();
   for (; t < last; t += stride) {
     const int tn = t + stride;
-    int n, a0, b0, c0;
-    tile_origin(t, n, a0, b0, c0);
+    const auto [n, a0, b0, c0] = tile_origin_abc<TA>(t, G);
     if (STATS) stat_run.enter(n, flush_stats);
     if constexpr (BST) {
       if (bst_run.enter(n, flush_bst)) bst_consts(n);
@@ -459,22 +445,9 @@ __global__ __launch_bounds__(DH_NTHR) void conv_down_halo_kernel(const ConvKArgs
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 static void down_geom(const ConvKArgs& a, int vb, DownGeom& g) {
-  const int ta = 4;
-  const int od[3] = {a.Xr, a.Yr, a.Zr}, id[3] = {a.Xi, a.Yi, a.Zi};
-  const int istr[3] = {a.Yi * a.Zi, a.Zi, 1}, ostr[3] = {a.Yo * a.Zo, a.Zo, 1};
-  auto waste = [&](int pa, int pb, int pc) {
-    const double padded = (double)((od[pa] + ta - 1) / ta * ta) * ((od[pb] + 7) / 8 * 8) * ((od[pc] + 7) / 8 * 8);
-    return padded / ((double)od[0] * od[1] * od[2]);
-  };
-  int pa = 0, pb = 1, pc = 2;
-  if (waste(2, 0, 1) < waste(0, 1, 2) - 1e-9) { pa = 2; pb = 0; pc = 1; }
-  g.pa = pa; g.pb = pb; g.pc = pc;
-  g.da = od[pa]; g.db = od[pb]; g.dc = od[pc];
-  g.xa = id[pa]; g.xb = id[pb]; g.xc = id[pc];
-  g.ia = istr[pa]; g.ib = istr[pb]; g.ic = istr[pc];
-  g.oa = ostr[pa]; g.ob = ostr[pb]; g.oc = ostr[pc];
-  g.tbn = (g.db + 7) / 8; g.tcn = (g.dc + 7) / 8;
-  g.tiles = ((g.da + ta - 1) / ta) * g.tbn * g.tcn;
+  tile_axes_fill(g, a, 4, 2);      // DownCfg<VB>::TA
+  const int id[3] = {a.Xi, a.Yi, a.Zi};
+  g.xa = id[g.pa]; g.xb = id[g.pb]; g.xc = id[g.pc];
 }
 
 bool conv_down_halo_eligible(const ConvKArgs& a, int dtype, int nclass) {
@@ -487,16 +460,11 @@ bool conv_down_halo_eligible(const ConvKArgs& a, int dtype, int nclass) {
   if (a.g_ld == 12 && (a.Xi != 2 * a.Xr || a.Yi != 2 * a.Yr || a.Zi != 2 * a.Zr)) return false;        // (only the -1 taps leave the volume)
   if (a.Xo != a.Xr || a.Yo != a.Yr || a.Zo != a.Zr) return false;
   if (2 * a.Xr - 1 > a.Xi + 1 || 2 * a.Yr - 1 > a.Yi + 1 || 2 * a.Zr - 1 > a.Zi + 1) return false;   // rows whose centre lies outside
-  if ((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * 2 >= (1ll << 31)) return false;
+  if (sample_bytes(a.Xi, a.Yi, a.Zi, a.g_ld, 2) >= (1ll << 31)) return false;
   if ((int64_t)a.Xr * a.Yr * a.Zr < 2048) return false;
   const ctseg_conv_class& k = a.cls[0];
   if (k.ntaps != 27 || k.kpad < 27 * a.Cg || (k.kpad % 64) != 0 || (k.w_off % 8) != 0) return false;
-  for (int j = 0; j < 27; ++j)
-    for (int s = 0; s < 24; s += 8) {
-      const int d = (int)(int8_t)((k.taps[j] >> s) & 0xff);
-      if (d < -1 || d > 1) return false;
-    }
-  return true;
+  return taps_within(k.taps, 27, -1, 1);
 }
 
 static int down_grid(const ConvKArgs& a, const DownGeom& g) {
@@ -516,7 +484,7 @@ int conv_down_halo_bst_slots(const ConvKArgs& a) {
   // 16-byte chunks of 8 channels: the written tensor(s) and y
   if ((a.bst.y_ld % 8) != 0 || ((uintptr_t)a.bst.y % 16) != 0 || (a.o_ld % 8) != 0 || ((uintptr_t)a.out % 16) != 0 || (a.Cn_store % 8) != 0) return 0;
   if (a.out2 != nullptr && ((a.o2_ld % 8) != 0 || (a.out2_col0 % 8) != 0 || ((uintptr_t)a.out2 % 16) != 0)) return 0;
-  if ((int64_t)a.Xo * a.Yo * a.Zo * a.bst.y_ld * 2 >= (1ll << 31)) return 0;
+  if (sample_bytes(a.Xo, a.Yo, a.Zo, a.bst.y_ld, 2) >= (1ll << 31)) return 0;
   return conv_down_halo_slots(a);
 }
 
@@ -527,21 +495,13 @@ void launch_conv_down_halo(ConvKArgs& a, hipStream_t st) {
   a.tiles = g.tiles;
   const int total = g.tiles * a.N;
   const dim3 grid((unsigned)down_grid(a, g), (unsigned)((a.Cn + DH_CN - 1) / DH_CN)), blk(DH_NTHR);
-  const bool stats = a.stats != nullptr;
-#define CTSEG_DH_GO(H, ST, R) hipLaunchKernelGGL((conv_down_halo_kernel<H, 32, ST, R>), grid, blk, 0, st, a, g, total)
-  const bool r12 = a.g_ld == 12;
   if (a.bst.part != nullptr) {        // (bf16, 12-wide gathered rows, no forward statistics, columns 32..63: conv_down_halo_bst_slots)
     hipLaunchKernelGGL((conv_down_halo_kernel<BF16, 32, false, true, 2>), grid, blk, 0, st, a, g, total);
     return;
   }
-  if (a.dtype == CTSEG_F16) {
-    if (stats) { if (r12) CTSEG_DH_GO(F16, true, true); else CTSEG_DH_GO(F16, true, false); }
-    else { if (r12) CTSEG_DH_GO(F16, false, true); else CTSEG_DH_GO(F16, false, false); }
-  } else {
-    if (stats) { if (r12) CTSEG_DH_GO(BF16, true, true); else CTSEG_DH_GO(BF16, true, false); }
-    else { if (r12) CTSEG_DH_GO(BF16, false, true); else CTSEG_DH_GO(BF16, false, false); }
-  }
-#undef CTSEG_DH_GO
+  with_storage(a.dtype, [&](auto h, auto stats, auto r12) {
+    hipLaunchKernelGGL((conv_down_halo_kernel<decltype(h), 32, decltype(stats)::value, decltype(r12)::value>), grid, blk, 0, st, a, g, total);
+  }, a.stats != nullptr, a.g_ld == 12);
 }
 
 }  // namespace ctseg

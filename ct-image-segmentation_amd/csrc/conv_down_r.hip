@@ -34,14 +34,8 @@ constexpr int DR_SLOTS = DR_HA * DR_HB * DR_HC;                 // 867 voxel slo
 constexpr int DR_NP = (DR_SLOTS + 15) / 16, DR_PJ = (DR_NP + 7) / 8;   // 55 DMA pieces (16 slots) per tile, <= 7 per wave
 constexpr int DR_HALO = DR_NP * 1024;                           // 56 320 bytes
 
-struct DownRGeom {
-  int da, db, dc;            // output (row grid) extents along the tile axes (a = the 1-deep axis)
-  int ia, ib, ic;            // input voxel strides of the tile axes
-  int oa, ob, oc;            // output voxel strides of the tile axes
-  int pa, pb, pc;            // volume axis of each tile axis
-  int tbn, tcn, tiles;
+struct DownRGeom : TileAxes {   // a = the 1-deep axis
   int in_sample_bytes, out_sample_bytes, out2_sample_bytes;
-  int a_fast;                // tile order: the 1-deep axis fastest
 };
 
 // BST (round 4): backward InstanceNorm statistics of the written gradient (ConvKArgs::bst) for the waves whose 16 columns are channels
@@ -65,7 +59,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
     int da1 = 1, db1 = 1, dc1 = 1;
     if (tid < 27) {
       const int tp = K.taps[tid];
-      const int dv[3] = {(int)(int8_t)(tp & 0xff), (int)(int8_t)((tp >> 8) & 0xff), (int)(int8_t)((tp >> 16) & 0xff)};
+      const int dv[3] = {tap_dx(tp), tap_dy(tp), tap_dz(tp)};
       da1 = dv[G.pa] + 1; db1 = dv[G.pb] + 1; dc1 = dv[G.pc] + 1;
     }
     sTab[tid] = (da1 * DR_HB + db1) * DR_HC * 64;              // row part of the tap (the c part goes through the slot swap)
@@ -96,19 +90,10 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
   }
   const int hbias = (G.ia + G.ib + G.ic) * P.g_ld * 2;
 
-  auto tile_origin = [&](int t, int& n, int& a0, int& b0, int& c0) {
-    n = t / G.tiles;
-    int r = t - n * G.tiles;
-    // the 1-deep axis runs fastest: the workgroups of one XCD (consecutive tile ids) work on neighbours along a, which share one of
-    // their three input planes through that XCD's L2
-    int ta, tb, tc;
-    if (G.a_fast) { ta = r % G.da; r /= G.da; tc = r % G.tcn; tb = r / G.tcn; }
-    else { tc = r % G.tcn; r /= G.tcn; tb = r % G.tbn; ta = r / G.tbn; }
-    a0 = ta; b0 = tb * 8; c0 = tc * 8;
-  };
+  // the 1-deep axis runs fastest (tile_origin_abc<1, true>): the workgroups of one XCD (consecutive tile ids) work on neighbours
+  // along a, which share one of their three input planes through that XCD's L2
   auto dma = [&](int t, int buf) {
-    int n, a0, b0, c0;
-    tile_origin(t, n, a0, b0, c0);
+    const auto [n, a0, b0, c0] = tile_origin_abc<1, true>(t, G);
     const i32x4 rs = make_rsrc(P.in + (int64_t)n * G.in_sample_bytes - hbias, (uint32_t)(G.in_sample_bytes + hbias));
     const int soff = (2 * a0 * G.ia + 2 * b0 * G.ib + 2 * c0 * G.ic) * P.g_ld * 2;
     const int m = (a0 == 0 ? 1 : 0) | (b0 == 0 ? 2 : 0) | (c0 == 0 ? 4 : 0) | 8;
@@ -167,7 +152,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
   float brs[4] = {0.f, 0.f, 0.f, 0.f}, bnm[4] = {0.f, 0.f, 0.f, 0.f};                      // rstd, -mean * rstd of the lane's channels
   float b1[4] = {0.f, 0.f, 0.f, 0.f}, b2[4] = {0.f, 0.f, 0.f, 0.f}, b3 = 0.f;
   SampleRun bst_run;
-  const int y_sample_bytes = BST ? (int)((int64_t)P.Xo * P.Yo * P.Zo * P.bst.y_ld * 2) : 0;   // < 2^31 (host-checked)
+  const int y_sample_bytes = BST ? (int)sample_bytes(P.Xo, P.Yo, P.Zo, P.bst.y_ld, 2) : 0;   // < 2^31 (host-checked)
   auto bst_consts = [&](int n) {
     if (ywave) {
 #pragma unroll
@@ -206,8 +191,7 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();        // ... for every wave; and every wave is done reading the other buffer
     asm volatile("" ::: "memory");
-    int n, a0, b0, c0;
-    tile_origin(t, n, a0, b0, c0);
+    const auto [n, a0, b0, c0] = tile_origin_abc<1, true>(t, G);
     u32x2 yv[4] = {u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}, u32x2{0u, 0u}};
     if constexpr (BST) {
       if (bst_run.enter(n, flush_bst)) bst_consts(n);
@@ -280,24 +264,11 @@ __global__ __launch_bounds__(DR_NTHR) void conv_down_r_kernel(const ConvKArgs P,
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 static void down_r_geom(const ConvKArgs& a, DownRGeom& g) {
-  const int od[3] = {a.Xr, a.Yr, a.Zr};
-  const int istr[3] = {a.Yi * a.Zi, a.Zi, 1}, ostr[3] = {a.Yo * a.Zo, a.Zo, 1};
-  auto waste = [&](int pb, int pc) { return (double)((od[pb] + 7) / 8 * 8) * ((od[pc] + 7) / 8 * 8) / ((double)od[pb] * od[pc]); };
   // the 1-deep tile axis takes the volume axis whose removal leaves the least padding in the 8 x 8 face; c stays the innermost of the rest
-  int pa = 0, pb = 1, pc = 2;
-  double best = waste(1, 2);
-  if (waste(0, 1) < best - 1e-9) { pa = 2; pb = 0; pc = 1; best = waste(0, 1); }
-  if (waste(0, 2) < best - 1e-9) { pa = 1; pb = 0; pc = 2; }
-  g.pa = pa; g.pb = pb; g.pc = pc;
-  g.da = od[pa]; g.db = od[pb]; g.dc = od[pc];
-  g.ia = istr[pa]; g.ib = istr[pb]; g.ic = istr[pc];
-  g.oa = ostr[pa]; g.ob = ostr[pb]; g.oc = ostr[pc];
-  g.tbn = (g.db + 7) / 8; g.tcn = (g.dc + 7) / 8;
-  g.tiles = g.da * g.tbn * g.tcn;
-  g.in_sample_bytes = (int)((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * 2);
-  g.out_sample_bytes = (int)((int64_t)a.Xo * a.Yo * a.Zo * a.o_ld * 2);
-  g.out2_sample_bytes = a.out2 != nullptr ? (int)((int64_t)a.Xo * a.Yo * a.Zo * a.o2_ld * 2) : 0;
-  g.a_fast = getenv("CTSEG_DR_AFAST") != nullptr ? atoi(getenv("CTSEG_DR_AFAST")) : 1;
+  tile_axes_fill(g, a, 1, 3);
+  g.in_sample_bytes = (int)sample_bytes(a.Xi, a.Yi, a.Zi, a.g_ld, 2);
+  g.out_sample_bytes = (int)sample_bytes(a.Xo, a.Yo, a.Zo, a.o_ld, 2);
+  g.out2_sample_bytes = a.out2 != nullptr ? (int)sample_bytes(a.Xo, a.Yo, a.Zo, a.o2_ld, 2) : 0;
 }
 
 bool conv_down_r_eligible(const ConvKArgs& a, int dtype, int nclass) {
@@ -307,18 +278,13 @@ bool conv_down_r_eligible(const ConvKArgs& a, int dtype, int nclass) {
   if (a.Xo != a.Xr || a.Yo != a.Yr || a.Zo != a.Zr) return false;
   if (a.Xi != 2 * a.Xr || a.Yi != 2 * a.Yr || a.Zi != 2 * a.Zr) return false;      // (only the -1 taps of a first tile leave the volume)
   if (((int64_t)a.Xi * a.Yi * a.Zi + (int64_t)a.Yi * a.Zi + a.Zi + 1) * a.g_ld * 2 >= (1ll << 31)) return false;
-  if ((int64_t)a.Xo * a.Yo * a.Zo * 128 * 2 >= (1ll << 31)) return false;
+  if (sample_bytes(a.Xo, a.Yo, a.Zo, 128, 2) >= (1ll << 31)) return false;
   if ((int64_t)a.Xr * a.Yr * a.Zr < 2048) return false;
   if (a.out2 != nullptr ? ((a.out2_col0 % 16) != 0 || (a.o2_ld % 4) != 0 || a.o2_ld < 128 - a.out2_col0 || a.o_ld < a.out2_col0) : a.o_ld < 128) return false;
   if ((a.o_ld % 4) != 0) return false;
   const ctseg_conv_class& k = a.cls[0];
   if (k.ntaps != 27 || k.kpad < 27 * 32 || (k.kpad % 8) != 0 || (k.w_off % 8) != 0) return false;
-  for (int j = 0; j < 27; ++j)
-    for (int s = 0; s < 24; s += 8) {
-      const int d = (int)(int8_t)((k.taps[j] >> s) & 0xff);
-      if (d < -1 || d > 1) return false;
-    }
-  return true;
+  return taps_within(k.taps, 27, -1, 1);
 }
 
 static int down_r_grid(const ConvKArgs& a, const DownRGeom& g) {
@@ -336,7 +302,7 @@ int conv_down_r_bst_slots(const ConvKArgs& a) {
   if (a.dtype != CTSEG_BF16 || a.stats != nullptr || a.bias != nullptr) return 0;
   if (a.bst.C <= 0 || (a.bst.C % 16) != 0 || (a.bst.col0 % 16) != 0 || a.bst.col0 + a.bst.C > 128) return 0;
   if ((a.bst.y_ld % 4) != 0 || a.bst.y_ld < a.bst.C || ((uintptr_t)a.bst.y % 8) != 0) return 0;
-  if ((int64_t)a.Xo * a.Yo * a.Zo * a.bst.y_ld * 2 >= (1ll << 31)) return 0;
+  if (sample_bytes(a.Xo, a.Yo, a.Zo, a.bst.y_ld, 2) >= (1ll << 31)) return 0;
   return conv_down_r_slots(a);
 }
 
@@ -346,18 +312,13 @@ void launch_conv_down_r(ConvKArgs& a, hipStream_t st) {
   a.tiles = g.tiles;
   const int total = g.tiles * a.N;
   const dim3 grid((unsigned)down_r_grid(a, g)), blk(DR_NTHR);
-  const bool stats = a.stats != nullptr;
   if (a.bst.part != nullptr) {        // (bf16, no forward statistics: conv_down_r_bst_slots)
     hipLaunchKernelGGL((conv_down_r_kernel<BF16, false, true>), grid, blk, 0, st, a, g, total);
     return;
   }
-  if (a.dtype == CTSEG_F16) {
-    if (stats) hipLaunchKernelGGL((conv_down_r_kernel<F16, true>), grid, blk, 0, st, a, g, total);
-    else hipLaunchKernelGGL((conv_down_r_kernel<F16, false>), grid, blk, 0, st, a, g, total);
-  } else {
-    if (stats) hipLaunchKernelGGL((conv_down_r_kernel<BF16, true>), grid, blk, 0, st, a, g, total);
-    else hipLaunchKernelGGL((conv_down_r_kernel<BF16, false>), grid, blk, 0, st, a, g, total);
-  }
+  with_storage(a.dtype, [&](auto h, auto stats) {
+    hipLaunchKernelGGL((conv_down_r_kernel<decltype(h), decltype(stats)::value>), grid, blk, 0, st, a, g, total);
+  }, a.stats != nullptr);
 }
 
 }  // namespace ctseg

@@ -71,7 +71,7 @@ __global__ __launch_bounds__((HaloCfg<VB, NT>::NTHR)) void conv_halo_kernel(cons
     int d = 0;
     if (tid < K.ntaps) {
       const int tp = K.taps[tid];
-      d = ((int)(int8_t)(tp & 0xff) * H_HY + (int)(int8_t)((tp >> 8) & 0xff)) * H_HZ + (int)(int8_t)((tp >> 16) & 0xff);
+      d = (tap_dx(tp) * H_HY + tap_dy(tp)) * H_HZ + tap_dz(tp);
     }
     sDelta[tid] = d * 16;
   }
@@ -91,16 +91,8 @@ __global__ __launch_bounds__((HaloCfg<VB, NT>::NTHR)) void conv_halo_kernel(cons
   }
   const bool ld12 = VB == 32 && SZ == 2 && (P.g_ld & 7) != 0;   // workgroup-uniform
   const int tiles_per_sample = P.tiles;
-  auto tile_origin = [&](int t, int& n, int& x0, int& y0, int& z0) {
-    n = t / tiles_per_sample;
-    int r = t - n * tiles_per_sample;
-    const int tz = r % tzn; r /= tzn;
-    const int ty = r % tyn; const int tx = r / tyn;
-    x0 = tx * H_TX; y0 = ty * H_TY; z0 = tz * H_TZ;
-  };
   auto gload = [&](int t, u32x4 (&rh)[J]) {
-    int n, x0, y0, z0;
-    tile_origin(t, n, x0, y0, z0);
+    const auto [n, x0, y0, z0] = tile_origin<H_TX, H_TY, H_TZ>(t, tiles_per_sample, tyn, tzn);
     const char* base = P.in + ((((int64_t)n * P.Xi + x0) * P.Yi + y0) * P.Zi + z0) * P.g_ld * SZ;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
@@ -182,8 +174,7 @@ __global__ __launch_bounds__((HaloCfg<VB, NT>::NTHR)) void conv_halo_kernel(cons
     __syncthreads();
   };
   auto compute_tile = [&](int t, int buf) {
-    int n, x0, y0, z0;
-    tile_origin(t, n, x0, y0, z0);
+    const auto [n, x0, y0, z0] = tile_origin<H_TX, H_TY, H_TZ>(t, tiles_per_sample, tyn, tzn);
     if (STATS && n != stat_n) {
       if (stat_n >= 0) flush_stats(stat_n);
       stat_n = n;
@@ -315,15 +306,8 @@ bool conv_halo_eligible(const ConvKArgs& a, int dtype, int nclass) {
   // gathered rows: 16-byte chunked, or 12 bf16 wide (24 bytes) for the 32-byte-voxel kernel
   if (((a.g_ld * SZ) % 16 != 0 && !(vb == 32 && SZ == 2 && a.g_ld == 12)) || ((uintptr_t)a.in % 16) != 0) return false;
   if (a.Xr != a.Xi || a.Yr != a.Yi || a.Zr != a.Zi || a.Zr < 4) return false;
-  if ((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * SZ >= (1ll << 31)) return false;   // per-sample byte offsets are 32-bit
-  for (int j = 0; j < 27; ++j) {
-    const int tp = a.cls[0].taps[j];
-    for (int s = 0; s < 24; s += 8) {
-      const int d = (int)(int8_t)((tp >> s) & 0xff);
-      if (d < -1 || d > 1) return false;
-    }
-  }
-  return true;
+  if (sample_bytes(a.Xi, a.Yi, a.Zi, a.g_ld, SZ) >= (1ll << 31)) return false;   // per-sample byte offsets are 32-bit
+  return taps_within(a.cls[0].taps, 27, -1, 1);
 }
 
 int conv_halo_tiles(const ConvKArgs& a) {

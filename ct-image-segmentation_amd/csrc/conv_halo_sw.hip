@@ -54,13 +54,7 @@ template <int VB, bool UP> struct SwCfg {
   __host__ __device__ static constexpr int slot(int ha, int hb, int hc) { return ((ha - O) * LB + (hb - O)) * 10 + hc; }
 };
 
-struct SwGeom {
-  int da, db, dc;            // extents of the row grid along the tile axes (a = short axis)
-  int ia, ib, ic;            // gathered-tensor voxel strides of the tile axes
-  int oa, ob, oc;            // written-tensor voxel strides of the tile axes (already multiplied by sout)
-  int pa, pb, pc;            // which volume axis (0 = x, 1 = y, 2 = z) each tile axis runs along
-  int tbn, tcn, tiles;       // tiles along b, c; tiles per sample
-};
+struct SwGeom : TileAxes {};
 
 // BST: backward InstanceNorm statistics of the written gradient (ConvKArgs::bst) on the input-gradient passes (8-class 128 -> 32,
 // single-class 64 -> 64).  After the v_permlane16_swap of the store a lane holds 16-byte chunks (8 consecutive channels) of one
@@ -95,7 +89,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
       while (tid >= first + P.cls[c].ntaps) { first += P.cls[c].ntaps; ++c; }
       const int ti = tid - first;
       const int tp = P.cls[c].taps[ti];
-      int dv[3] = {(int)(int8_t)(tp & 0xff), (int)(int8_t)((tp >> 8) & 0xff), (int)(int8_t)((tp >> 16) & 0xff)};
+      int dv[3] = {tap_dx(tp), tap_dy(tp), tap_dz(tp)};
       d = ((dv[G.pa] * CF::LB + dv[G.pb]) * 10 + dv[G.pc]) * 16;
       wo = (int)(P.cls[c].w_off + (int64_t)ti * CF::CG);
       kp = P.cls[c].kpad;
@@ -129,19 +123,11 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
     asm volatile("" : "+v"(h));
     ha = h & 0xff; hb = (h >> 8) & 0xff; hc = h >> 16;
   };
-  auto tile_origin = [&](int t, int& n, int& a0, int& b0, int& c0) {
-    n = t / G.tiles;
-    int r = t - n * G.tiles;
-    const int tc = r % G.tcn; r /= G.tcn;
-    const int tb = r % G.tbn; const int ta = r / G.tbn;
-    a0 = ta * TA; b0 = tb * 8; c0 = tc * 8;
-  };
   const int64_t in_sample = (int64_t)P.Xi * P.Yi * P.Zi, out_sample = (int64_t)P.Xo * P.Yo * P.Zo;
   u32x4 rh[J];
   // (branch-free raw buffer loads measured no faster here: 0.171 -> 0.182 ms on the 128 -> 32 up pass, 0.094 -> 0.103 on 64 -> 64)
   auto gload = [&](int t) {
-    int n, a0, b0, c0;
-    tile_origin(t, n, a0, b0, c0);
+    const auto [n, a0, b0, c0] = tile_origin_abc<TA>(t, G);
     const char* base = P.in + (n * in_sample + (int64_t)a0 * G.ia + (int64_t)b0 * G.ib + (int64_t)c0 * G.ic) * P.g_ld * 2;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
@@ -536,8 +522,7 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
   __syncthreads();                                   // halo + stage 0 of the weights landed
   for (; t < last; t += stride) {
     const int tn = t + stride;
-    int n, a0, b0, c0;
-    tile_origin(t, n, a0, b0, c0);
+    const auto [n, a0, b0, c0] = tile_origin_abc<TA>(t, G);
     if (STATS && n != stat_n) {
       if (stat_n >= 0) flush_stats(stat_n);
       stat_n = n;
@@ -605,27 +590,8 @@ __global__ __launch_bounds__(SW_NTHR) void conv_halo_sw_kernel(const ConvKArgs P
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static bool sw_geom(const ConvKArgs& a, int vb, SwGeom& g) {
-  const int ta = (vb == 128 || a.sout == 2) ? 4 : 2;      // SwCfg<VB, UP>::TA
-  const int dims[3] = {a.Xr, a.Yr, a.Zr};
-  const int istr[3] = {a.Yi * a.Zi, a.Zi, 1};
-  const int ostr[3] = {a.Yo * a.Zo * a.sout, a.Zo * a.sout, a.sout};
-  auto waste = [&](int pa, int pb, int pc) {
-    const double full = (double)dims[0] * dims[1] * dims[2];
-    const double padded = (double)((dims[pa] + ta - 1) / ta * ta) * ((dims[pb] + 7) / 8 * 8) * ((dims[pc] + 7) / 8 * 8);
-    return padded / full;
-  };
-  // (a,b,c) = (x,y,z) keeps z innermost; (z,x,y) puts the short tile axis along a shallow z
-  int pa = 0, pb = 1, pc = 2;
-  if (waste(2, 0, 1) < waste(0, 1, 2) - 1e-9) { pa = 2; pb = 0; pc = 1; }
-  g.pa = pa; g.pb = pb; g.pc = pc;
-  g.da = dims[pa]; g.db = dims[pb]; g.dc = dims[pc];
-  g.ia = istr[pa]; g.ib = istr[pb]; g.ic = istr[pc];
-  g.oa = ostr[pa]; g.ob = ostr[pb]; g.oc = ostr[pc];
-  const int tan = (g.da + ta - 1) / ta;
-  g.tbn = (g.db + 7) / 8; g.tcn = (g.dc + 7) / 8;
-  g.tiles = tan * g.tbn * g.tcn;
-  return true;
+static void sw_geom(const ConvKArgs& a, int vb, SwGeom& g) {
+  tile_axes_fill(g, a, (vb == 128 || a.sout == 2) ? 4 : 2, 2);      // SwCfg<VB, UP>::TA
 }
 
 bool conv_halo_sw_eligible(const ConvKArgs& a, int dtype, int nclass) {
@@ -634,7 +600,7 @@ bool conv_halo_sw_eligible(const ConvKArgs& a, int dtype, int nclass) {
   if (!((vb == 128 && a.Cn == 64) || (vb == 256 && a.Cn == 32)) || a.Cn_store != a.Cn) return false;
   if ((a.g_ld % 8) != 0 || ((uintptr_t)a.in % 16) != 0 || ((uintptr_t)a.w % 16) != 0) return false;
   if (a.Xr != a.Xi || a.Yr != a.Yi || a.Zr != a.Zi) return false;
-  if ((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * 2 >= (1ll << 31)) return false;       // 32-bit per-sample byte offsets
+  if (sample_bytes(a.Xi, a.Yi, a.Zi, a.g_ld, 2) >= (1ll << 31)) return false;      // 32-bit per-sample byte offsets
   if ((int64_t)a.Xr * a.Yr * a.Zr < 2048) return false;                            // too few tiles to fill the chip: generic kernel
   const bool up = nclass == 8;
   if (up) {
@@ -649,11 +615,7 @@ bool conv_halo_sw_eligible(const ConvKArgs& a, int dtype, int nclass) {
     if (k.kpad < k.ntaps * a.Cg || (k.kpad % 8) != 0 || (k.w_off % 8) != 0) return false;
     if (k.w_off + (int64_t)a.Cn * k.kpad >= (1ll << 31)) return false;
     taps += k.ntaps;
-    for (int j = 0; j < k.ntaps; ++j)
-      for (int s = 0; s < 24; s += 8) {
-        const int d = (int)(int8_t)((k.taps[j] >> s) & 0xff);
-        if (d < (up ? 0 : -1) || d > 1) return false;
-      }
+    if (!taps_within(k.taps, k.ntaps, up ? 0 : -1, 1)) return false;
   }
   return taps == 27;
 }
@@ -674,7 +636,7 @@ int conv_halo_sw_bst_slots(const ConvKArgs& a, int nclass) {
   if (!((nclass == 8 && a.Cg == 128) || (nclass == 1 && a.Cg == 64))) return 0;
   if (a.bst.C != a.Cn || a.bst.col0 != 0 || a.Cn_store != a.Cn || (a.o_ld % 8) != 0 || ((uintptr_t)a.out % 16) != 0) return 0;
   if ((a.bst.y_ld % 8) != 0 || ((uintptr_t)a.bst.y % 16) != 0) return 0;
-  if ((int64_t)a.Xo * a.Yo * a.Zo * a.bst.y_ld * 2 >= (1ll << 31) || (int64_t)a.Xo * a.Yo * a.Zo * a.o_ld * 2 >= (1ll << 31)) return 0;
+  if (sample_bytes(a.Xo, a.Yo, a.Zo, a.bst.y_ld, 2) >= (1ll << 31) || sample_bytes(a.Xo, a.Yo, a.Zo, a.o_ld, 2) >= (1ll << 31)) return 0;
   return conv_halo_sw_slots(a);
 }
 
@@ -691,19 +653,10 @@ void launch_conv_halo_sw(ConvKArgs& a, int nclass, hipStream_t st) {
     else hipLaunchKernelGGL((conv_halo_sw_kernel<BF16, 128, false, false, true>), grid, blk, 0, st, a, g, total);
     return;
   }
-#define CTSEG_SW_LAUNCH(VB, UP, ST)                                                                                      \
-  do {                                                                                                                  \
-    if (a.dtype == CTSEG_F16) hipLaunchKernelGGL((conv_halo_sw_kernel<F16, VB, UP, ST>), grid, blk, 0, st, a, g, total); \
-    else hipLaunchKernelGGL((conv_halo_sw_kernel<BF16, VB, UP, ST>), grid, blk, 0, st, a, g, total);                     \
-  } while (0)
-  if (vb == 128) {
-    if (up) { if (stats) CTSEG_SW_LAUNCH(128, true, true); else CTSEG_SW_LAUNCH(128, true, false); }
-    else { if (stats) CTSEG_SW_LAUNCH(128, false, true); else CTSEG_SW_LAUNCH(128, false, false); }
-  } else {
-    if (up) { if (stats) CTSEG_SW_LAUNCH(256, true, true); else CTSEG_SW_LAUNCH(256, true, false); }
-    else { if (stats) CTSEG_SW_LAUNCH(256, false, true); else CTSEG_SW_LAUNCH(256, false, false); }
-  }
-#undef CTSEG_SW_LAUNCH
+  with_storage(a.dtype, [&](auto h, auto vb128, auto up_, auto stats_) {
+    constexpr int VB = decltype(vb128)::value ? 128 : 256;
+    hipLaunchKernelGGL((conv_halo_sw_kernel<decltype(h), VB, decltype(up_)::value, decltype(stats_)::value>), grid, blk, 0, st, a, g, total);
+  }, vb == 128, up, stats);
 }
 
 }  // namespace ctseg

@@ -369,16 +369,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     __syncthreads();
   };
 
-  struct Org { int n, x0, y0, z0; };
-  auto tile_origin = [&](int t) -> Org {
-    Org o;
-    o.n = t / G.tiles;
-    int r = t - o.n * G.tiles;
-    const int tz = r % G.tzn; r /= G.tzn;
-    const int ty = r % G.tyn; const int tx = r / G.tyn;
-    o.x0 = tx * X_TX; o.y0 = ty * X_TY; o.z0 = tz * X_TZ;
-    return o;
-  };
+  using Org = TileOrigin;
   auto range_mask = [](int lo, int hi, int nbits) -> uint32_t {   // bits lo..hi (clamped to 0..nbits-1)
     lo = lo < 0 ? 0 : lo;
     hi = hi > nbits - 1 ? nbits - 1 : hi;
@@ -944,7 +935,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
   f32x4 accA[NT][X_TX], accB[NT][X_TX];
   u32x2 caddA[NT][X_TX], caddB[NT][X_TX];
   Ep ep;
-  Org ocur = tile_origin(first);
+  Org ocur = tile_origin<X_TX, X_TY, X_TZ>(first, G.tiles, G.tyn, G.tzn);
   Org onext = ocur;
   int t = first;
   if constexpr (CE) {
@@ -967,7 +958,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
       if constexpr (R12) { if (!(X_ABL & 256)) __syncthreads(); }
       else { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
       if (more) {
-        onext = tile_origin(t + stride);
+        onext = tile_origin<X_TX, X_TY, X_TZ>(t + stride, G.tiles, G.tyn, G.tzn);
         if constexpr (R12) gload(onext); else dma(onext, buf ^ 1);
         lab_next = ce_label(onext);
       }
@@ -998,7 +989,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     gload(ocur);
     sstore(0, ocur);
     __syncthreads();
-    if (t + stride < last) { onext = tile_origin(t + stride); gload(onext); }
+    if (t + stride < last) { onext = tile_origin<X_TX, X_TY, X_TZ>(t + stride, G.tiles, G.tyn, G.tzn); gload(onext); }
     compute_tile(F_{}, 0, accA, caddA, ep, accA, caddA);
     if (t + stride < last) sstore(1, onext);
     __syncthreads();
@@ -1007,7 +998,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // DMA pieces landed; the weight fragments this wave staged are written
     __builtin_amdgcn_s_barrier();
     cadd_early(caddA);
-    if (t + stride < last) { onext = tile_origin(t + stride); dma(onext, 1); }
+    if (t + stride < last) { onext = tile_origin<X_TX, X_TY, X_TZ>(t + stride, G.tiles, G.tyn, G.tzn); dma(onext, 1); }
     compute_tile(F_{}, 0, accA, caddA, ep, accA, caddA);
   }
   // invariant at the loop head: set A holds the finished multiplies of tile t (origin ocur); tile t+stride (origin onext) is in
@@ -1026,7 +1017,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     const bool more = t + stride < last;
     cadd_early(ccur);
     if (more || BST) {
-      onext = tile_origin(more ? t + stride : t);
+      onext = tile_origin<X_TX, X_TY, X_TZ>(more ? t + stride : t, G.tiles, G.tyn, G.tzn);
       if constexpr (R12) gload(onext, more); else dma(onext, buf ^ 1, more);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -1058,18 +1049,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
 
 // -------------------------------------------------------------------------------------------------------------------------------------
 static int x_tap_order(const ConvKArgs& a) {   // 0: canonical (offset = t - 1 per axis, x slowest), 1: every offset negated, -1: neither
-  int kind = -1;
-  for (int flip = 0; flip < 2 && kind < 0; ++flip) {
-    bool ok = true;
-    for (int j = 0; j < 27 && ok; ++j) {
-      const int tp = a.cls[0].taps[j];
-      const int s = flip ? -1 : 1;
-      const int ex = s * (j / 9 - 1), ey = s * ((j / 3) % 3 - 1), ez = s * (j % 3 - 1);
-      ok = (int)(int8_t)(tp & 0xff) == ex && (int)(int8_t)((tp >> 8) & 0xff) == ey && (int)(int8_t)((tp >> 16) & 0xff) == ez;
-    }
-    if (ok) kind = flip;
-  }
-  return kind;
+  return taps_canonical_27(a.cls[0].taps, 1) ? 0 : taps_canonical_27(a.cls[0].taps, -1) ? 1 : -1;
 }
 
 bool conv_halo_x_eligible(const ConvKArgs& a, int dtype, int nclass) {
@@ -1082,9 +1062,8 @@ bool conv_halo_x_eligible(const ConvKArgs& a, int dtype, int nclass) {
   if (a.Xr != a.Xi || a.Yr != a.Yi || a.Zr != a.Zi || a.Zr < 4) return false;
   const int64_t YZ = (int64_t)a.Yi * a.Zi;
   if (((int64_t)a.Xi * YZ + YZ + a.Zi + 1) * a.g_ld * 2 >= (1ll << 31) - 65536) return false;
-  const int64_t osz = a.out_f32 ? 4 : 2;
-  if ((int64_t)a.Xo * a.Yo * a.Zo * a.o_ld * osz >= (1ll << 31) - 65536) return false;
-  if (a.add != nullptr && (int64_t)a.Xo * a.Yo * a.Zo * a.add_ld * (a.add_f32 ? 4 : 2) >= (1ll << 31) - 65536) return false;
+  if (sample_bytes(a.Xo, a.Yo, a.Zo, a.o_ld, a.out_f32 ? 4 : 2) >= (1ll << 31) - 65536) return false;
+  if (a.add != nullptr && sample_bytes(a.Xo, a.Yo, a.Zo, a.add_ld, a.add_f32 ? 4 : 2) >= (1ll << 31) - 65536) return false;
   if (a.out2 != nullptr) return false;
   if (a.cls[0].kpad < 27 * a.Cg) return false;
   const int order = x_tap_order(a);
@@ -1103,6 +1082,18 @@ bool conv_halo_x_stats_ok(const ConvKArgs& a) { return x_tap_order(a) == 0 && !a
 
 static int x_tiles(const ConvKArgs& a) { return ((a.Xr + X_TX - 1) / X_TX) * ((a.Yr + X_TY - 1) / X_TY) * ((a.Zr + X_TZ - 1) / X_TZ); }
 
+// ce: the fused cross-entropy pass, which writes neither an output tensor nor takes a global-memory addend or backward statistics
+static XGeom x_geom(const ConvKArgs& a, bool ce) {
+  XGeom g;
+  g.tyn = (a.Yr + X_TY - 1) / X_TY; g.tzn = (a.Zr + X_TZ - 1) / X_TZ;
+  g.tiles = x_tiles(a);
+  g.in_sample_bytes = (int)sample_bytes(a.Xi, a.Yi, a.Zi, a.g_ld, 2);
+  g.out_sample_bytes = ce ? 0 : (int)sample_bytes(a.Xo, a.Yo, a.Zo, a.o_ld, a.out_f32 ? 4 : 2);
+  g.add_sample_bytes = (a.add && !ce) ? (int)sample_bytes(a.Xo, a.Yo, a.Zo, a.add_ld, a.add_f32 ? 4 : 2) : 0;
+  g.y_sample_bytes = (a.bst.part && !ce) ? (int)sample_bytes(a.Xo, a.Yo, a.Zo, a.bst.y_ld, 2) : 0;
+  return g;
+}
+
 static int x_grid(const ConvKArgs& a) {
   const int vb = a.Cg * 2, total = x_tiles(a) * a.N;
   // LDS: 2 x 41.5 KB of halo (+ 27 / 54 KB of weight fragments) per workgroup at 64-byte voxels: one workgroup per CU;
@@ -1118,7 +1109,7 @@ static int x_add_kind(const ConvKArgs& a);
 int conv_halo_x_bst_slots(const ConvKArgs& a) {
   if (x_tap_order(a) != 1 || a.out_f32 || a.stats != nullptr || a.bias != nullptr || x_add_kind(a) == 2) return 0;
   if (a.bst.col0 != 0 || a.bst.C > a.Cn_store || a.bst.y_ld != a.o_ld) return 0;      // y laid out like the written gradient
-  if ((int64_t)a.Xo * a.Yo * a.Zo * a.bst.y_ld * 2 >= (1ll << 31) - 65536) return 0;
+  if (sample_bytes(a.Xo, a.Yo, a.Zo, a.bst.y_ld, 2) >= (1ll << 31) - 65536) return 0;
   return x_grid(a);
 }
 
@@ -1176,30 +1167,15 @@ static void x_launch(ConvKArgs& a, const XGeom& g, int total, dim3 grid, hipStre
 }
 
 void launch_conv_halo_x(ConvKArgs& a, hipStream_t st) {
-  XGeom g;
-  g.tyn = (a.Yr + X_TY - 1) / X_TY; g.tzn = (a.Zr + X_TZ - 1) / X_TZ;
-  g.tiles = x_tiles(a);
+  const XGeom g = x_geom(a, false);
   a.tiles = g.tiles;
-  g.in_sample_bytes = (int)((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * 2);
-  g.out_sample_bytes = (int)((int64_t)a.Xo * a.Yo * a.Zo * a.o_ld * (a.out_f32 ? 4 : 2));
-  g.add_sample_bytes = a.add ? (int)((int64_t)a.Xo * a.Yo * a.Zo * a.add_ld * (a.add_f32 ? 4 : 2)) : 0;
-  g.y_sample_bytes = a.bst.part ? (int)((int64_t)a.Xo * a.Yo * a.Zo * a.bst.y_ld * 2) : 0;
   const int total = g.tiles * a.N;
   const int vb = a.Cg * 2, nt = a.Cn > 16 ? 2 : 1;
   const dim3 grid((unsigned)x_grid(a), 1u, 1u);
   const bool flip = x_tap_order(a) == 1;
-#define X_DT(H)                                                                                                         \
-  do {                                                                                                                  \
-    if (vb == 64) {                                                                                                     \
-      if (nt == 2) { if (flip) x_launch<H, 64, 1, 2, true>(a, g, total, grid, st); else x_launch<H, 64, 1, 2, false>(a, g, total, grid, st); } \
-      else { if (flip) x_launch<H, 64, 1, 1, true>(a, g, total, grid, st); else x_launch<H, 64, 1, 1, false>(a, g, total, grid, st); }         \
-    } else {                                                                                                            \
-      if (nt == 2) { if (flip) x_launch<H, 32, 1, 2, true>(a, g, total, grid, st); else x_launch<H, 32, 1, 2, false>(a, g, total, grid, st); } \
-      else { if (flip) x_launch<H, 32, 1, 1, true>(a, g, total, grid, st); else x_launch<H, 32, 1, 1, false>(a, g, total, grid, st); }         \
-    }                                                                                                                   \
-  } while (0)
-  if (a.dtype == CTSEG_F16) X_DT(F16); else X_DT(BF16);
-#undef X_DT
+  with_storage(a.dtype, [&](auto h, auto vb64, auto ns2, auto flip_) {
+    x_launch<decltype(h), decltype(vb64)::value ? 64 : 32, 1, decltype(ns2)::value ? 2 : 1, decltype(flip_)::value>(a, g, total, grid, st);
+  }, vb == 64, nt == 2, flip);
 }
 
 // ---- logits convolution with the cross-entropy fused into its epilogue --------------------------------------------------------
@@ -1217,24 +1193,14 @@ static int x_grid_ce(const ConvKArgs& a) {     // 48 KB of LDS but ~230 register
 int conv_halo_x_ce_slots(const ConvKArgs& a) { return x_grid_ce(a); }
 
 template <typename H> static void x_launch_ce(ConvKArgs& a, const XGeom& g, int total, dim3 grid, const XCe& e, hipStream_t st) {
-  const bool r12 = a.g_ld == 12, addc = a.add != nullptr;
-  const dim3 blk(256);
-#define X_CE(AD, R)                                                                                                         \
-  hipLaunchKernelGGL((conv_halo_x_kernel<H, 32, 1, 1, false, false, AD, true, R, true>), grid, blk, 0, st, a, g, total, e)
-  if (addc) { if (r12) X_CE(1, true); else X_CE(1, false); }
-  else { if (r12) X_CE(0, true); else X_CE(0, false); }
-#undef X_CE
+  with_flags([&](auto addc, auto r12) {
+    hipLaunchKernelGGL((conv_halo_x_kernel<H, 32, 1, 1, false, false, decltype(addc)::value ? 1 : 0, true, decltype(r12)::value, true>), grid, dim3(256), 0, st, a, g, total, e);
+  }, a.add != nullptr, a.g_ld == 12);
 }
 
 void launch_conv_halo_x_ce(ConvKArgs& a, const XCe& e, hipStream_t st) {
-  XGeom g;
-  g.tyn = (a.Yr + X_TY - 1) / X_TY; g.tzn = (a.Zr + X_TZ - 1) / X_TZ;
-  g.tiles = x_tiles(a);
+  const XGeom g = x_geom(a, true);
   a.tiles = g.tiles;
-  g.in_sample_bytes = (int)((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * 2);
-  g.out_sample_bytes = 0;
-  g.add_sample_bytes = 0;
-  g.y_sample_bytes = 0;
   const int total = g.tiles * a.N;
   const dim3 grid((unsigned)x_grid_ce(a), 1u, 1u);
   if (a.dtype == CTSEG_F16) x_launch_ce<F16>(a, g, total, grid, e, st); else x_launch_ce<BF16>(a, g, total, grid, e, st);

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_kernel(const ConvKA
     const int tp = (tid < ntaps) ? K.taps[tid] : 0;
     sTap[tid] = tp;
     // byte delta of the tap inside the gathered tensor (offsets are in [-1,1] per axis, checked on the host)
-    sTap[32 + tid] = (((int)(int8_t)(tp & 0xff) * P.Yi + (int)(int8_t)((tp >> 8) & 0xff)) * P.Zi + (int)(int8_t)((tp >> 16) & 0xff)) *
+    sTap[32 + tid] = ((tap_dx(tp) * P.Yi + tap_dy(tp)) * P.Zi + tap_dz(tp)) *
                      P.g_ld * SZ;
   }
   __syncthreads();
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_kernel(const ConvKA
       const bool sv = slot < ntaps;
       const int tp = sv ? sTap[slot & 31] : 0;
       const int tb = (sv ? sTap[32 + (slot & 31)] : 0) + ci * SZ;
-      const int sx = (int)(int8_t)(tp & 0xff) + 1, sy = (int)(int8_t)((tp >> 8) & 0xff) + 4, sz = (int)(int8_t)((tp >> 16) & 0xff) + 7;
+      const int sx = tap_dx(tp) + 1, sy = tap_dy(tp) + 4, sz = tap_dz(tp) + 7;
 #pragma unroll
       for (int j = 0; j < AR; ++j) {
         const bool ok = sv && (((rmask[j] >> sx) & (rmask[j] >> sy) & (rmask[j] >> sz) & 1) != 0);
@@ -157,8 +157,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_kernel(const ConvKA
           uint32_t val = 0u;
           if (sl < ntaps) {
             int tp = sTap[sl & 31];
-            int xi = (rxy[j] & 0xffff) + (int)(int8_t)(tp & 0xff), yi = (rxy[j] >> 16) + (int)(int8_t)((tp >> 8) & 0xff),
-                zi = rz[j] + (int)(int8_t)((tp >> 16) & 0xff);
+            int xi = (rxy[j] & 0xffff) + tap_dx(tp), yi = (rxy[j] >> 16) + tap_dy(tp),
+                zi = rz[j] + tap_dz(tp);
             if ((unsigned)xi < (unsigned)P.Xi && (unsigned)yi < (unsigned)P.Yi && (unsigned)zi < (unsigned)P.Zi) {
               int64_t vox = ((nbase + xi) * P.Yi + yi) * P.Zi + zi;
               const char* p = P.in + (vox * P.g_ld + c) * SZ;
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_igemm_kernel(const ConvKA
     const bool sv = slot < ntaps;
     const int tp = sv ? sTap[slot & 31] : 0;
     const int tb = (sv ? sTap[32 + (slot & 31)] : 0) + ci * SZ;
-    const int sx = (int)(int8_t)(tp & 0xff) + 1, sy = (int)(int8_t)((tp >> 8) & 0xff) + 4, sz = (int)(int8_t)((tp >> 16) & 0xff) + 7;
+    const int sx = tap_dx(tp) + 1, sy = tap_dy(tp) + 4, sz = tap_dz(tp) + 7;
     char* a = sA0 + buf * BM * BKB + (wave * 8) * BKB;
     char* b = sB0 + buf * BN * BKB + (wave * 8) * BKB;
 #pragma unroll
@@ -442,10 +442,8 @@ extern "C" int ctseg_conv_igemm(const ctseg_conv_desc* d, void* stream) {
     CTSEG_REQUIRE(k.kpad % BK == 0 && k.kpad >= k.ntaps * d->Cg, "conv_igemm: class %d kpad %d", c, k.kpad);
     CTSEG_REQUIRE(((k.w_off * SZ) % 16) == 0, "conv_igemm: class %d weight offset unaligned", c);
     for (int j = 0; j < k.ntaps; ++j)
-      for (int sh = 0; sh < 24; sh += 8) {
-        const int dd = (int)(int8_t)((k.taps[j] >> sh) & 0xff);
+      for (int dd : {tap_dx(k.taps[j]), tap_dy(k.taps[j]), tap_dz(k.taps[j])})
         CTSEG_REQUIRE(dd >= -1 && dd <= 1, "conv_igemm: class %d tap %d offset %d outside [-1,1]", c, j, dd);
-      }
     CTSEG_REQUIRE(k.ox >= 0 && k.oy >= 0 && k.oz >= 0 && k.ox < d->sout && k.oy < d->sout && k.oz < d->sout,
                   "conv_igemm: class %d output parity", c);
   }

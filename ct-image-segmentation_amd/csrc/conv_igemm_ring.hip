@@ -70,7 +70,7 @@ __device__ __forceinline__ void ring_main(const ConvKArgs& P, const ctseg_conv_c
     uint32_t m = 0;
     for (int t = 0; t < ntaps; ++t) {
       const int tp = sTap[t];
-      const int xi = xb + (int)(int8_t)(tp & 0xff), yi = yb + (int)(int8_t)((tp >> 8) & 0xff), zi = zb + (int)(int8_t)((tp >> 16) & 0xff);
+      const int xi = xb + tap_dx(tp), yi = yb + tap_dy(tp), zi = zb + tap_dz(tp);
       const bool ok = zb >= 0 && (unsigned)xi < (unsigned)P.Xi && (unsigned)yi < (unsigned)P.Yi && (unsigned)zi < (unsigned)P.Zi;
       m |= (ok ? 1u : 0u) << t;
     }
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(512) void conv_igemm_ring_kernel(const ConvKArgs P)
   if (tid < 32) {
     const int tp = (tid < ntaps) ? K.taps[tid] : 0;
     sTap[tid] = tp;
-    sTap[32 + tid] = (((int)(int8_t)(tp & 0xff) * P.Yi + (int)(int8_t)((tp >> 8) & 0xff)) * P.Zi + (int)(int8_t)((tp >> 16) & 0xff)) *
+    sTap[32 + tid] = ((tap_dx(tp) * P.Yi + tap_dy(tp)) * P.Zi + tap_dz(tp)) *
                      P.g_ld * 2;
   }
   __syncthreads();

@@ -101,13 +101,6 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(const ConvKArgs P, i
     abase[i] = (((2 * wave) * S_IY + 2 * (2 * i + pdy)) * S_PZ + 2 * pz) * 2;
     ovox[i] = (wave * P.Yo + 2 * i + pdy) * P.Zo + pz;
   }
-  auto origin = [&](int t, int& n, int& x0, int& y0, int& z0) {
-    n = t / G.tiles;
-    int r = t - n * G.tiles;
-    const int tz = r % G.tzn; r /= G.tzn;
-    const int ty = r % G.tyn; const int tx = r / G.tyn;
-    x0 = tx * 4; y0 = ty * 8; z0 = tz * 8;
-  };
   auto in_base = [&](int n, int x0, int y0, int z0) {
     return reinterpret_cast<const unsigned short*>(P.in) + (((int64_t)n * P.Xi + 2 * x0) * P.Yi + 2 * y0) * P.Zi + 2 * z0;
   };
@@ -145,23 +138,19 @@ __global__ __launch_bounds__(256) void conv_stem_fwd_kernel(const ConvKArgs P, i
 
   uint32_t rg[S_J];
   int t = blockIdx.x, cur = 0;
-  {
-    int n, x0, y0, z0;
-    if (t < total_tiles) {
-      origin(t, n, x0, y0, z0);
-      stg.load(in_base(n, x0, y0, z0), x0, y0, z0, P.Xi, P.Yi, P.Zi, rg);
-      stg.store(smem, rg);
-    }
+  if (t < total_tiles) {
+    const auto [n, x0, y0, z0] = tile_origin<4, 8, 8>(t, G.tiles, G.tyn, G.tzn);
+    stg.load(in_base(n, x0, y0, z0), x0, y0, z0, P.Xi, P.Yi, P.Zi, rg);
+    stg.store(smem, rg);
   }
   __syncthreads();
   for (; t < total_tiles; t += gridDim.x) {
     const int tn = t + gridDim.x;
-    int n, x0, y0, z0;
     if (tn < total_tiles) {
-      origin(tn, n, x0, y0, z0);
+      const auto [n, x0, y0, z0] = tile_origin<4, 8, 8>(tn, G.tiles, G.tyn, G.tzn);
       stg.load(in_base(n, x0, y0, z0), x0, y0, z0, P.Xi, P.Yi, P.Zi, rg);
     }
-    origin(t, n, x0, y0, z0);
+    const auto [n, x0, y0, z0] = tile_origin<4, 8, 8>(t, G.tiles, G.tyn, G.tzn);
     if (STATS) stat_run.enter(n, flush_stats);
     const char* h = smem + cur * S_INB + S_SHIFT;
     const int64_t vb = (((int64_t)n * P.Xo + x0) * P.Yo + y0) * P.Zo + z0;
@@ -233,12 +222,8 @@ bool conv_stem_eligible(const ConvKArgs& a, int dtype, int nclass) {
   if (((uintptr_t)a.in % 4) != 0) return false;       // the patch is staged in aligned 4-byte pairs
   if (a.cls[0].ntaps != 27 || a.cls[0].kpad != 64 || a.Cn > 64 || a.Cn % 16 != 0 || a.Zr < 4) return false;
   if (a.Xi != 2 * a.Xr || a.Yi != 2 * a.Yr || a.Zi != 2 * a.Zr) return false;
-  if ((int64_t)a.Xi * a.Yi * a.Zi >= (1ll << 31) || (int64_t)a.Xo * a.Yo * a.Zo * a.o_ld * 2 >= (1ll << 31)) return false;
-  for (int j = 0; j < 27; ++j) {   // taps must be the plain conv's, in torch order (taps_canonical_27, on the forward's own descriptor)
-    const int tp = a.cls[0].taps[j];
-    if (tap_dx(tp) != j / 9 - 1 || tap_dy(tp) != (j / 3) % 3 - 1 || tap_dz(tp) != j % 3 - 1) return false;
-  }
-  return true;
+  if ((int64_t)a.Xi * a.Yi * a.Zi >= (1ll << 31) || sample_bytes(a.Xo, a.Yo, a.Zo, a.o_ld, 2) >= (1ll << 31)) return false;
+  return taps_canonical_27(a.cls[0].taps, 1);      // the plain conv's taps, in torch order
 }
 
 static int stem_tiles(int Xr, int Yr, int Zr) { return ((Xr + 3) / 4) * ((Yr + 7) / 8) * ((Zr + 7) / 8); }
@@ -252,19 +237,15 @@ void launch_conv_stem(ConvKArgs& a, hipStream_t st) {
   a.tiles = g.tiles;
   const int total = g.tiles * a.N, grid = stem_grid(total);
   const int nt = (a.Cn + 15) / 16;
-#define CTSEG_STEM(NTV)                                                                                               \
-  do {                                                                                                              \
-    if (a.dtype == CTSEG_F16) {                                                                                       \
-      if (a.stats != nullptr) hipLaunchKernelGGL((conv_stem_fwd_kernel<F16, NTV, true>), dim3(grid), dim3(256), 0, st, a, total, g); \
-      else hipLaunchKernelGGL((conv_stem_fwd_kernel<F16, NTV, false>), dim3(grid), dim3(256), 0, st, a, total, g);    \
-    } else if (a.stats != nullptr) hipLaunchKernelGGL((conv_stem_fwd_kernel<BF16, NTV, true>), dim3(grid), dim3(256), 0, st, a, total, g); \
-    else hipLaunchKernelGGL((conv_stem_fwd_kernel<BF16, NTV, false>), dim3(grid), dim3(256), 0, st, a, total, g);     \
-  } while (0)
-  if (nt == 1) CTSEG_STEM(1);
-  else if (nt == 2) CTSEG_STEM(2);
-  else if (nt == 3) CTSEG_STEM(3);
-  else CTSEG_STEM(4);
-#undef CTSEG_STEM
+  with_storage(a.dtype, [&](auto h, auto stats) {
+    auto go = [&](auto ntv) {
+      hipLaunchKernelGGL((conv_stem_fwd_kernel<decltype(h), decltype(ntv)::value, decltype(stats)::value>), dim3(grid), dim3(256), 0, st, a, total, g);
+    };
+    if (nt == 1) go(std::integral_constant<int, 1>{});
+    else if (nt == 2) go(std::integral_constant<int, 2>{});
+    else if (nt == 3) go(std::integral_constant<int, 3>{});
+    else go(std::integral_constant<int, 4>{});
+  }, a.stats != nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -475,7 +456,7 @@ __global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(const StemWgradArg
 bool wgrad_stem_dyn_ok(const ctseg_wgrad_desc* d) {
   if (d->dyn_col0 * 2 != d->Cn || (d->Cn != 32 && d->Cn != 64) || d->N > S_DYN_MAXN) return false;
   if (d->dyn_g_ld % 8 != 0 || d->dyn_y_ld % 8 != 0 || d->dyn_g_ld < d->dyn_col0 || d->dyn_y_ld < d->dyn_col0) return false;
-  if ((int64_t)d->Xr * d->Yr * d->Zr * d->dyn_g_ld * 2 >= (1ll << 31) || (int64_t)d->Xr * d->Yr * d->Zr * d->dyn_y_ld * 2 >= (1ll << 31)) return false;
+  if (sample_bytes(d->Xr, d->Yr, d->Zr, d->dyn_g_ld, 2) >= (1ll << 31) || sample_bytes(d->Xr, d->Yr, d->Zr, d->dyn_y_ld, 2) >= (1ll << 31)) return false;
   return true;
 }
 
@@ -486,7 +467,7 @@ bool wgrad_stem_eligible(const ctseg_wgrad_desc* d) {
   if (((uintptr_t)d->in % 4) != 0) return false;      // the patch is staged in aligned 4-byte pairs
   if (d->Xi != 2 * d->Xr || d->Yi != 2 * d->Yr || d->Zi != 2 * d->Zr || d->Zr < 4) return false;
   if (d->kpad_w < 32 || d->cn_pad < d->Cn) return false;
-  if ((int64_t)d->Xi * d->Yi * d->Zi >= (1ll << 31) || (int64_t)d->Xr * d->Yr * d->Zr * d->d_ld * 2 >= (1ll << 31)) return false;
+  if ((int64_t)d->Xi * d->Yi * d->Zi >= (1ll << 31) || sample_bytes(d->Xr, d->Yr, d->Zr, d->d_ld, 2) >= (1ll << 31)) return false;
   return taps_canonical_27(d);
 }
 

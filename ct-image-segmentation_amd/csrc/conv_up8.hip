@@ -57,12 +57,7 @@ constexpr int u8_pos_find(int grp, int pos, int what) {     // what: 0 delta, 1 
 static_assert(u8_pos_find(0, 12, 0) == 7 && u8_pos_find(0, 12, 1) == 2 && u8_pos_find(0, 13, 0) == -1, "group 0: 13 pairs");
 static_assert(u8_pos_find(1, 13, 0) == 6 && u8_pos_find(1, 13, 1) == 4 && u8_pos_find(1, 14, 0) == -1, "group 1: 14 pairs");
 
-struct Up8Geom {
-  int da, db, dc;            // extents of the coarse (row) grid along the tile axes (a = short axis)
-  int ia, ib, ic;            // gathered-tensor voxel strides of the tile axes
-  int oa, ob, oc;            // written-tensor voxel strides of the tile axes (already times 2)
-  int pa, pb, pc;            // which volume axis (0 = x, 1 = y, 2 = z) each tile axis runs along
-  int tbn, tcn, tiles;       // tiles along b, c; tiles per sample
+struct Up8Geom : TileAxes {     // the row grid is the coarse grid; written strides already times 2
   int in_sample_bytes, out_sample_bytes, add_sample_bytes;
   int gxs;                   // spatial workgroups: the grid is 2 * gxs, workgroup L takes class group L / gxs
 };
@@ -106,20 +101,12 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
     h_off[r] = (ha * G.ia + hb * G.ib + hc * G.ic) * P.g_ld * 2 + pl * 16;
     h_abc[r] = ok ? (ha | (hb << 8) | (hc << 16)) : 0x7f7f7f;
   }
-  auto tile_origin = [&](int t, int& n, int& a0, int& b0, int& c0) {
-    n = t / G.tiles;
-    int r = t - n * G.tiles;
-    const int tc = r % G.tcn; r /= G.tcn;
-    const int tb = r % G.tbn; const int ta = r / G.tbn;
-    a0 = ta * U8_TA; b0 = tb * 8; c0 = tc * 8;
-  };
   // per tile: the sample's descriptor, the byte offset of the tile origin and the three per-lane offsets (out of range where the halo
   // voxel lies outside the volume, or there is no such tile); per chunk only the scalar offset moves
   i32x4 h_rs = make_rsrc(P.in, (uint32_t)G.in_sample_bytes);
   int h_soff = 0, h_v[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
   auto halo_tile = [&](int t, bool live) {
-    int n, a0, b0, c0;
-    tile_origin(live ? t : 0, n, a0, b0, c0);
+    const auto [n, a0, b0, c0] = tile_origin_abc<U8_TA>(live ? t : 0, G);
     h_rs = make_rsrc(P.in + (int64_t)n * G.in_sample_bytes, (uint32_t)G.in_sample_bytes);
     h_soff = (a0 * G.ia + b0 * G.ib + c0 * G.ic) * P.g_ld * 2;
 #pragma unroll
@@ -362,8 +349,7 @@ __device__ __forceinline__ void conv_up8_body(const ConvKArgs& P, const Up8Geom&
   __syncthreads();
   for (; t < last; t += stride) {
     const int tn = t + stride;
-    int n, a0, b0, c0;
-    tile_origin(t, n, a0, b0, c0);
+    const auto [n, a0, b0, c0] = tile_origin_abc<U8_TA>(t, G);
     if (STATS && n != stat_n) {
       if (stat_n >= 0) flush_stats(stat_n);
       stat_n = n;
@@ -404,27 +390,10 @@ __global__ __launch_bounds__(U8_NTHR) void conv_up8_kernel(const ConvKArgs P, co
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
 static void up8_geom(const ConvKArgs& a, Up8Geom& g) {
-  const int ta = U8_TA;
-  const int dims[3] = {a.Xr, a.Yr, a.Zr};
-  const int istr[3] = {a.Yi * a.Zi, a.Zi, 1};
-  const int ostr[3] = {a.Yo * a.Zo * 2, a.Zo * 2, 2};
-  auto waste = [&](int pa, int pb, int pc) {
-    const double full = (double)dims[0] * dims[1] * dims[2];
-    const double padded = (double)((dims[pa] + ta - 1) / ta * ta) * ((dims[pb] + 7) / 8 * 8) * ((dims[pc] + 7) / 8 * 8);
-    return padded / full;
-  };
-  int pa = 0, pb = 1, pc = 2;
-  if (waste(2, 0, 1) < waste(0, 1, 2) - 1e-9) { pa = 2; pb = 0; pc = 1; }
-  g.pa = pa; g.pb = pb; g.pc = pc;
-  g.da = dims[pa]; g.db = dims[pb]; g.dc = dims[pc];
-  g.ia = istr[pa]; g.ib = istr[pb]; g.ic = istr[pc];
-  g.oa = ostr[pa]; g.ob = ostr[pb]; g.oc = ostr[pc];
-  const int tan = (g.da + ta - 1) / ta;
-  g.tbn = (g.db + 7) / 8; g.tcn = (g.dc + 7) / 8;
-  g.tiles = tan * g.tbn * g.tcn;
-  g.in_sample_bytes = (int)((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * 2);
-  g.out_sample_bytes = (int)((int64_t)a.Xo * a.Yo * a.Zo * a.o_ld * 2);
-  g.add_sample_bytes = (int)((int64_t)a.Xo * a.Yo * a.Zo * a.add_ld * (a.add_f32 ? 4 : 2));
+  tile_axes_fill(g, a, U8_TA, 2);
+  g.in_sample_bytes = (int)sample_bytes(a.Xi, a.Yi, a.Zi, a.g_ld, 2);
+  g.out_sample_bytes = (int)sample_bytes(a.Xo, a.Yo, a.Zo, a.o_ld, 2);
+  g.add_sample_bytes = (int)sample_bytes(a.Xo, a.Yo, a.Zo, a.add_ld, a.add_f32 ? 4 : 2);
   const int total = g.tiles * a.N;
   g.gxs = persistent_grid(CTSEG_NUM_CU / 2, total);   // 2 x 128 workgroups = one per CU, the reference's 256 tiles twice each
 }
@@ -436,8 +405,8 @@ bool conv_up8_eligible(const ConvKArgs& a, int dtype, int nclass) {
   if (a.add != nullptr && ((a.add_ld % 4) != 0 || ((uintptr_t)a.add % 16) != 0)) return false;
   if (a.Xr != a.Xi || a.Yr != a.Yi || a.Zr != a.Zi) return false;
   if (a.Xo != 2 * a.Xr || a.Yo != 2 * a.Yr || a.Zo != 2 * a.Zr) return false;
-  if ((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * 2 >= (1ll << 31) || (int64_t)a.Xo * a.Yo * a.Zo * a.o_ld * 2 >= (1ll << 31)) return false;
-  if (a.add != nullptr && (int64_t)a.Xo * a.Yo * a.Zo * a.add_ld * (a.add_f32 ? 4 : 2) >= (1ll << 31)) return false;
+  if (sample_bytes(a.Xi, a.Yi, a.Zi, a.g_ld, 2) >= (1ll << 31) || sample_bytes(a.Xo, a.Yo, a.Zo, a.o_ld, 2) >= (1ll << 31)) return false;
+  if (a.add != nullptr && sample_bytes(a.Xo, a.Yo, a.Zo, a.add_ld, a.add_f32 ? 4 : 2) >= (1ll << 31)) return false;
   if ((int64_t)a.Xr * a.Yr * a.Zr < 2048) return false;                            // too few tiles to fill the chip: generic kernel
   int taps = 0;
   for (int c = 0; c < 8; ++c) {
@@ -451,7 +420,7 @@ bool conv_up8_eligible(const ConvKArgs& a, int dtype, int nclass) {
       if (tp < 0) continue;
       if (tp >= k.ntaps) return false;
       const int t = k.taps[tp];
-      if ((int)(int8_t)(t & 0xff) != ((dl >> 2) & 1) || (int)(int8_t)((t >> 8) & 0xff) != ((dl >> 1) & 1) || (int)(int8_t)((t >> 16) & 0xff) != (dl & 1)) return false;
+      if (tap_dx(t) != ((dl >> 2) & 1) || tap_dy(t) != ((dl >> 1) & 1) || tap_dz(t) != (dl & 1)) return false;
     }
   }
   return taps == 27;
@@ -470,16 +439,9 @@ void launch_conv_up8(ConvKArgs& a, hipStream_t st) {
   a.tiles = g.tiles;
   const int total = g.tiles * a.N;
   const dim3 grid((unsigned)(2 * g.gxs)), blk(U8_NTHR);
-  const bool stats = a.stats != nullptr;
-  const bool zxy = g.pa == 2;
-#define CTSEG_U8_GO(H, ST)                                                                                        \
-  do {                                                                                                            \
-    if (zxy) hipLaunchKernelGGL((conv_up8_kernel<H, ST, true>), grid, blk, 0, st, a, g, total);                    \
-    else hipLaunchKernelGGL((conv_up8_kernel<H, ST, false>), grid, blk, 0, st, a, g, total);                       \
-  } while (0)
-  if (a.dtype == CTSEG_F16) { if (stats) CTSEG_U8_GO(F16, true); else CTSEG_U8_GO(F16, false); }
-  else { if (stats) CTSEG_U8_GO(BF16, true); else CTSEG_U8_GO(BF16, false); }
-#undef CTSEG_U8_GO
+  with_storage(a.dtype, [&](auto h, auto stats, auto zxy) {
+    hipLaunchKernelGGL((conv_up8_kernel<decltype(h), decltype(stats)::value, decltype(zxy)::value>), grid, blk, 0, st, a, g, total);
+  }, a.stats != nullptr, g.pa == 2);
 }
 
 }  // namespace ctseg

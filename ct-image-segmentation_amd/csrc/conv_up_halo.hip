@@ -66,7 +66,7 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
     int d = 0;
     if (tp_i < P.cls[c].ntaps) {
       const int tp = P.cls[c].taps[tp_i];
-      d = ((int)(int8_t)(tp & 0xff) * U_HY + (int)(int8_t)((tp >> 8) & 0xff)) * U_HZ + (int)(int8_t)((tp >> 16) & 0xff);
+      d = (tap_dx(tp) * U_HY + tap_dy(tp)) * U_HZ + tap_dz(tp);
     }
     sDelta[tid] = d * 16;
   }
@@ -84,21 +84,13 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
     g_lds[j] = pl * U_PLANE + (((fx + 1) * U_HY + (fy + 1)) * U_HZ + (fz + 1)) * 16;
   }
   const int tiles_per_sample = P.tiles;
-  auto tile_origin = [&](int t, int& n, int& x0, int& y0, int& z0) {
-    n = t / tiles_per_sample;
-    int r = t - n * tiles_per_sample;
-    const int tz = r % tzn; r /= tzn;
-    const int ty = r % tyn; const int tx = r / tyn;
-    x0 = tx * 4; y0 = ty * 8; z0 = tz * 8;
-  };
   u32x4 rh[J];
   // branch-free: raw buffer loads with a per-sample descriptor, voxels outside the volume get an out-of-range offset (zeros).  (Plain
   // loads under `if (inside)` made the compiler wait for each one before the next branch: 0.10 of this pass's 0.37 ms at 2 x 256 x
   // 256 x 24 was the exposed latency of these seven loads.)
-  const int in_sample_bytes = (int)((int64_t)P.Xi * P.Yi * P.Zi * P.g_ld * 2);
+  const int in_sample_bytes = (int)sample_bytes(P.Xi, P.Yi, P.Zi, P.g_ld, 2);
   auto gload = [&](int t) {
-    int n, x0, y0, z0;
-    tile_origin(t, n, x0, y0, z0);
+    const auto [n, x0, y0, z0] = tile_origin<4, 8, 8>(t, tiles_per_sample, tyn, tzn);
     const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(P.in + (int64_t)n * in_sample_bytes, in_sample_bytes);
     const int soff = ((x0 * P.Yi + y0) * P.Zi + z0) * P.g_ld * 2;
 #pragma unroll
@@ -158,8 +150,7 @@ __global__ __launch_bounds__(512) void conv_up_halo_kernel(const ConvKArgs P, in
   };
 
   auto compute_tile = [&](int t) {
-    int n, x0, y0, z0;
-    tile_origin(t, n, x0, y0, z0);
+    const auto [n, x0, y0, z0] = tile_origin<4, 8, 8>(t, tiles_per_sample, tyn, tzn);
     if (P.stats != nullptr) stat_run.enter(n, flush_stats);
     const int64_t vb = (((int64_t)n * P.Xo + 2 * x0) * P.Yo + 2 * y0) * P.Zo + 2 * z0;
     const bool xok = x0 + wave < P.Xr, zok = z0 + pz < P.Zr;
@@ -340,17 +331,13 @@ bool conv_up_eligible(const ConvKArgs& a, int dtype, int nclass) {
   if ((a.g_ld % 8) != 0 || ((uintptr_t)a.in % 16) != 0) return false;
   if (a.Xr != a.Xi || a.Yr != a.Yi || a.Zr != a.Zi || a.Zr < 4) return false;
   if (a.Xo != 2 * a.Xr || a.Yo != 2 * a.Yr || a.Zo != 2 * a.Zr) return false;
-  if ((int64_t)a.Xi * a.Yi * a.Zi * a.g_ld * 2 >= (1ll << 31)) return false;
+  if (sample_bytes(a.Xi, a.Yi, a.Zi, a.g_ld, 2) >= (1ll << 31)) return false;
   int taps = 0;
   for (int c = 0; c < 8; ++c) {
     const ctseg_conv_class& k = a.cls[c];
     if (k.ntaps != (1 << __builtin_popcount(c)) || k.kpad != ((k.ntaps * a.Cg + 63) / 64) * 64) return false;
     taps += k.ntaps;
-    for (int j = 0; j < k.ntaps; ++j)
-      for (int s = 0; s < 24; s += 8) {
-        const int d = (int)(int8_t)((k.taps[j] >> s) & 0xff);
-        if (d < 0 || d > 1) return false;
-      }
+    if (!taps_within(k.taps, k.ntaps, 0, 1)) return false;
     // the delta-major schedule addresses a class's taps by (dx,dy,dz): class c = px*4 + py*2 + pz at parity (px,py,pz), taps in the
     // host's order (up_tap_index)
     if (k.ox != ((c >> 2) & 1) || k.oy != ((c >> 1) & 1) || k.oz != (c & 1)) return false;
@@ -359,7 +346,7 @@ bool conv_up_eligible(const ConvKArgs& a, int dtype, int nclass) {
       if (tp < 0) continue;
       if (tp >= k.ntaps) return false;
       const int t = k.taps[tp];
-      if ((int)(int8_t)(t & 0xff) != ((dl >> 2) & 1) || (int)(int8_t)((t >> 8) & 0xff) != ((dl >> 1) & 1) || (int)(int8_t)((t >> 16) & 0xff) != (dl & 1)) return false;
+      if (tap_dx(t) != ((dl >> 2) & 1) || tap_dy(t) != ((dl >> 1) & 1) || tap_dz(t) != (dl & 1)) return false;
     }
   }
   return taps == 27;
@@ -380,13 +367,9 @@ void launch_conv_up(ConvKArgs& a, hipStream_t st) {
   const int total = a.tiles * a.N;
   const int vb = a.Cg * 2;
   const int gx = up_grid(a);
-  if (a.dtype == CTSEG_F16) {
-    if (vb == 128) hipLaunchKernelGGL((conv_up_halo_kernel<F16, 128>), dim3(gx), dim3(512), 0, st, a, total, tyn, tzn);
-    else hipLaunchKernelGGL((conv_up_halo_kernel<F16, 64>), dim3(gx), dim3(512), 0, st, a, total, tyn, tzn);
-  } else {
-    if (vb == 128) hipLaunchKernelGGL((conv_up_halo_kernel<BF16, 128>), dim3(gx), dim3(512), 0, st, a, total, tyn, tzn);
-    else hipLaunchKernelGGL((conv_up_halo_kernel<BF16, 64>), dim3(gx), dim3(512), 0, st, a, total, tyn, tzn);
-  }
+  with_storage(a.dtype, [&](auto h, auto vb128) {
+    hipLaunchKernelGGL((conv_up_halo_kernel<decltype(h), decltype(vb128)::value ? 128 : 64>), dim3(gx), dim3(512), 0, st, a, total, tyn, tzn);
+  }, vb == 128);
 }
 
 }  // namespace ctseg

@@ -175,6 +175,40 @@ __device__ __forceinline__ bf16x8 tr16_frag(const char* p0, int hi_off) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// ---- packed taps: signed bytes (dx, dy, dz) in bits 0-7, 8-15, 16-23 -------------------------------------------------------------
+__host__ __device__ __forceinline__ int tap_dx(int tp) { return (int)(int8_t)(tp & 0xff); }
+__host__ __device__ __forceinline__ int tap_dy(int tp) { return (int)(int8_t)((tp >> 8) & 0xff); }
+__host__ __device__ __forceinline__ int tap_dz(int tp) { return (int)(int8_t)((tp >> 16) & 0xff); }
+
+// every offset of every tap lies in [lo, hi]
+static inline bool taps_within(const int* taps, int ntaps, int lo, int hi) {
+  for (int j = 0; j < ntaps; ++j) {
+    const int d[3] = {tap_dx(taps[j]), tap_dy(taps[j]), tap_dz(taps[j])};
+    for (int v : d)
+      if (v < lo || v > hi) return false;
+  }
+  return true;
+}
+
+// the first 27 taps are the 3x3x3 set in torch order, tap j = sign * (j / 9 - 1, (j / 3) % 3 - 1, j % 3 - 1): sign = 1 the forward
+// order, -1 the negated order of an input gradient
+static inline bool taps_canonical_27(const int* taps, int sign) {
+  for (int j = 0; j < 27; ++j)
+    if (tap_dx(taps[j]) != sign * (j / 9 - 1) || tap_dy(taps[j]) != sign * ((j / 3) % 3 - 1) || tap_dz(taps[j]) != sign * (j % 3 - 1)) return false;
+  return true;
+}
+
+// ---- persistent tile kernels -----------------------------------------------------------------------------------------------------
+// Tile id -> sample and first voxel of a TX x TY x TZ tile; tiles per sample `tiles`, of which tyn / tzn along y / z (z fastest).
+struct TileOrigin { int n, x0, y0, z0; };
+template <int TX, int TY, int TZ> __device__ __forceinline__ TileOrigin tile_origin(int t, int tiles, int tyn, int tzn) {
+  const int n = t / tiles;
+  int r = t - n * tiles;
+  const int tz = r % tzn; r /= tzn;
+  const int ty = r % tyn, tx = r / tyn;
+  return {n, tx * TX, ty * TY, tz * TZ};
+}
+
 // n consecutive elements, fp32 or 16-bit kind H by a runtime flag -> floats (n = 4 or 8; pointer aligned to n*size)
 template <typename H = BF16> __device__ __forceinline__ void load_n_as_float(const char* p, bool is_f32, int n, float* v) {
   if (is_f32) {

@@ -1,43 +1,14 @@
-// Building blocks shared by the weight-gradient kernels (conv_wgrad*.hip and the weight-gradient half of conv_stem.hip): packed
-// taps, tile origins, the bias pseudo-tap operand, and the geometry / row walk / slab order of the two split-K kernels.
+// Building blocks shared by the weight-gradient kernels (conv_wgrad*.hip and the weight-gradient half of conv_stem.hip): the bias
+// pseudo-tap operand and the geometry / row walk / slab order of the two split-K kernels.  (Packed taps, their predicates and
+// tile_origin are in ctseg_dev.h: the forward kernels use them too.)
 #pragma once
 #include "ctseg_dev.h"
 
 namespace ctseg {
 
-// ---- packed taps: signed bytes (dx, dy, dz) in bits 0-7, 8-15, 16-23 -------------------------------------------------------------
-__host__ __device__ __forceinline__ int tap_dx(int tp) { return (int)(int8_t)(tp & 0xff); }
-__host__ __device__ __forceinline__ int tap_dy(int tp) { return (int)(int8_t)((tp >> 8) & 0xff); }
-__host__ __device__ __forceinline__ int tap_dz(int tp) { return (int)(int8_t)((tp >> 16) & 0xff); }
-
-// every offset of every tap is -1, 0 or +1
-static inline bool taps_within_unit_cube(const ctseg_wgrad_desc* d) {
-  for (int j = 0; j < d->ntaps; ++j) {
-    const int tp = d->taps[j];
-    if (tap_dx(tp) < -1 || tap_dx(tp) > 1 || tap_dy(tp) < -1 || tap_dy(tp) > 1 || tap_dz(tp) < -1 || tap_dz(tp) > 1) return false;
-  }
-  return true;
-}
-
-// the first 27 taps are the 3x3x3 set in torch order: tap j = (j / 9 - 1, (j / 3) % 3 - 1, j % 3 - 1)
-static inline bool taps_canonical_27(const ctseg_wgrad_desc* d) {
-  for (int j = 0; j < 27; ++j) {
-    const int tp = d->taps[j];
-    if (tap_dx(tp) != j / 9 - 1 || tap_dy(tp) != (j / 3) % 3 - 1 || tap_dz(tp) != j % 3 - 1) return false;
-  }
-  return true;
-}
-
-// ---- persistent tile kernels -----------------------------------------------------------------------------------------------------
-// Tile id -> sample and first voxel of a TX x TY x TZ tile; tiles per sample `tiles`, of which tyn / tzn along y / z (z fastest).
-struct TileOrigin { int n, x0, y0, z0; };
-template <int TX, int TY, int TZ> __device__ __forceinline__ TileOrigin tile_origin(int t, int tiles, int tyn, int tzn) {
-  const int n = t / tiles;
-  int r = t - n * tiles;
-  const int tz = r % tzn; r /= tzn;
-  const int ty = r % tyn, tx = r / tyn;
-  return {n, tx * TX, ty * TY, tz * TZ};
-}
+// ---- the tap predicates of ctseg_dev.h on a weight-gradient descriptor -----------------------------------------------------------
+static inline bool taps_within_unit_cube(const ctseg_wgrad_desc* d) { return taps_within(d->taps, d->ntaps, -1, 1); }
+static inline bool taps_canonical_27(const ctseg_wgrad_desc* d) { return taps_canonical_27(d->taps, 1); }
 
 // Gathered operand of the all-ones pseudo tap: 1.0 on channel row 0 for every voxel, so that row 0 of its product is the column sum
 // of the other operand (the bias gradient).

@@ -228,6 +228,69 @@ def test_conv_pass_name_follows_the_extras_and_rejects_bad_descriptors(monkeypat
     assert L.ctseg_conv_pass_name(ctypes.byref(bad)) is None
 
 
+def _ceil_to(v, m):
+    return -(-v // m) * m
+
+
+def _tile_axis_rule(rows, ta, orders):
+    """The kernels' choice of tile axes, restated: a tile is ta x 8 x 8 along (a, b, c); the first order stands unless a later one
+    pads the row grid to a strictly smaller volume (by more than 1e-9 of the grid).  -> (order, tiles per sample of every order)"""
+    full = float(rows[0]) * rows[1] * rows[2]
+    waste = [float(_ceil_to(rows[a], ta)) * _ceil_to(rows[b], 8) * _ceil_to(rows[c], 8) / full for a, b, c in orders]
+    tiles = [(_ceil_to(rows[a], ta) // ta) * (_ceil_to(rows[b], 8) // 8) * (_ceil_to(rows[c], 8) // 8) for a, b, c in orders]
+    pick, best = 0, waste[0]
+    for i in range(1, len(orders)):
+        if waste[i] < best - 1e-9:
+            pick, best = i, waste[i]
+    return orders[pick], tiles
+
+
+XYZ, ZXY, YXZ = (0, 1, 2), (2, 0, 1), (1, 0, 2)
+# (family, Cg, Cn, kind, tile depth along a, candidate orders in the kernels' preference, tiles reported per tile of the grid)
+TILE_FAMILIES = {
+    "sw64": ("streamed-weight halo", 64, 64, "plain", 4, (XYZ, ZXY), 1),
+    "sw8": ("streamed-weight halo", 128, 32, "up", 4, (XYZ, ZXY), 1),
+    "down": ("stride-2 halo", 16, 64, "down", 4, (XYZ, ZXY), 1),
+    "up8": ("many-channel 8-class", 256, 64, "up", 3, (XYZ, ZXY), 2),       # two class groups: twice its per-group grid
+    "down_r": ("stride-2 register-weight", 32, 128, "down", 1, (XYZ, ZXY, YXZ), 1),
+}
+# (family, row grid, the order the rule picks (derived by hand), tiles of that order, tiles of the first order)
+TILE_AXIS_CASES = [
+    ("sw64", (229, 3, 3), ZXY, 29, 58),
+    ("sw64", (9, 20, 13), XYZ, 18, 18),
+    ("sw8", (16, 16, 12), ZXY, 12, 16),
+    ("sw8", (9, 20, 12), XYZ, 18, 18),         # an exact tie: both orders pad to 4608 voxels; the first one stays
+    ("down", (18, 10, 12), ZXY, 18, 20),
+    ("up8", (16, 16, 9), ZXY, 12, 24),
+    ("up8", (9, 20, 12), XYZ, 18, 18),
+    ("down_r", (8, 16, 17), ZXY, 17 * 2, 8 * 2 * 3),      # z is the 1-deep axis: the (x, y) face needs no padding
+    ("down_r", (8, 17, 16), YXZ, 17 * 2, 8 * 3 * 2),      # y is
+    ("down_r", (9, 20, 12), XYZ, 9 * 3 * 2, 9 * 3 * 2),   # x is: (y, z) pads 20 x 12 to 24 x 16 = 1.6, (x, y) 2.13, (x, z) 2.37
+]
+
+
+@pytest.mark.parametrize("fam,rows,order,tiles,tiles_first", TILE_AXIS_CASES, ids=[f"{c[0]} {c[1]}" for c in TILE_AXIS_CASES])
+def test_tile_axis_choice_matches_the_padding_rule(fam, rows, order, tiles, tiles_first, monkeypatch):
+    monkeypatch.delenv("CTSEG_MAX_WG", raising=False)
+    name, cg, cn, kind, ta, orders, per_tile = TILE_FAMILIES[fam]
+    want_order, all_tiles = _tile_axis_rule(rows, ta, orders)
+    # the table's hand-derived figures against the restated rule, then the rule against the library
+    assert want_order == order and all_tiles[orders.index(order)] == tiles and all_tiles[0] == tiles_first
+    if order != XYZ:
+        assert all(t != tiles for o, t in zip(orders, all_tiles) if o != order)      # a wrong choice shows in the count
+    L = nat.lib()
+    d = _conv_desc(nat.BF16, cg, cn, rows, kind)
+    d.N = 1
+    assert L.ctseg_conv_pass_name(ctypes.byref(d)) == name.encode()
+    assert L.ctseg_conv_num_tiles(ctypes.byref(d)) == per_tile * tiles
+
+
+def test_tile_axis_tie_stays_xyz():
+    """8-class rows (9, 20, 12) at a tile depth of 4 pad to 12 x 24 x 16 = 12 x 16 x 24 = 4608 voxels in either order: an exact tie"""
+    assert _ceil_to(9, 4) * _ceil_to(20, 8) * _ceil_to(12, 8) == _ceil_to(12, 4) * _ceil_to(9, 8) * _ceil_to(20, 8) == 4608
+    assert _tile_axis_rule((9, 20, 12), 4, (XYZ, ZXY))[0] == XYZ
+
+
 def _wgrad_desc(dt, cg, cn, rows, sin=1, g_ld=None, d_ld=None, k=3, dims=3, N=2):
     """a hand-filled weight-gradient descriptor (no memory behind the pointers: null `in` / `dy` are 16-byte aligned).  For a
     transposed convolution the caller passes the gathered side (dOut: cg = its channel stride) and cn = the layer's input channels"""

@@ -52,6 +52,11 @@ selector names "generic 256x16" for all four), and per family a case with an ext
 (DEGENERATE; the halo kernels need 4 rows along z, the streamed kernels 2048 rows: 1 x 3 x 683).  16-bit storage reaches the "halo"
 kernel only with CTSEG_NO_HALO_X set (conv_halo_x_eligible comes first): those cases set it.
 
+PERMUTED adds the tile orders those shapes do not reach (the (z, x, y) order of the many-channel 8-class, the 8-class streamed-weight
+and the stride-2 halo kernels; z and y as the 1-deep axis of the stride-2 register-weight kernel), uncapped and under CTSEG_MAX_WG=1;
+tests/test_abi_exports.py pins which order each of those row grids gets.  Reference maxima of the six cases, in table order: 156, 134,
+87, 47, 86, 93.
+
 Not covered, with the reason the library gives:
   * the stem's input gradient: the layer is the network's first, GemmLayer builds it without an input-gradient operand
     (need_dgrad=False); test_every_family_and_tile_has_a_forward_and_an_input_gradient_case lists the exemption;
@@ -376,6 +381,17 @@ DEGENERATE = [
     C("ring 192x128 thin", "fwd", RING128, "conv", 128, 128, (1, 3, 3, 37)),
     C("ring 192x256 thin", "dgrad", RING256, "conv", 256, 128, (1, 1, 3, 37)),
 ]
+# the permuted tile orders the tables above do not reach: (z, x, y) on the many-channel 8-class kernel (both passes), on the 8-class
+# streamed-weight halo kernel and on the stride-2 halo kernel with 12-wide dY, and the stride-2 register-weight kernel with z / with y
+# as its 1-deep axis.  One sample of 2.2k-3.1k rows; only CTSEG_MAX_WG=1 makes one workgroup walk several permuted tiles
+PERMUTED = [
+    C("up8 zxy", "fwd", UP8, "convT", 256, 64, (1, 16, 16, 9)),
+    C("up8 zxy, of 64->256 s2", "dgrad", UP8, "conv_s2", 64, 256, (1, 32, 32, 18)),
+    C("halo_sw 8-class zxy", "fwd", HALO_SW, "convT", 128, 32, (1, 16, 16, 12)),
+    C("down_halo zxy, of convT 64->10, 12-wide dY", "dgrad", DOWN_HALO, "convT", 64, 10, (1, 16, 16, 12), g_ld=12),
+    C("down_r 1-deep z", "fwd", DOWN_R, "conv_s2", 32, 128, (1, 16, 32, 34)),
+    C("down_r 1-deep y", "fwd", DOWN_R, "conv_s2", 32, 128, (1, 16, 34, 32)),
+]
 ALL = FWD + DGRAD + DEGENERATE
 PERSISTENT = [c for c in ALL if c.persistent]
 TILED = [c for c in ALL if not c.persistent]
@@ -425,6 +441,14 @@ def test_exact_bf16_persistent_kernels(monkeypatch, case, max_wg):
     case.setenv(monkeypatch, max_wg)
     run, ref = _exact(case, "unit")
     run.check_columns(ref, "bf16, operands in {-1, 0, 1}")
+
+
+@pytest.mark.parametrize("max_wg", CAPS[:2], ids=CAP_IDS[:2])
+@pytest.mark.parametrize("case", PERMUTED, ids=_ids(PERMUTED))
+def test_exact_bf16_permuted_tile_axes(monkeypatch, case, max_wg):
+    case.setenv(monkeypatch, max_wg)
+    run, ref = _exact(case, "unit")
+    run.check_columns(ref, "bf16, operands in {-1, 0, 1}, permuted tile axes")
 
 
 @pytest.mark.parametrize("case", TILED, ids=_ids(TILED))
