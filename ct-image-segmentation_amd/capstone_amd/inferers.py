@@ -10,10 +10,13 @@ builds (capstone/volumetric/base_trainer.py:65-72) with the call signature and s
   blurred by MONAI's erf-integrated Gaussian, sigma = ``sigma_scale * roi``, truncated at 4 sigma, scaled to max 1, zeros
   replaced by the smallest positive weight) and the weighted sum is divided by the sum of weights.
 
-Device work = three C-ABI calls per window batch: ``ctseg_window_gather`` (volume -> the plan's channels-last input, storage
-dtype, padding on the fly), the recorded forward program of an inference-only plan, ``ctseg_window_blend`` (weighted
-accumulate into the channels-last fp32 output).  The weight normalisation is input independent, so its reciprocal is computed
-once on the host and folded into the blend.  No CPU fallback: a predictor that is not backed by the engine raises.
+Device work = three steps per window batch: ``ctseg_window_gather_batch`` (volume -> the plan's channels-last input, storage
+dtype, padding on the fly, every window of the batch in one launch), the recorded forward program of an inference-only plan,
+``ctseg_window_blend_batch`` (weighted accumulate into the channels-last fp32 output, one output-centric launch; one
+``ctseg_window_blend`` per window instead where the logits' row stride differs from the output's, or under
+``CTSEG_SW_BLEND=per_window``).  The weight normalisation is input independent, so the sum of weights is accumulated once per
+window grid by ``ctseg_window_blend`` on unit logits and its reciprocal folded into the blend.  No CPU fallback: a predictor
+that is not backed by the engine raises.
 """
 import ctypes
 import math
@@ -164,21 +167,14 @@ def sliding_window_inference(inputs: torch.Tensor, roi_size: Union[Sequence[int]
     out = torch.zeros(img + (out_ld,), dtype=torch.float32, device=dev)
     xin, logits = plan.x, plan.logits
     win_elems = roi[0] * roi[1] * roi[2]
-    esz = xin.t.element_size()
     for g in range(0, len(starts), sw_batch_size):
         batch = starts[g:g + sw_batch_size]               # a short last batch re-runs stale windows; they are not blended
         rel = [[a - lo[0], bb - lo[1], c - lo[2]] for a, bb, c in batch]
-        on_gpu = dev.type == "cuda"
-        if on_gpu:                                            # one gather launch for the batch
-            st_d = torch.tensor(rel, dtype=torch.int32).to(dev, non_blocking=True)
-            nat.call("ctseg_window_gather_batch", vol.data_ptr(), net.in_channels, *img, st_d.data_ptr(), len(batch), *roi, float(cval),
-                     xin.t.data_ptr(), plan.dt, xin.ld)
-        else:
-            for b, (a, bb, c) in enumerate(rel):
-                nat.call("ctseg_window_gather", vol.data_ptr(), net.in_channels, *img, a, bb, c, *roi,
-                         float(cval), xin.t.data_ptr() + b * win_elems * xin.ld * esz, plan.dt, xin.ld)
+        st_d = torch.tensor(rel, dtype=torch.int32).to(dev, non_blocking=True)
+        nat.call("ctseg_window_gather_batch", vol.data_ptr(), net.in_channels, *img, st_d.data_ptr(), len(batch), *roi, float(cval),
+                 xin.t.data_ptr(), plan.dt, xin.ld)                      # one gather launch for the batch
         plan.forward()
-        if on_gpu and logits.ld == out_ld and os.environ.get("CTSEG_SW_BLEND", "batch") != "per_window":
+        if logits.ld == out_ld and os.environ.get("CTSEG_SW_BLEND", "batch") != "per_window":
             # one output-centric launch for the whole batch: same sums in the same (scan) order, the output read / written once
             b0 = [max(0, min(r[k] for r in rel)) for k in range(3)]
             b1 = [min(img[k], max(r[k] for r in rel) + roi[k]) for k in range(3)]

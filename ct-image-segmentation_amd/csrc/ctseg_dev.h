@@ -69,10 +69,12 @@ struct BF16 {};  // storage tag: 16-bit brain float kept as raw ushort
 struct F16 {};   // storage tag: IEEE half kept as raw ushort (forward / inference passes only)
 
 template <typename T> struct TT;
-// H = the 16-bit storage kind whose conversions a kernel body names in branches that are dead for fp32 storage
-template <> struct TT<float> { static constexpr int SZ = 4, EPC = 4, DT = CTSEG_F32; using H = BF16; };
-template <> struct TT<BF16> { static constexpr int SZ = 2, EPC = 8, DT = CTSEG_BF16; using H = BF16; };
-template <> struct TT<F16> { static constexpr int SZ = 2, EPC = 8, DT = CTSEG_F16; using H = F16; };
+// H = the 16-bit storage kind whose conversions a kernel body names in branches that are dead for fp32 storage;
+// E = what a pointer to such storage points at (both 16-bit kinds travel as raw uint16_t)
+template <> struct TT<float> { static constexpr int SZ = 4, EPC = 4, DT = CTSEG_F32; using H = BF16; using E = float; };
+template <> struct TT<BF16> { static constexpr int SZ = 2, EPC = 8, DT = CTSEG_BF16; using H = BF16; using E = uint16_t; };
+template <> struct TT<F16> { static constexpr int SZ = 2, EPC = 8, DT = CTSEG_F16; using H = F16; using E = uint16_t; };
+template <typename T> using elem_t = typename TT<T>::E;
 
 __device__ __forceinline__ float bf2f(uint32_t u16) { return __uint_as_float(u16 << 16); }
 __device__ __forceinline__ uint32_t f2bf(float x) {
@@ -97,6 +99,16 @@ template <> __device__ __forceinline__ uint32_t f2h<F16>(float x) {
   return (uint32_t)__builtin_bit_cast(unsigned short, h);
 }
 template <typename H> __device__ __forceinline__ uint32_t pack2(float lo, float hi) { return f2h<H>(lo) | (f2h<H>(hi) << 16); }
+
+// One element of storage kind T (float / BF16 / F16) <-> float: the identity for fp32, h2f / f2h of the kind otherwise
+template <typename T> __device__ __forceinline__ float to_float(elem_t<T> e) {
+  if constexpr (TT<T>::SZ == 4) return e;
+  else return h2f<typename TT<T>::H>(e);
+}
+template <typename T> __device__ __forceinline__ elem_t<T> from_float(float x) {
+  if constexpr (TT<T>::SZ == 4) return x;
+  else return (elem_t<T>)f2h<typename TT<T>::H>(x);
+}
 
 // Load / store EPC<T> consecutive elements (one 16-byte chunk) as floats.
 template <typename T> __device__ __forceinline__ void load_chunk(const char* p, float* v);
@@ -266,6 +278,17 @@ template <class D> static inline bool desc_ok(const D* d) { return d != nullptr 
                 name, (d) ? (d)->struct_size : -1, (int)sizeof(*(d)), CTSEG_ABI_VERSION)
 
 static inline bool is16(int dtype) { return dtype == CTSEG_BF16 || dtype == CTSEG_F16; }   // 16-bit storage kinds
+
+// Run-time storage kind -> its tag: calls f(float{}), f(BF16{}) or f(F16{}) and returns true.  A code that is none of the three,
+// or a kind outside ACCEPT (a mask of 1 << CTSEG_*; no call is instantiated for it), calls nothing and returns false: the entry
+// point refuses it.
+constexpr unsigned ANY_STORAGE = 1u << CTSEG_F32 | 1u << CTSEG_BF16 | 1u << CTSEG_F16;
+template <unsigned ACCEPT = ANY_STORAGE, class F> static inline bool with_dtype(int dtype, F&& f) {
+  if constexpr ((ACCEPT >> CTSEG_F32) & 1) if (dtype == CTSEG_F32) return f(float{}), true;
+  if constexpr ((ACCEPT >> CTSEG_BF16) & 1) if (dtype == CTSEG_BF16) return f(BF16{}), true;
+  if constexpr ((ACCEPT >> CTSEG_F16) & 1) if (dtype == CTSEG_F16) return f(F16{}), true;
+  return false;
+}
 
 static inline int ilog_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 

@@ -1,5 +1,10 @@
-// Adam step, weight packing, dtype / layout plumbing and the C-ABI error channel (gfx950).
+// Adam step, weight packing, dtype / layout plumbing, the sliding-window gather and blend, and the C-ABI error channel (gfx950).
+// Kernels are instantiated on the storage tags float / BF16 / F16 of ctseg_dev.h: pointers are elem_t<T>*, elements convert with
+// to_float<T> / from_float<T>, 16-byte groups go through load_chunk / store_chunk, and every entry point picks its instantiation
+// with with_dtype.
 #include "ctseg_dev.h"
+
+#include <type_traits>
 
 namespace ctseg {
 
@@ -43,34 +48,31 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
-template <typename TD> __global__ void gather_cast_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx,
-                                                           TD* __restrict__ dst, int64_t n);
-template <typename TS, typename TD> __device__ __forceinline__ TD cvt(TS x);
-template <> __device__ __forceinline__ float cvt<float, float>(float x) { return x; }
-template <> __device__ __forceinline__ unsigned short cvt<float, unsigned short>(float x) { return (unsigned short)f2bf(x); }
-template <> __device__ __forceinline__ float cvt<unsigned short, float>(unsigned short x) { return bf2f(x); }
-template <> __device__ __forceinline__ unsigned short cvt<unsigned short, unsigned short>(unsigned short x) { return x; }
-// IEEE half storage (CTSEG_F16) travels as _Float16 here so that it is a distinct type from the raw-ushort bf16
-template <> __device__ __forceinline__ _Float16 cvt<float, _Float16>(float x) {
-  return __builtin_bit_cast(_Float16, (unsigned short)f2h<F16>(x));
-}
-template <> __device__ __forceinline__ float cvt<_Float16, float>(_Float16 x) { return (float)x; }
-
-template <typename TD> __global__ void gather_cast_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx,
-                                                           TD* __restrict__ dst, int64_t n) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = cvt<float, TD>(src[idx[i]]);
+// eight consecutive elements of storage kind T from floats: one 16-byte store of 16-bit storage, two of fp32
+template <typename T> __device__ __forceinline__ void store8(elem_t<T>* p, const float* v) {
+#pragma unroll
+  for (int e = 0; e < 8; e += TT<T>::EPC) store_chunk<T>(reinterpret_cast<char*>(p + e), v + e);
 }
 
-template <typename TS, typename TD> __global__ void cast_kernel(const TS* __restrict__ s, TD* __restrict__ d, int64_t n) {
+template <typename TD> __global__ void gather_cast_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx,
+                                                           elem_t<TD>* __restrict__ dst, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    d[i] = cvt<TS, TD>(s[i]);
+    dst[i] = from_float<TD>(src[idx[i]]);
+}
+
+// a cast between two kinds goes through fp32; the same kind on both sides is a raw copy (a bf16 NaN keeps its payload)
+template <typename TS, typename TD> __global__ void cast_kernel(const elem_t<TS>* __restrict__ s, elem_t<TD>* __restrict__ d, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (std::is_same_v<TS, TD>) d[i] = s[i];
+    else d[i] = from_float<TD>(to_float<TS>(s[i]));
+  }
 }
 
 // structured weight re-layout (ctseg_pack_weights): one workgroup per (block, row)
 template <typename TD> __global__ __launch_bounds__(256) void pack_weights_kernel(const float* __restrict__ src,
                                                                                   const ctseg_pack_block* __restrict__ blocks,
-                                                                                  const int32_t* __restrict__ rows, TD* __restrict__ dst) {
+                                                                                  const int32_t* __restrict__ rows,
+                                                                                  elem_t<TD>* __restrict__ dst) {
   __shared__ float s_w[CTSEG_PACK_LDS_FLOATS];     // the row's source region(s): (g_hi - g_lo) * T floats per part (caller-checked)
   const int b = rows[2 * blockIdx.x], n = rows[2 * blockIdx.x + 1];
   const ctseg_pack_block& B = blocks[b];
@@ -102,7 +104,7 @@ template <typename TD> __global__ __launch_bounds__(256) void pack_weights_kerne
     }
   }
   __syncthreads();
-  TD* drow = dst + B.dst_off + (int64_t)n * B.kpad;
+  elem_t<TD>* drow = dst + B.dst_off + (int64_t)n * B.kpad;
   const int used = B.ntaps * B.gs;
   // eight consecutive K slots per thread: when gs is a multiple of 8 (every pass with 16-byte chunked rows) they share their tap and
   // their gathered channels are consecutive: one division per 16 bytes stored (2-byte stores moved 128 bytes per wave instruction)
@@ -122,17 +124,7 @@ template <typename TD> __global__ __launch_bounds__(256) void pack_weights_kerne
               if (g0 + e >= g_lo && g0 + e < g_hi) v[e] = s_w[loff[p] + (g0 + e - g_lo) * T + tp];
           }
       }
-      if constexpr (sizeof(TD) == 4) {
-        reinterpret_cast<f32x4*>(drow + k0)[0] = f32x4{v[0], v[1], v[2], v[3]};
-        reinterpret_cast<f32x4*>(drow + k0)[1] = f32x4{v[4], v[5], v[6], v[7]};
-      } else {
-        u32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          o[e] = (uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(v[2 * e])) |
-                 ((uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(v[2 * e + 1])) << 16);
-        *reinterpret_cast<u32x4*>(drow + k0) = o;
-      }
+      store8<TD>(drow + k0, v);
     }
     return;
   }
@@ -145,90 +137,87 @@ template <typename TD> __global__ __launch_bounds__(256) void pack_weights_kerne
         if (p < B.nparts && n >= B.part[p].n_lo && n < B.part[p].n_hi && g >= B.part[p].g_lo && g < B.part[p].g_hi)
           v = s_w[loff[p] + (g - B.part[p].g_lo) * T + B.tap[j]];
     }
-    drow[k] = cvt<float, TD>(v);
+    drow[k] = from_float<TD>(v);
   }
 }
 
 // fp32 [N][C][S] -> [N][S][ld]; thread per (voxel, channel<ld): reads strided by S, writes contiguous (small C only)
-template <typename TD> __global__ void nc_to_cl_kernel(const float* __restrict__ s, TD* __restrict__ d, int C, int64_t S, int ld) {
+template <typename TD> __global__ void nc_to_cl_kernel(const float* __restrict__ s, elem_t<TD>* __restrict__ d, int C, int64_t S, int ld) {
   const int n = blockIdx.y;
   const int64_t total = S * ld;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t v = i / ld;
     const int c = (int)(i - v * ld);
     const float x = c < C ? s[((int64_t)n * C + c) * S + v] : 0.f;
-    d[(int64_t)n * total + i] = cvt<float, TD>(x);
+    d[(int64_t)n * total + i] = from_float<TD>(x);
   }
 }
 // C == ld == 1 (the U-Net's one-channel input): a plain cast, 8 elements per thread (two 16-byte loads, one 16-byte store of
 // 16-bit storage).  The general kernel above does a 64-bit division and a 2-byte store per element: 95 us for the 100 MB batch,
 // on the critical path between two training steps (the next stem convolution waits for it).
-template <typename TD> __global__ __launch_bounds__(256) void cast8_kernel(const float* __restrict__ s, TD* __restrict__ d, int64_t n8) {
+template <typename TD> __global__ __launch_bounds__(256) void cast8_kernel(const float* __restrict__ s, elem_t<TD>* __restrict__ d,
+                                                                           int64_t n8) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-    const f32x4 a = reinterpret_cast<const f32x4*>(s)[2 * i], b = reinterpret_cast<const f32x4*>(s)[2 * i + 1];
-    if constexpr (sizeof(TD) == 4) {
-      reinterpret_cast<f32x4*>(d)[2 * i] = a;
-      reinterpret_cast<f32x4*>(d)[2 * i + 1] = b;
-    } else {
-      u32x4 o;
-      o[0] = (uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(a[0])) | ((uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(a[1])) << 16);
-      o[1] = (uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(a[2])) | ((uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(a[3])) << 16);
-      o[2] = (uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(b[0])) | ((uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(b[1])) << 16);
-      o[3] = (uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(b[2])) | ((uint32_t)__builtin_bit_cast(unsigned short, cvt<float, TD>(b[3])) << 16);
-      reinterpret_cast<u32x4*>(d)[i] = o;
-    }
+    float v[8];
+    load_chunk<float>(reinterpret_cast<const char*>(s + 8 * i), v);
+    load_chunk<float>(reinterpret_cast<const char*>(s + 8 * i + 4), v + 4);
+    store8<TD>(d + 8 * i, v);
   }
 }
-template <typename TS> __global__ void cl_to_nc_kernel(const TS* __restrict__ s, float* __restrict__ d, int C, int64_t S, int ld) {
+template <typename TS> __global__ void cl_to_nc_kernel(const elem_t<TS>* __restrict__ s, float* __restrict__ d, int C, int64_t S, int ld) {
   const int n = blockIdx.y;
   const int64_t total = S * C;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(i / S);
     const int64_t v = i - (int64_t)c * S;
-    d[(int64_t)n * total + i] = cvt<TS, float>(s[((int64_t)n * S + v) * ld + c]);
+    d[(int64_t)n * total + i] = to_float<TS>(s[((int64_t)n * S + v) * ld + c]);
   }
 }
 
 // ---- sliding-window inference (semantics of MONAI's sliding_window_inference) ----
-// one window per launch: windows of a batch may overlap, stream order makes the accumulation deterministic
+// voxel v of an rx x ry x rz window (z fastest) -> its (x, y, z) inside the window
+__device__ __forceinline__ int3 window_xyz(int64_t v, int ry, int rz) {
+  const int z = (int)(v % rz), y = (int)((v / rz) % ry), x = (int)(v / ((int64_t)rz * ry));
+  return make_int3(x, y, z);
+}
+// the window at (x0, y0, z0) of vol [Cin][X][Y][Z] -> dst [rx][ry][rz][ld]: cval outside the volume, zero in the pad channels.
+// The kernels hand in their grid-stride bounds: blockDim read inside a __device__ function compiles to a vector load from the
+// implicit kernel arguments ahead of the loop, where a kernel reads it with a scalar load.
 template <typename TD>
-__global__ void window_gather_kernel(const float* __restrict__ vol, int Cin, int X, int Y, int Z, int x0, int y0, int z0, int rx,
-                                     int ry, int rz, float cval, TD* __restrict__ dst, int ld) {
+__device__ __forceinline__ void window_gather_body(const float* __restrict__ vol, int Cin, int X, int Y, int Z, int x0, int y0, int z0,
+                                                   int rx, int ry, int rz, float cval, elem_t<TD>* __restrict__ dst, int ld,
+                                                   int64_t first, int64_t stride) {
   const int64_t total = (int64_t)rx * ry * rz * ld;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = first; i < total; i += stride) {
     const int64_t v = i / ld;
     const int c = (int)(i - v * ld);
-    const int z = (int)(v % rz), y = (int)((v / rz) % ry), x = (int)(v / ((int64_t)rz * ry));
-    const int gx = x0 + x, gy = y0 + y, gz = z0 + z;
+    const int3 p = window_xyz(v, ry, rz);
+    const int gx = x0 + p.x, gy = y0 + p.y, gz = z0 + p.z;
     float val = 0.f;
     if (c < Cin) {
       const bool in = (unsigned)gx < (unsigned)X && (unsigned)gy < (unsigned)Y && (unsigned)gz < (unsigned)Z;
       val = in ? vol[(((int64_t)c * X + gx) * Y + gy) * Z + gz] : cval;
     }
-    dst[i] = cvt<float, TD>(val);
+    dst[i] = from_float<TD>(val);
   }
+}
+// one window per launch
+template <typename TD>
+__global__ void window_gather_kernel(const float* __restrict__ vol, int Cin, int X, int Y, int Z, int x0, int y0, int z0, int rx,
+                                     int ry, int rz, float cval, elem_t<TD>* __restrict__ dst, int ld) {
+  window_gather_body<TD>(vol, Cin, X, Y, Z, x0, y0, z0, rx, ry, rz, cval, dst, ld, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                         (int64_t)gridDim.x * blockDim.x);
 }
 // every window of a forward batch in one launch (blockIdx.y = window, origins read from the device)
 template <typename TD>
 __global__ void window_gather_batch_kernel(const float* __restrict__ vol, int Cin, int X, int Y, int Z, const int* __restrict__ starts,
-                                           int rx, int ry, int rz, float cval, TD* __restrict__ dst, int ld) {
+                                           int rx, int ry, int rz, float cval, elem_t<TD>* __restrict__ dst, int ld) {
   const int w = blockIdx.y;
-  const int x0 = starts[3 * w], y0 = starts[3 * w + 1], z0 = starts[3 * w + 2];
-  const int64_t total = (int64_t)rx * ry * rz * ld;
-  TD* d = dst + (int64_t)w * total;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t v = i / ld;
-    const int c = (int)(i - v * ld);
-    const int z = (int)(v % rz), y = (int)((v / rz) % ry), x = (int)(v / ((int64_t)rz * ry));
-    const int gx = x0 + x, gy = y0 + y, gz = z0 + z;
-    float val = 0.f;
-    if (c < Cin) {
-      const bool in = (unsigned)gx < (unsigned)X && (unsigned)gy < (unsigned)Y && (unsigned)gz < (unsigned)Z;
-      val = in ? vol[(((int64_t)c * X + gx) * Y + gy) * Z + gz] : cval;
-    }
-    d[i] = cvt<float, TD>(val);
-  }
+  window_gather_body<TD>(vol, Cin, X, Y, Z, starts[3 * w], starts[3 * w + 1], starts[3 * w + 2], rx, ry, rz, cval,
+                         dst + (int64_t)w * rx * ry * rz * ld, ld, blockIdx.x * (int64_t)blockDim.x + threadIdx.x,
+                         (int64_t)gridDim.x * blockDim.x);
 }
+// one window per launch: windows of a batch may overlap, stream order makes the accumulation deterministic
 __global__ void window_blend_kernel(const float* __restrict__ logits, int ld, int C, int rx, int ry, int rz, int x0, int y0, int z0,
                                     const float* __restrict__ imp, const float* __restrict__ inv_count, float* __restrict__ out,
                                     int X, int Y, int Z, int out_ld) {
@@ -236,8 +225,8 @@ __global__ void window_blend_kernel(const float* __restrict__ logits, int ld, in
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t v = i / C;
     const int c = (int)(i - v * C);
-    const int z = (int)(v % rz), y = (int)((v / rz) % ry), x = (int)(v / ((int64_t)rz * ry));
-    const int gx = x0 + x, gy = y0 + y, gz = z0 + z;
+    const int3 p = window_xyz(v, ry, rz);
+    const int gx = x0 + p.x, gy = y0 + p.y, gz = z0 + p.z;
     if ((unsigned)gx >= (unsigned)X || (unsigned)gy >= (unsigned)Y || (unsigned)gz >= (unsigned)Z) continue;   // padded rim
     const int64_t d = ((int64_t)gx * Y + gy) * Z + gz;
     out[d * out_ld + c] += imp[v] * (inv_count ? inv_count[d] : 1.f) * logits[v * ld + c];
@@ -314,97 +303,76 @@ extern "C" int ctseg_adam_step(float* p, const float* g, float* m, float* v, int
 
 // x *= host_scale * (dev_scale ? *dev_scale : 1); every block reads the factor and leaves at once when it is exactly 1 (the usual
 // upstream gradient of ``loss.backward()``): the drop-in path pays a ~5 us launch, not a pass over d loss / d logits
-template <typename T> __global__ __launch_bounds__(256) void scale_inplace_kernel(T* __restrict__ x, int64_t n, const float* __restrict__ dev_scale,
-                                                                                    float host_scale) {
+template <typename T> __global__ __launch_bounds__(256) void scale_inplace_kernel(elem_t<T>* __restrict__ x, int64_t n,
+                                                                                    const float* __restrict__ dev_scale, float host_scale) {
   const float f = host_scale * (dev_scale ? *dev_scale : 1.f);
   if (f == 1.f) return;
-  constexpr int V = 16 / sizeof(T);
+  constexpr int V = TT<T>::EPC;
   const int64_t nv = n / V;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nv; i += (int64_t)gridDim.x * blockDim.x) {
-    if constexpr (sizeof(T) == 4) {
-      f32x4 v = reinterpret_cast<f32x4*>(x)[i];
+    char* p = reinterpret_cast<char*>(x) + 16 * i;
+    float v[V];
+    load_chunk<T>(p, v);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] *= f;
-      reinterpret_cast<f32x4*>(x)[i] = v;
-    } else {
-      u32x4 v = reinterpret_cast<u32x4*>(x)[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const unsigned lo = (unsigned)f2bf(bf2f(v[e] & 0xffffu) * f), hi = (unsigned)f2bf(bf2f(v[e] >> 16) * f);
-        v[e] = (lo & 0xffffu) | (hi << 16);
-      }
-      reinterpret_cast<u32x4*>(x)[i] = v;
-    }
+    for (int e = 0; e < V; ++e) v[e] *= f;
+    store_chunk<T>(p, v);
   }
   if (blockIdx.x == 0 && threadIdx.x < (int)(n - nv * V)) {
     const int64_t i = nv * V + threadIdx.x;
-    if constexpr (sizeof(T) == 4) x[i] *= f;
-    else x[i] = (T)f2bf(bf2f(x[i]) * f);
+    x[i] = from_float<T>(to_float<T>(x[i]) * f);
   }
 }
 
 extern "C" int ctseg_scale_inplace(void* x, int32_t dtype, int64_t n, const float* dev_scale, float host_scale, void* stream) {
   CTSEG_REQUIRE(x && n > 0 && (dtype == CTSEG_F32 || dtype == CTSEG_BF16) && ((uintptr_t)x % 16) == 0, "scale_inplace: bad arguments");
   dim3 grid(nblocks(n / 8 + 1, 2048)), blk(256);
-  if (dtype == CTSEG_F32)
-    hipLaunchKernelGGL(scale_inplace_kernel<float>, grid, blk, 0, (hipStream_t)stream, (float*)x, n, dev_scale, host_scale);
-  else
-    hipLaunchKernelGGL(scale_inplace_kernel<unsigned short>, grid, blk, 0, (hipStream_t)stream, (unsigned short*)x, n, dev_scale, host_scale);
+  with_dtype<1u << CTSEG_F32 | 1u << CTSEG_BF16>(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(scale_inplace_kernel<T>, grid, blk, 0, (hipStream_t)stream, (elem_t<T>*)x, n, dev_scale, host_scale);
+  });
   CTSEG_LAUNCH_CHECK("scale_inplace");
   return 0;
 }
 
 extern "C" int ctseg_gather_cast(const float* src, const int32_t* idx, void* dst, int32_t dtype, int64_t n, void* stream) {
   CTSEG_REQUIRE(src && idx && dst && n > 0 && (dtype == CTSEG_F32 || is16(dtype)), "gather_cast: bad arguments");
-  if (dtype == CTSEG_F32)
-    hipLaunchKernelGGL(gather_cast_kernel<float>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, src, idx, (float*)dst, n);
-  else if (dtype == CTSEG_F16)
-    hipLaunchKernelGGL(gather_cast_kernel<_Float16>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, src, idx, (_Float16*)dst, n);
-  else
-    hipLaunchKernelGGL(gather_cast_kernel<unsigned short>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, src, idx,
-                       (unsigned short*)dst, n);
+  with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(gather_cast_kernel<T>, dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, src, idx, (elem_t<T>*)dst, n);
+  });
   CTSEG_LAUNCH_CHECK("gather_cast");
   return 0;
 }
 
 extern "C" int ctseg_cast(const void* src, int32_t sd, void* dst, int32_t dd, int64_t n, void* stream) {
   CTSEG_REQUIRE(src && dst && n > 0, "cast: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(nblocks(n)), blk(256);
-  if (sd == CTSEG_F32 && dd == CTSEG_BF16)
-    hipLaunchKernelGGL((cast_kernel<float, unsigned short>), grid, blk, 0, st, (const float*)src, (unsigned short*)dst, n);
-  else if (sd == CTSEG_BF16 && dd == CTSEG_F32)
-    hipLaunchKernelGGL((cast_kernel<unsigned short, float>), grid, blk, 0, st, (const unsigned short*)src, (float*)dst, n);
-  else if (sd == CTSEG_F32 && dd == CTSEG_F32)
-    hipLaunchKernelGGL((cast_kernel<float, float>), grid, blk, 0, st, (const float*)src, (float*)dst, n);
-  else if (sd == CTSEG_BF16 && dd == CTSEG_BF16)
-    hipLaunchKernelGGL((cast_kernel<unsigned short, unsigned short>), grid, blk, 0, st, (const unsigned short*)src,
-                       (unsigned short*)dst, n);
-  else if (sd == CTSEG_F32 && dd == CTSEG_F16)
-    hipLaunchKernelGGL((cast_kernel<float, _Float16>), grid, blk, 0, st, (const float*)src, (_Float16*)dst, n);
-  else if (sd == CTSEG_F16 && dd == CTSEG_F32)
-    hipLaunchKernelGGL((cast_kernel<_Float16, float>), grid, blk, 0, st, (const _Float16*)src, (float*)dst, n);
-  else CTSEG_REQUIRE(false, "cast: bad dtypes %d -> %d", sd, dd);
+  bool ok = false;      // fp32 <-> any kind, and the raw copies fp32 -> fp32, bf16 -> bf16; half <-> bf16 and half -> half are refused
+  with_dtype(sd, [&](auto s) {
+    with_dtype(dd, [&](auto d) {
+      using TS = decltype(s);
+      using TD = decltype(d);
+      if constexpr (std::is_same_v<TS, float> || std::is_same_v<TD, float> || (std::is_same_v<TS, BF16> && std::is_same_v<TD, BF16>)) {
+        hipLaunchKernelGGL((cast_kernel<TS, TD>), dim3(nblocks(n)), dim3(256), 0, (hipStream_t)stream, (const elem_t<TS>*)src,
+                           (elem_t<TD>*)dst, n);
+        ok = true;
+      }
+    });
+  });
+  CTSEG_REQUIRE(ok, "cast: bad dtypes %d -> %d", sd, dd);
   CTSEG_LAUNCH_CHECK("cast");
   return 0;
 }
 
 extern "C" int ctseg_nc_to_cl(const float* src, void* dst, int32_t dtype, int32_t N, int32_t C, int64_t S, int32_t ld,
                               void* stream) {
-  CTSEG_REQUIRE(src && dst && N > 0 && C > 0 && S > 0 && ld >= C, "nc_to_cl: bad arguments");
-  if (C == 1 && ld == 1 && ((int64_t)N * S) % 8 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0) {
+  CTSEG_REQUIRE(src && dst && N > 0 && C > 0 && S > 0 && ld >= C && (dtype == CTSEG_F32 || is16(dtype)), "nc_to_cl: bad arguments");
+  const bool eight = C == 1 && ld == 1 && ((int64_t)N * S) % 8 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0;
+  with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
     const int64_t n8 = (int64_t)N * S / 8;
-    const dim3 g8(nblocks(n8 * 256 / 256, 8192));
-    if (dtype == CTSEG_F32) hipLaunchKernelGGL(cast8_kernel<float>, g8, dim3(256), 0, (hipStream_t)stream, src, (float*)dst, n8);
-    else if (dtype == CTSEG_F16) hipLaunchKernelGGL(cast8_kernel<_Float16>, g8, dim3(256), 0, (hipStream_t)stream, src, (_Float16*)dst, n8);
-    else hipLaunchKernelGGL(cast8_kernel<unsigned short>, g8, dim3(256), 0, (hipStream_t)stream, src, (unsigned short*)dst, n8);
-    CTSEG_LAUNCH_CHECK("nc_to_cl");
-    return 0;
-  }
-  dim3 grid(nblocks(S * ld), N);
-  if (dtype == CTSEG_F32) hipLaunchKernelGGL(nc_to_cl_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, (float*)dst, C, S, ld);
-  else if (dtype == CTSEG_F16) hipLaunchKernelGGL(nc_to_cl_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, src, (_Float16*)dst, C, S, ld);
-  else hipLaunchKernelGGL(nc_to_cl_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, src, (unsigned short*)dst, C, S, ld);
+    if (eight) hipLaunchKernelGGL(cast8_kernel<T>, dim3(nblocks(n8, 8192)), dim3(256), 0, (hipStream_t)stream, src, (elem_t<T>*)dst, n8);
+    else hipLaunchKernelGGL(nc_to_cl_kernel<T>, dim3(nblocks(S * ld), N), dim3(256), 0, (hipStream_t)stream, src, (elem_t<T>*)dst, C, S, ld);
+  });
   CTSEG_LAUNCH_CHECK("nc_to_cl");
   return 0;
 }
@@ -413,37 +381,34 @@ extern "C" int ctseg_pack_weights(const float* src, const ctseg_pack_block* bloc
                                   void* dst, int32_t dtype, void* stream) {
   CTSEG_REQUIRE(src && blocks && rows && dst && n_blocks > 0 && n_rows > 0, "pack_weights: bad arguments");
   CTSEG_REQUIRE(dtype == CTSEG_F32 || is16(dtype), "pack_weights: bad dtype %d", dtype);
-  const dim3 grid((unsigned)n_rows);
-  if (dtype == CTSEG_F32) hipLaunchKernelGGL(pack_weights_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, blocks, rows, (float*)dst);
-  else if (dtype == CTSEG_F16) hipLaunchKernelGGL(pack_weights_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, src, blocks, rows, (_Float16*)dst);
-  else hipLaunchKernelGGL(pack_weights_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, src, blocks, rows, (unsigned short*)dst);
+  with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(pack_weights_kernel<T>, dim3((unsigned)n_rows), dim3(256), 0, (hipStream_t)stream, src, blocks, rows, (elem_t<T>*)dst);
+  });
   CTSEG_LAUNCH_CHECK("pack_weights");
   return 0;
 }
 
 extern "C" int ctseg_cl_to_nc(const void* src, int32_t dtype, float* dst, int32_t N, int32_t C, int64_t S, int32_t ld,
                               void* stream) {
-  CTSEG_REQUIRE(src && dst && N > 0 && C > 0 && S > 0 && ld >= C, "cl_to_nc: bad arguments");
-  dim3 grid(nblocks(S * C), N);
-  if (dtype == CTSEG_F32) hipLaunchKernelGGL(cl_to_nc_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)src, dst, C, S, ld);
-  else if (dtype == CTSEG_F16) hipLaunchKernelGGL(cl_to_nc_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)src, dst, C, S, ld);
-  else hipLaunchKernelGGL(cl_to_nc_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, (const unsigned short*)src, dst, C, S, ld);
+  CTSEG_REQUIRE(src && dst && N > 0 && C > 0 && S > 0 && ld >= C && (dtype == CTSEG_F32 || is16(dtype)), "cl_to_nc: bad arguments");
+  with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(cl_to_nc_kernel<T>, dim3(nblocks(S * C), N), dim3(256), 0, (hipStream_t)stream, (const elem_t<T>*)src, dst, C, S, ld);
+  });
   CTSEG_LAUNCH_CHECK("cl_to_nc");
   return 0;
 }
 
 extern "C" int ctseg_window_gather(const float* vol, int32_t Cin, int32_t X, int32_t Y, int32_t Z, int32_t x0, int32_t y0, int32_t z0,
                                    int32_t rx, int32_t ry, int32_t rz, float cval, void* dst, int32_t dtype, int32_t ld, void* stream) {
-  CTSEG_REQUIRE(vol && dst && Cin > 0 && ld >= Cin && X > 0 && Y > 0 && Z > 0 && rx > 0 && ry > 0 && rz > 0, "window_gather: bad arguments");
-  dim3 grid(nblocks((int64_t)rx * ry * rz * ld));
-  if (dtype == CTSEG_F32)
-    hipLaunchKernelGGL(window_gather_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cin, X, Y, Z, x0, y0, z0, rx, ry, rz, cval, (float*)dst, ld);
-  else if (dtype == CTSEG_F16)
-    hipLaunchKernelGGL(window_gather_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cin, X, Y, Z, x0, y0, z0, rx, ry, rz, cval,
-                       (_Float16*)dst, ld);
-  else
-    hipLaunchKernelGGL(window_gather_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cin, X, Y, Z, x0, y0, z0, rx, ry, rz, cval,
-                       (unsigned short*)dst, ld);
+  CTSEG_REQUIRE(vol && dst && Cin > 0 && ld >= Cin && X > 0 && Y > 0 && Z > 0 && rx > 0 && ry > 0 && rz > 0 &&
+                    (dtype == CTSEG_F32 || is16(dtype)), "window_gather: bad arguments");
+  with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(window_gather_kernel<T>, dim3(nblocks((int64_t)rx * ry * rz * ld)), dim3(256), 0, (hipStream_t)stream, vol, Cin, X, Y,
+                       Z, x0, y0, z0, rx, ry, rz, cval, (elem_t<T>*)dst, ld);
+  });
   CTSEG_LAUNCH_CHECK("window_gather");
   return 0;
 }
@@ -452,17 +417,12 @@ extern "C" int ctseg_window_gather_batch(const float* vol, int32_t Cin, int32_t 
                                          int32_t rx, int32_t ry, int32_t rz, float cval, void* dst, int32_t dtype, int32_t ld,
                                          void* stream) {
   CTSEG_REQUIRE(vol && dst && starts && nw > 0 && nw < 65536 && Cin > 0 && ld >= Cin && X > 0 && Y > 0 && Z > 0 && rx > 0 && ry > 0 &&
-                    rz > 0, "window_gather_batch: bad arguments");
-  dim3 grid(nblocks((int64_t)rx * ry * rz * ld, 1024), (unsigned)nw);
-  if (dtype == CTSEG_F32)
-    hipLaunchKernelGGL(window_gather_batch_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cin, X, Y, Z, starts, rx, ry, rz,
-                       cval, (float*)dst, ld);
-  else if (dtype == CTSEG_F16)
-    hipLaunchKernelGGL(window_gather_batch_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cin, X, Y, Z, starts, rx,
-                       ry, rz, cval, (_Float16*)dst, ld);
-  else
-    hipLaunchKernelGGL(window_gather_batch_kernel<unsigned short>, grid, dim3(256), 0, (hipStream_t)stream, vol, Cin, X, Y, Z, starts, rx,
-                       ry, rz, cval, (unsigned short*)dst, ld);
+                    rz > 0 && (dtype == CTSEG_F32 || is16(dtype)), "window_gather_batch: bad arguments");
+  with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(window_gather_batch_kernel<T>, dim3(nblocks((int64_t)rx * ry * rz * ld, 1024), (unsigned)nw), dim3(256), 0,
+                       (hipStream_t)stream, vol, Cin, X, Y, Z, starts, rx, ry, rz, cval, (elem_t<T>*)dst, ld);
+  });
   CTSEG_LAUNCH_CHECK("window_gather_batch");
   return 0;
 }

@@ -44,6 +44,12 @@ expression (same association, windows in the same order) against it; asserted to
 Measured on an MI355X (max |out - out64|, bound in brackets):
   per window 1.0e-07 .. 1.5e-07 (5.4e-07 .. 8.3e-07);  batch 2.5e-07 .. 3.1e-07 (1.2e-06 .. 1.7e-06), the same with and without a bbox
 
+Every entry point picks one template instantiation per storage kind (with_dtype, ctseg_dev.h); entry point x accepted kind, all
+compared bit for bit here: ctseg_cast 6 pairs; ctseg_gather_cast, ctseg_nc_to_cl (general and 8-wide), ctseg_cl_to_nc,
+ctseg_pack_weights (plan-built and hand-written descriptions), ctseg_window_gather, ctseg_window_gather_batch fp32 / bf16 / fp16;
+ctseg_scale_inplace fp32 / bf16.  A dtype code that is no storage kind is refused; asserted for the layout, gather_cast and window
+gather entry points (test_layout_and_gather_refuse_a_dtype_that_is_no_storage_kind).
+
 Not covered, with the library's own reason:
   * ctseg_cast F16 -> BF16, BF16 -> F16, F16 -> F16: refused ("cast: bad dtypes"), asserted;
   * ctseg_scale_inplace on half storage: refused ("scale_inplace: bad arguments": the two users scale fp32 and bf16 gradients; half is
@@ -273,6 +279,22 @@ def test_nc_to_cl_eight_wide_above_the_block_cap(dt):
     _assert_bits(_nc_to_cl(x, dt, N, 1, S, 1), _nc_to_cl_ref(x, dt, N, 1, S, 1), "8-wide cast above the cap")
 
 
+def test_layout_and_gather_refuse_a_dtype_that_is_no_storage_kind():
+    """code 2 (CTSEG_I16) is a raw-input dtype of the resize pass only: every entry point that picks a kernel by storage kind refuses it"""
+    s, d = torch.zeros(64, device=DEV), _dst(64, F32, 0)
+    idx = torch.zeros(8, dtype=torch.int32, device=DEV)
+    calls = {"nc_to_cl": ("ctseg_nc_to_cl", s.data_ptr(), d.data_ptr(), 2, 1, 1, 8, 1),
+             "cl_to_nc": ("ctseg_cl_to_nc", s.data_ptr(), 2, d.data_ptr(), 1, 1, 8, 1),
+             "gather_cast": ("ctseg_gather_cast", s.data_ptr(), idx.data_ptr(), d.data_ptr(), 2, 8),
+             "window_gather": ("ctseg_window_gather", s.data_ptr(), 1, 2, 2, 2, 0, 0, 0, 2, 2, 2, 0.0, d.data_ptr(), 2, 1),
+             "window_gather_batch": ("ctseg_window_gather_batch", s.data_ptr(), 1, 2, 2, 2, idx.data_ptr(), 1, 2, 2, 2, 0.0, d.data_ptr(), 2, 1)}
+    for name, args in calls.items():
+        with pytest.raises(NativeError, match=name + ": bad arguments"):
+            nat.call(*args)
+    torch.cuda.synchronize()
+    assert _tail_untouched(d, 0)
+
+
 # ---- 3. weight packing -------------------------------------------------------------------------------------------------------
 def _pack_plan(dt, first=None):
     """the layers the issue names in one plan (one packed buffer, many blocks): name -> GemmLayer"""
@@ -394,7 +416,7 @@ def _synthetic_reference(src, blocks, n_dst):
     return out
 
 
-@pytest.mark.parametrize("dt", [F32, BF16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("dt", DTS, ids=DT_IDS)
 def test_pack_weights_synthetic_descriptions(dt):
     blocks = _synthetic_blocks()
     staged = [sum((gh - gl) * B["T"] for (_, _, _, gl, gh, _, _) in B["parts"]) for B in blocks]
