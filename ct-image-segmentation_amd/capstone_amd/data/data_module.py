@@ -1,8 +1,8 @@
 """Drop-in for reference capstone/data/data_module.py: ``MiccaiDataModule2D`` / ``FullMiccaiDataModule2D`` over the device store.
 
-The loaders are plain iterables of device batches ``(images, masks, mask_indicator)``: a shuffled (train) or sequential order cut
-into ``batch_size`` pieces, each piece one ``MiccaiDataset2D.batch`` launch.  No workers, no pinned memory: nothing crosses the
-host after ``setup``.  The classes derive from ``pl.LightningDataModule`` only when Lightning is importable.
+The loaders are plain iterables of device batches ``(images, masks, mask_indicator)`` (``enhanced=True, device_maps=True``: plus
+``distance_maps``): a shuffled (train) or sequential order cut into ``batch_size`` pieces, each piece one ``MiccaiDataset2D.batch``
+launch.  No workers, no pinned memory: nothing crosses the host after ``setup``.  The classes derive from ``pl.LightningDataModule`` only when Lightning is importable.
 """
 from typing import Optional
 
@@ -59,23 +59,25 @@ class DeviceBatches:
             if len(parts) == 1:
                 yield parts[0]
             else:
-                yield torch.cat([p[0] for p in parts]), _cat_masks([p[1] for p in parts]), torch.cat([p[2] for p in parts])
+                # (an enhanced dataset's fourth element, the distance maps, is concatenated like the indicator)
+                yield (torch.cat([p[0] for p in parts]), _cat_masks([p[1] for p in parts])) + tuple(
+                    torch.cat([p[k] for p in parts]) for k in range(2, len(parts[0])))
 
 
 class MiccaiDataModule2D(pl.LightningDataModule if pl is not None else object):
     def __init__(self, batch_size, transform_degree: int = None, enhanced=False, root: str = "storage", device="cuda",
-                 generator=None, device_warps=False, **kwargs):
+                 generator=None, device_warps=False, device_maps=False, **kwargs):
         super().__init__()
         self.batch_size = batch_size
         assert transform_degree in DEGREE.keys(), "Invalid transform degree passed"
         self.transform = WARPED_DEGREE[transform_degree] if device_warps and transform_degree in WARPED_DEGREE else DEGREE[transform_degree]
-        self.enhanced = enhanced
+        self.enhanced, self.device_maps = enhanced, device_maps      # enhanced without device_maps: the old refusal, at setup
         self.root, self.device = root, device
         self.generator = generator                 # numpy Generator: the shuffle and the random crop / rot90 / flip
 
     def _dataset(self, split, side):
         return get_miccai_2d(split=split, transform=self.transform[side], enhanced=self.enhanced, root=self.root, device=self.device,
-                             generator=self.generator)
+                             generator=self.generator, device_maps=self.device_maps)
 
     def setup(self, stage: Optional[str] = None):
         if stage == "fit" or stage is None:

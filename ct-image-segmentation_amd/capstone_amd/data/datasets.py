@@ -6,7 +6,9 @@ device store (``transforms.pipeline2d.SliceStore2D``: raw image elements, mask b
 ``mask_indicator`` (N, 9).  ``transform`` is a ``BatchPipeline2D`` (capstone_amd/transforms/predefined.py) instead of an
 albumentations Compose.  ``__getitem__`` returns the reference's triple ``(image (C,H',W'), masks (9,H',W'), mask_indicator (9,))``
 as device tensors; ``batch(indices)`` is the route the data module takes: one launch for the whole batch.
-Distance maps (``enhanced=True``, the Boundary loss) raise ``NotImplementedError``, as in the trainers.
+``EnhancedMiccaiDataset2D`` (``enhanced=True`` together with the opt-in ``device_maps=True``) adds the per-class distance maps of the
+transformed masks (data/utils.py) as a fourth element, computed on the device.  ``enhanced=True`` alone raises
+``NotImplementedError`` as before, and the Boundary loss that would consume the maps still raises in the trainers.
 """
 from pathlib import Path
 
@@ -15,6 +17,7 @@ import torch
 
 from .. import STRUCTURES
 from ..transforms.pipeline2d import SliceStore2D
+from .utils import compute_distance_map
 
 
 class MiccaiDataset2D:
@@ -56,8 +59,38 @@ class MiccaiDataset2D:
         return images[0], masks[0], indicator[0]
 
 
-def get_miccai_2d(split: str = "train", transform=None, enhanced=False, root: str = "storage", device="cuda", generator=None):
+class EnhancedMiccaiDataset2D(MiccaiDataset2D):
+    """reference datasets.py:58-69: the triple plus ``distance_maps`` (9, H', W') fp32 of the TRANSFORMED nine masks.  ``signed``:
+    the float signed map instead of the reference's uint8-wrapped one (data/utils.py)."""
+
+    def __init__(self, path: str, transform=None, device="cuda", generator=None, signed=False) -> None:
+        super().__init__(path, transform=transform, device=device, generator=generator)
+        self.signed = bool(signed)
+
+    def batch(self, indices, params=None):
+        """-> (images, masks — or the label maps of a squashing pipeline, stashes included —, mask_indicator,
+        distance_maps (B,9,H',W') fp32).  A squashing pipeline writes the nine masks in the same launch as its labels: overlapping
+        structures cannot be taken back from a label map."""
+        if self.transform is None:
+            raise ValueError("EnhancedMiccaiDataset2D.batch needs a BatchPipeline2D transform (raw slices differ in size)")
+        idx = torch.as_tensor(np.asarray(indices, dtype=np.int64))
+        images, masks, _ = self.transform(self.store, idx, params=params, generator=self.generator, with_masks=True)
+        nine = masks._ctseg_masks if hasattr(masks, "_ctseg_masks") else masks
+        return images, masks, self.mask_indicator[idx.to(self.device)], compute_distance_map(nine, signed=self.signed)
+
+    def __getitem__(self, index: int):
+        if self.transform is None:
+            image, masks, indicator = super().__getitem__(index)
+            return image, masks, indicator, compute_distance_map(masks, signed=self.signed)
+        images, masks, indicator, maps = self.batch([index])
+        return images[0], masks[0], indicator[0], maps[0]
+
+
+def get_miccai_2d(split: str = "train", transform=None, enhanced=False, root: str = "storage", device="cuda", generator=None,
+                  device_maps=False):
     assert split in ["train", "valid", "test"], "Invalid data split passed"
-    if enhanced:
-        raise NotImplementedError("distance maps (EnhancedMiccaiDataset2D, Boundary loss) are outside the MI355X hot path")
-    return MiccaiDataset2D(f"{root}/miccai_2d/{split}", transform=transform, device=device, generator=generator)
+    if enhanced and not device_maps:
+        raise NotImplementedError("distance maps (EnhancedMiccaiDataset2D) are computed on the device only on request: pass "
+                                  "device_maps=True (the Boundary loss that consumes them is outside the MI355X hot path)")
+    _dataset = EnhancedMiccaiDataset2D if enhanced else MiccaiDataset2D
+    return _dataset(f"{root}/miccai_2d/{split}", transform=transform, device=device, generator=generator)

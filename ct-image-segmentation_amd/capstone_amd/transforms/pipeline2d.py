@@ -117,7 +117,9 @@ class BatchPipeline2D:
     table of y0, x0, k, flip ("crop" only).  Without it the values are drawn on the host from ``generator`` (a
     ``numpy.random.Generator``) with the reference's probabilities: crop origin uniform over the valid range, rot90 with p = 0.5
     and then k uniform in 0..3 (0 or 2 for a non-square size), flip with p = 0.5.  albumentations' own stream is not reproduced.
-    The masks result carries ``_ctseg_present`` and, when squashing, ``_ctseg_labels`` = (labels (B, S), hist)."""
+    The masks result carries ``_ctseg_present`` and, when squashing, ``_ctseg_labels`` = (labels (B, S), hist); with
+    ``with_masks=True`` a squashing pipeline also writes the K unsquashed masks in the same launch and hands them over as
+    ``_ctseg_masks`` (structures can overlap: they cannot be taken back from the labels)."""
 
     def __init__(self, windows, mode, size, mean=None, std=None, squash: bool = False, shift: bool = True):
         self.windows = [tuple(int(v) for v in w) for w in windows]
@@ -156,7 +158,7 @@ class BatchPipeline2D:
         out[:, 3] = g.random(B) < 0.5
         return out
 
-    def __call__(self, store: SliceStore2D, indices, *, params=None, generator=None):
+    def __call__(self, store: SliceStore2D, indices, *, params=None, generator=None, with_masks=False):
         nat.require_gpu(store.images, "BatchPipeline2D")
         idx = np.asarray(indices.cpu() if isinstance(indices, torch.Tensor) else indices, dtype=np.int64).reshape(-1)
         if len(idx) == 0 or idx.min() < 0 or idx.max() >= len(store):
@@ -177,11 +179,13 @@ class BatchPipeline2D:
         elif params is not None:
             raise ValueError("BatchPipeline2D: params belong to the crop mode")
         image, m_out, lab, hist, present = pipeline2d_batch(
-            store, table, self.mode, self.size, self.windows, self.shift, self.mean, self.denom, want_masks=not self.squash,
-            want_labels=self.squash, want_present=True)
+            store, table, self.mode, self.size, self.windows, self.shift, self.mean, self.denom,
+            want_masks=not self.squash or with_masks, want_labels=self.squash, want_present=True)
         masks = lab if self.squash else m_out
         if masks is not None:
             masks._ctseg_present = present
             if self.squash:
                 masks._ctseg_labels = (lab.reshape(len(idx), -1), hist)
+                if with_masks:
+                    masks._ctseg_masks = m_out
         return image, masks, present

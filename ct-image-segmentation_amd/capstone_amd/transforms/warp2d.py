@@ -175,7 +175,8 @@ class WarpPipeline2D:
     with its own ``p``; ``oneof=True`` is ``A.OneOf(warps, p=0.5)``: with probability 0.5 one warp, chosen with equal weight, is
     forced.  A sample takes at most one warp.
 
-    ``pipe(store, indices, params=None, generator=None) -> (images, masks_or_labels, present)`` as ``BatchPipeline2D``.  ``params``:
+    ``pipe(store, indices, params=None, generator=None, with_masks=False) -> (images, masks_or_labels, present)`` as
+    ``BatchPipeline2D`` (``with_masks``: a squashing pipeline also hands over the K masks as ``_ctseg_masks``).  ``params``:
     the explicit draws, a dict of ``crop`` (B, 4) y0, x0, k, flip; ``kind`` (B,) 0 none / 1 elastic / 2 grid; ``seed`` (B,) uint64
     and ``matrix`` (B, 2, 3) forward affine (elastic samples); ``xsteps`` / ``ysteps`` (B, num_steps + 1) (grid samples) — what
     ``draw_params`` returns."""
@@ -268,7 +269,7 @@ class WarpPipeline2D:
                 yy.append(grid_table(Ho, self.grid.num_steps, p["ysteps"][b]))
         return table, (np.concatenate(xx) if xx else None), (np.concatenate(yy) if yy else None)
 
-    def __call__(self, store: SliceStore2D, indices, *, params=None, generator=None):
+    def __call__(self, store: SliceStore2D, indices, *, params=None, generator=None, with_masks=False):
         nat.require_gpu(store.images, "WarpPipeline2D")
         idx = np.asarray(indices.cpu() if isinstance(indices, torch.Tensor) else indices, dtype=np.int64).reshape(-1)
         if len(idx) == 0 or idx.min() < 0 or idx.max() >= len(store):
@@ -286,10 +287,13 @@ class WarpPipeline2D:
         el = self.elastic
         image, m_out, lab, hist, present, _ = pipeline2d_warp_batch(
             store, table, self.size, self.windows, self.shift, self.mean, self.denom, sigma=el.sigma if el else 1.0,
-            alpha=el.alpha if el else 0.0, xx=xx, yy=yy, want_masks=not self.squash, want_labels=self.squash, want_present=True)
+            alpha=el.alpha if el else 0.0, xx=xx, yy=yy, want_masks=not self.squash or with_masks, want_labels=self.squash,
+            want_present=True)
         masks = lab if self.squash else m_out
         if masks is not None:
             masks._ctseg_present = present
             if self.squash:
                 masks._ctseg_labels = (lab.reshape(len(idx), -1), hist)
+                if with_masks:
+                    masks._ctseg_masks = m_out
         return image, masks, present

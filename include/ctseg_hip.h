@@ -482,6 +482,21 @@ int ctseg_pipeline2d_warp_batch(const void* image_store, int32_t image_dtype, in
                                 void* inter, int64_t inter_bytes, float* image_out, uint8_t* masks_out, uint8_t* labels_out,
                                 int64_t* hist, int32_t* present, int32_t launches, void* stream);
 
+/* Distance maps of the 2-D pipeline (capstone/data/utils.py:10-26, compute_distance_map) for P planes of H x W mask bytes
+ * (contiguous, nonzero = foreground) in two launches: the exact Euclidean distance transform, separable and in integers.
+ *   d2_fg / d2_bg  int32 [P][H][W], each optional: the squared distance to the nearest foreground / background pixel of the
+ *                  plane, -1 where the plane has none
+ *   out            fp32 [P][H][W].  mode 0 (REFERENCE): the reference keeps its result in a uint8 array, so its map is
+ *                  k / 255.0 of the byte k = isqrt(d2_fg) & 255 outside a structure and (1 - isqrt(d2_bg)) & 255 inside; here
+ *                  out = table[k], table = 256 fp32 on the device that the caller fills with float32(k / 255.0).  mode 1
+ *                  (SIGNED): sqrt(d2_fg) / 255 outside, -(sqrt(d2_bg) - 1) / 255 inside, each step rounded to fp32.
+ *                  A plane without foreground is all zero, as in the reference; so is a plane without background, for which
+ *                  the reference has no defined value.
+ *   workspace      >= 4 * P * H * W bytes on the device, 4-byte aligned; its contents are not kept between calls
+ * H, W <= 1024.  Every argument is validated on the host before the first launch. */
+int ctseg_distmap2d_batch(const uint8_t* masks, int32_t P, int32_t H, int32_t W, int32_t mode, const float* table,
+                          void* workspace, int64_t workspace_bytes, float* out, int32_t* d2_fg, int32_t* d2_bg, void* stream);
+
 /* Sliding-window inference (BASELINE.json configs[4]).  The reference has no inferer (grep: 0 hits); the
  * semantics are those of MONAI 0.3 `monai.inferers.sliding_window_inference`, the companion of the `monai.networks.nets.UNet`
  * the reference builds at capstone/volumetric/base_trainer.py:65-72.
