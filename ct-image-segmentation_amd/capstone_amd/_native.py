@@ -158,6 +158,8 @@ _SIGS = {
     "ctseg_mixup_images": (C.c_int, [_vp, _vp, _i32, _i64, _f64, _vp, _vp]),
     "ctseg_seg_loss_pair": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp]),
     "ctseg_seg_loss": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "ctseg_boundary_stats": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp]),
+    "ctseg_boundary_grad": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "ctseg_conv_logits_ce_slots": (C.c_int, [C.POINTER(ConvDesc), _i32]),
     "ctseg_conv_logits_ce": (C.c_int, [C.POINTER(ConvDesc), _vp, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
     "ctseg_dice_counts": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp]),

@@ -4,8 +4,9 @@ tensor with grad), computed by the fused HIP loss pass (capstone_amd.segloss) fo
 
 Deliberate fix, flagged: the reference's 3-D wrapper resolves ``"Dice"``, ``"GeneralizedDice"`` and
 ``"Focal"`` in the 2-D registry whose ``assert input.ndim == 4`` raises on volumes (SURVEY.md §3.1
-bug 1).  Here the same formulas run on 4-D and 5-D input alike.  ``"Boundary"`` (2-D only, needs
-distance maps from the CPU data pipeline, models/losses.py:124-157) is outside the hot path and raises.
+bug 1).  Here the same formulas run on 4-D and 5-D input alike.  ``"Boundary"`` (2-D only, models/losses.py:127-157)
+raises unless the wrapper is built with ``device_boundary=True``: it then takes the batch's distance maps
+(``MiccaiDataModule2D(enhanced=True, device_maps=True)``) through HIP passes of its own (csrc/boundary_loss.hip).
 """
 import torch
 import torch.nn as nn
@@ -46,35 +47,52 @@ def _as_cl(logits):
     return buf.data_ptr(), ldn, buf
 
 
+def _write_grad(ctx, eng, plan, names, grad):
+    """One gradient row per voxel for the requested losses: ``grad(ptr, ld, dl_ptr, g_ld, gdt)`` (the label losses' pass) and then
+    the Boundary pass adding to it, or the Boundary pass alone storing when it is the only name.  The row goes to the UNet
+    plan in its own storage dtype (no fp32 round trip), or to an fp32 buffer returned as the autograd gradient."""
+    ptr, ld, _ = ctx.cl
+    boundary, others = "Boundary" in names, any(n != "Boundary" for n in names)
+    if boundary:
+        eng.maps = ctx.maps             # another forward may have set other maps on the same engine since
+    if plan is not None:
+        dl_ptr, g_ld, gdt = plan.dlogits.ptr(), plan.dlogits.ld, plan.dt
+    else:
+        B, C = ctx.shape[:2]
+        g_ld, gdt = (C + 3) // 4 * 4, nat.F32
+        buf = torch.zeros((B, eng.S, g_ld), dtype=torch.float32, device=eng.device)
+        dl_ptr = buf.data_ptr()
+    if others:
+        grad(ptr, ld, dl_ptr, g_ld, gdt)
+    if boundary:
+        eng.boundary_grad(ptr, ld, dl_ptr, g_ld, gdt, accumulate=others)
+    if plan is not None:
+        plan.dlogits_is_current = True
+        return torch.zeros((), dtype=torch.float32, device=eng.device).expand(ctx.shape)
+    return buf[..., :C].permute(0, 2, 1).reshape(ctx.shape)
+
+
 class _SegLossFn(torch.autograd.Function):
-    """values of the requested losses; backward writes d(sum_i g_i * loss_i)/d(logits)."""
+    """values of the requested losses; backward writes d(sum_i g_i * loss_i)/d(logits).  ``"Boundary"`` among the names reads
+    the maps the caller set on the engine (``set_dist_maps``)."""
 
     @staticmethod
     def forward(ctx, logits, eng, plan, names, exclude_missing, indicator):
         ptr, ld, keep = _as_cl(logits)
-        eng.stats(ptr, ld, weighted_too="WeightedCrossEntropy" in names)
+        if any(n != "Boundary" for n in names):
+            eng.stats(ptr, ld, weighted_too="WeightedCrossEntropy" in names)
+        if "Boundary" in names:
+            eng.boundary_stats(ptr, ld)
         vals = eng.loss_values(names, exclude_missing, indicator)
         ctx.eng, ctx.plan, ctx.names, ctx.cl = eng, plan, names, (ptr, ld, keep)
-        ctx.shape = logits.shape
+        ctx.shape, ctx.maps = logits.shape, eng.maps
         return tuple(vals[n] for n in names)
 
     @staticmethod
     def backward(ctx, *gs):
         eng, plan = ctx.eng, ctx.plan
-        ptr, ld, _ = ctx.cl
         eng.build_coef({n: (g if g is not None else 0.0) for n, g in zip(ctx.names, gs)})
-        if plan is not None:   # hand the gradient to the UNet plan in its own storage dtype, no fp32 round trip
-            dl = plan.dlogits
-            eng.grad(ptr, ld, dl.ptr(), dl.ld, plan.dt)
-            plan.dlogits_is_current = True
-            g = torch.zeros((), dtype=torch.float32, device=eng.device).expand(ctx.shape)
-        else:
-            B, C = ctx.shape[:2]
-            ldn = (C + 3) // 4 * 4
-            buf = torch.zeros((B, eng.S, ldn), dtype=torch.float32, device=eng.device)
-            eng.grad(ptr, ld, buf.data_ptr(), ldn, nat.F32)
-            g = buf[..., :C].permute(0, 2, 1).reshape(ctx.shape)
-        return g, None, None, None, None, None
+        return _write_grad(ctx, eng, plan, ctx.names, eng.grad), None, None, None, None, None
 
 
 class _SegLossPairFn(torch.autograd.Function):
@@ -85,36 +103,26 @@ class _SegLossPairFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, eng, plan, names, exclude_missing, indicators, lambda_):
         ptr, ld, keep = _as_cl(logits)
-        eng.stats_pair(ptr, ld, weighted_too="WeightedCrossEntropy" in names)
+        eng.stats_pair(ptr, ld, weighted_too="WeightedCrossEntropy" in names)      # (always: the step's Dice counts come from it)
+        if "Boundary" in names:
+            eng.boundary_stats(ptr, ld)
         vals, ctx.w = [], []
         for s in (0, 1):
             with eng.side(s):
                 vals.append(eng.loss_values(names, exclude_missing, indicators[s]))
                 ctx.w.append(eng._w)
         ctx.eng, ctx.plan, ctx.names, ctx.cl, ctx.lambda_ = eng, plan, names, (ptr, ld, keep), lambda_
-        ctx.shape = logits.shape
+        ctx.shape, ctx.maps = logits.shape, eng.maps
         return tuple(lambda_ * vals[0][n] + (1 - lambda_) * vals[1][n] for n in names)
 
     @staticmethod
     def backward(ctx, *gs):
         eng, plan = ctx.eng, ctx.plan
-        ptr, ld, _ = ctx.cl
         for s, lam in ((0, ctx.lambda_), (1, 1 - ctx.lambda_)):     # lambda enters through the upstream gradients only
             with eng.side(s):
                 eng._w = ctx.w[s]
                 eng.build_coef({n: (g * lam if g is not None else 0.0) for n, g in zip(ctx.names, gs)})
-        if plan is not None:
-            dl = plan.dlogits
-            eng.grad_pair(ptr, ld, dl.ptr(), dl.ld, plan.dt)
-            plan.dlogits_is_current = True
-            g = torch.zeros((), dtype=torch.float32, device=eng.device).expand(ctx.shape)
-        else:
-            B, C = ctx.shape[:2]
-            ldn = (C + 3) // 4 * 4
-            buf = torch.zeros((B, eng.S, ldn), dtype=torch.float32, device=eng.device)
-            eng.grad_pair(ptr, ld, buf.data_ptr(), ldn, nat.F32)
-            g = buf[..., :C].permute(0, 2, 1).reshape(ctx.shape)
-        return g, None, None, None, None, None, None
+        return _write_grad(ctx, eng, plan, ctx.names, eng.grad_pair), None, None, None, None, None, None
 
 
 class _SegLossTableFn(torch.autograd.Function):
@@ -123,14 +131,21 @@ class _SegLossTableFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, eng, plan, name):
         ptr, ld, keep = _as_cl(logits)
-        eng.stats(ptr, ld)
         ctx.eng, ctx.plan, ctx.name, ctx.cl, ctx.shape = eng, plan, name, (ptr, ld, keep), logits.shape
+        if name == "Boundary":
+            ctx.maps = eng.maps
+            eng.boundary_stats(ptr, ld)
+        else:
+            eng.stats(ptr, ld)
         return eng.loss_table(name)
 
     @staticmethod
     def backward(ctx, g):
         eng = ctx.eng
         ptr, ld, _ = ctx.cl
+        if ctx.name == "Boundary":      # linear in the table: its gradient needs the maps and the table's gradient only
+            eng.build_coef({ctx.name: g})
+            return _write_grad(ctx, eng, None, (ctx.name,), None), None, None, None
         eng.stats(ptr, ld)              # another entry's forward may have run on the same engine since
         eng.build_coef({ctx.name: g})
         B, C = ctx.shape[:2]
@@ -156,11 +171,16 @@ class LossEntry(nn.Module):
     def forward(self, input, target):
         nat.require_gpu(input, f"{self.name} loss")
         eng, plan = _engine_for(input)
-        stash = getattr(target, "_ctseg_labels", None)
-        if stash is not None:
-            eng.set_labels(*stash)
+        if self.name == "Boundary":      # the reference calls this entry as fx(input, dist_maps) (models/losses.py:188-192)
+            assert input.ndim == 4, "Expected input of shape: (N, C, H, W)"
+            assert target.ndim == 4, "Expected distance maps of shape: (N, C, H, W)"
+            eng.set_dist_maps(target)
         else:
-            eng.set_labels_from_i64(target)
+            stash = getattr(target, "_ctseg_labels", None)
+            if stash is not None:
+                eng.set_labels(*stash)
+            else:
+                eng.set_labels_from_i64(target)
         if self.reduction == "none" and self.name not in ("CrossEntropy", "WeightedCrossEntropy"):
             return _SegLossTableFn.apply(input, eng, None, self.name)
         return _SegLossFn.apply(input, eng, None, (self.name,), False, None)[0]
@@ -170,11 +190,16 @@ class LossEntry(nn.Module):
 
 
 class MultipleLossWrapper(nn.Module):
-    def __init__(self, losses, exclude_missing=False):
+    def __init__(self, losses, exclude_missing=False, device_boundary=False):
+        """``device_boundary``: opt in to the Boundary loss on the device; ``forward`` then needs ``dist_maps`` (B, C-1, H, W) when
+        ``"Boundary"`` is among the losses.  Off (the default), a ``"Boundary"`` entry raises."""
         super().__init__()
         self.exclude_missing = exclude_missing
+        self.device_boundary = device_boundary
         for name in losses:
             if name == "Boundary":
+                if device_boundary:
+                    continue
                 raise NotImplementedError("Boundary loss needs CPU distance maps (2-D pipeline); outside the MI355X hot path")
             assert name in LOSSES.keys()
         self.names = list(losses)
@@ -184,7 +209,13 @@ class MultipleLossWrapper(nn.Module):
         reduction = "none" if exclude_missing else "mean"
         self.losses = nn.ModuleDict({name: LossEntry(name, reduction) for name in losses})
 
+    def _take_maps(self, eng, dist_maps):
+        """the maps go to the engine when "Boundary" is requested (asserted as the reference does, :189-191); ignored otherwise"""
+        if "Boundary" in self.names:
+            eng.set_dist_maps(dist_maps)
+
     def forward(self, input, target, mask_indicator=None, dist_maps=None):
+        assert "Boundary" not in self.names or dist_maps is not None, "Distance maps are required for using boundary loss"
         nat.require_gpu(input, "MultipleLossWrapper")
         eng, plan = _engine_for(input)
         stash = getattr(target, "_ctseg_labels", None)
@@ -192,17 +223,20 @@ class MultipleLossWrapper(nn.Module):
             eng.set_labels(*stash)
         else:
             eng.set_labels_from_i64(target)
+        self._take_maps(eng, dist_maps)
         if mask_indicator is not None:
             mask_indicator = mask_indicator.type_as(input)
         vals = _SegLossFn.apply(input, eng, plan, tuple(self.names), self.exclude_missing, mask_indicator)
         return dict(zip(self.names, vals))
 
-    def forward_mixed(self, input, target, index, lambda_, mask_indicator=None):
+    def forward_mixed(self, input, target, index, lambda_, mask_indicator=None, dist_maps=None):
         """The mixup step's two calls in one (capstone/training/mixup_trainer.py:63-81): dict name ->
         ``lambda_ * loss(input, target) + (1 - lambda_) * loss(input, target[index])``, side B under ``mask_indicator[index]``.
         ``index``: (B,) integer device tensor, ``lambda_``: host float.  Two plain ``forward`` calls on one prediction are NOT
         equivalent here (they share one engine and one gradient buffer): this is the supported route.
-        ``last_mixed_counts`` = the (B, 2, 3, C) Dice counts of both sides, valid until the next call."""
+        ``last_mixed_counts`` = the (B, 2, 3, C) Dice counts of both sides, valid until the next call.  ``dist_maps``: side B of
+        the Boundary loss reads ``dist_maps[index]`` in place (:74); no gathered copy is made."""
+        assert "Boundary" not in self.names or dist_maps is not None, "Distance maps are required for using boundary loss"
         nat.require_gpu(input, "MultipleLossWrapper.forward_mixed")
         eng, plan = _engine_for(input, segloss.SegLossPairEngine, "_ctseg_loss_pair")
         stash = getattr(target, "_ctseg_labels", None)
@@ -210,6 +244,7 @@ class MultipleLossWrapper(nn.Module):
             eng.set_labels_from_i64(target)
             stash = (eng.labels, eng.hist)
         eng.set_pair(stash[0], stash[1], index)
+        self._take_maps(eng, dist_maps)
         indicators = (None, None)
         if mask_indicator is not None:
             mask_indicator = mask_indicator.type_as(input)

@@ -1,10 +1,11 @@
-"""Loss / metric engine: host side of ctseg_squash_masks / ctseg_seg_loss / ctseg_dice_counts.
+"""Loss / metric engine: host side of ctseg_squash_masks / ctseg_seg_loss / ctseg_dice_counts / ctseg_boundary_*.
 
 One pass over the fp32 channels-last logits produces every sum the reference's losses and its Dice
 metric need (capstone/models/losses.py, capstone/models/temp.py, capstone/models/metrics.py); the
 per-(sample, class) closed forms are then a handful of ops on (B, 10) device tensors, and one more
 pass writes d(loss)/d(logits).  CE-only (the reference's 3-D default, base_trainer.py:28) is a single
-fused pass.
+fused pass.  The Boundary loss (models/losses.py:127-157) has a statistics and a gradient pass of its own over the same logits
+and the batch's distance maps; its gradient pass can add to the row the other losses' pass wrote.
 """
 import contextlib
 import math
@@ -85,6 +86,40 @@ class SegLossEngine:
         self.own_dlogits = {}
         self._ce_ready = None        # the `weighted` that prepare_fused_ce last set the tables up for, until a pass uses them
         self._part_head = None       # head_ce's partial records (B, slots, R)
+        self.maps = None             # Boundary loss: fp32 distance maps (B, C-1, S) and, once they are set, its tables
+        self._b_side = 0             # the side whose Boundary tables the closed forms below read and fill
+
+    # ---- Boundary loss: maps, statistics, gradient (ctseg_boundary_stats / ctseg_boundary_grad) ----
+    NS = 1                           # sides per sample; SegLossPairEngine has 2
+
+    def _boundary_perm(self):
+        return None
+
+    def set_dist_maps(self, maps):
+        """(B, C-1, *spatial) floating-point device tensor (no background plane); another float dtype is converted on the device"""
+        nat.require_gpu(maps, "Boundary loss distance maps")
+        if not maps.is_floating_point():
+            raise TypeError(f"Boundary loss: distance maps must be floating point, got {maps.dtype}")
+        if maps.ndim < 3 or tuple(maps.shape[:2]) != (self.B, self.C - 1) or maps[0, 0].numel() != self.S:
+            raise ValueError(f"Boundary loss: distance maps of shape {tuple(maps.shape)}, expected ({self.B}, {self.C - 1}, ...) with "
+                             f"{self.S} voxels per plane")
+        self.maps = maps.detach().to(torch.float32).reshape(self.B, self.C - 1, self.S).contiguous()
+        if getattr(self, "b_red", None) is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            self.b_part = torch.zeros((self.B, self.P, self.NS, self.C - 1), **f64)
+            self.b_red = torch.zeros((self.B, self.NS, self.C - 1), **f64)
+            self.bw = torch.zeros((self.B, self.NS, self.C - 1), dtype=torch.float32, device=self.device)
+
+    def boundary_stats(self, logits_ptr, ld):
+        """b_red (B, NS, C-1) = sum over voxels of softmax(x)[c+1] * D_s[c]"""
+        nat.call("ctseg_boundary_stats", logits_ptr, ld, self.maps.data_ptr(), nat.ptr(self._boundary_perm()), self.B, self.S, self.C,
+                 self.b_part.data_ptr(), self.P)
+        nat.call("ctseg_reduce_partials_f64", self.b_part.data_ptr(), self.B, self.P, self.NS * (self.C - 1), self.b_red.data_ptr())
+
+    def boundary_grad(self, logits_ptr, ld, dl_ptr, g_ld, gdt, accumulate):
+        """d(sum of bw-weighted table entries)/d(logits) from bw, which build_coef filled: stored, or added to the rows ``grad`` wrote"""
+        nat.call("ctseg_boundary_grad", logits_ptr, ld, self.maps.data_ptr(), nat.ptr(self._boundary_perm()), self.B, self.S, self.C,
+                 self.bw.data_ptr(), self.P, dl_ptr, g_ld, gdt, int(bool(accumulate)))
 
     # ---- targets ----
     def set_labels(self, labels_u8, hist):
@@ -164,6 +199,10 @@ class SegLossEngine:
         return pred
 
     # ---- closed forms on (B, C) tables ----
+    def _tables_for(self, names):
+        """``_tables()`` when a loss other than Boundary asks for them (Boundary alone needs no labels)"""
+        return self._tables() if any(n != "Boundary" for n in names) else (None,) * 4
+
     def _tables(self):
         C = self.C
         r = self.red
@@ -172,7 +211,7 @@ class SegLossEngine:
     def loss_values(self, names, exclude_missing=False, indicator=None):
         """dict name -> 0-dim fp32 tensor, plus per-loss (B,C) weights used for the gradient tables."""
         B, C, S = self.B, self.C, self.S
-        P, I, FO, Y = self._tables()
+        P, I, FO, Y = self._tables_for(names)
         out, self._w = {}, {}
         for name in names:
             if name == "CrossEntropy":
@@ -194,6 +233,11 @@ class SegLossEngine:
                 wt = self._mask_weights(name, indicator, exclude_missing, C)
                 out[name] = (f * wt).sum()
                 self._w[name] = wt
+            elif name == "Boundary":
+                f = self.loss_table(name)
+                wt = self._mask_weights(name, indicator, exclude_missing, C - 1)       # the weights Dice gets
+                out[name] = (f * wt).sum()
+                self._w[name] = wt
             else:
                 raise KeyError(name)
         return out
@@ -201,7 +245,9 @@ class SegLossEngine:
     def loss_table(self, name):
         """the unreduced per-(sample, class) table of one loss after ``stats()`` — what the reference's wrapper returns with
         ``reduction="none"`` (capstone/models/losses.py:177-180 builds every entry that way under ``exclude_missing``):
-        Dice / GeneralizedDice (B, C-1) (background excluded), Focal (B, C)"""
+        Dice / GeneralizedDice (B, C-1) (background excluded), Focal (B, C); Boundary (B, C-1) after ``boundary_stats()``"""
+        if name == "Boundary":
+            return (self.b_red[:, self._b_side] / self.S).float()           # models/losses.py:146: the mean over (H, W)
         P, I, FO, Y = self._tables()
         if name == "Dice":
             return (1.0 - (2.0 * I + SMOOTH) / (P + Y + SMOOTH))[:, 1:].float()
@@ -248,7 +294,7 @@ class SegLossEngine:
     def build_coef(self, scales):
         """scales: dict name -> upstream gradient (0-dim tensor or float). Fills coef (B,1+3C) and cw_eff (C)."""
         B, C, S = self.B, self.C, self.S
-        P, I, FO, Y = self._tables()
+        P, I, FO, Y = self._tables_for(scales)
         dev = self.device
         a = torch.zeros((B, C), dtype=torch.float64, device=dev)
         b = torch.zeros((B, C), dtype=torch.float64, device=dev)
@@ -273,6 +319,9 @@ class SegLossEngine:
                 b = b + wt * w * (2.0 * I * w + SMOOTH) / (D * D)
             elif name == "Focal":
                 fcoef = fcoef + self._table_weight(name, g) / float(S)
+            elif name == "Boundary":        # bw (B, NS, C-1): weight of the table entry, times the upstream gradient, times 1 / S
+                wt = g if g.ndim == 2 else self._w[name].double() * g
+                self.bw[:, self._b_side] = (wt / float(S)).float()
         self.cw_eff.copy_(cw.float())
         self.coef[:, 0] = 1.0
         self.coef[:, 1:1 + C] = a.float()
@@ -314,6 +363,11 @@ class SegLossPairEngine(SegLossEngine):
         self.cw2_stats = self.cw[None, :].repeat(2, 1)
         self.perm = self.hist2 = None
 
+    NS = 2                           # Boundary loss: side 1 of sample b reads the maps of sample perm[b]
+
+    def _boundary_perm(self):
+        return self.perm
+
     def set_pair(self, labels_u8, hist, index):
         """index: (B,) integer device tensor; it never visits the host"""
         self.labels = labels_u8
@@ -323,13 +377,13 @@ class SegLossPairEngine(SegLossEngine):
     @contextlib.contextmanager
     def side(self, s):
         """the base class's tables (red, red_w, hist, cnt, coef, cw_eff) stand for side ``s`` inside the block"""
-        keep = (self.red, self.red_w, self.hist, self.cnt, self.coef, self.cw_eff)
+        keep = (self.red, self.red_w, self.hist, self.cnt, self.coef, self.cw_eff, self._b_side)
         self.red, self.red_w, self.hist = self.red2[:, s], self.red2_w[:, s], self.hist2[s]
-        self.cnt, self.coef, self.cw_eff = self.cnt2[:, s], self.coef2[:, s], self.cw2[s]
+        self.cnt, self.coef, self.cw_eff, self._b_side = self.cnt2[:, s], self.coef2[:, s], self.cw2[s], s
         try:
             yield self
         finally:
-            self.red, self.red_w, self.hist, self.cnt, self.coef, self.cw_eff = keep
+            self.red, self.red_w, self.hist, self.cnt, self.coef, self.cw_eff, self._b_side = keep
 
     def _pass_pair(self, logits_ptr, ld, cw, do_grad, dl_ptr=None, g_ld=0, gdt=F32):
         nat.call("ctseg_seg_loss_pair", logits_ptr, ld, self.labels.data_ptr(), self.perm.data_ptr(), self.B, self.S, self.C,

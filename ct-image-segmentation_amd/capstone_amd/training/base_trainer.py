@@ -7,8 +7,10 @@ engine with Z = 1 (9-tap convolutions, 4-class transposed convs); no 2-D-specifi
 
 ``--downsample`` (reference :53,81-85: a trainable 3->1 ``conv1x1`` in front of the U-Net) is carried: the channel mix is three
 elementwise multiply-adds on the input image and the engine records an input-gradient pass for the stem when its input requires grad.
-Not carried over (outside the hot path): the Boundary loss (CPU distance maps) and the W&B logger patch.  They
-raise instead of silently doing something else.  Mixup is ``training/mixup_trainer.py``.
+The Boundary loss is opt-in: ``device_boundary=True`` takes the batch's fourth element (the distance maps of
+``MiccaiDataModule2D(enhanced=True, device_maps=True)``) to the loss as reference :98-108 does; without the flag a 4-tuple batch
+and a ``"Boundary"`` entry raise.  Not carried over (outside the hot path): the W&B logger patch, which raises
+instead of silently doing something else.  Mixup is ``training/mixup_trainer.py``.
 """
 from argparse import ArgumentParser
 from typing import List
@@ -23,7 +25,8 @@ from .utils import _squash_masks, _squash_predictions
 
 class BaseUNet2D(_DataParallelSurface, _Base):
     def __init__(self, filters: List = [64, 128, 256, 512, 1024], use_res_units: bool = False, downsample: bool = False,
-                 lr: float = 1e-3, loss_fx: list = ["Focal", "Dice"], exclude_missing: bool = False, **kwargs) -> None:
+                 lr: float = 1e-3, loss_fx: list = ["Focal", "Dice"], exclude_missing: bool = False, device_boundary: bool = False,
+                 **kwargs) -> None:
         super().__init__()
         assert isinstance(filters, list)
         assert len(filters) == 5, "This module requires a standard 5 block UNet specification"
@@ -39,7 +42,8 @@ class BaseUNet2D(_DataParallelSurface, _Base):
         # checkpoint: kept as a parameter container for state_dict interchange
         self.conv1x1 = torch.nn.Conv2d(in_channels=3, out_channels=1, kernel_size=1, stride=1)
         self.unet = self._construct_model()
-        self.loss_func = MultipleLossWrapper(losses=loss_fx, exclude_missing=exclude_missing)
+        self.device_boundary = device_boundary      # (a switch of this port, not a reference hyperparameter: kept out of hparams)
+        self.loss_func = MultipleLossWrapper(losses=loss_fx, exclude_missing=exclude_missing, device_boundary=device_boundary)
         self.dice_score = DiceMetricWrapper()
 
     @property
@@ -70,19 +74,24 @@ class BaseUNet2D(_DataParallelSurface, _Base):
         self._shared_step(batch, prefix="test")
 
     def _shared_step(self, batch, prefix: str):
-        images, masks, mask_indicator, *dist_maps = batch
-        if dist_maps:
-            raise NotImplementedError("distance maps (Boundary loss) are outside the MI355X hot path")
+        images, masks, mask_indicator, dist_maps = self._split_batch(batch)
         masks = _squash_masks(masks, self._n_classes, self.device)
         mask_indicator = mask_indicator.type_as(images)
         prediction = self.forward(images)
         prediction._ctseg_plan = self.unet.engine().last_plan if prediction.requires_grad else None
-        loss_dict = self.loss_func(input=prediction, target=masks, mask_indicator=mask_indicator)
+        loss_dict = self.loss_func(input=prediction, target=masks, mask_indicator=mask_indicator, dist_maps=dist_maps)
         total_loss = torch.stack(list(loss_dict.values())).sum()
         for name, loss_value in loss_dict.items():
             self.log(f"{name} Loss ({prefix})", loss_value, on_step=False, on_epoch=True)
         self._log_dice_scores(prediction, masks, mask_indicator, prefix)
         return images, masks, mask_indicator, prediction, total_loss
+
+    def _split_batch(self, batch):
+        """(images, masks, mask_indicator, dist_maps or None), reference :98-101; a fourth element needs ``device_boundary``"""
+        images, masks, mask_indicator, *dist_maps = batch
+        if dist_maps and not self.device_boundary:
+            raise NotImplementedError("distance maps (Boundary loss) are outside the MI355X hot path unless device_boundary=True")
+        return images, masks, mask_indicator, (dist_maps[0] if dist_maps else None)
 
     def _log_dice_scores(self, prediction, masks, mask_indicator, prefix):
         with torch.no_grad():

@@ -4,7 +4,8 @@ A ``BaseUNet2D`` with one residual subunit per level (reference :26-42) whose tr
 drawn by ``weighted_mixup`` and takes the loss against both targets (:52-92).  The reference calls ``loss_func`` twice on one
 prediction; here both terms come from ``MultipleLossWrapper.forward_mixed``: one statistics pass and one gradient pass over the
 logits for the two targets, and the Dice counts of both sides from the same statistics pass.  Validation and test steps are
-the base class's.  Distance maps (Boundary loss) raise as in the base class.
+the base class's.  Distance maps (Boundary loss) need ``device_boundary=True`` as in the base class; side B then reads
+``dist_maps[shuffle_index]`` (:74) in place.
 """
 import torch
 
@@ -30,16 +31,14 @@ class MixupUNet2D(BaseUNet2D):
 
     def _shared_step(self, batch, prefix: str):
         assert prefix == "train", "Mixup can be used only while training"
-        images, masks, mask_indicator, *dist_maps = batch
-        if dist_maps:
-            raise NotImplementedError("distance maps (Boundary loss) are outside the MI355X hot path")
+        images, masks, mask_indicator, dist_maps = self._split_batch(batch)
         mixed_images, shuffle_index, lambda_ = weighted_mixup(images, masks, alpha=0.2, device=self.device)
         masks = _squash_masks(masks, self._n_classes, self.device)      # weighted_mixup left the label maps on ``masks``
         mask_indicator = mask_indicator.type_as(images)
         prediction = self.forward(mixed_images)
         prediction._ctseg_plan = self.unet.engine().last_plan if prediction.requires_grad else None
         loss_dict = self.loss_func.forward_mixed(input=prediction, target=masks, index=shuffle_index, lambda_=lambda_,
-                                                 mask_indicator=mask_indicator)
+                                                 mask_indicator=mask_indicator, dist_maps=dist_maps)
         total_loss = torch.stack(list(loss_dict.values())).sum()
         for name, loss_value in loss_dict.items():
             self.log(f"{name} Loss ({prefix})", loss_value, on_step=False, on_epoch=True)

@@ -3,7 +3,8 @@
 // the gradient row store, the counts' wave sum and the record / count flush exist here once, plus the host-side argument checks and
 // the CP dispatch of both entry points.  Two pieces stay spelled out in both kernels, softmax -> argmax and one side's soft
 // gradient: as inlined helpers they changed the kernels' register counts (see the comments there).  (The fused cross-entropy
-// epilogue of conv_halo_x.hip is a different formulation on purpose and shares nothing with this.)
+// epilogue of conv_halo_x.hip is a different formulation on purpose and shares nothing with this.)  The Boundary loss passes
+// (boundary_loss.hip) are a third user: the logits row load, the gradient row store and its counterpart load_grad_row, the CP dispatch.
 #pragma once
 #include <type_traits>
 
@@ -74,6 +75,33 @@ template <typename GT, int CP> __device__ __forceinline__ void store_grad_row(ch
 #pragma unroll
     for (int q = 0; q < CMAX / GEPC; ++q)
       if (q * GEPC < g_ld) store_chunk<GT>(gp + q * 16, d + q * GEPC);
+  }
+}
+
+// store_grad_row's counterpart: one gradient row of g_ld elements at gp -> o[CMAX], zeros beyond the row (a pass that adds to a
+// row another pass wrote, boundary_loss.hip)
+template <typename GT, int CP> __device__ __forceinline__ void load_grad_row(const char* gp, int g_ld, float* o) {
+  constexpr int GSZ = TT<GT>::SZ, GEPC = TT<GT>::EPC;
+  if (GSZ == 2 && (g_ld & 7) != 0) {
+    if constexpr (GSZ == 2) {
+#pragma unroll
+      for (int u = 0; u < CMAX / 4; ++u) {
+        float t[4] = {0.f, 0.f, 0.f, 0.f};
+        if (u < CP / 4 && u * 4 < g_ld) load_ep<GT, 4>(gp + u * 8, t);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[u * 4 + i] = t[i];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < CMAX / GEPC; ++q) {
+      float t[GEPC];
+#pragma unroll
+      for (int i = 0; i < GEPC; ++i) t[i] = 0.f;
+      if (q * GEPC < g_ld) load_chunk<GT>(gp + q * 16, t);
+#pragma unroll
+      for (int i = 0; i < GEPC; ++i) o[q * GEPC + i] = t[i];
+    }
   }
 }
 

@@ -369,6 +369,19 @@ int ctseg_seg_loss(const float* logits, int32_t ld, const uint8_t* labels, int32
 int ctseg_seg_loss_pair(const float* logits, int32_t ld, const uint8_t* labels, const int32_t* perm, int32_t B, int64_t S,
                         int32_t C, const float* class_weight, int32_t do_grad, double* part, int32_t P, int64_t* cnt,
                         const float* coef, void* dlogits, int32_t g_ld, int32_t gdtype, void* stream);
+/* Boundary loss (capstone/models/losses.py:127-157): passes of their own over the same fp32 channels-last logits (the row rules of
+ * ctseg_seg_loss) and the fp32 distance maps [B][C-1][S] (planar, contiguous, no background plane; any S).  perm: NULL, or int32 [B]
+ * on the device (clamped to [0, B)): NS = 2 sides, side 1 of sample b reads the maps of sample perm[b] (the mixup step).
+ * ctseg_boundary_stats: part[B][P][NS][C-1] doubles = per-workgroup sums over voxels of softmax(x)[c+1] * D_s[c]; the voxel ranges
+ *   are ctseg_seg_loss's for the same P; ctseg_reduce_partials_f64 with R = NS*(C-1) finishes.  No atomics: deterministic.
+ * ctseg_boundary_grad: bw[B][NS][C-1] fp32 = weight of (sample, side, class) in the differentiated scalar (1/S and the upstream
+ *   gradient folded in by the caller); g_c = sum_s bw[b][s][c-1] * D_s[c-1], g_0 = 0, d_k = p_k (g_k - sum_j g_j p_j).
+ *   accumulate = 0: dlogits rows = d, zeros in the pad columns.  accumulate = 1: rows += d (one fp32 add, one store), pad columns
+ *   unchanged.  dlogits / g_ld / gdtype as in ctseg_seg_loss. */
+int ctseg_boundary_stats(const float* logits, int32_t ld, const float* maps, const int32_t* perm, int32_t B, int64_t S, int32_t C,
+                         double* part, int32_t P, void* stream);
+int ctseg_boundary_grad(const float* logits, int32_t ld, const float* maps, const int32_t* perm, int32_t B, int64_t S, int32_t C,
+                        const float* bw, int32_t P, void* dlogits, int32_t g_ld, int32_t gdtype, int32_t accumulate, void* stream);
 /* The logits convolution of the U-Net's head with the cross-entropy of the training step fused into its epilogue: the fp32 logits
  * (1.2 GB per step at 2 x 512 x 512 x 48) are never written or re-read.  Replaces, for the native training step, the pair
  *   ctseg_conv_igemm(d) [monai UNet model.2.1.conv.unit0 + identity residual]  +  ctseg_seg_loss(do_stats = do_grad = 2)

@@ -1,0 +1,321 @@
+"""CPU: the host side of the Boundary loss (capstone/models/losses.py:127-157 on the device).  The argument checks of
+ctseg_boundary_stats / ctseg_boundary_grad run in the library itself (they return before any launch); the opt-in switch, the
+weights, the ``bw`` table and the dict assembly of capstone_amd.segloss / models.losses / the two trainers run with the C ABI
+routed through the emulator, whose two new entries are emulated here in numpy (a subclass: tests/abi_emulator.py is not edited).
+
+The comparison target is the reference's formula restated in float64 torch:
+    T[b, c] = mean_v softmax(x)[b, c + 1, v] * D[b, c, v];  "mean": T.mean();  exclude_missing: apply_missing_mask's non-Focal branch
+and autograd of it."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from abi_emulator import cl_view, mem, patch_native
+from test_mixup_host import MixupEmulator
+from capstone_amd import _native as nat
+from capstone_amd import plan as plan_mod
+from oracle import losses as OL
+
+F32, BF16 = 0, 1
+
+
+# ---- the float64 restatement ------------------------------------------------------------------------------------------------
+def ref_table(x, D):
+    """(B, C, H, W) logits, (B, C-1, H, W) maps -> (B, C-1)"""
+    return (torch.softmax(x, dim=1)[:, 1:] * D).mean(dim=(2, 3))
+
+
+def ref_missing(T, ind):
+    w = 1.0 / ind.sum(dim=0)
+    if torch.any(torch.isinf(w)):
+        w = torch.ones_like(w)
+    w = w / w.sum()
+    return (T * w[None, :] * ind).sum(dim=1).mean()
+
+
+def ref_scalar(x, D, exclude_missing=False, ind=None):
+    T = ref_table(x, D)
+    return ref_missing(T, ind.to(T.dtype)) if exclude_missing else T.mean()
+
+
+# ---- numpy emulation of the two entry points --------------------------------------------------------------------------------
+class BoundaryEmulator(MixupEmulator):
+    @staticmethod
+    def _inputs(logits, ld, maps, perm, B, S, C):
+        x = cl_view(logits, B, S, 1, 1, C, ld).reshape(B, S, C).astype(np.float64)
+        e = np.exp(x - x.max(-1, keepdims=True))
+        p = e / e.sum(-1, keepdims=True)
+        D = mem(maps, B * (C - 1) * S).reshape(B, C - 1, S).astype(np.float64)
+        sides = [D] if not perm else [D, D[np.clip(mem(perm, B, np.int32), 0, B - 1)]]
+        return p, sides
+
+    def boundary_stats(self, logits, ld, maps, perm, B, S, C, part, P):
+        p, sides = self._inputs(logits, ld, maps, perm, B, S, C)
+        ns = len(sides)
+        pr = mem(part, B * P * ns * (C - 1), np.float64).reshape(B, P, ns, C - 1)
+        pr[:] = 0
+        for s, D in enumerate(sides):
+            pr[:, 0, s] = (np.transpose(p[..., 1:], (0, 2, 1)) * D).sum(-1)
+
+    def boundary_grad(self, logits, ld, maps, perm, B, S, C, bw, P, dlogits, g_ld, gdtype, accumulate):
+        assert gdtype == F32
+        p, sides = self._inputs(logits, ld, maps, perm, B, S, C)
+        ns = len(sides)
+        w = mem(bw, B * ns * (C - 1)).reshape(B, ns, C - 1).astype(np.float64)
+        g = np.zeros((B, S, C))
+        for s, D in enumerate(sides):
+            g[..., 1:] += np.transpose(w[:, s, :, None] * D, (0, 2, 1))
+        d = p * (g - (g * p).sum(-1, keepdims=True))
+        o = cl_view(dlogits, B, S, 1, 1, g_ld, g_ld).reshape(B, S, g_ld)
+        if accumulate:
+            o[..., :C] += d.astype(np.float32)
+        else:
+            o[..., :C] = d
+            o[..., C:] = 0
+
+
+@pytest.fixture()
+def emu():
+    e = BoundaryEmulator()
+    undo = patch_native(nat, e)
+    orig = plan_mod.Plan.__dict__["run"]
+    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
+    yield e
+    plan_mod.Plan.run = orig
+    undo()
+
+
+# ---- argument validation: the library itself, no launch -----------------------------------------------------------------------
+A = 1 << 20            # a 16-byte aligned address nothing is read from: every call below is refused before a launch
+
+
+def _stats(logits=A, ld=12, maps=A, perm=None, B=2, S=100, C=10, part=A, P=1):
+    return nat.lib().ctseg_boundary_stats(logits, ld, maps, perm, B, S, C, part, P, None)
+
+
+def _grad(logits=A, ld=12, maps=A, perm=None, B=2, S=100, C=10, bw=A, P=1, dlogits=A, g_ld=12, gdtype=F32, accumulate=0):
+    return nat.lib().ctseg_boundary_grad(logits, ld, maps, perm, B, S, C, bw, P, dlogits, g_ld, gdtype, accumulate, None)
+
+
+BAD_COMMON = [dict(maps=None), dict(logits=None), dict(C=17), dict(C=1), dict(ld=10), dict(ld=8), dict(ld=20, C=16), dict(logits=A + 4),
+              dict(maps=A + 2), dict(P=0), dict(B=0), dict(S=0)]
+
+
+@pytest.mark.parametrize("kw", BAD_COMMON, ids=[str(k) for k in BAD_COMMON])
+def test_both_entry_points_refuse_bad_arguments_with_a_message(kw):
+    for fn, tag in ((_stats, b"boundary_stats"), (_grad, b"boundary_grad")):
+        assert fn(**kw) < 0
+        assert nat.lib().ctseg_last_error().startswith(tag), nat.lib().ctseg_last_error()
+
+
+def test_stats_needs_its_partial_buffer():
+    assert _stats(part=None) < 0 and b"boundary_stats: stats buffers" in nat.lib().ctseg_last_error()
+
+
+BAD_GRAD = [(dict(dlogits=A + 8), b"dlogits stride"), (dict(dlogits=None), b"grad buffers"), (dict(bw=None), b"grad buffers"),
+            (dict(gdtype=2), b"grad buffers"), (dict(gdtype=4), b"grad buffers"), (dict(g_ld=8), b"dlogits stride"),
+            (dict(g_ld=10), b"dlogits stride"), (dict(g_ld=20), b"dlogits stride"), (dict(g_ld=4, C=4, ld=4, gdtype=BF16), b"dlogits stride")]
+
+
+@pytest.mark.parametrize("kw,msg", BAD_GRAD, ids=[str(k) for k, _ in BAD_GRAD])
+def test_grad_refuses_bad_gradient_rows(kw, msg):
+    assert _grad(**kw) < 0
+    assert msg in nat.lib().ctseg_last_error(), nat.lib().ctseg_last_error()
+
+
+def test_grad_accepts_12_wide_rows_in_both_storage_kinds():
+    """g_ld = 12 passes the checks with fp32 and with bf16 rows.  Past the checks the call launches: on a machine with a GPU it
+    gets real buffers and succeeds; without one the launch itself fails (-2, the runtime's message), which is not a refusal (-1)."""
+    L = nat.lib()
+    if torch.cuda.is_available():
+        x = torch.zeros(2, 100, 12, device="cuda")
+        D, bw = torch.zeros(2, 9, 100, device="cuda"), torch.zeros(2, 1, 9, device="cuda")
+        for gdt, dt in ((F32, torch.float32), (BF16, torch.bfloat16)):
+            dl = torch.zeros(2, 100, 12, dtype=dt, device="cuda")
+            rc = _grad(logits=x.data_ptr(), maps=D.data_ptr(), bw=bw.data_ptr(), dlogits=dl.data_ptr(), gdtype=gdt)
+            torch.cuda.synchronize()
+            assert rc == 0, L.ctseg_last_error()
+    else:
+        for gdt in (F32, BF16):
+            rc = _grad(gdtype=gdt)
+            assert rc != -1 and not L.ctseg_last_error().startswith(b"boundary_grad: dlogits"), (rc, L.ctseg_last_error())
+
+
+# ---- the opt-in ------------------------------------------------------------------------------------------------------------------
+def test_flag_off_still_raises_and_flag_on_constructs():
+    from capstone_amd.models.losses import LOSSES, LossEntry, MultipleLossWrapper
+    from capstone_amd.training.base_trainer import BaseUNet2D
+    from capstone_amd.training.mixup_trainer import MixupUNet2D
+    from capstone_amd import segloss
+    with pytest.raises(NotImplementedError):
+        MultipleLossWrapper(["Boundary", "Dice"])
+    with pytest.raises(NotImplementedError):
+        MultipleLossWrapper(["Boundary"], exclude_missing=True, device_boundary=False)
+    w = MultipleLossWrapper(["Boundary", "Dice"], exclude_missing=True, device_boundary=True)
+    assert w.names == ["Boundary", "Dice"] and isinstance(w.losses["Boundary"], LossEntry) and w.losses["Boundary"].reduction == "none"
+    assert "Boundary" not in LOSSES and "Boundary" not in segloss.LOSS_NAMES             # the registries stay as they are
+    with pytest.raises(AssertionError):
+        MultipleLossWrapper(["Boundry"], device_boundary=True)
+    for cls in (BaseUNet2D, MixupUNet2D):
+        with pytest.raises(NotImplementedError):
+            cls(filters=[4, 8, 8, 8, 8], loss_fx=["Boundary", "Dice"])
+        m = cls(filters=[4, 8, 8, 8, 8], loss_fx=["Boundary", "Dice"], device_boundary=True)
+        assert m.loss_func.device_boundary and "device_boundary" not in m.hparams
+        off = cls(filters=[4, 8, 8, 8, 8], loss_fx=["Dice"])
+        with pytest.raises(NotImplementedError):
+            off._split_batch((1, 2, 3, 4))
+        assert off._split_batch((1, 2, 3)) == (1, 2, 3, None) and m._split_batch((1, 2, 3, 4)) == (1, 2, 3, 4)
+
+
+def test_boundary_without_maps_asserts():
+    from capstone_amd.models.losses import MultipleLossWrapper
+    w = MultipleLossWrapper(["Boundary", "Dice"], device_boundary=True)
+    x, t = torch.zeros(2, 10, 4, 4), torch.zeros(2, 4, 4, dtype=torch.int64)
+    with pytest.raises(AssertionError, match="Distance maps are required"):
+        w(x, t)
+    with pytest.raises(AssertionError, match="Distance maps are required"):
+        w.forward_mixed(x, t, torch.tensor([1, 0]), 0.5)
+
+
+def test_integer_maps_and_a_wrong_plane_count_raise(emu):
+    from capstone_amd.models.losses import MultipleLossWrapper
+    w = MultipleLossWrapper(["Boundary"], device_boundary=True)
+    x, t = torch.zeros(2, 10, 4, 4), torch.zeros(2, 4, 4, dtype=torch.int64)
+    with pytest.raises(TypeError):
+        w(x, t, dist_maps=torch.zeros(2, 9, 4, 4, dtype=torch.int32))
+    with pytest.raises(ValueError):
+        w(x, t, dist_maps=torch.zeros(2, 10, 4, 4))                                      # a background plane too many
+
+
+def test_host_maps_raise_in_the_product_path():
+    from capstone_amd import segloss
+    with pytest.raises(nat.NativeError):
+        segloss.SegLossEngine(torch.device("cpu"), 2, 16, 10).set_dist_maps(torch.zeros(2, 9, 4, 4))
+
+
+# ---- host logic through the emulator ------------------------------------------------------------------------------------------
+def _case(seed=5, B=3, C=10, H=6, W=5):
+    g = torch.Generator().manual_seed(seed)
+    logits = torch.randn(B, C, H, W, generator=g) * 2
+    target = torch.randint(0, C, (B, H, W), generator=g)
+    D = torch.rand(B, C - 1, H, W, generator=g) * 2 - 1
+    return logits, target, D
+
+
+def _indicator(exclude_missing, zero_column):
+    ind = torch.ones(3, 9)
+    ind[1, 3] = 0
+    if zero_column:
+        ind[:, 6] = 0              # no sample annotates the class: 1 / 0 -> the isinf branch replaces the weights by ones
+    return ind
+
+
+@pytest.mark.parametrize("exclude_missing,zero_column", [(False, False), (True, False), (True, True)])
+def test_wrapper_values_and_gradient_match_the_restatement(emu, exclude_missing, zero_column):
+    from capstone_amd.models.losses import MultipleLossWrapper
+    logits, target, D = _case()
+    ind = _indicator(exclude_missing, zero_column)
+    names = ["Boundary", "Dice", "Focal"]
+    x_ref = logits.double().requires_grad_(True)
+    rb = ref_scalar(x_ref, D.double(), exclude_missing, ind)
+    ro = OL.MultipleLoss(["Dice", "Focal"], exclude_missing=exclude_missing)(x_ref, target, ind.double())
+    (rb + ro["Dice"] + ro["Focal"]).backward()
+    x = logits.clone().requires_grad_(True)
+    wrap = MultipleLossWrapper(names, exclude_missing=exclude_missing, device_boundary=True)
+    v = wrap(x, target, mask_indicator=ind, dist_maps=D.double())                        # (another float dtype is converted)
+    assert list(v) == names
+    np.testing.assert_allclose(v["Boundary"].item(), rb.item(), rtol=2e-5, atol=1e-8)
+    for n in ("Dice", "Focal"):
+        np.testing.assert_allclose(v[n].item(), ro[n].item(), rtol=2e-4, atol=1e-6, err_msg=n)
+    torch.stack(list(v.values())).sum().backward()
+    np.testing.assert_allclose(x.grad.numpy(), x_ref.grad.numpy(), rtol=2e-3, atol=2e-6)
+    # Boundary alone: the storing variant of the gradient pass, no label pass at all
+    x1 = logits.clone().requires_grad_(True)
+    x1_ref = logits.double().requires_grad_(True)
+    ref_scalar(x1_ref, D.double(), exclude_missing, ind).backward()
+    only = MultipleLossWrapper(["Boundary"], exclude_missing=exclude_missing, device_boundary=True)
+    v1 = only(x1, target, mask_indicator=ind, dist_maps=D)
+    (3.0 * v1["Boundary"]).backward()
+    np.testing.assert_allclose(x1.grad.numpy(), 3.0 * x1_ref.grad.numpy(), rtol=1e-4, atol=1e-9)
+    # maps handed to a wrapper without "Boundary" are ignored
+    plain = MultipleLossWrapper(["Dice"], device_boundary=True)(logits, target, dist_maps=D)
+    assert list(plain) == ["Dice"]
+
+
+def test_unreduced_entry_with_a_table_gradient(emu):
+    from capstone_amd.models.losses import LossEntry
+    logits, _, D = _case(seed=8)
+    gT = torch.randn(3, 9, generator=torch.Generator().manual_seed(9))
+    x_ref = logits.double().requires_grad_(True)
+    T_ref = ref_table(x_ref, D.double())
+    (T_ref * gT.double()).sum().backward()
+    x = logits.clone().requires_grad_(True)
+    T = LossEntry("Boundary", "none")(x, D)
+    assert T.shape == (3, 9) and T.dtype == torch.float32
+    np.testing.assert_allclose(T.detach().numpy(), T_ref.detach().numpy(), rtol=2e-5, atol=1e-8)
+    (T * gT).sum().backward()
+    np.testing.assert_allclose(x.grad.numpy(), x_ref.grad.numpy(), rtol=1e-4, atol=1e-9)
+    x2 = logits.clone().requires_grad_(True)
+    m = LossEntry("Boundary", "mean")(x2, D)
+    np.testing.assert_allclose(m.item(), T_ref.mean().item(), rtol=2e-5, atol=1e-8)
+
+
+@pytest.mark.parametrize("exclude_missing", [False, True])
+def test_forward_mixed_is_lambda_a_plus_one_minus_lambda_b(emu, exclude_missing):
+    from capstone_amd.models.losses import MultipleLossWrapper
+    logits, target, D = _case(seed=6)
+    ind = _indicator(True, False)                                                      # sample 1 differs from its partner, sample 1
+    ind[0, 2] = 0                                                                      # ... and sample 0 from its partner, sample 2
+    index, lam = torch.tensor([2, 0, 0]), 0.3
+    names = ["Boundary", "Dice"]
+    x_ref = logits.double().requires_grad_(True)
+    ol = OL.MultipleLoss(["Dice"], exclude_missing=exclude_missing)
+    ra = dict(ol(x_ref, target, ind.double()), Boundary=ref_scalar(x_ref, D.double(), exclude_missing, ind))
+    rb = dict(ol(x_ref, target[index], ind[index].double()), Boundary=ref_scalar(x_ref, D[index].double(), exclude_missing, ind[index]))
+    rv = {n: lam * ra[n] + (1 - lam) * rb[n] for n in names}
+    torch.stack(list(rv.values())).sum().backward()
+    x = logits.clone().requires_grad_(True)
+    wrap = MultipleLossWrapper(names, exclude_missing=exclude_missing, device_boundary=True)
+    v = wrap.forward_mixed(x, target, index, lam, mask_indicator=ind, dist_maps=D)
+    np.testing.assert_allclose(v["Boundary"].item(), rv["Boundary"].item(), rtol=2e-5, atol=1e-8)
+    np.testing.assert_allclose(v["Dice"].item(), rv["Dice"].item(), rtol=2e-4, atol=1e-6)
+    torch.stack(list(v.values())).sum().backward()
+    np.testing.assert_allclose(x.grad.numpy(), x_ref.grad.numpy(), rtol=2e-3, atol=2e-6)
+
+
+@pytest.mark.parametrize("mixup", [False, True], ids=["BaseUNet2D", "MixupUNet2D"])
+def test_trainer_step_passes_the_maps_on(emu, monkeypatch, mixup):
+    from capstone_amd.training import mixup_trainer as MT
+    from capstone_amd.training.base_trainer import BaseUNet2D
+    from capstone_amd.training.utils import weighted_mixup
+    torch.manual_seed(3)
+    cls = MT.MixupUNet2D if mixup else BaseUNet2D
+    m = cls(filters=[4, 8, 8, 8, 8], loss_fx=["Boundary", "Dice"], transform_degree=0, device_boundary=True)
+    g = torch.Generator().manual_seed(4)
+    images = torch.randn(2, 1, 32, 32, generator=g)
+    masks = torch.zeros(2, 9, 32, 32, dtype=torch.uint8)
+    for b in range(2):
+        for k in range(9):
+            masks[b, k, 3 * k + 2:3 * k + 5, 4 + 2 * b:28] = 1
+    ind = torch.ones(2, 9)
+    D = torch.rand(2, 9, 32, 32, generator=g) * 2 - 1
+    index, lam = torch.tensor([1, 0]), 0.3
+    monkeypatch.setattr(MT, "weighted_mixup", functools.partial(weighted_mixup, index=index, lambda_=lam))
+    _, _, _, pred, total = m._shared_step((images, masks, ind, D), prefix="train")
+    x64 = pred.detach().double()
+    want = ref_scalar(x64, D.double())
+    if mixup:
+        want = lam * want + (1 - lam) * ref_scalar(x64, D[index].double())
+    np.testing.assert_allclose(m.logged["Boundary Loss (train)"].item(), want.item(), rtol=2e-5, atol=1e-8)
+    assert "Dice Loss (train)" in m.logged
+    total.backward()
+    grads = [p.grad for p in m.unet.parameters()]
+    assert all(g_ is not None and torch.isfinite(g_).all() for g_ in grads) and any(float(g_.abs().max()) > 0 for g_ in grads)
+    if not mixup:
+        with torch.no_grad():
+            m.validation_step((images, masks, ind, D))
+            m.test_step((images, masks, ind, D))
+        assert "Boundary Loss (val)" in m.logged and "Boundary Loss (test)" in m.logged
