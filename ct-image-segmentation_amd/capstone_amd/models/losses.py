@@ -4,9 +4,10 @@ tensor with grad), computed by the fused HIP loss pass (capstone_amd.segloss) fo
 
 Deliberate fix, flagged: the reference's 3-D wrapper resolves ``"Dice"``, ``"GeneralizedDice"`` and
 ``"Focal"`` in the 2-D registry whose ``assert input.ndim == 4`` raises on volumes (SURVEY.md §3.1
-bug 1).  Here the same formulas run on 4-D and 5-D input alike.  ``"Boundary"`` (2-D only, models/losses.py:127-157)
-raises unless the wrapper is built with ``device_boundary=True``: it then takes the batch's distance maps
-(``MiccaiDataModule2D(enhanced=True, device_maps=True)``) through HIP passes of its own (csrc/boundary_loss.hip).
+bug 1).  Here the same formulas run on 4-D and 5-D input alike.  ``"Boundary"`` (2-D only in the reference,
+models/losses.py:127-157) raises unless the wrapper is built with ``device_boundary=True``: it then takes the batch's distance maps
+(``MiccaiDataModule2D(enhanced=True, device_maps=True)``, or ``MiccaiDataset3D(dist_maps=True)`` for volumes) through HIP passes
+of its own (csrc/boundary_loss.hip), which see rows of voxels and do not care about the spatial rank.
 """
 import torch
 import torch.nn as nn
@@ -172,8 +173,8 @@ class LossEntry(nn.Module):
         nat.require_gpu(input, f"{self.name} loss")
         eng, plan = _engine_for(input)
         if self.name == "Boundary":      # the reference calls this entry as fx(input, dist_maps) (models/losses.py:188-192)
-            assert input.ndim == 4, "Expected input of shape: (N, C, H, W)"
-            assert target.ndim == 4, "Expected distance maps of shape: (N, C, H, W)"
+            assert input.ndim in (4, 5), "Expected input of shape: (N, C, H, W) or (N, C, H, W, D)"
+            assert target.ndim == input.ndim, "Expected distance maps of the input's rank: (N, C, H, W) or (N, C, H, W, D)"
             eng.set_dist_maps(target)
         else:
             stash = getattr(target, "_ctseg_labels", None)
@@ -191,7 +192,7 @@ class LossEntry(nn.Module):
 
 class MultipleLossWrapper(nn.Module):
     def __init__(self, losses, exclude_missing=False, device_boundary=False):
-        """``device_boundary``: opt in to the Boundary loss on the device; ``forward`` then needs ``dist_maps`` (B, C-1, H, W) when
+        """``device_boundary``: opt in to the Boundary loss on the device; ``forward`` then needs ``dist_maps`` (B, C-1, *spatial) when
         ``"Boundary"`` is among the losses.  Off (the default), a ``"Boundary"`` entry raises."""
         super().__init__()
         self.exclude_missing = exclude_missing

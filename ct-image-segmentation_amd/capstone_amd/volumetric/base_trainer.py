@@ -16,6 +16,7 @@ import torch.nn as nn
 from .. import STRUCTURES, segloss
 from .. import _native as nat
 from ..models import UNet
+from ..models.losses import _as_cl
 from ..training.utils import _squash_predictions  # noqa: F401  (same import the reference has)
 from .losses import MultipleLossWrapper3D
 from .metrics import DiceMetricWrapper3D
@@ -175,7 +176,10 @@ def _precision(kwargs):
 
 class BaseUNet3D(_DataParallelSurface, _Base):
     def __init__(self, filters: List = [16, 32, 64, 128, 256], use_res_units: bool = False, downsample: bool = False,
-                 lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, **kwargs) -> None:
+                 lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
+                 **kwargs) -> None:
+        """``device_boundary``: opt in to the Boundary loss on volumes; the batch then carries the distance maps as its fourth
+        element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise."""
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
@@ -186,7 +190,8 @@ class BaseUNet3D(_DataParallelSurface, _Base):
             self.save_hyperparameters(*names, frame_locals=dict(locals()))
         self._precision = _precision(kwargs)
         self.unet = self._construct_model()
-        self.loss_func = MultipleLossWrapper3D(losses=loss_fx, exclude_missing=exclude_missing)
+        self.device_boundary = device_boundary      # (a switch of this port, not a reference hyperparameter: kept out of hparams)
+        self.loss_func = MultipleLossWrapper3D(losses=loss_fx, exclude_missing=exclude_missing, device_boundary=device_boundary)
         self.dice_score = DiceMetricWrapper3D()
 
     @property
@@ -213,6 +218,13 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         _, _, _, _, loss = self._shared_step(batch, is_training=True)
         return loss
 
+    def _split_batch(self, batch):
+        """(images, masks, mask_indicator, dist_maps or None); a fourth element needs ``device_boundary``, as in BaseUNet2D"""
+        images, masks, mask_indicator, *dist_maps = batch
+        if dist_maps and not self.device_boundary:
+            raise NotImplementedError("distance maps (Boundary loss) are outside the MI355X hot path unless device_boundary=True")
+        return images, masks, mask_indicator, (dist_maps[0] if dist_maps else None)
+
     def _ce_only(self):
         names = list(self.loss_func.names)
         return len(names) == 1 and names[0] in ("CrossEntropy", "WeightedCrossEntropy")
@@ -225,7 +237,7 @@ class BaseUNet3D(_DataParallelSurface, _Base):
     def _forward_and_ce(self, batch, keep_logits):
         """squash masks (side stream) -> forward -> cross-entropy + Dice counts + d loss / d logits for an upstream gradient of 1.
         Returns (engine, plan, loss engine, weighted)."""
-        images, masks, mask_indicator = batch
+        images, masks, mask_indicator, _ = self._split_batch(batch)     # (cross-entropy only: the maps are not read)
         eng = self.unet.engine()
         plan = eng.plan_for(images)
         side = plan.side_stream()
@@ -287,13 +299,13 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         self._shared_step(batch, is_training=False)
 
     def _shared_step(self, batch, is_training: bool):
-        (images, masks, mask_indicator) = batch
+        images, masks, mask_indicator, dist_maps = self._split_batch(batch)
         masks = _squash_masks_3D(masks, self._n_classes, self.device)
         mask_indicator = mask_indicator.type_as(images)
         prefix = "train" if is_training else "val"
         prediction = self.forward(images)
         prediction._ctseg_plan = self.unet.engine().last_plan
-        loss_dict = self.loss_func(input=prediction, target=masks, mask_indicator=mask_indicator)
+        loss_dict = self.loss_func(input=prediction, target=masks, mask_indicator=mask_indicator, dist_maps=dist_maps)
         total_loss = torch.stack(list(loss_dict.values())).sum()
         for name, loss_value in loss_dict.items():
             self.log(f"{name} Loss ({prefix})", loss_value, on_step=False, on_epoch=True)
@@ -311,6 +323,9 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         # already counted |pred==c & true==c|, |pred==c|, |true==c| with the same softmax->argmax tie rule.
         with torch.no_grad():
             eng = getattr(prediction._ctseg_plan, "_ctseg_loss", None)
+            if all(n == "Boundary" for n in self.loss_func.names):      # no label loss ran: count now, on the labels the wrapper set
+                ptr, ld, _keep = _as_cl(prediction)
+                eng.stats(ptr, ld)
             dice_mean, dice_per_class = eng.dice_metric()
             self._keep_dice_counts(eng.cnt, prefix)
             for structure, score in zip(STRUCTURES, dice_per_class):
@@ -322,10 +337,12 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         """keep_logits=False lets a cross-entropy-only step run the logits convolution with the loss fused into its epilogue
         (ctseg_conv_logits_ce): the fp32 logits are then never materialised and ``engine.logits_view()`` raises after the step;
         loss, Dice metric, gradients and the update are the same (gradient of the loss w.r.t. the logits bit-identical)."""
-        images, masks, mask_indicator = batch
+        images, masks, mask_indicator, dist_maps = self._split_batch(batch)
         nat.require_gpu(images, "fit_step")
         names = list(self.loss_func.names)
         ce_only = self._ce_only()
+        boundary, others = "Boundary" in names, any(n != "Boundary" for n in names)
+        assert not boundary or dist_maps is not None, "Distance maps are required for using boundary loss"
         vals = None
         if ce_only:
             eng, plan, le, weighted = self._forward_and_ce(batch, keep_logits)
@@ -351,10 +368,18 @@ class BaseUNet3D(_DataParallelSurface, _Base):
                 le.set_labels(lab_u8, hist)
                 logits = plan.forward(images)
             dl = plan.dlogits
+            if boundary:
+                le.set_dist_maps(dist_maps)
+            # (always: the step's Dice counts come from the label pass, as in _SegLossPairFn)
             le.stats(logits.ptr(), logits.ld, weighted_too="WeightedCrossEntropy" in names)
+            if boundary:
+                le.boundary_stats(logits.ptr(), logits.ld)
             vals = le.loss_values(names, self.loss_func.exclude_missing, mask_indicator.float())
             le.build_coef({n: 1.0 for n in names})
-            le.grad(logits.ptr(), logits.ld, dl.ptr(), dl.ld, plan.dt)
+            if others:      # the order of models.losses._write_grad: the label losses store, the Boundary pass adds
+                le.grad(logits.ptr(), logits.ld, dl.ptr(), dl.ld, plan.dt)
+            if boundary:
+                le.boundary_grad(logits.ptr(), logits.ld, dl.ptr(), dl.ld, plan.dt, accumulate=others)
         book = {}
 
         def bookkeeping():     # scalar-sized work: queued behind the backward pass, beside the side stream's tail

@@ -13,13 +13,20 @@ import numpy as np
 import torch
 
 from .. import STRUCTURES
+from ..data.utils import compute_distance_map
 from .transforms import InstancePipeline3D
 
 
 class MiccaiDataset3D:
-    def __init__(self, path: str, transform=None, device="cuda"):
+    def __init__(self, path: str, transform=None, device="cuda", dist_maps: bool = False, signed: bool = False):
+        """``dist_maps=True``: ``__getitem__`` returns a fourth element, the (9,H,W,D) fp32 distance maps of the transformed masks
+        (the Boundary loss's input, ``BaseUNet3D(device_boundary=True)``); ``signed`` as ``data.utils.compute_distance_map``."""
         self.path = Path(path).absolute()
         self.transform = transform
+        self.dist_maps, self.signed = dist_maps, signed
+        if dist_maps and transform is not None and not getattr(transform, "dist_maps", False):
+            raise ValueError("MiccaiDataset3D(dist_maps=True) needs a transform that returns \"dist_maps\" "
+                             "(InstancePipeline3D(dist_maps=True)) or no transform")
         self.device = torch.device(device)
         self.instance_paths = sorted(p.as_posix() for p in self.path.iterdir())      # same order on every platform (ref :16-18)
 
@@ -34,29 +41,38 @@ class MiccaiDataset3D:
         image = torch.from_numpy(np.ascontiguousarray(image)).to(self.device, non_blocking=True)
         masks = torch.from_numpy(np.ascontiguousarray(masks).view(np.uint8) if masks.dtype == np.bool_ else np.ascontiguousarray(masks))
         masks = masks.to(self.device, non_blocking=True)
-        hist = None
+        hist = maps = None
         if self.transform is not None:
             transformed = self.transform(image=image, masks=masks)
             image, masks, hist = transformed["image"], transformed["masks"], transformed.get("hist")
+            maps = transformed.get("dist_maps") if self.dist_maps else None
+        elif self.dist_maps:
+            maps = compute_distance_map(masks, signed=self.signed, spatial_dims=3)
         mask_indicator = torch.from_numpy(mask_indicator).to(self.device)
         if hist is not None:
             masks._ctseg_hist = hist
+        if self.dist_maps:
+            return image, masks, mask_indicator, maps
         return image, masks, mask_indicator
 
 
 def collate_3d(samples):
     """list of ``__getitem__`` triples -> (images (B,1,H,W,D), masks, mask_indicator (B,9)); masks = (B,9,H,W,D) uint8, or the
-    (B,H,W,D) uint8 label maps of a squashing pipeline carrying ``_ctseg_labels`` = (labels (B,S), per-class counts (B,10))"""
+    (B,H,W,D) uint8 label maps of a squashing pipeline carrying ``_ctseg_labels`` = (labels (B,S), per-class counts (B,10)).
+    When every sample has a fourth element (``dist_maps=True``), the (B,9,H,W,D) fp32 maps follow as the batch's fourth."""
     images = torch.stack([s[0] for s in samples])
     indicator = torch.stack([s[2] for s in samples])
     masks = torch.stack([s[1] for s in samples])
     if all(hasattr(s[1], "_ctseg_hist") for s in samples):
         masks._ctseg_labels = (masks.reshape(len(samples), -1), torch.stack([s[1]._ctseg_hist for s in samples]))
+    if all(len(s) == 4 for s in samples):
+        return images, masks, indicator, torch.stack([s[3] for s in samples])
     return images, masks, indicator
 
 
-def get_miccai_3d(split: str = "train", transform=None, root: str = "storage", device="cuda"):
+def get_miccai_3d(split: str = "train", transform=None, root: str = "storage", device="cuda", dist_maps: bool = False,
+                  signed: bool = False):
     assert split in ["train", "valid", "test"], "Invalid data split passed"
     if transform is None:
-        transform = InstancePipeline3D()
-    return MiccaiDataset3D(f"{root}/miccai_3d/{split}", transform=transform, device=device)
+        transform = InstancePipeline3D(dist_maps=dist_maps, signed=signed)
+    return MiccaiDataset3D(f"{root}/miccai_3d/{split}", transform=transform, device=device, dist_maps=dist_maps, signed=signed)

@@ -17,6 +17,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from .. import _native as nat
+from ..data.utils import compute_distance_map
 
 _IMG_DTYPES = {torch.float32: nat.F32, torch.int16: nat.I16, torch.uint8: nat.U8}
 
@@ -101,19 +102,25 @@ class ToTensorV3:
 class InstancePipeline3D:
     """``transform(image=..., masks=...) -> {"image": (1,H,W,D) fp32, "masks": ...}`` like the albumentations Compose of
     volumetric/predefined.py:4-7.  ``squash=False``: "masks" = (9,H,W,D) uint8 (the reference's batch element);
-    ``squash=True``: "masks" = (H,W,D) uint8 label map with ``"hist"`` = per-class voxel counts riding along."""
+    ``squash=True``: "masks" = (H,W,D) uint8 label map with ``"hist"`` = per-class voxel counts riding along.
+    ``dist_maps=True`` adds ``"dist_maps"``: the (9,H,W,D) fp32 distance maps of the nine RESIZED masks
+    (``data.utils.compute_distance_map(spatial_dims=3)``, ``signed`` as there).  Structures overlap, so the label map cannot give
+    them back: a squashing pipeline then has the same resize launch write the nine masks beside the label map."""
 
-    def __init__(self, size=(96, 256, 256), squash: bool = False, window: Optional[Tuple] = None):
-        self.size, self.squash, self.window = tuple(size), squash, window
+    def __init__(self, size=(96, 256, 256), squash: bool = False, window: Optional[Tuple] = None, dist_maps: bool = False,
+                 signed: bool = False):
+        self.size, self.squash, self.window, self.dist_maps, self.signed = tuple(size), squash, window, dist_maps, signed
 
     def __call__(self, image: torch.Tensor, masks) -> dict:
         if isinstance(masks, (list, tuple)):
             masks = torch.stack(list(masks))
-        img, m, lab, hist = resize3d_to_hwd(image, masks, self.size, self.window, want_masks=not self.squash,
+        img, m, lab, hist = resize3d_to_hwd(image, masks, self.size, self.window, want_masks=self.dist_maps or not self.squash,
                                             want_labels=self.squash)
         out = {"image": img.unsqueeze(0), "masks": lab if self.squash else m}
         if self.squash:
             out["hist"] = hist
+        if self.dist_maps:
+            out["dist_maps"] = compute_distance_map(m, signed=self.signed, spatial_dims=3)
         return out
 
 

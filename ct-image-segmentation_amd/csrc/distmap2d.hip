@@ -11,15 +11,11 @@
 //   k = isqrt(d2_fg) & 255 outside, (1 - isqrt(d2_bg)) & 255 inside, 0 on a plane without foreground
 // and the map is k / 255.0, here table[k] with the host's float32(k / 255.0).  SIGNED is the evidently intended float map.  A plane
 // without any background pixel has no defined reference value (scipy's output there is an artefact): it is all zero in both modes.
-#include "ctseg_dev.h"
+#include "distmap_common.h"
 
 namespace ctseg {
 
-enum { DM_REFERENCE = 0, DM_SIGNED = 1 };
-constexpr int DM_MAX_SIDE = 1024;        // 2 * 1023^2 fits int32 (and float's 24 bits); a vertical distance fits uint16 below the sentinel
 constexpr int DM_ROWS = 4;               // rows of a plane per workgroup of the row pass: 4 * 1024 * 4 B = 16 KiB of LDS at the most
-constexpr uint32_t DM_NONE = 0xffffu;
-constexpr int DM_INF = 0x7fffffff;
 
 // Lane (plane p, column x); the workspace holds fg | bg << 16 per pixel.  Both sweeps are coalesced across x.
 __global__ __launch_bounds__(256) void distmap2d_columns_kernel(const uint8_t* __restrict__ masks, int P, int H, int W,
@@ -50,42 +46,6 @@ __global__ __launch_bounds__(256) void distmap2d_columns_kernel(const uint8_t* _
     dbg = ubg < dbg ? ubg : dbg;
     g[(int64_t)y * W] = dfg | (dbg << 16);
   }
-}
-
-// min over x' of (x - x')^2 + g[x']^2 on one LDS row; DM_INF when no column of the row holds a value
-__device__ __forceinline__ int row_min(const uint16_t* g, int x, int W) {
-  int best = DM_INF;
-  const uint32_t g0 = g[x];
-  if (g0 != DM_NONE) best = (int)(g0 * g0);
-  for (int d = 1; d < W; ++d) {
-    const int dd = d * d;
-    if (dd >= best) break;
-    const int xl = x - d, xr = x + d;
-    if (xl < 0 && xr >= W) break;
-    if (xl >= 0) {
-      const uint32_t v = g[xl];
-      if (v != DM_NONE) { const int c = dd + (int)(v * v); best = c < best ? c : best; }
-    }
-    if (xr < W) {
-      const uint32_t v = g[xr];
-      if (v != DM_NONE) { const int c = dd + (int)(v * v); best = c < best ? c : best; }
-    }
-  }
-  return best;
-}
-
-// floor(sqrt(v)) for 0 <= v < 2^24: the float root is only a first guess
-__device__ __forceinline__ int isqrt(int v) {
-  int r = (int)__fsqrt_rn((float)v);
-  while (r * r > v) --r;
-  while ((r + 1) * (r + 1) <= v) ++r;
-  return r;
-}
-
-// sqrt(v) in float32, correctly rounded; a perfect square gives its integer root
-__device__ __forceinline__ float root_f32(int v) {
-  const int r = isqrt(v);
-  return r * r == v ? (float)r : __fsqrt_rn((float)v);
 }
 
 // Workgroup b: rows [r0, r0 + DM_ROWS) of plane p.

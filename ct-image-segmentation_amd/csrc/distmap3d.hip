@@ -1,0 +1,154 @@
+// Distance maps of the 3-D pipeline on gfx950: capstone/data/utils.py:10-26 (compute_distance_map, rank-agnostic in the reference)
+// for P volumes [X][Y][Z] of mask bytes, Z innermost: the (K, H, W, D) storage of ctseg_resize3d_to_hwd.
+// The exact Euclidean distance transform in its separable form, in integers throughout, three launches:
+//   sweep   along X.  One lane per line (y, z) walks down and then up; neighbouring lanes hold neighbouring (y, z), which are
+//           contiguous in memory, so every load and store of both sweeps is coalesced.  (A sweep along Z would stride by a line
+//           per lane.)
+//   lines   lower envelope along Z, the contiguous axis: a workgroup stages a run of whole Z lines in LDS, squared.
+//   slabs   lower envelope along Y and the map value: a workgroup stages the slab Y x ztile of one x, so its global loads and
+//           stores stay contiguous along Z, and searches along Y with the slab's row length as the step.
+// A voxel is foreground or background, and its squared distance to its own class is 0.  So every pass keeps ONE number per voxel,
+// the distance to the OTHER class, beside the class bit; every voxel runs one search per pass, not two; and the workspace is
+//   sweep: uint16  class << 15 | distance along X (DM3_NONE: the line has no voxel of the other class)
+//   lines: uint32  class << 31 | squared distance within the voxel's (X, Z) plane (DM_INF: the plane has none)
+// A search sees "class differs: 0, class equal: the stored number".  "None" survives a pass exactly when the whole line holds
+// none, so after the last pass it means that the volume has no voxel of the other class: -1 in that d2 output and a map of 0,
+// decided per voxel, with no flag shared between lanes.
+// The value pass is that of distmap2d.hip: REFERENCE gives table[k] of the byte the reference stores, SIGNED the float map.
+#include "distmap_common.h"
+
+namespace ctseg {
+
+constexpr uint32_t DM3_NONE = 0x7fffu;   // of the sweep's 15-bit distance (a side is at most DM_MAX_SIDE = 1024)
+constexpr int DM3_LINE_WORDS = 4096;     // LDS words of the line pass: 16 KiB, whole Z lines back to back (at least one: Z <= 1024)
+constexpr int DM3_SLAB_WORDS = 8192;     // LDS words of the slab pass: 32 KiB = Y x ztile, ztile a power of two in 8..64 (Y <= 1024)
+constexpr int DM3_ZTILE_MIN = 8, DM3_ZTILE_MAX = 64;
+
+// Lane: line (y, z) of volume p; `plane` = Y * Z voxels.
+__global__ __launch_bounds__(256) void distmap3d_sweep_kernel(const uint8_t* __restrict__ masks, int64_t lines, int X, int64_t plane,
+                                                              uint16_t* __restrict__ ws) {
+  const int64_t line = (int64_t)blockIdx.x * 256 + threadIdx.x;     // the lines of all volumes, back to back
+  if (line >= lines) return;
+  const int64_t p = line / plane, yz = line - p * plane;
+  const int64_t base = p * X * plane + yz;
+  const uint8_t* m = masks + base;
+  uint16_t* g = ws + base;
+  int last_fg = -1, last_bg = -1;        // x of the nearest one below, -1: none yet
+#pragma unroll 8
+  for (int x = 0; x < X; ++x) {
+    const bool fg = m[(int64_t)x * plane] != 0;
+    if (fg) last_fg = x; else last_bg = x;
+    const int other = fg ? last_bg : last_fg;
+    const uint32_t d = other < 0 ? DM3_NONE : (uint32_t)(x - other);
+    g[(int64_t)x * plane] = (uint16_t)((fg ? 0x8000u : 0u) | d);
+  }
+  int next_fg = -1, next_bg = -1;
+#pragma unroll 8
+  for (int x = X - 1; x >= 0; --x) {
+    const uint32_t v = g[(int64_t)x * plane];
+    const bool fg = (v & 0x8000u) != 0;
+    if (fg) next_fg = x; else next_bg = x;
+    const int other = fg ? next_bg : next_fg;
+    const uint32_t u = other < 0 ? DM3_NONE : (uint32_t)(other - x);
+    const uint32_t d = v & 0x7fffu;
+    g[(int64_t)x * plane] = (uint16_t)((v & 0x8000u) | (u < d ? u : d));    // the sentinel is the largest value
+  }
+}
+
+// Workgroup b: the Z lines [b * L, b * L + L) of all volumes, L * Z <= DM3_LINE_WORDS voxels that are contiguous in memory.
+__global__ __launch_bounds__(256) void distmap3d_lines_kernel(const uint16_t* __restrict__ g, int64_t voxels, int Z, int L,
+                                                              uint32_t* __restrict__ f) {
+  __shared__ uint32_t s[DM3_LINE_WORDS];
+  const int64_t e0 = (int64_t)blockIdx.x * L * Z;
+  const int n = voxels - e0 < (int64_t)L * Z ? (int)(voxels - e0) : L * Z;   // whole lines: voxels is a multiple of Z
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += 256) {
+    const uint32_t v = g[e0 + i], d = v & 0x7fffu;
+    s[i] = ((v & 0x8000u) << 16) | (d == DM3_NONE ? (uint32_t)DM_INF : d * d);
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) {
+    const int r = i / Z, z = i - r * Z;
+    const uint32_t mine = s[i] & 0x80000000u;
+    f[e0 + i] = mine | (uint32_t)line_min_sq(s + r * Z, z, Z, 1, mine);
+  }
+}
+
+// Workgroup (b, t): row b = p * X + x of Y lines, columns [t * ZT, t * ZT + ZT) of Z; ZT = 1 << zshift, Y * ZT <= DM3_SLAB_WORDS.
+__global__ __launch_bounds__(256) void distmap3d_slabs_kernel(const uint32_t* __restrict__ f, int Y, int Z, int zshift, int ztiles,
+                                                              int mode, const float* __restrict__ table, float* __restrict__ out,
+                                                              int* __restrict__ d2_fg, int* __restrict__ d2_bg) {
+  __shared__ uint32_t s[DM3_SLAB_WORDS];
+  const int ZT = 1 << zshift;
+  const int64_t b = blockIdx.x / ztiles;
+  const int z0 = (int)(blockIdx.x - b * ztiles) << zshift;
+  const int zn = Z - z0 < ZT ? Z - z0 : ZT;
+  const int64_t base = b * Y * Z + z0;
+  const int n = Y << zshift;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += 256) {
+    const int y = i >> zshift, zc = i & (ZT - 1);
+    if (zc < zn) s[i] = f[base + (int64_t)y * Z + zc];
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) {
+    const int y = i >> zshift, zc = i & (ZT - 1);
+    if (zc >= zn) continue;
+    const uint32_t mine = s[i] & 0x80000000u;
+    const bool inside = mine != 0;
+    const int d2 = line_min_sq(s + zc, y, Y, ZT, mine);        // to the other class
+    const bool none = d2 == DM_INF;                            // the volume has no voxel of the other class
+    const int64_t o = base + (int64_t)y * Z + zc;
+    if (d2_fg) d2_fg[o] = inside ? 0 : (none ? -1 : d2);
+    if (d2_bg) d2_bg[o] = inside ? (none ? -1 : d2) : 0;
+    float val = 0.f;
+    if (!none) {
+      if (mode == DM_REFERENCE) {
+        const int k = inside ? (1 - isqrt(d2)) & 255 : isqrt(d2) & 255;
+        val = table[k];
+      } else {
+        val = inside ? __fdiv_rn(-(root_f32(d2) - 1.f), 255.f) : __fdiv_rn(root_f32(d2), 255.f);
+      }
+    }
+    out[o] = val;
+  }
+}
+
+}  // namespace ctseg
+
+using namespace ctseg;
+
+extern "C" int ctseg_distmap3d_batch(const uint8_t* masks, int32_t P, int32_t X, int32_t Y, int32_t Z, int32_t mode, const float* table,
+                                     void* workspace, int64_t workspace_bytes, float* out, int32_t* d2_fg, int32_t* d2_bg,
+                                     void* stream) {
+  CTSEG_REQUIRE(masks && table && workspace && out, "distmap3d_batch: null pointer (masks, table, workspace and out are required)");
+  CTSEG_REQUIRE(P >= 1 && X >= 1 && Y >= 1 && Z >= 1, "distmap3d_batch: P, X, Y, Z >= 1 (got %d volumes of %d x %d x %d)", P, X, Y, Z);
+  CTSEG_REQUIRE(X <= DM_MAX_SIDE && Y <= DM_MAX_SIDE && Z <= DM_MAX_SIDE, "distmap3d_batch: sides up to %d (got %d x %d x %d)",
+                DM_MAX_SIDE, X, Y, Z);
+  CTSEG_REQUIRE(mode == DM_REFERENCE || mode == DM_SIGNED, "distmap3d_batch: mode %d", mode);
+  const int64_t plane = (int64_t)Y * Z, voxels = (int64_t)P * X * plane;
+  CTSEG_REQUIRE(workspace_bytes >= 6 * voxels, "distmap3d_batch: the workspace holds %lld bytes, %lld are needed",
+                (long long)workspace_bytes, (long long)(6 * voxels));
+  CTSEG_REQUIRE(((uintptr_t)workspace % 4) == 0 && ((uintptr_t)out % 4) == 0 && ((uintptr_t)table % 4) == 0 &&
+                    ((uintptr_t)d2_fg % 4) == 0 && ((uintptr_t)d2_bg % 4) == 0,
+                "distmap3d_batch: unaligned pointer");
+  const int L = DM3_LINE_WORDS / Z;                            // Z lines per workgroup of the line pass, >= 4
+  int zshift = 3;                                              // the widest slab tile that fits and that Z can fill
+  while ((2 << zshift) <= DM3_ZTILE_MAX && ((int64_t)Y << (zshift + 1)) <= DM3_SLAB_WORDS && (1 << zshift) < Z) ++zshift;
+  const int ztiles = (Z + (1 << zshift) - 1) >> zshift;
+  const int64_t sweep_blocks = ((int64_t)P * plane + 255) / 256, line_blocks = ((int64_t)P * X * Y + L - 1) / L;
+  const int64_t slab_blocks = (int64_t)P * X * ztiles;
+  CTSEG_REQUIRE(sweep_blocks <= 0x7fffffff && line_blocks <= 0x7fffffff && slab_blocks <= 0x7fffffff,
+                "distmap3d_batch: %d volumes are too many for one launch", P);
+  uint32_t* f = (uint32_t*)workspace;                          // [voxels] uint32, then [voxels] uint16
+  uint16_t* g = (uint16_t*)(f + voxels);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(distmap3d_sweep_kernel, dim3((unsigned)sweep_blocks), dim3(256), 0, st, masks, (int64_t)P * plane, X, plane, g);
+  CTSEG_LAUNCH_CHECK("distmap3d_batch (sweep)");
+  hipLaunchKernelGGL(distmap3d_lines_kernel, dim3((unsigned)line_blocks), dim3(256), 0, st, (const uint16_t*)g, voxels, Z, L, f);
+  CTSEG_LAUNCH_CHECK("distmap3d_batch (lines)");
+  hipLaunchKernelGGL(distmap3d_slabs_kernel, dim3((unsigned)slab_blocks), dim3(256), 0, st, (const uint32_t*)f, Y, Z, zshift, ztiles,
+                     mode, table, out, d2_fg, d2_bg);
+  CTSEG_LAUNCH_CHECK("distmap3d_batch (slabs)");
+  return 0;
+}

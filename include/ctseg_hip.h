@@ -510,6 +510,17 @@ int ctseg_pipeline2d_warp_batch(const void* image_store, int32_t image_dtype, in
 int ctseg_distmap2d_batch(const uint8_t* masks, int32_t P, int32_t H, int32_t W, int32_t mode, const float* table,
                           void* workspace, int64_t workspace_bytes, float* out, int32_t* d2_fg, int32_t* d2_bg, void* stream);
 
+/* The same maps for P volumes of X x Y x Z mask bytes, Z innermost (the (K, H, W, D) storage ctseg_resize3d_to_hwd writes), in
+ * three launches: a sweep along X, a lower-envelope pass along Z and one along Y that also forms the value.  The distances are the
+ * exact 3-D squared Euclidean distances; masks, mode, table, out, d2_fg and d2_bg are as above, per volume.  No atomics: two runs
+ * give the same bits.
+ *   workspace      >= 6 * P * X * Y * Z bytes on the device (4 per voxel for the line pass's result, then 2 per voxel for the
+ *                  sweep's), 4-byte aligned; its contents are not kept between calls
+ * X, Y, Z <= 1024 (3 * 1023^2 fits int32 and float's 24 bits; the LDS tiles cover lines of 1024 on Y and Z, and X is only
+ * swept).  Every argument is validated on the host before the first launch. */
+int ctseg_distmap3d_batch(const uint8_t* masks, int32_t P, int32_t X, int32_t Y, int32_t Z, int32_t mode, const float* table,
+                          void* workspace, int64_t workspace_bytes, float* out, int32_t* d2_fg, int32_t* d2_bg, void* stream);
+
 /* Sliding-window inference (BASELINE.json configs[4]).  The reference has no inferer (grep: 0 hits); the
  * semantics are those of MONAI 0.3 `monai.inferers.sliding_window_inference`, the companion of the `monai.networks.nets.UNet`
  * the reference builds at capstone/volumetric/base_trainer.py:65-72.
