@@ -48,28 +48,28 @@ def _as_cl(logits):
     return buf.data_ptr(), ldn, buf
 
 
-def _write_grad(ctx, eng, plan, names, grad):
-    """One gradient row per voxel for the requested losses: ``grad(ptr, ld, dl_ptr, g_ld, gdt)`` (the label losses' pass) and then
-    the Boundary pass adding to it, or the Boundary pass alone storing when it is the only name.  The row goes to the UNet
-    plan in its own storage dtype (no fp32 round trip), or to an fp32 buffer returned as the autograd gradient."""
+def _stash(ctx, logits, eng, plan, names):
+    """what backward needs, kept on ``ctx``; returns the channels-last (ptr, ld) of the logits"""
+    ctx.cl = _as_cl(logits)
+    ctx.eng, ctx.plan, ctx.names, ctx.shape, ctx.maps = eng, plan, names, logits.shape, eng.maps
+    return ctx.cl[:2]
+
+
+def _write_grad(ctx):
+    """The gradient row of ``ctx.names`` (``SegLossEngine.grad_passes``, after the caller's ``build_coef``) goes to the UNet plan in
+    its own storage dtype (no fp32 round trip), or to an fp32 buffer returned as the autograd gradient."""
+    eng, plan, names = ctx.eng, ctx.plan, ctx.names
     ptr, ld, _ = ctx.cl
-    boundary, others = "Boundary" in names, any(n != "Boundary" for n in names)
-    if boundary:
+    if "Boundary" in names:
         eng.maps = ctx.maps             # another forward may have set other maps on the same engine since
     if plan is not None:
-        dl_ptr, g_ld, gdt = plan.dlogits.ptr(), plan.dlogits.ld, plan.dt
-    else:
-        B, C = ctx.shape[:2]
-        g_ld, gdt = (C + 3) // 4 * 4, nat.F32
-        buf = torch.zeros((B, eng.S, g_ld), dtype=torch.float32, device=eng.device)
-        dl_ptr = buf.data_ptr()
-    if others:
-        grad(ptr, ld, dl_ptr, g_ld, gdt)
-    if boundary:
-        eng.boundary_grad(ptr, ld, dl_ptr, g_ld, gdt, accumulate=others)
-    if plan is not None:
+        eng.grad_passes(ptr, ld, names, plan.dlogits.ptr(), plan.dlogits.ld, plan.dt)
         plan.dlogits_is_current = True
         return torch.zeros((), dtype=torch.float32, device=eng.device).expand(ctx.shape)
+    B, C = ctx.shape[:2]
+    g_ld = (C + 3) // 4 * 4
+    buf = torch.zeros((B, eng.S, g_ld), dtype=torch.float32, device=eng.device)
+    eng.grad_passes(ptr, ld, names, buf.data_ptr(), g_ld, nat.F32)
     return buf[..., :C].permute(0, 2, 1).reshape(ctx.shape)
 
 
@@ -79,21 +79,14 @@ class _SegLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, eng, plan, names, exclude_missing, indicator):
-        ptr, ld, keep = _as_cl(logits)
-        if any(n != "Boundary" for n in names):
-            eng.stats(ptr, ld, weighted_too="WeightedCrossEntropy" in names)
-        if "Boundary" in names:
-            eng.boundary_stats(ptr, ld)
-        vals = eng.loss_values(names, exclude_missing, indicator)
-        ctx.eng, ctx.plan, ctx.names, ctx.cl = eng, plan, names, (ptr, ld, keep)
-        ctx.shape, ctx.maps = logits.shape, eng.maps
+        ptr, ld = _stash(ctx, logits, eng, plan, names)
+        vals = eng.loss_forward(ptr, ld, names, exclude_missing, indicator)
         return tuple(vals[n] for n in names)
 
     @staticmethod
     def backward(ctx, *gs):
-        eng, plan = ctx.eng, ctx.plan
-        eng.build_coef({n: (g if g is not None else 0.0) for n, g in zip(ctx.names, gs)})
-        return _write_grad(ctx, eng, plan, ctx.names, eng.grad), None, None, None, None, None
+        ctx.eng.build_coef({n: (g if g is not None else 0.0) for n, g in zip(ctx.names, gs)})
+        return (_write_grad(ctx),) + (None,) * 5
 
 
 class _SegLossPairFn(torch.autograd.Function):
@@ -103,57 +96,41 @@ class _SegLossPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, eng, plan, names, exclude_missing, indicators, lambda_):
-        ptr, ld, keep = _as_cl(logits)
-        eng.stats_pair(ptr, ld, weighted_too="WeightedCrossEntropy" in names)      # (always: the step's Dice counts come from it)
-        if "Boundary" in names:
-            eng.boundary_stats(ptr, ld)
-        vals, ctx.w = [], []
+        ptr, ld = _stash(ctx, logits, eng, plan, names)
+        eng.stat_passes(ptr, ld, names, count_dice=True)        # (the step's Dice counts come from the label pass)
+        vals, ctx.w, ctx.lambda_ = [], [], lambda_
         for s in (0, 1):
             with eng.side(s):
                 vals.append(eng.loss_values(names, exclude_missing, indicators[s]))
                 ctx.w.append(eng._w)
-        ctx.eng, ctx.plan, ctx.names, ctx.cl, ctx.lambda_ = eng, plan, names, (ptr, ld, keep), lambda_
-        ctx.shape, ctx.maps = logits.shape, eng.maps
         return tuple(lambda_ * vals[0][n] + (1 - lambda_) * vals[1][n] for n in names)
 
     @staticmethod
     def backward(ctx, *gs):
-        eng, plan = ctx.eng, ctx.plan
+        eng = ctx.eng
         for s, lam in ((0, ctx.lambda_), (1, 1 - ctx.lambda_)):     # lambda enters through the upstream gradients only
             with eng.side(s):
                 eng._w = ctx.w[s]
                 eng.build_coef({n: (g * lam if g is not None else 0.0) for n, g in zip(ctx.names, gs)})
-        return _write_grad(ctx, eng, plan, ctx.names, eng.grad_pair), None, None, None, None, None, None
+        return (_write_grad(ctx),) + (None,) * 6
 
 
 class _SegLossTableFn(torch.autograd.Function):
     """the unreduced (B, C-1) / (B, C) table of ONE loss (``reduction="none"``); backward takes the table's gradient"""
 
     @staticmethod
-    def forward(ctx, logits, eng, plan, name):
-        ptr, ld, keep = _as_cl(logits)
-        ctx.eng, ctx.plan, ctx.name, ctx.cl, ctx.shape = eng, plan, name, (ptr, ld, keep), logits.shape
-        if name == "Boundary":
-            ctx.maps = eng.maps
-            eng.boundary_stats(ptr, ld)
-        else:
-            eng.stats(ptr, ld)
+    def forward(ctx, logits, eng, name):
+        ptr, ld = _stash(ctx, logits, eng, None, (name,))
+        eng.stat_passes(ptr, ld, ctx.names)
         return eng.loss_table(name)
 
     @staticmethod
     def backward(ctx, g):
-        eng = ctx.eng
-        ptr, ld, _ = ctx.cl
-        if ctx.name == "Boundary":      # linear in the table: its gradient needs the maps and the table's gradient only
-            eng.build_coef({ctx.name: g})
-            return _write_grad(ctx, eng, None, (ctx.name,), None), None, None, None
-        eng.stats(ptr, ld)              # another entry's forward may have run on the same engine since
-        eng.build_coef({ctx.name: g})
-        B, C = ctx.shape[:2]
-        ldn = (C + 3) // 4 * 4
-        buf = torch.zeros((B, eng.S, ldn), dtype=torch.float32, device=eng.device)
-        eng.grad(ptr, ld, buf.data_ptr(), ldn, nat.F32)
-        return buf[..., :C].permute(0, 2, 1).reshape(ctx.shape), None, None, None
+        eng, name = ctx.eng, ctx.names[0]
+        if name != "Boundary":          # (Boundary is linear in its table: its gradient needs the maps and the table's gradient only)
+            eng.stats(*ctx.cl[:2])      # another entry's forward may have run on the same engine since
+        eng.build_coef({name: g})
+        return _write_grad(ctx), None, None
 
 
 class LossEntry(nn.Module):
@@ -177,13 +154,9 @@ class LossEntry(nn.Module):
             assert target.ndim == input.ndim, "Expected distance maps of the input's rank: (N, C, H, W) or (N, C, H, W, D)"
             eng.set_dist_maps(target)
         else:
-            stash = getattr(target, "_ctseg_labels", None)
-            if stash is not None:
-                eng.set_labels(*stash)
-            else:
-                eng.set_labels_from_i64(target)
+            eng.set_target(target)
         if self.reduction == "none" and self.name not in ("CrossEntropy", "WeightedCrossEntropy"):
-            return _SegLossTableFn.apply(input, eng, None, self.name)
+            return _SegLossTableFn.apply(input, eng, self.name)
         return _SegLossFn.apply(input, eng, None, (self.name,), False, None)[0]
 
     def extra_repr(self):
@@ -219,11 +192,7 @@ class MultipleLossWrapper(nn.Module):
         assert "Boundary" not in self.names or dist_maps is not None, "Distance maps are required for using boundary loss"
         nat.require_gpu(input, "MultipleLossWrapper")
         eng, plan = _engine_for(input)
-        stash = getattr(target, "_ctseg_labels", None)
-        if stash is not None:
-            eng.set_labels(*stash)
-        else:
-            eng.set_labels_from_i64(target)
+        eng.set_target(target)
         self._take_maps(eng, dist_maps)
         if mask_indicator is not None:
             mask_indicator = mask_indicator.type_as(input)
@@ -240,11 +209,8 @@ class MultipleLossWrapper(nn.Module):
         assert "Boundary" not in self.names or dist_maps is not None, "Distance maps are required for using boundary loss"
         nat.require_gpu(input, "MultipleLossWrapper.forward_mixed")
         eng, plan = _engine_for(input, segloss.SegLossPairEngine, "_ctseg_loss_pair")
-        stash = getattr(target, "_ctseg_labels", None)
-        if stash is None:
-            eng.set_labels_from_i64(target)
-            stash = (eng.labels, eng.hist)
-        eng.set_pair(stash[0], stash[1], index)
+        eng.set_target(target)
+        eng.set_pair(eng.labels, eng.hist, index)
         self._take_maps(eng, dist_maps)
         indicators = (None, None)
         if mask_indicator is not None:

@@ -83,7 +83,6 @@ class SegLossEngine:
         self.cw = torch.tensor(CLASS_WEIGHT[:C], dtype=torch.float32, device=device)
         self.cw_eff = torch.ones(C, dtype=torch.float32, device=device)
         self.labels = self.hist = None
-        self.own_dlogits = {}
         self._ce_ready = None        # the `weighted` that prepare_fused_ce last set the tables up for, until a pass uses them
         self._part_head = None       # head_ce's partial records (B, slots, R)
         self.maps = None             # Boundary loss: fp32 distance maps (B, C-1, S) and, once they are set, its tables
@@ -130,6 +129,14 @@ class SegLossEngine:
         self.labels = t.to(torch.uint8).contiguous()
         self.hist = torch.zeros((self.B, self.C), dtype=torch.int64, device=self.device)
         self.hist.scatter_add_(1, t.long(), torch.ones_like(t, dtype=torch.int64))
+
+    def set_target(self, target):
+        """labels of a loss call's ``target``: the (labels u8, hist) the device squash left on it, or built from its int64 map"""
+        stash = getattr(target, "_ctseg_labels", None)
+        if stash is not None:
+            self.set_labels(stash[0], stash[1])
+        else:
+            self.set_labels_from_i64(target)
 
     # ---- passes ----
     def _pass(self, logits_ptr, ld, cw, do_stats, do_grad, coef=None, dl_ptr=None, g_ld=0, gdt=F32, pred=None, part=None):
@@ -210,45 +217,29 @@ class SegLossEngine:
 
     def loss_values(self, names, exclude_missing=False, indicator=None):
         """dict name -> 0-dim fp32 tensor, plus per-loss (B,C) weights used for the gradient tables."""
-        B, C, S = self.B, self.C, self.S
-        P, I, FO, Y = self._tables_for(names)
+        tables = self._tables_for(names)
         out, self._w = {}, {}
         for name in names:
             if name == "CrossEntropy":
                 out[name] = (self.red[:, 0].sum() / self.red[:, 1].sum()).float()
             elif name == "WeightedCrossEntropy":
                 out[name] = (self.red_w[:, 0].sum() / self.red_w[:, 1].sum()).float()
-            elif name in ("Dice", "GeneralizedDice"):
-                if name == "Dice":
-                    f = 1.0 - (2.0 * I + SMOOTH) / (P + Y + SMOOTH)
-                else:
-                    w = self._gdl_w(Y)
-                    f = 1.0 - (2.0 * I * w + SMOOTH) / ((P + Y) * w + SMOOTH)
-                f = f[:, 1:].float()
-                wt = self._mask_weights(name, indicator, exclude_missing, C - 1)       # (B, C-1)
+            else:       # a table loss (KeyError for an unknown name): its entries under the plain mean or the missing-mask weights
+                f = self.loss_table(name, tables)
+                wt = self._mask_weights(name, indicator, exclude_missing, f.shape[1])       # Boundary: the weights Dice gets
                 out[name] = (f * wt).sum()
-                self._w[name] = torch.cat([torch.zeros_like(wt[:, :1]), wt], 1)
-            elif name == "Focal":
-                f = (FO / S).float()
-                wt = self._mask_weights(name, indicator, exclude_missing, C)
-                out[name] = (f * wt).sum()
-                self._w[name] = wt
-            elif name == "Boundary":
-                f = self.loss_table(name)
-                wt = self._mask_weights(name, indicator, exclude_missing, C - 1)       # the weights Dice gets
-                out[name] = (f * wt).sum()
-                self._w[name] = wt
-            else:
-                raise KeyError(name)
+                # the two Dice tables leave the background out: their gradient weights get a zero column for it
+                self._w[name] = torch.cat([torch.zeros_like(wt[:, :1]), wt], 1) if name in ("Dice", "GeneralizedDice") else wt
         return out
 
-    def loss_table(self, name):
+    def loss_table(self, name, tables=None):
         """the unreduced per-(sample, class) table of one loss after ``stats()`` — what the reference's wrapper returns with
         ``reduction="none"`` (capstone/models/losses.py:177-180 builds every entry that way under ``exclude_missing``):
-        Dice / GeneralizedDice (B, C-1) (background excluded), Focal (B, C); Boundary (B, C-1) after ``boundary_stats()``"""
+        Dice / GeneralizedDice (B, C-1) (background excluded), Focal (B, C); Boundary (B, C-1) after ``boundary_stats()``.
+        ``tables``: what ``_tables()`` returned, when the caller holds it already"""
         if name == "Boundary":
             return (self.b_red[:, self._b_side] / self.S).float()           # models/losses.py:146: the mean over (H, W)
-        P, I, FO, Y = self._tables()
+        P, I, FO, Y = tables or self._tables()
         if name == "Dice":
             return (1.0 - (2.0 * I + SMOOTH) / (P + Y + SMOOTH))[:, 1:].float()
         if name == "GeneralizedDice":
@@ -331,17 +322,33 @@ class SegLossEngine:
     def grad(self, logits_ptr, ld, dl_ptr, g_ld, gdt):
         self._pass(logits_ptr, ld, self.cw_eff, False, True, self.coef, dl_ptr, g_ld, gdt)
 
-    # ---- Dice metric from exact integer counts (models/metrics.py:15-21, temp.py:173-292) ----
-    def dice_metric(self, cnt=None):
-        cnt = self.cnt if cnt is None else cnt
-        inter, pred, true = (cnt[:, i, 1:].float() for i in range(3))
-        nan = torch.full_like(inter, float("nan"))
-        score = torch.where(true > 0, 2.0 * inter / (true + pred), nan)      # (B, 9), NaN where truth empty
-        ok = (~torch.isnan(score)).float()
-        score = torch.nan_to_num(score, nan=0.0)
-        n_ok = ok.sum(dim=0)
-        per_class = torch.where(n_ok > 0, score.sum(dim=0) / n_ok, torch.zeros_like(n_ok))   # "mean_batch"
-        return per_class.mean(), per_class
+    # ---- the loss sequence: stat_passes -> loss_values -> build_coef -> grad_passes ----
+    _label_stats, _label_grad = stats, grad      # the label losses' pass of each half (SegLossPairEngine: its two-target pass)
+
+    def stat_passes(self, logits_ptr, ld, names, count_dice=False):
+        """the statistics passes ``names`` need.  ``count_dice``: the label pass runs for a Boundary-only recipe too (a training
+        step takes its Dice counts from it)"""
+        if count_dice or any(n != "Boundary" for n in names):
+            self._label_stats(logits_ptr, ld, weighted_too="WeightedCrossEntropy" in names)
+        if "Boundary" in names:
+            self.boundary_stats(logits_ptr, ld)
+
+    def loss_forward(self, logits_ptr, ld, names, exclude_missing=False, indicator=None, count_dice=False):
+        """``stat_passes`` and then ``loss_values``"""
+        self.stat_passes(logits_ptr, ld, names, count_dice)
+        return self.loss_values(names, exclude_missing, indicator)
+
+    def grad_passes(self, logits_ptr, ld, names, dl_ptr, g_ld, gdt):
+        """one gradient row per voxel from the tables ``build_coef`` filled: the label losses' pass stores it and the Boundary
+        pass adds to it, or the Boundary pass stores when it is the only name"""
+        others = any(n != "Boundary" for n in names)
+        if others:
+            self._label_grad(logits_ptr, ld, dl_ptr, g_ld, gdt)
+        if "Boundary" in names:
+            self.boundary_grad(logits_ptr, ld, dl_ptr, g_ld, gdt, accumulate=others)
+
+    def dice_metric(self):
+        return dice_metric(self.cnt)
 
 
 class SegLossPairEngine(SegLossEngine):
@@ -403,6 +410,21 @@ class SegLossPairEngine(SegLossEngine):
     def grad_pair(self, logits_ptr, ld, dl_ptr, g_ld, gdt):
         """d(sum over both sides)/d(logits) from coef2 / cw2, which build_coef filled inside ``side(0)`` and ``side(1)``"""
         self._pass_pair(logits_ptr, ld, self.cw2, True, dl_ptr, g_ld, gdt)
+
+    _label_stats, _label_grad = stats_pair, grad_pair
+
+
+def dice_metric(cnt):
+    """(mean Dice, Dice per class (C-1,)) from exact integer counts (B, 3, C) = |pred == c & true == c|, |pred == c|, |true == c|
+    (models/metrics.py:15-21, temp.py:173-292)"""
+    inter, pred, true = (cnt[:, i, 1:].float() for i in range(3))
+    nan = torch.full_like(inter, float("nan"))
+    score = torch.where(true > 0, 2.0 * inter / (true + pred), nan)      # (B, 9), NaN where truth empty
+    ok = (~torch.isnan(score)).float()
+    score = torch.nan_to_num(score, nan=0.0)
+    n_ok = ok.sum(dim=0)
+    per_class = torch.where(n_ok > 0, score.sum(dim=0) / n_ok, torch.zeros_like(n_ok))   # "mean_batch"
+    return per_class.mean(), per_class
 
 
 def dice_counts(pred_u8, true_u8, C=N_CLASSES):

@@ -12,18 +12,19 @@ The Boundary loss is opt-in: ``device_boundary=True`` takes the batch's fourth e
 and a ``"Boundary"`` entry raise.  Not carried over (outside the hot path): the W&B logger patch, which raises
 instead of silently doing something else.  Mixup is ``training/mixup_trainer.py``.
 """
-from argparse import ArgumentParser
+import inspect
 from typing import List
 
 import torch
 
-from .. import STRUCTURES
 from ..models import DiceMetricWrapper, MultipleLossWrapper, UNet
-from ..volumetric.base_trainer import _Base, _DataParallelSurface, _precision, pl
+from .module_base import _TrainerBase, _precision
 from .utils import _squash_masks, _squash_predictions
 
 
-class BaseUNet2D(_DataParallelSurface, _Base):
+class BaseUNet2D(_TrainerBase):
+    RES_UNITS = 2       # residual subunits per level under ``use_res_units``
+
     def __init__(self, filters: List = [64, 128, 256, 512, 1024], use_res_units: bool = False, downsample: bool = False,
                  lr: float = 1e-3, loss_fx: list = ["Focal", "Dice"], exclude_missing: bool = False, device_boundary: bool = False,
                  **kwargs) -> None:
@@ -32,11 +33,7 @@ class BaseUNet2D(_DataParallelSurface, _Base):
         assert len(filters) == 5, "This module requires a standard 5 block UNet specification"
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()
-        names = ("batch_size", "transform_degree", "filters", "use_res_units", "downsample", "lr", "loss_fx", "exclude_missing")
-        if pl is not None:
-            self.save_hyperparameters(*names)
-        else:
-            self.save_hyperparameters(*names, frame_locals=dict(locals()))
+        self.save_hyperparameters(*self.HPARAMS, frame=inspect.currentframe())
         self._precision = _precision(kwargs)
         # reference :53 builds this 3->1 convolution whatever ``downsample`` says, so its two tensors are in every reference
         # checkpoint: kept as a parameter container for state_dict interchange
@@ -46,14 +43,10 @@ class BaseUNet2D(_DataParallelSurface, _Base):
         self.loss_func = MultipleLossWrapper(losses=loss_fx, exclude_missing=exclude_missing, device_boundary=device_boundary)
         self.dice_score = DiceMetricWrapper()
 
-    @property
-    def _n_classes(self):
-        return len(STRUCTURES) + 1
-
     def _construct_model(self):
         in_channels = 1 if (self.hparams.downsample or (self.hparams.get("transform_degree") in (0, None))) else 3
         return UNet(dimensions=2, in_channels=in_channels, out_channels=self._n_classes, channels=self.hparams.filters,
-                    strides=[2, 2, 2, 2], num_res_units=(2 if self.hparams.use_res_units else 0), precision=self._precision)
+                    strides=[2, 2, 2, 2], num_res_units=(self.RES_UNITS if self.hparams.use_res_units else 0), precision=self._precision)
 
     def forward(self, x):
         if self.hparams.downsample:
@@ -81,17 +74,9 @@ class BaseUNet2D(_DataParallelSurface, _Base):
         prediction._ctseg_plan = self.unet.engine().last_plan if prediction.requires_grad else None
         loss_dict = self.loss_func(input=prediction, target=masks, mask_indicator=mask_indicator, dist_maps=dist_maps)
         total_loss = torch.stack(list(loss_dict.values())).sum()
-        for name, loss_value in loss_dict.items():
-            self.log(f"{name} Loss ({prefix})", loss_value, on_step=False, on_epoch=True)
+        self._log_losses(prefix, loss_dict)
         self._log_dice_scores(prediction, masks, mask_indicator, prefix)
         return images, masks, mask_indicator, prediction, total_loss
-
-    def _split_batch(self, batch):
-        """(images, masks, mask_indicator, dist_maps or None), reference :98-101; a fourth element needs ``device_boundary``"""
-        images, masks, mask_indicator, *dist_maps = batch
-        if dist_maps and not self.device_boundary:
-            raise NotImplementedError("distance maps (Boundary loss) are outside the MI355X hot path unless device_boundary=True")
-        return images, masks, mask_indicator, (dist_maps[0] if dist_maps else None)
 
     def _log_dice_scores(self, prediction, masks, mask_indicator, prefix):
         with torch.no_grad():
@@ -102,9 +87,7 @@ class BaseUNet2D(_DataParallelSurface, _Base):
             pred = _squash_predictions(pred)
             dice_mean, dice_per_class = self.dice_score(pred, masks)
             self._keep_dice_counts(self.dice_score.last_counts, prefix)
-            for structure, score in zip(STRUCTURES, dice_per_class):
-                self.log(f"{structure} Dice ({prefix})", score, on_step=False, on_epoch=True)
-            self.log(f"Mean Dice Score ({prefix})", dice_mean, on_step=False, on_epoch=True)
+            self._log_dice(prefix, dice_mean, dice_per_class)
 
     def configure_optimizers(self):
         from ..optim import Adam            # a torch.optim.Adam whose step() is one launch for the U-Net's flat parameter buffer
@@ -115,17 +98,5 @@ class BaseUNet2D(_DataParallelSurface, _Base):
     @staticmethod
     def add_model_specific_args(parent_parser):
         """Same flags and defaults as reference :150-210."""
-        parser = ArgumentParser(parents=[parent_parser], add_help=False)
-        parser.add_argument("--batch_size", type=int, default=128, help="Slices per optimizer step")
-        parser.add_argument("--transform_degree", type=int, default=0,
-                            help="Augmentation preset index (0 = none)")
-        parser.add_argument("--filters", nargs=5, type=int, default=[64, 128, 256, 512, 1024],
-                            help="Channel widths of the five encoder levels")
-        parser.add_argument("--use_res_units", action="store_true", default=False, help="Build the U-Net from residual units")
-        parser.add_argument("--downsample", action="store_true", default=False,
-                            help="Reduce a 3-channel input to 1 channel with a 1x1 convolution before the U-Net")
-        parser.add_argument("--lr", type=float, default=1e-3, help="Adam step size")
-        parser.add_argument("--loss_fx", nargs="+", type=str, default=["Focal", "Dice"], help="One or more loss names, summed")
-        parser.add_argument("--exclude_missing", action="store_true", default=False,
-                            help="Weight per-class loss terms by annotation availability (AnatomyNet)")
-        return parser
+        return _TrainerBase._model_args(parent_parser, batch_size=128, batch_size_help="Slices per optimizer step",
+                                        loss_fx=["Focal", "Dice"])

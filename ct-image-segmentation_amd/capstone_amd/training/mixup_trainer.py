@@ -9,18 +9,13 @@ the base class's.  Distance maps (Boundary loss) need ``device_boundary=True`` a
 """
 import torch
 
-from .. import STRUCTURES, segloss
-from ..models import UNet
+from .. import segloss
 from .base_trainer import BaseUNet2D
 from .utils import _squash_masks, _squash_predictions, mixup_tensors, weighted_mixup
 
 
 class MixupUNet2D(BaseUNet2D):
-    def _construct_model(self):
-        """1 residual unit works better for mixup (reference :27)."""
-        in_channels = 1 if (self.hparams.downsample or (self.hparams.get("transform_degree") in (0, None))) else 3
-        return UNet(dimensions=2, in_channels=in_channels, out_channels=self._n_classes, channels=self.hparams.filters,
-                    strides=[2, 2, 2, 2], num_res_units=(1 if self.hparams.use_res_units else 0), precision=self._precision)
+    RES_UNITS = 1       # 1 residual unit works better for mixup (reference :27)
 
     def validation_step(self, batch, batch_idx=0):
         """Mixup is used only while training and not during validation/testing."""
@@ -40,8 +35,7 @@ class MixupUNet2D(BaseUNet2D):
         loss_dict = self.loss_func.forward_mixed(input=prediction, target=masks, index=shuffle_index, lambda_=lambda_,
                                                  mask_indicator=mask_indicator, dist_maps=dist_maps)
         total_loss = torch.stack(list(loss_dict.values())).sum()
-        for name, loss_value in loss_dict.items():
-            self.log(f"{name} Loss ({prefix})", loss_value, on_step=False, on_epoch=True)
+        self._log_losses(prefix, loss_dict)
         self._log_mixed_dice_scores(prediction, masks, mask_indicator, shuffle_index, lambda_, prefix)
         return images, masks, mask_indicator, prediction, total_loss
 
@@ -54,11 +48,9 @@ class MixupUNet2D(BaseUNet2D):
                          ((masks, mask_indicator), (masks[shuffle_index], mask_indicator[shuffle_index]))]
             else:
                 cnt = self.loss_func.last_mixed_counts
-                sides = [segloss.SegLossEngine.dice_metric(None, cnt[:, s]) for s in (0, 1)]      # (takes no state with given counts)
+                sides = [segloss.dice_metric(cnt[:, s]) for s in (0, 1)]
             (mean_a, per_a), (mean_b, per_b) = sides
-            for structure, score_a, score_b in zip(STRUCTURES, per_a, per_b):
-                self.log(f"{structure} Dice ({prefix})", mixup_tensors(score_a, score_b, lambda_), on_step=False, on_epoch=True)
-            self.log(f"Mean Dice Score ({prefix})", mixup_tensors(mean_a, mean_b, lambda_), on_step=False, on_epoch=True)
+            self._log_dice(prefix, mixup_tensors(mean_a, mean_b, lambda_), mixup_tensors(per_a, per_b, lambda_))
 
     def _masked_dice(self, pred, target, indicator):
         pred = pred.clone()

@@ -7,174 +7,25 @@ Works as a ``pytorch_lightning.LightningModule`` when Lightning is importable an
 reproduces Lightning 1.0's per-batch order (zero_grad -> training_step -> backward -> [DDP mean of
 gradients] -> Adam.step) without autograd, and is what bench.py times.
 """
-from argparse import ArgumentParser
+import inspect
 from typing import List
 
 import torch
-import torch.nn as nn
 
-from .. import STRUCTURES, segloss
+from .. import segloss
 from .. import _native as nat
 from ..models import UNet
 from ..models.losses import _as_cl
+from ..training.module_base import _TrainerBase, _precision, pl
 from ..training.utils import _squash_predictions  # noqa: F401  (same import the reference has)
 from .losses import MultipleLossWrapper3D
 from .metrics import DiceMetricWrapper3D
 from .utils import _squash_masks_3D
 
-try:  # pragma: no cover - Lightning is absent from the build image
-    import pytorch_lightning as pl
-    _Base = pl.LightningModule
-except Exception:  # noqa: BLE001
-    pl = None
-
-    class _HParams(dict):
-        __getattr__ = dict.__getitem__
-
-    class _Base(nn.Module):
-        """The slice of LightningModule the reference's module uses."""
-
-        def __init__(self):
-            super().__init__()
-            self.hparams = _HParams()
-            self.logged = {}
-            self._epoch = {}
-
-        def save_hyperparameters(self, *names, frame_locals=None):
-            for n in names:
-                self.hparams[n] = frame_locals.get(n, frame_locals.get("kwargs", {}).get(n))
-
-        def log(self, name, value, on_step=False, on_epoch=True, **kw):
-            """``logged[name]`` = the value of the last step; with ``on_epoch=True`` (what the reference passes everywhere,
-            volumetric/base_trainer.py:106-109,125-131) the value also enters a running sum whose mean over the steps of the
-            epoch is what Lightning 1.0 reports (``epoch_means``)."""
-            v = value.detach() if torch.is_tensor(value) else value
-            self.logged[name] = v
-            if on_epoch:
-                acc = self._epoch.get(name)
-                if acc is None:
-                    self._epoch[name] = [v.clone() if torch.is_tensor(v) else v, 1]
-                else:
-                    acc[0] = acc[0] + v
-                    acc[1] += 1
-
-        def log_packed(self, packed, layout):
-            """several logged values that are slices of ONE small device tensor (the native step's loss / Dice summary):
-            one accumulate for all of them instead of one tiny launch per name.  layout: [(name, index or slice)]"""
-            packed = packed.detach()
-            for name, sl in layout:
-                self.logged[name] = packed[sl]
-            key = ("packed",) + tuple(n for n, _ in layout)
-            acc = self._epoch.get(key)
-            if acc is None:
-                self._epoch[key] = [packed.clone(), 1, layout]
-            else:
-                acc[0] += packed
-                acc[1] += 1
-
-        def epoch_means(self, reset=True):
-            """{name: mean over the steps logged since the last reset} — Lightning's ``on_epoch=True`` reduction"""
-            out = {}
-            for k, acc in self._epoch.items():
-                if isinstance(k, tuple):
-                    mean = acc[0] / acc[1]
-                    out.update({name: mean[sl] for name, sl in acc[2]})
-                else:
-                    out[k] = acc[0] / acc[1]
-            if reset:
-                self._epoch = {}
-            return out
-
-        @property
-        def device(self):
-            return next(self.parameters()).device
-
 SEED = 12342
 
 
-class _DataParallelSurface:
-    """What both drop-in modules (BaseUNet3D, BaseUNet2D) need so that the reference's ONLY way into multi-GPU training —
-    ``Trainer.from_argparse_args(args)`` with ``--gpus N --distributed_backend ddp`` (capstone/volumetric/base_trainer.py:196,217;
-    capstone/training/base_trainer.py: the same Trainer flags) — lands on the engine's own gradient exchange."""
-
-    # ---- the gradient reducer lives on the engine (plan.Engine.reducer): one object for every route into the backward ----
-    @property
-    def reducer(self):
-        return self.unet.engine().reducer
-
-    @reducer.setter
-    def reducer(self, value):
-        self.unet.engine().reducer = value
-
-    def configure_ddp(self, model, device_ids):
-        """Lightning 1.0 hook (``LightningModule.configure_ddp(model, device_ids)``, called by the DDP accelerator once the process
-        group exists and the module sits on its GPU; stock: ``LightningDistributedDataParallel(model, device_ids, ...)``).  Here:
-        build the flat parameter store on the module's device, make the replicas identical and install the flat-buffer gradient
-        exchange (``distributed.attach``), and return a pass-through wrapper with DDP's ``.module`` / per-mode ``forward``."""
-        from .. import distributed as cdist
-        dev = next(model.unet.parameters()).device
-        model.unet.engine().ensure(dev)
-        cdist.attach(model)
-        return cdist.NativeDataParallel(model, device_ids)
-
-    @property
-    def _ddp_params_and_buffers_to_ignore(self):
-        """torch's ``DistributedDataParallel.__init__`` probes the wrapped module for this attribute: the probe is the tripwire.
-        A stock DDP wrap would train on rank-local gradients without any error (its reducer waits for AccumulateGrad hooks that
-        never fire: the HIP kernels write the flat gradient buffer and the autograd nodes return None for the parameters)."""
-        raise nat.NativeError(
-            "torch.nn.parallel.DistributedDataParallel cannot wrap this module: its gradients are written into one flat buffer by "
-            "the HIP backward kernels and averaged by capstone_amd.distributed.attach(module). Under Lightning the module's own "
-            "configure_ddp() does that; in a hand-written loop call attach(module) after init_process_group and skip the DDP wrap.")
-
-    # ---- Dice across ranks (SURVEY.md §8e: the integer counts, one small all-gather at epoch end) -------------------------
-    def _keep_dice_counts(self, cnt, prefix):
-        """remember this step's per-sample integer Dice counts (B, 3, C) when the module is data-parallel (or on request,
-        ``CTSEG_KEEP_DICE_COUNTS=1``): 30 int64 per sample and step"""
-        import os
-        red = self.unet.engine().reducer
-        if (red is not None and red.world > 1) or os.environ.get("CTSEG_KEEP_DICE_COUNTS") == "1":
-            self.__dict__.setdefault("_dice_counts", {}).setdefault(prefix, []).append(cnt.detach().clone())
-
-    def epoch_dice_across_ranks(self, prefix="train", reset=True, group=None):
-        """(mean Dice, per-class Dice (9,)) of the epoch as the reference computes it on the GLOBAL batch: per step, the
-        per-sample counts of all ranks are one batch for ``compute_meandice`` + ``do_metric_reduction("mean_batch")``
-        (capstone/models/temp.py:173-292, capstone/models/metrics.py:15-21); the epoch value is the mean over the steps
-        (Lightning's ``on_epoch=True``).  The reference itself logs per rank (no ``sync_dist``, :106-109,125-131); this is the
-        figure "Dice vs ref" is read from at N > 1.  One all-gather of (steps, B, 3, C) int64.  None when nothing was kept."""
-        from .. import distributed as cdist
-        kept = self.__dict__.get("_dice_counts", {}).get(prefix)
-        if not kept:
-            return None
-        if len({tuple(k.shape) for k in kept}) == 1:
-            cnt = list(cdist.gather_dice_counts(torch.stack(kept), group))  # ONE collective: (steps, world * B, 3, C)
-        else:                                                               # a short last batch: one small collective per step
-            cnt = [cdist.gather_dice_counts(k, group) for k in kept]
-        if reset:
-            self._dice_counts[prefix] = []
-        eng = segloss.SegLossEngine.__new__(segloss.SegLossEngine)
-        per_step = [segloss.SegLossEngine.dice_metric(eng, c) for c in cnt]
-        mean = torch.stack([m for m, _ in per_step]).mean()
-        per_class = torch.stack([p for _, p in per_step]).mean(dim=0)
-        return mean, per_class
-
-
-def _precision(kwargs):
-    """Lightning's Trainer flag arrives through **vars(args) too.  ``--precision 16`` is IEEE half, as in the reference's stack
-    (Lightning 1.0 native AMP): fp16 STORAGE for the inference passes (validation / test / sliding window), and bf16 storage
-    for the training plans after a one-time RuntimeWarning (plan.Engine.train_dt: no fp16 backward kernels, no loss scaling;
-    bf16 has fp32's range).  "bf16" by name uses bf16 throughout.  Nothing is remapped silently."""
-    p = kwargs.get("precision", "fp32")
-    if p in (16, "16", "fp16", "16-mixed", "16-true"):
-        return "fp16"
-    if p in ("bf16", "bf16-mixed", "bf16-true"):
-        return "bf16"
-    if p in (32, "32", "fp32", "32-true", None):
-        return "fp32"
-    raise ValueError(f"unsupported precision {p!r}")
-
-
-class BaseUNet3D(_DataParallelSurface, _Base):
+class BaseUNet3D(_TrainerBase):
     def __init__(self, filters: List = [16, 32, 64, 128, 256], use_res_units: bool = False, downsample: bool = False,
                  lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
                  **kwargs) -> None:
@@ -183,20 +34,12 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
-        names = ("batch_size", "transform_degree", "filters", "use_res_units", "downsample", "lr", "loss_fx", "exclude_missing")
-        if pl is not None:
-            self.save_hyperparameters(*names)
-        else:
-            self.save_hyperparameters(*names, frame_locals=dict(locals()))
+        self.save_hyperparameters(*self.HPARAMS, frame=inspect.currentframe())
         self._precision = _precision(kwargs)
         self.unet = self._construct_model()
         self.device_boundary = device_boundary      # (a switch of this port, not a reference hyperparameter: kept out of hparams)
         self.loss_func = MultipleLossWrapper3D(losses=loss_fx, exclude_missing=exclude_missing, device_boundary=device_boundary)
         self.dice_score = DiceMetricWrapper3D()
-
-    @property
-    def _n_classes(self):
-        return len(STRUCTURES) + 1
 
     def _construct_model(self):
         # reference :58-72 — in_channels=1, strides for a 5-entry filter list, num_res_units hard-wired to 2
@@ -218,13 +61,6 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         _, _, _, _, loss = self._shared_step(batch, is_training=True)
         return loss
 
-    def _split_batch(self, batch):
-        """(images, masks, mask_indicator, dist_maps or None); a fourth element needs ``device_boundary``, as in BaseUNet2D"""
-        images, masks, mask_indicator, *dist_maps = batch
-        if dist_maps and not self.device_boundary:
-            raise NotImplementedError("distance maps (Boundary loss) are outside the MI355X hot path unless device_boundary=True")
-        return images, masks, mask_indicator, (dist_maps[0] if dist_maps else None)
-
     def _ce_only(self):
         names = list(self.loss_func.names)
         return len(names) == 1 and names[0] in ("CrossEntropy", "WeightedCrossEntropy")
@@ -234,35 +70,42 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         return (torch.is_grad_enabled() and self._ce_only() and os.environ.get("CTSEG_DROPIN_FUSED", "1") != "0"
                 and any(p.requires_grad for p in self.unet.parameters()))
 
+    def _labels_then_forward(self, plan, images, masks, side_work=None, skip_head=False):
+        """The plan's loss engine, found or built, with this batch's labels, and the forward pass: (loss engine, logits).  The
+        label map is not needed before the loss: where the plan has a side stream the masks are squashed there — and
+        ``side_work(loss engine)``, work that needs only the labels, runs behind them — while the forward pass starts."""
+        le = getattr(plan, "_ctseg_loss", None)
+        if le is None:
+            le = plan._ctseg_loss = segloss.SegLossEngine(images.device, images.shape[0], plan.logits.S, self._n_classes)
+        side = plan.side_stream()
+        if side is None:
+            lab_u8, _, hist = segloss.squash_masks(masks, self._n_classes, want_i64=False)
+            le.set_labels(lab_u8, hist)
+            return le, plan.forward(images, skip_head=skip_head)
+        main = torch.cuda.current_stream(images.device)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            lab_u8, _, hist = segloss.squash_masks(masks, self._n_classes, want_i64=False)
+            le.set_labels(lab_u8, hist)
+            if side_work is not None:
+                side_work(le)
+        for t in (lab_u8, hist):
+            t.record_stream(main)
+        logits = plan.forward(images, skip_head=skip_head)
+        main.wait_stream(side)
+        return le, logits
+
     def _forward_and_ce(self, batch, keep_logits):
         """squash masks (side stream) -> forward -> cross-entropy + Dice counts + d loss / d logits for an upstream gradient of 1.
         Returns (engine, plan, loss engine, weighted)."""
         images, masks, mask_indicator, _ = self._split_batch(batch)     # (cross-entropy only: the maps are not read)
         eng = self.unet.engine()
         plan = eng.plan_for(images)
-        side = plan.side_stream()
-        le = getattr(plan, "_ctseg_loss", None)
-        if le is None:
-            le = plan._ctseg_loss = segloss.SegLossEngine(images.device, images.shape[0], plan.logits.S, self._n_classes)
         weighted = self.loss_func.names[0] != "CrossEntropy"
         head_slots = 0 if keep_logits else plan.head_ce_slots(self._n_classes)
-        if side is not None:
-            # the label map is not needed before the loss: squash the masks (and build the loss tables that need only the label
-            # histogram) on the side stream while the forward pass starts
-            main = torch.cuda.current_stream(images.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                lab_u8, _, hist = segloss.squash_masks(masks, self._n_classes, want_i64=False)
-                le.set_labels(lab_u8, hist)
-                le.prepare_fused_ce(weighted=weighted)
-            for t in (lab_u8, hist):
-                t.record_stream(main)
-            logits = plan.forward(images, skip_head=head_slots > 0)
-            main.wait_stream(side)
-        else:
-            lab_u8, _, hist = segloss.squash_masks(masks, self._n_classes, want_i64=False)
-            le.set_labels(lab_u8, hist)
-            logits = plan.forward(images, skip_head=head_slots > 0)
+        # (side stream: also the loss tables that need only the label histogram)
+        le, logits = self._labels_then_forward(plan, images, masks, side_work=lambda le: le.prepare_fused_ce(weighted=weighted),
+                                               skip_head=head_slots > 0)
         dl = plan.dlogits
         if head_slots > 0:
             le.head_ce(plan._head_ce[2], head_slots, dl.ptr(), dl.ld, weighted=weighted)
@@ -275,14 +118,10 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         name = self.loss_func.names[0]
         loss, dm, dpc = le.ce_summary(weighted=weighted)
         if pl is None:
-            self.log_packed(le.last_summary, [(f"{name} Loss ({prefix})", 0), (f"Mean Dice Score ({prefix})", 1),
-                                              (f"Dice per class ({prefix})", slice(2, None))] +
-                            [(f"{s_} Dice ({prefix})", 2 + i) for i, s_ in enumerate(STRUCTURES)])
-        else:   # Lightning logs scalars: one entry per structure, as the reference's _log_dice_scores does (:125-129)
-            self.log(f"{name} Loss ({prefix})", loss, on_step=False, on_epoch=True)
-            for structure, score in zip(STRUCTURES, dpc):
-                self.log(f"{structure} Dice ({prefix})", score, on_step=False, on_epoch=True)
-            self.log(f"Mean Dice Score ({prefix})", dm, on_step=False, on_epoch=True)
+            self.log_packed(le.last_summary, self._summary_layout(name, prefix))
+        else:   # Lightning logs scalars
+            self._log_losses(prefix, {name: loss})
+            self._log_dice(prefix, dm, dpc)
         return loss
 
     def _fused_training_step(self, batch):
@@ -307,8 +146,7 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         prediction._ctseg_plan = self.unet.engine().last_plan
         loss_dict = self.loss_func(input=prediction, target=masks, mask_indicator=mask_indicator, dist_maps=dist_maps)
         total_loss = torch.stack(list(loss_dict.values())).sum()
-        for name, loss_value in loss_dict.items():
-            self.log(f"{name} Loss ({prefix})", loss_value, on_step=False, on_epoch=True)
+        self._log_losses(prefix, loss_dict)
         self._log_dice_scores(prediction, masks, mask_indicator, prefix)
         return images, masks, mask_indicator, prediction, total_loss
 
@@ -328,9 +166,7 @@ class BaseUNet3D(_DataParallelSurface, _Base):
                 eng.stats(ptr, ld)
             dice_mean, dice_per_class = eng.dice_metric()
             self._keep_dice_counts(eng.cnt, prefix)
-            for structure, score in zip(STRUCTURES, dice_per_class):
-                self.log(f"{structure} Dice ({prefix})", score, on_step=False, on_epoch=True)
-            self.log(f"Mean Dice Score ({prefix})", dice_mean, on_step=False, on_epoch=True)
+            self._log_dice(prefix, dice_mean, dice_per_class)
 
     # ---- native step: what Lightning's loop does per batch, without autograd -------------------------
     def fit_step(self, batch, betas=(0.9, 0.999), eps=1e-8, keep_logits=True):
@@ -341,45 +177,22 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         nat.require_gpu(images, "fit_step")
         names = list(self.loss_func.names)
         ce_only = self._ce_only()
-        boundary, others = "Boundary" in names, any(n != "Boundary" for n in names)
-        assert not boundary or dist_maps is not None, "Distance maps are required for using boundary loss"
+        assert "Boundary" not in names or dist_maps is not None, "Distance maps are required for using boundary loss"
         vals = None
         if ce_only:
             eng, plan, le, weighted = self._forward_and_ce(batch, keep_logits)
         else:
             eng = self.unet.engine()
             plan = eng.plan_for(images)
-            side = plan.side_stream()
-            le = getattr(plan, "_ctseg_loss", None)
-            if le is None:
-                le = plan._ctseg_loss = segloss.SegLossEngine(images.device, images.shape[0], plan.logits.S, self._n_classes)
-            if side is not None:
-                main = torch.cuda.current_stream(images.device)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    lab_u8, _, hist = segloss.squash_masks(masks, self._n_classes, want_i64=False)
-                    le.set_labels(lab_u8, hist)
-                for t in (lab_u8, hist):
-                    t.record_stream(main)
-                logits = plan.forward(images)
-                main.wait_stream(side)
-            else:
-                lab_u8, _, hist = segloss.squash_masks(masks, self._n_classes, want_i64=False)
-                le.set_labels(lab_u8, hist)
-                logits = plan.forward(images)
+            le, logits = self._labels_then_forward(plan, images, masks)
             dl = plan.dlogits
-            if boundary:
+            if "Boundary" in names:
                 le.set_dist_maps(dist_maps)
-            # (always: the step's Dice counts come from the label pass, as in _SegLossPairFn)
-            le.stats(logits.ptr(), logits.ld, weighted_too="WeightedCrossEntropy" in names)
-            if boundary:
-                le.boundary_stats(logits.ptr(), logits.ld)
-            vals = le.loss_values(names, self.loss_func.exclude_missing, mask_indicator.float())
+            # (count_dice: the step's Dice counts come from the label pass, as in _SegLossPairFn)
+            vals = le.loss_forward(logits.ptr(), logits.ld, names, self.loss_func.exclude_missing, mask_indicator.float(),
+                                   count_dice=True)
             le.build_coef({n: 1.0 for n in names})
-            if others:      # the order of models.losses._write_grad: the label losses store, the Boundary pass adds
-                le.grad(logits.ptr(), logits.ld, dl.ptr(), dl.ld, plan.dt)
-            if boundary:
-                le.boundary_grad(logits.ptr(), logits.ld, dl.ptr(), dl.ld, plan.dt, accumulate=others)
+            le.grad_passes(logits.ptr(), logits.ld, names, dl.ptr(), dl.ld, plan.dt)
         book = {}
 
         def bookkeeping():     # scalar-sized work: queued behind the backward pass, beside the side stream's tail
@@ -406,18 +219,10 @@ class BaseUNet3D(_DataParallelSurface, _Base):
         vals, total = book["vals"], book["total"]
         dice_mean, dice_per_class = book["dice"]
         if "packed" in book and pl is None:
-            self.log_packed(book["packed"], [(f"{names[0]} Loss (train)", 0), ("Mean Dice Score (train)", 1),
-                                             ("Dice per class (train)", slice(2, None))] +
-                            [(f"{s_} Dice (train)", 2 + i) for i, s_ in enumerate(STRUCTURES)])
+            self.log_packed(book["packed"], self._summary_layout(names[0], "train"))
         else:
-            for n in names:
-                self.log(f"{n} Loss (train)", vals[n], on_step=False, on_epoch=True)
-            self.log("Mean Dice Score (train)", dice_mean, on_step=False, on_epoch=True)
-            if pl is None:
-                self.log("Dice per class (train)", dice_per_class, on_step=False, on_epoch=True)
-            else:   # Lightning logs scalars: one entry per structure, as the reference's _log_dice_scores does (:125-129)
-                for structure, score in zip(STRUCTURES, dice_per_class):
-                    self.log(f"{structure} Dice (train)", score, on_step=False, on_epoch=True)
+            self._log_losses("train", vals)
+            self._log_dice("train", dice_mean, dice_per_class, native=True)
         return total
 
     # ---- optimizer state of the native step, in torch.optim.Adam's own state_dict layout ------------------------------
@@ -480,18 +285,6 @@ class BaseUNet3D(_DataParallelSurface, _Base):
 
     @staticmethod
     def add_model_specific_args(parent_parser):
-        """Same flags and defaults as reference :134-182."""
-        parser = ArgumentParser(parents=[parent_parser], add_help=False)
-        parser.add_argument("--batch_size", type=int, default=1, help="Volumes per optimizer step")
-        parser.add_argument("--transform_degree", type=int, default=0,
-                            help="Augmentation preset index (0 = none)")
-        parser.add_argument("--filters", nargs=5, type=int, default=[64, 128, 256, 512, 1024],
-                            help="Channel widths of the five encoder levels")
-        parser.add_argument("--use_res_units", action="store_true", default=False, help="Build the U-Net from residual units")
-        parser.add_argument("--downsample", action="store_true", default=False,
-                            help="Reduce a 3-channel input to 1 channel with a 1x1 convolution before the U-Net")
-        parser.add_argument("--lr", type=float, default=1e-3, help="Adam step size")
-        parser.add_argument("--loss_fx", nargs="+", type=str, default="CrossEntropy", help="One or more loss names, summed")
-        parser.add_argument("--exclude_missing", action="store_true", default=False,
-                            help="Weight per-class loss terms by annotation availability (AnatomyNet)")
-        return parser
+        """Same flags and defaults as reference :134-182 (the ``--loss_fx`` default a string, as there)."""
+        return _TrainerBase._model_args(parent_parser, batch_size=1, batch_size_help="Volumes per optimizer step",
+                                        loss_fx="CrossEntropy")

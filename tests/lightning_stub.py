@@ -117,8 +117,9 @@ def seed_everything(seed):
 
 
 def install():
-    """register the stand-in as ``pytorch_lightning`` — BEFORE capstone_amd.volumetric.base_trainer is imported"""
-    assert "capstone_amd.volumetric.base_trainer" not in sys.modules, "install() must run before the product module is imported"
+    """register the stand-in as ``pytorch_lightning`` — BEFORE capstone_amd.training.module_base (which picks the modules' base
+    class) is imported, by a trainer module or on its own"""
+    assert "capstone_amd.training.module_base" not in sys.modules, "install() must run before the product module is imported"
     m = types.ModuleType("pytorch_lightning")
     m.LightningModule, m.seed_everything, m.__version__ = LightningModule, seed_everything, "1.0.0-stub"
     m.Trainer = type("Trainer", (), {})

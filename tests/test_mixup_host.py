@@ -162,7 +162,7 @@ def test_forward_mixed_matches_the_oracle(emu, exclude_missing):
     pred = OM.squash_predictions(logits)
     for s, t in enumerate((target, target[index])):
         mean, per = OM.DiceMetric()(pred, t)
-        got_mean, got_per = segloss.SegLossEngine.dice_metric(None, wrap.last_mixed_counts[:, s])
+        got_mean, got_per = segloss.dice_metric(wrap.last_mixed_counts[:, s])
         np.testing.assert_allclose(got_per.numpy(), per.numpy(), atol=1e-6)
         np.testing.assert_allclose(got_mean.item(), mean.item(), atol=1e-6)
     # lambda = 1: the plain wrapper's values
