@@ -461,6 +461,8 @@ extern "C" int ctseg_colsum(int32_t dtype, const void* x, int32_t ld, int64_t ro
   CHECK_CL(dtype, C, false, false, ld);
   CTSEG_REQUIRE(Cv <= 256, "colsum: too many channels");
   const int pld = Cv * EPC_;
+  // colsum_final_kernel: one block of 1024 threads, one lane per partial column (1024 / pld sub-sums; none when pld > 1024)
+  CTSEG_REQUIRE(pld <= 1024, "colsum: %d partial columns for C=%d, the final sum takes at most 1024", pld, C);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == CTSEG_F32)
     hipLaunchKernelGGL(colsum_partial_kernel<float>, dim3(P), dim3(256), 0, st, (const char*)x, ld, rows, C, Cv, partials, P, pld);
