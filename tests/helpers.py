@@ -1,11 +1,17 @@
 """Shared test helpers: a one-layer plan around capstone_amd.engine.GemmLayer so single conv modules can be
-driven through the C ABI exactly as the UNet plan drives them (same packing, taps, descriptors)."""
+driven through the C ABI exactly as the UNet plan drives them (same packing, taps, descriptors); the names, grid caps and error
+bounds the op-level tests share (the float64 references themselves: reference_ops.py)."""
+import json
+import os
+
 import numpy as np
 import torch
 
 from capstone_amd import _native as nat
+from capstone_amd._native import BF16, F16, F32
 from capstone_amd.engine import Act, GemmLayer, Packer, ParamStore, new_act, rup
 from capstone_amd.plan import Plan, _NormAct
+from reference_ops import rounded
 
 
 class MiniPlan:
@@ -77,6 +83,29 @@ def run_conv_module(mod, x, gy, dt, device):
     gw = plan.store.grad_view(mod.weight).cpu().clone()
     gb = plan.store.grad_view(mod.bias).cpu().clone()
     return from_cl(y, dims == 2), gx, gw, gb
+
+
+def autograd_conv_module(mod, shape):
+    """operands of one conv module drawn from torch's global generator (the caller seeds it: x of (N, *spatial) = ``shape``, then dY)
+    and torch's float32 autograd on the CPU -> (x, gy, y, gx); the weight / bias gradient are left on the module's parameters"""
+    x = torch.randn(shape[0], mod.in_channels, *shape[1:])
+    xr = x.clone().requires_grad_(True)
+    y = mod(xr)
+    gy = torch.randn_like(y)
+    y.backward(gy)
+    return x, gy, y.detach(), xr.grad
+
+
+def check_conv_module(mod, shape, dt, device, tol):
+    """all four passes of the module (the input gradient where the layer has one) against autograd_conv_module, by rel_err"""
+    x, gy, y, gx_ref = autograd_conv_module(mod, shape)
+    yy, gx, gw, gb = run_conv_module(mod, x, gy, dt, device)
+    assert rel_err(yy, y) < tol, "forward"
+    assert (gx is None) == (mod.in_channels == 1)
+    if gx is not None:
+        assert rel_err(gx, gx_ref) < tol, "input gradient"
+    assert rel_err(gw, mod.weight.grad) < tol, "weight gradient"
+    assert rel_err(gb, mod.bias.grad) < tol, "bias gradient"
 
 
 class ConvPassDriver:
@@ -224,17 +253,15 @@ def norm_for(drv, alpha, N, C, dims, seed, eps=1e-5):
     """a _NormAct with a real forward output y (bf16-rounded, no element within 1e-3 of its mean in units of the standard
     deviation: the sign of xhat decides a PReLU branch, and float32 and float64 must agree on it) and its real (mean, rstd)
     -> (norm, y, mean, rstd); mean / rstd: the float32 table values as float64, shaped (N, C, 1, 1, 1)"""
-    def rounded(t):
-        return t.detach().to(torch.bfloat16).float()
     torch.manual_seed(seed)
-    y = rounded(torch.randn(N, C, *dims) * 1.3 + 0.4)
+    y = rounded(torch.randn(N, C, *dims) * 1.3 + 0.4, torch.bfloat16)
     mean = y.double().mean((2, 3, 4), keepdim=True)
     rstd = (y.double().var((2, 3, 4), unbiased=False, keepdim=True) + eps).rsqrt()
     mr32 = torch.stack([mean.float().reshape(N, C), rstd.float().reshape(N, C)], -1).contiguous()
     m32, r32 = mr32[..., 0].double().reshape(N, C, 1, 1, 1), mr32[..., 1].double().reshape(N, C, 1, 1, 1)
     for _ in range(3):
         near = ((y.double() - m32) * r32).abs() < 1e-3
-        y = rounded(torch.where(near, y + 0.25, y))
+        y = rounded(torch.where(near, y + 0.25, y), torch.bfloat16)
     assert float(((y.double() - m32) * r32).abs().min()) >= 1e-3
     na = _NormAct(drv.plan, alpha)
     na.y = to_cl(y, nat.BF16, drv.device)
@@ -242,6 +269,81 @@ def norm_for(drv, alpha, N, C, dims, seed, eps=1e-5):
     return na, y, m32, r32
 
 
+# ---- kernel family names (ctseg_conv_pass_name) and grid caps -----------------------------------------------------------------
+HALO_X, HALO, UP, STEM, HALO_SW = "x-column halo", "halo", "up", "stem", "streamed-weight halo"
+DOWN_HALO, DOWN_R, UP8 = "stride-2 halo", "stride-2 register-weight", "many-channel 8-class"
+G16, G32, G64, G128, G256 = "generic 256x16", "generic 256x32", "generic 128x64", "generic 128x128", "generic 192x256"
+RING128, RING256 = "generic ring 192x128", "generic ring 192x256"
+CAPS = [None, "1", "3"]      # CTSEG_MAX_WG: several tiles per workgroup of a persistent kernel
+CAP_IDS = ["uncapped", "max_wg1", "max_wg3"]
+
+
+def cap_env(monkeypatch, max_wg):
+    monkeypatch.delenv("CTSEG_MAX_WG", raising=False)
+    if max_wg is not None:
+        monkeypatch.setenv("CTSEG_MAX_WG", max_wg)
+
+
+def dump(out_dir, name, obj):
+    """a test's figures as JSON under ``out_dir`` (best effort: a read-only tree is no failure)"""
+    try:
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, name), "w") as f:
+            json.dump(obj, f, indent=1)
+    except OSError:
+        pass
+
+
+TDT = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}      # storage type -> torch dtype (reference_ops.rounded)
+# ---- the error bounds -----------------------------------------------------------------------------------------------------------
+EXACT_CAP = {BF16: 256.0, F16: 2048.0, F32: 2.0 ** 24}      # below it every integer is a value of the storage type
+REL_TOL = {F32: 2e-5, BF16: 2.5e-2}                         # max |error| / max |reference| of a whole tensor (rel_err)
+ULP = {BF16: 2.0 ** -8, F16: 2.0 ** -10, F32: 0.0}          # one unit in the last place, relative (fp32: the e32 term alone)
+
+
+def elem_bound(ref64, ref32, dt):
+    """per element: u * |ref64| + 16 * e32, e32 the largest |float32 - float64| evaluation of the case -> (bound, e32)"""
+    e32 = float((ref32.double() - ref64).abs().max())
+    assert e32 > 0.0
+    return ULP[dt] * ref64.abs() + 16.0 * e32, e32
+
+
+def check_elems(tag, got, ref64, ref32, dt):
+    """every element: |got - ref64| <= u * |ref64| + 16 * e32"""
+    bound, e32 = elem_bound(ref64, ref32, dt)
+    ratio = float(((got.double() - ref64).abs() / bound).max())
+    print(f"{tag}: worst error / bound {ratio:.3f} (e32 {e32:.2e})")
+    assert ratio <= 1.0, (tag, ratio)
+    return ratio
+
+
+def sum_bound(tag, t64, t32, dims, rows, div=1.0):
+    """-> (float64 sums of t64 over ``dims``, sums of |terms| (1 where none is nonzero), which sums have a nonzero term, bound on the error
+    normalised by them: 16 x that of the plain float32 evaluation (sum / div, as the kernel stores it), under 1 / (4 * rows))"""
+    s64, a64 = t64.sum(dims), t64.abs().sum(dims)
+    s32 = (t32.sum(dims) / div).double() * div
+    live = a64 > 0
+    norm = torch.where(live, a64, torch.ones_like(a64))
+    f32 = float(((s32 - s64).abs() / norm)[live].max())
+    bound, cap = 16.0 * f32, 1.0 / (4.0 * rows)
+    assert 0.0 < bound < cap, (tag, "float32 reference error x 16 is not inside (0, 1 / (4 * rows)): shrink the shape", bound, cap)
+    return s64, norm, live, bound
+
+
+def ulp32(s):
+    """spacing of fp32 at |s| (float64 tensor)"""
+    _, e = torch.frexp(s.abs())
+    return torch.where(s == 0, torch.full_like(s, 2.0 ** -149), torch.pow(2.0, (e - 24).double()))
+
+
 def rel_err(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-12))
+
+
+def rel_err_nonzero(x, x64):
+    """(max, rms) of |x - x64| / |x64| over x64 != 0, and whether x is exactly 0 wherever x64 is (numpy arrays)"""
+    nz = x64 != 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        r = np.abs(x[nz].astype(np.float64) - x64[nz]) / np.abs(x64[nz])
+        return float(r.max()), float(np.sqrt(np.mean(r * r))), bool((x[~nz] == 0).all())

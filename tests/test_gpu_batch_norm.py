@@ -15,11 +15,10 @@ from capstone_amd._native import BF16, F32  # noqa: E402
 from capstone_amd.engine import BufferStore, GemmLayer  # noqa: E402
 from capstone_amd.models import UNet  # noqa: E402
 from capstone_amd.plan import _BatchNormAct  # noqa: E402
-from helpers import MiniPlan, from_cl, rel_err, to_cl  # noqa: E402
+from helpers import REL_TOL, MiniPlan, cap_env, from_cl, rel_err, to_cl  # noqa: E402
 from test_batch_norm import swapped_oracle  # noqa: E402
 
 DEV = "cuda:0"
-TOL = {F32: 2e-5, BF16: 2.5e-2}
 
 
 def _bn_op(dt, N, C, residual, shape=(12, 16, 8), seed=0):
@@ -62,7 +61,7 @@ def _bn_op(dt, N, C, residual, shape=(12, 16, 8), seed=0):
     dy = na.emit_bwd(ga, g_copy=gcopy)
     plan.run()
     torch.cuda.synchronize()
-    tol = TOL[dt]
+    tol = REL_TOL[dt]
     assert rel_err(from_cl(out), yr.detach()) < tol, "forward"
     assert rel_err(from_cl(dy), xr.grad) < max(tol, 3e-5), "dx"
     assert torch.equal(from_cl(gcopy), from_cl(ga)), "g copy"
@@ -87,7 +86,7 @@ def test_batchnorm_prelu_op_fwd_bwd_running_stats(dt, residual, N, C):
 @pytest.mark.parametrize("max_wg", ["1", "3"])
 @pytest.mark.parametrize("dt,N,C", [(BF16, 2, 32), (F32, 2, 64), (BF16, 1, 256)])
 def test_batchnorm_prelu_op_with_capped_grids(monkeypatch, max_wg, dt, N, C):
-    monkeypatch.setenv("CTSEG_MAX_WG", max_wg)
+    cap_env(monkeypatch, max_wg)
     _bn_op(dt, N, C, True, shape=(16, 12, 24))
 
 

@@ -1,7 +1,8 @@
 """GPU: the Boundary loss on the MI355X — ctseg_boundary_stats / ctseg_boundary_grad at op level, then MultipleLossWrapper(...,
 device_boundary=True), LossEntry("Boundary", ...), forward_mixed and the two 2-D trainers.
 
-The comparison target is the reference's formula (capstone/models/losses.py:139-148) restated in float64 torch on the CPU:
+The comparison target is the reference's formula (capstone/models/losses.py:139-148) restated in float64 torch on the CPU (boundary64 /
+boundary_weights64 of reference_ops.py):
     p = softmax(x, 1);  T[b, c] = (1 / S) sum_v p[b, c + 1, v] D[b, c, v];  "mean": T.mean();  exclude_missing: the non-Focal branch
     of apply_missing_mask;  gradient d_k = p_k (g_k - sum_j g_j p_j), g_0 = 0, g_c = W[b, c - 1] D[b, c - 1] with W = weight of the
     table entry in the scalar / S;  mixup: g_c = W0 D[b] + W1 D[perm[b]].
@@ -29,6 +30,8 @@ pytestmark = pytest.mark.gpu
 from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd import segloss  # noqa: E402
 from capstone_amd._native import BF16, F32  # noqa: E402
+from helpers import ulp32  # noqa: E402
+from reference_ops import boundary64, boundary_weights64, softmax64  # noqa: E402
 
 DEV = "cuda:0"
 B = 3
@@ -36,10 +39,6 @@ PERM = [2, 0, 0]                 # no bijection (0 drawn twice, 1 never), no fix
 H, W = 47, 45                    # S = 2115: two workgroups per sample, a ragged second range, odd plane stride
 SHAPES = {"C10-ld12": (10, 12, H, W), "C5-ld8": (5, 8, H, W), "C14-ld16": (14, 16, H, W), "C10-S7": (10, 12, 7, 1)}
 _CASE = {}
-
-
-def _softmax64(x):
-    return torch.softmax(x.double(), dim=-1)
 
 
 def _case(key):
@@ -54,7 +53,7 @@ def _case(key):
     D = torch.rand(B, C - 1, S, generator=g) * 2 - 1                                 # both signs (signed=True); [0, 1] is inside
     bw = (torch.rand(B, 2, C - 1, generator=g) * 2 - 1) * 1e-3
     perm = torch.tensor(PERM)
-    p = _softmax64(x[..., :C])                                                        # (B, S, C)
+    p = softmax64(x[..., :C])                                                        # (B, S, C)
     pf = p[..., 1:].permute(0, 2, 1)                                                  # (B, C-1, S)
     sides = [D.double(), D[perm].double()]
     T = torch.stack([(pf * Ds).sum(-1) / S for Ds in sides], 1)                       # (B, 2, C-1)
@@ -127,12 +126,6 @@ def test_gradient_fp32_rows_vs_float64(key, ns):
     assert case["ld"] > C and float(got[..., C:].abs().max()) == 0.0                   # pad columns written as zeros (over the 7.0)
 
 
-def _ulp32(s):
-    """spacing of fp32 at |s| (float64 tensor)"""
-    _, e = torch.frexp(s.abs())
-    return torch.where(s == 0, torch.full_like(s, 2.0 ** -149), torch.pow(2.0, (e - 24).double()))
-
-
 @pytest.mark.parametrize("ns", [1, 2], ids=["single", "pair"])
 @pytest.mark.parametrize("key", list(SHAPES))
 def test_accumulate_into_fp32_rows(key, ns):
@@ -144,7 +137,7 @@ def test_accumulate_into_fp32_rows(key, ns):
     _engine(case, ns).boundary_grad(case["xd"].data_ptr(), ld, dl.data_ptr(), ld, F32, accumulate=True)
     got = dl.cpu()
     s = buf0[..., :C].double() + r0[..., :C].double()
-    assert bool(((got[..., :C].double() - s).abs() <= _ulp32(s)).all())
+    assert bool(((got[..., :C].double() - s).abs() <= ulp32(s)).all())
     assert torch.equal(got[..., C:], buf0[..., C:])                                    # pad columns unchanged
 
 
@@ -199,33 +192,6 @@ def test_exact_integer_case():
 
 
 # ---- the loss surface ---------------------------------------------------------------------------------------------------------
-def _weights64(ind, exclude_missing, K):
-    """weight of T[b, c] in the scalar, float64: the plain mean, or models/losses.py:206-221 (non-Focal branch)"""
-    if not exclude_missing:
-        return torch.full((B, K), 1.0 / (B * K), dtype=torch.float64)
-    ind = ind.double()
-    w = 1.0 / ind.sum(dim=0)
-    if torch.any(torch.isinf(w)):
-        w = torch.ones_like(w)
-    w = w / w.sum()
-    return w[None, :] * ind / B
-
-
-def _boundary64(logits, sides):
-    """sides: [(maps (B, C-1, H, W), weights (B, C-1) float64)] -> (value, its magnitude sum, gradient, sum_j |g_j| p_j), float64:
-    the scalar sum_s sum_bc W_s T(D_s)"""
-    x = logits.double().requires_grad_(True)
-    p = torch.softmax(x, dim=1)
-    val = sum(((p[:, 1:] * D.double()).mean(dim=(2, 3)) * Wt).sum() for D, Wt in sides)
-    mag = sum(((p[:, 1:] * D.double()).abs().mean(dim=(2, 3)) * Wt.abs()).sum() for D, Wt in sides)
-    grad = torch.autograd.grad(val, x)[0]
-    S = logits.shape[2] * logits.shape[3]
-    gk = torch.zeros_like(p)
-    for D, Wt in sides:
-        gk[:, 1:] += Wt[:, :, None, None] * D.double() / S
-    return val.item(), mag.item(), grad, (gk.abs() * p).sum(dim=1, keepdim=True).detach()
-
-
 def _surface_inputs(seed=7, C=10):
     g = torch.Generator().manual_seed(seed)
     logits = torch.randn(B, C, H, W, generator=g) * 2
@@ -241,8 +207,8 @@ def test_wrapper_on_a_foreign_tensor(exclude_missing):
     ind = torch.ones(B, 9)
     ind[1, 3] = 0
     ind[:, 6] = 0                                # a zero column: 1 / 0 -> the isinf branch (used under exclude_missing only)
-    Wt = _weights64(ind, exclude_missing, 9)
-    val, mag, gb, gabs = _boundary64(logits, [(D, Wt)])
+    Wt = boundary_weights64(ind, exclude_missing, B, 9)
+    val, mag, gb, gabs = boundary64(logits, [(D, Wt)])
     old = MultipleLossWrapper(["Dice", "Focal"], exclude_missing=exclude_missing)
     xo = logits.to(DEV).requires_grad_(True)
     vo = old(xo, target.to(DEV), mask_indicator=ind.to(DEV))
@@ -278,7 +244,7 @@ def test_unreduced_entry_and_forward_mixed():
     from capstone_amd.models.losses import LossEntry, MultipleLossWrapper
     logits, target, D = _surface_inputs(seed=8)
     gT = torch.randn(B, 9, generator=torch.Generator().manual_seed(9))
-    val, mag, gb, gabs = _boundary64(logits, [(D, gT.double())])
+    val, mag, gb, gabs = boundary64(logits, [(D, gT.double())])
     x = logits.to(DEV).requires_grad_(True)
     T = LossEntry("Boundary", "none")(x, D.to(DEV))
     assert T.shape == (B, 9) and T.dtype == torch.float32
@@ -297,8 +263,8 @@ def test_unreduced_entry_and_forward_mixed():
     ind[2, 4] = 0                                # sample 0's partner is sample 2: their indicators differ; sample 1's is sample 0
     ind[1, 1] = 0
     for exclude_missing in (False, True):
-        sides = [(D, lam * _weights64(ind, exclude_missing, 9)), (D[index], (1 - lam) * _weights64(ind[index], exclude_missing, 9))]
-        val, mag, gb, gabs = _boundary64(logits, sides)
+        sides = [(D, lam * boundary_weights64(ind, exclude_missing, B, 9)), (D[index], (1 - lam) * boundary_weights64(ind[index], exclude_missing, B, 9))]
+        val, mag, gb, gabs = boundary64(logits, sides)
         old = MultipleLossWrapper(["Dice"], exclude_missing=exclude_missing)
         xo = logits.to(DEV).requires_grad_(True)
         vo = old.forward_mixed(xo, target.to(DEV), index.to(DEV), lam, mask_indicator=ind.to(DEV))

@@ -2,7 +2,8 @@
 BaseUNet3D step fed by compute_distance_map(spatial_dims=3).
 
 The kernels are those of the 2-D route (ctseg_boundary_stats / ctseg_boundary_grad see B x S x C rows and [B][C-1][S] planes, whatever
-the spatial rank), so the comparison target and the bounds are those of tests/test_gpu_boundary_loss.py, restated for a volume:
+the spatial rank), so the comparison target (boundary64 of reference_ops.py, any rank) and the bounds are those of
+tests/test_gpu_boundary_loss.py, restated for a volume:
     p = softmax(x, 1);  T[b, c] = mean over the volume of p[b, c + 1] D[b, c];  "mean": T.mean();  exclude_missing: the non-Focal
     branch of apply_missing_mask
   * a scalar loss value: 2^-18 * sum_bc w_bc mean |p D|                                   (test_gpu_boundary_loss.py:16-17, :255)
@@ -20,34 +21,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from capstone_amd.data import utils as DU  # noqa: E402
+from reference_ops import boundary64, boundary_weights64  # noqa: E402
 
 DEV = "cuda:0"
 B, C, SP = 2, 10, (6, 5, 4)
-
-
-def _weights64(ind, exclude_missing, K):
-    """weight of T[b, c] in the scalar, float64: the plain mean, or models/losses.py:206-221 (non-Focal branch)"""
-    if not exclude_missing:
-        return torch.full((B, K), 1.0 / (B * K), dtype=torch.float64)
-    ind = ind.double()
-    w = 1.0 / ind.sum(dim=0)
-    if torch.any(torch.isinf(w)):
-        w = torch.ones_like(w)
-    w = w / w.sum()
-    return w[None, :] * ind / B
-
-
-def _boundary64(logits, D, Wt):
-    """(value, its magnitude sum, gradient, sum_j |g_j| p_j) of sum_bc W[b, c] T[b, c], float64"""
-    x = logits.double().requires_grad_(True)
-    p = torch.softmax(x, dim=1)
-    val = ((p[:, 1:] * D.double()).mean(dim=(2, 3, 4)) * Wt).sum()
-    mag = ((p[:, 1:] * D.double()).abs().mean(dim=(2, 3, 4)) * Wt.abs()).sum()
-    grad = torch.autograd.grad(val, x)[0]
-    S = logits[0, 0].numel()
-    gk = torch.zeros_like(p)
-    gk[:, 1:] = Wt[:, :, None, None, None] * D.double() / S
-    return val.item(), mag.item(), grad, (gk.abs() * p).sum(dim=1, keepdim=True).detach()
 
 
 def _inputs(seed=7):
@@ -65,8 +42,8 @@ def test_wrapper_value_and_gradient_on_a_volume(exclude_missing):
     ind = torch.ones(B, 9)
     ind[1, 3] = 0
     ind[:, 6] = 0                                # a zero column: 1 / 0 -> the isinf branch (used under exclude_missing only)
-    Wt = _weights64(ind, exclude_missing, 9)
-    val, mag, gb, gabs = _boundary64(logits, D, Wt)
+    Wt = boundary_weights64(ind, exclude_missing, B, 9)
+    val, mag, gb, gabs = boundary64(logits, [(D, Wt)])
     old = MultipleLossWrapper3D(["Dice", "Focal"], exclude_missing=exclude_missing)
     xo = logits.to(DEV).requires_grad_(True)
     vo = old(xo, target.to(DEV), mask_indicator=ind.to(DEV))
@@ -101,7 +78,7 @@ def test_the_boundary_entry_on_5d_input():
     from capstone_amd.models.losses import LossEntry
     logits, _, D = _inputs(seed=8)
     gT = torch.randn(B, 9, generator=torch.Generator().manual_seed(9))
-    _, _, gb, gabs = _boundary64(logits, D, gT.double())
+    _, _, gb, gabs = boundary64(logits, [(D, gT.double())])
     x = logits.to(DEV).requires_grad_(True)
     T = LossEntry("Boundary", "none")(x, D.to(DEV))
     assert T.shape == (B, 9) and T.dtype == torch.float32
@@ -160,7 +137,7 @@ def test_one_training_step_with_the_boundary_loss():
     np.testing.assert_allclose(m1.logged["Mean Dice Score (train)"].item(), m2.logged["Mean Dice Score (train)"].item(), rtol=1e-6)
     # the Boundary value itself against float64, from the logits the native step kept (bound: test_gpu_boundary_loss.py:365)
     y = m2.unet.engine().logits_view().detach().float().cpu()
-    val, mag, _, _ = _boundary64(y, batch[3].cpu(), torch.full((2, 9), 1.0 / 18, dtype=torch.float64))
+    val, mag, _, _ = boundary64(y, [(batch[3].cpu(), torch.full((2, 9), 1.0 / 18, dtype=torch.float64))])
     assert abs(m2.logged["Boundary Loss (train)"].item() - val) <= 2.0 ** -18 * mag and mag > 0
     store = m2.unet.engine().store
     grads = {k: store.grad_view(q).detach().cpu().clone() for k, q in m2.named_parameters()}

@@ -2,7 +2,8 @@
 
 Every case names the kernel family (or generic / ring tile) it is written for; helpers.ConvPassDriver asserts ctseg_conv_pass_name of
 the recorded descriptor before the pass runs.  The existing conv tests bound max |error| / max |reference| by 2.5e-2 (16-bit) or
-compare two kernels with each other; here every stored ELEMENT is held to a float64 CPU convolution (_conv / _dgrad below).
+compare two kernels with each other; here every stored ELEMENT is held to a float64 CPU convolution (conv_fwd / conv_dgrad of
+reference_ops.py).
 
 Oracle A, exact.  Operands are small integers, so every product and every partial sum is an integer far below 2^24: the fp32
 accumulator holds the exact result in any summation order, and the stored value is exact whenever the storage type holds that integer.
@@ -73,54 +74,19 @@ import zlib
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
 from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd._native import BF16, F16, F32  # noqa: E402
 from capstone_amd.engine import rup  # noqa: E402
-from helpers import ACT_SENTINEL, ConvPassDriver, sentinel_act, to_cl, wide_act  # noqa: E402
+from helpers import (ACT_SENTINEL, CAP_IDS, CAPS, DOWN_HALO, DOWN_R, EXACT_CAP, G16, G32, G64, G128, G256, HALO, HALO_SW,  # noqa: E402
+                     HALO_X, RING128, RING256, STEM, ULP, UP, UP8, ConvPassDriver, cap_env, elem_bound, sentinel_act, to_cl, wide_act)
+from reference_ops import conv_dgrad, conv_fwd, conv_module, conv_out_shape  # noqa: E402
 
 DEV = "cuda:0"
-CAPS = [None, "1", "3"]
-CAP_IDS = ["uncapped", "max_wg1", "max_wg3"]
-
-HALO_X, HALO, UP, STEM, HALO_SW = "x-column halo", "halo", "up", "stem", "streamed-weight halo"
-DOWN_HALO, DOWN_R, UP8 = "stride-2 halo", "stride-2 register-weight", "many-channel 8-class"
-G16, G32, G64, G128, G256 = "generic 256x16", "generic 256x32", "generic 128x64", "generic 128x128", "generic 192x256"
-RING128, RING256 = "generic ring 192x128", "generic ring 192x256"
 NO_X = {"CTSEG_NO_HALO_X": "1"}      # conv_halo_x_eligible turns every pass down: 16-bit storage on the "halo" kernel
 ENV_KEYS = ("CTSEG_MAX_WG", "CTSEG_NO_HALO_X", "CTSEG_NO_DOWN_R")
-# the largest integer magnitude below which every integer is a value of the storage type (8 / 11 / 24 significand bits)
-EXACT_CAP = {BF16: 256.0, F16: 2048.0, F32: 2.0 ** 24}
-ULP = {BF16: 2.0 ** -8, F16: 2.0 ** -10, F32: 0.0}
-
-
-# ---- the layer and its float64 reference -------------------------------------------------------------------------------------
-def _module(kind, cin, cout, k, dims):
-    conv, convT = (torch.nn.Conv3d, torch.nn.ConvTranspose3d) if dims == 3 else (torch.nn.Conv2d, torch.nn.ConvTranspose2d)
-    if kind == "convT":
-        return convT(cin, cout, 3, 2, 1, output_padding=1)
-    return conv(cin, cout, k, 2 if kind == "conv_s2" else 1, (k - 1) // 2)
-
-
-def _conv(kind, k, x, w, b):
-    two_d = x.ndim == 4
-    if kind == "convT":
-        return (F.conv_transpose2d if two_d else F.conv_transpose3d)(x, w, b, stride=2, padding=1, output_padding=1)
-    return (F.conv2d if two_d else F.conv3d)(x, w, b, stride=2 if kind == "conv_s2" else 1, padding=(k - 1) // 2)
-
-
-def _dgrad(kind, k, gy, w, x_shape):
-    """input gradient of the same layer: the transposed operator, no bias"""
-    two_d = gy.ndim == 4
-    if kind == "convT":
-        return (F.conv2d if two_d else F.conv3d)(gy, w, None, stride=2, padding=1)
-    s = 2 if kind == "conv_s2" else 1
-    p = (k - 1) // 2
-    op = tuple(x_shape[2 + i] - ((gy.shape[2 + i] - 1) * s - 2 * p + k) for i in range(gy.ndim - 2))
-    return (F.conv_transpose2d if two_d else F.conv_transpose3d)(gy, w, None, stride=s, padding=p, output_padding=op)
 
 
 class _Case:
@@ -146,17 +112,15 @@ class _Case:
         return f"{self.name} | {self.pas} {self.kind} {self.cin}->{self.cout} {self.shape}{st}".replace(" ", "_")
 
     def with_dt(self, dt):
-        c = _Case(self.name, self.pas, self.family, self.kind, self.cin, self.cout, self.shape, dt, self.k, self.wd, self.env, self.g_ld,
-                  self.o_ld, self.cg, self.out_f32, self.wide)
-        return c
+        return _Case(self.name, self.pas, self.family, self.kind, self.cin, self.cout, self.shape, dt, self.k, self.wd, self.env, self.g_ld,
+                     self.o_ld, self.cg, self.out_f32, self.wide)
 
     def setenv(self, monkeypatch, cap=None):
         for k in ENV_KEYS:
             monkeypatch.delenv(k, raising=False)
         for k, v in self.env.items():
             monkeypatch.setenv(k, v)
-        if cap is not None:
-            monkeypatch.setenv("CTSEG_MAX_WG", cap)
+        cap_env(monkeypatch, cap)
 
 
 class _Ops:
@@ -177,12 +141,10 @@ class _Ops:
     def __init__(self, case, mode, seed):
         g = torch.Generator().manual_seed(seed)
         self.kind, self.k = case.kind, case.k
-        mod = _module(case.kind, case.cin, case.cout, case.k, case.dims)
+        mod = conv_module(case.kind, case.cin, case.cout, case.k, case.dims)
         N, sp = case.shape[0], case.shape[1:]
         xs = (N, case.cin) + sp
-        with torch.no_grad():
-            ys = tuple(_conv(case.kind, case.k, torch.zeros((1, case.cin) + sp), torch.zeros_like(mod.weight), None).shape[2:])
-        ys = (N, case.cout) + ys
+        ys = (N, case.cout) + conv_out_shape(case.kind, case.k, sp)
         ws = tuple(mod.weight.shape)
         if mode == "unit":
             def tern(shape, p):
@@ -202,7 +164,7 @@ class _Ops:
         self._ref = {}
 
     def module(self, case):
-        mod = _module(case.kind, case.cin, case.cout, case.k, case.dims)
+        mod = conv_module(case.kind, case.cin, case.cout, case.k, case.dims)
         with torch.no_grad():
             mod.weight.copy_(self.w)
             mod.bias.copy_(self.b)
@@ -214,7 +176,7 @@ class _Ops:
         if key not in self._ref:
             x, w, b, gy = ((t if f32 else t.double()) for t in (self.x, self.w, self.b, self.gy))
             with torch.no_grad():
-                self._ref[key] = _conv(self.kind, self.k, x, w, b) if pas == "fwd" else _dgrad(self.kind, self.k, gy, w, self.x.shape)
+                self._ref[key] = conv_fwd(self.kind, self.k, x, w, b) if pas == "fwd" else conv_dgrad(self.kind, self.k, gy, w, self.x.shape)
         return self._ref[key]
 
 
@@ -526,14 +488,13 @@ def test_normal_operands_per_element(monkeypatch, case):
     case.setenv(monkeypatch)
     ops = _Ops.of(case, ("randn", case.dt))
     y64, y32 = ops.ref(case.pas), ops.ref(case.pas, f32=True)
-    e32 = float((y32.double() - y64).abs().max())
-    assert e32 > 0
-    u = ULP[F32 if case.out_f32 else case.dt]
+    odt = F32 if case.out_f32 else case.dt
+    want, want32 = (y if y.ndim == 5 else y.unsqueeze(-1) for y in (y64, y32))
+    bound, e32 = elem_bound(want, want32, odt)
+    u = ULP[odt]
     run = _Run(case, ops)
     T = run.buffer()
     got = T[..., :run.Cn].permute(0, 4, 1, 2, 3)
-    want = y64 if y64.ndim == 5 else y64.unsqueeze(-1)
-    bound = u * want.abs() + 16.0 * e32
     ratio = float(((got - want).abs() / bound).max())
     print(f"{case.id}: worst error / bound {ratio:.3f} (e32 {e32:.3e}, u {u:.1e}, max |y| {float(want.abs().max()):.2f})")
     assert bool(((got - want).abs() <= bound).all()), ("per-element bound", ratio)

@@ -4,7 +4,7 @@ Every case names the family it is written for; helpers.ConvPassDriver asserts ct
 before it launches, so a later eligibility change cannot move a shape to another kernel unnoticed.
 
 Reference: operands rounded to the storage type (x, weight, addend, y of the backward statistics), convolution in float64 on the
-CPU.  What the statistics are taken of, read from each family's epilogue:
+CPU (conv_fwd / conv_dgrad, norm_prelu_terms / norm_prelu_dy of reference_ops.py; the sum bound: helpers.sum_bound).  What the statistics are taken of, read from each family's epilogue:
   * forward (sum, sumsq) partials: the fp32 result (accumulator + bias) BEFORE it is rounded to the storage type, in every family
     (x-column halo, halo, up, stem, streamed-weight halo, stride-2 halo, stride-2 register-weight, many-channel 8-class, generic
     and ring) -> the reference sums the unrounded float64 result;
@@ -54,7 +54,6 @@ import ctypes
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
@@ -62,42 +61,14 @@ from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd._native import BF16, F32  # noqa: E402
 from capstone_amd.engine import Act, GemmLayer, SplitAct, rup  # noqa: E402
 from capstone_amd.plan import _NormAct  # noqa: E402
-from helpers import ConvPassDriver, MiniPlan, from_cl, norm_for, rel_err, to_cl  # noqa: E402
+from helpers import (CAP_IDS, CAPS, DOWN_HALO, DOWN_R, GRAD_SENTINEL, HALO, HALO_SW, HALO_X, REL_TOL, STEM, TDT, UP, UP8, ConvPassDriver,  # noqa: E402
+                     MiniPlan, cap_env, from_cl, norm_for, rel_err, sum_bound, to_cl)
+from reference_ops import conv_dgrad, conv_fwd, conv_module, norm_prelu_dy, norm_prelu_terms, rounded  # noqa: E402
 
 DEV = "cuda:0"
-TOL = {F32: 2e-5, BF16: 2.5e-2}
 EPS = 1e-5
 
-HALO_X, HALO, UP, STEM, HALO_SW = "x-column halo", "halo", "up", "stem", "streamed-weight halo"
-DOWN_HALO, DOWN_R, UP8 = "stride-2 halo", "stride-2 register-weight", "many-channel 8-class"
-
-# ---- the layer under test and its float64 / float32 references ---------------------------------------------------------------
-def _module(kind, cin, cout, k=3):
-    if kind == "convT":
-        return torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1)
-    return torch.nn.Conv3d(cin, cout, k, 2 if kind == "conv_s2" else 1, (k - 1) // 2)
-
-
-def _conv(kind, k, x, w, b):
-    if kind == "convT":
-        return F.conv_transpose3d(x, w, b, stride=2, padding=1, output_padding=1)
-    return F.conv3d(x, w, b, stride=2 if kind == "conv_s2" else 1, padding=(k - 1) // 2)
-
-
-def _dgrad(kind, k, gy, w, x_shape):
-    """input gradient of the same layer: the transposed operator, no bias"""
-    if kind == "convT":
-        return F.conv3d(gy, w, None, stride=2, padding=1)
-    s = 2 if kind == "conv_s2" else 1
-    p = (k - 1) // 2
-    op = tuple(x_shape[2 + i] - ((gy.shape[2 + i] - 1) * s - 2 * p + k) for i in range(3))
-    return F.conv_transpose3d(gy, w, None, stride=s, padding=p, output_padding=op)
-
-
-def _rounded(t, dt):
-    return t.detach().to(nat.torch_dtype(dt)).float()
-
-
+# ---- the layer under test with its rounded operands -----------------------------------------------------------------------------
 class _Layer:
     """a seeded layer with the CPU copies of its rounded operands (the driver moves the module's parameters to the device)"""
 
@@ -105,19 +76,19 @@ class _Layer:
         self.key = (kind, cin, cout, shape, dt, k, bias_shift)
         torch.manual_seed(7 * cin + cout + shape[2])
         self.kind, self.k, self.dt, self.cin, self.cout, self.shape = kind, k, dt, cin, cout, shape
-        self.mod = _module(kind, cin, cout, k)
+        self.mod = conv_module(kind, cin, cout, k)
         with torch.no_grad():
             self.mod.bias.add_(bias_shift)
-        self.x = _rounded(torch.randn(shape[0], cin, *shape[1:]), dt)
-        self.w, self.b = _rounded(self.mod.weight, dt), self.mod.bias.detach().clone()      # (the bias stays fp32 on the device)
+        self.x = rounded(torch.randn(shape[0], cin, *shape[1:]), TDT[dt])
+        self.w, self.b = rounded(self.mod.weight, TDT[dt]), self.mod.bias.detach().clone()      # (the bias stays fp32 on the device)
 
     def y(self):
         """(float64 result, float32 result) of the forward convolution: computed once per configuration (the layer is seeded, so
         every test of one configuration builds the same operands) and never written to"""
         if self.key not in _FWD_REF:
             with torch.no_grad():
-                _FWD_REF[self.key] = (_conv(self.kind, self.k, self.x.double(), self.w.double(), self.b.double()),
-                                      _conv(self.kind, self.k, self.x, self.w, self.b))
+                _FWD_REF[self.key] = (conv_fwd(self.kind, self.k, self.x.double(), self.w.double(), self.b.double()),
+                                      conv_fwd(self.kind, self.k, self.x, self.w, self.b))
         return _FWD_REF[self.key]
 
     def driver(self, extra_params=(), cg=None):
@@ -142,42 +113,27 @@ def _bst_partials(gx):
     return mark[1].cpu()
 
 
-def _cap(monkeypatch, max_wg):
-    if max_wg is None:
-        monkeypatch.delenv("CTSEG_MAX_WG", raising=False)
-    else:
-        monkeypatch.setenv("CTSEG_MAX_WG", max_wg)
-
-
-CAPS = [None, "1", "3"]
-CAP_IDS = ["uncapped", "max_wg1", "max_wg3"]
-
-
-# ---- sums against float64 with the measured float32 bound --------------------------------------------------------------------
-def _sum_bounds(v64, v32, voxels):
-    """v64 / v32: (N, C, voxels...) float64 / float32 evaluations of the summed quantity.  Returns the float64 sums and the bound
-    (16 x the worst normalised float32 error) for the plain sum and the sum of squares, after checking the bound against the cap."""
-    dims = tuple(range(2, v64.ndim))
-    s64, q64, a64 = v64.sum(dims), (v64 * v64).sum(dims), v64.abs().sum(dims)
-    s32, q32 = v32.sum(dims).double(), (v32 * v32).sum(dims).double()
-    bs = 16.0 * float(((s32 - s64).abs() / a64).max())
-    bq = 16.0 * float(((q32 - q64).abs() / q64).max())
-    cap = 1.0 / (4.0 * voxels)
-    assert 0.0 < bs < cap and 0.0 < bq < cap, ("float32 reference error x 16 is not under 1 / (4 * voxels): shrink the shape", bs, bq, cap)
-    return s64, q64, a64, bs, bq
+# ---- sums against float64 with the measured float32 bound (helpers.sum_bound) --------------------------------------------------
+def _live_sum_bound(tag, t64, t32, dims, rows):
+    """helpers.sum_bound where no sum may be without a nonzero term -> (float64 sums, sums of |terms|, bound)"""
+    s64, a64, live, bound = sum_bound(tag, t64, t32, dims, rows)
+    assert bool(live.all()), (tag, "a sum without a nonzero term")
+    return s64, a64, bound
 
 
 def _check_forward_stats(tag, lay, drv, out, stats):
     y64, y32 = lay.y()
     N, Cn = y64.shape[:2]
     voxels = y64[0, 0].numel()
-    s64, q64, a64, bs, bq = _sum_bounds(y64, y32, voxels)
+    dims = tuple(range(2, y64.ndim))
+    s64, a64, bs = _live_sum_bound(f"{tag} sum", y64, y32, dims, voxels)
+    q64, _, bq = _live_sum_bound(f"{tag} sumsq", y64 * y64, y32 * y32, dims, voxels)
     part = stats.partials.cpu()
     tot = part.double().sum(1)
     es = float(((tot[:, 0, :Cn] - s64).abs() / a64).max())
     eq = float(((tot[:, 1, :Cn] - q64).abs() / q64).max())
     print(f"{tag}: sum err {es:.3e} (bound {bs:.3e}), sumsq err {eq:.3e} (bound {bq:.3e}), cap {1 / (4 * voxels):.3e}")
-    assert rel_err(from_cl(out), y64) < TOL[lay.dt], "forward output"
+    assert rel_err(from_cl(out), y64) < REL_TOL[lay.dt], "forward output"
     assert es <= bs, ("sum partials", es, bs)
     assert eq <= bq, ("sum-of-squares partials", eq, bq)
     assert stats.ld == part.shape[-1] and (stats.ld == Cn or float(part[..., Cn:].abs().max()) == 0.0), "columns [Cn, stats_ld) stay zero"
@@ -231,7 +187,7 @@ STATS_CASES = [
 @pytest.mark.parametrize("max_wg", CAPS, ids=CAP_IDS)
 @pytest.mark.parametrize("tag,family,kind,cin,cout,k,shape,dt,shift", STATS_CASES, ids=[c[0] for c in STATS_CASES])
 def test_forward_statistics(monkeypatch, max_wg, tag, family, kind, cin, cout, k, shape, dt, shift):
-    _cap(monkeypatch, max_wg)
+    cap_env(monkeypatch, max_wg)
     lay = _Layer(kind, cin, cout, shape, dt, k=k, bias_shift=shift)
     drv = lay.driver()
     out, stats = drv.fwd(family, drv.act(lay.x), want_stats=True)
@@ -274,7 +230,7 @@ def _addend(kind, lay, drv, xa, shape_nc):
     if kind == "f32" and lay.dt != F32:
         aa = to_cl(a, F32, DEV, ld=rup(shape_nc[1], 8))
         return aa, a
-    return to_cl(a, lay.dt, DEV), _rounded(a, lay.dt)
+    return to_cl(a, lay.dt, DEV), rounded(a, TDT[lay.dt])
 
 
 @pytest.mark.parametrize("tag,family,kind,cin,cout,k,shape,dt,addk", ADD_CASES, ids=[c[0] for c in ADD_CASES])
@@ -287,7 +243,7 @@ def test_forward_addend(tag, family, kind, cin, cout, k, shape, dt, addk):
     out, _ = drv.fwd(family, xa, add=aa)
     err = rel_err(from_cl(out), y64 + acpu.double())
     print(f"{tag}: rel err {err:.3e}")
-    assert err < TOL[dt]
+    assert err < REL_TOL[dt]
     assert (drv.desc.add_f32 == 1) == (addk == "f32" and dt != F32)
 
 
@@ -314,15 +270,15 @@ def test_input_gradient_addend(tag, family, kind, cin, cout, shape, dt):
     torch.manual_seed(17)
     drv = lay.driver()
     od = drv.layer.out_dims((shape[0],) + tuple(shape[1:]))
-    gy = _rounded(torch.randn(od[0], cout, *od[1:]), dt)
-    add = _rounded(torch.randn(*lay.x.shape), dt)
+    gy = rounded(torch.randn(od[0], cout, *od[1:]), TDT[dt])
+    add = rounded(torch.randn(*lay.x.shape), TDT[dt])
     with torch.no_grad():
-        ref = _dgrad(kind, 3, gy.double(), lay.w.double(), lay.x.shape) + add.double()
+        ref = conv_dgrad(kind, 3, gy.double(), lay.w.double(), lay.x.shape) + add.double()
     drv.set_input_dims((shape[0],) + tuple(shape[1:]))
     gx = drv.dgrad(family, to_cl(gy, dt, DEV), add=to_cl(add, dt, DEV))
     err = rel_err(from_cl(gx), ref)
     print(f"{tag}: rel err {err:.3e}")
-    assert err < TOL[dt]
+    assert err < REL_TOL[dt]
 
 
 def test_halo_x_refuses_statistics_with_an_addend():
@@ -351,7 +307,7 @@ def test_fp32_output_under_bf16_storage(tag, family, cin, cout, shape, ld):
     assert out.t.dtype == torch.float32 and drv.desc.out_f32 == 1 and drv.desc.g_ld == (ld or cin)
     err = rel_err(from_cl(out), y64)
     print(f"{tag}: rel err {err:.3e}")
-    assert err < TOL[F32]
+    assert err < REL_TOL[F32]
 
 
 # ---- split output ------------------------------------------------------------------------------------------------------------
@@ -374,7 +330,7 @@ def test_split_output(tag, family, cin, cout, shape, at):
     w = from_cl(whole)
     a, b = from_cl(split.a), from_cl(split.b)
     assert torch.equal(a, w[:, :at]) and torch.equal(b, w[:, at:]), "halves are the column slices of the unsplit run"
-    assert rel_err(a, y64[:, :at]) < TOL[BF16] and rel_err(b, y64[:, at:]) < TOL[BF16]
+    assert rel_err(a, y64[:, :at]) < REL_TOL[BF16] and rel_err(b, y64[:, at:]) < REL_TOL[BF16]
     assert torch.equal(st_w.partials, st_s.partials), "statistics partials of the split run"
     assert float(st_w.partials.abs().max()) > 0
 
@@ -396,21 +352,6 @@ def test_split_output_is_refused_where_the_family_cannot():
 
 
 # ---- backward statistics -----------------------------------------------------------------------------------------------------
-def _norm_for(drv, alpha, N, C, dims, seed):
-    return norm_for(drv, alpha, N, C, dims, seed, eps=EPS)      # (shared with the weight-gradient tests: helpers.norm_for)
-
-
-def _bst_reference(g, y, m, r, alpha, f32):
-    """the three sums of the header's formula, float64 (f32=False) or plain float32 torch"""
-    if f32:
-        g, y, m, r = g.float(), y.float(), m.float(), r.float()
-    else:
-        g, y = g.double(), y.double()
-    xh = (y - m) * r
-    dxh = g * torch.where(xh > 0, torch.ones_like(xh), torch.full_like(xh, alpha))
-    return dxh, dxh * xh, g * xh.clamp(max=0)
-
-
 # (id, family of the input-gradient pass, kind, cin, cout, shape of x, norm channels, bst_col0, with addend, row width of dY)
 BST_CASES = [
     ("halo_x dgrad 16->16", HALO_X, "conv", 16, 16, (2, 9, 11, 13), 16, 0, False, None),
@@ -433,17 +374,17 @@ BST_CASES = [
 @pytest.mark.parametrize("max_wg", CAPS, ids=CAP_IDS)
 @pytest.mark.parametrize("tag,family,kind,cin,cout,shape,C,col0,with_add,gy_ld", BST_CASES, ids=[c[0] for c in BST_CASES])
 def test_backward_statistics(monkeypatch, max_wg, tag, family, kind, cin, cout, shape, C, col0, with_add, gy_ld):
-    _cap(monkeypatch, max_wg)
+    cap_env(monkeypatch, max_wg)
     lay = _Layer(kind, cin, cout, shape, BF16)
     alpha = torch.nn.Parameter(torch.tensor([0.2]))
     drv = lay.driver(extra_params=[alpha])
     N, dims = shape[0], tuple(shape[1:])
-    na, y, m, r = _norm_for(drv, alpha, N, C, dims, seed=cin + C + col0)
+    na, y, m, r = norm_for(drv, alpha, N, C, dims, seed=cin + C + col0)
     od = drv.layer.out_dims((N,) + dims)
     torch.manual_seed(23)
-    gy = _rounded(torch.randn(od[0], cout, *od[1:]), BF16)
+    gy = rounded(torch.randn(od[0], cout, *od[1:]), TDT[BF16])
     drv.set_input_dims((N,) + dims)
-    add = _rounded(torch.randn(*lay.x.shape), BF16) if with_add else None
+    add = rounded(torch.randn(*lay.x.shape), TDT[BF16]) if with_add else None
     extras = {"add": to_cl(add, BF16, DEV)} if with_add else {}
     gx = drv.dgrad(family, to_cl(gy, BF16, DEV, ld=gy_ld), bst=na, bst_col0=col0, **extras)
     assert drv.desc.g_ld == (gy_ld or cout)
@@ -454,19 +395,19 @@ def test_backward_statistics(monkeypatch, max_wg, tag, family, kind, cin, cout, 
     assert tuple(part.shape) == (N, P, 3, ld)
     # the gradient itself: asking for the statistics selects kernel instantiations of their own
     with torch.no_grad():
-        ref = _dgrad(kind, 3, gy.double(), lay.w.double(), lay.x.shape)
+        ref = conv_dgrad(kind, 3, gy.double(), lay.w.double(), lay.x.shape)
     err = rel_err(from_cl(gx), ref + add.double() if with_add else ref)
-    assert err < TOL[BF16], ("input gradient of the pass that takes the statistics", err)
+    assert err < REL_TOL[BF16], ("input gradient of the pass that takes the statistics", err)
     g = from_cl(gx)[:, col0:col0 + C]                     # the STORED gradient
     voxels = g[0, 0].numel()
-    t64, t32 = _bst_reference(g, y, m, r, 0.2, False), _bst_reference(g, y, m, r, 0.2, True)
+    # the three sums of the header's formula, in float64 and in plain float32 torch
+    t64 = norm_prelu_terms(g.double(), y.double(), m, r, 0.2)[2]
+    t32 = norm_prelu_terms(g.float(), y.float(), m.float(), r.float(), 0.2)[2]
     dims3 = (2, 3, 4)
     tot = part.double().sum(1)                            # (N, 3, ld)
     figs = []
     for i in (0, 1):
-        s64, a64 = t64[i].sum(dims3), t64[i].abs().sum(dims3)
-        b = 16.0 * float(((t32[i].sum(dims3).double() - s64).abs() / a64).max())
-        assert 0 < b < 1.0 / (4 * voxels), (i, b, "float32 reference error x 16 is not under the cap")
+        s64, a64, b = _live_sum_bound(f"{tag} term {i}", t64[i], t32[i], dims3, voxels)
         e = float(((tot[:, i, :C] - s64).abs() / a64).max())
         figs.append((e, b))
     # the slope term: one parameter, and a lane of the conv kernels keeps ONE accumulator for it over all its channels
@@ -504,7 +445,7 @@ def test_norm_on_load_equals_the_materialised_activation():
     alpha = torch.nn.Parameter(torch.tensor([0.2]))
     drv = lay.driver(extra_params=[alpha], cg=16)
     drv.plan.narrow_rows = True
-    na, y, m, r = _norm_for(drv, alpha, N, C, dims, seed=3)
+    na, y, m, r = norm_for(drv, alpha, N, C, dims, seed=3)
     ya = to_cl(y, BF16, DEV, ld=12)
     na.y = ya
     xm = na._apply(ya, None, None)                          # the materialised activation (12-wide rows as well)
@@ -518,23 +459,18 @@ def test_norm_on_load_equals_the_materialised_activation():
     xh = (y.double() - m) * r
     act = torch.where(xh > 0, xh, 0.2 * xh)
     with torch.no_grad():
-        ref = _conv("conv", 3, act, lay.w.double(), lay.b.double())
+        ref = conv_fwd("conv", 3, act, lay.w.double(), lay.b.double())
     err = rel_err(from_cl(fused), ref)
     print(f"norm on load: rel err {err:.3e}")
-    assert err < TOL[BF16]
+    assert err < REL_TOL[BF16]
 
 
 # ---- InstanceNorm + PReLU op sweep -------------------------------------------------------------------------------------------
-_SENTINEL = -12345.0
-
-
 def _instnorm_prelu_dy(g, y, mr, alpha):
-    """dL/dy of InstanceNorm + PReLU from the header's formula, in the precision of the arguments; mr: (N, C, 2) mean, rstd"""
+    """(dL/dy of InstanceNorm + PReLU, xhat) in the precision of the arguments; mr: (N, C, 2) mean, rstd"""
     N, C = y.shape[:2]
     m, r = mr[..., 0].reshape(N, C, 1, 1, 1), mr[..., 1].reshape(N, C, 1, 1, 1)
-    xh = (y - m) * r
-    dxh = g * torch.where(xh > 0, torch.ones_like(xh), torch.full_like(xh, alpha))
-    return r * (dxh - dxh.mean((2, 3, 4), keepdim=True) - xh * (dxh * xh).mean((2, 3, 4), keepdim=True)), xh
+    return norm_prelu_dy(g, y, m, r, alpha), (y - m) * r
 
 
 def _check_colsum(tag, colsum, y, g, mr, alpha, C, nonzero=False):
@@ -543,14 +479,10 @@ def _check_colsum(tag, colsum, y, g, mr, alpha, C, nonzero=False):
     dy64, xh = _instnorm_prelu_dy(g.double(), y.double(), mr, alpha)
     dy32, _ = _instnorm_prelu_dy(g, y, mr.float(), alpha)
     assert float(xh.abs().min()) > 1e-5, "an element on the PReLU kink: float32 and float64 may take different branches"
-    dims = (0, 2, 3, 4)
-    s64, a64 = dy64.sum(dims), dy64.abs().sum(dims)
-    rows = dy64[:, 0].numel()
-    bound = 16.0 * float(((dy32.sum(dims).double() - s64).abs() / a64).max())
-    assert 0.0 < bound < 1.0 / (4 * rows), (bound, rows)
+    s64, a64, bound = _live_sum_bound(tag, dy64, dy32, (0, 2, 3, 4), dy64[:, 0].numel())
     got = colsum.cpu().double()
-    assert bool((got[:C] != _SENTINEL).all()), "every column sum was written"
-    assert bool((got[C:] == _SENTINEL).all()), "nothing written beyond the C columns"
+    assert bool((got[:C] != GRAD_SENTINEL).all()), "every column sum was written"
+    assert bool((got[C:] == GRAD_SENTINEL).all()), "nothing written beyond the C columns"
     err = float(((got[:C] - s64).abs() / a64).max())
     size = float((s64.abs() / a64).min())
     print(f"{tag}: error / sum |dy| = {err:.3e} (bound {bound:.3e}), smallest |column sum| / sum |dy| = {size:.3e}")
@@ -558,14 +490,16 @@ def _check_colsum(tag, colsum, y, g, mr, alpha, C, nonzero=False):
         assert size > 100 * bound, "the moved mean leaves column sums far above the bound"
     assert err <= bound, ("column sums of dy", err, bound)
     return dy64
+
+
 def _in_op(dt, N, C, residual, shape=(12, 16, 8), variant="g_copy"):
     """ctseg_instnorm_prelu_fwd and the 3-kernel backward against float64 InstanceNorm3d + PReLU on the storage-rounded input.
     variant: "g_copy" (the gradient copied out beside dy), "colsum" (column sums of dy from the apply pass), "no_apply"
     (statistics and slope gradient only: ctseg_instnorm_prelu_dalpha)"""
     torch.manual_seed(C + 7 * N + shape[0])
-    x = _rounded(torch.randn(N, C, *shape) * 1.5 + 0.3, dt)
-    gy = _rounded(torch.randn(N, C, *shape), dt)
-    res = _rounded(torch.randn(N, C, *shape), dt) if residual else None
+    x = rounded(torch.randn(N, C, *shape) * 1.5 + 0.3, TDT[dt])
+    gy = rounded(torch.randn(N, C, *shape), TDT[dt])
+    res = rounded(torch.randn(N, C, *shape), TDT[dt]) if residual else None
     conv = torch.nn.Conv3d(C, C, 1)          # identity 1x1x1 conv: the statistics come out of the conv epilogue as in the network
     alpha = torch.nn.Parameter(torch.tensor([0.2]))
     with torch.no_grad():
@@ -586,7 +520,7 @@ def _in_op(dt, N, C, residual, shape=(12, 16, 8), variant="g_copy"):
     na = _NormAct(plan, alpha)
     out = na.emit_fwd(y, stats, 0, to_cl(res, dt, DEV) if residual else None, None)
     plan.run()
-    tol = TOL[dt]
+    tol = REL_TOL[dt]
     assert rel_err(from_cl(out), yr.detach()) < tol, "forward"
     ga = to_cl(gy, dt, DEV)
     da_ref = float(ref[1].weight.grad)
@@ -608,7 +542,7 @@ def _in_op(dt, N, C, residual, shape=(12, 16, 8), variant="g_copy"):
     if variant == "g_copy":
         extras["g_copy"] = gcopy = to_cl(torch.zeros_like(gy), dt, DEV)
     else:
-        colsum = torch.full((rup(C, 4),), _SENTINEL, dtype=torch.float32, device=DEV)     # (the pass overwrites columns [0, C))
+        colsum = torch.full((rup(C, 4),), GRAD_SENTINEL, dtype=torch.float32, device=DEV)     # (the pass overwrites columns [0, C))
         extras["colsum_out"] = colsum.data_ptr()
     dy = na.emit_bwd(ga, **extras)
     plan.run()
@@ -627,7 +561,7 @@ def _in_op(dt, N, C, residual, shape=(12, 16, 8), variant="g_copy"):
         # of the order of sum |dy|, and a wrong column, a dropped row or a dropped sample shows.  The kernels are functions of
         # (g, y, mean, rstd, alpha); the reference is the same formula in float64.
         na.mr[..., 0] += 0.625 / na.mr[..., 1]
-        colsum.fill_(_SENTINEL)
+        colsum.fill_(GRAD_SENTINEL)
         plan.store.flat_g.zero_()
         dy2 = na.emit_bwd(ga, **extras)
         plan.run()
@@ -648,7 +582,7 @@ def test_instnorm_prelu_op_fwd_bwd(dt, residual, N, C):
 @pytest.mark.parametrize("max_wg", ["1", "3"])
 @pytest.mark.parametrize("dt,N,C", [(BF16, 2, 32), (F32, 2, 64), (BF16, 1, 256)])
 def test_instnorm_prelu_op_with_capped_grids(monkeypatch, max_wg, dt, N, C):
-    monkeypatch.setenv("CTSEG_MAX_WG", max_wg)
+    cap_env(monkeypatch, max_wg)
     _in_op(dt, N, C, True, shape=(16, 12, 24))
 
 

@@ -3,12 +3,13 @@ their shared skeleton (norm_common.h), element by element against float64.
 
 The older op tests (_in_op, _bn_op) bound max |error| / max |reference| of a whole tensor by 2.5e-2 (bf16) and allow the fp32 scalars the
 same; here every stored element and every sum is held to float64.  The kernels are functions of (g, y, float32 tables, alpha): the
-reference reads the same float32 table values as float64, so it is exact up to fp32 arithmetic.  Operands are drawn with a seeded
+reference (norm_prelu_terms / norm_prelu_dy of reference_ops.py) reads the same float32 table values as float64, so it is exact up
+to fp32 arithmetic.  Operands are drawn with a seeded
 generator and rounded to the storage type; gamma in [0.5, 1.5] with channel 1 = 2^-6 and the last channel = -0.75, beta = 0.3 randn,
 alpha = 0.2.  No pre-activation (xhat; gamma * xhat + beta; y * scale + shift) lies within 1e-3 of the PReLU kink: elements that did
 were moved by +0.25 and rounded again (one round sufficed in every case), then the condition is ASSERTED; no element is left out.
 
-Bounds.  Per element (out, dy): |got - ref64| <= u * |ref64| + 16 * e32, e32 = largest |float32 - float64| evaluation of the case
+Bounds (helpers.elem_bound / check_elems / sum_bound).  Per element (out, dy): |got - ref64| <= u * |ref64| + 16 * e32, e32 = largest |float32 - float64| evaluation of the case
 (asserted > 0), u = 2^-8 bf16, 2^-10 fp16, 0 fp32; g_copy bit-equal to g.  Sums (reduce partials, sums table, d gamma, d beta,
 da_part, colsum_out, ctseg_colsum): error normalised by the sum of |terms|, at most 16 x the normalised error of the plain float32
 evaluation, and 0 < bound < 1 / (4 * rows summed) is asserted, so one dropped or doubled row fails.  d alpha is one scalar: see
@@ -65,13 +66,11 @@ from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd._native import BF16, F16, F32  # noqa: E402
 from capstone_amd.engine import BufferStore, GemmLayer, rup  # noqa: E402
 from capstone_amd.plan import Plan, _BatchNormAct, _bwd_row_ranges, _NormAct  # noqa: E402
-from helpers import ACT_SENTINEL, GRAD_SENTINEL, MiniPlan, from_cl, to_cl  # noqa: E402
-from test_gpu_conv_extras import _sum_bounds  # noqa: E402
+from helpers import ACT_SENTINEL, GRAD_SENTINEL, TDT, MiniPlan, check_elems, elem_bound, from_cl, sum_bound, to_cl  # noqa: E402
+from reference_ops import norm_prelu_dy, norm_prelu_terms, rounded  # noqa: E402
 
 DEV = "cuda:0"
-TDT = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16}
 DT_ID = {F32: "fp32", BF16: "bf16", F16: "fp16"}
-ULP = {BF16: 2.0 ** -8, F16: 2.0 ** -10, F32: 0.0}
 ALPHA = 0.2
 EPS = 1e-5
 KINK = 1e-3
@@ -86,10 +85,6 @@ def _call(name, *args):
 
 def _sync():
     torch.cuda.synchronize()
-
-
-def _rounded(t, dt):
-    return t.to(TDT[dt]).float()
 
 
 def _dev32(a):
@@ -153,9 +148,9 @@ def _data(kind, N, C, S, dt, moved=False):
     y * scale + shift).  moved: the mean table moved by 0.625 standard deviations.  No element's pre-activation, evaluated in
     float64 on the float32 tables, lies within KINK of the PReLU kink (asserted)."""
     g = torch.Generator().manual_seed(zlib.crc32(repr((kind, N, C, S, dt, moved)).encode()))
-    y = _rounded(torch.randn(N, C, S, generator=g) * 1.3 + 0.4, dt)
-    gy = _rounded(torch.randn(N, C, S, generator=g), dt)
-    res = _rounded(torch.randn(N, C, S, generator=g), dt)
+    y = rounded(torch.randn(N, C, S, generator=g) * 1.3 + 0.4, TDT[dt])
+    gy = rounded(torch.randn(N, C, S, generator=g), TDT[dt])
+    res = rounded(torch.randn(N, C, S, generator=g), TDT[dt])
     dims = (2,) if kind == "in" else (0, 2)
     m64 = y.double().mean(dims, keepdim=True)
     v64 = y.double().var(dims, unbiased=False, keepdim=True)
@@ -179,7 +174,7 @@ def _data(kind, N, C, S, dt, moved=False):
         if not bool(near.any()):
             break
         assert rounds < 8
-        y = _rounded(torch.where(near, y + 0.25, y), dt)
+        y = rounded(torch.where(near, y + 0.25, y), TDT[dt])
     assert float(pre(y).abs().min()) >= KINK
     d.y, d.kink_rounds = y, rounds
     return d
@@ -196,38 +191,22 @@ def _fwd_ref(d, T, residual):
     return o + d.res.to(T) if residual else o
 
 
+def _bwd_args(d, T):
+    """(g, y, mean, rstd, alpha, gamma, beta) of a case in precision T; gamma and beta None for InstanceNorm"""
+    gb = (None, None) if d.kind == "in" else (d.gamma.to(T), d.beta.to(T))
+    return (d.g.to(T), d.y.to(T), d.m.to(T), d.r.to(T), _al(T)) + gb
+
+
 def _bwd_terms(d, T):
     """xhat, dz (the gradient behind the PReLU) and the three summed terms, in precision T"""
-    y, g = d.y.to(T), d.g.to(T)
-    xh = (y - d.m.to(T)) * d.r.to(T)
-    pre = xh if d.kind == "in" else d.gamma.to(T) * xh + d.beta.to(T)
-    dz = g * torch.where(pre > 0, torch.ones((), dtype=T), _al(T))
-    return xh, dz, (dz, dz * xh, torch.where(pre > 0, torch.zeros((), dtype=T), g * pre))
+    return norm_prelu_terms(*_bwd_args(d, T))
 
 
 def _bwd_dy(d, T, per_sample=False):
-    xh, dz, (t1, t2, _) = _bwd_terms(d, T)
-    dims = (2,) if (d.kind == "in" or per_sample) else (0, 2)
-    scale = d.r.to(T) if d.kind == "in" else d.gamma.to(T) * d.r.to(T)
-    return scale * (dz - t1.mean(dims, keepdim=True) - xh * t2.mean(dims, keepdim=True))
+    return norm_prelu_dy(*_bwd_args(d, T), dims=(2,) if (d.kind == "in" or per_sample) else (0, 2))
 
 
-# ---- the two bounds -------------------------------------------------------------------------------------------------------------
-def _elem_bound(ref64, ref32, dt):
-    e32 = float((ref32.double() - ref64).abs().max())
-    assert e32 > 0.0
-    return ULP[dt] * ref64.abs() + 16.0 * e32, e32
-
-
-def _check_elems(tag, got, ref64, ref32, dt):
-    """every element: |got - ref64| <= u * |ref64| + 16 * e32"""
-    bound, e32 = _elem_bound(ref64, ref32, dt)
-    ratio = float(((got.double() - ref64).abs() / bound).max())
-    print(f"{tag}: worst error / bound {ratio:.3f} (e32 {e32:.2e})")
-    assert ratio <= 1.0, (tag, ratio)
-    return ratio
-
-
+# ---- the checks (the bounds per element and per sum: helpers) -------------------------------------------------------------------
 def _check_rows(tag, flat, N, S, ld, C, store, ref64, ref32, dt):
     """an output the test pre-filled with the sentinel: columns [0, C) within the bound, [C, store) zero, the rest untouched"""
     got = flat.float().cpu()
@@ -235,26 +214,13 @@ def _check_rows(tag, flat, N, S, ld, C, store, ref64, ref32, dt):
     assert bool((tail == ACT_SENTINEL).all()), f"{tag}: written behind the last row"
     assert bool((body[..., store:] == ACT_SENTINEL).all()), f"{tag}: columns [{store}, {ld}) were written"
     assert bool((body[..., C:store] == 0).all()), f"{tag}: pad columns [{C}, {store}) are not zero"
-    return _check_elems(tag, body[..., :C].permute(0, 2, 1), ref64, ref32, dt)
-
-
-def _sum_bound(tag, t64, t32, dims, rows, div=1.0):
-    """float64 sums of t64 over ``dims``, the sums of |terms|, and the bound on the error normalised by them: 16 x the normalised
-    error of the plain float32 evaluation (sum / div, as the kernel stores it), which must lie under 1 / (4 * rows)"""
-    s64, a64 = t64.sum(dims), t64.abs().sum(dims)
-    s32 = (t32.sum(dims) / div).double() * div
-    live = a64 > 0
-    norm = torch.where(live, a64, torch.ones_like(a64))
-    f32 = float(((s32 - s64).abs() / norm)[live].max())
-    bound, cap = 16.0 * f32, 1.0 / (4.0 * rows)
-    assert 0.0 < bound < cap, (tag, bound, cap)
-    return s64, norm, live, bound
+    return check_elems(tag, body[..., :C].permute(0, 2, 1), ref64, ref32, dt)
 
 
 def _check_sums(tag, got, t64, t32, dims, rows, div=1.0):
-    """``got`` (= sums / div) against the float64 sums, error normalised by the sum of |terms| (_sum_bound).  A sum none of whose
+    """``got`` (= sums / div) against the float64 sums, error normalised by the sum of |terms| (helpers.sum_bound).  A sum none of whose
     terms is nonzero must be exactly 0."""
-    s64, norm, live, bound = _sum_bound(tag, t64, t32, dims, rows, div)
+    s64, norm, live, bound = sum_bound(tag, t64, t32, dims, rows, div)
     got = got.double().cpu() * div
     assert got.shape == s64.shape, (got.shape, s64.shape)
     assert bool((got[~live] == 0).all()), f"{tag}: a sum without terms is not 0"
@@ -268,9 +234,9 @@ def _check_slope(tag, got, t64, t32, dims, rows):
     """d alpha, one scalar: the float32 cast of the float64 sum of the per-channel slope terms (da_part), which the reduce pass
     accumulated in fp32.  The plain float32 sum of all terms is ONE sample of a rounding error (5e-10 of the sum of |terms| at
     (2, 10, 125) fp32, where the kernel's 6.7e-10 was 1.26 x 16 times it), not a bound.  The kernel's order of operations gives
-    one: every da_part lies within the per-channel bound of its own sum of |terms| (_sum_bound over ``dims``), so their float64
+    one: every da_part lies within the per-channel bound of its own sum of |terms| (sum_bound over ``dims``), so their float64
     sum lies within that bound of the total, and the cast adds at most 2^-24 of it."""
-    _, _, _, bound = _sum_bound(tag, t64, t32, dims, rows)
+    _, _, _, bound = sum_bound(tag, t64, t32, dims, rows)
     bound += 2.0 ** -24
     assert bound < 1.0 / (4.0 * rows)
     s64, a64 = t64.sum(), t64.abs().sum()
@@ -555,7 +521,7 @@ def test_instnorm_prelu_fwd_without_a_norm_adds_the_residual():
     _call("ctseg_instnorm_prelu_fwd", BF16, y.data_ptr(), 16, None, None, res.data_ptr(), 24, out.data_ptr(), 24, 2, 315, 10)
     _sync()
     body = out.float().cpu()[:2 * 315 * 24].view(2, 315, 24)
-    assert torch.equal(body[..., :10].permute(0, 2, 1), _rounded(d.y + d.res, BF16))
+    assert torch.equal(body[..., :10].permute(0, 2, 1), rounded(d.y + d.res, TDT[BF16]))
     assert bool((body[..., 10:16] == 0).all()) and bool((body[..., 16:] == ACT_SENTINEL).all())
 
 
@@ -716,7 +682,7 @@ def test_batchnorm_statistics_span_the_batch():
     for dt in TRAIN2:
         d = _data("bn", 3, 256, 315, dt)
         ref = _bwd_dy(d, F64)
-        bound, _ = _elem_bound(ref, _bwd_dy(d, F32T), dt)
+        bound, _ = elem_bound(ref, _bwd_dy(d, F32T), dt)
         apart = float(((ref - _bwd_dy(d, F64, per_sample=True)).abs() / bound).max())
         print(f"batch against per-sample sums, {DT_ID[dt]}: up to {apart:.0f} bounds apart")
         assert apart > 100.0
@@ -757,7 +723,7 @@ def test_instnorm_bwd_apply_colsum(N, C, dt, cap_per_sample):
     assert bool((got[C:] == GRAD_SENTINEL).all()), "column sums beyond C"
     assert bool((cs_part[p_cap:] == GRAD_SENTINEL).all()), "partial rows beyond P_cap"
     _check_sums(f"{b.tag} colsum_out P_cap={p_cap}", got[:C], dy64, dy32, (0, 2), N * S)
-    s64, a64, _, bound = _sum_bound(b.tag, dy64, dy32, (0, 2), N * S)
+    s64, a64, _, bound = sum_bound(b.tag, dy64, dy32, (0, 2), N * S)
     assert float((s64.abs() / a64).min()) > 100 * bound, "the moved mean leaves column sums far above the bound"
 
 
@@ -817,9 +783,9 @@ def test_batchnorm_plan_node(C, dt):
     N, dims, S = 2, (7, 9, 5), 315
     M = N * S
     g = torch.Generator().manual_seed(C + 100 * dt)
-    x = _rounded(torch.randn(N, C, *dims, generator=g) * 1.5 + 0.3, dt)
-    gy = _rounded(torch.randn(N, C, *dims, generator=g), dt)
-    res = _rounded(torch.randn(N, C, *dims, generator=g), dt)
+    x = rounded(torch.randn(N, C, *dims, generator=g) * 1.5 + 0.3, TDT[dt])
+    gy = rounded(torch.randn(N, C, *dims, generator=g), TDT[dt])
+    res = rounded(torch.randn(N, C, *dims, generator=g), TDT[dt])
     conv, bn, act = torch.nn.Conv3d(C, C, 1), torch.nn.BatchNorm3d(C, momentum=0.25), torch.nn.PReLU()
     with torch.no_grad():
         conv.weight.copy_(torch.eye(C).reshape(C, C, 1, 1, 1))     # identity: the statistics come out of a conv epilogue
@@ -841,7 +807,7 @@ def test_batchnorm_plan_node(C, dt):
         if not bool(near.any()):
             break
         assert rounds < 8
-        x = _rounded(torch.where(near, x + 0.25, x), dt)
+        x = rounded(torch.where(near, x + 0.25, x), TDT[dt])
     plan = MiniPlan([conv.weight, conv.bias, bn.weight, bn.bias, act.weight], DEV, dt, 3)
     plan.bn_train = True
     plan.engine = types.SimpleNamespace(bufs=BufferStore([bn], plan.device))
@@ -858,7 +824,9 @@ def test_batchnorm_plan_node(C, dt):
     yv = from_cl(y).reshape(N, C, S)                 # what the passes normalise: the identity conv's stored output
     # statistics: float64 on the stored y, the partial-sum bounds of test_gpu_conv_extras.py carried through
     yb = yv.permute(1, 0, 2).reshape(1, C, M)
-    s64, q64, a64, bs, bq = _sum_bounds(yb.double(), yb, M)
+    s64, a64, live, bs = sum_bound("sum", yb.double(), yb, (2,), M)
+    q64, _, liveq, bq = sum_bound("sumsq", yb.double() * yb.double(), yb * yb, (2,), M)
+    assert bool(live.all()) and bool(liveq.all()), "a channel of zeros"
     mean64, ey2, eabs = s64[0] / M, q64[0] / M, a64[0] / M
     var64 = ey2 - mean64 * mean64
     rstd64 = (var64 + EPS).rsqrt()
@@ -889,13 +857,13 @@ def test_batchnorm_plan_node(C, dt):
     sc64 = gam.double() * d.r.double()
     sh64 = bet.double() - d.m.double() * sc64
     tag = f"plan node C={C} {DT_ID[dt]}"
-    _check_elems(f"{tag} out", from_cl(out).reshape(N, C, S), fwd(F64, sc64, sh64), fwd(F32T, sc64.float(), sh64.float()), dt)
+    check_elems(f"{tag} out", from_cl(out).reshape(N, C, S), fwd(F64, sc64, sh64), fwd(F32T, sc64.float(), sh64.float()), dt)
     assert bool((out.t[..., C:] == 0).all())
     ga, gc = to_cl(gy, dt, DEV), to_cl(torch.ones_like(gy), dt, DEV)
     dy = na.emit_bwd(ga, g_copy=gc)
     plan.run()
     _sync()
-    _check_elems(f"{tag} dy", from_cl(dy).reshape(N, C, S), _bwd_dy(d, F64), _bwd_dy(d, F32T), dt)
+    check_elems(f"{tag} dy", from_cl(dy).reshape(N, C, S), _bwd_dy(d, F64), _bwd_dy(d, F32T), dt)
     assert bool((dy.t[..., C:] == 0).all())
     assert torch.equal(from_cl(gc), gy), "g_copy"
     t64, t32, st = _bwd_terms(d, F64)[2], _bwd_terms(d, F32T)[2], plan.store
@@ -914,13 +882,13 @@ def test_batchnorm_plan_node(C, dt):
     rm2, rv2 = bn.running_mean.cpu().clone(), bn.running_var.cpu().clone()
     sc64 = gam.double() / (rv2.double().reshape(1, C, 1) + EPS).sqrt()
     sh64 = bet.double() - rm2.double().reshape(1, C, 1) * sc64
-    xe = _rounded(torch.randn(N, C, S, generator=g) * 1.5 + 0.3, dt)
+    xe = rounded(torch.randn(N, C, S, generator=g) * 1.5 + 0.3, TDT[dt])
     for rounds in range(9):
         near = (xe.double() * sc64 + sh64).abs() < KINK
         if not bool(near.any()):
             break
         assert rounds < 8
-        xe = _rounded(torch.where(near, xe + 0.25, xe), dt)
+        xe = rounded(torch.where(near, xe + 0.25, xe), TDT[dt])
     assert float((xe.double() * sc64 + sh64).abs().min()) >= KINK
     d.y = xe
     plan.bn_train = False
@@ -929,7 +897,7 @@ def test_batchnorm_plan_node(C, dt):
     assert [p[0] for p in plan.prog] == ["ctseg_batchnorm_eval_table", "ctseg_scale_shift_prelu_fwd"]
     plan.run()
     _sync()
-    _check_elems(f"{tag} eval out", from_cl(oe).reshape(N, C, S), fwd(F64, sc64, sh64), fwd(F32T, sc64.float(), sh64.float()), dt)
+    check_elems(f"{tag} eval out", from_cl(oe).reshape(N, C, S), fwd(F64, sc64, sh64), fwd(F32T, sc64.float(), sh64.float()), dt)
     assert torch.equal(bn.running_mean.cpu(), rm2) and torch.equal(bn.running_var.cpu(), rv2) and int(bn.num_batches_tracked) == 2
 
 
@@ -938,7 +906,7 @@ def test_batchnorm_plan_node(C, dt):
 # =================================================================================================================================
 def _colsum(rows, C, dt, P, seed=0):
     g = torch.Generator().manual_seed(rows * 7 + C + seed)
-    x = _rounded(torch.randn(rows, C, generator=g) * 1.3 + 0.4, dt)
+    x = rounded(torch.randn(rows, C, generator=g) * 1.3 + 0.4, TDT[dt])
     epc, Cv = _chunks(dt, C, half_chunks=False)
     ld = Cv * epc + _wide(dt)
     xd = torch.full((rows, ld), POISON, dtype=TDT[dt])

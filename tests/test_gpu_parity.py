@@ -17,7 +17,8 @@ pytestmark = pytest.mark.gpu
 from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd import segloss  # noqa: E402
 from capstone_amd._native import BF16, F32  # noqa: E402
-from helpers import MiniPlan, from_cl, rel_err, run_conv_module, to_cl  # noqa: E402
+from helpers import MiniPlan, check_conv_module, from_cl, rel_err, run_conv_module, to_cl  # noqa: E402
+from reference_ops import conv_module  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -63,17 +64,7 @@ def test_conv_ops_vs_torch_cpu(golden, tag, dt, tol):
 def test_halo_kernel_layers_vs_torch_cpu(cin, cout, shape, dt, tol):
     """3x3x3 stride-1 layers that take the LDS-halo kernel (Cg*size in {32,64} bytes, Cn <= 32), incl. ragged tiles."""
     torch.manual_seed(cin * 100 + cout)
-    mod = torch.nn.Conv3d(cin, cout, 3, 1, 1)
-    x = torch.randn(shape[0], cin, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
-    yy, gx, gw, gb = run_conv_module(mod, x, gy, dt, DEV)
-    assert rel_err(yy, y.detach()) < tol, "forward"
-    assert rel_err(gx, xr.grad) < tol, "input gradient"
-    assert rel_err(gw, mod.weight.grad) < tol, "weight gradient"
-    assert rel_err(gb, mod.bias.grad) < tol, "bias gradient"
+    check_conv_module(conv_module("conv", cin, cout), shape, dt, DEV, tol)
 
 
 @pytest.mark.parametrize("kind,cin,cout,shape", [("convT", 64, 10, (1, 8, 8, 8)), ("convT", 32, 8, (2, 5, 9, 12)),
@@ -82,21 +73,7 @@ def test_halo_kernel_layers_vs_torch_cpu(cin, cout, shape, dt, tol):
 def test_up_halo_kernel_vs_torch_cpu(kind, cin, cout, shape):
     """8-class stride-2 passes that take conv_up_halo (bf16, gathered channels*2 in {64,128} bytes, <= 16 columns):
     ConvTranspose3d forward, and the input gradient of a stride-2 Conv3d; ragged tiles included."""
-    torch.manual_seed(cin + cout)
-    if kind == "convT":
-        mod = torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1)
-    else:
-        mod = torch.nn.Conv3d(cin, cout, 3, 2, 1)
-    x = torch.randn(shape[0], cin, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
-    yy, gx, gw, gb = run_conv_module(mod, x, gy, BF16, DEV)
-    assert rel_err(yy, y.detach()) < 2.5e-2, "forward"
-    assert rel_err(gx, xr.grad) < 2.5e-2, "input gradient"
-    assert rel_err(gw, mod.weight.grad) < 2.5e-2, "weight gradient"
-    assert rel_err(gb, mod.bias.grad) < 2.5e-2, "bias gradient"
+    _check_conv_module(kind, cin, cout, shape, seed=cin + cout)
 
 
 @pytest.mark.parametrize("kind,cin,cout,shape", [("conv", 64, 64, (2, 16, 16, 12)), ("conv", 64, 64, (1, 9, 20, 13)),
@@ -104,6 +81,8 @@ def test_up_halo_kernel_vs_torch_cpu(kind, cin, cout, shape):
                                                  ("convT", 128, 32, (2, 6, 20, 12)), ("conv_s2", 32, 128, (1, 32, 32, 16)),
                                                  ("conv_s2", 32, 128, (1, 18, 40, 24))])
 def test_streamed_weight_halo_kernel_vs_torch_cpu(kind, cin, cout, shape):
+    """passes that take conv_halo_sw (bf16): 64->64 k3 s1 forward + input gradient (one class), ConvTranspose3d 128->32
+    forward and the input gradient of a stride-2 conv 32->128 (8 parity classes); both tile-axis mappings, ragged tiles."""
     _check_conv_module(kind, cin, cout, shape)
 
 
@@ -149,24 +128,10 @@ def test_weight_gradient_with_xcd_grouped_slabs_vs_torch_cpu(kind, cin, cout, sh
     _check_conv_module(kind, cin, cout, shape)
 
 
-def _check_conv_module(kind, cin, cout, shape):
-    """passes that take conv_halo_sw (bf16): 64->64 k3 s1 forward + input gradient (one class), ConvTranspose3d 128->32
-    forward and the input gradient of a stride-2 conv 32->128 (8 parity classes); both tile-axis mappings, ragged tiles."""
-    torch.manual_seed(cin + cout + shape[3])
-    if kind == "convT":
-        mod = torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1)
-    else:
-        mod = torch.nn.Conv3d(cin, cout, 3, 2 if kind == "conv_s2" else 1, 1)
-    x = torch.randn(shape[0], cin, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
-    yy, gx, gw, gb = run_conv_module(mod, x, gy, BF16, DEV)
-    assert rel_err(yy, y.detach()) < 2.5e-2, "forward"
-    assert rel_err(gx, xr.grad) < 2.5e-2, "input gradient"
-    assert rel_err(gw, mod.weight.grad) < 2.5e-2, "weight gradient"
-    assert rel_err(gb, mod.bias.grad) < 2.5e-2, "bias gradient"
+def _check_conv_module(kind, cin, cout, shape, seed=None):
+    """all four bf16 passes of one seeded 3 x 3 x 3 layer (reference_ops.conv_module) against torch's float32 autograd on the CPU"""
+    torch.manual_seed(cin + cout + shape[3] if seed is None else seed)
+    check_conv_module(conv_module(kind, cin, cout), shape, BF16, DEV, 2.5e-2)
 
 
 @pytest.mark.parametrize("kind,cin,cout,shape", [("conv_s2", 32, 128, (1, 32, 32, 24)), ("conv_s2", 32, 64, (2, 18, 40, 34)),
@@ -175,21 +140,7 @@ def _check_conv_module(kind, cin, cout, shape):
 def test_stride2_halo_kernel_vs_torch_cpu(kind, cin, cout, shape):
     """stride-2 passes that take conv_down_halo (bf16, 16 / 32 gathered channels, >= 48 columns): Conv3d k3 s2 forward and the
     input gradient of a ConvTranspose3d (a stride-2 conv over dOut); odd extents, both tile-axis mappings, two column blocks."""
-    torch.manual_seed(cin * 3 + cout + shape[2])
-    if kind == "convT":
-        mod = torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1)
-    else:
-        mod = torch.nn.Conv3d(cin, cout, 3, 2, 1)
-    x = torch.randn(shape[0], cin, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
-    yy, gx, gw, gb = run_conv_module(mod, x, gy, BF16, DEV)
-    assert rel_err(yy, y.detach()) < 2.5e-2, "forward"
-    assert rel_err(gx, xr.grad) < 2.5e-2, "input gradient"
-    assert rel_err(gw, mod.weight.grad) < 2.5e-2, "weight gradient"
-    assert rel_err(gb, mod.bias.grad) < 2.5e-2, "bias gradient"
+    _check_conv_module(kind, cin, cout, shape, seed=cin * 3 + cout + shape[2])
 
 
 @pytest.mark.parametrize("cout,shape", [(16, (1, 16, 16, 8)), (64, (2, 8, 16, 16)), (32, (1, 10, 12, 8)), (48, (1, 8, 8, 24))])
@@ -197,16 +148,7 @@ def test_stem_kernels_vs_torch_cpu(cout, shape):
     """single-channel 3x3x3 stride-2 conv (conv_stem.hip: forward with LDS input patch, weight gradient with 4 slabs per
     workgroup), bf16, ragged tiles included."""
     torch.manual_seed(cout)
-    mod = torch.nn.Conv3d(1, cout, 3, 2, 1)
-    x = torch.randn(shape[0], 1, *shape[1:])
-    y = mod(x)
-    gy = torch.randn_like(y)
-    y.backward(gy)
-    yy, gx, gw, gb = run_conv_module(mod, x, gy, BF16, DEV)
-    assert gx is None
-    assert rel_err(yy, y.detach()) < 2.5e-2, "forward"
-    assert rel_err(gw, mod.weight.grad) < 2.5e-2, "weight gradient"
-    assert rel_err(gb, mod.bias.grad) < 2.5e-2, "bias gradient"
+    check_conv_module(conv_module("conv_s2", 1, cout), shape, BF16, DEV, 2.5e-2)      # (no input gradient: the first layer)
 
 
 @pytest.mark.parametrize("dt,tol", [(F32, 1e-5), (BF16, 2e-2)])

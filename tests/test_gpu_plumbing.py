@@ -69,7 +69,7 @@ pytestmark = pytest.mark.gpu
 from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd._native import BF16, F16, F32, NativeError  # noqa: E402
 from capstone_amd.engine import GemmLayer  # noqa: E402
-from helpers import MiniPlan  # noqa: E402
+from helpers import MiniPlan, rel_err_nonzero  # noqa: E402
 
 DEV = "cuda:0"
 DTS = [F32, BF16, F16]
@@ -564,14 +564,6 @@ def _adam_torch(p0, g0, gscale, betas, steps, carried):
     return out
 
 
-def _rel_err(x, x64):
-    """(max, rms) of |x - x64| / |x64| over x64 != 0, and whether x is exactly 0 wherever x64 is"""
-    nz = x64 != 0
-    with np.errstate(invalid="ignore", over="ignore"):
-        r = np.abs(x[nz].astype(np.float64) - x64[nz]) / np.abs(x64[nz])
-        return float(r.max()), float(np.sqrt(np.mean(r * r))), bool((x[~nz] == 0).all())
-
-
 def _adam_bounds(p0, g0, gscale, betas, steps=(1, 2, 10), carried=True):
     """-> (float64 reference, torch fp32 trajectory, bounds[checkpoint][buffer] = (max, rms)); asserts on the CPU that both wrong
     restatements exceed a bound at every checkpoint"""
@@ -582,13 +574,13 @@ def _adam_bounds(p0, g0, gscale, betas, steps=(1, 2, 10), carried=True):
     for ck in ref:
         bounds[ck] = []
         for x, x64 in zip(tor[ck], ref[ck]):
-            mx, rms, zeros = _rel_err(x, x64)
+            mx, rms, zeros = rel_err_nonzero(x, x64)
             assert zeros and mx < 1e-5, (ck, mx)               # torch in fp32 is itself close (m of step 1 at beta1 = 0.5 is exact)
             bounds[ck].append((4 * mx, 4 * rms))
     for mutant in ("omb2", "step"):
         mut = _adam_restated(p0, g0, gscale, betas, steps, carried, mutant)
         for ck in ref:
-            errs = [_rel_err(x, x64)[:2] for x, x64 in zip(mut[ck], ref[ck])]
+            errs = [rel_err_nonzero(x, x64)[:2] for x, x64 in zip(mut[ck], ref[ck])]
             if ck == 1000 and all(e == 0 for es in errs for e in es):
                 assert b2 ** 999 < 1e-17 and mutant == "step"      # 1 - beta2^999 == 1 - beta2^1000 == 1 in float64: not wrong here
                 continue
@@ -637,7 +629,7 @@ def _adam_device_run(p0, g0, n, gscale, betas, steps, carried):
 def _adam_check(got, ref, tor, bounds, n, worst):
     for ck in got:
         for name, x, x64, (bmax, brms) in zip("pmv", got[ck], ref[ck], bounds[ck]):
-            mx, rms, zeros = _rel_err(x, x64[:n])
+            mx, rms, zeros = rel_err_nonzero(x, x64[:n])
             worst[name] = max(worst[name], mx / bmax if mx else 0.0, rms / brms if n >= 1023 and rms else 0.0)
             assert zeros, (name, ck, n)
             assert mx <= bmax, f"{name} after step {ck}, n={n}: max relative error {mx:.3e} > 4 x torch fp32's ({bmax:.3e})"

@@ -5,7 +5,6 @@
   * an optimizer update on one plan reaching every other cached plan,
   * the checkpoint layout of the native step's Adam state.
 """
-import json
 import os
 
 import numpy as np
@@ -16,17 +15,11 @@ pytestmark = pytest.mark.gpu
 
 from capstone_amd import segloss  # noqa: E402
 
+from helpers import dump  # noqa: E402
+from reference_ops import conv_module  # noqa: E402
+
 DEV = "cuda:0"
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-
-
-def _dump(name, obj):
-    try:
-        os.makedirs(OUT, exist_ok=True)
-        with open(os.path.join(OUT, name), "w") as f:
-            json.dump(obj, f, indent=1)
-    except OSError:
-        pass
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -201,11 +194,11 @@ def test_full_size_fp32_step_vs_oracle():
         e_cpu = float((F["g32"][k].flatten().double() - g64).norm() / g64.norm())
         rows.append((e_gpu, e_cpu, k))
     worst = sorted(rows, reverse=True)[:6]
-    _dump("full_size_fp32_vs_oracle.json", {"logits_max_abs_err": err, "loss": loss.item(), "oracle_loss": oloss,
-                                            "oracle_loss_fp64": F["l64"], "dice": dice, "oracle_dice": odice,
-                                            "safe_fraction": float(safe.float().mean()), "mask_flips_total": flips,
-                                            "voxels": int(opred.numel()),
-                                            "worst_grad_rel_err_vs_fp64 (gpu, cpu_fp32, tensor)": worst})
+    dump(OUT, "full_size_fp32_vs_oracle.json", {"logits_max_abs_err": err, "loss": loss.item(), "oracle_loss": oloss,
+                                                "oracle_loss_fp64": F["l64"], "dice": dice, "oracle_dice": odice,
+                                                "safe_fraction": float(safe.float().mean()), "mask_flips_total": flips,
+                                                "voxels": int(opred.numel()),
+                                                "worst_grad_rel_err_vs_fp64 (gpu, cpu_fp32, tensor)": worst})
     assert err < 1e-3, err
     assert abs(loss.item() - oloss) < 1e-4 * abs(oloss)
     assert abs(dice - odice) <= 0.002
@@ -257,7 +250,7 @@ def test_full_size_bf16_fused_head_step_vs_oracle():
         a = eng.store.grad_view(q).cpu().flatten().double()
         cos.append((float(torch.dot(a, g64) / (a.norm() * g64.norm())), float((a - g64).norm() / g64.norm()), k))
     worst = sorted(cos)[:6]
-    _dump("full_size_bf16_fused_head_vs_oracle.json", {
+    dump(OUT, "full_size_bf16_fused_head_vs_oracle.json", {
         "logits_max_abs_err": err, "logits_rel_err": rel, "loss": loss.item(), "oracle_loss": oloss,
         "loss_rel_err": abs(loss.item() - oloss) / abs(oloss), "dice": dice, "oracle_dice": odice,
         "argmax_agreement": agree, "safe_fraction": float(safe.float().mean()),
@@ -347,8 +340,8 @@ def test_k_step_trajectory_tracks_the_oracle(trajectory_oracle, task, precision)
         dices.append(float(m.logged["Mean Dice Score (train)"]))
     dl = [abs(a - b) / abs(b) for a, b in zip(losses, olosses)]
     dd = [abs(a - b) for a, b in zip(dices, odices)]
-    _dump(f"trajectory_{task}_{precision}.json", {"steps": len(olosses), "loss": losses, "oracle_loss": olosses, "dice": dices,
-                                                  "oracle_dice": odices, "max_rel_loss_diff": max(dl), "max_abs_dice_diff": max(dd)})
+    dump(OUT, f"trajectory_{task}_{precision}.json", {"steps": len(olosses), "loss": losses, "oracle_loss": olosses, "dice": dices,
+                                                      "oracle_dice": odices, "max_rel_loss_diff": max(dl), "max_abs_dice_diff": max(dd)})
     assert olosses[-1] < 0.8 * olosses[0], "the curve must actually descend"
     if task == "learnable":
         assert max(odices) > 0.2, "the Dice curve must actually climb"
@@ -447,24 +440,15 @@ def test_fp16_forward_and_input_gradient_passes_vs_torch_cpu(kind, cin, cout, sh
     the inference plans use.  Half keeps 11 significant bits: relative L-inf error < 4e-3 (bf16's bound in this file's
     siblings is 2.5e-2)."""
     from capstone_amd import _native as nat
-    from helpers import rel_err, run_conv_module
+    from helpers import autograd_conv_module, rel_err, run_conv_module
     torch.manual_seed(cin + 3 * cout + shape[2])
-    if kind == "convT":
-        mod = torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1)
-    elif kind == "conv1":
-        mod = torch.nn.Conv3d(cin, cout, 1, 1, 0)
-    else:
-        mod = torch.nn.Conv3d(cin, cout, 3, 2 if kind == "conv_s2" else 1, 1)
-    x = torch.randn(shape[0], cin, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
+    mod = conv_module("conv", cin, cout, k=1) if kind == "conv1" else conv_module(kind, cin, cout)
+    x, gy, y, gx_ref = autograd_conv_module(mod, shape)
     yy, gx, gw, gb = run_conv_module(mod, x, gy, nat.F16, DEV)
     assert gw is None and gb is None
-    assert rel_err(yy, y.detach()) < 4e-3, family + ": forward"
+    assert rel_err(yy, y) < 4e-3, family + ": forward"
     if gx is not None:
-        assert rel_err(gx, xr.grad) < 4e-3, family + ": input gradient"
+        assert rel_err(gx, gx_ref) < 4e-3, family + ": input gradient"
 
 
 def test_fp16_instnorm_prelu_and_saturating_store():
@@ -604,14 +588,10 @@ def test_transposed_conv_weight_gradient_lds_halo_kernel(monkeypatch, cout, shap
     capstone/models/unet.py) vs torch on the CPU and vs the generic split-K kernel it replaces: ragged tiles on every axis,
     several samples, extents smaller than one tile."""
     from capstone_amd._native import BF16
-    from helpers import run_conv_module, rel_err
+    from helpers import autograd_conv_module, run_conv_module, rel_err
     torch.manual_seed(cout + shape[1])
-    mod = torch.nn.ConvTranspose3d(64, cout, 3, 2, 1, output_padding=1)
-    x = torch.randn(shape[0], 64, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
+    mod = conv_module("convT", 64, cout)
+    x, gy, _, _ = autograd_conv_module(mod, shape)
     _, _, gw, _ = run_conv_module(mod, x, gy, BF16, DEV)
     assert rel_err(gw, mod.weight.grad) < 2.5e-2
     monkeypatch.setenv("CTSEG_NO_WGRAD_UP", "1")
@@ -678,15 +658,11 @@ def test_head_transposed_conv_backward_reads_12_wide_gradient_rows(cout, shape):
     give the BITS of the 16-wide layout, and agree with torch on the CPU.  Ragged tiles, several samples."""
     from capstone_amd import _native as nat
     from capstone_amd.engine import GemmLayer
-    from helpers import MiniPlan, to_cl, from_cl, rel_err
+    from helpers import MiniPlan, autograd_conv_module, to_cl, from_cl, rel_err
     torch.manual_seed(cout + shape[2])
-    mod = torch.nn.ConvTranspose3d(64, cout, 3, 2, 1, output_padding=1)
-    x = torch.randn(shape[0], 64, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
-    ref_gx, ref_gw = xr.grad.clone(), mod.weight.grad.detach().clone()      # (the plans below re-home the parameters and their .grad)
+    mod = conv_module("convT", 64, cout)
+    x, gy, _, ref_gx = autograd_conv_module(mod, shape)
+    ref_gw = mod.weight.grad.detach().clone()      # (the plans below re-home the parameters and their .grad)
     res = {}
     for ld in (16, 12):
         plan = MiniPlan([mod.weight, mod.bias], DEV, nat.BF16, 3)
@@ -714,15 +690,11 @@ def test_stride2_conv_32_to_128_with_register_resident_weights(monkeypatch, shap
     and weight gradient vs torch on the CPU, forward also vs the generic kernel it replaces (same bf16 operands, another sum order).
     Ragged 8 x 8 faces, each volume axis as the 1-deep tile axis, two samples."""
     from capstone_amd._native import BF16
-    from helpers import run_conv_module, rel_err
+    from helpers import autograd_conv_module, run_conv_module, rel_err
     torch.manual_seed(shape[1] + shape[3])
-    mod = torch.nn.Conv3d(32, 128, 3, 2, 1)
-    x = torch.randn(shape[0], 32, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
-    ref_y, ref_gx, ref_gw = y.detach().clone(), xr.grad.clone(), mod.weight.grad.detach().clone()
+    mod = conv_module("conv_s2", 32, 128)
+    x, gy, ref_y, ref_gx = autograd_conv_module(mod, shape)
+    ref_gw = mod.weight.grad.detach().clone()
     yy, gx, gw, _ = run_conv_module(mod, x, gy, BF16, DEV)
     assert rel_err(yy, ref_y) < 2.5e-2 and rel_err(gx, ref_gx) < 2.5e-2 and rel_err(gw, ref_gw) < 2.5e-2
     monkeypatch.setenv("CTSEG_NO_DOWN_R", "1")
@@ -744,17 +716,10 @@ def test_generic_weight_gradient_offset_addressing_equals_the_64_bit_chain(monke
     torch.nn.Conv3d / ConvTranspose3d as in the reference's loss.backward(), capstone/volumetric/base_trainer.py:80-82).
     Odd extents (carries on every axis inside a 32-row stage), several samples, stride 2, the transposed conv's swapped roles."""
     from capstone_amd._native import BF16
-    from helpers import run_conv_module, rel_err
+    from helpers import autograd_conv_module, run_conv_module, rel_err
     torch.manual_seed(cin + cout + shape[2])
-    if kind == "convT":
-        mod = torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1)
-    else:
-        mod = torch.nn.Conv3d(cin, cout, 3, 2 if kind == "conv_s2" else 1, 1)
-    x = torch.randn(shape[0], cin, *shape[1:])
-    xr = x.clone().requires_grad_(True)
-    y = mod(xr)
-    gy = torch.randn_like(y)
-    y.backward(gy)
+    mod = conv_module(kind, cin, cout)
+    x, gy, _, _ = autograd_conv_module(mod, shape)
     _, _, gw, gb = run_conv_module(mod, x, gy, BF16, DEV)
     assert rel_err(gw, mod.weight.grad) < 2.5e-2
     assert rel_err(gb, mod.bias.grad) < 2.5e-2
@@ -772,10 +737,7 @@ def test_parity_classes_longest_first_equals_index_order(monkeypatch, kind, cin,
     from capstone_amd._native import BF16
     from helpers import run_conv_module
     torch.manual_seed(cin + shape[1])
-    if kind == "convT":
-        mod = torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1)
-    else:
-        mod = torch.nn.Conv3d(cin, cout, 3, 2, 1)
+    mod = conv_module(kind, cin, cout)
     x = torch.randn(shape[0], cin, *shape[1:])
     gy = torch.randn_like(mod(x))
     y1, gx1, _, _ = run_conv_module(mod, x, gy, BF16, DEV)

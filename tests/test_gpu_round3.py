@@ -7,7 +7,6 @@
   * MultipleLossWrapper.losses entries called on their own (capstone/models/losses.py:177-180);
   * --precision 16: fp16 inference plans, bf16 training plans after one warning.
 """
-import json
 import os
 import warnings
 
@@ -17,17 +16,10 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from helpers import dump  # noqa: E402
+
 DEV = "cuda:0"
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-
-
-def _dump(name, obj):
-    try:
-        os.makedirs(OUT, exist_ok=True)
-        with open(os.path.join(OUT, name), "w") as f:
-            json.dump(obj, f, indent=1)
-    except OSError:
-        pass
 
 
 @pytest.mark.parametrize("scale", [0.5, 0.125])
@@ -96,9 +88,9 @@ def test_configs0_as_written_2d_unet_64_to_1024_on_a_512_slice():
         if b.norm() > 1e-5 and not (k.endswith(".bias") and "residual" not in k and ".2.1.conv.unit0" not in k):
             rows.append((float(torch.dot(a, b) / (a.norm() * b.norm())), float((a - b).norm() / b.norm()), k))
     worst = sorted(rows)[:5]
-    _dump("configs0_2d_512_fp32_vs_oracle.json", {"logits_max_abs_err": err, "loss": float(loss), "oracle_loss": float(total_ref),
-                                                  "dice": dice, "oracle_dice": float(odice), "parameters": 25980905,
-                                                  "worst_gradient (cos, rel err, tensor)": worst, "tensors_compared": len(rows)})
+    dump(OUT, "configs0_2d_512_fp32_vs_oracle.json", {"logits_max_abs_err": err, "loss": float(loss), "oracle_loss": float(total_ref),
+                                                      "dice": dice, "oracle_dice": float(odice), "parameters": 25980905,
+                                                      "worst_gradient (cos, rel err, tensor)": worst, "tensors_compared": len(rows)})
     assert err < 1e-3, err
     np.testing.assert_allclose(float(loss), float(total_ref), rtol=1e-4)
     assert abs(dice - float(odice)) <= 0.002
@@ -275,9 +267,9 @@ def test_backward_norm_statistics_from_the_conv_epilogue_equal_the_reduce_pass(m
     first = next(i for i, (_, f) in enumerate(diffs) if f)
     ga, gb = a[1].double(), b[1].double()
     cos = float(torch.dot(ga, gb) / (ga.norm() * gb.norm()))
-    _dump(f"bst_epilogue_{B}x{H}x{W}x{D}.json", {"norms": len(b[2]), "fused": fused, "reduce_passes_left": b[3],
-                                                  "rel_diff_of_finalised_sums (backward order; fused?)": diffs,
-                                                  "flat_gradient_cosine": cos})
+    dump(OUT, f"bst_epilogue_{B}x{H}x{W}x{D}.json", {"norms": len(b[2]), "fused": fused, "reduce_passes_left": b[3],
+                                                      "rel_diff_of_finalised_sums (backward order; fused?)": diffs,
+                                                      "flat_gradient_cosine": cos})
     assert all(d == 0.0 for d, _ in diffs[:first]), diffs
     assert diffs[first][0] < 1e-5, diffs
     assert max(d for d, _ in diffs) < 2e-2, diffs

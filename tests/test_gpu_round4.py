@@ -1,25 +1,16 @@
 """GPU, round 4: the metric configuration as a TRAJECTORY — north_star's "mean Dice within +-0.002 of the CPU reference on fixed seeds"
 at BASELINE.json's shape, over optimizer steps, in the dtype and through the step bench.py times."""
-import json
 import os
 
-import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+from helpers import dump  # noqa: E402
+
 DEV = "cuda:0"
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
-
-
-def _dump(name, obj):
-    try:
-        os.makedirs(OUT, exist_ok=True)
-        with open(os.path.join(OUT, name), "w") as f:
-            json.dump(obj, f, indent=1)
-    except OSError:
-        pass
 
 
 def test_full_size_bf16_fused_head_trajectory_tracks_the_oracle():
@@ -56,7 +47,7 @@ def test_full_size_bf16_fused_head_trajectory_tracks_the_oracle():
         dl = [abs(a - b) / abs(b) for a, b in zip(losses, olosses)]
         dd = [abs(a - b) for a, b in zip(dices, odices)]
         res[precision] = {"loss": losses, "dice": dices, "max_rel_loss_diff": max(dl), "max_abs_dice_diff": max(dd)}
-        _dump("parity_full_size_trajectory_vs_oracle.json", res)
+        dump(OUT, "parity_full_size_trajectory_vs_oracle.json", res)
         assert olosses[-1] < olosses[0], "the oracle's loss must descend"
         assert max(dd) <= 0.002, (precision, dd)
         assert max(dl) <= tol_l, (precision, dl)

@@ -5,7 +5,7 @@ descriptor before anything runs.
 
 Oracle A (default): x and dy are integers in [-4, 4] (seeded, no symmetry).  Every product is an integer of magnitude <= 16 and a
 sum of N * rows of them stays below 2^24 (asserted), so the gradient is exact in fp32 in any summation order: the kernel must equal
-the float64 autograd reference bit for bit (torch.equal), bias gradient included.  Every such case runs over slabs poisoned with
+the float64 autograd reference (conv_wgrad of reference_ops.py) bit for bit (torch.equal), bias gradient included.  Every such case runs over slabs poisoned with
 NaN, checks that nothing of the flat gradient outside the layer's views changed, and replays the recorded program with other
 operands over its own stale slabs: `ws` need not be initialised (include/ctseg_hip.h).
 
@@ -51,54 +51,16 @@ import ctypes
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
 from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd._native import BF16, F32  # noqa: E402
 from capstone_amd.engine import Act, new_act  # noqa: E402
-from helpers import GRAD_SENTINEL, WgradPassDriver, norm_for, to_cl  # noqa: E402
+from helpers import CAP_IDS, CAPS, GRAD_SENTINEL, WgradPassDriver, cap_env, norm_for, to_cl  # noqa: E402
+from reference_ops import conv_module, conv_out_shape, conv_wgrad, norm_prelu_dy  # noqa: E402
 
 DEV = "cuda:0"
-CAPS = [None, "1", "3"]
-CAP_IDS = ["uncapped", "max_wg1", "max_wg3"]
-
-
-def _module(kind, cin, cout, k=3):
-    """kind: conv / conv_s2 / convT (3-D), conv2d / conv2d_s2 / convT2d"""
-    p = (k - 1) // 2
-    return {"conv": lambda: torch.nn.Conv3d(cin, cout, k, 1, p), "conv_s2": lambda: torch.nn.Conv3d(cin, cout, k, 2, p),
-            "convT": lambda: torch.nn.ConvTranspose3d(cin, cout, 3, 2, 1, output_padding=1),
-            "conv2d": lambda: torch.nn.Conv2d(cin, cout, k, 1, p), "conv2d_s2": lambda: torch.nn.Conv2d(cin, cout, k, 2, p),
-            "convT2d": lambda: torch.nn.ConvTranspose2d(cin, cout, 3, 2, 1, output_padding=1)}[kind]()
-
-
-def _fwd(kind, k, x, w, b):
-    p = (k - 1) // 2
-    if kind == "convT":
-        return F.conv_transpose3d(x, w, b, stride=2, padding=1, output_padding=1)
-    if kind == "convT2d":
-        return F.conv_transpose2d(x, w, b, stride=2, padding=1, output_padding=1)
-    if kind.startswith("conv2d"):
-        return F.conv2d(x, w, b, stride=2 if kind.endswith("s2") else 1, padding=p)
-    return F.conv3d(x, w, b, stride=2 if kind.endswith("s2") else 1, padding=p)
-
-
-def _out_shape(kind, k, cin, cout, shape):
-    two_d = "2d" in kind
-    sp = shape[1:3] if two_d else shape[1:]
-    with torch.no_grad():
-        w = torch.zeros((cin, cout) + (3,) * len(sp)) if kind.startswith("convT") else torch.zeros((cout, cin) + (k,) * len(sp))
-        return tuple(_fwd(kind, k, torch.zeros((1, cin) + tuple(sp)), w, None).shape[2:])
-
-
-def _grads(kind, k, x, dy, wshape, dtype):
-    """autograd weight / bias gradient of the layer at (x, dy) in ``dtype``"""
-    w = torch.zeros(wshape, dtype=dtype, requires_grad=True)
-    b = torch.zeros(dy.shape[1], dtype=dtype, requires_grad=True)
-    _fwd(kind, k, x.to(dtype), w, b).backward(dy.to(dtype))
-    return w.grad.detach(), b.grad.detach()
 
 
 def _ints(shape, gen):
@@ -106,8 +68,11 @@ def _ints(shape, gen):
 
 
 class _Case:
+    """kind: conv / conv_s2 / convT (3-D), conv2d / conv2d_s2 / convT2d (shape (N, X, Y, 1)); op, dims: the same for reference_ops"""
+
     def __init__(self, name, kind, cin, cout, shape, dt=BF16, k=3, cg=None, x_ld=None, dy_ld=None, env=None, splits=None, target=None):
         self.name, self.kind, self.cin, self.cout, self.shape, self.dt, self.k = name, kind, cin, cout, shape, dt, k
+        self.op, self.dims = kind.replace("2d", ""), 2 if "2d" in kind else 3
         self.cg, self.x_ld, self.dy_ld, self.env, self.splits, self.target = cg, x_ld, dy_ld, env or {}, splits, target
 
     @property
@@ -126,11 +91,10 @@ class _Case:
         return f"{self.name} | {self.kind} {self.cin}->{self.cout} {self.shape}{' fp32' if self.dt == F32 else ''}{w}{e}".replace(" ", "_")
 
     def sizes(self):
-        two_d = "2d" in self.kind
-        N = self.shape[0]
-        xs = (N, self.cin) + tuple(self.shape[1:3] if two_d else self.shape[1:])
-        ys = (N, self.cout) + _out_shape(self.kind, self.k, self.cin, self.cout, self.shape)
-        mod_w = ((self.cin, self.cout) if self.kind.startswith("convT") else (self.cout, self.cin)) + (self.k if not self.kind.startswith("convT") else 3,) * (len(xs) - 2)
+        N, sp = self.shape[0], tuple(self.shape[1:1 + self.dims])
+        xs = (N, self.cin) + sp
+        ys = (N, self.cout) + conv_out_shape(self.op, self.k, sp)
+        mod_w = ((self.cin, self.cout) + (3,) * self.dims) if self.op == "convT" else ((self.cout, self.cin) + (self.k,) * self.dims)
         return xs, ys, mod_w
 
     def setenv(self, monkeypatch, cap=None):
@@ -140,12 +104,11 @@ class _Case:
             monkeypatch.setenv(k, v)
         if self.target:
             monkeypatch.setenv("CTSEG_WGRAD_TARGET_WGS", str(self.target))
-        if cap is not None:
-            monkeypatch.setenv("CTSEG_MAX_WG", cap)
+        cap_env(monkeypatch, cap)
 
     def driver(self):
         torch.manual_seed(1)
-        return WgradPassDriver(_module(self.kind, self.cin, self.cout, self.k), self.dt, DEV, cg=self.cg)
+        return WgradPassDriver(conv_module(self.op, self.cin, self.cout, self.k, self.dims), self.dt, DEV, cg=self.cg)
 
     def acts(self, drv, x, dy):
         # a transposed layer's 12 / 16 wide rows are those of dOut (the gathered operand)
@@ -167,7 +130,7 @@ def _exact_run(case, monkeypatch, cap=None):
     first = None
     for rnd in range(2):
         x, dy = _ints(xs, gen), _ints(ys, gen)
-        rw, rb = _grads(case.kind, case.k, x, dy, wshape, torch.float64)
+        rw, rb = conv_wgrad(case.op, case.k, x, dy, wshape, torch.float64)
         assert bool((rw.abs().flatten(1).sum(1) > 0).all()) and bool((rw.abs().transpose(0, 1).flatten(1).sum(1) > 0).all()), \
             "an all-zero channel slice of the reference: a skipped column block would pass"
         assert bool((rb != 0).any())
@@ -301,7 +264,7 @@ def test_up_kernel_writes_the_bias_row_of_the_tightest_slab(monkeypatch):
     nat.call("ctseg_conv_wgrad", d)
     torch.cuda.synchronize()
     tot = ws.sum(0).cpu()
-    rw, _ = _grads(case.kind, case.k, x, dy, wshape, torch.float64)              # [ci][co][tap]
+    rw, _ = conv_wgrad(case.op, case.k, x, dy, wshape, torch.float64)              # [ci][co][tap]
     assert torch.equal(tot[:432].view(27, 16, d.cn_pad)[:, :10, :64], rw.reshape(64, 10, 27).permute(2, 1, 0).float())
     assert torch.equal(tot[432, :64], x.sum((0, 2, 3, 4)))
 
@@ -361,9 +324,9 @@ NORMAL_CASES = [
 
 def _normalised_check(tag, gw, gb, x, dy, kind, k, wshape, n_rows):
     """|got - ref| / S against 16 x the float32 evaluation's, S = gradient of (|x|, |dy|)"""
-    rw, rb = _grads(kind, k, x, dy, wshape, torch.float64)
-    sw, sb = _grads(kind, k, x.abs(), dy.abs(), wshape, torch.float64)
-    fw, fb = _grads(kind, k, x, dy, wshape, torch.float32)
+    rw, rb = conv_wgrad(kind, k, x, dy, wshape, torch.float64)
+    sw, sb = conv_wgrad(kind, k, x.abs(), dy.abs(), wshape, torch.float64)
+    fw, fb = conv_wgrad(kind, k, x, dy, wshape, torch.float32)
     assert bool((sw > 0).all()) and bool((sb > 0).all())
     bound_w, bound_b = 16.0 * float(((fw.double() - rw).abs() / sw).max()), 16.0 * float(((fb.double() - rb).abs() / sb).max())
     if bound_b == 0.0:      # torch's float32 column sums of dy came out exact (few hundred bf16 values): one float32 rounding, see above
@@ -390,8 +353,8 @@ def test_normal_valued_operands_within_the_float32_bound(case, monkeypatch):
     gw, gb, d, flat = drv.go(poison=float("nan"))
     assert drv.outside_untouched(flat)
     if case.bias_done:
-        gb = _grads(case.kind, case.k, x, dy, wshape, torch.float64)[1].float()       # (not computed by this pass)
-    _normalised_check(case.id, gw, gb, x, dy, case.kind, case.k, wshape, d.N * d.Xr * d.Yr * d.Zr)
+        gb = conv_wgrad(case.op, case.k, x, dy, wshape, torch.float64)[1].float()       # (not computed by this pass)
+    _normalised_check(case.id, gw, gb, x, dy, case.op, case.k, wshape, d.N * d.Xr * d.Yr * d.Zr)
 
 
 # ---- operand normalised on load (in_mean_rstd): the x-column head kernel -----------------------------------------------------
@@ -403,7 +366,7 @@ def test_operand_normalised_on_load_equals_the_materialised_activation(N, monkey
     C, dims = 10, case.shape[1:]
     alpha = torch.nn.Parameter(torch.tensor([0.2]))
     torch.manual_seed(1)
-    drv = WgradPassDriver(_module("conv", 10, 10), BF16, DEV, cg=16, extra_params=[alpha])
+    drv = WgradPassDriver(conv_module("conv", 10, 10), BF16, DEV, cg=16, extra_params=[alpha])
     drv.plan.narrow_rows = True
     na, y, m, r = norm_for(drv, alpha, N, C, dims, seed=5)
     ya = to_cl(y, BF16, DEV, ld=12)
@@ -468,12 +431,6 @@ def test_operand_normalisation_is_refused_off_the_head_kernel(monkeypatch):
 
 
 # ---- dY formed on load (dyn_*): the stem kernel --------------------------------------------------------------------------------
-def _inorm_prelu_dy(g, y, m, r, alpha):
-    xh = (y - m) * r
-    dxh = g * torch.where(xh > 0, torch.ones_like(xh), torch.full_like(xh, alpha))
-    return r * (dxh - dxh.mean((2, 3, 4), keepdim=True) - xh * (dxh * xh).mean((2, 3, 4), keepdim=True))
-
-
 @pytest.mark.parametrize("Cn,N", [(32, 2), (64, 2), (32, 8), (64, 8)])
 def test_dy_formed_on_load_equals_the_apply_pass(Cn, N, monkeypatch):
     C = Cn // 2
@@ -483,7 +440,7 @@ def test_dy_formed_on_load_equals_the_apply_pass(Cn, N, monkeypatch):
     rdims = ys[2:]
     alpha = torch.nn.Parameter(torch.tensor([0.2]))
     torch.manual_seed(1)
-    drv = WgradPassDriver(_module("conv_s2", 1, Cn), BF16, DEV, extra_params=[alpha])
+    drv = WgradPassDriver(conv_module("conv_s2", 1, Cn), BF16, DEV, extra_params=[alpha])
     gen = torch.Generator().manual_seed(Cn + N)
     x = torch.randn(xs, generator=gen).bfloat16().float()
     dy_lo = torch.randn((N, C) + rdims, generator=gen).bfloat16().float()
@@ -509,7 +466,7 @@ def test_dy_formed_on_load_equals_the_apply_pass(Cn, N, monkeypatch):
     assert torch.equal(gw1, gw0) and torch.equal(gb1, gb0)
     # float64 through InstanceNorm + PReLU + the convolution (the norm's float32 (mean, rstd) table); the formed dy0 is rounded to
     # bf16 by the kernel as the apply pass rounds it, which the references take as their operand
-    dy0 = _inorm_prelu_dy(g.double(), y.double(), m, r, 0.2)
+    dy0 = norm_prelu_dy(g.double(), y.double(), m, r, 0.2)
     stored = fused.valid().float().cpu()
     assert float((stored[:, C:].double() - dy0).abs().max() / dy0.abs().max()) < 2.0 ** -7, "the apply pass against float64"
     _normalised_check(case.id + " dyn", gw1, gb1, x, stored, "conv_s2", 3, wshape, N * d.Xr * d.Yr * d.Zr)

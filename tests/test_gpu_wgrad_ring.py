@@ -19,21 +19,22 @@ from capstone_amd import _native as nat
 from capstone_amd.engine import GemmLayer, rup
 
 from helpers import MiniPlan, to_cl, rel_err
+from reference_ops import conv_module
 
 pytestmark = pytest.mark.gpu
 
 CASES = [
     # name, module ctor, input spatial dims (N, X, Y, Z)
-    ("64->64 s1 (512x64 tile), ragged rows", lambda: torch.nn.Conv3d(64, 64, 3, 1, 1), (2, 7, 10, 6)),
-    ("32->128 s2 (256x128 tile, K = 865 of 1024)", lambda: torch.nn.Conv3d(32, 128, 3, 2, 1), (2, 12, 16, 8)),
-    ("128->128 s1 (bias row in a tile of its own: K = 3456 = 13.5 x 256)", lambda: torch.nn.Conv3d(128, 128, 3, 1, 1), (1, 6, 8, 6)),
-    ("64->256 s1 (256x256 tile)", lambda: torch.nn.Conv3d(64, 256, 3, 1, 1), (2, 6, 6, 6)),
-    ("256->256 s1 (256x256 tile; K = 6912 = 27 x 256: bias-only last tile)", lambda: torch.nn.Conv3d(256, 256, 3, 1, 1), (1, 4, 6, 6)),
-    ("128->256 s1 (256x256 tile, bias row inside the last tile), two samples", lambda: torch.nn.Conv3d(128, 256, 3, 1, 1), (2, 5, 6, 7)),
-    ("64->384 s2 (three column tiles)", lambda: torch.nn.Conv3d(64, 384, 3, 2, 1), (1, 8, 8, 12)),
-    ("transposed 128->32 s2 (roles swapped: gathered = dOut)", lambda: torch.nn.ConvTranspose3d(128, 32, 3, 2, 1, output_padding=1), (2, 6, 6, 4)),
-    ("transposed 256->64 s2", lambda: torch.nn.ConvTranspose3d(256, 64, 3, 2, 1, output_padding=1), (1, 4, 6, 6)),
-    ("1x1x1 128->64 (one tap)", lambda: torch.nn.Conv3d(128, 64, 1, 1, 0), (2, 9, 5, 7)),
+    ("64->64 s1 (512x64 tile), ragged rows", lambda: conv_module("conv", 64, 64), (2, 7, 10, 6)),
+    ("32->128 s2 (256x128 tile, K = 865 of 1024)", lambda: conv_module("conv_s2", 32, 128), (2, 12, 16, 8)),
+    ("128->128 s1 (bias row in a tile of its own: K = 3456 = 13.5 x 256)", lambda: conv_module("conv", 128, 128), (1, 6, 8, 6)),
+    ("64->256 s1 (256x256 tile)", lambda: conv_module("conv", 64, 256), (2, 6, 6, 6)),
+    ("256->256 s1 (256x256 tile; K = 6912 = 27 x 256: bias-only last tile)", lambda: conv_module("conv", 256, 256), (1, 4, 6, 6)),
+    ("128->256 s1 (256x256 tile, bias row inside the last tile), two samples", lambda: conv_module("conv", 128, 256), (2, 5, 6, 7)),
+    ("64->384 s2 (three column tiles)", lambda: conv_module("conv_s2", 64, 384), (1, 8, 8, 12)),
+    ("transposed 128->32 s2 (roles swapped: gathered = dOut)", lambda: conv_module("convT", 128, 32), (2, 6, 6, 4)),
+    ("transposed 256->64 s2", lambda: conv_module("convT", 256, 64), (1, 4, 6, 6)),
+    ("1x1x1 128->64 (one tap)", lambda: conv_module("conv", 128, 64, k=1), (2, 9, 5, 7)),
 ]
 
 
@@ -90,7 +91,7 @@ def test_ring_kernel_equals_the_generic_kernel_and_autograd(name, ctor, dims):
 def test_ring_kernel_is_deterministic_and_takes_any_split_count():
     """a run is bit-reproducible, and forcing odd split counts (last split short or empty) changes only the summation order"""
     torch.manual_seed(3)
-    mod = torch.nn.Conv3d(64, 128, 3, 1, 1)
+    mod = conv_module("conv", 64, 128)
     x = torch.randn(2, 64, 12, 12, 10).bfloat16().float()
     gy = torch.randn(2, 128, 12, 12, 10).bfloat16().float()
     a = _wgrad(mod, x, gy, ring=True)
