@@ -9,7 +9,7 @@ from one pass over the two label maps (ctseg_dice_counts) — or for free from t
 import torch
 
 from .. import _native as nat
-from .. import segloss
+from .. import segloss, surface
 from ..segloss import N_CLASSES
 
 
@@ -27,3 +27,27 @@ class DiceMetricWrapper(object):
             cnt = segloss.dice_counts(p, t, self.n_classes)
         self.last_counts = cnt      # (B, 3, C) int64: what epoch_dice_across_ranks gathers at N > 1
         return segloss.dice_metric(cnt)
+
+
+class SurfaceDistanceMetricWrapper(object):
+    """``SurfaceDistanceMetricWrapper(percentile=95.0)(pred_labels, true_labels) -> (mean, per-class (9,))`` of the symmetric
+    percentile Hausdorff distance in voxels (``capstone_amd.surface``): label maps ``(B, H, W, D)`` or planes ``(B, H, W)``, in the
+    shape of ``DiceMetricWrapper``.  Not in the reference, which scores with Dice only.  A class absent from the prediction or the
+    truth of a sample has no value there (NaN, never 0); the per-class value is the mean over the samples that have one, the mean
+    that over the classes that have one.  ``last`` keeps the full tables of the call and ``assd()`` gives (mean, per-class) of the
+    average symmetric surface distance from the same call."""
+
+    def __init__(self, percentile=95.0):
+        self.n_classes = N_CLASSES
+        self.percentile = float(percentile)
+        self.last = None
+
+    def __call__(self, input, target):
+        nat.require_gpu(input, "SurfaceDistanceMetricWrapper")
+        self.last = surface.surface_distances(input, target, self.n_classes, self.percentile)
+        return surface.reduce_nan_mean(self.last.hd)
+
+    def assd(self):
+        if self.last is None:
+            raise RuntimeError("SurfaceDistanceMetricWrapper.assd(): call the wrapper on a batch first")
+        return surface.reduce_nan_mean(self.last.assd)

@@ -1,0 +1,125 @@
+"""Surface metrics on the device: the percentile Hausdorff distance (HD95 by default) and the average symmetric surface distance
+between two label maps, per sample and class.  The reference scores with Dice only; the data it targets (MICCAI 2015 head-and-neck
+organs at risk) is scored by Dice and the 95 % Hausdorff distance.
+
+Definitions, for class c of sample b:
+
+* surface of c in a label map L: the voxels with ``L == c`` of which an axis neighbour (+-1 along each active axis) lies outside the
+  volume or has ``L != c``: ``m ^ scipy.ndimage.binary_erosion(m)`` with scipy's defaults, the edge rule of MONAI's
+  ``get_mask_edges``.  Volumes ``(B, H, W, D)`` use all three axes; planes ``(B, H, W)`` are ``(H, W, 1)`` volumes whose third
+  axis contributes no neighbours.
+* directed distances pred -> target: ``sqrt(d2(v))`` for every v on the prediction's surface, d2 the exact integer squared
+  Euclidean distance in voxels to the nearest voxel of the truth's surface; target -> pred is the mirror image.
+* percentile distance: ``np.percentile(distances, q)`` with linear interpolation per direction; the symmetric value is the larger
+  of the two.  ``q = 100`` is the classical Hausdorff distance.
+* ASSD: (sum of both directions' distances) / (number of both surfaces' voxels).
+* a class absent from the prediction or from the truth of a sample has NaN in every table: for a distance, 0 means perfect.
+  ``reduce_nan_mean`` is the reduction: NaN-ignoring mean over samples per class, then over the classes that have a value.
+
+Distances are in voxels of the grid the labels live on; physical spacing would need a weighted transform and is not supported.
+
+Three device stages per launch, no host synchronisation between them: ``ctseg_surface_edges`` (surface masks of both maps, one
+byte per voxel and volume, and their voxel counts), ``ctseg_distmap3d_batch`` on those masks (unchanged: its float map is written
+and ignored) and ``ctseg_surface_select`` (exact order statistics by a radix select, the maximum, the float64 sum of the roots).
+The working set is 15 bytes per voxel and volume (1 mask + 4 squared distances + 4 float map + 6 transform workspace), times
+``2 * (n_classes - 1)`` = 18 volumes per sample: 1.7 GB for one 256 x 256 x 96 sample.  Samples are therefore processed in groups
+that keep the working set under ``MAX_WORKING_SET`` bytes (at least one sample per launch).  There is no CPU fallback.
+"""
+from types import SimpleNamespace
+
+import torch
+
+from . import _native as nat
+from .data import utils as DU
+from .segloss import N_CLASSES
+
+AXIS_X, AXIS_Y, AXIS_Z = 1, 2, 4
+BYTES_PER_VOXEL = 1 + 4 + 4 + DU.WORKSPACE_BYTES_3D      # per voxel of each of the 2 * (C - 1) surface volumes of a sample
+SELECT_ROW_BYTES = 25096                                  # CTSEG_SURFACE_SELECT_ROW_BYTES of include/ctseg_hip.h
+MAX_CLASSES = 16
+MAX_WORKING_SET = 2 << 30
+
+
+def _label_maps(pred, target):
+    if pred.shape != target.shape or pred.dim() not in (3, 4):
+        raise ValueError(f"surface_distances: two label maps of one shape, (B, H, W, D) or (B, H, W); got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    if pred.is_floating_point() or target.is_floating_point() or pred.dtype == torch.bool or target.dtype == torch.bool:
+        raise ValueError(f"surface_distances: integer label maps, not {pred.dtype} / {target.dtype}")
+    if pred.device != target.device:
+        raise ValueError(f"surface_distances: the label maps are on {pred.device} and {target.device}")
+    sides = tuple(int(s) for s in pred.shape[1:]) + ((1,) if pred.dim() == 3 else ())
+    axes = AXIS_X | AXIS_Y | (AXIS_Z if pred.dim() == 4 else 0)
+    if pred.shape[0] < 1 or min(sides) < 1 or max(sides) > DU.MAX_SIDE:
+        raise nat.NativeError(f"surface_distances: at least one sample with sides in 1..{DU.MAX_SIDE} (got {tuple(pred.shape)})")
+    return pred.to(torch.uint8).contiguous(), target.to(torch.uint8).contiguous(), sides, axes
+
+
+def surface_distances(pred, target, n_classes=N_CLASSES, percentile=95.0, samples_per_launch=None):
+    """pred, target: integer label maps ``(B, H, W, D)`` or ``(B, H, W)`` on the device -> a namespace of device tensors, C =
+    ``n_classes``, direction 0 = pred -> target, 1 = target -> pred:
+
+    ``hd_directed`` (2, B, C-1) float64, ``hd`` (B, C-1), ``hd_max_directed`` (2, B, C-1) (the q = 100 values), ``assd`` (B, C-1),
+    ``asd_directed`` (2, B, C-1), ``counts`` (2, B, C-1) int64 surface voxels, and the exact integers the float values come from:
+    ``d2_lo``, ``d2_hi``, ``d2_max`` (2, B, C-1) int32, ``gamma`` and ``root_sum`` (2, B, C-1) float64, ``valid`` (2, B, C-1) bool.
+    """
+    nat.require_gpu(pred, "surface_distances")
+    nat.require_gpu(target, "surface_distances")
+    C, q = int(n_classes), float(percentile)
+    if not 2 <= C <= MAX_CLASSES:
+        raise ValueError(f"surface_distances: 2 <= n_classes <= {MAX_CLASSES}, not {n_classes!r}")
+    if not 0.0 <= q <= 100.0:
+        raise ValueError(f"surface_distances: a percentile in [0, 100], not {percentile!r}")
+    p, t, (X, Y, Z), axes = _label_maps(pred, target)
+    B, S, K, dev = p.shape[0], X * Y * Z, C - 1, p.device
+    if samples_per_launch is None:
+        samples_per_launch = max(1, MAX_WORKING_SET // (BYTES_PER_VOXEL * 2 * K * S))
+    G = max(1, min(int(samples_per_launch), B))
+    P = 2 * G * K
+    edges = torch.empty((P * S,), dtype=torch.uint8, device=dev)
+    d2 = torch.empty((P * S,), dtype=torch.int32, device=dev)
+    fmap = torch.empty((P * S,), dtype=torch.float32, device=dev)                    # the transform's map: written, not read
+    dm_ws = torch.empty((DU.WORKSPACE_BYTES_3D * P * S,), dtype=torch.uint8, device=dev)
+    sel_ws = torch.empty((P * SELECT_ROW_BYTES // 8,), dtype=torch.float64, device=dev)
+    table = DU._byte_table(dev)
+    counts, stats, fstats = [], [], []
+    for b0 in range(0, B, G):
+        g = min(G, B - b0)
+        rows = 2 * g * K
+        cnt = torch.zeros((2, g, K), dtype=torch.int32, device=dev)
+        st = torch.empty((2, g, K, 4), dtype=torch.int32, device=dev)
+        fs = torch.empty((2, g, K, 2), dtype=torch.float64, device=dev)
+        nat.call("ctseg_surface_edges", nat.ptr(p[b0:b0 + g]), nat.ptr(t[b0:b0 + g]), g, X, Y, Z, C, axes, nat.ptr(edges), nat.ptr(cnt))
+        nat.call("ctseg_distmap3d_batch", nat.ptr(edges), rows, X, Y, Z, DU.REFERENCE, nat.ptr(table), nat.ptr(dm_ws),
+                 DU.WORKSPACE_BYTES_3D * rows * S, nat.ptr(fmap), nat.ptr(d2), None)
+        nat.call("ctseg_surface_select", nat.ptr(edges), nat.ptr(d2), nat.ptr(cnt), g, X, Y, Z, C, q, nat.ptr(sel_ws),
+                 rows * SELECT_ROW_BYTES, nat.ptr(st), nat.ptr(fs))
+        counts.append(cnt)
+        stats.append(st)
+        fstats.append(fs)
+    cnt, st, fs = torch.cat(counts, 1), torch.cat(stats, 1), torch.cat(fstats, 1)
+    return _tables(cnt, st, fs)
+
+
+def _tables(cnt, st, fs):
+    """the float64 tables from the integers of the select: a few small torch ops"""
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=cnt.device)
+    valid = st[..., 3] != 0
+    n = cnt.to(torch.int64)
+    lo, hi = st[..., 0].double().sqrt(), st[..., 1].double().sqrt()
+    gamma, root_sum = fs[..., 1], fs[..., 0]
+    hd_directed = torch.where(valid, lo + (hi - lo) * gamma, nan)
+    both = n[0] + n[1]
+    return SimpleNamespace(
+        hd_directed=hd_directed, hd=torch.maximum(hd_directed[0], hd_directed[1]),
+        hd_max_directed=torch.where(valid, st[..., 2].double().sqrt(), nan),
+        asd_directed=torch.where(valid, root_sum / n.clamp(min=1), nan),
+        assd=torch.where(valid[0], (root_sum[0] + root_sum[1]) / both.clamp(min=1), nan),
+        counts=n, d2_lo=st[..., 0], d2_hi=st[..., 1], d2_max=st[..., 2], gamma=gamma, root_sum=root_sum, valid=valid)
+
+
+def reduce_nan_mean(table):
+    """(N, C-1) per-sample values -> (mean, per_class (C-1,)): per class the mean over the samples that have a value (NaN if
+    none has), then the mean over the classes that have one (NaN if none has)"""
+    per_class = torch.nanmean(table, dim=0)
+    return torch.nanmean(per_class), per_class

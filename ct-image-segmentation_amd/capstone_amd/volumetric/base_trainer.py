@@ -12,14 +12,14 @@ from typing import List
 
 import torch
 
-from .. import segloss
+from .. import STRUCTURES, segloss, surface
 from .. import _native as nat
 from ..models import UNet
 from ..models.losses import _as_cl
 from ..training.module_base import _TrainerBase, _precision, pl
 from ..training.utils import _squash_predictions  # noqa: F401  (same import the reference has)
 from .losses import MultipleLossWrapper3D
-from .metrics import DiceMetricWrapper3D
+from .metrics import DiceMetricWrapper3D, SurfaceDistanceMetricWrapper3D
 from .utils import _squash_masks_3D
 
 SEED = 12342
@@ -28,9 +28,13 @@ SEED = 12342
 class BaseUNet3D(_TrainerBase):
     def __init__(self, filters: List = [16, 32, 64, 128, 256], use_res_units: bool = False, downsample: bool = False,
                  lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
-                 **kwargs) -> None:
+                 surface_metrics: bool = False, surface_percentile: float = 95.0, **kwargs) -> None:
         """``device_boundary``: opt in to the Boundary loss on volumes; the batch then carries the distance maps as its fourth
-        element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise."""
+        element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise.
+        ``surface_metrics``: ``validation_step`` also scores the batch with the percentile Hausdorff distance (``surface_percentile``,
+        HD95 by default) and the average symmetric surface distance, in voxels (``capstone_amd.surface``); the tables are kept per
+        step, reduced by ``epoch_surface_metrics`` and logged by ``on_validation_epoch_end``.  Per rank: they are not gathered
+        across data-parallel ranks.  Training steps never compute them."""
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
@@ -40,6 +44,9 @@ class BaseUNet3D(_TrainerBase):
         self.device_boundary = device_boundary      # (a switch of this port, not a reference hyperparameter: kept out of hparams)
         self.loss_func = MultipleLossWrapper3D(losses=loss_fx, exclude_missing=exclude_missing, device_boundary=device_boundary)
         self.dice_score = DiceMetricWrapper3D()
+        self.surface_metrics = surface_metrics      # (as device_boundary: a switch of this port, kept out of hparams)
+        self.surface_score = SurfaceDistanceMetricWrapper3D(surface_percentile) if surface_metrics else None
+        self._surface_kept = {}
 
     def _construct_model(self):
         # reference :58-72 — in_channels=1, strides for a 5-entry filter list, num_res_units hard-wired to 2
@@ -135,7 +142,41 @@ class BaseUNet3D(_TrainerBase):
         return _StepLossFn.apply(loss, eng, plan, self, *eng.store.params)
 
     def validation_step(self, batch, batch_idx=0):
-        self._shared_step(batch, is_training=False)
+        _, masks, _, prediction, _ = self._shared_step(batch, is_training=False)
+        if self.surface_metrics:
+            with torch.no_grad():
+                self.surface_score(_squash_predictions(prediction), masks)
+            last = self.surface_score.last
+            self._surface_kept.setdefault("val", []).append((last.hd, last.assd))
+
+    def epoch_surface_metrics(self, prefix="val", reset=True):
+        """(HD mean, HD per class (9,), ASSD mean, ASSD per class (9,)) over all samples scored since the last reset: per class the
+        mean over the samples where the class is in both the prediction and the truth, then the mean over the classes that have a
+        value; NaN where nothing has.  None with ``surface_metrics`` off or when nothing was kept.  The values of this rank."""
+        kept = self._surface_kept.get(prefix)
+        if not self.surface_metrics or not kept:
+            return None
+        hd, assd = (torch.cat([k[i] for k in kept]) for i in (0, 1))
+        if reset:
+            self._surface_kept[prefix] = []
+        return surface.reduce_nan_mean(hd) + surface.reduce_nan_mean(assd)
+
+    def on_validation_epoch_end(self, *args, **kwargs):
+        """logs the epoch's surface metrics that have a value: "{structure} HD95 (val)", "Mean HD95 (val)", "{structure} ASSD
+        (val)", "Mean ASSD (val)" (``HD`` and the percentile)"""
+        if not self.surface_metrics:
+            return
+        res = self.epoch_surface_metrics("val")
+        if res is None:
+            return
+        hd = f"HD{self.surface_score.percentile:g}"
+        for name, mean, per_class in ((hd, res[0], res[1]), ("ASSD", res[2], res[3])):
+            finite = torch.isfinite(per_class).tolist()
+            for structure, value, ok in zip(STRUCTURES, per_class, finite):
+                if ok:
+                    self.log(f"{structure} {name} (val)", value, on_step=False, on_epoch=True)
+            if any(finite):
+                self.log(f"Mean {name} (val)", mean, on_step=False, on_epoch=True)
 
     def _shared_step(self, batch, is_training: bool):
         images, masks, mask_indicator, dist_maps = self._split_batch(batch)

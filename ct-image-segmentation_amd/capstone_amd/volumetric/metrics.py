@@ -1,6 +1,10 @@
 """Mirror of reference capstone/volumetric/metrics.py: the 3-D metric wrapper (rank-agnostic here)."""
-from ..models.metrics import DiceMetricWrapper
+from ..models.metrics import DiceMetricWrapper, SurfaceDistanceMetricWrapper
 
 
 class DiceMetricWrapper3D(DiceMetricWrapper):
+    pass
+
+
+class SurfaceDistanceMetricWrapper3D(SurfaceDistanceMetricWrapper):
     pass

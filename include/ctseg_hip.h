@@ -521,6 +521,30 @@ int ctseg_distmap2d_batch(const uint8_t* masks, int32_t P, int32_t H, int32_t W,
 int ctseg_distmap3d_batch(const uint8_t* masks, int32_t P, int32_t X, int32_t Y, int32_t Z, int32_t mode, const float* table,
                           void* workspace, int64_t workspace_bytes, float* out, int32_t* d2_fg, int32_t* d2_bg, void* stream);
 
+/* Surface metrics between two label maps: the percentile Hausdorff distance and the average surface distance, per sample and
+ * class 1..C-1, in voxels of the labels' grid.  Three calls in stream order, no host synchronisation between them:
+ *   ctseg_surface_edges -> ctseg_distmap3d_batch(masks = edges, P = 2*B*(C-1), d2_fg = d2, d2_bg = NULL) -> ctseg_surface_select.
+ * ctseg_surface_edges: pred, target uint8 [B][X][Y][Z] -> edges uint8 [2][B][C-1][X][Y][Z] (side 0 = pred, 1 = target; every byte
+ *   written, 0 or 1) and counts[2][B][C-1] += the surface voxels of each volume (zeroed by the caller; integer atomics).  A voxel of
+ *   label c is on the surface of class c when a neighbour at +-1 along an active axis is outside the volume or holds another
+ *   label; `axes` is the mask of active axes, X = 1 | Y = 2 | Z = 4 (planes: [B][H][W][1] with axes = 3).  A label >= C is in no
+ *   class and differs from every neighbour's.  With Z a multiple of 16, pred, target and edges are 16-byte aligned.
+ * ctseg_surface_select: row r = (side, b, c) takes the values d2[partner row][v] at the voxels v with edges[r][v] != 0, the
+ *   squared distances from this side's surface to the other's (d2: the d2_fg output of the transform of `edges`).  With n =
+ *   counts[r], r_q = (n - 1) * (q / 100) in float64, lo = floor(r_q), hi = min(lo + 1, n - 1):
+ *     stats[r]  = {d2 of rank lo, d2 of rank hi, the largest d2, 1}   (ranks in ascending order, from 0; exact integers)
+ *     fstats[r] = {sum over v of sqrt(d2) in float64, r_q - lo}
+ *   and all zeros on a row where counts[r] or its partner's is 0: the flag stats[r][3] says whether the row has values.  The sum
+ *   is added from per-workgroup partials in a fixed order and the histograms are integer atomics: two runs give the same bits.
+ *   workspace >= 2*B*(C-1) * CTSEG_SURFACE_SELECT_ROW_BYTES bytes, 8-byte aligned; the call zeroes what it needs of it.
+ * Both: B >= 1, sides in 1..1024, 2 <= C <= 16, 2*B*(C-1) <= 65535; validated on the host before the first launch. */
+#define CTSEG_SURFACE_SELECT_ROW_BYTES 25096
+int ctseg_surface_edges(const uint8_t* pred, const uint8_t* target, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t C,
+                        int32_t axes, uint8_t* edges, int32_t* counts, void* stream);
+int ctseg_surface_select(const uint8_t* edges, const int32_t* d2, const int32_t* counts, int32_t B, int32_t X, int32_t Y, int32_t Z,
+                         int32_t C, double q, void* workspace, int64_t workspace_bytes, int32_t* stats, double* fstats,
+                         void* stream);
+
 /* Sliding-window inference (BASELINE.json configs[4]).  The reference has no inferer (grep: 0 hits); the
  * semantics are those of MONAI 0.3 `monai.inferers.sliding_window_inference`, the companion of the `monai.networks.nets.UNet`
  * the reference builds at capstone/volumetric/base_trainer.py:65-72.
