@@ -35,16 +35,20 @@ class SurfaceDistanceMetricWrapper(object):
     shape of ``DiceMetricWrapper``.  Not in the reference, which scores with Dice only.  A class absent from the prediction or the
     truth of a sample has no value there (NaN, never 0); the per-class value is the mean over the samples that have one, the mean
     that over the classes that have one.  ``last`` keeps the full tables of the call and ``assd()`` gives (mean, per-class) of the
-    average symmetric surface distance from the same call."""
+    average symmetric surface distance from the same call.  ``spacing``: the voxel sizes of the label grid (a triple, a pair for
+    planes, or one row per sample), fixed at construction or given per call, which takes precedence; the distances are then in
+    that unit (``surface.surface_distances``)."""
 
-    def __init__(self, percentile=95.0):
+    def __init__(self, percentile=95.0, spacing=None):
         self.n_classes = N_CLASSES
         self.percentile = float(percentile)
+        self.spacing = spacing
         self.last = None
 
-    def __call__(self, input, target):
+    def __call__(self, input, target, spacing=None):
         nat.require_gpu(input, "SurfaceDistanceMetricWrapper")
-        self.last = surface.surface_distances(input, target, self.n_classes, self.percentile)
+        self.last = surface.surface_distances(input, target, self.n_classes, self.percentile,
+                                              spacing=self.spacing if spacing is None else spacing)
         return surface.reduce_nan_mean(self.last.hd)
 
     def assd(self):

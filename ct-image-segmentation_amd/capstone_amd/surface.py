@@ -16,14 +16,25 @@ Definitions, for class c of sample b:
 * a class absent from the prediction or from the truth of a sample has NaN in every table: for a distance, 0 means perfect.
   ``reduce_nan_mean`` is the reduction: NaN-ignoring mean over samples per class, then over the classes that have a value.
 
-Distances are in voxels of the grid the labels live on; physical spacing would need a weighted transform and is not supported.
+Distances are in voxels of the grid the labels live on, or, with ``spacing=``, in the unit of the voxel sizes given (millimetres
+for CT headers).  Under anisotropic spacing the nearest surface voxel is another voxel, so the physical value is no rescaling of
+the voxel one: that path runs its own transform.
 
 Three device stages per launch, no host synchronisation between them: ``ctseg_surface_edges`` (surface masks of both maps, one
 byte per voxel and volume, and their voxel counts), ``ctseg_distmap3d_batch`` on those masks (unchanged: its float map is written
 and ignored) and ``ctseg_surface_select`` (exact order statistics by a radix select, the maximum, the float64 sum of the roots).
-The working set is 15 bytes per voxel and volume (1 mask + 4 squared distances + 4 float map + 6 transform workspace), times
-``2 * (n_classes - 1)`` = 18 volumes per sample: 1.7 GB for one 256 x 256 x 96 sample.  Samples are therefore processed in groups
-that keep the working set under ``MAX_WORKING_SET`` bytes (at least one sample per launch).  There is no CPU fallback.
+Without a spacing the working set is 15 bytes per voxel and volume (1 mask + 4 squared distances + 4 float map + 6 transform
+workspace), times ``2 * (n_classes - 1)`` = 18 volumes per sample: 1.7 GB for one 256 x 256 x 96 sample.  Samples are therefore
+processed in groups that keep the working set under ``MAX_WORKING_SET`` bytes (at least one sample per launch).  There is no CPU
+fallback.
+
+With ``spacing=`` the middle and last stages are ``ctseg_distmap3d_weighted`` and ``ctseg_surface_select_f32``.  The transform takes
+a table of squared voxel sizes per volume and gives float32 squared distances, each the minimum over the other surface's voxels of
+``fl(fl(wy dy^2) + fl(fl(wz dz^2) + fl(wx dx^2)))``, one float32 rounding per ``fl``: defined bit for bit, and within 3 * 2^-24
+relative of the real squared distance, so within 2^-23 of the distance after the root.  It writes no value map, so the working
+set that sizes the launch groups is 11 bytes per voxel and volume on this path (1 mask + 4 squared distances + 6 transform
+workspace, ``BYTES_PER_VOXEL_WEIGHTED``): 1.25 GB for the same sample.  The select orders those floats by their bit patterns.
+``spacing=(1, 1, 1)`` reproduces the voxel path exactly (``fl(1 * d^2)`` is exact).
 """
 from types import SimpleNamespace
 
@@ -35,7 +46,10 @@ from .segloss import N_CLASSES
 
 AXIS_X, AXIS_Y, AXIS_Z = 1, 2, 4
 BYTES_PER_VOXEL = 1 + 4 + 4 + DU.WORKSPACE_BYTES_3D      # per voxel of each of the 2 * (C - 1) surface volumes of a sample
+BYTES_PER_VOXEL_WEIGHTED = 1 + 4 + DU.WORKSPACE_BYTES_3D  # with spacing: float32 squared distances and no value map
 SELECT_ROW_BYTES = 25096                                  # CTSEG_SURFACE_SELECT_ROW_BYTES of include/ctseg_hip.h
+SELECT_F32_ROW_BYTES = 41480                              # CTSEG_SURFACE_SELECT_F32_ROW_BYTES
+MIN_SPACING, MAX_SPACING = 1e-3, 1e3
 MAX_CLASSES = 16
 MAX_WORKING_SET = 2 << 30
 
@@ -55,13 +69,33 @@ def _label_maps(pred, target):
     return pred.to(torch.uint8).contiguous(), target.to(torch.uint8).contiguous(), sides, axes
 
 
-def surface_distances(pred, target, n_classes=N_CLASSES, percentile=95.0, samples_per_launch=None):
+def _squared_spacing(spacing, B, n_axes):
+    """one ``n_axes``-tuple or ``(B, n_axes)`` voxel sizes -> (B, 3) float32 squared sizes on the host (planes: 1 on the third axis)"""
+    s = torch.as_tensor(spacing).detach().to("cpu", torch.float64)
+    if s.dim() == 1 and s.shape[0] == n_axes:
+        s = s[None].expand(B, n_axes)
+    if s.dim() != 2 or tuple(s.shape) != (B, n_axes):
+        raise ValueError(f"surface_distances: spacing is {n_axes} voxel sizes or ({B}, {n_axes}) of them, not {tuple(s.shape)}")
+    if not bool((torch.isfinite(s) & (s >= MIN_SPACING) & (s <= MAX_SPACING)).all()):
+        raise ValueError(f"surface_distances: finite voxel sizes in [{MIN_SPACING:g}, {MAX_SPACING:g}], not {s.tolist()}")
+    s = s.to(torch.float32)
+    w = torch.ones((B, 3), dtype=torch.float32)
+    w[:, :n_axes] = s * s
+    return w
+
+
+def surface_distances(pred, target, n_classes=N_CLASSES, percentile=95.0, samples_per_launch=None, spacing=None):
     """pred, target: integer label maps ``(B, H, W, D)`` or ``(B, H, W)`` on the device -> a namespace of device tensors, C =
     ``n_classes``, direction 0 = pred -> target, 1 = target -> pred:
 
     ``hd_directed`` (2, B, C-1) float64, ``hd`` (B, C-1), ``hd_max_directed`` (2, B, C-1) (the q = 100 values), ``assd`` (B, C-1),
     ``asd_directed`` (2, B, C-1), ``counts`` (2, B, C-1) int64 surface voxels, and the exact integers the float values come from:
     ``d2_lo``, ``d2_hi``, ``d2_max`` (2, B, C-1) int32, ``gamma`` and ``root_sum`` (2, B, C-1) float64, ``valid`` (2, B, C-1) bool.
+
+    ``spacing``: the voxel sizes along the label map's axes, one triple (a pair for planes) or ``(B, 3)`` / ``(B, 2)`` per sample, as
+    a sequence, an array or a tensor; every value finite and in [1e-3, 1e3], else ``ValueError``.  They are read on the host (a
+    device tensor is copied back) and squared in float32.  The distances are then in the spacing's unit, and ``d2_lo``, ``d2_hi``,
+    ``d2_max`` are float32: the squared physical distances as the weighted transform rounds them (see the module's docstring).
     """
     nat.require_gpu(pred, "surface_distances")
     nat.require_gpu(target, "surface_distances")
@@ -72,16 +106,20 @@ def surface_distances(pred, target, n_classes=N_CLASSES, percentile=95.0, sample
         raise ValueError(f"surface_distances: a percentile in [0, 100], not {percentile!r}")
     p, t, (X, Y, Z), axes = _label_maps(pred, target)
     B, S, K, dev = p.shape[0], X * Y * Z, C - 1, p.device
+    weighted = spacing is not None
+    w2 = _squared_spacing(spacing, B, pred.dim() - 1).to(dev) if weighted else None
+    row_bytes = SELECT_F32_ROW_BYTES if weighted else SELECT_ROW_BYTES
     if samples_per_launch is None:
-        samples_per_launch = max(1, MAX_WORKING_SET // (BYTES_PER_VOXEL * 2 * K * S))
+        samples_per_launch = max(1, MAX_WORKING_SET // ((BYTES_PER_VOXEL_WEIGHTED if weighted else BYTES_PER_VOXEL) * 2 * K * S))
     G = max(1, min(int(samples_per_launch), B))
     P = 2 * G * K
     edges = torch.empty((P * S,), dtype=torch.uint8, device=dev)
-    d2 = torch.empty((P * S,), dtype=torch.int32, device=dev)
-    fmap = torch.empty((P * S,), dtype=torch.float32, device=dev)                    # the transform's map: written, not read
+    d2 = torch.empty((P * S,), dtype=torch.float32 if weighted else torch.int32, device=dev)
     dm_ws = torch.empty((DU.WORKSPACE_BYTES_3D * P * S,), dtype=torch.uint8, device=dev)
-    sel_ws = torch.empty((P * SELECT_ROW_BYTES // 8,), dtype=torch.float64, device=dev)
-    table = DU._byte_table(dev)
+    sel_ws = torch.empty((P * row_bytes // 8,), dtype=torch.float64, device=dev)
+    if not weighted:
+        fmap = torch.empty((P * S,), dtype=torch.float32, device=dev)                # the transform's map: written, not read
+        table = DU._byte_table(dev)
     counts, stats, fstats = [], [], []
     for b0 in range(0, B, G):
         g = min(G, B - b0)
@@ -90,21 +128,27 @@ def surface_distances(pred, target, n_classes=N_CLASSES, percentile=95.0, sample
         st = torch.empty((2, g, K, 4), dtype=torch.int32, device=dev)
         fs = torch.empty((2, g, K, 2), dtype=torch.float64, device=dev)
         nat.call("ctseg_surface_edges", nat.ptr(p[b0:b0 + g]), nat.ptr(t[b0:b0 + g]), g, X, Y, Z, C, axes, nat.ptr(edges), nat.ptr(cnt))
-        nat.call("ctseg_distmap3d_batch", nat.ptr(edges), rows, X, Y, Z, DU.REFERENCE, nat.ptr(table), nat.ptr(dm_ws),
-                 DU.WORKSPACE_BYTES_3D * rows * S, nat.ptr(fmap), nat.ptr(d2), None)
-        nat.call("ctseg_surface_select", nat.ptr(edges), nat.ptr(d2), nat.ptr(cnt), g, X, Y, Z, C, q, nat.ptr(sel_ws),
-                 rows * SELECT_ROW_BYTES, nat.ptr(st), nat.ptr(fs))
+        if weighted:
+            w = w2[b0:b0 + g].view(1, g, 1, 3).expand(2, g, K, 3).contiguous()       # a row of the table per surface volume
+            nat.call("ctseg_distmap3d_weighted", nat.ptr(edges), rows, X, Y, Z, nat.ptr(w), nat.ptr(dm_ws),
+                     DU.WORKSPACE_BYTES_3D * rows * S, nat.ptr(d2), None)
+            nat.call("ctseg_surface_select_f32", nat.ptr(edges), nat.ptr(d2), nat.ptr(cnt), g, X, Y, Z, C, q, nat.ptr(sel_ws),
+                     rows * row_bytes, nat.ptr(st), nat.ptr(fs))
+        else:
+            nat.call("ctseg_distmap3d_batch", nat.ptr(edges), rows, X, Y, Z, DU.REFERENCE, nat.ptr(table), nat.ptr(dm_ws),
+                     DU.WORKSPACE_BYTES_3D * rows * S, nat.ptr(fmap), nat.ptr(d2), None)
+            nat.call("ctseg_surface_select", nat.ptr(edges), nat.ptr(d2), nat.ptr(cnt), g, X, Y, Z, C, q, nat.ptr(sel_ws),
+                     rows * row_bytes, nat.ptr(st), nat.ptr(fs))
         counts.append(cnt)
         stats.append(st)
         fstats.append(fs)
     cnt, st, fs = torch.cat(counts, 1), torch.cat(stats, 1), torch.cat(fstats, 1)
-    return _tables(cnt, st, fs)
+    return _tables(cnt, st[..., :3].contiguous().view(torch.float32) if weighted else st[..., :3], st[..., 3] != 0, fs)
 
 
-def _tables(cnt, st, fs):
-    """the float64 tables from the integers of the select: a few small torch ops"""
+def _tables(cnt, st, valid, fs):
+    """the float64 tables from the select's {d2[lo], d2[hi], max} (int32, or float32 with spacing): a few small torch ops"""
     nan = torch.full((), float("nan"), dtype=torch.float64, device=cnt.device)
-    valid = st[..., 3] != 0
     n = cnt.to(torch.int64)
     lo, hi = st[..., 0].double().sqrt(), st[..., 1].double().sqrt()
     gamma, root_sum = fs[..., 1], fs[..., 0]

@@ -28,13 +28,17 @@ SEED = 12342
 class BaseUNet3D(_TrainerBase):
     def __init__(self, filters: List = [16, 32, 64, 128, 256], use_res_units: bool = False, downsample: bool = False,
                  lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
-                 surface_metrics: bool = False, surface_percentile: float = 95.0, **kwargs) -> None:
+                 surface_metrics: bool = False, surface_percentile: float = 95.0, surface_spacing=None, **kwargs) -> None:
         """``device_boundary``: opt in to the Boundary loss on volumes; the batch then carries the distance maps as its fourth
         element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise.
         ``surface_metrics``: ``validation_step`` also scores the batch with the percentile Hausdorff distance (``surface_percentile``,
-        HD95 by default) and the average symmetric surface distance, in voxels (``capstone_amd.surface``); the tables are kept per
-        step, reduced by ``epoch_surface_metrics`` and logged by ``on_validation_epoch_end``.  Per rank: they are not gathered
-        across data-parallel ranks.  Training steps never compute them."""
+        HD95 by default) and the average symmetric surface distance (``capstone_amd.surface``), in voxels of the label grid unless
+        ``surface_spacing`` is given; the tables are kept per step, reduced by ``epoch_surface_metrics`` and logged by
+        ``on_validation_epoch_end``.  Per rank: they are not gathered across data-parallel ranks.  Training steps never compute
+        them.
+        ``surface_spacing``: the voxel size (x, y, z) of the grid the network trains on, in millimetres, such as the cohort's mean
+        after ``Resize3D``; one value for every sample, since the datasets carry no spacing.  The surface metrics are then physical
+        distances and their log keys say so: ``"... HD95 mm (val)"``, ``"... ASSD mm (val)"``."""
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
@@ -45,7 +49,8 @@ class BaseUNet3D(_TrainerBase):
         self.loss_func = MultipleLossWrapper3D(losses=loss_fx, exclude_missing=exclude_missing, device_boundary=device_boundary)
         self.dice_score = DiceMetricWrapper3D()
         self.surface_metrics = surface_metrics      # (as device_boundary: a switch of this port, kept out of hparams)
-        self.surface_score = SurfaceDistanceMetricWrapper3D(surface_percentile) if surface_metrics else None
+        self.surface_spacing = surface_spacing      # (kept out of hparams too)
+        self.surface_score = SurfaceDistanceMetricWrapper3D(surface_percentile, surface_spacing) if surface_metrics else None
         self._surface_kept = {}
 
     def _construct_model(self):
@@ -163,14 +168,16 @@ class BaseUNet3D(_TrainerBase):
 
     def on_validation_epoch_end(self, *args, **kwargs):
         """logs the epoch's surface metrics that have a value: "{structure} HD95 (val)", "Mean HD95 (val)", "{structure} ASSD
-        (val)", "Mean ASSD (val)" (``HD`` and the percentile)"""
+        (val)", "Mean ASSD (val)" (``HD`` and the percentile); with ``surface_spacing`` the unit follows the name, as in "{structure}
+        HD95 mm (val)" and "Mean ASSD mm (val)", and the keys without it are not logged"""
         if not self.surface_metrics:
             return
         res = self.epoch_surface_metrics("val")
         if res is None:
             return
+        unit = "" if self.surface_spacing is None else " mm"
         hd = f"HD{self.surface_score.percentile:g}"
-        for name, mean, per_class in ((hd, res[0], res[1]), ("ASSD", res[2], res[3])):
+        for name, mean, per_class in ((hd + unit, res[0], res[1]), ("ASSD" + unit, res[2], res[3])):
             finite = torch.isfinite(per_class).tolist()
             for structure, value, ok in zip(STRUCTURES, per_class, finite):
                 if ok:

@@ -15,6 +15,8 @@
 // none, so after the last pass it means that the volume has no voxel of the other class: -1 in that d2 output and a map of 0,
 // decided per voxel, with no flag shared between lanes.
 // The value pass is that of distmap2d.hip: REFERENCE gives table[k] of the byte the reference stores, SIGNED the float map.
+// ctseg_distmap3d_weighted (further down) is the same transform under per-volume voxel sizes: squared physical distances in float32,
+// the class bit in the float's sign bit, +inf for "none", and no value pass.
 #include "distmap_common.h"
 
 namespace ctseg {
@@ -114,6 +116,80 @@ __global__ __launch_bounds__(256) void distmap3d_slabs_kernel(const uint32_t* __
   }
 }
 
+// ---- the weighted transform: squared physical distances in float32 -------------------------------------------------------------
+// The sweep is the integer one.  The line pass turns its distance dx into fl(wx * dx^2) and searches along Z with wz, the slab pass
+// searches along Y with wy and writes the result: fl(fl(wy dy^2) + fl(fl(wz dz^2) + fl(wx dx^2))) minimised over the candidates,
+// because every pass applies a monotone map to the minimum of the pass before.  w[p] = {wx, wy, wz} of volume p, on the device.
+
+// As distmap3d_lines_kernel; a workgroup's lines may belong to two or more volumes, so each line looks its volume up: XY = X * Y.
+__global__ __launch_bounds__(256) void distmap3d_lines_w_kernel(const uint16_t* __restrict__ g, int64_t voxels, int Z, int L, int XY,
+                                                                const float* __restrict__ w, uint32_t* __restrict__ f) {
+  __shared__ uint32_t s[DM3_LINE_WORDS];
+  const int64_t line0 = (int64_t)blockIdx.x * L, e0 = line0 * Z;
+  const int64_t p0 = line0 / XY;
+  const int rem0 = (int)(line0 - p0 * XY);
+  const int n = voxels - e0 < (int64_t)L * Z ? (int)(voxels - e0) : L * Z;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += 256) {
+    const int r = i / Z;
+    const float wx = w[(p0 + (rem0 + r) / XY) * 3];
+    const uint32_t v = g[e0 + i], d = v & 0x7fffu;
+    s[i] = ((v & 0x8000u) << 16) | (d == DM3_NONE ? DM_W_NONE : __float_as_uint(mul_rn(wx, (float)(d * d))));
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) {
+    const int r = i / Z, z = i - r * Z;
+    const float wz = w[(p0 + (rem0 + r) / XY) * 3 + 2];
+    const uint32_t mine = s[i] & 0x80000000u;
+    f[e0 + i] = mine | __float_as_uint(line_min_w(s + r * Z, z, Z, 1, mine, wz));
+  }
+}
+
+// As distmap3d_slabs_kernel without the value pass; row b = p * X + x belongs to volume b / X.
+__global__ __launch_bounds__(256) void distmap3d_slabs_w_kernel(const uint32_t* __restrict__ f, int X, int Y, int Z, int zshift,
+                                                                int ztiles, const float* __restrict__ w, float* __restrict__ d2_fg,
+                                                                float* __restrict__ d2_bg) {
+  __shared__ uint32_t s[DM3_SLAB_WORDS];
+  const int ZT = 1 << zshift;
+  const int64_t b = blockIdx.x / ztiles;
+  const int z0 = (int)(blockIdx.x - b * ztiles) << zshift;
+  const int zn = Z - z0 < ZT ? Z - z0 : ZT;
+  const int64_t base = b * Y * Z + z0;
+  const float wy = w[(b / X) * 3 + 1];
+  const int n = Y << zshift;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += 256) {
+    const int y = i >> zshift, zc = i & (ZT - 1);
+    if (zc < zn) s[i] = f[base + (int64_t)y * Z + zc];
+  }
+  __syncthreads();
+  for (int i = tid; i < n; i += 256) {
+    const int y = i >> zshift, zc = i & (ZT - 1);
+    if (zc >= zn) continue;
+    const uint32_t mine = s[i] & 0x80000000u;
+    const bool inside = mine != 0;
+    const float d2 = line_min_w(s + zc, y, Y, ZT, mine, wy);   // to the other class
+    const float val = __float_as_uint(d2) == DM_W_NONE ? -1.f : d2;   // +inf: the volume has no voxel of the other class
+    const int64_t o = base + (int64_t)y * Z + zc;
+    if (d2_fg) d2_fg[o] = inside ? 0.f : val;
+    if (d2_bg) d2_bg[o] = inside ? val : 0.f;
+  }
+}
+
+// the launch geometry both transforms share: Z lines per workgroup of the line pass, the slab tile, the three grids
+struct Dm3Grid { int L, zshift, ztiles; int64_t sweep_blocks, line_blocks, slab_blocks; };
+static inline Dm3Grid dm3_grid(int P, int X, int Y, int Z) {
+  Dm3Grid g;
+  g.L = DM3_LINE_WORDS / Z;                                    // >= 4
+  g.zshift = 3;                                                // the widest slab tile that fits and that Z can fill
+  while ((2 << g.zshift) <= DM3_ZTILE_MAX && ((int64_t)Y << (g.zshift + 1)) <= DM3_SLAB_WORDS && (1 << g.zshift) < Z) ++g.zshift;
+  g.ztiles = (Z + (1 << g.zshift) - 1) >> g.zshift;
+  g.sweep_blocks = ((int64_t)P * Y * Z + 255) / 256;
+  g.line_blocks = ((int64_t)P * X * Y + g.L - 1) / g.L;
+  g.slab_blocks = (int64_t)P * X * g.ztiles;
+  return g;
+}
+
 }  // namespace ctseg
 
 using namespace ctseg;
@@ -132,23 +208,49 @@ extern "C" int ctseg_distmap3d_batch(const uint8_t* masks, int32_t P, int32_t X,
   CTSEG_REQUIRE(((uintptr_t)workspace % 4) == 0 && ((uintptr_t)out % 4) == 0 && ((uintptr_t)table % 4) == 0 &&
                     ((uintptr_t)d2_fg % 4) == 0 && ((uintptr_t)d2_bg % 4) == 0,
                 "distmap3d_batch: unaligned pointer");
-  const int L = DM3_LINE_WORDS / Z;                            // Z lines per workgroup of the line pass, >= 4
-  int zshift = 3;                                              // the widest slab tile that fits and that Z can fill
-  while ((2 << zshift) <= DM3_ZTILE_MAX && ((int64_t)Y << (zshift + 1)) <= DM3_SLAB_WORDS && (1 << zshift) < Z) ++zshift;
-  const int ztiles = (Z + (1 << zshift) - 1) >> zshift;
-  const int64_t sweep_blocks = ((int64_t)P * plane + 255) / 256, line_blocks = ((int64_t)P * X * Y + L - 1) / L;
-  const int64_t slab_blocks = (int64_t)P * X * ztiles;
-  CTSEG_REQUIRE(sweep_blocks <= 0x7fffffff && line_blocks <= 0x7fffffff && slab_blocks <= 0x7fffffff,
+  const Dm3Grid gr = dm3_grid(P, X, Y, Z);
+  CTSEG_REQUIRE(gr.sweep_blocks <= 0x7fffffff && gr.line_blocks <= 0x7fffffff && gr.slab_blocks <= 0x7fffffff,
                 "distmap3d_batch: %d volumes are too many for one launch", P);
   uint32_t* f = (uint32_t*)workspace;                          // [voxels] uint32, then [voxels] uint16
   uint16_t* g = (uint16_t*)(f + voxels);
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(distmap3d_sweep_kernel, dim3((unsigned)sweep_blocks), dim3(256), 0, st, masks, (int64_t)P * plane, X, plane, g);
+  hipLaunchKernelGGL(distmap3d_sweep_kernel, dim3((unsigned)gr.sweep_blocks), dim3(256), 0, st, masks, (int64_t)P * plane, X, plane, g);
   CTSEG_LAUNCH_CHECK("distmap3d_batch (sweep)");
-  hipLaunchKernelGGL(distmap3d_lines_kernel, dim3((unsigned)line_blocks), dim3(256), 0, st, (const uint16_t*)g, voxels, Z, L, f);
+  hipLaunchKernelGGL(distmap3d_lines_kernel, dim3((unsigned)gr.line_blocks), dim3(256), 0, st, (const uint16_t*)g, voxels, Z, gr.L, f);
   CTSEG_LAUNCH_CHECK("distmap3d_batch (lines)");
-  hipLaunchKernelGGL(distmap3d_slabs_kernel, dim3((unsigned)slab_blocks), dim3(256), 0, st, (const uint32_t*)f, Y, Z, zshift, ztiles,
-                     mode, table, out, d2_fg, d2_bg);
+  hipLaunchKernelGGL(distmap3d_slabs_kernel, dim3((unsigned)gr.slab_blocks), dim3(256), 0, st, (const uint32_t*)f, Y, Z, gr.zshift,
+                     gr.ztiles, mode, table, out, d2_fg, d2_bg);
   CTSEG_LAUNCH_CHECK("distmap3d_batch (slabs)");
+  return 0;
+}
+
+extern "C" int ctseg_distmap3d_weighted(const uint8_t* masks, int32_t P, int32_t X, int32_t Y, int32_t Z, const float* w, void* workspace,
+                                        int64_t workspace_bytes, float* d2_fg, float* d2_bg, void* stream) {
+  CTSEG_REQUIRE(masks && w && workspace && (d2_fg || d2_bg),
+                "distmap3d_weighted: null pointer (masks, w, workspace and one of d2_fg, d2_bg are required)");
+  CTSEG_REQUIRE(P >= 1 && X >= 1 && Y >= 1 && Z >= 1, "distmap3d_weighted: P, X, Y, Z >= 1 (got %d volumes of %d x %d x %d)", P, X, Y,
+                Z);
+  CTSEG_REQUIRE(X <= DM_MAX_SIDE && Y <= DM_MAX_SIDE && Z <= DM_MAX_SIDE, "distmap3d_weighted: sides up to %d (got %d x %d x %d)",
+                DM_MAX_SIDE, X, Y, Z);
+  const int64_t plane = (int64_t)Y * Z, voxels = (int64_t)P * X * plane;
+  CTSEG_REQUIRE(workspace_bytes >= 6 * voxels, "distmap3d_weighted: the workspace holds %lld bytes, %lld are needed",
+                (long long)workspace_bytes, (long long)(6 * voxels));
+  CTSEG_REQUIRE(((uintptr_t)workspace % 4) == 0 && ((uintptr_t)w % 4) == 0 && ((uintptr_t)d2_fg % 4) == 0 &&
+                    ((uintptr_t)d2_bg % 4) == 0,
+                "distmap3d_weighted: unaligned pointer");
+  const Dm3Grid gr = dm3_grid(P, X, Y, Z);
+  CTSEG_REQUIRE(gr.sweep_blocks <= 0x7fffffff && gr.line_blocks <= 0x7fffffff && gr.slab_blocks <= 0x7fffffff,
+                "distmap3d_weighted: %d volumes are too many for one launch", P);
+  uint32_t* f = (uint32_t*)workspace;                          // [voxels] uint32, then [voxels] uint16
+  uint16_t* g = (uint16_t*)(f + voxels);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(distmap3d_sweep_kernel, dim3((unsigned)gr.sweep_blocks), dim3(256), 0, st, masks, (int64_t)P * plane, X, plane, g);
+  CTSEG_LAUNCH_CHECK("distmap3d_weighted (sweep)");
+  hipLaunchKernelGGL(distmap3d_lines_w_kernel, dim3((unsigned)gr.line_blocks), dim3(256), 0, st, (const uint16_t*)g, voxels, Z, gr.L,
+                     X * Y, w, f);
+  CTSEG_LAUNCH_CHECK("distmap3d_weighted (lines)");
+  hipLaunchKernelGGL(distmap3d_slabs_w_kernel, dim3((unsigned)gr.slab_blocks), dim3(256), 0, st, (const uint32_t*)f, X, Y, Z, gr.zshift,
+                     gr.ztiles, w, d2_fg, d2_bg);
+  CTSEG_LAUNCH_CHECK("distmap3d_weighted (slabs)");
   return 0;
 }

@@ -1,5 +1,6 @@
 // What the distance-map kernels of the 2-D planes (distmap2d.hip) and of the volumes (distmap3d.hip) share: the modes, the sentinels,
-// the outward lower-envelope searches and the exact integer / correctly rounded roots of the value pass.
+// the outward lower-envelope searches (integer, and float32 under voxel sizes) and the exact integer / correctly rounded roots of
+// the value pass.
 #pragma once
 #include "ctseg_dev.h"
 
@@ -51,6 +52,44 @@ __device__ __forceinline__ int line_min_sq(const uint32_t* f, int t, int n, int 
       const uint32_t v = f[tr * stride];
       const int fv = ((v ^ mine) >> 31) ? 0 : (int)(v & 0x7fffffffu);
       if (fv != DM_INF) { const int c = dd + fv; best = c < best ? c : best; }
+    }
+  }
+  return best;
+}
+
+// One float32 rounding each.  Device code is compiled with contraction on, and the toolchain's __fmul_rn / __fadd_rn are a plain
+// `*` and `+` that may still fuse once inlined; the pragma takes the contraction flag off these two operations themselves, and a
+// product or a sum without it is never made part of an FMA.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// The weighted form of line_min_sq, on float32: a word is class << 31 | the bits of f >= 0, the squared physical distance found so
+// far (DM_W_NONE, +inf: none).  Non-negative floats order like their bit patterns, so the layout is that of the integer search.
+// The candidate at offset d is fl(fl(w * d^2) + f), each a single rounding (mul_rn, add_rn); adding a non-negative term is monotone
+// in float arithmetic, so fl(w * d^2) >= best ends the search as d^2 >= best does there.
+constexpr uint32_t DM_W_NONE = 0x7f800000u;
+__device__ __forceinline__ float line_min_w(const uint32_t* f, int t, int n, int stride, uint32_t mine, float w) {
+  float best = __uint_as_float(f[t * stride] & 0x7fffffffu);    // its own word is of its own class
+  for (int d = 1; d < n; ++d) {
+    const float dd = mul_rn(w, (float)(d * d));                  // d^2 < 2^24: exact
+    if (dd >= best) break;
+    const int tl = t - d, tr = t + d;
+    if (tl < 0 && tr >= n) break;
+    if (tl >= 0) {
+      const uint32_t v = f[tl * stride];
+      const float c = add_rn(dd, ((v ^ mine) >> 31) ? 0.f : __uint_as_float(v & 0x7fffffffu));   // (+inf stays +inf)
+      best = c < best ? c : best;
+    }
+    if (tr < n) {
+      const uint32_t v = f[tr * stride];
+      const float c = add_rn(dd, ((v ^ mine) >> 31) ? 0.f : __uint_as_float(v & 0x7fffffffu));
+      best = c < best ? c : best;
     }
   }
   return best;

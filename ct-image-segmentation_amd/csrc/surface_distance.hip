@@ -12,6 +12,8 @@
 //           pick.  Histograms are integer atomics (LDS, then one flush per workgroup): order independent.  The float64 sum of the
 //           roots goes through per-workgroup partials in fixed slots, added in slot order.  The ranks lo = floor((n - 1) * q / 100)
 //           and hi = min(lo + 1, n - 1) are computed on the device from the counts of the edge pass: no host synchronisation.
+//           ctseg_surface_select_f32 is the same select on the float32 squared distances of ctseg_distmap3d_weighted (physical
+//           units), three levels over the 31-bit patterns of the non-negative floats.
 #include "distmap_common.h"
 
 namespace ctseg {
@@ -295,6 +297,127 @@ __global__ __launch_bounds__(256) void surface_pick_kernel(const int32_t* __rest
   }
 }
 
+// ---- the select on float32 keys ----------------------------------------------------------------------------------------------
+// The values are the non-negative float32 squared distances of ctseg_distmap3d_weighted (-1.0f: none, skipped by its sign like the
+// integer -1).  Their 31-bit patterns order like the values, so the select runs on the patterns, in three levels of 11 + 11 + 9
+// bits: `top` = bits >> 20, `mid` = (bits >> 9) & 2047 inside the top buckets of the two ranks, `low` = bits & 511 inside their
+// mid buckets.  Every histogram has SD_BINS slots (the low ones use 512 of them), so sd_locate serves all three.
+constexpr int SDF_TOP_SHIFT = 20, SDF_MID_SHIFT = 9, SDF_LOW_MASK = 511;
+
+template <bool WIDE>
+__global__ __launch_bounds__(256) void surface_top_f32_kernel(const uint8_t* __restrict__ edges, const int32_t* __restrict__ d2,
+                                                              const int32_t* __restrict__ counts, int half, int64_t S, int64_t per,
+                                                              uint32_t* __restrict__ top, int32_t* __restrict__ vmax,
+                                                              double* __restrict__ part) {
+  __shared__ uint32_t s_h[SD_BINS];
+  __shared__ double s_red[4];
+  __shared__ int s_max;
+  const int r = blockIdx.y, o = sd_partner(r, half), tid = threadIdx.x;
+  if (counts[r] <= 0 || counts[o] <= 0) return;                      // (the whole workgroup)
+  for (int i = tid; i < SD_BINS; i += 256) s_h[i] = 0u;
+  if (tid == 0) s_max = 0;
+  __syncthreads();
+  const int64_t v0 = (int64_t)blockIdx.x * per, v1 = v0 + per < S ? v0 + per : S;
+  double sum = 0.0;
+  int mx = 0;
+  sd_for_each<WIDE>(edges + (int64_t)r * S, d2 + (int64_t)o * S, v0, v1, [&](int d) {   // d: the bits of a float >= 0
+    atomicAdd(&s_h[d >> SDF_TOP_SHIFT], 1u);
+    mx = d > mx ? d : mx;
+    sum += sqrt((double)__int_as_float(d));
+  });
+  sum = wave_sum(sum);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const int t = __shfl_xor(mx, off, 64); mx = t > mx ? t : mx; }
+  if ((tid & 63) == 0) { s_red[tid >> 6] = sum; atomicMax(&s_max, mx); }
+  __syncthreads();
+  for (int i = tid; i < SD_BINS; i += 256)
+    if (s_h[i]) atomicAdd(&top[(int64_t)r * SD_BINS + i], s_h[i]);
+  if (tid == 0) {
+    part[(int64_t)r * gridDim.x + blockIdx.x] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+    if (s_max) atomicMax(&vmax[r], s_max);
+  }
+}
+
+// LEVEL 1: the mid histograms inside the top buckets of lo and hi; LEVEL 2: the low histograms inside their mid buckets.
+// `lower` is [rows][2][SD_BINS] of the level being written, `mid` the finished mid histograms (LEVEL 2 only).
+template <bool WIDE, int LEVEL>
+__global__ __launch_bounds__(256) void surface_lower_f32_kernel(const uint8_t* __restrict__ edges, const int32_t* __restrict__ d2,
+                                                                const int32_t* __restrict__ counts, int half, int64_t S, int64_t per,
+                                                                double q, const uint32_t* __restrict__ top,
+                                                                const uint32_t* __restrict__ mid, uint32_t* __restrict__ lower) {
+  __shared__ uint32_t s_h[2 * SD_BINS];                             // of the bucket of lo, then of hi
+  __shared__ uint32_t s_sum[256];
+  __shared__ int64_t s_found[4];
+  const int r = blockIdx.y, o = sd_partner(r, half), tid = threadIdx.x;
+  const int32_t n = counts[r];
+  if (n <= 0 || counts[o] <= 0) return;
+  const SdRanks k = sd_ranks(n, q);
+  for (int i = tid; i < 2 * SD_BINS; i += 256) s_h[i] = 0u;
+  if (tid < 4) s_found[tid] = 0;
+  int t0, t1, unused_b;
+  int64_t below0, below1, unused;
+  sd_locate(top + (int64_t)r * SD_BINS, k.lo, k.hi, s_sum, s_found, t0, below0, t1, below1);
+  int p0 = t0, p1 = t1, shift = SDF_TOP_SHIFT, mask = SD_BINS - 1;   // the prefixes to match above `shift`, the bin below it
+  if constexpr (LEVEL == 2) {
+    const uint32_t* mr = mid + (int64_t)r * 2 * SD_BINS;
+    int m0, m1;
+    sd_locate(mr, k.lo - below0, k.lo - below0, s_sum, s_found, m0, unused, unused_b, unused);
+    sd_locate(mr + SD_BINS, k.hi - below1, k.hi - below1, s_sum, s_found, m1, unused, unused_b, unused);
+    p0 = (t0 << (SDF_TOP_SHIFT - SDF_MID_SHIFT)) | m0;
+    p1 = (t1 << (SDF_TOP_SHIFT - SDF_MID_SHIFT)) | m1;
+    shift = SDF_MID_SHIFT;
+  }
+  const int low_shift = LEVEL == 1 ? SDF_MID_SHIFT : 0;
+  if constexpr (LEVEL == 2) mask = SDF_LOW_MASK;
+  const int64_t v0 = (int64_t)blockIdx.x * per, v1 = v0 + per < S ? v0 + per : S;
+  sd_for_each<WIDE>(edges + (int64_t)r * S, d2 + (int64_t)o * S, v0, v1, [&](int d) {
+    const int p = d >> shift, bin = (d >> low_shift) & mask;
+    if (p == p0) atomicAdd(&s_h[bin], 1u);
+    if (p == p1) atomicAdd(&s_h[SD_BINS + bin], 1u);
+  });
+  __syncthreads();
+  for (int i = tid; i < 2 * SD_BINS; i += 256)
+    if (s_h[i]) atomicAdd(&lower[(int64_t)r * 2 * SD_BINS + i], s_h[i]);
+}
+
+// Grid (rows).  stats[r] = {bits of d2[lo], bits of d2[hi], bits of the maximum, 1}, fstats[r] as surface_pick_kernel.
+__global__ __launch_bounds__(256) void surface_pick_f32_kernel(const int32_t* __restrict__ counts, int half, int slots, double q,
+                                                               const uint32_t* __restrict__ top, const uint32_t* __restrict__ mid,
+                                                               const uint32_t* __restrict__ low, const int32_t* __restrict__ vmax,
+                                                               const double* __restrict__ part, int32_t* __restrict__ stats,
+                                                               double* __restrict__ fstats) {
+  __shared__ uint32_t s_sum[256];
+  __shared__ int64_t s_found[4];
+  const int r = blockIdx.x, o = sd_partner(r, half), tid = threadIdx.x;
+  const int32_t n = counts[r];
+  if (n <= 0 || counts[o] <= 0) {
+    if (tid < 4) stats[r * 4 + tid] = 0;
+    if (tid < 2) fstats[r * 2 + tid] = 0.0;
+    return;
+  }
+  const SdRanks k = sd_ranks(n, q);
+  if (tid < 4) s_found[tid] = 0;
+  int t0, t1, m0, m1, l0, l1, unused_b;
+  int64_t below0, below1, mbelow0, mbelow1, unused;
+  sd_locate(top + (int64_t)r * SD_BINS, k.lo, k.hi, s_sum, s_found, t0, below0, t1, below1);
+  const uint32_t* mr = mid + (int64_t)r * 2 * SD_BINS;
+  const uint32_t* lr = low + (int64_t)r * 2 * SD_BINS;
+  sd_locate(mr, k.lo - below0, k.lo - below0, s_sum, s_found, m0, mbelow0, unused_b, unused);
+  sd_locate(mr + SD_BINS, k.hi - below1, k.hi - below1, s_sum, s_found, m1, mbelow1, unused_b, unused);
+  sd_locate(lr, k.lo - below0 - mbelow0, k.lo - below0 - mbelow0, s_sum, s_found, l0, unused, unused_b, unused);
+  sd_locate(lr + SD_BINS, k.hi - below1 - mbelow1, k.hi - below1 - mbelow1, s_sum, s_found, l1, unused, unused_b, unused);
+  if (tid == 0) {
+    double sum = 0.0;
+    for (int w = 0; w < slots; ++w) sum += part[(int64_t)r * slots + w];       // slot order: the same bits every run
+    stats[r * 4 + 0] = (t0 << SDF_TOP_SHIFT) | (m0 << SDF_MID_SHIFT) | l0;
+    stats[r * 4 + 1] = (t1 << SDF_TOP_SHIFT) | (m1 << SDF_MID_SHIFT) | l1;
+    stats[r * 4 + 2] = vmax[r];
+    stats[r * 4 + 3] = 1;
+    fstats[r * 2 + 0] = sum;
+    fstats[r * 2 + 1] = k.gamma;
+  }
+}
+
 // voxels per workgroup of the select (a multiple of SD_CHUNK) and the workgroups per row that follow from it, <= SD_MAX_SLOTS
 static inline int64_t sd_per_slot(int64_t S) {
   const int64_t per = (S + SD_MAX_SLOTS - 1) / SD_MAX_SLOTS;
@@ -303,6 +426,8 @@ static inline int64_t sd_per_slot(int64_t S) {
 
 // per row: SD_MAX_SLOTS float64 partials, the coarse and the two fine histograms, the maximum (+ pad)
 static_assert(CTSEG_SURFACE_SELECT_ROW_BYTES == SD_MAX_SLOTS * 8 + 3 * SD_BINS * 4 + 8, "the header's workspace size");
+// float32 keys: the top histogram and two each of the mid and low ones
+static_assert(CTSEG_SURFACE_SELECT_F32_ROW_BYTES == SD_MAX_SLOTS * 8 + 5 * SD_BINS * 4 + 8, "the header's workspace size");
 
 }  // namespace ctseg
 
@@ -380,5 +505,57 @@ extern "C" int ctseg_surface_select(const uint8_t* edges, const int32_t* d2, con
   hipLaunchKernelGGL(surface_pick_kernel, dim3((unsigned)rows), dim3(256), 0, st, counts, half, slots, q, (const uint32_t*)coarse,
                      (const uint32_t*)fine, (const int32_t*)vmax, (const double*)part, stats, fstats);
   CTSEG_LAUNCH_CHECK("surface_select (pick)");
+  return 0;
+}
+
+extern "C" int ctseg_surface_select_f32(const uint8_t* edges, const float* d2, const int32_t* counts, int32_t B, int32_t X, int32_t Y,
+                                        int32_t Z, int32_t C, double q, void* workspace, int64_t workspace_bytes, int32_t* stats,
+                                        double* fstats, void* stream) {
+  CTSEG_REQUIRE(edges && d2 && counts && workspace && stats && fstats,
+                "surface_select_f32: null pointer (edges, d2, counts, workspace, stats and fstats are required)");
+  if (check_surface_dims("surface_select_f32", B, X, Y, Z, C)) return -1;
+  CTSEG_REQUIRE(q >= 0.0 && q <= 100.0, "surface_select_f32: a percentile in [0, 100] (got %g)", q);
+  const int64_t S = (int64_t)X * Y * Z, per = sd_per_slot(S);
+  const int rows = 2 * B * (C - 1), slots = (int)((S + per - 1) / per);
+  const int64_t need = (int64_t)rows * CTSEG_SURFACE_SELECT_F32_ROW_BYTES;
+  CTSEG_REQUIRE(workspace_bytes >= need, "surface_select_f32: the workspace holds %lld bytes, %lld are needed",
+                (long long)workspace_bytes, (long long)need);
+  const bool wide = S % SD_RUN == 0;
+  CTSEG_REQUIRE(((uintptr_t)workspace % 8) == 0 && ((uintptr_t)fstats % 8) == 0 && ((uintptr_t)stats % 4) == 0 &&
+                    ((uintptr_t)counts % 4) == 0 && ((uintptr_t)d2 % 4) == 0 && (!wide || ((uintptr_t)edges % 16) == 0),
+                "surface_select_f32: unaligned pointer");
+  double* part = (double*)workspace;                                 // [rows][slots <= 64], then the integer tables
+  uint32_t* top = (uint32_t*)(part + (int64_t)rows * SD_MAX_SLOTS);  // [rows][2048]
+  uint32_t* mid = top + (int64_t)rows * SD_BINS;                     // [rows][2][2048]
+  uint32_t* low = mid + (int64_t)rows * 2 * SD_BINS;                 // [rows][2][2048], 512 of each in use
+  int32_t* vmax = (int32_t*)(low + (int64_t)rows * 2 * SD_BINS);     // [rows]
+  const int64_t words = (int64_t)rows * (5 * SD_BINS + 1);
+  const int half = B * (C - 1);
+  const int32_t* bits = (const int32_t*)d2;                          // a float >= 0 orders like its bits; -1.0f is negative either way
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(surface_zero_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, top, words);
+  CTSEG_LAUNCH_CHECK("surface_select_f32 (zero)");
+  const dim3 grid((unsigned)slots, (unsigned)rows);
+  if (wide) {
+    hipLaunchKernelGGL(surface_top_f32_kernel<true>, grid, dim3(256), 0, st, edges, bits, counts, half, S, per, top, vmax, part);
+    CTSEG_LAUNCH_CHECK("surface_select_f32 (top)");
+    hipLaunchKernelGGL((surface_lower_f32_kernel<true, 1>), grid, dim3(256), 0, st, edges, bits, counts, half, S, per, q,
+                       (const uint32_t*)top, (const uint32_t*)mid, mid);
+    CTSEG_LAUNCH_CHECK("surface_select_f32 (mid)");
+    hipLaunchKernelGGL((surface_lower_f32_kernel<true, 2>), grid, dim3(256), 0, st, edges, bits, counts, half, S, per, q,
+                       (const uint32_t*)top, (const uint32_t*)mid, low);
+  } else {
+    hipLaunchKernelGGL(surface_top_f32_kernel<false>, grid, dim3(256), 0, st, edges, bits, counts, half, S, per, top, vmax, part);
+    CTSEG_LAUNCH_CHECK("surface_select_f32 (top)");
+    hipLaunchKernelGGL((surface_lower_f32_kernel<false, 1>), grid, dim3(256), 0, st, edges, bits, counts, half, S, per, q,
+                       (const uint32_t*)top, (const uint32_t*)mid, mid);
+    CTSEG_LAUNCH_CHECK("surface_select_f32 (mid)");
+    hipLaunchKernelGGL((surface_lower_f32_kernel<false, 2>), grid, dim3(256), 0, st, edges, bits, counts, half, S, per, q,
+                       (const uint32_t*)top, (const uint32_t*)mid, low);
+  }
+  CTSEG_LAUNCH_CHECK("surface_select_f32 (low)");
+  hipLaunchKernelGGL(surface_pick_f32_kernel, dim3((unsigned)rows), dim3(256), 0, st, counts, half, slots, q, (const uint32_t*)top,
+                     (const uint32_t*)mid, (const uint32_t*)low, (const int32_t*)vmax, (const double*)part, stats, fstats);
+  CTSEG_LAUNCH_CHECK("surface_select_f32 (pick)");
   return 0;
 }

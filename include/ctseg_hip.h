@@ -545,6 +545,28 @@ int ctseg_surface_select(const uint8_t* edges, const int32_t* d2, const int32_t*
                          int32_t C, double q, void* workspace, int64_t workspace_bytes, int32_t* stats, double* fstats,
                          void* stream);
 
+/* The same metrics in physical units: a weighted transform and a select on float32 keys.  Three calls in stream order:
+ *   ctseg_surface_edges -> ctseg_distmap3d_weighted(masks = edges, P = 2*B*(C-1), d2_fg = d2, d2_bg = NULL) -> ctseg_surface_select_f32.
+ * ctseg_distmap3d_weighted: masks as ctseg_distmap3d_batch takes them; w[P][3] float32 on the device, the SQUARED voxel sizes of
+ *   every volume along X, Y, Z (finite and positive: the table is on the device, so the caller answers for its values).
+ *   d2_fg / d2_bg float32 [P][X][Y][Z], either may be NULL, not both: the squared physical distance to the nearest foreground /
+ *   background voxel, 0 at a voxel of that class, -1.0f everywhere when the volume has none.  For voxel v the value is the
+ *   minimum over the voxels u of the class, (dx, dy, dz) = |u - v|, of
+ *     fl(fl(wy * dy^2) + fl(fl(wz * dz^2) + fl(wx * dx^2)))
+ *   every fl() one float32 rounding to nearest, the integer squares exact: the result is defined bit for bit.  No value map is
+ *   written.  workspace >= 6 * P * X * Y * Z bytes, 4-byte aligned, as for ctseg_distmap3d_batch; sides up to 1024.
+ * ctseg_surface_select_f32: ctseg_surface_select on those float32 squared distances.  Rows, ranks, fstats and determinism are the
+ *   same; the order statistics are taken over the bit patterns of the non-negative floats (three radix levels, 11 + 11 + 9 bits);
+ *     stats[r] = {bits of d2 of rank lo, bits of d2 of rank hi, bits of the largest d2, 1}   (float32 bit patterns in int32 words)
+ *   workspace >= 2*B*(C-1) * CTSEG_SURFACE_SELECT_F32_ROW_BYTES bytes, 8-byte aligned.
+ * Both validate every argument on the host before the first launch. */
+#define CTSEG_SURFACE_SELECT_F32_ROW_BYTES 41480
+int ctseg_distmap3d_weighted(const uint8_t* masks, int32_t P, int32_t X, int32_t Y, int32_t Z, const float* w, void* workspace,
+                             int64_t workspace_bytes, float* d2_fg, float* d2_bg, void* stream);
+int ctseg_surface_select_f32(const uint8_t* edges, const float* d2, const int32_t* counts, int32_t B, int32_t X, int32_t Y, int32_t Z,
+                             int32_t C, double q, void* workspace, int64_t workspace_bytes, int32_t* stats, double* fstats,
+                             void* stream);
+
 /* Sliding-window inference (BASELINE.json configs[4]).  The reference has no inferer (grep: 0 hits); the
  * semantics are those of MONAI 0.3 `monai.inferers.sliding_window_inference`, the companion of the `monai.networks.nets.UNet`
  * the reference builds at capstone/volumetric/base_trainer.py:65-72.

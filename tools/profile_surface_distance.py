@@ -10,8 +10,14 @@ surface_distances() call, its allocations and the closing torch ops included.  N
 attached to any figure.
 The host figure is the same metric with scipy on the machine the script runs on: binary_erosion for the surfaces, one
 distance_transform_edt per surface, np.percentile and the means.
+With --spacing SX SY SZ the same run also times the physical-unit path on the same surface masks: ctseg_distmap3d_weighted
+("transform_weighted"), ctseg_surface_select_f32 ("select_f32") and surface_distances(spacing=...) ("whole_call_spacing"), so the two
+transforms are compared on one box in one process.  The per-kernel split of a transform (sweep, Z lines, Y slabs) is not visible to
+device events around an entry point; --kernel-times FILE merges the per-kernel averages of a kernel trace taken in a run of its own
+(a CSV with "Name" and "AverageNs" or "Average" columns, such as a profiler's kernel statistics) into the result under
+"kernel_ms_per_call".
 
-  python tools/profile_surface_distance.py --out profiles/surface_distance.json
+  python tools/profile_surface_distance.py --spacing 0.9765625 0.9765625 2.5 --out profiles/surface_distance.json
 """
 import argparse
 import json
@@ -70,6 +76,16 @@ def host_scipy(pred, target, q):
             "scipy": scipy.__version__}
 
 
+def kernel_times(path):
+    """a kernel-statistics CSV ("Name", "AverageNs" or "Average") -> {kernel name without signature: ms per call} of this library's
+    distance-map and surface kernels"""
+    import csv
+    with open(path) as f:
+        rows = list(csv.DictReader(f))
+    return {r["Name"].split("(")[0].replace("void ", "").replace("ctseg::", ""): float(r.get("AverageNs") or r.get("Average")) / 1e6
+            for r in rows if "distmap3d" in r["Name"] or "surface_" in r["Name"]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", type=int, nargs=3, default=[256, 256, 96])
@@ -78,6 +94,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--spacing", type=float, nargs=3, default=None)
+    ap.add_argument("--kernel-times", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
@@ -119,6 +137,24 @@ def main():
         surface.surface_distances(pair[0], pair[1], C, q)
 
     stages = {"edges": stage_edges, "transform": stage_transform, "select": stage_select, "whole_call": whole}
+    if a.spacing:
+        d2f = torch.empty((P * S,), dtype=torch.float32, device=dev)
+        sel_ws_f = torch.empty((P * surface.SELECT_F32_ROW_BYTES // 8,), dtype=torch.float64, device=dev)
+        w = surface._squared_spacing(a.spacing, 1, 3).to(dev).expand(P, 3).contiguous()
+
+        def stage_transform_weighted(pair):
+            nat.call("ctseg_distmap3d_weighted", nat.ptr(edges), P, X, Y, Z, nat.ptr(w), nat.ptr(dm_ws), dm_ws.numel(), nat.ptr(d2f),
+                     None)
+
+        def stage_select_f32(pair):
+            nat.call("ctseg_surface_select_f32", nat.ptr(edges), nat.ptr(d2f), nat.ptr(cnt), 1, X, Y, Z, C, q, nat.ptr(sel_ws_f),
+                     P * surface.SELECT_F32_ROW_BYTES, nat.ptr(st), nat.ptr(fs))
+
+        def whole_spacing(pair):
+            surface.surface_distances(pair[0], pair[1], C, q, spacing=a.spacing)
+
+        # (after whole_call, which has buffers of its own: `edges` and `cnt` still hold this input's surfaces)
+        stages.update(transform_weighted=stage_transform_weighted, select_f32=stage_select_f32, whole_call_spacing=whole_spacing)
 
     def timed(fn, pair):
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -153,6 +189,18 @@ def main():
                             "d2_max": tab.d2_max[:, 0].tolist(),
                             "ms_per_sample": {n: statistics.median(v) for n, v in times[k].items()},
                             "ms_min_max": {n: [min(v), max(v)] for n, v in times[k].items()}}
+        if a.spacing:
+            tab = surface.surface_distances(pair[0], pair[1], C, q, spacing=a.spacing)
+            torch.cuda.synchronize()
+            ms = res["inputs"][k]["ms_per_sample"]
+            res["inputs"][k]["spacing"] = {"hd": tab.hd[0].tolist(), "assd": tab.assd[0].tolist(), "d2_max": tab.d2_max[:, 0].tolist(),
+                                           "transform_weighted_over_transform": ms["transform_weighted"] / ms["transform"]}
+    if a.spacing:
+        res["workload"]["spacing"] = list(a.spacing)
+        res["workload"]["working_set_bytes_spacing"] = surface.BYTES_PER_VOXEL_WEIGHTED * P * S
+    if a.kernel_times:
+        res["kernel_ms_per_call"] = kernel_times(a.kernel_times)
+        res["kernel_ms_per_call_source"] = "per-kernel averages of a kernel trace of this script, taken in a separate run"
     res["host_scipy"] = "not measured" if a.no_host else {k: host_scipy(*pair, q) for k, pair in host.items()}
     line = json.dumps(res)
     print(line)
