@@ -12,7 +12,7 @@ from typing import List
 
 import torch
 
-from .. import STRUCTURES, segloss, surface
+from .. import STRUCTURES, components, segloss, surface
 from .. import _native as nat
 from ..models import UNet
 from ..models.losses import _as_cl
@@ -28,7 +28,8 @@ SEED = 12342
 class BaseUNet3D(_TrainerBase):
     def __init__(self, filters: List = [16, 32, 64, 128, 256], use_res_units: bool = False, downsample: bool = False,
                  lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
-                 surface_metrics: bool = False, surface_percentile: float = 95.0, surface_spacing=None, **kwargs) -> None:
+                 surface_metrics: bool = False, surface_percentile: float = 95.0, surface_spacing=None,
+                 largest_component: bool = False, largest_component_connectivity=None, **kwargs) -> None:
         """``device_boundary``: opt in to the Boundary loss on volumes; the batch then carries the distance maps as its fourth
         element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise.
         ``surface_metrics``: ``validation_step`` also scores the batch with the percentile Hausdorff distance (``surface_percentile``,
@@ -38,7 +39,14 @@ class BaseUNet3D(_TrainerBase):
         them.
         ``surface_spacing``: the voxel size (x, y, z) of the grid the network trains on, in millimetres, such as the cohort's mean
         after ``Resize3D``; one value for every sample, since the datasets carry no spacing.  The surface metrics are then physical
-        distances and their log keys say so: ``"... HD95 mm (val)"``, ``"... ASSD mm (val)"``."""
+        distances and their log keys say so: ``"... HD95 mm (val)"``, ``"... ASSD mm (val)"``.
+        ``largest_component``: ``validation_step`` also cleans the predicted label map, keeping the largest connected component of
+        every class in every sample (``capstone_amd.components``; ``largest_component_connectivity``: 1, 2, 3 or ``None`` for the
+        full 26 neighbours), and scores the cleaned map IN ADDITION to the raw one: its Dice under the prefix ``"val LCC"``
+        (``"{structure} Dice (val LCC)"``, ``"Mean Dice Score (val LCC)"``) and, with ``surface_metrics``, its surface metrics, kept
+        under ``"val LCC"`` and logged as ``"{structure} HD95 (val LCC)"`` and so on.  ``on_validation_epoch_end`` also logs
+        ``"{structure} components (val)"``, the mean number of components of the raw prediction per class over the epoch's
+        samples.  Per rank, and never in a training step, like the surface metrics."""
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
@@ -52,6 +60,10 @@ class BaseUNet3D(_TrainerBase):
         self.surface_spacing = surface_spacing      # (kept out of hparams too)
         self.surface_score = SurfaceDistanceMetricWrapper3D(surface_percentile, surface_spacing) if surface_metrics else None
         self._surface_kept = {}
+        self.largest_component = largest_component                  # (kept out of hparams, like the switches above)
+        self.largest_component_connectivity = largest_component_connectivity
+        self.lcc_dice_score = DiceMetricWrapper3D() if largest_component else None
+        self._components_kept = []
 
     def _construct_model(self):
         # reference :58-72 — in_channels=1, strides for a 5-entry filter list, num_res_units hard-wired to 2
@@ -148,11 +160,24 @@ class BaseUNet3D(_TrainerBase):
 
     def validation_step(self, batch, batch_idx=0):
         _, masks, _, prediction, _ = self._shared_step(batch, is_training=False)
-        if self.surface_metrics:
-            with torch.no_grad():
-                self.surface_score(_squash_predictions(prediction), masks)
-            last = self.surface_score.last
-            self._surface_kept.setdefault("val", []).append((last.hd, last.assd))
+        if not (self.surface_metrics or self.largest_component):
+            return
+        with torch.no_grad():
+            labels = _squash_predictions(prediction)
+            if self.surface_metrics:
+                self._score_surfaces(labels, masks, "val")
+            if self.largest_component:
+                kept = components.keep_largest_component(labels, self._n_classes,
+                                                         connectivity=self.largest_component_connectivity)
+                self._components_kept.append(kept.count)
+                self._log_dice("val LCC", *self.lcc_dice_score(kept.labels, masks))
+                if self.surface_metrics:
+                    self._score_surfaces(kept.labels, masks, "val LCC")
+
+    def _score_surfaces(self, labels, masks, prefix):
+        self.surface_score(labels, masks)
+        last = self.surface_score.last
+        self._surface_kept.setdefault(prefix, []).append((last.hd, last.assd))
 
     def epoch_surface_metrics(self, prefix="val", reset=True):
         """(HD mean, HD per class (9,), ASSD mean, ASSD per class (9,)) over all samples scored since the last reset: per class the
@@ -169,10 +194,19 @@ class BaseUNet3D(_TrainerBase):
     def on_validation_epoch_end(self, *args, **kwargs):
         """logs the epoch's surface metrics that have a value: "{structure} HD95 (val)", "Mean HD95 (val)", "{structure} ASSD
         (val)", "Mean ASSD (val)" (``HD`` and the percentile); with ``surface_spacing`` the unit follows the name, as in "{structure}
-        HD95 mm (val)" and "Mean ASSD mm (val)", and the keys without it are not logged"""
-        if not self.surface_metrics:
-            return
-        res = self.epoch_surface_metrics("val")
+        HD95 mm (val)" and "Mean ASSD mm (val)", and the keys without it are not logged.  With ``largest_component`` the same
+        keys under "(val LCC)" for the cleaned predictions, and "{structure} components (val)" besides"""
+        if self.surface_metrics:
+            for prefix in ("val", "val LCC") if self.largest_component else ("val",):
+                self._log_surface_epoch(prefix)
+        if self.largest_component and self._components_kept:
+            mean = torch.cat(self._components_kept).double().mean(dim=0)
+            self._components_kept = []
+            for structure, value in zip(STRUCTURES, mean):
+                self.log(f"{structure} components (val)", value, on_step=False, on_epoch=True)
+
+    def _log_surface_epoch(self, prefix):
+        res = self.epoch_surface_metrics(prefix)
         if res is None:
             return
         unit = "" if self.surface_spacing is None else " mm"
@@ -181,9 +215,9 @@ class BaseUNet3D(_TrainerBase):
             finite = torch.isfinite(per_class).tolist()
             for structure, value, ok in zip(STRUCTURES, per_class, finite):
                 if ok:
-                    self.log(f"{structure} {name} (val)", value, on_step=False, on_epoch=True)
+                    self.log(f"{structure} {name} ({prefix})", value, on_step=False, on_epoch=True)
             if any(finite):
-                self.log(f"Mean {name} (val)", mean, on_step=False, on_epoch=True)
+                self.log(f"Mean {name} ({prefix})", mean, on_step=False, on_epoch=True)
 
     def _shared_step(self, batch, is_training: bool):
         images, masks, mask_indicator, dist_maps = self._split_batch(batch)

@@ -15,32 +15,14 @@
 //           ctseg_surface_select_f32 is the same select on the float32 squared distances of ctseg_distmap3d_weighted (physical
 //           units), three levels over the 31-bit patterns of the non-negative floats.
 #include "distmap_common.h"
+#include "label_runs.h"
 
 namespace ctseg {
 
-constexpr int SD_RUN = 16;               // voxels of a lane's run along Z, and bytes of the wide loads and stores
-constexpr int SD_MAX_CLASSES = 16;
 constexpr int SD_BINS = 2048;            // of either radix level: 11 + 11 bits
 constexpr int SD_SHIFT = 11;
 constexpr int SD_MAX_SLOTS = 64;         // workgroups (and float64 partials) per row of the select
 constexpr int SD_CHUNK = 256 * SD_RUN;   // voxels one workgroup of the select takes per step
-enum { SD_AXIS_X = 1, SD_AXIS_Y = 2, SD_AXIS_Z = 4 };
-
-// byte i of a run held as four words; i is a constant after unrolling, so the run stays in registers
-__device__ __forceinline__ uint32_t run_byte(const u32x4& w, int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 255u; }
-
-// n <= 16 bytes at p as four words; WIDE: n == 16 and p is 16-byte aligned
-template <bool WIDE> __device__ __forceinline__ u32x4 load_run(const uint8_t* p, int n) {
-  if constexpr (WIDE) {
-    return *reinterpret_cast<const u32x4*>(p);
-  } else {
-    u32x4 w = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int i = 0; i < SD_RUN; ++i)
-      if (i < n) w[i >> 2] |= (uint32_t)p[i] << ((i & 3) * 8);
-    return w;
-  }
-}
 
 // Grid (ceil(lines * runs / 256), B, 2): side 0 = pred, 1 = target.  Lane: run k of line (x, y) of sample b.
 template <bool WIDE>

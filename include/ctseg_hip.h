@@ -567,6 +567,40 @@ int ctseg_surface_select_f32(const uint8_t* edges, const float* d2, const int32_
                              int32_t C, double q, void* workspace, int64_t workspace_bytes, int32_t* stats, double* fstats,
                              void* stream);
 
+/* Connected components of a label map, and the keep-largest / minimum-size clean-up of a prediction on top of them (what MONAI
+ * ships as KeepLargestConnectedComponent).  Two calls in stream order, no host synchronisation between them:
+ *   ctseg_components_label -> ctseg_components_keep(labels, ids, sizes as the first call left them).
+ * A component is a maximal set of voxels of ONE label in 1..C-1 joined by neighbour steps inside its sample: different classes never
+ * join, samples never join, and the end of a Z row (or of a Y plane) is no neighbour of the start of the next.  Label 0 and labels
+ * >= C are in no component.  Neighbours differ by +-1 along at most `connectivity` (1, 2, 3) of the active axes: 6 / 18 / 26 of them
+ * in a volume; `axes` is the mask of active axes, X = 1 | Y = 2 | Z = 4, as in ctseg_surface_edges (planes: [B][H][W][1] with
+ * axes = 3, where connectivity 1 / 2 is 4 / 8 neighbours); a connectivity above the number of active axes means all of them.
+ * ctseg_components_label: labels uint8 [B][X][Y][Z] -> both int32 [B][X][Y][Z], every word written:
+ *     ids[v]    the smallest index (x * Y + y) * Z + z WITHIN THE SAMPLE over the voxels of v's component, its representative;
+ *               -1 where the voxel is in no component
+ *     sizes[v]  the component's voxel count at its representative (ids[v] == v), 0 everywhere else
+ *   Three launches: tiles of 8 x 16 x 32 voxels labelled in LDS, unions across the tile faces on `ids` (atomic minima), a flatten
+ *   that also adds the tiles' counts up (integer atomic adds).  Parent links only ever decrease, so every loop ends and no
+ *   workgroup waits for another; the representative is the minimum whatever the order of the unions and integer sums commute: the
+ *   output is unique, and two runs give the same bits.  With Z a multiple of 16, labels, ids and sizes are 16-byte aligned.
+ * ctseg_components_keep: out uint8 [B][X][Y][Z], every byte written.  A voxel of a class c whose bit is set in class_mask (bits
+ *   1..C-1 only) keeps its label when (keep_largest == 0 or its component is the largest of class c in its sample) and its
+ *   component has at least min_size voxels; otherwise it becomes 0.  Among equally large components the one with the smallest
+ *   representative wins: the one whose first voxel comes first in raster order.  Label 0, labels >= C and the other classes are
+ *   copied.  table int32 [B][C-1][4], for every class 1..C-1, processed or not:
+ *     {number of components, size of the largest, its representative (-1: the class is absent), voxels set to 0}
+ *   Four launches; the winner is one 64-bit atomic maximum of size << 32 | ~representative per class, counts are integer atomic
+ *   adds: the same bits every run.  workspace >= B * (C-1) * CTSEG_COMPONENTS_KEEP_ROW_BYTES bytes, 8-byte aligned; the call zeroes
+ *   it.  With X * Y * Z a multiple of 16, labels and out are 16-byte aligned.
+ * Both: B >= 1 (at most 65535), sides in 1..1024, B * X * Y * Z < 2^31, 2 <= C <= 16; every argument is validated on the host
+ * before the first launch.  Device memory: 10 bytes per voxel (labels 1 + ids 4 + sizes 4 + out 1) and 16 per sample and class. */
+#define CTSEG_COMPONENTS_KEEP_ROW_BYTES 16
+int ctseg_components_label(const uint8_t* labels, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t C, int32_t connectivity,
+                           int32_t axes, int32_t* ids, int32_t* sizes, void* stream);
+int ctseg_components_keep(const uint8_t* labels, const int32_t* ids, const int32_t* sizes, int32_t B, int32_t X, int32_t Y, int32_t Z,
+                          int32_t C, int32_t class_mask, int32_t keep_largest, int32_t min_size, void* workspace,
+                          int64_t workspace_bytes, uint8_t* out, int32_t* table, void* stream);
+
 /* Sliding-window inference (BASELINE.json configs[4]).  The reference has no inferer (grep: 0 hits); the
  * semantics are those of MONAI 0.3 `monai.inferers.sliding_window_inference`, the companion of the `monai.networks.nets.UNet`
  * the reference builds at capstone/volumetric/base_trainer.py:65-72.
