@@ -971,9 +971,13 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     }
     ce_flush(ce_n);
     // samples this workgroup never touched: zero records (the host sums every slot of every sample)
-    const int n_first = first / G.tiles, n_last = (last - 1) / G.tiles;
-    for (int n = 0; n < P.N; ++n)
-      if ((n < n_first || n > n_last) && tid < E.R) E.part[((int64_t)n * E.P + blockIdx.x) * E.R + tid] = 0.0;
+    // (a workgroup walks first, first + stride, ... < last: with a stride above one it may pass over a whole sample between two
+    // it touches, so the test is per sample — the first tile of the walk at or behind the sample's first tile lies inside it)
+    for (int n = 0; n < P.N; ++n) {
+      const int lo = n * G.tiles > first ? n * G.tiles : first, hi = (n + 1) * G.tiles < last ? (n + 1) * G.tiles : last;
+      const int tn = first + (lo - first + stride - 1) / stride * stride;
+      if (!(tn < hi) && tid < E.R) E.part[((int64_t)n * E.P + blockIdx.x) * E.R + tid] = 0.0;
+    }
     return;
   }
   if constexpr (BST) {      // y values of the first tile (every later tile's are fetched by the slices of the tile before it)

@@ -1,5 +1,5 @@
 """The CPU specification the HIP kernels are held to: a conv layer's forward, input and weight gradient, the InstanceNorm / BatchNorm +
-PReLU backward, the Boundary loss.  torch only, in the precision of the arguments (float64: the reference; float32: the evaluation a
+PReLU backward, the Boundary loss, the per-voxel terms and the gradient of the label losses.  torch only, in the precision of the arguments (float64: the reference; float32: the evaluation a
 bound is measured from); nothing here touches the library.  tests/test_reference_ops.py checks this file against autograd."""
 import torch
 import torch.nn.functional as F
@@ -104,3 +104,58 @@ def boundary64(logits, sides):
     for D, Wt in sides:
         gk[:, 1:] += Wt.reshape(Wt.shape + (1,) * len(sp)) * D.double() / S
     return val.item(), mag.item(), grad, (gk.abs() * p).sum(dim=1, keepdim=True).detach()
+
+
+# ---- label losses: cross-entropy, soft Dice / focal sums, prediction, Dice counts ---------------------------------------------------
+def first_max_index(v):
+    """first index along the last axis at which ``v`` takes its maximum"""
+    C = v.shape[-1]
+    at_max = v == v.max(dim=-1, keepdim=True).values
+    return torch.where(at_max, torch.arange(C), torch.full((), C, dtype=torch.int64)).min(dim=-1).values
+
+
+def dice_count_table(pred, labels, C):
+    """(..., S) predictions and labels -> (..., 3, C) int64: |pred == c & label == c|, |pred == c|, |label == c|; values >= C count nowhere"""
+    cls = torch.arange(C)
+    p, t = pred.long()[..., None] == cls, labels.long()[..., None] == cls
+    return torch.stack([(p & t).sum(-2), p.sum(-2), t.sum(-2)], dim=-2)
+
+
+def seg_loss_terms(x, labels, C, class_weight=None):
+    """per voxel, in the precision of ``x`` (logits (..., S, >= C), labels (..., S) < C): ce = w (lse - x_t) and w (the class weight of
+    the label, or 1); p = softmax, py = p * onehot, fo = (1 - p_t)^2 (-log p_t) at the label's class; pred = softmax THEN the first
+    maximal index; cnt (..., 3, C) = the Dice counts of pred against the labels"""
+    x = x[..., :C]
+    lab = labels.long()
+    oh = F.one_hot(lab, C).to(x.dtype)
+    logp = torch.log_softmax(x, -1)
+    p = torch.softmax(x, -1)
+    logpt, pt = (logp * oh).sum(-1), (p * oh).sum(-1)
+    w = torch.ones_like(logpt) if class_weight is None else class_weight.to(x.dtype)[lab]
+    pred = first_max_index(p)
+    return dict(ce=w * -logpt, w=w, p=p, py=p * oh, fo=((1 - pt) ** 2 * -logpt)[..., None] * oh, pred=pred,
+                cnt=dice_count_table(pred, lab, C))
+
+
+def seg_loss_records(terms, ce_only=False):
+    """the terms of seg_loss_terms as one row per voxel in the order of a partial record: (ce, w, p[C], py[C], fo[C]); ``ce_only``:
+    the cross-entropy-only pass, whose entries from 2 on are 0"""
+    soft = torch.cat([terms["p"], terms["py"], terms["fo"]], -1)
+    return torch.cat([terms["ce"][..., None], terms["w"][..., None], torch.zeros_like(soft) if ce_only else soft], -1)
+
+
+def seg_loss_grad(x, labels, C, coef, cw):
+    """d L / d x in the precision of ``x`` (logits (B, S, C)) by autograd, L the scalar one coefficient row per sample defines:
+    coef (B, 1 + 3 C) = (s, a[C], b[C], f[C]), cw (C,) class weights:
+    L = sum_voxels  s w_t (-log p_t)  +  sum_c (a_c [c = t] + b_c) p_c  +  f_t (1 - p_t)^2 (-log p_t)"""
+    xr = x[..., :C].detach().clone().requires_grad_(True)
+    dt = xr.dtype
+    p = torch.softmax(xr, -1)
+    oh = F.one_hot(labels.long(), C).to(dt)
+    logp = torch.log_softmax(xr, -1)
+    pt, logpt = (p * oh).sum(-1), (logp * oh).sum(-1)
+    cf = coef.to(dt)
+    a, b_, f = cf[:, None, 1:1 + C], cf[:, None, 1 + C:1 + 2 * C], cf[:, None, 1 + 2 * C:]
+    w = cw.to(dt)[labels.long()]
+    L = (cf[:, None, 0] * w * -logpt).sum() + ((a * oh + b_) * p).sum() + ((f * oh).sum(-1) * -(1 - pt) ** 2 * logpt).sum()
+    return torch.autograd.grad(L, xr)[0]

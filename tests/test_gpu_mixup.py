@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd import segloss  # noqa: E402
 from capstone_amd._native import BF16, F32  # noqa: E402
+from reference_ops import seg_loss_grad  # noqa: E402
 
 DEV = "cuda:0"
 NAMES = ["CrossEntropy", "Dice", "Focal", "GeneralizedDice", "WeightedCrossEntropy"]
@@ -73,18 +74,7 @@ def _pair_case(S):
         eng.stats(xd.data_ptr(), LD)
         single.append((eng.cnt.cpu().clone(), eng.red.cpu().clone()))
     # float64 reference of each side's gradient: the scalar whose derivative the kernel's formula is
-    terms = []
-    for s, lab in enumerate((labels, labels[idx])):
-        xr = x[..., :C].double().requires_grad_(True)
-        p = torch.softmax(xr, -1)
-        oh = torch.nn.functional.one_hot(lab.long(), C).double()
-        logp = torch.log_softmax(xr, -1)
-        pt, logpt = (p * oh).sum(-1), (logp * oh).sum(-1)
-        cf = coef[:, s].double()
-        a, b_, f = cf[:, None, 1:1 + C], cf[:, None, 1 + C:1 + 2 * C], cf[:, None, 1 + 2 * C:]
-        w = cw[s].double()[lab.long()]
-        L = (cf[:, None, 0] * w * -logpt).sum() + ((a * oh + b_) * p).sum() + ((f * oh).sum(-1) * -(1 - pt) ** 2 * logpt).sum()
-        terms.append(torch.autograd.grad(L, xr)[0])
+    terms = [seg_loss_grad(x[..., :C].double(), lab, C, coef[:, s], cw[s]) for s, lab in enumerate((labels, labels[idx]))]
     _CASE[S] = dict(x=x, xd=xd, labels=labels, coef=coef, cw=cw, single=single, terms=terms)
     return _CASE[S]
 

@@ -6,8 +6,10 @@ import torch.nn.functional as F
 
 from capstone_amd._native import BF16, F32
 from helpers import check_elems, elem_bound, sum_bound
-from reference_ops import (boundary64, boundary_weights64, conv_dgrad, conv_fwd, conv_module, conv_out_shape, conv_wgrad, norm_prelu_dy,
-                           norm_prelu_terms)
+from loss_cases import (HEAD_CASES, HEAD_EMPTY_WG_CASE, HEAD_IDS, HEAD_LOSS_SCALE, SEG_S, SEG_SHAPES, head_case, head_reference, partials_case,
+                        partials_reference, seg_class_weight, seg_loss_case, seg_stats_reference, top_margin)
+from reference_ops import (boundary64, boundary_weights64, conv_dgrad, conv_fwd, conv_module, conv_out_shape, conv_wgrad, dice_count_table,
+                           first_max_index, norm_prelu_dy, norm_prelu_terms, seg_loss_grad, seg_loss_records, seg_loss_terms)
 
 F64 = torch.float64
 # an odd and an even extent per axis: stride 2 needs output_padding 1 for the even ones and 0 for the odd ones
@@ -134,6 +136,166 @@ def test_boundary_weights64():
     w = boundary_weights64(ind, True, B, K)
     assert torch.equal(w, torch.full((K,), 0.25, dtype=F64)[None, :] * ind.double() / B)
     assert float(w[:, 0].abs().max()) == 0.0
+
+
+# ---- label losses -------------------------------------------------------------------------------------------------------------
+def _loss_inputs(C=5, B=2, S=37):
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(B, S, C, generator=g, dtype=F64) * 2
+    labels = torch.randint(0, C, (B, S), generator=g)
+    cw = torch.rand(C, generator=g, dtype=F64) + 0.1
+    return x, labels, cw
+
+
+def test_seg_loss_terms_equal_cross_entropy_and_the_written_out_sums():
+    C = 5
+    x, labels, cw = _loss_inputs(C)
+    flat, lab = x.reshape(-1, C), labels.reshape(-1)
+    for w in (None, cw):
+        t = seg_loss_terms(x, labels, C, w)
+        want_sum = F.cross_entropy(flat, lab, weight=w, reduction="sum")
+        want_mean = F.cross_entropy(flat, lab, weight=w)
+        assert abs(float(t["ce"].sum() - want_sum)) <= 1e-12 * float(want_sum)
+        assert abs(float(t["ce"].sum() / t["w"].sum() - want_mean)) <= 1e-12 * float(want_mean), "the mean divides by the weight sum"
+        assert torch.equal(t["w"], torch.ones_like(t["w"]) if w is None else w[labels])
+    t = seg_loss_terms(x, labels, C)
+    p = torch.softmax(x, -1)
+    oh = F.one_hot(labels, C).double()
+    pt = p.gather(-1, labels[..., None])[..., 0]
+    assert torch.equal(t["p"], p) and torch.equal(t["py"], p * oh)
+    assert float((t["py"].sum(-1) - pt).abs().max()) == 0.0
+    fo = (1 - pt) ** 2 * -torch.log(pt)
+    assert float((t["fo"].sum(-1) - fo).abs().max()) <= 1e-14 and bool(((t["fo"] != 0) <= (oh == 1)).all()), "focal term at the label's class"
+    rec = seg_loss_records(t)
+    assert rec.shape[-1] == 2 + 3 * C and torch.equal(rec[..., 0], t["ce"]) and torch.equal(rec[..., 2 + C:2 + 2 * C], t["py"])
+    assert float(seg_loss_records(t, ce_only=True)[..., 2:].abs().max()) == 0.0
+    # a wider row: the columns from C on are not read
+    wide = torch.cat([x, torch.full_like(x[..., :3], 64.0)], -1)
+    assert torch.equal(seg_loss_terms(wide, labels, C)["ce"], t["ce"])
+
+
+def test_prediction_is_the_first_maximal_index_and_the_counts_follow_it():
+    x = torch.tensor([[[0.0, 1.0, 1.0, -1.0], [2.0, 2.0, 2.0, 0.0], [0.5, -1.0, 0.25, 0.5], [0.0, 0.0, 0.0, 3.0]]], dtype=F64)
+    labels = torch.tensor([[1, 0, 3, 3]])
+    t = seg_loss_terms(x, labels, 4)
+    assert t["pred"].tolist() == [[1, 0, 0, 3]]
+    assert torch.equal(first_max_index(x), t["pred"])
+    #                         intersection   predicted      truth
+    assert t["cnt"].tolist() == [[[1, 1, 0, 1], [2, 1, 0, 1], [1, 1, 0, 2]]]
+    # labels outside the classes count nowhere
+    got = dice_count_table(torch.tensor([[0, 255, 4, 1]]), torch.tensor([[0, 255, 1, 4]]), 4)
+    assert got.tolist() == [[[1, 0, 0, 0], [1, 1, 0, 0], [1, 1, 0, 0]]]
+
+
+def test_seg_loss_grad_equals_autograd_of_cross_entropy_and_the_closed_form():
+    C = 5
+    x, labels, cw = _loss_inputs(C)
+    B = x.shape[0]
+    g = torch.Generator().manual_seed(12)
+    # cross-entropy alone: coefficient row (s, 0 ...)
+    coef = torch.zeros(B, 1 + 3 * C, dtype=F64)
+    coef[:, 0] = torch.tensor([0.25, 3.0], dtype=F64)
+    got = seg_loss_grad(x, labels, C, coef, cw)
+    xr = x.clone().requires_grad_(True)
+    L = sum(coef[b, 0] * F.cross_entropy(xr[b], labels[b], weight=cw, reduction="sum") for b in range(B))
+    want, = torch.autograd.grad(L, xr)
+    assert float((got - want).abs().max()) <= 1e-13 * float(want.abs().max())
+    # the full row against the derivative written out: s w (p - 1) + p (g - <g, p>) + f (2 (1 - p_t) p_t log p_t - (1 - p_t)^2)(1 - p)
+    coef[:, 1:] = torch.randn(B, 3 * C, generator=g, dtype=F64)
+    got = seg_loss_grad(x, labels, C, coef, cw)
+    p = torch.softmax(x, -1)
+    oh = F.one_hot(labels, C).double()
+    pt = (p * oh).sum(-1, keepdim=True)
+    a, b_, f = coef[:, None, 1:1 + C], coef[:, None, 1 + C:1 + 2 * C], coef[:, None, 1 + 2 * C:]
+    gk = a * oh + b_
+    ft = (f * oh).sum(-1, keepdim=True)
+    fterm = ft * (2 * (1 - pt) * pt * torch.log(pt) - (1 - pt) ** 2)
+    want = coef[:, None, :1] * cw[labels][..., None] * (p - oh) + p * (gk - (gk * p).sum(-1, keepdim=True)) + fterm * (oh - p)
+    assert float((got - want).abs().max()) <= 1e-12 * float(want.abs().max())
+    assert got.dtype == F64 and seg_loss_grad(x.float(), labels, C, coef, cw).dtype == torch.float32, "the precision of x"
+
+
+@pytest.mark.parametrize("C,ld,S", [(C, ld, S) for C, ld in SEG_SHAPES for S in SEG_S] + [(10, 12, 10)])      # S = 10: the direct call
+def test_seg_loss_case_preconditions(C, ld, S):
+    case = seg_loss_case(C, ld, S)
+    x, labels = case["x"], case["labels"].long()
+    assert x.shape == (3, S, ld) and x.dtype == torch.float32
+    assert torch.equal(torch.round(x * 1024.0), x * 1024.0), "multiples of 2^-10"
+    m = top_margin(x[..., :C].double())
+    assert bool(((m == 0) | (m >= 2.0 ** -10)).all())
+    ties = x[..., :C] == x[..., :C].max(-1, keepdim=True).values
+    assert int((ties.sum(-1) == 2).sum()) >= 3 and (C < 3 or int((ties.sum(-1) == 3).sum()) >= 3), "exact ties of two and of three"
+    for r, cls in case["tie_rows"]:
+        assert first_max_index(x[:, r, :C]).tolist() == [cls[0]] * 3
+    assert int(labels.max()) == C - 1
+    hist = F.one_hot(labels, C).sum(1)
+    assert bool((hist[1:] > 0).all()) and int(hist[0, C - 1]) == 0 and bool((hist[0, :C - 1] > 0).all() or S < 100)
+    for weighted in (False, True):
+        for ce_only in (False, True):
+            ref = seg_stats_reference(C, ld, S, weighted, ce_only)          # asserts 0 < bound < 1 / (4 S)
+            assert 0.0 < ref["bound"] < 1.0 / (4 * S)
+            assert torch.equal(ref["pred"], ref["pred32"]), "float32 and float64 softmax order the classes alike"
+            assert torch.equal(ref["pred"], first_max_index(x[..., :C])), "softmax keeps the order and the ties of the logits"
+            assert ref["sums"].shape == (3, 2 + 3 * C)
+
+
+HEAD_ALL = HEAD_CASES + [HEAD_EMPTY_WG_CASE]
+
+
+@pytest.mark.parametrize("C,cin,residual,g_ld,dtn,weighted,shape", HEAD_ALL, ids=HEAD_IDS + ["empty-workgroups"])
+def test_head_case_preconditions(C, cin, residual, g_ld, dtn, weighted, shape):
+    hc = head_case(C, cin, shape, residual)
+    st = torch.bfloat16 if dtn == "bf16" else torch.float16
+    unit = 2.0 ** -11
+    assert torch.equal(hc.x, torch.round(hc.x)) and torch.equal(hc.x.to(st).float(), hc.x), "activations: integers of the storage type"
+    wu, bu = hc.w / unit, hc.b / unit
+    assert torch.equal(wu, torch.round(wu)) and float(wu.abs().max()) <= 127 and torch.equal(hc.w.to(st).float(), hc.w)
+    assert bool((wu[:, 1:].abs().flatten(2).sum(1) > 0).all()), "all 27 taps carry weights"
+    assert torch.equal(bu, torch.round(bu))
+    y64, y32 = hc.logits(torch.float64), hc.logits(torch.float32)
+    assert torch.equal(y32.double(), y64), "the float32 convolution is exact"
+    assert float(y64.abs().max()) / unit < 2.0 ** 20
+    r = hc.regions()
+    print(r)
+    assert r["min_margin"] >= 2.0 ** -12
+    assert r["tie2"] > 0 and (C < 3 or r["tie3"] > 0), "(a) exact ties of the top two and the top three"
+    assert r["near_first"] + r["near_later"] > 0, "(b) margins in (0, 1e-3)"
+    assert r["background"] == r["tile0"] == shape[0] * 256, "(c) the first tile of every sample: background in truth and prediction"
+    assert r["ordinary"] > r["tile0"] // 2, "(d)"
+    spread = y64.max(-1).values - y64.min(-1).values
+    assert 0.25 < float(spread.median()) < 8.0, "logits spread of order 1: no saturated softmax"
+    ref = head_reference(C, cin, residual, weighted, shape, HEAD_LOSS_SCALE[dtn])
+    S = shape[1] * shape[2] * shape[3]
+    if dtn == "fp16":
+        mag = ref["g64"].abs()
+        assert float(mag[mag > 0].min()) >= 2.0 ** -14 and float(mag.max()) < 65504.0, "no fp16 subnormal or overflow in the gradient"
+    assert 0.0 < ref["bound"] < 1.0 / (4 * S)
+    assert torch.equal(ref["pred"], ref["pred_softmax"]), "softmax then argmax = first maximal logit"
+    hist = F.one_hot(hc.labels.long().reshape(shape[0], -1), C).sum(1)
+    assert bool((hist > 0).all()), "labels cover every class in every sample"
+    assert float((ref["g32"].double() - ref["g64"]).abs().max()) > 0
+
+
+def test_head_cases_take_both_directions_of_a_near_tie():
+    tot = {"near_first": 0, "near_later": 0}
+    for C, cin, residual, _, _, _, shape in HEAD_CASES:
+        r = head_case(C, cin, shape, residual).regions()
+        tot = {k: tot[k] + r[k] for k in tot}
+    assert tot["near_first"] > 0 and tot["near_later"] > 0, tot
+
+
+@pytest.mark.parametrize("R", [1, 32, 64])
+@pytest.mark.parametrize("P", [1, 255, 256, 257, 2048])
+def test_partials_case_bound(P, R):
+    part = partials_case(P, R)
+    exact, mag, bound = partials_reference(part)
+    assert part.shape == (2, P, R) and bool((part > 0).any()) and bool((part < 0).any()) or P * R == 1
+    assert float(part.abs().max() / part.abs().min()) > 2.0 ** 20 or P * R == 1, "mixed magnitude"
+    if P == 1:
+        assert bound == 0.0 and torch.equal(exact, part[:, 0]), "one slot: the sum is the entry"
+    else:
+        assert 0.0 < bound < 1e-13, "numpy's pairwise sum errs, by a few ulp"
+    assert bool((mag >= exact.abs()).all())
 
 
 # ---- bounds -------------------------------------------------------------------------------------------------------------------
