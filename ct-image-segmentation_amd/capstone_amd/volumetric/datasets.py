@@ -18,11 +18,15 @@ from .transforms import InstancePipeline3D
 
 
 class MiccaiDataset3D:
-    def __init__(self, path: str, transform=None, device="cuda", dist_maps: bool = False, signed: bool = False):
+    def __init__(self, path: str, transform=None, device="cuda", dist_maps: bool = False, signed: bool = False, generator=None):
         """``dist_maps=True``: ``__getitem__`` returns a fourth element, the (9,H,W,D) fp32 distance maps of the transformed masks
-        (the Boundary loss's input, ``BaseUNet3D(device_boundary=True)``); ``signed`` as ``data.utils.compute_distance_map``."""
+        (the Boundary loss's input, ``BaseUNet3D(device_boundary=True)``); ``signed`` as ``data.utils.compute_distance_map``.
+        ``generator`` (a ``numpy.random.Generator``) is handed to an augmenting transform (``InstancePipeline3D(augment=...)``) for
+        its draws; when such a transform reports a channel permutation (``"channel_src"``: a left-right mirror swapped the paired
+        structures), ``mask_indicator`` is permuted with it."""
         self.path = Path(path).absolute()
         self.transform = transform
+        self.generator = generator
         self.dist_maps, self.signed = dist_maps, signed
         if dist_maps and transform is not None and not getattr(transform, "dist_maps", False):
             raise ValueError("MiccaiDataset3D(dist_maps=True) needs a transform that returns \"dist_maps\" "
@@ -43,9 +47,14 @@ class MiccaiDataset3D:
         masks = masks.to(self.device, non_blocking=True)
         hist = maps = None
         if self.transform is not None:
-            transformed = self.transform(image=image, masks=masks)
+            if getattr(self.transform, "augment", None) is not None:
+                transformed = self.transform(image=image, masks=masks, generator=self.generator)
+            else:
+                transformed = self.transform(image=image, masks=masks)
             image, masks, hist = transformed["image"], transformed["masks"], transformed.get("hist")
             maps = transformed.get("dist_maps") if self.dist_maps else None
+            if transformed.get("channel_src") is not None:
+                mask_indicator = mask_indicator[np.asarray(transformed["channel_src"], dtype=np.int64)]
         elif self.dist_maps:
             maps = compute_distance_map(masks, signed=self.signed, spatial_dims=3)
         mask_indicator = torch.from_numpy(mask_indicator).to(self.device)
@@ -71,8 +80,9 @@ def collate_3d(samples):
 
 
 def get_miccai_3d(split: str = "train", transform=None, root: str = "storage", device="cuda", dist_maps: bool = False,
-                  signed: bool = False):
+                  signed: bool = False, generator=None):
     assert split in ["train", "valid", "test"], "Invalid data split passed"
     if transform is None:
         transform = InstancePipeline3D(dist_maps=dist_maps, signed=signed)
-    return MiccaiDataset3D(f"{root}/miccai_3d/{split}", transform=transform, device=device, dist_maps=dist_maps, signed=signed)
+    return MiccaiDataset3D(f"{root}/miccai_3d/{split}", transform=transform, device=device, dist_maps=dist_maps, signed=signed,
+                           generator=generator)

@@ -10,10 +10,16 @@ volumetric/predefined.py:4-7 — ends on a contiguous tensor with no further cop
 capstone/transforms/transforms_2d.py:97-107, which the reference's 3-D path omits) and the nine masks resized, permuted and —
 with ``squash=True`` — reduced to the label map of ``_squash_masks_3D`` (volumetric/utils.py:4-7) in the same pass: 1 byte
 per voxel leaves the kernel instead of 9, and the trainer's squash pass disappears.
+
+``Augment3D`` is the spatial and intensity augmentation of that pipeline, which the reference's 3-D path lacks: random rotation,
+zoom, shift and mirror as one 3 x 4 matrix, drawn on the host and applied by ``ctseg_augment3d_to_hwd`` in the same single pass
+(``augment3d_to_hwd``).  A left-right mirror swaps the paired structures' mask channels, see ``Augment3D.channel_src``.
 There is no CPU fallback: CPU tensors raise ``NativeError``.
 """
+import ctypes
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .. import _native as nat
@@ -67,6 +73,148 @@ def resize3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor]
     return img_out, m_out, lab, hist
 
 
+_BORDERS = {"constant": 0, "edge": 1}
+_INTERPS = {"nearest": 0, "trilinear": 1}
+
+
+def augment3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor], size: Sequence[int], matrix, interp=1,
+                     border="constant", cval: float = 0.0, mask_src=None, window=None, gain: float = 1.0, bias: float = 0.0,
+                     want_masks: bool = True, want_labels: bool = False):
+    """``resize3d_to_hwd`` with the output voxel sent through ``matrix`` first: (3, 4), rows and columns ordered d, h, w, mapping an
+    OUTPUT voxel of the ``size`` grid to the point of that same grid it samples (include/ctseg_hip.h has the rules).  ``interp``
+    0 / "nearest" or 1 / "trilinear" for the image (masks are always nearest), ``border`` "constant" (image ``cval``, masks 0) or
+    "edge"; output mask channel k reads input channel ``mask_src[k]``; the windowed value becomes ``v * gain + bias``.
+    -> image (H',W',D') fp32, masks (K,H',W',D') u8, labels (H',W',D') u8, hist (K+1)"""
+    ref = image if image is not None else masks
+    nat.require_gpu(ref, "Augment3D")
+    D, H, W = ref.shape[-3:]
+    Do, Ho, Wo = (int(v) for v in size)
+    dev = ref.device
+    img_out = m_out = lab = hist = None
+    code, K = nat.F32, 0
+    if image is not None:
+        image, code = _image_code(image.reshape(D, H, W))
+        img_out = torch.empty((Ho, Wo, Do), dtype=torch.float32, device=dev)
+    if masks is not None:
+        masks = masks.reshape(-1, D, H, W)
+        if masks.dtype != torch.uint8:
+            masks = masks.to(torch.uint8)
+        masks = masks.contiguous()
+        K = masks.shape[0]
+        if want_masks:
+            m_out = torch.empty((K, Ho, Wo, Do), dtype=torch.uint8, device=dev)
+        if want_labels:
+            lab = torch.empty((Ho, Wo, Do), dtype=torch.uint8, device=dev)
+            hist = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    wmode, lo, hi = _window_args(window)
+    mat = (ctypes.c_float * 12)(*np.asarray(matrix, dtype=np.float32).reshape(12).tolist())
+    src = None
+    if mask_src is not None:
+        src = [int(v) for v in mask_src]
+        if len(src) != K:
+            raise nat.NativeError(f"Augment3D: mask_src has {len(src)} entries for {K} mask channels")
+        src = (ctypes.c_int32 * K)(*src)
+    nat.call("ctseg_augment3d_to_hwd", nat.ptr(image), code, nat.ptr(masks), K, D, H, W, Do, Ho, Wo,
+             ctypes.addressof(mat), _INTERPS.get(interp, interp), _BORDERS.get(border, border), float(cval),
+             ctypes.addressof(src) if src is not None else None, wmode, lo, hi, float(gain), float(bias),
+             nat.ptr(img_out), nat.ptr(m_out), nat.ptr(lab), nat.ptr(hist))
+    return img_out, m_out, lab, hist
+
+
+def _axis_ranges(v, what):
+    """(lo, hi) for all three axes, or ((lo, hi), (lo, hi), (lo, hi)) per axis d, h, w -> (3, 2) float64"""
+    a = np.asarray(v, dtype=np.float64)
+    if a.shape == (2,):
+        a = np.tile(a, (3, 1))
+    if a.shape != (3, 2) or (a[:, 0] > a[:, 1]).any():
+        raise ValueError(f"Augment3D: {what} is (lo, hi) or one (lo, hi) per axis, lo <= hi")
+    return a
+
+
+class Augment3D:
+    """Random affine + mirror + intensity augmentation of a volume, applied by ``InstancePipeline3D(augment=...)`` in its one pass.
+
+    All axes are ordered d, h, w: the reference's (D, H, W) arrays, W being the patient's left-right axis.
+    ``rotate`` = half-ranges in radians of the angles about the d, h and w axes (the turn about d is the in-plane one), about the
+    centre of the output grid; ``scale`` = (lo, hi) of the zoom factors, drawn per axis, or one (lo, hi) per axis (a factor above
+    1 magnifies); ``translate`` = half-ranges in output voxels; ``flip_prob`` = probability of a mirror per axis;
+    ``swap_pairs`` = mask channels that trade places under a w mirror (default: OpticNerve, Parotid, Submandibular L/R of
+    ``STRUCTURES``); ``gain`` / ``bias`` = (lo, hi) of ``v * gain + bias`` after the window, or None; ``interp`` "trilinear" or
+    "nearest" for the image (masks are always nearest); ``border`` "constant" (``cval`` / 0) or "edge"; ``p`` = probability that
+    anything is applied at all.
+
+    The matrix maps an output voxel o to the point q = L o + offset it samples (the sampling direction), composed in float64 as
+        L = R_w(angle_w) . R_h(angle_h) . R_d(angle_d) . diag(1 / scale) . F,      offset = c - L c + shift,   c = (size - 1) / 2
+    so, read from the right: the output voxel is mirrored (F = diag of +-1, exact integers), divided by the zoom, then turned
+    about d, about h and about w; the shift comes last.  With axes ordered (d, h, w) and (c, s) = (cos, sin) of the angle,
+        R_d = [[1, 0, 0], [0, c, -s], [0, s, c]],   R_h = [[c, 0, s], [0, 1, 0], [-s, 0, c]],   R_w = [[c, -s, 0], [s, c, 0], [0, 0, 1]].
+    The result is rounded to float32 once."""
+
+    def __init__(self, rotate=(0.0, 0.0, 0.0), scale=(1.0, 1.0), translate=(0.0, 0.0, 0.0), flip_prob=(0.0, 0.0, 0.0),
+                 swap_pairs=((3, 4), (5, 6), (7, 8)), gain=None, bias=None, interp="trilinear", border="constant", cval: float = 0.0,
+                 p: float = 1.0):
+        self.rotate = np.abs(np.asarray(rotate, dtype=np.float64).reshape(3))
+        self.scale = _axis_ranges(scale, "scale")
+        if (self.scale <= 0).any():
+            raise ValueError("Augment3D: scale factors are positive")
+        self.translate = np.abs(np.asarray(translate, dtype=np.float64).reshape(3))
+        self.flip_prob = np.asarray(flip_prob, dtype=np.float64).reshape(3)
+        self.swap_pairs = tuple((int(a), int(b)) for a, b in swap_pairs)
+        self.gain = None if gain is None else tuple(float(v) for v in gain)
+        self.bias = None if bias is None else tuple(float(v) for v in bias)
+        if interp not in _INTERPS or border not in _BORDERS:
+            raise ValueError(f"Augment3D: interp is one of {sorted(_INTERPS)}, border one of {sorted(_BORDERS)}")
+        self.interp, self.border, self.cval, self.p = interp, border, float(cval), float(p)
+        self._rng = np.random.default_rng()
+
+    @staticmethod
+    def identity_params() -> dict:
+        return {"applied": False, "angles": (0.0, 0.0, 0.0), "scales": (1.0, 1.0, 1.0), "shifts": (0.0, 0.0, 0.0),
+                "flips": (False, False, False), "gain": 1.0, "bias": 0.0}
+
+    def draw(self, generator=None) -> dict:
+        """one instance's parameters, uniform in the ranges, from a ``numpy.random.Generator``; the draws are made in one fixed
+        order and number whatever the ranges are (applied, angles, scales, shifts, flips, gain, bias): 15 uniforms per call"""
+        g = generator if generator is not None else self._rng
+        u = g.random(15)
+        if not u[0] < self.p:
+            return self.identity_params()
+        sym = 2.0 * u[1:10] - 1.0
+        lo, hi = self.scale[:, 0], self.scale[:, 1]
+        gain = 1.0 if self.gain is None else self.gain[0] + (self.gain[1] - self.gain[0]) * u[13]
+        bias = 0.0 if self.bias is None else self.bias[0] + (self.bias[1] - self.bias[0]) * u[14]
+        return {"applied": True, "angles": tuple((sym[0:3] * self.rotate).tolist()),
+                "scales": tuple((lo + (hi - lo) * u[4:7]).tolist()), "shifts": tuple((sym[6:9] * self.translate).tolist()),
+                "flips": tuple(bool(v) for v in u[10:13] < self.flip_prob), "gain": float(gain), "bias": float(bias)}
+
+    @staticmethod
+    def matrix(size, params) -> np.ndarray:
+        """(3, 4) float32 sampling matrix of ``params`` on the ``size`` = (D', H', W') grid: the class docstring has the order"""
+        c = (np.asarray(size, dtype=np.float64).reshape(3) - 1.0) / 2.0
+        ad, ah, aw = (float(v) for v in params["angles"])
+        cd, sd, ch, sh, cw, sw = np.cos(ad), np.sin(ad), np.cos(ah), np.sin(ah), np.cos(aw), np.sin(aw)
+        Rd = np.array([[1, 0, 0], [0, cd, -sd], [0, sd, cd]], dtype=np.float64)
+        Rh = np.array([[ch, 0, sh], [0, 1, 0], [-sh, 0, ch]], dtype=np.float64)
+        Rw = np.array([[cw, -sw, 0], [sw, cw, 0], [0, 0, 1]], dtype=np.float64)
+        S = np.diag(1.0 / np.asarray(params["scales"], dtype=np.float64).reshape(3))
+        F = np.diag([-1.0 if f else 1.0 for f in params["flips"]])
+        L = Rw @ Rh @ Rd @ S @ F
+        out = np.empty((3, 4), dtype=np.float64)
+        out[:, :3] = L
+        out[:, 3] = c - L @ c + np.asarray(params["shifts"], dtype=np.float64).reshape(3)
+        return out.astype(np.float32)
+
+    def channel_src(self, params, K: int) -> list:
+        """output mask channel k reads input channel ``channel_src[k]``: the identity, or ``swap_pairs`` swapped when the w mirror
+        (the patient's left-right) was drawn; ``mask_indicator`` takes the same permutation"""
+        src = list(range(K))
+        if params["flips"][2]:
+            for a, b in self.swap_pairs:
+                if a < K and b < K:
+                    src[a], src[b] = b, a
+        return src
+
+
 class Resize3D:
     def __init__(self, size=(96, 256, 256), always_apply=True, p=1.0):
         self.size = tuple(size)      # DxHxW, as the reference
@@ -105,18 +253,34 @@ class InstancePipeline3D:
     ``squash=True``: "masks" = (H,W,D) uint8 label map with ``"hist"`` = per-class voxel counts riding along.
     ``dist_maps=True`` adds ``"dist_maps"``: the (9,H,W,D) fp32 distance maps of the nine RESIZED masks
     (``data.utils.compute_distance_map(spatial_dims=3)``, ``signed`` as there).  Structures overlap, so the label map cannot give
-    them back: a squashing pipeline then has the same resize launch write the nine masks beside the label map."""
+    them back: a squashing pipeline then has the same resize launch write the nine masks beside the label map.
+    ``augment`` = an ``Augment3D``: the one launch is ``ctseg_augment3d_to_hwd`` instead, with parameters drawn from ``generator``
+    (a ``numpy.random.Generator``) or given as ``params`` (``Augment3D.draw``'s dict); the result then carries ``"params"`` and
+    ``"channel_src"``, the K input channels behind the output mask channels, which ``mask_indicator`` has to follow.  The
+    distance maps are those of the augmented masks."""
 
     def __init__(self, size=(96, 256, 256), squash: bool = False, window: Optional[Tuple] = None, dist_maps: bool = False,
-                 signed: bool = False):
+                 signed: bool = False, augment: Optional[Augment3D] = None):
         self.size, self.squash, self.window, self.dist_maps, self.signed = tuple(size), squash, window, dist_maps, signed
+        self.augment = augment
 
-    def __call__(self, image: torch.Tensor, masks) -> dict:
+    def __call__(self, image: torch.Tensor, masks, params=None, generator=None) -> dict:
         if isinstance(masks, (list, tuple)):
             masks = torch.stack(list(masks))
-        img, m, lab, hist = resize3d_to_hwd(image, masks, self.size, self.window, want_masks=self.dist_maps or not self.squash,
-                                            want_labels=self.squash)
-        out = {"image": img.unsqueeze(0), "masks": lab if self.squash else m}
+        want_masks = self.dist_maps or not self.squash
+        extra = {}
+        if self.augment is None:
+            img, m, lab, hist = resize3d_to_hwd(image, masks, self.size, self.window, want_masks=want_masks, want_labels=self.squash)
+        else:
+            aug = self.augment
+            if params is None:
+                params = aug.draw(generator)
+            src = aug.channel_src(params, masks.reshape((-1,) + tuple(masks.shape[-3:])).shape[0])
+            img, m, lab, hist = augment3d_to_hwd(image, masks, self.size, aug.matrix(self.size, params), aug.interp, aug.border,
+                                                 aug.cval, src, self.window, params["gain"], params["bias"], want_masks=want_masks,
+                                                 want_labels=self.squash)
+            extra = {"channel_src": src, "params": params}
+        out = {"image": img.unsqueeze(0), "masks": lab if self.squash else m, **extra}
         if self.squash:
             out["hist"] = hist
         if self.dist_maps:
@@ -125,3 +289,10 @@ class InstancePipeline3D:
 
 
 windowed_degree_0 = {"train": InstancePipeline3D(), "test": InstancePipeline3D()}      # volumetric/predefined.py:4-7
+# the reference has no augmenting 3-D preset.  Up to 15 degrees in plane and 3 degrees out of it, +-10 % zoom, a few voxels of shift
+# and the left-right mirror; no intensity jitter: the 3-D path has no window, so the image scale is raw and unknown here
+augmented_degree_1 = {
+    "train": InstancePipeline3D(augment=Augment3D(rotate=(0.26, 0.05, 0.05), scale=(0.9, 1.1), translate=(2, 8, 8),
+                                                  flip_prob=(0, 0, 0.5))),
+    "test": InstancePipeline3D(),
+}

@@ -438,6 +438,33 @@ int ctseg_resize3d_to_hwd(const void* image, int32_t image_dtype, const uint8_t*
                           int32_t Do, int32_t Ho, int32_t Wo, int32_t window, float win_lo, float win_hi, float* image_out,
                           uint8_t* masks_out, uint8_t* labels_out, int64_t* hist, void* stream);
 
+/* 3-D augmentation in that same pass: an affine resample, a permutation of the mask channels and an intensity gain / bias.  Inputs,
+ * outputs, dtypes (CTSEG_F32 / CTSEG_I16 / CTSEG_U8), layouts and the K <= 15 limit are those of ctseg_resize3d_to_hwd; each
+ * volume (D * H * W, Do * Ho * Wo) has fewer than 2^31 voxels.  matrix (12 floats, row-major 3 x 4; rows and columns ordered
+ * d, h, w) and mask_src (K ints, or NULL for the identity) are HOST arrays copied into the kernel's arguments: no device upload, no
+ * synchronisation.  Rejected: a matrix entry that is not finite (or a row that sends the output grid beyond 1e30), a mask_src that
+ * is no permutation of 0..K-1, interp or border out of range, a cval, gain or bias that is not finite.
+ * Every float operation is one float32 rounding; nothing is contracted into an FMA.
+ *   - The augmentation acts on the VIRTUAL RESIZED VOLUME V of size Do x Ho x Wo: V[r] = src[rz(r_d), rz(r_h), rz(r_w)], rz the
+ *     nearest rule above, min((int)floorf(r * ((float)in / out)), in - 1).  V is never stored.
+ *   - For output voxel o = (od, oh, ow), taken as floats, the sampling coordinate is
+ *     q_a = ((A[a][0]*od + A[a][1]*oh) + A[a][2]*ow) + A[a][3], evaluated in that order.
+ *   - Nearest (interp 0): r_a = (int)floorf(q_a + 0.5f).  border 0 (constant): any r_a outside [0, out_a) gives cval for the image
+ *     and 0 for the masks.  border 1 (edge): r_a is clamped to the volume.
+ *   - Trilinear (interp 1), image only: b_a = floorf(q_a), f_a = q_a - b_a.  The eight corners V[b + {0,1}^3] are fetched by the
+ *     same in/out rule: a corner outside gives cval, or the clamped voxel with border 1.  They are combined as
+ *     lerp(x, y, t) = x + t * (y - x), along w first, then h, then d.
+ *   - Image value: sample, then the window (the arithmetic of ctseg_resize3d_to_hwd, unchanged), then v * gain + bias; that last
+ *     step is skipped altogether when gain == 1 && bias == 0.
+ *   - Masks are always nearest: output channel k is the nearest sample of input channel mask_src[k].  labels = max_k(m_k * (k + 1))
+ *     and hist (which the caller zeroes) are taken over the OUTPUT channels, as in the resize kernel.
+ * The identity matrix reproduces ctseg_resize3d_to_hwd bit for bit with either interp (all weights are exactly 0 and
+ * x + 0 * (y - x) = x); integer flip and quarter-turn matrices reproduce the flipped / turned resize. */
+int ctseg_augment3d_to_hwd(const void* image, int32_t image_dtype, const uint8_t* masks, int32_t K, int32_t D, int32_t H, int32_t W,
+                           int32_t Do, int32_t Ho, int32_t Wo, const float* matrix /* host */, int32_t interp, int32_t border,
+                           float cval, const int32_t* mask_src /* host */, int32_t window, float win_lo, float win_hi, float gain,
+                           float bias, float* image_out, uint8_t* masks_out, uint8_t* labels_out, int64_t* hist, void* stream);
+
 /* 2-D input pipeline on the device, a whole batch in one launch: the presets of capstone/transforms/predefined.py that are
  * per-pixel and index arithmetic (windowed_degree_1, windowed_degree_2, every "test" side):
  *   window     apply_window (capstone/transforms/transforms_2d.py:97-107) per window c: lo = win_lo[c], hi = win_hi[c] (HOST
