@@ -104,11 +104,89 @@ def new_act(N, X, Y, Z, C, dt, device, ld=None, zero=True, narrow=False):
     return Act(f((N, X, Y, Z, ld), dtype=nat.torch_dtype(dt), device=device), C, 0, dt)
 
 
-def plan_act(plan, dims, C, dt=None, ld=None):
-    """a fresh activation of the plan being recorded: its device and row layout, its storage dtype unless ``dt`` says otherwise.
+# ------------------------------------------------------------------------------------------------
+# the declared role of every device buffer of a step ("Buffer roles")
+# ------------------------------------------------------------------------------------------------
+SCRATCH = "scratch"                   # fully written before it is read within one step: any content on entry is legal
+ZERO_RESTORED = "zero-on-entry"       # zero when a step starts, and the step itself leaves it zero (completion counters)
+ZERO_PAD = "zero-never-written"       # zero pad the kernels rely on and never touch
+ZERO_UNWRITTEN = "zero-where-unwritten"   # the step overwrites some elements (any content is legal there) and never touches the others,
+#                                       which it reads as the zeros of the allocation
+STATE = "state"                       # input / state / constant: set by the caller or persistent by design
+ROLES = (SCRATCH, ZERO_RESTORED, ZERO_PAD, ZERO_UNWRITTEN, STATE)
+
+
+class BufferRole:
+    """One entry of a buffer registry: ``view`` = ``base[sel]`` is the part of the allocation ``base`` that has ``role``.  An activation
+    has two entries, its channels [0, C) and its pad columns [C, ld) (``act`` = (C, ld, ld was given by the caller)); a buffer with a
+    tail of counters has one per part."""
+    __slots__ = ("name", "base", "sel", "role", "reason", "act")
+
+    def __init__(self, name, base, sel, role, reason=None, act=None):
+        assert role in ROLES and (role == SCRATCH or reason), (name, role, "every role other than scratch states its reason")
+        self.name, self.base, self.sel, self.role, self.reason, self.act = name, base, sel, role, reason, act
+
+    @property
+    def view(self):
+        return self.base if self.sel is None else self.base[self.sel]
+
+    def __repr__(self):
+        return f"<{self.name}: {self.role} {tuple(self.view.shape)} {str(self.base.dtype).replace('torch.', '')}>"
+
+
+def declare(owner, name, base, role=SCRATCH, reason=None, sel=None, act=None):
+    """enter ``base[sel]`` (None: all of it) into the registry of ``owner`` (``owner.buffers``: a list, or a dict by name where the
+    caller hands in a new tensor every step) and return ``base``.  An owner without a registry (the op tests' one-layer plans) keeps
+    no record."""
+    reg = getattr(owner, "buffers", None)
+    if reg is not None:
+        e = BufferRole(name, base, sel, role, reason, act)
+        if isinstance(reg, dict):
+            reg[(name, str(sel))] = e
+        else:
+            reg.append(e)
+    return base
+
+
+def undeclare(owner, base):
+    """take the entries of an allocation the caller drops again out of the owner's registry (a list)"""
+    reg = getattr(owner, "buffers", None)
+    if reg is not None:
+        reg[:] = [e for e in reg if e.base is not base]
+
+
+def plan_buf(owner, name, shape, dtype, role=SCRATCH, reason=None, parts=None, fill=0.0, device=None):
+    """THE allocation of a persistent device buffer of a plan, a layer object or a loss engine: zero-filled (``fill``: a constant
+    instead) and entered into the owner's registry under its role.  ``parts``: [(flat element range (lo, hi), role, reason)] for a
+    one-dimensional buffer whose ranges have different roles; they must cover it."""
+    dev = device if device is not None else owner.device
+    shape = (shape,) if isinstance(shape, int) else tuple(shape)
+    t = torch.zeros(shape, dtype=dtype, device=dev) if fill == 0.0 else torch.full(shape, fill, dtype=dtype, device=dev)
+    if parts is None:
+        return declare(owner, name, t, role, reason)
+    assert t.ndim == 1 and [lo for (lo, _), _, _ in parts] + [t.numel()] == [0] + [hi for (_, hi), _, _ in parts], (name, parts)
+    for (lo, hi), r, why in parts:
+        declare(owner, f"{name}[{lo}:{hi}]", t, r, why, sel=slice(lo, hi))
+    return t
+
+
+def declare_act(owner, name, act, role=SCRATCH, reason=None, pad_role=SCRATCH, pad_reason=None, ld_given=False):
+    """the two entries of a freshly allocated activation: channels [0, C) under ``role``, pad columns [C, ld) under ``pad_role``"""
+    C, ld = act.C, act.ld
+    assert act.c0 == 0 and C <= ld, (name, act.c0, C, ld)
+    declare(owner, name, act.t, role, reason, sel=(Ellipsis, slice(0, C)), act=(C, ld, ld_given))
+    if ld > C:
+        declare(owner, name + " pad", act.t, pad_role, pad_reason, sel=(Ellipsis, slice(C, ld)), act=(C, ld, ld_given))
+    return act
+
+
+def plan_act(plan, dims, C, dt=None, ld=None, name="activation", pad_role=SCRATCH, pad_reason=None):
+    """a fresh activation of the plan being recorded: its device and row layout, its storage dtype unless ``dt`` says otherwise;
+    entered into the plan's buffer registry as ``name`` (scratch channels, pad columns under ``pad_role``).
     ``plan`` may be a duck-typed stand-in that drives single layers (the op-level tests' one-layer plan) and knows nothing of the
-    row layout: it gets 16-byte chunked rows"""
-    return new_act(*dims, C, plan.dt if dt is None else dt, plan.device, ld=ld, narrow=getattr(plan, "narrow_rows", False))
+    row layout or the registry: it gets 16-byte chunked rows and a plain allocation"""
+    a = new_act(*dims, C, plan.dt if dt is None else dt, plan.device, ld=ld, narrow=getattr(plan, "narrow_rows", False))
+    return declare_act(plan, name, a, pad_role=pad_role, pad_reason=pad_reason, ld_given=ld is not None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -168,8 +246,11 @@ class ParamStore:
         self.n = off
         self.n_pad = rup(off, 4)
         self.zero_index = self.n_pad  # flat_p[n_pad:] stays 0.0 forever (pad source for packing)
-        self.flat_p = torch.zeros(self.n_pad + 4, dtype=torch.float32, device=device)
-        self.flat_g = torch.zeros(self.n_pad, dtype=torch.float32, device=device)
+        self.buffers = []             # BufferRole of every device buffer of the store (Plan.all_buffers)
+        self.flat_p = plan_buf(self, "store/flat parameters", self.n_pad + 4, torch.float32, STATE,
+                               "the parameters themselves; the tail [n_pad, n_pad + 4) is the zero that every pad entry of a pack index reads")
+        # (every parameter's gradient is stored, never accumulated, by the backward program: the step's output, not its state)
+        self.flat_g = plan_buf(self, "store/flat gradient", self.n_pad, torch.float32)
         self.adam_m = self.adam_v = None
         self.step = 0
         self._grad_views = None       # per-parameter views of flat_g, made once (grad_views)
@@ -221,8 +302,8 @@ class ParamStore:
 
     def ensure_adam_state(self):
         if self.adam_m is None:
-            self.adam_m = torch.zeros_like(self.flat_g)
-            self.adam_v = torch.zeros_like(self.flat_g)
+            self.adam_m = plan_buf(self, "store/adam m", self.n_pad, torch.float32, STATE, "Adam's first moment, carried across steps")
+            self.adam_v = plan_buf(self, "store/adam v", self.n_pad, torch.float32, STATE, "Adam's second moment, carried across steps")
 
     def adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0):
         """torch.optim.Adam semantics (capstone/volumetric/base_trainer.py:113-114), one launch."""
@@ -247,8 +328,11 @@ class BufferStore:
         for i, m in enumerate(self.norms):
             self.offsets[id(m)] = (off, i)
             off += 2 * m.num_features
-        self.flat = torch.zeros(max(off, 4), dtype=torch.float32, device=device)
-        self.nbt = torch.zeros(max(len(self.norms), 1), dtype=torch.int64, device=device)
+        self.buffers = []             # BufferRole of the two buffers (Plan.all_buffers)
+        self.flat = plan_buf(self, "bufs/running statistics", max(off, 4), torch.float32, STATE,
+                             "BatchNorm running mean / variance: module state that every training forward updates in place")
+        self.nbt = plan_buf(self, "bufs/num_batches_tracked", max(len(self.norms), 1), torch.int64, STATE,
+                            "BatchNorm step counters: module state, incremented by every training forward")
         self.copy_in()
 
     def _views(self, m):
@@ -432,18 +516,19 @@ class GemmLayer:
         if nat.query("ctseg_conv_split_ok", d) != 1:
             d.out2_col0 = 0
             return None
-        a, b = plan_act(self.plan, od, split_at), plan_act(self.plan, od, d.Cn - split_at)
+        a = plan_act(self.plan, od, split_at, name=f"{self.name}/{self._out_kind} [:{split_at}]")
+        b = plan_act(self.plan, od, d.Cn - split_at, name=f"{self.name}/{self._out_kind} [{split_at}:]")
         d.out, d.o_ld = a.ptr(), a.ld
         d.out2, d.o2_ld = b.ptr(), b.ld
         return SplitAct(a, b)
 
     def emit_fwd(self, x, out=None, want_stats=False, add=None, out_f32=False, split_at=None):
         plan = self.plan
-        self.x_dims = x.dims
+        self.x_dims, self._out_kind = x.dims, "output"
         od = self.out_dims(x.dims)
         own_out = out is None
         if out is None:
-            out = plan_act(plan, od, self.Cn, F32 if out_f32 else None)
+            out = plan_act(plan, od, self.Cn, F32 if out_f32 else None, name=f"{self.name}/output")
         assert out.dims == od and out.C == self.Cn, (self.name, out.dims, od)
         rowgrid, sin, sout = self._grid("fwd", x.dims, od)
         stats = None
@@ -463,11 +548,12 @@ class GemmLayer:
         if want_stats:
             tiles = nat.lib().ctseg_conv_num_tiles(d)
             assert tiles > 0
-            stats = NormStats(plan, od[0], tiles, self.Cn, od[1] * od[2] * od[3])
+            stats = NormStats(plan, od[0], tiles, self.Cn, od[1] * od[2] * od[3], name=self.name)
             d.stats, d.stats_ld, d.stats_tiles, d.stats_tile0 = stats.partials.data_ptr(), stats.ld, stats.tiles, 0
         if own_out and add is None and not out_f32:
             sp = self._try_split(d, od, split_at)
             if sp is not None:
+                undeclare(plan, out.t)       # (the single output tensor is dropped for the two dense ones)
                 out = sp
         plan.emit("ctseg_conv_igemm", d, keep=(x, out, add, stats))
         return out, stats
@@ -489,7 +575,9 @@ class GemmLayer:
             return None
         plan = self.plan
         ld = rup(y.C, 4)
-        part = torch.zeros((y.dims[0], P, 3, ld), dtype=torch.float32, device=plan.device)
+        part = plan_buf(plan, f"{self.name}/bwd stats partials of {norm.name}", (y.dims[0], P, 3, ld), torch.float32, ZERO_UNWRITTEN,
+                        "a workgroup writes the rows of the samples it worked on only (ctseg_conv_desc::bst_partials): the finalize "
+                        "pass sums every row, the others are the zeros of the allocation")
         d.bst_mean_rstd, d.bst_alpha = norm.mr.data_ptr(), plan.store.p_ptr(norm.alpha)
         d.bst_partials, d.bst_P, d.bst_ld = part.data_ptr(), P, ld
         tgt.bst = (norm, part, P, ld)
@@ -505,13 +593,15 @@ class GemmLayer:
         xd = self.x_dims
         own_out = out is None
         if out is None:
-            out = plan_act(plan, xd, self.cin)
+            out = plan_act(plan, xd, self.cin, name=f"{self.name}/input gradient")
+        self._out_kind = "input gradient"
         assert out.dims == xd and out.C == self.cin and dy.C == self.Cn
         rowgrid, sin, sout = self._grid("dgrad", xd, dy.dims)
         d = self._desc(self.dg_pack, self.dg_classes, dy, out, rowgrid, sin, sout, self.cin, self.cgd, None, add, None, False)
         if own_out and add is None:
             sp = self._try_split(d, xd, split_at)
             if sp is not None:
+                undeclare(plan, out.t)
                 out = sp
         marked = self._try_bst(d, out, bst, bst_col0)
         plan.emit("ctseg_conv_igemm", d, keep=(dy, out, add, marked.bst[1] if marked is not None else None, bst.y if marked is not None else None))
@@ -612,7 +702,7 @@ class GemmLayer:
             raise NarrowUnsupported(self.name + " (weight gradient)")
         nslabs = nat.lib().ctseg_conv_wgrad_slabs(d)     # N*splits, or one per persistent workgroup (LDS-halo kernel)
         assert nslabs > 0
-        ws = torch.zeros(nslabs * kpad_w * cn_pad, dtype=torch.float32, device=plan.device)
+        ws = plan_buf(plan, f"{self.name}/wgrad slabs", nslabs * kpad_w * cn_pad, torch.float32)
         d.ws = ws.data_ptr()
         plan.emit("ctseg_conv_wgrad", d, keep=(gathered, dyy, ws, dyn))
         if not self.transposed:
@@ -631,14 +721,21 @@ class GemmLayer:
 
 
 class NormStats:
-    def __init__(self, plan, N, tiles, C, count):
-        self.plan, self.N, self.tiles, self.C, self.count = plan, N, tiles, C, count
+    def __init__(self, plan, N, tiles, C, count, name="norm"):
+        self.plan, self.N, self.tiles, self.C, self.count, self.name = plan, N, tiles, C, count, name
         self.ld = rup(C, 256 if C > 128 else nat.lib().ctseg_conv_tile_cols(C))   # 192x256 tile for C > 128
-        self.partials = torch.zeros((N, tiles, 2, self.ld), dtype=torch.float32, device=plan.device)
-        self.scratch = torch.zeros(N * 64 * 2 * self.ld + N, dtype=torch.float64, device=plan.device)   # + N completion counters
+        self.partials = plan_buf(plan, f"{name}/stats partials", (N, tiles, 2, self.ld), torch.float32, ZERO_UNWRITTEN,
+                                 "the conv pass that takes the statistics writes the slots of the tiles and samples its workgroups worked "
+                                 "on, and the columns of the normalised channels; the finalize pass sums whole rows of every slot, so the "
+                                 "others must be the zeros of the allocation")
+        groups = N * 64 * 2 * self.ld
+        self.scratch = plan_buf(plan, f"{name}/stats group sums", groups + N, torch.float64, parts=[
+            ((0, groups), SCRATCH, None),
+            ((groups, groups + N), ZERO_RESTORED, "completion counters of ctseg_instnorm_finalize: the block that finishes last for a "
+                                                  "sample combines the groups and resets the sample's counter")])
 
     def emit_finalize(self, col0, C, eps=1e-5):
-        mr = torch.zeros((self.N, C, 2), dtype=torch.float32, device=self.plan.device)
+        mr = plan_buf(self.plan, f"{self.name}/mean rstd [{col0}:{col0 + C}]", (self.N, C, 2), torch.float32)
         self.plan.emit("ctseg_instnorm_finalize", self.partials.data_ptr(), self.N, self.tiles, self.ld, col0, C,
                        float(self.count), float(eps), self.scratch.data_ptr(), mr.data_ptr(), keep=(self, mr))
         return mr
@@ -725,16 +822,19 @@ class Packer:
 
     def finalize(self):
         dev = self.plan.device
-        self.buf = torch.zeros(max(self.total, 8), dtype=nat.torch_dtype(self.plan.dt), device=dev)
-        self.bias_buf = torch.zeros(max(self.bias_total, 4), dtype=torch.float32, device=dev)
+        self.buf = plan_buf(self.plan, "packer/packed weights", max(self.total, 8), nat.torch_dtype(self.plan.dt), STATE,
+                            "the MFMA operands, rebuilt from the parameters after an update; the structured re-layout leaves the padding "
+                            "rows of a block to the zeros of the allocation")
+        self.bias_buf = plan_buf(self.plan, "packer/biases", max(self.bias_total, 4), torch.float32, STATE,
+                                 "the biases in pass order, rebuilt from the parameters after an update")
         idx = np.full(self.total, self.plan.store.zero_index, dtype=np.int32)
         for off, blk in self.blocks:
             idx[off:off + len(blk)] = blk
-        self.idx = torch.from_numpy(idx).to(dev)
+        self.idx = declare(self.plan, "packer/weight index", torch.from_numpy(idx).to(dev), STATE, "constant index table of ctseg_gather_cast")
         bidx = np.full(max(self.bias_total, 4), self.plan.store.zero_index, dtype=np.int32)
         for off, blk in self.bias_blocks:
             bidx[off:off + len(blk)] = blk
-        self.bias_idx = torch.from_numpy(bidx).to(dev)
+        self.bias_idx = declare(self.plan, "packer/bias index", torch.from_numpy(bidx).to(dev), STATE, "constant index table of ctseg_gather_cast")
         self.n_idx, self.n_bidx = self.total, max(self.bias_total, 4)
         self.dirty = True
         # structured re-layout (ctseg_pack_weights) where every block's source region fits its LDS staging buffer; the index
@@ -754,14 +854,15 @@ class Packer:
                     P.o, P.n_lo, P.n_hi, P.g_lo, P.g_hi, P.SN, P.SG = o, n_lo, n_hi, g_lo, min(g_hi, d["gs"]), SN, SG
                 rows += [(b, n) for n in range(d["rows"])]
             raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone()
-            self.pack_blocks = raw.to(dev)
+            self.pack_blocks = declare(self.plan, "packer/pack blocks", raw.to(dev), STATE, "constant block descriptions of ctseg_pack_weights")
             # rows of the blocks of the FIRST forward pass first (Packer.first = its pack): refresh(part="first") rebuilds them alone,
             # the next step's first convolution waits for nothing else
             lo, hi = self.first
             head = [(b, n) for (b, n) in rows if lo <= self.descs[b]["dst_off"] < hi]
             rest = [(b, n) for (b, n) in rows if not (lo <= self.descs[b]["dst_off"] < hi)]
             self.n_first_rows = len(head)
-            self.pack_rows = torch.tensor(head + rest, dtype=torch.int32).reshape(-1).to(dev)
+            self.pack_rows = declare(self.plan, "packer/pack rows", torch.tensor(head + rest, dtype=torch.int32).reshape(-1).to(dev), STATE,
+                                     "constant (block, row) table of ctseg_pack_weights")
             self.n_pack_blocks, self.n_pack_rows = len(self.descs), len(rows)
 
     def can_split(self):

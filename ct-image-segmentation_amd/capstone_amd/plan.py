@@ -15,7 +15,8 @@ import torch.nn as nn
 
 from . import _native as nat
 from ._native import BF16, F32
-from .engine import Act, BufferStore, GemmLayer, NarrowUnsupported, Packer, ParamStore, plan_act, rup
+from .engine import (SCRATCH, STATE, ZERO_RESTORED, ZERO_UNWRITTEN, Act, BufferStore, GemmLayer, NarrowUnsupported, Packer, ParamStore, declare,
+                     declare_act, plan_act, plan_buf, rup)
 
 
 def _is_seq(m):
@@ -47,8 +48,8 @@ class _NormBase:
     passes may apply / take them on load — in_norm, bst, dyn) and ``needs_stats`` (the producing conv pass writes (sum, sumsq)
     partials)."""
 
-    def __init__(self, plan, alpha, params):
-        self.plan, self.alpha, self.params = plan, alpha, params
+    def __init__(self, plan, alpha, params, name="norm"):
+        self.plan, self.alpha, self.params, self.name = plan, alpha, params, name      # name: the layer's, for the buffer registry
         self.y = None         # the raw conv output this node normalises (set by the forward)
         self.mr = None        # its (mean, rstd) table
 
@@ -57,11 +58,11 @@ class _NormBase:
         which the pass that wrote the gradient left (Act.bst) — and the tensor that receives dL/dy"""
         plan, y = self.plan, self.y
         if dy_out is None and apply:
-            dy_out = plan_act(plan, y.dims, y.C)
+            dy_out = plan_act(plan, y.dims, y.C, name=f"{self.name}/gradient of the conv output")
         if mark is not None:
             return (*mark[1:], dy_out)
         P, ld = _bwd_row_ranges(y.S, y.dims[0], plan.dt), rup(y.C, 4)
-        return torch.zeros((y.dims[0], P, 3, ld), dtype=torch.float32, device=plan.device), P, ld, dy_out
+        return plan_buf(plan, f"{self.name}/bwd partials", (y.dims[0], P, 3, ld), torch.float32), P, ld, dy_out
 
 
 class _NormAct(_NormBase):
@@ -69,8 +70,8 @@ class _NormAct(_NormBase):
     fusable = True
     needs_stats = True
 
-    def __init__(self, plan, alpha):
-        super().__init__(plan, alpha, [alpha])
+    def __init__(self, plan, alpha, name="norm"):
+        super().__init__(plan, alpha, [alpha], name)
         self._applied = None  # the applied activation of a deferred norm, once a consumer needed it (materialise)
 
     def defer(self, y, stats):
@@ -89,7 +90,7 @@ class _NormAct(_NormBase):
     def _apply(self, y, res, out):
         plan = self.plan
         if out is None:
-            out = plan_act(plan, y.dims, y.C)
+            out = plan_act(plan, y.dims, y.C, name=f"{self.name}/activation")
         plan.emit("ctseg_instnorm_prelu_fwd", plan.dt, y.ptr(), y.ld, self.mr.data_ptr(), plan.store.p_ptr(self.alpha),
                   *_ptr_ld(res), out.ptr(), out.ld, y.dims[0], y.S, y.C, keep=(y, res, out))
         return out
@@ -106,7 +107,7 @@ class _NormAct(_NormBase):
         on load (ctseg_wgrad_desc::dyn_*); returns the finalised sums instead."""
         plan, y = self.plan, self.y
         N, S, C = y.dims[0], y.S, y.C
-        sums = torch.zeros((N, C, 2), dtype=torch.float32, device=plan.device)
+        sums = plan_buf(plan, f"{self.name}/bwd sums", (N, C, 2), torch.float32)
         a_ptr = plan.store.p_ptr(self.alpha)
         # the pass that wrote g took the three sums in its epilogue (ctseg_conv_desc::bst_*): no reduce pass, no second read of g
         fused = g.bst is not None and g.bst[0] is self
@@ -118,7 +119,10 @@ class _NormAct(_NormBase):
         if not fused:
             plan.emit("ctseg_instnorm_prelu_bwd_reduce", plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), a_ptr,
                       part.data_ptr(), P, ld, N, S, C, keep=(g, part))
-        da_part = torch.zeros(N * C + 1, dtype=torch.float64, device=plan.device)
+        da_part = plan_buf(plan, f"{self.name}/slope terms", N * C + 1, torch.float64, parts=[
+            ((0, N * C), SCRATCH, None),
+            ((N * C, N * C + 1), ZERO_RESTORED, "completion counter of ctseg_instnorm_prelu_bwd_finalize: the block that finishes last sums "
+                                                "the slope terms and resets it (unused where the sum rides on the apply pass)")])
         # the slope-gradient sum over da_part rides on the apply pass below (one of its workgroups; no launch, no atomics)
         plan.emit("ctseg_instnorm_prelu_bwd_finalize", part.data_ptr(), N, P, ld, C, float(S), da_part.data_ptr(), sums.data_ptr(),
                   None, keep=(sums, da_part))
@@ -132,7 +136,7 @@ class _NormAct(_NormBase):
             plan.emit("ctseg_instnorm_prelu_bwd_apply", *args, *slope, keep=(dy_out, g_copy))
         else:
             p_cap = N * 512
-            cs_part = torch.zeros((p_cap, rup(C, nat.epc(plan.dt))), dtype=torch.float32, device=plan.device)
+            cs_part = plan_buf(plan, f"{self.name}/colsum partials", (p_cap, rup(C, nat.epc(plan.dt))), torch.float32)
             plan.emit("ctseg_instnorm_prelu_bwd_apply_colsum", *args, cs_part.data_ptr(), p_cap, colsum_out, *slope,
                       keep=(dy_out, g_copy, cs_part))
         return dy_out
@@ -160,9 +164,9 @@ class _BatchNormAct(_NormBase):
     load in the weight gradient): they assume per-sample statistics and no affine."""
     fusable = False
 
-    def __init__(self, plan, norm, alpha):
+    def __init__(self, plan, norm, alpha, name="norm"):
         check_batch_norm(norm)
-        super().__init__(plan, alpha, [alpha, norm.weight, norm.bias])
+        super().__init__(plan, alpha, [alpha, norm.weight, norm.bias], name)
         self.norm, self.gamma, self.beta = norm, norm.weight, norm.bias
         self.eps, self.momentum = float(norm.eps), float(norm.momentum)
         self.train = plan.bn_train
@@ -172,8 +176,8 @@ class _BatchNormAct(_NormBase):
         plan, st = self.plan, self.plan.store
         self.y = y
         N, S, C = y.dims[0], y.S, y.C
-        self.mr = torch.zeros((C, 2), dtype=torch.float32, device=plan.device)
-        ss = torch.zeros((C, 2), dtype=torch.float32, device=plan.device)
+        self.mr = plan_buf(plan, f"{self.name}/batch mean rstd", (C, 2), torch.float32)
+        ss = plan_buf(plan, f"{self.name}/scale shift", (C, 2), torch.float32)
         rm, rv, nbt = plan.engine.bufs.ptrs(self.norm)
         g_p, b_p = st.p_ptr(self.gamma), st.p_ptr(self.beta)
         if self.train:
@@ -183,7 +187,7 @@ class _BatchNormAct(_NormBase):
         else:
             plan.emit("ctseg_batchnorm_eval_table", rm, rv, g_p, b_p, C, self.eps, ss.data_ptr(), keep=(ss,))
         if out is None:
-            out = plan_act(plan, y.dims, C)
+            out = plan_act(plan, y.dims, C, name=f"{self.name}/activation")
         plan.emit("ctseg_scale_shift_prelu_fwd", plan.dt, y.ptr(), y.ld, ss.data_ptr(), st.p_ptr(self.alpha),
                   *_ptr_ld(res), out.ptr(), out.ld, N, S, C, keep=(y, res, out))
         return out
@@ -197,8 +201,8 @@ class _BatchNormAct(_NormBase):
         g_p, b_p, a_p = st.p_ptr(self.gamma), st.p_ptr(self.beta), st.p_ptr(self.alpha)
         plan.emit("ctseg_batchnorm_prelu_bwd_reduce", plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), g_p, b_p, a_p,
                   part.data_ptr(), P, ld, N, S, C, keep=(g, part))
-        sums = torch.zeros((C, 2), dtype=torch.float32, device=plan.device)
-        da_part = torch.zeros(C, dtype=torch.float64, device=plan.device)
+        sums = plan_buf(plan, f"{self.name}/bwd sums", (C, 2), torch.float32)
+        da_part = plan_buf(plan, f"{self.name}/slope terms", C, torch.float64)
         plan.emit("ctseg_batchnorm_prelu_bwd_finalize", part.data_ptr(), N, P, ld, C, float(N * S), sums.data_ptr(),
                   st.g_ptr(self.gamma), st.g_ptr(self.beta), da_part.data_ptr(), keep=(sums, da_part))
         plan.emit("ctseg_batchnorm_prelu_bwd_apply", plan.dt, g.ptr(), g.ld, y.ptr(), y.ld, self.mr.data_ptr(), g_p, b_p, a_p,
@@ -207,13 +211,13 @@ class _BatchNormAct(_NormBase):
         return dy_out
 
 
-def _norm_act(plan, mod):
-    """the norm + PReLU node of a monai Convolution block (None: conv_only)"""
+def _norm_act(plan, mod, name):
+    """the norm + PReLU node of a monai Convolution block (None: conv_only); ``name``: the block's, for the buffer registry"""
     if mod.conv_only:
         return None
     if isinstance(mod.norm, nn.modules.batchnorm._BatchNorm):
-        return _BatchNormAct(plan, mod.norm, mod.act.weight)
-    return _NormAct(plan, mod.act.weight)
+        return _BatchNormAct(plan, mod.norm, mod.act.weight, name + ".norm")
+    return _NormAct(plan, mod.act.weight, name + ".norm")
 
 
 class _ConvBlock:
@@ -225,7 +229,7 @@ class _ConvBlock:
         self.gemm = GemmLayer(plan, name, mod.is_transposed, mod.kernel_size, mod.strides, mod.cin, [_parts(mod.conv)], cg,
                               need_dgrad)
         self.first_gemm = self.gemm       # the GEMM that reads the node's input (as _ResUnit's)
-        self.na = _norm_act(plan, mod)
+        self.na = _norm_act(plan, mod, name)
         self.params = [mod.conv.weight, mod.conv.bias] + ([] if mod.conv_only else self.na.params)
 
     def emit_fwd(self, x, out=None, out_f32=False, defer_norm=False):
@@ -259,7 +263,8 @@ class _ConvBlock:
             gm = self.gemm
             narrow = (self.na.fusable and self.plan.dt == BF16 and gm.transposed and gm.s == 2 and gm.cin == 64 and self.x.ld == 64 and
                       gm.cgd == 16)
-            dy_wide = plan_act(self.plan, y.dims, y.C, ld=None if narrow else rup(y.C, nat.epc(self.plan.dt)))
+            dy_wide = plan_act(self.plan, y.dims, y.C, ld=None if narrow else rup(y.C, nat.epc(self.plan.dt)),
+                               name=f"{self.gemm.name}/gradient of the conv output")
             dy = self.na.emit_bwd(g, dy_out=dy_wide, colsum_out=self.plan.store.g_ptr(bias) if fuse_bias else None)
         self.gemm.emit_wgrad(self.x, dy, bias_done=fuse_bias)
         self.plan.grads_ready(self.params)
@@ -292,7 +297,8 @@ class _ResUnit:
         for i, u in enumerate(units[1:], 1):
             self.gemms.append(GemmLayer(plan, f"{name}.unit{i}", False, k, 1, mod.cout, [_parts(u.conv)], rup(mod.cout, e)))
         self.first_gemm = self.gemms[0]
-        self.nas = [_norm_act(plan, u) for u in units]
+        self.nas = [_norm_act(plan, u, f"{name}.unit{i}") for i, u in enumerate(units)]
+        self.name = name
         self.x = self.inputs = self.ys = None     # the node's input, every unit's input and raw conv output (set by the forward)
 
     def emit_fwd(self, x, out=None, out_f32=False):
@@ -336,7 +342,7 @@ class _ResUnit:
         dyn = (self.fused is not None and not need_dx and n >= 2 and self.nas[0] is not None and self.nas[0].fusable and
                self.fused.wgrad_dyn_ok(self.x, g, self.ys[0]))
         if self.fused is not None and not dyn:
-            dfused = plan_act(plan, self.ys[0].dims, 2 * C)   # [ d_res | d_y0 ]
+            dfused = plan_act(plan, self.ys[0].dims, 2 * C, name=f"{self.name}/gradient [residual | unit0]")   # [ d_res | d_y0 ]
         for i in range(n - 1, -1, -1):
             na, gm = self.nas[i], self.gemms[i]
             last = i == n - 1
@@ -387,7 +393,7 @@ class _ResUnit:
             # dx = g + dgrad(dy) into a fresh tensor, then one elementwise pass adds the accumulated term
             tmp = g0.emit_dgrad(dy, add=g)
             if out is None:
-                out = plan_act(plan, tmp.dims, tmp.C)
+                out = plan_act(plan, tmp.dims, tmp.C, name=f"{self.name}/input gradient + skip")
             plan.emit("ctseg_instnorm_prelu_fwd", plan.dt, tmp.ptr(), tmp.ld, None, None, accumulate.ptr(), accumulate.ld, out.ptr(),
                       out.ld, tmp.dims[0], tmp.S, tmp.C, keep=(tmp, accumulate, out))       # mean_rstd = NULL: out = tmp + accumulate
             return out
@@ -407,7 +413,7 @@ class _Level:
     """Sequential(down, SkipConnection(sub), up)"""
 
     def __init__(self, plan, seq, name, cg, is_top):
-        self.plan, self.is_top = plan, is_top
+        self.plan, self.is_top, self.name = plan, is_top, name
         down, skip, up = seq[0], seq[1], seq[2]
         e = nat.epc(plan.dt)
         # construction order = MONAI's (sub, down, up); gradient-readiness order is up, sub, down
@@ -434,7 +440,7 @@ class _Level:
 
     def emit_fwd(self, x, out=None, out_f32=False):
         plan = self.plan
-        self.cat = plan_act(plan, self.down.first_gemm.out_dims(x.dims), self.c1 + self.c2)
+        self.cat = plan_act(plan, self.down.first_gemm.out_dims(x.dims), self.c1 + self.c2, name=f"{self.name}/skip concat")
         xd = self.down.emit_fwd(x, out=self.cat.slice(0, self.c1))
         self.sub.emit_fwd(xd, out=self.cat.slice(self.c1, self.c2))
         if self.up1 is None:
@@ -488,6 +494,7 @@ class Plan:
         self.fwd, self.bwd = [], []    # the recorded programs: (name, cfunc, args) per op
         self._cur = None               # the program being recorded (None once recording is over)
         self._keep = []                # everything the recorded pointers point into
+        self.buffers = []              # engine.BufferRole of every device buffer this plan allocated (all_buffers adds the shared ones)
         self.ready_marks = []          # (program index in bwd, flat offsets of the gradients final there) for all-reduce overlap
         self.norm_bwd = []             # (sums, statistics came from the producing pass) of every InstanceNorm backward, for the tests
         # slab reduces collected for the next batched launch (_batch_reduce), the gradients that become final with it, and how many
@@ -510,12 +517,16 @@ class Plan:
         self.packer.first = (first["base"], first["base"] + first["size"])
         self.packer.finalize()
         # ---- record programs ----
-        self.x = Act(torch.zeros((N, X, Y, Z, cin), dtype=nat.torch_dtype(self.dt), device=self.device), cin, 0, self.dt)
+        self.x = declare_act(self, "plan/input", Act(torch.zeros((N, X, Y, Z, cin), dtype=nat.torch_dtype(self.dt), device=self.device), cin, 0, self.dt),
+                             STATE, "the step's input image: load_input, or the sliding-window gather, writes it", ld_given=True)
         self._cur = self.fwd
         self.logits = self.root.emit_fwd(self.x, out_f32=True)
         assert self.logits.t.dtype == torch.float32
         if not inference:
-            self.dlogits = plan_act(self, self.logits.dims, net.out_channels)
+            self.dlogits = plan_act(self, self.logits.dims, net.out_channels, name="plan/gradient of the logits", pad_role=ZERO_UNWRITTEN,
+                                    pad_reason="the loss passes store zeros in the pad columns, but the fused head (ctseg_conv_logits_ce) stores "
+                                    "columns 0..11 only: 12..15 of a 16-wide row keep the zeros of the allocation, and the head's input-gradient "
+                                    "and weight-gradient passes gather all 16 against zero-packed weights (0 x NaN is not 0)")
             self._cur = self.bwd
             self.dx = self.root.emit_bwd(self.dlogits, need_dx=self.need_input_grad)
             self._flush_reduces()
@@ -531,7 +542,7 @@ class Plan:
     def emit_colsum(self, x, out_ptr):
         rows = x.dims[0] * x.S
         P = max(1, min(2048, math.ceil(rows / 2048)))
-        part = torch.zeros((P, rup(x.C, 8)), dtype=torch.float32, device=self.device)
+        part = plan_buf(self, "colsum partials", (P, rup(x.C, 8)), torch.float32)
         self.emit("ctseg_colsum", self.dt, x.ptr(), x.ld, rows, x.C, part.data_ptr(), P, out_ptr, keep=(x, part))
 
     # ---- slab reduces of the weight gradients, batched ---------------------------------------------------------------------------
@@ -581,7 +592,8 @@ class Plan:
             J.lanes = 8 if nslabs >= 64 else 32
             J.block0 = b0
             b0 += -(-((T * AS + 1) * ((nb + 3) // 4)) // J.lanes)
-        table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(self.device)
+        table = declare(self, "plan/reduce job table", torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).clone().to(self.device),
+                        STATE, "constant job descriptions (pointers) of ctseg_conv_wgrad_reduce_batch")
         ready, self._pending_reduce, self._pending_ready = self._pending_ready, [], []
         self.emit("ctseg_conv_wgrad_reduce_batch", table.data_ptr(), len(jobs), b0, keep=(table,))
         if ready:
@@ -597,6 +609,18 @@ class Plan:
             self._flush_reduces(only_if_chunk=True)
         else:
             self.ready_marks.append((len(self.bwd), offs))
+
+    def all_buffers(self):
+        """the registry of a whole step on this plan: the plan's own buffers, the shared parameter / running-statistics stores' and
+        those of the loss engines attached to the plan"""
+        out = list(self.buffers) + list(self.store.buffers)
+        if getattr(self.engine, "bufs", None) is not None:
+            out += self.engine.bufs.buffers
+        for attr in ("_ctseg_loss", "_ctseg_loss_pair"):
+            le = getattr(self, attr, None)
+            if le is not None:
+                out += list(le.buffers.values())
+        return out
 
     # ---- running ----
     @staticmethod

@@ -14,6 +14,7 @@ import torch
 
 from . import _native as nat
 from ._native import BF16, F32
+from .engine import SCRATCH, STATE, declare, plan_buf
 
 N_CLASSES = 10
 CLASS_WEIGHT = (1e-10, 0.007, 0.3296, 0.0046, 0.2619, 0.3035, 0.0068, 0.0065, 0.0374, 0.0426)  # models/losses.py:10-21
@@ -74,14 +75,19 @@ class SegLossEngine:
         self.device, self.B, self.S, self.C = device, B, S, C
         self.P = max(1, min(2048, math.ceil(S / 2048)))
         self.R = 2 + 3 * C
-        f64 = dict(dtype=torch.float64, device=device)
-        self.part = torch.zeros((B, self.P, self.R), **f64)
-        self.red = torch.zeros((B, self.R), **f64)
-        self.red_w = torch.zeros((B, self.R), **f64)
-        self.cnt = torch.zeros((B, 3, C), dtype=torch.int64, device=device)
-        self.coef = torch.zeros((B, 1 + 3 * C), dtype=torch.float32, device=device)
-        self.cw = torch.tensor(CLASS_WEIGHT[:C], dtype=torch.float32, device=device)
-        self.cw_eff = torch.ones(C, dtype=torch.float32, device=device)
+        # BufferRole of every device buffer of the engine, by name: the tensors the caller hands in every step (labels, histogram,
+        # maps) replace their entry (Plan.all_buffers reaches this registry through the plan the engine is cached on)
+        self.buffers = {}
+        self.part = plan_buf(self, "loss/part", (B, self.P, self.R), torch.float64)
+        self.red = plan_buf(self, "loss/red", (B, self.R), torch.float64)
+        self.red_w = plan_buf(self, "loss/red_w", (B, self.R), torch.float64)
+        # (cnt and coef are accumulated into / partly written by the kernels: every pass that uses them re-zeroes them first, so
+        # within a step they are written before they are read)
+        self.cnt = plan_buf(self, "loss/cnt", (B, 3, C), torch.int64)
+        self.coef = plan_buf(self, "loss/coef", (B, 1 + 3 * C), torch.float32)
+        self.cw = declare(self, "loss/class weights", torch.tensor(CLASS_WEIGHT[:C], dtype=torch.float32, device=device), STATE,
+                          "constant: the reference's class-weight table")
+        self.cw_eff = plan_buf(self, "loss/cw_eff", C, torch.float32, fill=1.0)
         self.labels = self.hist = None
         self._ce_ready = None        # the `weighted` that prepare_fused_ce last set the tables up for, until a pass uses them
         self._part_head = None       # head_ce's partial records (B, slots, R)
@@ -102,12 +108,12 @@ class SegLossEngine:
         if maps.ndim < 3 or tuple(maps.shape[:2]) != (self.B, self.C - 1) or maps[0, 0].numel() != self.S:
             raise ValueError(f"Boundary loss: distance maps of shape {tuple(maps.shape)}, expected ({self.B}, {self.C - 1}, ...) with "
                              f"{self.S} voxels per plane")
-        self.maps = maps.detach().to(torch.float32).reshape(self.B, self.C - 1, self.S).contiguous()
+        self.maps = declare(self, "loss/distance maps", maps.detach().to(torch.float32).reshape(self.B, self.C - 1, self.S).contiguous(),
+                            STATE, "input: the batch's distance maps, given by the caller")
         if getattr(self, "b_red", None) is None:
-            f64 = dict(dtype=torch.float64, device=self.device)
-            self.b_part = torch.zeros((self.B, self.P, self.NS, self.C - 1), **f64)
-            self.b_red = torch.zeros((self.B, self.NS, self.C - 1), **f64)
-            self.bw = torch.zeros((self.B, self.NS, self.C - 1), dtype=torch.float32, device=self.device)
+            self.b_part = plan_buf(self, "loss/b_part", (self.B, self.P, self.NS, self.C - 1), torch.float64)
+            self.b_red = plan_buf(self, "loss/b_red", (self.B, self.NS, self.C - 1), torch.float64)
+            self.bw = plan_buf(self, "loss/bw", (self.B, self.NS, self.C - 1), torch.float32)
 
     def boundary_stats(self, logits_ptr, ld):
         """b_red (B, NS, C-1) = sum over voxels of softmax(x)[c+1] * D_s[c]"""
@@ -122,12 +128,14 @@ class SegLossEngine:
 
     # ---- targets ----
     def set_labels(self, labels_u8, hist):
-        self.labels, self.hist = labels_u8, hist
+        self.labels = declare(self, "loss/labels", labels_u8, STATE, "input: the batch's label map, given by the caller")
+        self.hist = declare(self, "loss/hist", hist, STATE, "input: the batch's label histogram, given by the caller")
 
     def set_labels_from_i64(self, target):
         t = target.reshape(self.B, self.S)
-        self.labels = t.to(torch.uint8).contiguous()
-        self.hist = torch.zeros((self.B, self.C), dtype=torch.int64, device=self.device)
+        self.labels = declare(self, "loss/labels", t.to(torch.uint8).contiguous(), STATE, "input: the label map of the caller's target")
+        self.hist = declare(self, "loss/hist", torch.zeros((self.B, self.C), dtype=torch.int64, device=self.device), STATE,
+                            "input: the label histogram of the caller's target")
         self.hist.scatter_add_(1, t.long(), torch.ones_like(t, dtype=torch.int64))
 
     def set_target(self, target):
@@ -184,7 +192,7 @@ class SegLossEngine:
         self._take_ce_tables(weighted)
         part = self._part_head
         if part is None or part.shape[1] != slots:
-            part = self._part_head = torch.zeros((self.B, slots, self.R), dtype=torch.float64, device=self.device)
+            part = self._part_head = plan_buf(self, "loss/head partial records", (self.B, slots, self.R), torch.float64)
         nat.call("ctseg_conv_logits_ce", desc, self.labels.data_ptr(), self.C, nat.ptr(self.cw if weighted else None),
                  self.coef.data_ptr(), self.coef.shape[1], dl_ptr, g_ld, part.data_ptr(), slots, self.R, self.cnt.data_ptr())
         nat.call("ctseg_reduce_partials_f64", part.data_ptr(), self.B, slots, self.R, (self.red_w if weighted else self.red).data_ptr())
@@ -195,13 +203,14 @@ class SegLossEngine:
         out = torch.empty(1 + self.C, dtype=torch.float32, device=self.device)
         nat.call("ctseg_loss_dice_summary", (self.red_w if weighted else self.red).data_ptr(), self.B, self.R, self.cnt.data_ptr(),
                  self.C, out.data_ptr())
-        self.last_summary = out
+        self.last_summary = declare(self, "loss/summary", out, SCRATCH)
         return out[0], out[1], out[2:]
 
     def predictions(self, logits_ptr, ld):
         pred = torch.empty((self.B, self.S), dtype=torch.uint8, device=self.device)
         if self.labels is None:
-            self.labels = torch.zeros((self.B, self.S), dtype=torch.uint8, device=self.device)
+            self.labels = declare(self, "loss/labels", torch.zeros((self.B, self.S), dtype=torch.uint8, device=self.device), STATE,
+                                  "input: a stand-in label map for a pass that only predicts")
         self._pass(logits_ptr, ld, None, False, False, pred=pred)
         return pred
 
@@ -360,14 +369,14 @@ class SegLossPairEngine(SegLossEngine):
         super().__init__(device, B, S, C)
         if 2 * self.R > 64:
             raise nat.NativeError(f"pair loss pass: {C} classes need reduced records of {2 * self.R} > 64 doubles")
-        f64 = dict(dtype=torch.float64, device=device)
-        self.part2 = torch.zeros((B, self.P, 2, self.R), **f64)
-        self.red2 = torch.zeros((B, 2, self.R), **f64)
-        self.red2_w = torch.zeros((B, 2, self.R), **f64)
-        self.cnt2 = torch.zeros((B, 2, 3, C), dtype=torch.int64, device=device)
-        self.coef2 = torch.zeros((B, 2, 1 + 3 * C), dtype=torch.float32, device=device)
-        self.cw2 = torch.ones((2, C), dtype=torch.float32, device=device)
-        self.cw2_stats = self.cw[None, :].repeat(2, 1)
+        self.part2 = plan_buf(self, "loss/part2", (B, self.P, 2, self.R), torch.float64)
+        self.red2 = plan_buf(self, "loss/red2", (B, 2, self.R), torch.float64)
+        self.red2_w = plan_buf(self, "loss/red2_w", (B, 2, self.R), torch.float64)
+        self.cnt2 = plan_buf(self, "loss/cnt2", (B, 2, 3, C), torch.int64)          # (re-zeroed by every pass that uses it, as cnt)
+        self.coef2 = plan_buf(self, "loss/coef2", (B, 2, 1 + 3 * C), torch.float32)
+        self.cw2 = plan_buf(self, "loss/cw2", (2, C), torch.float32, fill=1.0)
+        self.cw2_stats = declare(self, "loss/class weights of both sides", self.cw[None, :].repeat(2, 1), STATE,
+                                 "constant: the class-weight table, one row per side")
         self.perm = self.hist2 = None
 
     NS = 2                           # Boundary loss: side 1 of sample b reads the maps of sample perm[b]
@@ -377,9 +386,10 @@ class SegLossPairEngine(SegLossEngine):
 
     def set_pair(self, labels_u8, hist, index):
         """index: (B,) integer device tensor; it never visits the host"""
-        self.labels = labels_u8
-        self.perm = index.to(torch.int32).contiguous()
-        self.hist2 = (hist, hist[index.long()])
+        self.labels = declare(self, "loss/labels", labels_u8, STATE, "input: the batch's label map, given by the caller")
+        self.perm = declare(self, "loss/perm", index.to(torch.int32).contiguous(), STATE, "input: the mixup partner of every sample")
+        self.hist2 = (declare(self, "loss/hist", hist, STATE, "input: the batch's label histogram, given by the caller"),
+                      declare(self, "loss/hist of the partners", hist[index.long()], STATE, "input: the partners' label histograms"))
 
     @contextlib.contextmanager
     def side(self, s):

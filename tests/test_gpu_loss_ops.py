@@ -16,7 +16,9 @@ under CTSEG_MAX_WG = 8 the chunks of workgroups 5, 6 and 7 are empty (test_fused
 of a 16-wide d loss / d logits row: the pass stores columns 0 to 11 only; the plan allocates the buffer zeroed (plan.py:
 plan_act -> engine.new_act, zero=True) and every writer either stores zeros there (ctseg_seg_loss) or leaves them (this pass, the
 copy of an upstream gradient into columns [0, C)), so the state the plan guarantees is 0: the test prepares that state and asserts
-it after the launch.
+it after the launch.  (The same guarantee for the assembled step, where this row is the next pass's gathered operand:
+tests/test_plan_buffers.py runs the whole step over a poisoned workspace and asserts every range the buffer registry declares
+zero, capstone_amd.engine.ZERO_PAD / ZERO_UNWRITTEN, after it; DESIGN.md "Buffer roles" lists them.)
 
 Every test prints its worst error / bound before it asserts.  Measured on an MI355X, worst of each group:
   ctseg_seg_loss record sums 0.15, ctseg_seg_loss_pair (13 classes) 0.005; gradients fp32 0.08 (cross-entropy only 0.07), bf16 0.99
