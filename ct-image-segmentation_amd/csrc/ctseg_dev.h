@@ -269,6 +269,15 @@ void set_error(const char* fmt, ...);
       return -2;                                                         \
     }                                                                    \
   } while (0)
+// the same for an entry point whose name is a run-time string: "<who> (<pass>): <error>"
+#define CTSEG_LAUNCH_CHECK_PASS(who, pass)                                        \
+  do {                                                                            \
+    hipError_t e_ = hipGetLastError();                                            \
+    if (e_ != hipSuccess) {                                                       \
+      ctseg::set_error("%s (%s): %s", who, pass, hipGetErrorString(e_));          \
+      return -2;                                                                  \
+    }                                                                             \
+  } while (0)
 
 // ABI 2: a descriptor names the size of the struct its caller was compiled against; anything else is a caller built against
 // another header (round 2 grew both structs under version 1: the library would read past the end of the old, shorter struct)

@@ -79,8 +79,8 @@ __global__ __launch_bounds__(256) void distmap2d_rows_kernel(const uint32_t* __r
   const bool has_fg = s_any_fg != 0, has_bg = s_any_bg != 0;   // of the whole plane, see the head of this file
   for (int i = tid; i < n; i += blockDim.x) {
     const int r = i / W, x = i - r * W;
-    const int dfg = has_fg ? row_min(s_fg[r], x, W) : DM_INF;
-    const int dbg = has_bg ? row_min(s_bg[r], x, W) : DM_INF;
+    const int dfg = has_fg ? envelope_min(CellsU16{}, s_fg[r], x, W, 1) : DM_INF;
+    const int dbg = has_bg ? envelope_min(CellsU16{}, s_bg[r], x, W, 1) : DM_INF;
     if (d2_fg) d2_fg[base + i] = has_fg ? dfg : -1;
     if (d2_bg) d2_bg[base + i] = has_bg ? dbg : -1;
     float val = 0.f;

@@ -15,8 +15,10 @@
 // none, so after the last pass it means that the volume has no voxel of the other class: -1 in that d2 output and a map of 0,
 // decided per voxel, with no flag shared between lanes.
 // The value pass is that of distmap2d.hip: REFERENCE gives table[k] of the byte the reference stores, SIGNED the float map.
-// ctseg_distmap3d_weighted (further down) is the same transform under per-volume voxel sizes: squared physical distances in float32,
-// the class bit in the float's sign bit, +inf for "none", and no value pass.
+// The line and slab kernels are written once over a metric, and the search once over its cells (envelope_min, distmap_common.h).
+// ctseg_distmap3d_batch runs them with MetricSq, as described above.  ctseg_distmap3d_weighted runs them with MetricW, the same
+// transform under per-volume voxel sizes: squared physical distances in float32, the class bit in the float's sign bit, +inf for
+// "none", and no value pass.
 #include "distmap_common.h"
 
 namespace ctseg {
@@ -57,52 +59,23 @@ __global__ __launch_bounds__(256) void distmap3d_sweep_kernel(const uint8_t* __r
   }
 }
 
-// Workgroup b: the Z lines [b * L, b * L + L) of all volumes, L * Z <= DM3_LINE_WORDS voxels that are contiguous in memory.
-__global__ __launch_bounds__(256) void distmap3d_lines_kernel(const uint16_t* __restrict__ g, int64_t voxels, int Z, int L,
-                                                              uint32_t* __restrict__ f) {
-  __shared__ uint32_t s[DM3_LINE_WORDS];
-  const int64_t e0 = (int64_t)blockIdx.x * L * Z;
-  const int n = voxels - e0 < (int64_t)L * Z ? (int)(voxels - e0) : L * Z;   // whole lines: voxels is a multiple of Z
-  const int tid = threadIdx.x;
-  for (int i = tid; i < n; i += 256) {
-    const uint32_t v = g[e0 + i], d = v & 0x7fffu;
-    s[i] = ((v & 0x8000u) << 16) | (d == DM3_NONE ? (uint32_t)DM_INF : d * d);
-  }
-  __syncthreads();
-  for (int i = tid; i < n; i += 256) {
-    const int r = i / Z, z = i - r * Z;
-    const uint32_t mine = s[i] & 0x80000000u;
-    f[e0 + i] = mine | (uint32_t)line_min_sq(s + r * Z, z, Z, 1, mine);
-  }
-}
-
-// Workgroup (b, t): row b = p * X + x of Y lines, columns [t * ZT, t * ZT + ZT) of Z; ZT = 1 << zshift, Y * ZT <= DM3_SLAB_WORDS.
-__global__ __launch_bounds__(256) void distmap3d_slabs_kernel(const uint32_t* __restrict__ f, int Y, int Z, int zshift, int ztiles,
-                                                              int mode, const float* __restrict__ table, float* __restrict__ out,
-                                                              int* __restrict__ d2_fg, int* __restrict__ d2_bg) {
-  __shared__ uint32_t s[DM3_SLAB_WORDS];
-  const int ZT = 1 << zshift;
-  const int64_t b = blockIdx.x / ztiles;
-  const int z0 = (int)(blockIdx.x - b * ztiles) << zshift;
-  const int zn = Z - z0 < ZT ? Z - z0 : ZT;
-  const int64_t base = b * Y * Z + z0;
-  const int n = Y << zshift;
-  const int tid = threadIdx.x;
-  for (int i = tid; i < n; i += 256) {
-    const int y = i >> zshift, zc = i & (ZT - 1);
-    if (zc < zn) s[i] = f[base + (int64_t)y * Z + zc];
-  }
-  __syncthreads();
-  for (int i = tid; i < n; i += 256) {
-    const int y = i >> zshift, zc = i & (ZT - 1);
-    if (zc >= zn) continue;
-    const uint32_t mine = s[i] & 0x80000000u;
-    const bool inside = mine != 0;
-    const int d2 = line_min_sq(s + zc, y, Y, ZT, mine);        // to the other class
+// ---- the two metrics ---------------------------------------------------------------------------------------------------------
+// A metric names its cells (distmap_common.h), turns the sweep's squared distance along X into the first of them and writes what the
+// last pass found.  MetricSq: squared voxel distances in int32, and the value pass.  MetricW: squared physical distances in float32
+// under w[p] = {wx, wy, wz}, the squared voxel sizes of volume p, on the device.  The line pass turns dx into fl(wx * dx^2) and
+// searches along Z with wz, the slab pass searches along Y with wy: fl(fl(wy dy^2) + fl(fl(wz dz^2) + fl(wx dx^2))) minimised over
+// the candidates, because every pass applies a monotone map to the minimum of the pass before.  It has no value pass.
+struct MetricSq {
+  static constexpr bool WEIGHTED = false;
+  static constexpr uint32_t NONE = (uint32_t)DM_INF;
+  using D2 = int32_t;
+  static __device__ __forceinline__ CellsSq cells(uint32_t mine, float) { return {mine}; }
+  static __device__ __forceinline__ uint32_t first_cell(uint32_t dd, float) { return dd; }
+  static __device__ __forceinline__ void store(int64_t at, bool inside, int d2, int mode, const float* __restrict__ table,
+                                               float* __restrict__ map, int32_t* __restrict__ d2_fg, int32_t* __restrict__ d2_bg) {
     const bool none = d2 == DM_INF;                            // the volume has no voxel of the other class
-    const int64_t o = base + (int64_t)y * Z + zc;
-    if (d2_fg) d2_fg[o] = inside ? 0 : (none ? -1 : d2);
-    if (d2_bg) d2_bg[o] = inside ? (none ? -1 : d2) : 0;
+    if (d2_fg) d2_fg[at] = inside ? 0 : (none ? -1 : d2);
+    if (d2_bg) d2_bg[at] = inside ? (none ? -1 : d2) : 0;
     float val = 0.f;
     if (!none) {
       if (mode == DM_REFERENCE) {
@@ -112,50 +85,68 @@ __global__ __launch_bounds__(256) void distmap3d_slabs_kernel(const uint32_t* __
         val = inside ? __fdiv_rn(-(root_f32(d2) - 1.f), 255.f) : __fdiv_rn(root_f32(d2), 255.f);
       }
     }
-    out[o] = val;
+    map[at] = val;
   }
-}
+};
 
-// ---- the weighted transform: squared physical distances in float32 -------------------------------------------------------------
-// The sweep is the integer one.  The line pass turns its distance dx into fl(wx * dx^2) and searches along Z with wz, the slab pass
-// searches along Y with wy and writes the result: fl(fl(wy dy^2) + fl(fl(wz dz^2) + fl(wx dx^2))) minimised over the candidates,
-// because every pass applies a monotone map to the minimum of the pass before.  w[p] = {wx, wy, wz} of volume p, on the device.
+struct MetricW {
+  static constexpr bool WEIGHTED = true;
+  static constexpr uint32_t NONE = DM_W_NONE;
+  using D2 = float;
+  static __device__ __forceinline__ CellsW cells(uint32_t mine, float w) { return {mine, w}; }
+  static __device__ __forceinline__ uint32_t first_cell(uint32_t dd, float wx) { return __float_as_uint(mul_rn(wx, (float)dd)); }
+  static __device__ __forceinline__ void store(int64_t at, bool inside, float d2, int, const float*, float*,   // (no value pass)
+                                               float* __restrict__ d2_fg, float* __restrict__ d2_bg) {
+    const float val = __float_as_uint(d2) == DM_W_NONE ? -1.f : d2;   // +inf: the volume has no voxel of the other class
+    if (d2_fg) d2_fg[at] = inside ? 0.f : val;
+    if (d2_bg) d2_bg[at] = inside ? val : 0.f;
+  }
+};
 
-// As distmap3d_lines_kernel; a workgroup's lines may belong to two or more volumes, so each line looks its volume up: XY = X * Y.
-__global__ __launch_bounds__(256) void distmap3d_lines_w_kernel(const uint16_t* __restrict__ g, int64_t voxels, int Z, int L, int XY,
-                                                                const float* __restrict__ w, uint32_t* __restrict__ f) {
+// Workgroup b: the Z lines [b * L, b * L + L) of all volumes, L * Z <= DM3_LINE_WORDS voxels that are contiguous in memory.  Under
+// MetricW the lines may belong to two or more volumes, so each line looks its volume up, XY = X * Y; MetricSq has no such lookup.
+template <class M>
+__global__ __launch_bounds__(256) void distmap3d_lines_kernel(const uint16_t* __restrict__ g, int64_t voxels, int Z, int L, int XY,
+                                                              const float* __restrict__ w, uint32_t* __restrict__ f) {
   __shared__ uint32_t s[DM3_LINE_WORDS];
   const int64_t line0 = (int64_t)blockIdx.x * L, e0 = line0 * Z;
-  const int64_t p0 = line0 / XY;
-  const int rem0 = (int)(line0 - p0 * XY);
-  const int n = voxels - e0 < (int64_t)L * Z ? (int)(voxels - e0) : L * Z;
+  const int n = voxels - e0 < (int64_t)L * Z ? (int)(voxels - e0) : L * Z;   // whole lines: voxels is a multiple of Z
   const int tid = threadIdx.x;
+  int64_t p0 = 0;
+  int rem0 = 0;
+  if constexpr (M::WEIGHTED) { p0 = line0 / XY; rem0 = (int)(line0 - p0 * XY); }
+  const auto weight = [&](int r, int axis) -> float {          // of the volume of the workgroup's line r
+    if constexpr (M::WEIGHTED) return w[(p0 + (rem0 + r) / XY) * 3 + axis];
+    else return 0.f;
+  };
   for (int i = tid; i < n; i += 256) {
-    const int r = i / Z;
-    const float wx = w[(p0 + (rem0 + r) / XY) * 3];
+    const float wx = weight(i / Z, 0);
     const uint32_t v = g[e0 + i], d = v & 0x7fffu;
-    s[i] = ((v & 0x8000u) << 16) | (d == DM3_NONE ? DM_W_NONE : __float_as_uint(mul_rn(wx, (float)(d * d))));
+    s[i] = ((v & 0x8000u) << 16) | (d == DM3_NONE ? M::NONE : M::first_cell(d * d, wx));
   }
   __syncthreads();
   for (int i = tid; i < n; i += 256) {
     const int r = i / Z, z = i - r * Z;
-    const float wz = w[(p0 + (rem0 + r) / XY) * 3 + 2];
     const uint32_t mine = s[i] & 0x80000000u;
-    f[e0 + i] = mine | __float_as_uint(line_min_w(s + r * Z, z, Z, 1, mine, wz));
+    f[e0 + i] = mine | __builtin_bit_cast(uint32_t, envelope_min(M::cells(mine, weight(r, 2)), s + r * Z, z, Z, 1));
   }
 }
 
-// As distmap3d_slabs_kernel without the value pass; row b = p * X + x belongs to volume b / X.
-__global__ __launch_bounds__(256) void distmap3d_slabs_w_kernel(const uint32_t* __restrict__ f, int X, int Y, int Z, int zshift,
-                                                                int ztiles, const float* __restrict__ w, float* __restrict__ d2_fg,
-                                                                float* __restrict__ d2_bg) {
+// Workgroup (b, t): row b = p * X + x of Y lines, columns [t * ZT, t * ZT + ZT) of Z; ZT = 1 << zshift, Y * ZT <= DM3_SLAB_WORDS.
+// The row belongs to volume b / X.
+template <class M>
+__global__ __launch_bounds__(256) void distmap3d_slabs_kernel(const uint32_t* __restrict__ f, int X, int Y, int Z, int zshift, int ztiles,
+                                                              const float* __restrict__ w, int mode, const float* __restrict__ table,
+                                                              float* __restrict__ map, typename M::D2* __restrict__ d2_fg,
+                                                              typename M::D2* __restrict__ d2_bg) {
   __shared__ uint32_t s[DM3_SLAB_WORDS];
   const int ZT = 1 << zshift;
   const int64_t b = blockIdx.x / ztiles;
   const int z0 = (int)(blockIdx.x - b * ztiles) << zshift;
   const int zn = Z - z0 < ZT ? Z - z0 : ZT;
   const int64_t base = b * Y * Z + z0;
-  const float wy = w[(b / X) * 3 + 1];
+  float wy = 0.f;
+  if constexpr (M::WEIGHTED) wy = w[(b / X) * 3 + 1];
   const int n = Y << zshift;
   const int tid = threadIdx.x;
   for (int i = tid; i < n; i += 256) {
@@ -167,12 +158,8 @@ __global__ __launch_bounds__(256) void distmap3d_slabs_w_kernel(const uint32_t* 
     const int y = i >> zshift, zc = i & (ZT - 1);
     if (zc >= zn) continue;
     const uint32_t mine = s[i] & 0x80000000u;
-    const bool inside = mine != 0;
-    const float d2 = line_min_w(s + zc, y, Y, ZT, mine, wy);   // to the other class
-    const float val = __float_as_uint(d2) == DM_W_NONE ? -1.f : d2;   // +inf: the volume has no voxel of the other class
-    const int64_t o = base + (int64_t)y * Z + zc;
-    if (d2_fg) d2_fg[o] = inside ? 0.f : val;
-    if (d2_bg) d2_bg[o] = inside ? val : 0.f;
+    const auto d2 = envelope_min(M::cells(mine, wy), s + zc, y, Y, ZT);   // to the other class
+    M::store(base + (int64_t)y * Z + zc, mine != 0, d2, mode, table, map, d2_fg, d2_bg);
   }
 }
 
@@ -190,6 +177,35 @@ static inline Dm3Grid dm3_grid(int P, int X, int Y, int Z) {
   return g;
 }
 
+// What the two entry points share: the checks that do not depend on the metric, and the three launches.
+template <class M>
+static int distmap3d_impl(const char* who, const uint8_t* masks, int P, int X, int Y, int Z, const float* w, void* workspace,
+                          int64_t workspace_bytes, int mode, const float* table, float* map, typename M::D2* d2_fg,
+                          typename M::D2* d2_bg, void* stream) {
+  if (check_sides(who, P, X, Y, Z)) return -1;
+  const int64_t plane = (int64_t)Y * Z, voxels = (int64_t)P * X * plane;
+  CTSEG_REQUIRE(workspace_bytes >= 6 * voxels, "%s: the workspace holds %lld bytes, %lld are needed", who, (long long)workspace_bytes,
+                (long long)(6 * voxels));
+  CTSEG_REQUIRE(((uintptr_t)workspace % 4) == 0 && ((uintptr_t)w % 4) == 0 && ((uintptr_t)table % 4) == 0 && ((uintptr_t)map % 4) == 0 &&
+                    ((uintptr_t)d2_fg % 4) == 0 && ((uintptr_t)d2_bg % 4) == 0,
+                "%s: unaligned pointer", who);
+  const Dm3Grid gr = dm3_grid(P, X, Y, Z);
+  CTSEG_REQUIRE(gr.sweep_blocks <= 0x7fffffff && gr.line_blocks <= 0x7fffffff && gr.slab_blocks <= 0x7fffffff,
+                "%s: %d volumes are too many for one launch", who, P);
+  uint32_t* f = (uint32_t*)workspace;                          // [voxels] uint32, then [voxels] uint16
+  uint16_t* g = (uint16_t*)(f + voxels);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(distmap3d_sweep_kernel, dim3((unsigned)gr.sweep_blocks), dim3(256), 0, st, masks, (int64_t)P * plane, X, plane, g);
+  CTSEG_LAUNCH_CHECK_PASS(who, "sweep");
+  hipLaunchKernelGGL(distmap3d_lines_kernel<M>, dim3((unsigned)gr.line_blocks), dim3(256), 0, st, (const uint16_t*)g, voxels, Z, gr.L,
+                     X * Y, w, f);
+  CTSEG_LAUNCH_CHECK_PASS(who, "lines");
+  hipLaunchKernelGGL(distmap3d_slabs_kernel<M>, dim3((unsigned)gr.slab_blocks), dim3(256), 0, st, (const uint32_t*)f, X, Y, Z, gr.zshift,
+                     gr.ztiles, w, mode, table, map, d2_fg, d2_bg);
+  CTSEG_LAUNCH_CHECK_PASS(who, "slabs");
+  return 0;
+}
+
 }  // namespace ctseg
 
 using namespace ctseg;
@@ -198,59 +214,15 @@ extern "C" int ctseg_distmap3d_batch(const uint8_t* masks, int32_t P, int32_t X,
                                      void* workspace, int64_t workspace_bytes, float* out, int32_t* d2_fg, int32_t* d2_bg,
                                      void* stream) {
   CTSEG_REQUIRE(masks && table && workspace && out, "distmap3d_batch: null pointer (masks, table, workspace and out are required)");
-  CTSEG_REQUIRE(P >= 1 && X >= 1 && Y >= 1 && Z >= 1, "distmap3d_batch: P, X, Y, Z >= 1 (got %d volumes of %d x %d x %d)", P, X, Y, Z);
-  CTSEG_REQUIRE(X <= DM_MAX_SIDE && Y <= DM_MAX_SIDE && Z <= DM_MAX_SIDE, "distmap3d_batch: sides up to %d (got %d x %d x %d)",
-                DM_MAX_SIDE, X, Y, Z);
   CTSEG_REQUIRE(mode == DM_REFERENCE || mode == DM_SIGNED, "distmap3d_batch: mode %d", mode);
-  const int64_t plane = (int64_t)Y * Z, voxels = (int64_t)P * X * plane;
-  CTSEG_REQUIRE(workspace_bytes >= 6 * voxels, "distmap3d_batch: the workspace holds %lld bytes, %lld are needed",
-                (long long)workspace_bytes, (long long)(6 * voxels));
-  CTSEG_REQUIRE(((uintptr_t)workspace % 4) == 0 && ((uintptr_t)out % 4) == 0 && ((uintptr_t)table % 4) == 0 &&
-                    ((uintptr_t)d2_fg % 4) == 0 && ((uintptr_t)d2_bg % 4) == 0,
-                "distmap3d_batch: unaligned pointer");
-  const Dm3Grid gr = dm3_grid(P, X, Y, Z);
-  CTSEG_REQUIRE(gr.sweep_blocks <= 0x7fffffff && gr.line_blocks <= 0x7fffffff && gr.slab_blocks <= 0x7fffffff,
-                "distmap3d_batch: %d volumes are too many for one launch", P);
-  uint32_t* f = (uint32_t*)workspace;                          // [voxels] uint32, then [voxels] uint16
-  uint16_t* g = (uint16_t*)(f + voxels);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(distmap3d_sweep_kernel, dim3((unsigned)gr.sweep_blocks), dim3(256), 0, st, masks, (int64_t)P * plane, X, plane, g);
-  CTSEG_LAUNCH_CHECK("distmap3d_batch (sweep)");
-  hipLaunchKernelGGL(distmap3d_lines_kernel, dim3((unsigned)gr.line_blocks), dim3(256), 0, st, (const uint16_t*)g, voxels, Z, gr.L, f);
-  CTSEG_LAUNCH_CHECK("distmap3d_batch (lines)");
-  hipLaunchKernelGGL(distmap3d_slabs_kernel, dim3((unsigned)gr.slab_blocks), dim3(256), 0, st, (const uint32_t*)f, Y, Z, gr.zshift,
-                     gr.ztiles, mode, table, out, d2_fg, d2_bg);
-  CTSEG_LAUNCH_CHECK("distmap3d_batch (slabs)");
-  return 0;
+  return distmap3d_impl<MetricSq>("distmap3d_batch", masks, P, X, Y, Z, nullptr, workspace, workspace_bytes, mode, table, out, d2_fg,
+                                  d2_bg, stream);
 }
 
 extern "C" int ctseg_distmap3d_weighted(const uint8_t* masks, int32_t P, int32_t X, int32_t Y, int32_t Z, const float* w, void* workspace,
                                         int64_t workspace_bytes, float* d2_fg, float* d2_bg, void* stream) {
   CTSEG_REQUIRE(masks && w && workspace && (d2_fg || d2_bg),
                 "distmap3d_weighted: null pointer (masks, w, workspace and one of d2_fg, d2_bg are required)");
-  CTSEG_REQUIRE(P >= 1 && X >= 1 && Y >= 1 && Z >= 1, "distmap3d_weighted: P, X, Y, Z >= 1 (got %d volumes of %d x %d x %d)", P, X, Y,
-                Z);
-  CTSEG_REQUIRE(X <= DM_MAX_SIDE && Y <= DM_MAX_SIDE && Z <= DM_MAX_SIDE, "distmap3d_weighted: sides up to %d (got %d x %d x %d)",
-                DM_MAX_SIDE, X, Y, Z);
-  const int64_t plane = (int64_t)Y * Z, voxels = (int64_t)P * X * plane;
-  CTSEG_REQUIRE(workspace_bytes >= 6 * voxels, "distmap3d_weighted: the workspace holds %lld bytes, %lld are needed",
-                (long long)workspace_bytes, (long long)(6 * voxels));
-  CTSEG_REQUIRE(((uintptr_t)workspace % 4) == 0 && ((uintptr_t)w % 4) == 0 && ((uintptr_t)d2_fg % 4) == 0 &&
-                    ((uintptr_t)d2_bg % 4) == 0,
-                "distmap3d_weighted: unaligned pointer");
-  const Dm3Grid gr = dm3_grid(P, X, Y, Z);
-  CTSEG_REQUIRE(gr.sweep_blocks <= 0x7fffffff && gr.line_blocks <= 0x7fffffff && gr.slab_blocks <= 0x7fffffff,
-                "distmap3d_weighted: %d volumes are too many for one launch", P);
-  uint32_t* f = (uint32_t*)workspace;                          // [voxels] uint32, then [voxels] uint16
-  uint16_t* g = (uint16_t*)(f + voxels);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(distmap3d_sweep_kernel, dim3((unsigned)gr.sweep_blocks), dim3(256), 0, st, masks, (int64_t)P * plane, X, plane, g);
-  CTSEG_LAUNCH_CHECK("distmap3d_weighted (sweep)");
-  hipLaunchKernelGGL(distmap3d_lines_w_kernel, dim3((unsigned)gr.line_blocks), dim3(256), 0, st, (const uint16_t*)g, voxels, Z, gr.L,
-                     X * Y, w, f);
-  CTSEG_LAUNCH_CHECK("distmap3d_weighted (lines)");
-  hipLaunchKernelGGL(distmap3d_slabs_w_kernel, dim3((unsigned)gr.slab_blocks), dim3(256), 0, st, (const uint32_t*)f, X, Y, Z, gr.zshift,
-                     gr.ztiles, w, d2_fg, d2_bg);
-  CTSEG_LAUNCH_CHECK("distmap3d_weighted (slabs)");
-  return 0;
+  return distmap3d_impl<MetricW>("distmap3d_weighted", masks, P, X, Y, Z, w, workspace, workspace_bytes, 0, nullptr, nullptr, d2_fg,
+                                 d2_bg, stream);   // (no mode, table or map: no value pass)
 }
