@@ -29,7 +29,7 @@ class BaseUNet3D(_TrainerBase):
     def __init__(self, filters: List = [16, 32, 64, 128, 256], use_res_units: bool = False, downsample: bool = False,
                  lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
                  surface_metrics: bool = False, surface_percentile: float = 95.0, surface_spacing=None,
-                 largest_component: bool = False, largest_component_connectivity=None, **kwargs) -> None:
+                 largest_component: bool = False, largest_component_connectivity=None, tta=None, **kwargs) -> None:
         """``device_boundary``: opt in to the Boundary loss on volumes; the batch then carries the distance maps as its fourth
         element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise.
         ``surface_metrics``: ``validation_step`` also scores the batch with the percentile Hausdorff distance (``surface_percentile``,
@@ -46,7 +46,12 @@ class BaseUNet3D(_TrainerBase):
         (``"{structure} Dice (val LCC)"``, ``"Mean Dice Score (val LCC)"``) and, with ``surface_metrics``, its surface metrics, kept
         under ``"val LCC"`` and logged as ``"{structure} HD95 (val LCC)"`` and so on.  ``on_validation_epoch_end`` also logs
         ``"{structure} components (val)"``, the mean number of components of the raw prediction per class over the epoch's
-        samples.  Per rank, and never in a training step, like the surface metrics."""
+        samples.  Per rank, and never in a training step, like the surface metrics.
+        ``tta``: a ``volumetric.tta.TestTimeAugmenter3D`` whose ``size`` is the batch's grid.  ``validation_step`` then also predicts
+        every sample once per view, merges the views (``predict_batch``) and scores the ensemble label map IN ADDITION to the plain
+        one: its Dice under the prefix ``"val TTA"`` (``"{structure} Dice (val TTA)"``, ``"Mean Dice Score (val TTA)"``) and, with
+        ``surface_metrics``, its surface metrics, kept under ``"val TTA"`` and logged as ``"{structure} HD95 (val TTA)"`` and so
+        on.  ``predict_volume`` is the inference call.  Per rank, and never in a training step."""
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
@@ -64,6 +69,8 @@ class BaseUNet3D(_TrainerBase):
         self.largest_component_connectivity = largest_component_connectivity
         self.lcc_dice_score = DiceMetricWrapper3D() if largest_component else None
         self._components_kept = []
+        self.tta = tta                                              # (kept out of hparams too)
+        self.tta_dice_score = DiceMetricWrapper3D() if tta is not None else None
 
     def _construct_model(self):
         # reference :58-72 — in_channels=1, strides for a 5-entry filter list, num_res_units hard-wired to 2
@@ -159,11 +166,12 @@ class BaseUNet3D(_TrainerBase):
         return _StepLossFn.apply(loss, eng, plan, self, *eng.store.params)
 
     def validation_step(self, batch, batch_idx=0):
-        _, masks, _, prediction, _ = self._shared_step(batch, is_training=False)
-        if not (self.surface_metrics or self.largest_component):
+        images, masks, _, prediction, _ = self._shared_step(batch, is_training=False)
+        if not (self.surface_metrics or self.largest_component or self.tta is not None):
             return
         with torch.no_grad():
-            labels = _squash_predictions(prediction)
+            if self.surface_metrics or self.largest_component:
+                labels = _squash_predictions(prediction)
             if self.surface_metrics:
                 self._score_surfaces(labels, masks, "val")
             if self.largest_component:
@@ -173,6 +181,19 @@ class BaseUNet3D(_TrainerBase):
                 self._log_dice("val LCC", *self.lcc_dice_score(kept.labels, masks))
                 if self.surface_metrics:
                     self._score_surfaces(kept.labels, masks, "val LCC")
+            if self.tta is not None:        # last: the views' forward passes overwrite the storage behind ``prediction``
+                merged = self.tta.predict_batch(self, images).labels
+                self._log_dice("val TTA", *self.tta_dice_score(merged, masks))
+                if self.surface_metrics:
+                    self._score_surfaces(merged, masks, "val TTA")
+
+    def predict_volume(self, image, native: bool = True, want_probs: bool = False):
+        """the inference call: a raw (D, H, W) scan on the device -> ``TestTimeAugmenter3D.predict``'s namespace, whose ``labels``
+        are uint8 on the scan's own grid (``native``) or on the model's (H', W', D').  Needs ``tta``; one identity view
+        (``TestTimeAugmenter3D([Augment3D.identity_params()])``) is the plain prediction carried back to the scan."""
+        if self.tta is None:
+            raise ValueError("predict_volume: construct the module with tta=TestTimeAugmenter3D(...)")
+        return self.tta.predict(self, image, native=native, want_probs=want_probs)
 
     def _score_surfaces(self, labels, masks, prefix):
         self.surface_score(labels, masks)
@@ -197,8 +218,9 @@ class BaseUNet3D(_TrainerBase):
         HD95 mm (val)" and "Mean ASSD mm (val)", and the keys without it are not logged.  With ``largest_component`` the same
         keys under "(val LCC)" for the cleaned predictions, and "{structure} components (val)" besides"""
         if self.surface_metrics:
-            for prefix in ("val", "val LCC") if self.largest_component else ("val",):
-                self._log_surface_epoch(prefix)
+            for prefix, on in (("val", True), ("val LCC", self.largest_component), ("val TTA", self.tta is not None)):
+                if on:
+                    self._log_surface_epoch(prefix)
         if self.largest_component and self._components_kept:
             mean = torch.cat(self._components_kept).double().mean(dim=0)
             self._components_kept = []

@@ -188,8 +188,9 @@ class Augment3D:
                 "flips": tuple(bool(v) for v in u[10:13] < self.flip_prob), "gain": float(gain), "bias": float(bias)}
 
     @staticmethod
-    def matrix(size, params) -> np.ndarray:
-        """(3, 4) float32 sampling matrix of ``params`` on the ``size`` = (D', H', W') grid: the class docstring has the order"""
+    def matrix(size, params, dtype=np.float32) -> np.ndarray:
+        """(3, 4) float32 sampling matrix of ``params`` on the ``size`` = (D', H', W') grid: the class docstring has the order;
+        ``dtype=np.float64`` hands out the composition before its one rounding (``tta.view_to_target_matrix`` inverts that)"""
         c = (np.asarray(size, dtype=np.float64).reshape(3) - 1.0) / 2.0
         ad, ah, aw = (float(v) for v in params["angles"])
         cd, sd, ch, sh, cw, sw = np.cos(ad), np.sin(ad), np.cos(ah), np.sin(ah), np.cos(aw), np.sin(aw)
@@ -202,7 +203,7 @@ class Augment3D:
         out = np.empty((3, 4), dtype=np.float64)
         out[:, :3] = L
         out[:, 3] = c - L @ c + np.asarray(params["shifts"], dtype=np.float64).reshape(3)
-        return out.astype(np.float32)
+        return out.astype(dtype)
 
     def channel_src(self, params, K: int) -> list:
         """output mask channel k reads input channel ``channel_src[k]``: the identity, or ``swap_pairs`` swapped when the w mirror

@@ -465,6 +465,44 @@ int ctseg_augment3d_to_hwd(const void* image, int32_t image_dtype, const uint8_t
                            float cval, const int32_t* mask_src /* host */, int32_t window, float win_lo, float win_hi, float gain,
                            float bias, float* image_out, uint8_t* masks_out, uint8_t* labels_out, int64_t* hist, void* stream);
 
+/* Test-time augmentation of the 3-D network: the prediction of one VIEW (the network's logits for an augmented copy of the scan)
+ * is resampled onto a TARGET grid and added into an accumulator there; ctseg_tta_finish turns the accumulator into labels.
+ * Inputs and layout:
+ *   - logits is the view's fp32 channels-last block [H][W][D][ld], the storage the network returns for one sample; channels
+ *     0..C-1 are read.  ld % 4 == 0, 1 <= C <= 16, C <= ld.
+ *   - The target grid is Dt x Ht x Wt.  layout 0 stores target rows in (h, w, d) order, the model's grid: row (th * Wt + tw) * Dt
+ *     + td.  layout 1 stores them in (d, h, w) order, the raw scan's grid: row (td * Ht + th) * Wt + tw.
+ *   - acc is [St][acc_ld] fp32, St = Dt * Ht * Wt, acc_ld % 4 == 0, acc_ld >= C + 1.  The caller zeroes it before the first view.
+ *   - logits and acc are 16-byte aligned; every volume (D * H * W, Dt * Ht * Wt) has fewer than 2^31 voxels.
+ *   - matrix (12 floats, row-major 3 x 4; rows and columns ordered d, h, w, as for ctseg_augment3d_to_hwd) and chan_src (C ints,
+ *     or NULL for the identity) are HOST arrays copied into the kernel's arguments: no device upload, no synchronisation.
+ * Every float operation is one float32 rounding; nothing is contracted into an FMA.
+ *   - Sampling coordinate: the matrix maps a TARGET voxel t = (td, th, tw), taken as floats, to the point of the VIEW's grid that
+ *     it samples: q_a = ((M[a][0]*td + M[a][1]*th) + M[a][2]*tw) + M[a][3], evaluated in that order.
+ *   - Coverage: r_a = (int)floorf(q_a + 0.5f), the float clamped into [-1, n_a] before the conversion.  If any r_a lies outside
+ *     [0, n_a) the view contributes nothing to this voxel and its accumulator row is not touched.
+ *   - Sample, per channel: interp 0 takes z_c = logits[r][c].  interp 1 (trilinear) uses b_a = floorf(q_a), f_a = q_a - b_a; the
+ *     corners b + {0,1}^3 are clamped to the volume and combined as lerp(x, y, t) = x + t * (y - x), along w first, then h, then d.
+ *   - Value: mode 0 (mean of logits) v_c = z_c.  mode 1 (mean of probabilities) m = max_c z_c, e_c = expf(z_c - m), s = the sum
+ *     of e_c in channel order, v_c = e_c / s.
+ *   - Accumulate: acc[t][k] += weight * v[chan_src[k]] for k < C, and acc[t][C] += weight: column C is the voxel's weight sum.
+ *     Columns beyond C keep their bits.  One thread owns a voxel's row and there are no atomics: views added in the same order
+ *     give the same bits.
+ * Rejected before any launch: a null pointer; a matrix entry that is not finite, or a row that sends the target grid beyond 1e30;
+ * a weight that is not finite or is <= 0; a chan_src that is no permutation of 0..C-1; mode, interp or layout out of range; ld or
+ * acc_ld breaking the conditions above; an unaligned logits or acc. */
+int ctseg_tta_accumulate(const float* logits, int32_t ld, int32_t C, int32_t D, int32_t H, int32_t W, const float* matrix /* host, 12 */,
+                         const int32_t* chan_src /* host, C, or NULL */, float weight, int32_t mode, int32_t interp, int32_t Dt,
+                         int32_t Ht, int32_t Wt, int32_t layout, float* acc, int32_t acc_ld, void* stream);
+/* The accumulator of ctseg_tta_accumulate (same acc_ld, C, mode; St rows, 0 < St < 2^31) -> an answer:
+ *   - labels[t] is the first maximal k of acc[t][0..C), the tie rule of _squash_predictions (capstone/training/utils.py); a voxel
+ *     that no view covered (acc[t][C] == 0) gets label 0.
+ *   - probs [St][C], or NULL: acc[t][k] / acc[t][C] in mode 1; in mode 0 the softmax, by the formula above, of acc[t][k] / acc[t][C].
+ *     An uncovered voxel gets an all-zero row.
+ *   - hist (C counters, which the caller zeroes), or NULL: hist[k] counts the labels. */
+int ctseg_tta_finish(const float* acc, int32_t acc_ld, int32_t C, int64_t St, int32_t mode, uint8_t* labels,
+                     float* probs /* [St][C] or NULL */, int64_t* hist /* C, caller zeroes, or NULL */, void* stream);
+
 /* 2-D input pipeline on the device, a whole batch in one launch: the presets of capstone/transforms/predefined.py that are
  * per-pixel and index arithmetic (windowed_degree_1, windowed_degree_2, every "test" side):
  *   window     apply_window (capstone/transforms/transforms_2d.py:97-107) per window c: lo = win_lo[c], hi = win_hi[c] (HOST
