@@ -1,7 +1,8 @@
 """Drop-in for reference capstone/volumetric/data_module.py: ``MiccaiDataModule3D`` over the device-fed ``MiccaiDataset3D``.
 
 ``transform_degree`` 0 is the reference's only preset (resize + permute); 1 adds the device augmentation of
-``transforms.augmented_degree_1`` on the "train" side.  The loaders are plain iterables of device batches
+``transforms.augmented_degree_1`` on the "train" side (``transforms.augmented_degree_2``, which adds the free-form deformation, goes
+to ``get_miccai_3d`` / ``MiccaiDataset3D`` directly).  The loaders are plain iterables of device batches
 ``(images, masks, mask_indicator)`` (``dist_maps=True``: plus the distance maps): a shuffled (train) or sequential order cut into
 ``batch_size`` pieces, every instance one ``MiccaiDataset3D.__getitem__`` (one launch) and every piece one ``collate_3d``.  No
 workers, no pinned memory.  The class derives from ``pl.LightningDataModule`` only when Lightning is importable.

@@ -14,6 +14,8 @@ per voxel leaves the kernel instead of 9, and the trainer's squash pass disappea
 ``Augment3D`` is the spatial and intensity augmentation of that pipeline, which the reference's 3-D path lacks: random rotation,
 zoom, shift and mirror as one 3 x 4 matrix, drawn on the host and applied by ``ctseg_augment3d_to_hwd`` in the same single pass
 (``augment3d_to_hwd``).  A left-right mirror swaps the paired structures' mask channels, see ``Augment3D.channel_src``.
+``Deform3D`` adds a non-rigid part to that pass: a cubic B-spline free-form deformation over a coarse control lattice, which the
+device fills from a drawn seed (``ctseg_deform3d_lattice``, then ``ctseg_augment3d_deform_to_hwd``).
 There is no CPU fallback: CPU tensors raise ``NativeError``.
 """
 import ctypes
@@ -75,15 +77,46 @@ def resize3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor]
 
 _BORDERS = {"constant": 0, "edge": 1}
 _INTERPS = {"nearest": 0, "trilinear": 1}
+# the control lattice of the deformed pass: one small fp32 tensor per (device, stream), grown when a larger one is asked for.  The
+# lattice launch and the pass that reads it go to the same stream, so the next instance's lattice launch is ordered behind this
+# instance's pass: reusing the buffer needs no synchronisation.
+_LATTICES = {}
+
+
+def _check_deform(cells, magnitude, size):
+    """the limits of a lattice of ``cells`` over the ``size`` = (D', H', W') grid: a cell of at least 4 voxels (the kernel's slab)
+    and a control-point displacement of at most 0.4 of a cell, below which a cubic B-spline deformation cannot fold"""
+    for a, (g, m, n) in enumerate(zip(cells, magnitude, size)):
+        if g < 1 or 4 * g > n:
+            raise ValueError(f"Deform3D: {g} cells over {n} voxels along axis {'dhw'[a]}: a cell has at least 4 voxels")
+        if not (np.isfinite(m) and 0.0 <= m <= 0.4 * n / g):
+            raise ValueError(f"Deform3D: magnitude {m} along axis {'dhw'[a]} is outside [0, 0.4 cells] = [0, {0.4 * n / g:g}] voxels")
+
+
+def _lattice(deform, device):
+    """the cached lattice buffer filled for ``deform`` (any lattice the entry accepts: ``Deform3D.check`` has the preset's limits)"""
+    cells = tuple(int(v) for v in deform["cells"])
+    magnitude = tuple(float(v) for v in deform["magnitude"])
+    n = 3 * (cells[0] + 3) * (cells[1] + 3) * (cells[2] + 3)
+    key = (device, nat.stream_ptr())
+    buf = _LATTICES.get(key)
+    if buf is None or buf.numel() < n:
+        _LATTICES[key] = buf = torch.empty(n, dtype=torch.float32, device=device)
+    c_cells = (ctypes.c_int32 * 3)(*cells)
+    c_mag = (ctypes.c_float * 3)(*magnitude)
+    nat.call("ctseg_deform3d_lattice", int(deform["seed"]), ctypes.addressof(c_cells), ctypes.addressof(c_mag), nat.ptr(buf), n)
+    return buf, c_cells
 
 
 def augment3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor], size: Sequence[int], matrix, interp=1,
                      border="constant", cval: float = 0.0, mask_src=None, window=None, gain: float = 1.0, bias: float = 0.0,
-                     want_masks: bool = True, want_labels: bool = False):
+                     want_masks: bool = True, want_labels: bool = False, deform: Optional[dict] = None):
     """``resize3d_to_hwd`` with the output voxel sent through ``matrix`` first: (3, 4), rows and columns ordered d, h, w, mapping an
     OUTPUT voxel of the ``size`` grid to the point of that same grid it samples (include/ctseg_hip.h has the rules).  ``interp``
     0 / "nearest" or 1 / "trilinear" for the image (masks are always nearest), ``border`` "constant" (image ``cval``, masks 0) or
     "edge"; output mask channel k reads input channel ``mask_src[k]``; the windowed value becomes ``v * gain + bias``.
+    ``deform`` = {"seed", "cells", "magnitude"} (``Deform3D``): the device fills the control lattice from the seed and the pass
+    adds its B-spline displacement to the sampling point, two launches instead of one.
     -> image (H',W',D') fp32, masks (K,H',W',D') u8, labels (H',W',D') u8, hist (K+1)"""
     ref = image if image is not None else masks
     nat.require_gpu(ref, "Augment3D")
@@ -114,10 +147,15 @@ def augment3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor
         if len(src) != K:
             raise nat.NativeError(f"Augment3D: mask_src has {len(src)} entries for {K} mask channels")
         src = (ctypes.c_int32 * K)(*src)
-    nat.call("ctseg_augment3d_to_hwd", nat.ptr(image), code, nat.ptr(masks), K, D, H, W, Do, Ho, Wo,
-             ctypes.addressof(mat), _INTERPS.get(interp, interp), _BORDERS.get(border, border), float(cval),
-             ctypes.addressof(src) if src is not None else None, wmode, lo, hi, float(gain), float(bias),
-             nat.ptr(img_out), nat.ptr(m_out), nat.ptr(lab), nat.ptr(hist))
+    args = (nat.ptr(image), code, nat.ptr(masks), K, D, H, W, Do, Ho, Wo,
+            ctypes.addressof(mat), _INTERPS.get(interp, interp), _BORDERS.get(border, border), float(cval),
+            ctypes.addressof(src) if src is not None else None, wmode, lo, hi, float(gain), float(bias),
+            nat.ptr(img_out), nat.ptr(m_out), nat.ptr(lab), nat.ptr(hist))
+    if deform is None:
+        nat.call("ctseg_augment3d_to_hwd", *args)
+    else:
+        lattice, cells = _lattice(deform, dev)
+        nat.call("ctseg_augment3d_deform_to_hwd", *args, nat.ptr(lattice), ctypes.addressof(cells))
     return img_out, m_out, lab, hist
 
 
@@ -131,6 +169,25 @@ def _axis_ranges(v, what):
     return a
 
 
+class Deform3D:
+    """Random free-form deformation for ``Augment3D(deform=...)``: a cubic B-spline over a lattice of ``cells`` = cells per axis
+    d, h, w of the output grid, whose control points move by up to ``magnitude`` output voxels per axis (uniform, from a drawn
+    seed, on the device); ``p`` = probability that an augmented instance is deformed.  ``check(size)`` raises ``ValueError`` for a
+    grid on which a cell has under 4 voxels or a magnitude exceeds 0.4 of a cell, the bound below which the map cannot fold."""
+
+    def __init__(self, cells=(3, 8, 8), magnitude=(1.0, 4.0, 4.0), p: float = 1.0):
+        self.cells = tuple(int(v) for v in cells)
+        self.magnitude = tuple(float(v) for v in magnitude)
+        if len(self.cells) != 3 or len(self.magnitude) != 3 or min(self.cells) < 1:
+            raise ValueError("Deform3D: cells and magnitude have one entry per axis d, h, w; at least one cell per axis")
+        if not all(np.isfinite(m) and m >= 0.0 for m in self.magnitude):
+            raise ValueError("Deform3D: magnitudes are finite and not negative")
+        self.p = float(p)
+
+    def check(self, size):
+        _check_deform(self.cells, self.magnitude, tuple(int(v) for v in size))
+
+
 class Augment3D:
     """Random affine + mirror + intensity augmentation of a volume, applied by ``InstancePipeline3D(augment=...)`` in its one pass.
 
@@ -141,7 +198,7 @@ class Augment3D:
     ``swap_pairs`` = mask channels that trade places under a w mirror (default: OpticNerve, Parotid, Submandibular L/R of
     ``STRUCTURES``); ``gain`` / ``bias`` = (lo, hi) of ``v * gain + bias`` after the window, or None; ``interp`` "trilinear" or
     "nearest" for the image (masks are always nearest); ``border`` "constant" (``cval`` / 0) or "edge"; ``p`` = probability that
-    anything is applied at all.
+    anything is applied at all; ``deform`` = a ``Deform3D`` or None: a non-rigid displacement added to the affine sampling point.
 
     The matrix maps an output voxel o to the point q = L o + offset it samples (the sampling direction), composed in float64 as
         L = R_w(angle_w) . R_h(angle_h) . R_d(angle_d) . diag(1 / scale) . F,      offset = c - L c + shift,   c = (size - 1) / 2
@@ -152,7 +209,7 @@ class Augment3D:
 
     def __init__(self, rotate=(0.0, 0.0, 0.0), scale=(1.0, 1.0), translate=(0.0, 0.0, 0.0), flip_prob=(0.0, 0.0, 0.0),
                  swap_pairs=((3, 4), (5, 6), (7, 8)), gain=None, bias=None, interp="trilinear", border="constant", cval: float = 0.0,
-                 p: float = 1.0):
+                 p: float = 1.0, deform: Optional[Deform3D] = None):
         self.rotate = np.abs(np.asarray(rotate, dtype=np.float64).reshape(3))
         self.scale = _axis_ranges(scale, "scale")
         if (self.scale <= 0).any():
@@ -165,6 +222,7 @@ class Augment3D:
         if interp not in _INTERPS or border not in _BORDERS:
             raise ValueError(f"Augment3D: interp is one of {sorted(_INTERPS)}, border one of {sorted(_BORDERS)}")
         self.interp, self.border, self.cval, self.p = interp, border, float(cval), float(p)
+        self.deform = deform
         self._rng = np.random.default_rng()
 
     @staticmethod
@@ -174,9 +232,19 @@ class Augment3D:
 
     def draw(self, generator=None) -> dict:
         """one instance's parameters, uniform in the ranges, from a ``numpy.random.Generator``; the draws are made in one fixed
-        order and number whatever the ranges are (applied, angles, scales, shifts, flips, gain, bias): 15 uniforms per call"""
+        order and number whatever the ranges are (applied, angles, scales, shifts, flips, gain, bias): 15 uniforms per call.
+        With a ``deform``, two more values follow them in every call, a uniform (deformed or not) and the lattice's seed, and
+        the dict gains ``"deform"``: None or {"seed", "cells", "magnitude"}"""
         g = generator if generator is not None else self._rng
         u = g.random(15)
+        params = self._affine_params(u)
+        if self.deform is not None:
+            chance, seed = g.random(), int(g.integers(0, 2 ** 63))
+            on = params["applied"] and chance < self.deform.p
+            params["deform"] = {"seed": seed, "cells": self.deform.cells, "magnitude": self.deform.magnitude} if on else None
+        return params
+
+    def _affine_params(self, u) -> dict:
         if not u[0] < self.p:
             return self.identity_params()
         sym = 2.0 * u[1:10] - 1.0
@@ -258,12 +326,15 @@ class InstancePipeline3D:
     ``augment`` = an ``Augment3D``: the one launch is ``ctseg_augment3d_to_hwd`` instead, with parameters drawn from ``generator``
     (a ``numpy.random.Generator``) or given as ``params`` (``Augment3D.draw``'s dict); the result then carries ``"params"`` and
     ``"channel_src"``, the K input channels behind the output mask channels, which ``mask_indicator`` has to follow.  The
-    distance maps are those of the augmented masks."""
+    distance maps are those of the augmented masks.  An ``Augment3D`` with a ``deform`` is checked against ``size`` here, and an
+    instance whose ``params["deform"]`` is set takes the lattice launch and the deformed pass instead."""
 
     def __init__(self, size=(96, 256, 256), squash: bool = False, window: Optional[Tuple] = None, dist_maps: bool = False,
                  signed: bool = False, augment: Optional[Augment3D] = None):
         self.size, self.squash, self.window, self.dist_maps, self.signed = tuple(size), squash, window, dist_maps, signed
         self.augment = augment
+        if augment is not None and augment.deform is not None:
+            augment.deform.check(self.size)
 
     def __call__(self, image: torch.Tensor, masks, params=None, generator=None) -> dict:
         if isinstance(masks, (list, tuple)):
@@ -279,7 +350,7 @@ class InstancePipeline3D:
             src = aug.channel_src(params, masks.reshape((-1,) + tuple(masks.shape[-3:])).shape[0])
             img, m, lab, hist = augment3d_to_hwd(image, masks, self.size, aug.matrix(self.size, params), aug.interp, aug.border,
                                                  aug.cval, src, self.window, params["gain"], params["bias"], want_masks=want_masks,
-                                                 want_labels=self.squash)
+                                                 want_labels=self.squash, deform=params.get("deform"))
             extra = {"channel_src": src, "params": params}
         out = {"image": img.unsqueeze(0), "masks": lab if self.squash else m, **extra}
         if self.squash:
@@ -295,5 +366,13 @@ windowed_degree_0 = {"train": InstancePipeline3D(), "test": InstancePipeline3D()
 augmented_degree_1 = {
     "train": InstancePipeline3D(augment=Augment3D(rotate=(0.26, 0.05, 0.05), scale=(0.9, 1.1), translate=(2, 8, 8),
                                                   flip_prob=(0, 0, 0.5))),
+    "test": InstancePipeline3D(),
+}
+# degree 1 plus a free-form deformation of every other augmented instance: 3 x 8 x 8 cells of 32 voxels over the 96 x 256 x 256 grid,
+# control points moved by up to 1 voxel through the slices and 4 in plane (0.03 and 0.125 of a cell: far below the folding bound)
+augmented_degree_2 = {
+    "train": InstancePipeline3D(augment=Augment3D(rotate=(0.26, 0.05, 0.05), scale=(0.9, 1.1), translate=(2, 8, 8),
+                                                  flip_prob=(0, 0, 0.5),
+                                                  deform=Deform3D(cells=(3, 8, 8), magnitude=(1.0, 4.0, 4.0), p=0.5))),
     "test": InstancePipeline3D(),
 }

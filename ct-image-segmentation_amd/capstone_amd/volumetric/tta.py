@@ -130,6 +130,9 @@ class TestTimeAugmenter3D:
         self.views = [dict(v) for v in views]
         if not self.views:
             raise ValueError("TestTimeAugmenter3D: at least one view")
+        if any(v.get("deform") is not None for v in self.views):
+            raise ValueError("TestTimeAugmenter3D: a deformed view (params['deform'] is set) has no inverse matrix to merge its "
+                             "prediction through; draw the views from an Augment3D without deform")
         self.size = tuple(int(v) for v in size)
         if mode not in _MODES or interp not in _INTERPS:
             raise ValueError(f"TestTimeAugmenter3D: mode is one of {sorted(_MODES)}, interp one of {sorted(_INTERPS)}")

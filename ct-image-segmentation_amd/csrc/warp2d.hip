@@ -9,6 +9,7 @@
 // OpenCV's fixed-point rules are restated here as the tests' numpy restatement states them; nothing may be contracted:
 #pragma clang fp contract(off)
 #include "pipeline2d_common.h"
+#include "splitmix.h"
 
 namespace ctseg {
 
@@ -56,11 +57,7 @@ __device__ __forceinline__ int reflect_101(int p, int n) {
 
 // noise of field f at (i, j): one splitmix64 mix of seed + (counter + 1) * golden, counter = f << 40 | i << 20 | j; the top 53 bits
 __device__ __forceinline__ double field_noise(uint64_t seed, int f, int i, int j) {
-  uint64_t z = seed + ((((uint64_t)f << 40) | ((uint64_t)i << 20) | (uint64_t)j) + 1ull) * 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  const double u = (double)(z >> 11) * 0x1.0p-53;
+  const double u = splitmix64_unit(seed, ((uint64_t)f << 40) | ((uint64_t)i << 20) | (uint64_t)j);
   return 2.0 * u - 1.0;
 }
 

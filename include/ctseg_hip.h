@@ -465,6 +465,39 @@ int ctseg_augment3d_to_hwd(const void* image, int32_t image_dtype, const uint8_t
                            float cval, const int32_t* mask_src /* host */, int32_t window, float win_lo, float win_hi, float gain,
                            float bias, float* image_out, uint8_t* masks_out, uint8_t* labels_out, int64_t* hist, void* stream);
 
+/* Free-form deformation of that pass: a cubic B-spline over a coarse control lattice (Rueckert et al. 1999) is added to the
+ * sampling coordinate.  The lattice is made on the device from a seed: no upload, no synchronisation.  Every float operation below
+ * is one float32 rounding (double where it says so); nothing is contracted into an FMA.
+ *
+ * ctseg_deform3d_lattice fills lattice, DEVICE fp32 [3][Gd+3][Gh+3][Gw+3] (component c = 0: d, 1: h, 2: w displacement, in output
+ * voxels), for cells = (Gd, Gh, Gw) and magnitude[3], both HOST arrays:
+ *   lattice[c][i][j][k] = (float)((2 u - 1) * (double)magnitude[c]), u = (z >> 11) * 2^-53 in double, z the splitmix64 mix
+ *   (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31) of
+ *   seed + (((c << 60) | (i << 40) | (j << 20) | k) + 1) * 0x9E3779B97F4A7C15, all in uint64.
+ * Rejected: G_a < 1, G_a + 3 > 2^20, a magnitude that is negative or not finite, lattice_elems != 3 * prod(G_a + 3). */
+int ctseg_deform3d_lattice(int64_t seed, const int32_t* cells /* host, 3 */, const float* magnitude /* host, 3 */, float* lattice,
+                           int64_t lattice_elems, void* stream);
+
+/* ctseg_augment3d_to_hwd with that lattice (DEVICE) over cells = (Gd, Gh, Gw) (HOST) cells of the OUTPUT grid.  Inputs, outputs,
+ * limits and rules are those of ctseg_augment3d_to_hwd; rejected in addition: lattice or cells NULL, G_a < 1, 4 * G_a > out_a
+ * along d and w (a cell is at least 4 output voxels along the axes the kernel tiles, which bounds the lattice rows a tile touches),
+ * G_h > out_h.
+ *   - Per axis a of output voxel o = (od, oh, ow): g_a = (float)G_a / (float)out_a (formed on the host), u_a = (float)o_a * g_a,
+ *     i_a = min((int)floorf(u_a), G_a - 1), t_a = u_a - (float)i_a and, with s = 1 - t, the weights
+ *       B0 = ((s*s)*s) / 6,  B1 = ((((3*t - 6)*t)*t) + 4) / 6,  B2 = (((((-3*t + 3)*t) + 3)*t) + 1) / 6,  B3 = ((t*t)*t) / 6.
+ *   - Displacement, component c:
+ *       s_c = sum_{a=0..3} Bd[a] * ( sum_{b=0..3} Bw[b] * ( sum_{e=0..3} Bh[e] * lattice[c][id+a][ih+e][iw+b] ) ),
+ *     each sum starting from its first product and adding left to right.  h is innermost: a workgroup of the kernel has one h and
+ *     collapses that axis once for all its voxels.
+ *   - Sampling coordinate: q_a = (((A[a][0]*od + A[a][1]*oh) + A[a][2]*ow) + A[a][3]) + s_a.  From q on everything is
+ *     ctseg_augment3d_to_hwd: nearest and trilinear rules, border, window, gain / bias, masks, labels, hist.
+ * An all-zero lattice reproduces ctseg_augment3d_to_hwd bit for bit (q + 0 = q). */
+int ctseg_augment3d_deform_to_hwd(const void* image, int32_t image_dtype, const uint8_t* masks, int32_t K, int32_t D, int32_t H,
+                                  int32_t W, int32_t Do, int32_t Ho, int32_t Wo, const float* matrix /* host */, int32_t interp,
+                                  int32_t border, float cval, const int32_t* mask_src /* host */, int32_t window, float win_lo,
+                                  float win_hi, float gain, float bias, float* image_out, uint8_t* masks_out, uint8_t* labels_out,
+                                  int64_t* hist, const float* lattice, const int32_t* cells /* host, 3 */, void* stream);
+
 /* Test-time augmentation of the 3-D network: the prediction of one VIEW (the network's logits for an augmented copy of the scan)
  * is resampled onto a TARGET grid and added into an accumulator there; ctseg_tta_finish turns the accumulator into labels.
  * Inputs and layout:
