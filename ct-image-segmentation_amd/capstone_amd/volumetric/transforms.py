@@ -45,11 +45,11 @@ def _window_args(window):
     return (2 if shift else 1), float(level - (width // 2)), float(level + (width // 2))
 
 
-def resize3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor], size: Sequence[int], window=None,
-                    want_masks: bool = True, want_labels: bool = False):
-    """image (D,H,W) f32/i16/u8, masks (K,D,H,W) u8 -> image (H',W',D') fp32, masks (K,H',W',D') u8, labels (H',W',D') u8, hist (K+1)"""
+def _prepare_call(image, masks, size, who, want_masks, want_labels):
+    """the inputs and outputs of one resample call -> image (D,H,W) contiguous and its dtype code, masks (K,D,H,W) uint8
+    contiguous and K, (D, H, W, D', H', W'), and the outputs (image, masks, labels, hist), None where not asked for"""
     ref = image if image is not None else masks
-    nat.require_gpu(ref, "Resize3D")
+    nat.require_gpu(ref, who)
     D, H, W = ref.shape[-3:]
     Do, Ho, Wo = (int(v) for v in size)
     dev = ref.device
@@ -69,10 +69,31 @@ def resize3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor]
         if want_labels:
             lab = torch.empty((Ho, Wo, Do), dtype=torch.uint8, device=dev)
             hist = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-    wmode, lo, hi = _window_args(window)
-    nat.call("ctseg_resize3d_to_hwd", nat.ptr(image), code, nat.ptr(masks), K, D, H, W, Do, Ho, Wo, wmode, lo, hi,
-             nat.ptr(img_out), nat.ptr(m_out), nat.ptr(lab), nat.ptr(hist))
-    return img_out, m_out, lab, hist
+    return image, code, masks, K, (D, H, W, Do, Ho, Wo), (img_out, m_out, lab, hist)
+
+
+def _c_matrix(matrix):
+    """a (3, 4) matrix as the 12 floats an entry reads; the caller keeps the object alive across the call"""
+    return (ctypes.c_float * 12)(*np.asarray(matrix, dtype=np.float32).reshape(12).tolist())
+
+
+def _c_permutation(values, n, who, what):
+    """``values`` (None: the identity) as the ``n`` int32 an entry reads, or None; ``who`` names the argument and ``what`` the
+    things it permutes in the message.  The caller keeps the object alive across the call"""
+    if values is None:
+        return None
+    src = [int(v) for v in values]
+    if len(src) != n:
+        raise nat.NativeError(f"{who} has {len(src)} entries for {n} {what}")
+    return (ctypes.c_int32 * n)(*src)
+
+
+def resize3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor], size: Sequence[int], window=None,
+                    want_masks: bool = True, want_labels: bool = False):
+    """image (D,H,W) f32/i16/u8, masks (K,D,H,W) u8 -> image (H',W',D') fp32, masks (K,H',W',D') u8, labels (H',W',D') u8, hist (K+1)"""
+    image, code, masks, K, dims, outs = _prepare_call(image, masks, size, "Resize3D", want_masks, want_labels)
+    nat.call("ctseg_resize3d_to_hwd", nat.ptr(image), code, nat.ptr(masks), K, *dims, *_window_args(window), *(nat.ptr(t) for t in outs))
+    return outs
 
 
 _BORDERS = {"constant": 0, "edge": 1}
@@ -118,45 +139,19 @@ def augment3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor
     ``deform`` = {"seed", "cells", "magnitude"} (``Deform3D``): the device fills the control lattice from the seed and the pass
     adds its B-spline displacement to the sampling point, two launches instead of one.
     -> image (H',W',D') fp32, masks (K,H',W',D') u8, labels (H',W',D') u8, hist (K+1)"""
-    ref = image if image is not None else masks
-    nat.require_gpu(ref, "Augment3D")
-    D, H, W = ref.shape[-3:]
-    Do, Ho, Wo = (int(v) for v in size)
-    dev = ref.device
-    img_out = m_out = lab = hist = None
-    code, K = nat.F32, 0
-    if image is not None:
-        image, code = _image_code(image.reshape(D, H, W))
-        img_out = torch.empty((Ho, Wo, Do), dtype=torch.float32, device=dev)
-    if masks is not None:
-        masks = masks.reshape(-1, D, H, W)
-        if masks.dtype != torch.uint8:
-            masks = masks.to(torch.uint8)
-        masks = masks.contiguous()
-        K = masks.shape[0]
-        if want_masks:
-            m_out = torch.empty((K, Ho, Wo, Do), dtype=torch.uint8, device=dev)
-        if want_labels:
-            lab = torch.empty((Ho, Wo, Do), dtype=torch.uint8, device=dev)
-            hist = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-    wmode, lo, hi = _window_args(window)
-    mat = (ctypes.c_float * 12)(*np.asarray(matrix, dtype=np.float32).reshape(12).tolist())
-    src = None
-    if mask_src is not None:
-        src = [int(v) for v in mask_src]
-        if len(src) != K:
-            raise nat.NativeError(f"Augment3D: mask_src has {len(src)} entries for {K} mask channels")
-        src = (ctypes.c_int32 * K)(*src)
-    args = (nat.ptr(image), code, nat.ptr(masks), K, D, H, W, Do, Ho, Wo,
+    image, code, masks, K, dims, outs = _prepare_call(image, masks, size, "Augment3D", want_masks, want_labels)
+    mat = _c_matrix(matrix)
+    src = _c_permutation(mask_src, K, "Augment3D: mask_src", "mask channels")
+    args = (nat.ptr(image), code, nat.ptr(masks), K, *dims,
             ctypes.addressof(mat), _INTERPS.get(interp, interp), _BORDERS.get(border, border), float(cval),
-            ctypes.addressof(src) if src is not None else None, wmode, lo, hi, float(gain), float(bias),
-            nat.ptr(img_out), nat.ptr(m_out), nat.ptr(lab), nat.ptr(hist))
+            ctypes.addressof(src) if src is not None else None, *_window_args(window), float(gain), float(bias),
+            *(nat.ptr(t) for t in outs))
     if deform is None:
         nat.call("ctseg_augment3d_to_hwd", *args)
     else:
-        lattice, cells = _lattice(deform, dev)
+        lattice, cells = _lattice(deform, (image if image is not None else masks).device)
         nat.call("ctseg_augment3d_deform_to_hwd", *args, nat.ptr(lattice), ctypes.addressof(cells))
-    return img_out, m_out, lab, hist
+    return outs
 
 
 def _axis_ranges(v, what):

@@ -24,7 +24,7 @@ import torch
 
 from .. import _native as nat
 from ..models.losses import _as_cl
-from .transforms import _INTERPS, Augment3D, augment3d_to_hwd
+from .transforms import _INTERPS, Augment3D, _c_matrix, _c_permutation, augment3d_to_hwd
 
 _MODES = {"logits": 0, "probabilities": 1}
 _LAYOUTS = {"hwd": 0, "dhw": 1}
@@ -55,13 +55,8 @@ def tta_accumulate(acc: torch.Tensor, logits: torch.Tensor, matrix, chan_src=Non
         raise nat.NativeError(f"tta_accumulate: acc is a contiguous fp32 tensor of {Dt * Ht * Wt} rows of {acc_ld}; got "
                               f"{acc.dtype} {tuple(acc.shape)}")
     ptr, ld, _keep = _as_cl(logits if logits.dtype == torch.float32 else logits.float())
-    mat = (ctypes.c_float * 12)(*np.asarray(matrix, dtype=np.float32).reshape(12).tolist())
-    src = None
-    if chan_src is not None:
-        src = [int(v) for v in chan_src]
-        if len(src) != C:
-            raise nat.NativeError(f"tta_accumulate: chan_src has {len(src)} entries for {C} channels")
-        src = (ctypes.c_int32 * C)(*src)
+    mat = _c_matrix(matrix)
+    src = _c_permutation(chan_src, C, "tta_accumulate: chan_src", "channels")
     nat.call("ctseg_tta_accumulate", ptr, ld, C, D, H, W, ctypes.addressof(mat), ctypes.addressof(src) if src is not None else None,
              float(weight), _MODES.get(mode, mode), _INTERPS.get(interp, interp), Dt, Ht, Wt, _LAYOUTS.get(layout, layout),
              nat.ptr(acc), acc_ld)

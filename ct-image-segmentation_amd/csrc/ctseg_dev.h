@@ -299,6 +299,16 @@ template <unsigned ACCEPT = ANY_STORAGE, class F> static inline bool with_dtype(
   return false;
 }
 
+// The raw-image dtypes of the input pipelines (CTSEG_F32 / CTSEG_I16 / CTSEG_U8), and their element types in the same style:
+// calls f(float{}), f(short{}) or f(uint8_t{}) and returns true; any other code calls nothing and returns false
+static inline bool is_raw_dtype(int dtype) { return dtype == CTSEG_F32 || dtype == CTSEG_I16 || dtype == CTSEG_U8; }
+template <class F> static inline bool with_raw_dtype(int dtype, F&& f) {
+  if (dtype == CTSEG_F32) return f(float{}), true;
+  if (dtype == CTSEG_I16) return f(short{}), true;
+  if (dtype == CTSEG_U8) return f(uint8_t{}), true;
+  return false;
+}
+
 static inline int ilog_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 }  // namespace ctseg

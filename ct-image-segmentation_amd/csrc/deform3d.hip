@@ -1,12 +1,12 @@
 // Free-form deformation in the 3-D augmentation pass: a cubic B-spline over a coarse control lattice (Rueckert-style) is added to the
-// sampling coordinate of ctseg_augment3d_to_hwd; from that coordinate on the pass is unchanged (augment3d_tile.h).  The rules are in
+// sampling coordinate of ctseg_augment3d_to_hwd; from that coordinate on the pass is unchanged (resample3d_tile.h).  The rules are in
 // include/ctseg_hip.h (ctseg_deform3d_lattice, ctseg_augment3d_deform_to_hwd).
 //   lattice  one thread per control point: a counter hash of the seed (splitmix.h), scaled by the axis' magnitude.  No upload.
 //   pass     the workgroup (one h) collapses the lattice's h axis once into an LDS slab of at most 12 x 20 rows per component; a
 //            voxel then takes 16 taps per component from it, along w inside and along d outside: the rule's summation order.
 // Every float operation is one float32 rounding: nothing may be contracted into an FMA.
 #pragma clang fp contract(off)
-#include "augment3d_tile.h"
+#include "resample3d_tile.h"
 #include "splitmix.h"
 
 namespace ctseg {
@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void augment3d_deform_hwd_kernel(const TI* __r
                                                                    const Deform3dArgs dg, float* __restrict__ image_out,
                                                                    uint8_t* __restrict__ masks_out, uint8_t* __restrict__ labels_out,
                                                                    unsigned long long* __restrict__ hist) {
-  augment3d_tile<TI, INTERP, true>(image, masks, p, image_out, masks_out, labels_out, hist, lattice, dg);
+  resample3d_tile<Coord::LATTICE, TI, INTERP>(image, masks, p, image_out, masks_out, labels_out, hist, lattice, dg);
 }
 
 }  // namespace ctseg
@@ -79,20 +79,11 @@ extern "C" int ctseg_augment3d_deform_to_hwd(const void* image, int32_t image_dt
   Deform3dArgs dg;
   dg.Gd = cells[0], dg.Gh = cells[1], dg.Gw = cells[2];
   dg.gd = (float)cells[0] / (float)Do, dg.gh = (float)cells[1] / (float)Ho, dg.gw = (float)cells[2] / (float)Wo;
-  hipStream_t st = (hipStream_t)stream;
-#define CTSEG_DF_LAUNCH(TI)                                                                                                          \
-  do {                                                                                                                               \
-    if (interp)                                                                                                                      \
-      hipLaunchKernelGGL((augment3d_deform_hwd_kernel<TI, 1>), grid, dim3(256), 0, st, (const TI*)image, masks, p, lattice, dg,      \
-                         image_out, masks_out, labels_out, (unsigned long long*)hist);                                               \
-    else                                                                                                                             \
-      hipLaunchKernelGGL((augment3d_deform_hwd_kernel<TI, 0>), grid, dim3(256), 0, st, (const TI*)image, masks, p, lattice, dg,      \
-                         image_out, masks_out, labels_out, (unsigned long long*)hist);                                               \
-  } while (0)
-  if (image_dtype == CTSEG_F32) CTSEG_DF_LAUNCH(float);
-  else if (image_dtype == CTSEG_I16) CTSEG_DF_LAUNCH(short);
-  else CTSEG_DF_LAUNCH(uint8_t);
-#undef CTSEG_DF_LAUNCH
+  with_pixel_and_interp(image_dtype, interp, [&](auto ti, auto ic) {
+    using TI = decltype(ti);
+    hipLaunchKernelGGL((augment3d_deform_hwd_kernel<TI, decltype(ic)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const TI*)image,
+                       masks, p, lattice, dg, image_out, masks_out, labels_out, (unsigned long long*)hist);
+  });
   CTSEG_LAUNCH_CHECK("augment3d_deform_to_hwd");
   return 0;
 }

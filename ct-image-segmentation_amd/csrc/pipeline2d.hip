@@ -196,8 +196,7 @@ extern "C" int ctseg_pipeline2d_batch(const void* image_store, int32_t image_dty
   CTSEG_REQUIRE(mode == P2_CROP || mode == P2_RESIZE, "pipeline2d_batch: mode %d", mode);
   CTSEG_REQUIRE(!image_store || (image_out && C >= 1 && C <= P2_CMAX && win_lo && win_hi && image_elems > 0),
                 "pipeline2d_batch: an image needs image_out and 1..%d windows", P2_CMAX);
-  CTSEG_REQUIRE(!image_store || image_dtype == CTSEG_F32 || image_dtype == CTSEG_I16 || image_dtype == CTSEG_U8,
-                "pipeline2d_batch: image dtype %d", image_dtype);
+  CTSEG_REQUIRE(!image_store || is_raw_dtype(image_dtype), "pipeline2d_batch: image dtype %d", image_dtype);
   CTSEG_REQUIRE((mean == nullptr) == (denom == nullptr), "pipeline2d_batch: mean and denom come together");
   CTSEG_REQUIRE(!mask_store || (K > 0 && K <= P2_KMAX && mask_bytes > 0 && (masks_out || labels_out || present)),
                 "pipeline2d_batch: masks need K <= %d and an output", P2_KMAX);
@@ -212,20 +211,17 @@ extern "C" int ctseg_pipeline2d_batch(const void* image_store, int32_t image_dty
   int64_t blocks = (ngroups + 255) / 256;
   if (blocks > 64) blocks = 64;
   const dim3 grid((unsigned)blocks, B);
-  hipStream_t st = (hipStream_t)stream;
-#define CTSEG_P2_LAUNCH(TI, MODE)                                                                                                   \
-  hipLaunchKernelGGL((pipeline2d_kernel<TI, MODE>), grid, dim3(256), 0, st, (const TI*)image_store, image_elems, mask_store, mask_bytes, \
-                     table, K, Ho, Wo, w, image_out, masks_out, labels_out, (unsigned long long*)hist, present)
-  if (mode == P2_CROP) {
-    if (image_dtype == CTSEG_I16) CTSEG_P2_LAUNCH(short, P2_CROP);
-    else if (image_dtype == CTSEG_U8) CTSEG_P2_LAUNCH(uint8_t, P2_CROP);
-    else CTSEG_P2_LAUNCH(float, P2_CROP);
-  } else {
-    if (image_dtype == CTSEG_I16) CTSEG_P2_LAUNCH(short, P2_RESIZE);
-    else if (image_dtype == CTSEG_U8) CTSEG_P2_LAUNCH(uint8_t, P2_RESIZE);
-    else CTSEG_P2_LAUNCH(float, P2_RESIZE);
-  }
-#undef CTSEG_P2_LAUNCH
+  // (a call without an image may carry any dtype code: one that names no pixel type takes the float kernel)
+  with_raw_dtype(is_raw_dtype(image_dtype) ? image_dtype : CTSEG_F32, [&](auto ti) {
+    using TI = decltype(ti);
+    auto launch = [&](auto md) {
+      hipLaunchKernelGGL((pipeline2d_kernel<TI, decltype(md)::value>), grid, dim3(256), 0, (hipStream_t)stream, (const TI*)image_store,
+                         image_elems, mask_store, mask_bytes, table, K, Ho, Wo, w, image_out, masks_out, labels_out,
+                         (unsigned long long*)hist, present);
+    };
+    if (mode == P2_CROP) launch(std::integral_constant<int, P2_CROP>{});
+    else launch(std::integral_constant<int, P2_RESIZE>{});
+  });
   CTSEG_LAUNCH_CHECK("pipeline2d_batch");
   return 0;
 }

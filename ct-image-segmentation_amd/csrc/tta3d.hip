@@ -9,9 +9,7 @@
 // the same workgroup.  The lanes' fast axis is the accumulator's contiguous one (d for layout 0, w for layout 1).
 // Every float operation is one float32 rounding: nothing may be contracted into an FMA.
 #pragma clang fp contract(off)
-#include <cmath>
-
-#include "ctseg_dev.h"
+#include "affine3d.h"
 
 namespace ctseg {
 
@@ -19,24 +17,21 @@ constexpr int TTA_T = 16, TTA_CMAX = 16;
 
 struct TtaArgs {
   int C, D, H, W, Dt, Ht, Wt, layout, mode, ld, acc_ld, permute;
-  float a[12];                       // row-major 3 x 4, rows and columns ordered d, h, w (read with constant indices only)
+  Affine3d m;                        // target voxel -> the point of the view it samples
   float weight;
   unsigned long long src;            // 4 bits per accumulator column: the view channel it takes
 };
 
-__device__ __forceinline__ float tta_lerp(float x, float y, float t) { return x + t * (y - x); }
-
-// nearest index of one axis: floorf(q + 0.5f) clamped into [-1, n] before the conversion, so that no float outside the int range
-// is converted; inside = the index lies in [0, n)
+// nearest index of one axis; inside = it lies in [0, n)
 __device__ __forceinline__ int tta_near(float q, int n, bool& inside) {
-  const int r = (int)fminf(fmaxf(floorf(q + 0.5f), -1.f), (float)n);
+  const int r = affine3d_nearest(q, n);
   inside = r >= 0 && r < n;
   return r;
 }
 
-// corner b + c of one axis, clamped to the volume (b clamped into [-2, n] first, as above)
+// corner b + c of one axis, clamped to the volume
 __device__ __forceinline__ int tta_corner(float b, int c, int n) {
-  const int r = (int)fminf(fmaxf(b, -2.f), (float)n) + c;
+  const int r = (int)affine3d_corner(b, n) + c;
   return r < 0 ? 0 : (r > n - 1 ? n - 1 : r);
 }
 
@@ -77,10 +72,8 @@ __global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __rest
   const int tw = (blockIdx.x / ndt) * TTA_T + (p.layout == 0 ? slow : fast);
   const int th = blockIdx.y;
   if (td >= Dt || tw >= Wt) return;
-  const float fd = (float)td, fh = (float)th, fw = (float)tw;
-  const float qd = ((p.a[0] * fd + p.a[1] * fh) + p.a[2] * fw) + p.a[3];
-  const float qh = ((p.a[4] * fd + p.a[5] * fh) + p.a[6] * fw) + p.a[7];
-  const float qw = ((p.a[8] * fd + p.a[9] * fh) + p.a[10] * fw) + p.a[11];
+  float qd, qh, qw;
+  affine3d_point(p.m, (float)td, (float)th, (float)tw, qd, qh, qw);
   bool okd, okh, okw;
   const int rd = tta_near(qd, D, okd), rh = tta_near(qh, H, okh), rw = tta_near(qw, W, okw);
   if (!(okd && okh && okw)) return;         // not covered by this view: the row is not touched
@@ -106,13 +99,13 @@ __global__ __launch_bounds__(256) void tta_accumulate_kernel(const float* __rest
         tta_row<N4>(logits, (ih[b] + iw[0]) * D + id[a], p.ld, x);
         tta_row<N4>(logits, (ih[b] + iw[1]) * D + id[a], p.ld, y);
 #pragma unroll
-        for (int c = 0; c < 4 * N4; ++c) ch[b][c] = tta_lerp(x[c], y[c], gw);
+        for (int c = 0; c < 4 * N4; ++c) ch[b][c] = affine3d_lerp(x[c], y[c], gw);
       }
 #pragma unroll
-      for (int c = 0; c < 4 * N4; ++c) cd[a][c] = tta_lerp(ch[0][c], ch[1][c], gh);
+      for (int c = 0; c < 4 * N4; ++c) cd[a][c] = affine3d_lerp(ch[0][c], ch[1][c], gh);
     }
 #pragma unroll
-    for (int c = 0; c < 4 * N4; ++c) z[c] = tta_lerp(cd[0][c], cd[1][c], gd);
+    for (int c = 0; c < 4 * N4; ++c) z[c] = affine3d_lerp(cd[0][c], cd[1][c], gd);
   }
   tta_value<N4>(z, C, p.mode);
   if (p.permute) {
@@ -213,26 +206,10 @@ extern "C" int ctseg_tta_accumulate(const float* logits, int32_t ld, int32_t C, 
   CTSEG_REQUIRE(std::isfinite(weight) && weight > 0.f, "tta_accumulate: weight is not a finite positive number");
   TtaArgs p;
   const int tgt[3] = {Dt, Ht, Wt};
-  for (int a = 0; a < 3; ++a) {
-    // finite entries, and coordinates that stay far inside float32 over the whole target grid: no inf - inf in the kernel
-    double reach = 0.0;
-    for (int j = 0; j < 4; ++j) {
-      const float v = matrix[a * 4 + j];
-      CTSEG_REQUIRE(std::isfinite(v), "tta_accumulate: matrix entry [%d][%d] is not finite", a, j);
-      reach += fabs((double)v) * (j < 3 ? (double)(tgt[j] - 1) : 1.0);
-      p.a[a * 4 + j] = v;
-    }
-    CTSEG_REQUIRE(reach < 1e30, "tta_accumulate: matrix row %d sends the target grid beyond 1e30", a);
-  }
-  p.src = 0, p.permute = 0;
-  unsigned seen = 0;
-  for (int k = 0; k < C; ++k) {
-    const int s = chan_src ? chan_src[k] : k;
-    CTSEG_REQUIRE(s >= 0 && s < C && !((seen >> s) & 1u), "tta_accumulate: chan_src is not a permutation of 0..%d (entry %d = %d)", C - 1, k, s);
-    seen |= 1u << s;
-    p.src |= (unsigned long long)s << (4 * k);
-    p.permute |= s != k;
-  }
+  if (int rc = affine3d_check("tta_accumulate", matrix, tgt, "target grid", p.m)) return rc;
+  bool identity;
+  if (int rc = pack_permutation("tta_accumulate", "chan_src", chan_src, C, p.src, identity)) return rc;
+  p.permute = !identity;
   p.C = C, p.D = D, p.H = H, p.W = W, p.Dt = Dt, p.Ht = Ht, p.Wt = Wt, p.layout = layout, p.mode = mode, p.ld = ld, p.acc_ld = acc_ld;
   p.weight = weight;
   dim3 grid(((Dt + TTA_T - 1) / TTA_T) * ((Wt + TTA_T - 1) / TTA_T), Ht);

@@ -339,8 +339,7 @@ extern "C" int ctseg_pipeline2d_warp_batch(const void* image_store, int32_t imag
   CTSEG_REQUIRE(launches > 0 && launches <= (W2_FIELDS | W2_PASS1 | W2_PASS2), "%s: launches %d", who, launches);
   CTSEG_REQUIRE(!image_store || (image_out && C >= 1 && C <= P2_CMAX && win_lo && win_hi && image_elems > 0),
                 "%s: an image needs image_out and 1..%d windows", who, P2_CMAX);
-  CTSEG_REQUIRE(!image_store || image_dtype == CTSEG_F32 || image_dtype == CTSEG_I16 || image_dtype == CTSEG_U8, "%s: image dtype %d", who,
-                image_dtype);
+  CTSEG_REQUIRE(!image_store || is_raw_dtype(image_dtype), "%s: image dtype %d", who, image_dtype);
   CTSEG_REQUIRE((mean == nullptr) == (denom == nullptr), "%s: mean and denom come together", who);
   CTSEG_REQUIRE(!mask_store || (K > 0 && K <= P2_KMAX && mask_bytes > 0 && (masks_out || labels_out || present)),
                 "%s: masks need K <= %d and an output", who, P2_KMAX);
@@ -375,14 +374,12 @@ extern "C" int ctseg_pipeline2d_warp_batch(const void* image_store, int32_t imag
   hipStream_t st = (hipStream_t)stream;
   if ((launches & W2_FIELDS) && n_slots > 0)
     hipLaunchKernelGGL(warp2d_fields_kernel, dim3(2, B), dim3(W2_FIELD_THREADS), 0, st, table, d, gauss_w, radius, alpha, field_tmp, fields);
-  if (launches & W2_PASS1) {
-#define CTSEG_W2_PASS1(TI) \
-  hipLaunchKernelGGL((warp2d_pass1_kernel<TI>), grid, dim3(256), 0, st, (const TI*)image_store, mask_store, table, d, w, inter_img, inter_msk)
-    if (image_dtype == CTSEG_I16) CTSEG_W2_PASS1(short);
-    else if (image_dtype == CTSEG_U8) CTSEG_W2_PASS1(uint8_t);
-    else CTSEG_W2_PASS1(float);
-#undef CTSEG_W2_PASS1
-  }
+  if (launches & W2_PASS1)      // (a call without an image may carry any dtype code: one that names no pixel type takes the float kernel)
+    with_raw_dtype(is_raw_dtype(image_dtype) ? image_dtype : CTSEG_F32, [&](auto ti) {
+      using TI = decltype(ti);
+      hipLaunchKernelGGL((warp2d_pass1_kernel<TI>), grid, dim3(256), 0, st, (const TI*)image_store, mask_store, table, d, w, inter_img,
+                         inter_msk);
+    });
   if (launches & W2_PASS2)
     hipLaunchKernelGGL(warp2d_pass2_kernel, grid, dim3(256), 0, st, image_store ? inter_img : nullptr, inter_msk, table, d, w, fields, xx, yy,
                        image_out, masks_out, labels_out, (unsigned long long*)hist, present);

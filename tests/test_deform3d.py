@@ -412,6 +412,50 @@ def test_entries_reject_bad_arguments_without_a_device():
     assert bytes(buf) == b"\x5a" * 4096                          # nothing was written
 
 
+# the checks that ctseg_resize3d_to_hwd, ctseg_augment3d_to_hwd and ctseg_augment3d_deform_to_hwd share, on a 2 x 2 x 2 volume:
+# what is wrong with the call, and the words the message carries
+SHARED_REFUSALS = [
+    ({"dims": (0, 2, 2, 2, 2, 2)}, "bad geometry"), ({"dims": (2, 2, 2, 2, 0, 2)}, "bad geometry"), ({"dims": (2, -1, 2, 2, 2, 2)}, "bad geometry"),
+    ({"dims": (2, 2, 2, 2, 2, -3)}, "bad geometry"), ({"image_out": None}, "image without image_out"), ({"Kn": 16}, "K <= 15"),
+    ({"hist": True, "labels_out": None}, "hist needs labels_out"), ({"window": (3, 0.0, 1.0)}, "bad window"),
+    ({"window": (1, 1.0, 1.0)}, "bad window"), ({"window": (2, 2.0, 1.0)}, "bad window"), ({"dtype": 1}, "image dtype 1"),
+    ({"dtype": 4}, "image dtype 4"), ({"dtype": -1}, "image dtype -1"),
+]
+SHARED_ENTRIES = ["resize3d_to_hwd", "augment3d_to_hwd", "augment3d_deform_to_hwd"]
+
+
+def shared_refusal(entry, dims=(2, 2, 2, 2, 2, 2), image_out=True, labels_out=True, hist=False, Kn=K, window=(0, 0.0, 1.0), dtype=nat.F32):
+    """one refused call of ``entry``, everything else about it in order -> (rc, message)"""
+    L = nat.lib()
+    buf = (ctypes.c_char * 64)()
+    p = ctypes.addressof(buf)
+    outs = (p if image_out else None, p, p if labels_out else None, p if hist else None)
+    A = (ctypes.c_float * 12)(*A3.identity().reshape(-1).tolist())
+    c = (ctypes.c_int32 * 3)(1, 1, 1)
+    if entry == "resize3d_to_hwd":
+        rc = L.ctseg_resize3d_to_hwd(p, dtype, p, Kn, *dims, *window, *outs, None)
+    else:
+        args = (p, dtype, p, Kn, *dims, ctypes.addressof(A), 1, 0, 0.0, None, *window, 1.0, 0.0, *outs)
+        if entry == "augment3d_to_hwd":
+            rc = L.ctseg_augment3d_to_hwd(*args, None)
+        else:
+            rc = L.ctseg_augment3d_deform_to_hwd(*args, p, ctypes.addressof(c), None)
+    return rc, L.ctseg_last_error().decode()
+
+
+def test_resize_entry_rejects_bad_arguments_without_a_device():
+    for kw, words in SHARED_REFUSALS:
+        rc, msg = shared_refusal("resize3d_to_hwd", **kw)
+        assert rc < 0 and words in msg, (kw, msg)
+
+
+@pytest.mark.parametrize("entry", SHARED_ENTRIES)
+def test_shared_refusals_name_their_own_entry(entry):
+    for kw, words in SHARED_REFUSALS:
+        rc, msg = shared_refusal(entry, **kw)
+        assert rc < 0 and msg.startswith(entry + ": ") and words in msg, (kw, msg)
+
+
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
 def on_device(shape, code):
     image, masks = inputs(shape, code)
