@@ -1,8 +1,10 @@
 """Drop-in for reference capstone/volumetric/data_module.py: ``MiccaiDataModule3D`` over the device-fed ``MiccaiDataset3D``.
 
 ``transform_degree`` 0 is the reference's only preset (resize + permute); 1 adds the device augmentation of
-``transforms.augmented_degree_1`` on the "train" side (``transforms.augmented_degree_2``, which adds the free-form deformation, goes
-to ``get_miccai_3d`` / ``MiccaiDataset3D`` directly).  The loaders are plain iterables of device batches
+``transforms.augmented_degree_1`` on the "train" side; 3 is ``transforms.augmented_degree_3``: the soft-tissue window on both sides
+and, on the "train" side, degree 1 plus the free-form deformation and the intensity stage (blur, noise, gamma).
+``transforms.augmented_degree_2``, degree 1 plus the deformation on the unwindowed image, has no number here: it goes to
+``get_miccai_3d`` / ``MiccaiDataset3D`` directly.  The loaders are plain iterables of device batches
 ``(images, masks, mask_indicator)`` (``dist_maps=True``: plus the distance maps): a shuffled (train) or sequential order cut into
 ``batch_size`` pieces, every instance one ``MiccaiDataset3D.__getitem__`` (one launch) and every piece one ``collate_3d``.  No
 workers, no pinned memory.  The class derives from ``pl.LightningDataModule`` only when Lightning is importable.
@@ -16,7 +18,7 @@ from .base_trainer import pl
 from .datasets import collate_3d, get_miccai_3d
 from .transforms import InstancePipeline3D
 
-DEGREE = {0: transforms.windowed_degree_0, 1: transforms.augmented_degree_1}
+DEGREE = {0: transforms.windowed_degree_0, 1: transforms.augmented_degree_1, 3: transforms.augmented_degree_3}
 
 
 class InstanceBatches:

@@ -16,6 +16,9 @@ zoom, shift and mirror as one 3 x 4 matrix, drawn on the host and applied by ``c
 (``augment3d_to_hwd``).  A left-right mirror swaps the paired structures' mask channels, see ``Augment3D.channel_src``.
 ``Deform3D`` adds a non-rigid part to that pass: a cubic B-spline free-form deformation over a coarse control lattice, which the
 device fills from a drawn seed (``ctseg_deform3d_lattice``, then ``ctseg_augment3d_deform_to_hwd``).
+``Intensity3D`` is the second, small stage on that pass' (H', W', D') output: Gaussian blur, additive Gaussian noise and a gamma
+curve (``intensity3d`` -> ``ctseg_intensity3d``), which cannot go into the gather pass: a blur needs a voxel's neighbours on the
+output grid, and noise and gamma come after the window.
 There is no CPU fallback: CPU tensors raise ``NativeError``.
 """
 import ctypes
@@ -26,6 +29,7 @@ import torch
 
 from .. import _native as nat
 from ..data.utils import compute_distance_map
+from ..transforms.transforms_2d import WINDOWING_CONFIG
 
 _IMG_DTYPES = {torch.float32: nat.F32, torch.int16: nat.I16, torch.uint8: nat.U8}
 
@@ -154,13 +158,84 @@ def augment3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor
     return outs
 
 
-def _axis_ranges(v, what):
+_MAX_SIGMA, _MAX_RADIUS = 4.0, 12
+
+
+def gaussian_taps(sigma: float):
+    """(r, taps) of one blurred axis: r = ceil(3 sigma) and the r + 1 float32 taps exp(-k^2 / (2 sigma^2)), k = 0..r, normalised in
+    float64 so that w_0 + 2 sum_{k>=1} w_k = 1 and rounded once"""
+    sigma = float(sigma)
+    if not 0.0 < sigma <= _MAX_SIGMA:
+        raise ValueError(f"intensity3d: sigma {sigma} is outside (0, {_MAX_SIGMA}] (0 skips the axis)")
+    r = int(np.ceil(3.0 * sigma))
+    k = np.arange(r + 1, dtype=np.float64)
+    w = np.exp(-(k * k) / (2.0 * sigma * sigma))
+    return r, (w / (w[0] + 2.0 * w[1:].sum())).astype(np.float32)
+
+
+def _check_range(value_range, who):
+    if value_range is None:
+        return None
+    lo, hi = (float(v) for v in value_range)
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"{who}: value_range is (lo, hi), finite, lo < hi")
+    return lo, hi
+
+
+def _check_intensity(sigma, noise_std, noise_seed, gamma, value_range, who="intensity3d"):
+    """the stage's parameters as the entry takes them, or ``ValueError``: sigma per axis d, h, w, each 0 (axis skipped) or in
+    (0, 4]; noise_std finite and >= 0; a seed of 64 bits; gamma in [0.25, 4] over a value range, or exactly 1 without one"""
+    sigma = tuple(float(v) for v in sigma)
+    if len(sigma) != 3 or not all(0.0 <= v <= _MAX_SIGMA for v in sigma):
+        raise ValueError(f"{who}: sigma has one entry per axis d, h, w, each in [0, {_MAX_SIGMA}]")
+    noise_std, gamma, noise_seed = float(noise_std), float(gamma), int(noise_seed)
+    if not (np.isfinite(noise_std) and noise_std >= 0.0):
+        raise ValueError(f"{who}: noise_std is finite and not negative")
+    if not -2 ** 63 <= noise_seed < 2 ** 64:
+        raise ValueError(f"{who}: noise_seed has 64 bits")
+    value_range = _check_range(value_range, who)
+    if value_range is None and gamma != 1.0:
+        raise ValueError(f"{who}: gamma {gamma} needs a value_range (lo, hi)")
+    if not 0.25 <= gamma <= 4.0:
+        raise ValueError(f"{who}: gamma {gamma} is outside [0.25, 4]")
+    return sigma, noise_std, noise_seed - 2 ** 64 if noise_seed >= 2 ** 63 else noise_seed, gamma, value_range
+
+
+def intensity3d(image: torch.Tensor, sigma=(0, 0, 0), noise_std: float = 0.0, noise_seed: int = 0, gamma: float = 1.0,
+                value_range=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the intensity stage on one (H', W', D') fp32 device tensor: blur, then noise, then gamma (include/ctseg_hip.h,
+    ``ctseg_intensity3d``, has the rules).  ``sigma`` = the Gaussian's sigma in voxels per axis d, h, w: 0 skips an axis, otherwise
+    0 < sigma <= 4; ``noise_std`` > 0 adds ``noise_std * n(noise_seed, voxel index)``, a stateless standard normal field;
+    ``value_range`` = (lo, hi) switches the gamma step on: the value is clamped to the range and sent through
+    ``lo + (hi - lo) * t ** gamma`` (``gamma`` = 1: the clamp alone).  ``out`` = None (a new tensor), ``image`` itself (in place)
+    or another tensor of its shape.  One launch per blurred axis with the rest folded into the last of them; no scratch volume.
+    Bad parameters raise ``ValueError``, a CPU tensor ``NativeError``"""
+    sigma, noise_std, noise_seed, gamma, value_range = _check_intensity(sigma, noise_std, noise_seed, gamma, value_range)
+    if out is None:
+        out = torch.empty_like(image, memory_format=torch.contiguous_format)
+    for t, what in ((image, "image"), (out, "out")):
+        if t.dim() != 3 or t.dtype != torch.float32 or not t.is_contiguous() or t.shape != image.shape or t.device != image.device:
+            raise ValueError(f"intensity3d: {what} is a contiguous float32 (H', W', D') tensor; image and out agree in shape and device")
+    nat.require_gpu(image, "intensity3d")
+    radius, taps = (ctypes.c_int32 * 3)(), (ctypes.c_float * (3 * (_MAX_RADIUS + 1)))()
+    for a, s in enumerate(sigma):
+        if s > 0.0:
+            radius[a], w = gaussian_taps(s)
+            taps[a * (_MAX_RADIUS + 1):a * (_MAX_RADIUS + 1) + len(w)] = w.tolist()
+    Ho, Wo, Do = image.shape
+    lo, hi = value_range if value_range is not None else (0.0, 0.0)
+    nat.call("ctseg_intensity3d", nat.ptr(image), nat.ptr(out), Do, Ho, Wo, ctypes.addressof(radius), ctypes.addressof(taps), noise_std,
+             noise_seed, int(value_range is not None), lo, hi, gamma)
+    return out
+
+
+def _axis_ranges(v, what, who="Augment3D"):
     """(lo, hi) for all three axes, or ((lo, hi), (lo, hi), (lo, hi)) per axis d, h, w -> (3, 2) float64"""
     a = np.asarray(v, dtype=np.float64)
     if a.shape == (2,):
         a = np.tile(a, (3, 1))
     if a.shape != (3, 2) or (a[:, 0] > a[:, 1]).any():
-        raise ValueError(f"Augment3D: {what} is (lo, hi) or one (lo, hi) per axis, lo <= hi")
+        raise ValueError(f"{who}: {what} is (lo, hi) or one (lo, hi) per axis, lo <= hi")
     return a
 
 
@@ -183,6 +258,51 @@ class Deform3D:
         _check_deform(self.cells, self.magnitude, tuple(int(v) for v in size))
 
 
+class Intensity3D:
+    """Random blur, noise and gamma for ``Augment3D(intensity=...)``, run by ``intensity3d`` on the resampled image.  Each of the
+    three is chosen on its own: ``blur_sigma`` = (lo, hi) of the Gaussian's sigma in output voxels, or one pair per axis d, h, w
+    (one uniform places all three axes inside their ranges), with probability ``blur_p``; ``noise_std`` = (lo, hi) of the standard
+    deviation of the added Gaussian noise, with probability ``noise_p``; ``gamma`` = (lo, hi) of the exponent, drawn log-uniformly,
+    exp(ln lo + (ln hi - ln lo) u), with probability ``gamma_p``, over ``value_range`` = (lo, hi) of the windowed image, to which
+    the gamma step also clamps.  None switches a component off.  The limits of ``ctseg_intensity3d`` are checked here: sigma in
+    [0, 4], std >= 0, gamma in [0.25, 4] and only with a ``value_range``."""
+
+    def __init__(self, value_range=None, blur_sigma=None, blur_p: float = 0.2, noise_std=None, noise_p: float = 0.15, gamma=None,
+                 gamma_p: float = 0.3):
+        who = "Intensity3D"
+        self.value_range = _check_range(value_range, who)
+        self.blur_sigma = None if blur_sigma is None else _axis_ranges(blur_sigma, "blur_sigma", who)
+        if self.blur_sigma is not None and not (np.isfinite(self.blur_sigma).all() and self.blur_sigma.min() >= 0.0
+                                                and self.blur_sigma.max() <= _MAX_SIGMA):
+            raise ValueError(f"{who}: blur_sigma lies in [0, {_MAX_SIGMA}]")
+        self.noise_std = None if noise_std is None else tuple(float(v) for v in noise_std)
+        if self.noise_std is not None and not (len(self.noise_std) == 2 and np.isfinite(self.noise_std).all()
+                                               and 0.0 <= self.noise_std[0] <= self.noise_std[1]):
+            raise ValueError(f"{who}: noise_std is (lo, hi), finite, 0 <= lo <= hi")
+        self.gamma = None if gamma is None else tuple(float(v) for v in gamma)
+        if self.gamma is not None:
+            if not (len(self.gamma) == 2 and 0.25 <= self.gamma[0] <= self.gamma[1] <= 4.0):
+                raise ValueError(f"{who}: gamma is (lo, hi) with 0.25 <= lo <= hi <= 4")
+            if self.value_range is None:
+                raise ValueError(f"{who}: gamma needs a value_range (lo, hi)")
+        self.blur_p, self.noise_p, self.gamma_p = float(blur_p), float(noise_p), float(gamma_p)
+
+    def params(self, applied: bool, blur_chance, sigma_u, noise_chance, std_u, noise_seed, gamma_chance, gamma_u):
+        """the seven drawn values -> None (not applied, or no component chosen) or the keyword arguments of ``intensity3d``"""
+        blur = applied and self.blur_sigma is not None and blur_chance < self.blur_p
+        noise = applied and self.noise_std is not None and noise_chance < self.noise_p
+        curve = applied and self.gamma is not None and gamma_chance < self.gamma_p
+        if not (blur or noise or curve):
+            return None
+        sigma = (0.0, 0.0, 0.0)
+        if blur:
+            sigma = tuple((self.blur_sigma[:, 0] + (self.blur_sigma[:, 1] - self.blur_sigma[:, 0]) * sigma_u).tolist())
+        std = self.noise_std[0] + (self.noise_std[1] - self.noise_std[0]) * std_u if noise else 0.0
+        g = float(np.exp(np.log(self.gamma[0]) + (np.log(self.gamma[1]) - np.log(self.gamma[0])) * gamma_u)) if curve else 1.0
+        return {"sigma": sigma, "noise_std": float(std), "noise_seed": int(noise_seed), "gamma": g,
+                "value_range": self.value_range if curve else None}
+
+
 class Augment3D:
     """Random affine + mirror + intensity augmentation of a volume, applied by ``InstancePipeline3D(augment=...)`` in its one pass.
 
@@ -193,7 +313,8 @@ class Augment3D:
     ``swap_pairs`` = mask channels that trade places under a w mirror (default: OpticNerve, Parotid, Submandibular L/R of
     ``STRUCTURES``); ``gain`` / ``bias`` = (lo, hi) of ``v * gain + bias`` after the window, or None; ``interp`` "trilinear" or
     "nearest" for the image (masks are always nearest); ``border`` "constant" (``cval`` / 0) or "edge"; ``p`` = probability that
-    anything is applied at all; ``deform`` = a ``Deform3D`` or None: a non-rigid displacement added to the affine sampling point.
+    anything is applied at all; ``deform`` = a ``Deform3D`` or None: a non-rigid displacement added to the affine sampling point;
+    ``intensity`` = an ``Intensity3D`` or None: blur, noise and gamma on the resampled image, a second stage after the pass.
 
     The matrix maps an output voxel o to the point q = L o + offset it samples (the sampling direction), composed in float64 as
         L = R_w(angle_w) . R_h(angle_h) . R_d(angle_d) . diag(1 / scale) . F,      offset = c - L c + shift,   c = (size - 1) / 2
@@ -204,7 +325,7 @@ class Augment3D:
 
     def __init__(self, rotate=(0.0, 0.0, 0.0), scale=(1.0, 1.0), translate=(0.0, 0.0, 0.0), flip_prob=(0.0, 0.0, 0.0),
                  swap_pairs=((3, 4), (5, 6), (7, 8)), gain=None, bias=None, interp="trilinear", border="constant", cval: float = 0.0,
-                 p: float = 1.0, deform: Optional[Deform3D] = None):
+                 p: float = 1.0, deform: Optional[Deform3D] = None, intensity: Optional[Intensity3D] = None):
         self.rotate = np.abs(np.asarray(rotate, dtype=np.float64).reshape(3))
         self.scale = _axis_ranges(scale, "scale")
         if (self.scale <= 0).any():
@@ -217,7 +338,7 @@ class Augment3D:
         if interp not in _INTERPS or border not in _BORDERS:
             raise ValueError(f"Augment3D: interp is one of {sorted(_INTERPS)}, border one of {sorted(_BORDERS)}")
         self.interp, self.border, self.cval, self.p = interp, border, float(cval), float(p)
-        self.deform = deform
+        self.deform, self.intensity = deform, intensity
         self._rng = np.random.default_rng()
 
     @staticmethod
@@ -229,7 +350,9 @@ class Augment3D:
         """one instance's parameters, uniform in the ranges, from a ``numpy.random.Generator``; the draws are made in one fixed
         order and number whatever the ranges are (applied, angles, scales, shifts, flips, gain, bias): 15 uniforms per call.
         With a ``deform``, two more values follow them in every call, a uniform (deformed or not) and the lattice's seed, and
-        the dict gains ``"deform"``: None or {"seed", "cells", "magnitude"}"""
+        the dict gains ``"deform"``: None or {"seed", "cells", "magnitude"}.  With an ``intensity``, seven more values follow
+        those in every call (blur chance, sigma uniform, noise chance, std uniform, noise seed, gamma chance, gamma uniform) and
+        the dict gains ``"intensity"``: None or {"sigma", "noise_std", "noise_seed", "gamma", "value_range"}"""
         g = generator if generator is not None else self._rng
         u = g.random(15)
         params = self._affine_params(u)
@@ -237,6 +360,12 @@ class Augment3D:
             chance, seed = g.random(), int(g.integers(0, 2 ** 63))
             on = params["applied"] and chance < self.deform.p
             params["deform"] = {"seed": seed, "cells": self.deform.cells, "magnitude": self.deform.magnitude} if on else None
+        if self.intensity is not None:
+            blur_chance, sigma_u, noise_chance, std_u = g.random(), g.random(), g.random(), g.random()
+            seed = int(g.integers(0, 2 ** 63))
+            gamma_chance, gamma_u = g.random(), g.random()
+            params["intensity"] = self.intensity.params(params["applied"], blur_chance, sigma_u, noise_chance, std_u, seed,
+                                                        gamma_chance, gamma_u)
         return params
 
     def _affine_params(self, u) -> dict:
@@ -322,7 +451,8 @@ class InstancePipeline3D:
     (a ``numpy.random.Generator``) or given as ``params`` (``Augment3D.draw``'s dict); the result then carries ``"params"`` and
     ``"channel_src"``, the K input channels behind the output mask channels, which ``mask_indicator`` has to follow.  The
     distance maps are those of the augmented masks.  An ``Augment3D`` with a ``deform`` is checked against ``size`` here, and an
-    instance whose ``params["deform"]`` is set takes the lattice launch and the deformed pass instead."""
+    instance whose ``params["deform"]`` is set takes the lattice launch and the deformed pass instead.  An instance whose
+    ``params["intensity"]`` is set sends the image, and nothing else, through ``intensity3d`` after the pass, in place."""
 
     def __init__(self, size=(96, 256, 256), squash: bool = False, window: Optional[Tuple] = None, dist_maps: bool = False,
                  signed: bool = False, augment: Optional[Augment3D] = None):
@@ -346,6 +476,8 @@ class InstancePipeline3D:
             img, m, lab, hist = augment3d_to_hwd(image, masks, self.size, aug.matrix(self.size, params), aug.interp, aug.border,
                                                  aug.cval, src, self.window, params["gain"], params["bias"], want_masks=want_masks,
                                                  want_labels=self.squash, deform=params.get("deform"))
+            if params.get("intensity") is not None and img is not None:
+                intensity3d(img, **params["intensity"], out=img)
             extra = {"channel_src": src, "params": params}
         out = {"image": img.unsqueeze(0), "masks": lab if self.squash else m, **extra}
         if self.squash:
@@ -370,4 +502,16 @@ augmented_degree_2 = {
                                                   flip_prob=(0, 0, 0.5),
                                                   deform=Deform3D(cells=(3, 8, 8), magnitude=(1.0, 4.0, 4.0), p=0.5))),
     "test": InstancePipeline3D(),
+}
+# degree 2 on the soft-tissue window, shifted to (0, 1), which gives the image the known scale an intensity stage needs: what differs
+# between scanners and reconstruction kernels is sharpness (a blur of up to half a voxel through the slices and 0.5 to 1 in plane),
+# noise (up to 5 % of the window) and the contrast curve (gamma between 0.7 and 1 / 0.7).  The "test" side takes the same window
+_SOFT_TISSUE = (*WINDOWING_CONFIG["soft_tissue"], True)
+augmented_degree_3 = {
+    "train": InstancePipeline3D(window=_SOFT_TISSUE,
+                                augment=Augment3D(rotate=(0.26, 0.05, 0.05), scale=(0.9, 1.1), translate=(2, 8, 8), flip_prob=(0, 0, 0.5),
+                                                  deform=Deform3D(cells=(3, 8, 8), magnitude=(1.0, 4.0, 4.0), p=0.5),
+                                                  intensity=Intensity3D(value_range=(0, 1), blur_sigma=((0, 0.5), (0.5, 1.0), (0.5, 1.0)),
+                                                                        noise_std=(0, 0.05), gamma=(0.7, 1 / 0.7)))),
+    "test": InstancePipeline3D(window=_SOFT_TISSUE),
 }

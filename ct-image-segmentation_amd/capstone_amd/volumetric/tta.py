@@ -128,6 +128,9 @@ class TestTimeAugmenter3D:
         if any(v.get("deform") is not None for v in self.views):
             raise ValueError("TestTimeAugmenter3D: a deformed view (params['deform'] is set) has no inverse matrix to merge its "
                              "prediction through; draw the views from an Augment3D without deform")
+        if any(v.get("intensity") is not None for v in self.views):
+            raise ValueError("TestTimeAugmenter3D: a view with an intensity stage (params['intensity'] is set: blur, noise, gamma) "
+                             "is no view of the same scan; draw the views from an Augment3D without intensity")
         self.size = tuple(int(v) for v in size)
         if mode not in _MODES or interp not in _INTERPS:
             raise ValueError(f"TestTimeAugmenter3D: mode is one of {sorted(_MODES)}, interp one of {sorted(_INTERPS)}")

@@ -498,6 +498,40 @@ int ctseg_augment3d_deform_to_hwd(const void* image, int32_t image_dtype, const 
                                   float win_hi, float gain, float bias, float* image_out, uint8_t* masks_out, uint8_t* labels_out,
                                   int64_t* hist, const float* lattice, const int32_t* cells /* host, 3 */, void* stream);
 
+/* Intensity stage of that pipeline: Gaussian blur, additive Gaussian noise and a gamma curve on the fp32 image [Ho][Wo][Do] that the
+ * passes above write, applied in this fixed order: blur, then noise, then gamma; any of the three may be absent.  image and image_out
+ * may be the same buffer (every pass can run in place: a workgroup reads nothing but the lines it owns) and there is no scratch
+ * volume; otherwise image is left untouched.  Sides are in [1, 1024].  radius (3 ints) and taps (3 rows of 13 floats, row a holding
+ * w_0..w_radius[a]; may be NULL when every radius is 0) are HOST arrays ordered d, h, w and copied into the kernels' arguments: no
+ * device upload, no synchronisation.  Every float operation below is one float32 rounding; nothing is contracted into an FMA.
+ *   - Blur: separable, one pass per axis with radius[a] > 0, in the order d (the contiguous axis), w, h; each pass stores float32.
+ *     The caller forms r = ceil(3 sigma) and w_k = exp(-k^2 / (2 sigma^2)), k = 0..r, normalised so that w_0 + 2 sum_{k>=1} w_k = 1,
+ *     in float64 and rounds once; 0 < sigma <= 4, so r <= 12; radius 0 skips the axis with no launch.  Border: edge replication,
+ *     indices clamped to [0, n - 1]; r may exceed n.  Along an axis with values v[]:
+ *         acc = w_0 * v[i];    for k = 1..r:  acc = acc + w_k * (v[max(i-k, 0)] + v[min(i+k, n-1)])
+ *     where the pair's sum, its product with w_k and the sum into acc are three separate roundings (a rounded multiply and a
+ *     rounded add, NOT a fused multiply-add).
+ *   - Noise (noise_std > 0): v = v + noise_std * n(seed, i), i = (h * Wo + w) * Do + d, the voxel's linear index in storage:
+ *         z = splitmix64 mix (see ctseg_deform3d_lattice) of noise_seed + (i + 1) * 0x9E3779B97F4A7C15, in uint64,
+ *         u1 = ((z >> 40) + 1) * 2^-24 in (0, 1],   u2 = ((z >> 16) & 0xFFFFFF) * 2^-24 in [0, 1)   (both exact in float32),
+ *         n = sqrtf(-2 * logf(u1)) * cosf(6.2831855f * u2).
+ *     Stateless: the seed and the index fix the field, whatever the volume's shape.  It is added after the blur.
+ *   - Gamma (has_range = 1, over the value range (lo, hi)): t = min(max((v - lo) * inv, 0), 1), v = lo + (hi - lo) * powf(t, gamma),
+ *     with inv = (float)(1 / ((double)hi - (double)lo)) and the float32 hi - lo formed on the host; gamma in [0.25, 4].  Values
+ *     outside the range, such as those the noise pushed out, are CLAMPED by this step (gamma = 1 is a clamp to the range).
+ *   - Launches (ctseg_intensity3d_launches returns their number for the same arguments, or a negative value where the entry
+ *     refuses them; it touches no device): one per blurred axis, the point stage (noise, gamma) folded into the store of the last
+ *     of them; one launch for a point stage alone; none when there is nothing to do (image_out, if another buffer, then gets the
+ *     input's bits by an asynchronous copy).
+ * Rejected before any launch: a null image or image_out (or taps, with a radius > 0); a side outside [1, 1024]; a radius outside
+ * [0, 12]; a tap that is negative or not finite, or taps whose w_0 + 2 sum w_k differs from 1 by more than (r + 2) * 2^-24; a
+ * noise_std that is negative or not finite; has_range other than 0 / 1; gamma outside [0.25, 4], or other than 1 without a range;
+ * a range that is not finite or has lo >= hi. */
+int ctseg_intensity3d(const float* image, float* image_out, int32_t Do, int32_t Ho, int32_t Wo, const int32_t* radius /* host, 3 */,
+                      const float* taps /* host, 3 x 13 */, float noise_std, int64_t noise_seed, int32_t has_range, float lo, float hi,
+                      float gamma, void* stream);
+int ctseg_intensity3d_launches(const int32_t* radius /* host, 3 */, float noise_std, int32_t has_range, float gamma);
+
 /* Test-time augmentation of the 3-D network: the prediction of one VIEW (the network's logits for an augmented copy of the scan)
  * is resampled onto a TARGET grid and added into an accumulator there; ctseg_tta_finish turns the accumulator into labels.
  * Inputs and layout:
