@@ -861,7 +861,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
       }
     }
     const float rs = __builtin_amdgcn_rcpf(ssum);                  // (gradient only: 1 ulp)
-    const float lse = m + __logf(ssum);
+    const float ls = __logf(ssum);                                 // (the cross-entropy below: the order of seg_loss_kernel)
     // one-hot of the label as products: oh_c = clamp(1 - (c - t)^2); x_t = sum_c oh_c x_c (a column >= C has oh = 0 and a FINITE x)
     const float tf = (float)t;
     f32x2 oh[6], xt2 = zero2;
@@ -874,7 +874,7 @@ __global__ __launch_bounds__(256 * NS, (BST && VB == 32 && NS == 1) ? 2 : 1) voi
     const float xt = xt2[0] + xt2[1];
     const float w = (E.class_weight != nullptr && t < C) ? E.class_weight[t] : 1.f;
     if (valid) {
-      ce_nll += w * (lse - xt);
+      ce_nll += w * (ls + (m - xt));
       ce_w += w;
     }
     // a wave whose 64 voxels are all background in truth and prediction — the common case once the net has trained for a few

@@ -145,14 +145,16 @@ __global__ __launch_bounds__(256) void seg_loss_kernel(const float* __restrict__
       pr[c] = (c < C) ? e[c] / ssum : 0.f;
       if (c < C && pr[c] > best) { best = pr[c]; pred = c; }
     }
-    const float lse = m + logf(ssum);
+    // cross-entropy as log(sum) + (m - x_t), log p_t as (x_t - m) - log(sum): m + log(sum) would be rounded at the magnitude of m
+    // before the subtraction cancels it (confident voxels, a shifted head bias)
+    const float ls = logf(ssum);
     float xt, pt;
     target_terms<CP>(x, pr, t, xt, pt);
-    const float logpt = xt - lse;
+    const float logpt = (xt - m) - ls;
     const float w = s_cw[t < CMAX ? t : 0];
     if (pred_out != nullptr) pred_out[vox] = (uint8_t)pred;
     if (do_stats) {
-      a_ce += w * (lse - xt);
+      a_ce += w * (ls + (m - xt));
       a_w += w;
       const float om = 1.f - pt;
       const float fo = -om * om * logpt;

@@ -110,7 +110,9 @@ __global__ __launch_bounds__(256) void seg_loss_pair_kernel(const float* __restr
       pr[c] = (c < C) ? e[c] / ssum : 0.f;
       if (c < C && pr[c] > best) { best = pr[c]; pred = c; }
     }
-    const float lse = m + logf(ssum);
+    // cross-entropy as log(sum) + (m - x_t), log p_t as (x_t - m) - log(sum): m + log(sum) would be rounded at the magnitude of m
+    // before the subtraction cancels it (confident voxels, a shifted head bias)
+    const float ls = logf(ssum);
     if constexpr (!GRAD) {
 #pragma unroll
       for (int c = 0; c < CP; ++c) {
@@ -125,11 +127,11 @@ __global__ __launch_bounds__(256) void seg_loss_pair_kernel(const float* __restr
       const int t = tt[s];
       float xt, pt;
       target_terms<CP>(x, pr, t, xt, pt);
-      const float logpt = xt - lse;
+      const float logpt = (xt - m) - ls;
       const float w = s_cw[s][t < CMAX ? t : 0];
       const float om = 1.f - pt;
       if constexpr (!GRAD) {
-        a_ce[s] += w * (lse - xt);
+        a_ce[s] += w * (ls + (m - xt));
         a_w[s] += w;
         const float fo = -om * om * logpt;
 #pragma unroll

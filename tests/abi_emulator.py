@@ -300,7 +300,7 @@ class Emulator:
         ssum = e.sum(-1, keepdims=True, dtype=np.float32)
         p = e / ssum
         pred = p.argmax(-1)
-        lse = (m + np.log(ssum))[..., 0]
+        ls, m1 = np.log(ssum)[..., 0], m[..., 0]      # the kernels' order: log(sum) + (m - x_t), (x_t - m) - log(sum)
         oh = np.eye(C, dtype=np.float32)[t]
         xt, pt = (x * oh).sum(-1), (p * oh).sum(-1)
         w = cw[t]
@@ -310,11 +310,11 @@ class Emulator:
             R = 2 + 3 * C
             pr = mem(part, B * P * R, np.float64).reshape(B, P, R)
             pr[:] = 0
-            pr[:, 0, 0] = (w * (lse - xt)).astype(np.float64).sum(1)
+            pr[:, 0, 0] = (w * (ls + (m1 - xt))).astype(np.float64).sum(1)
             pr[:, 0, 1] = w.astype(np.float64).sum(1)
             pr[:, 0, 2:2 + C] = p.astype(np.float64).sum(1)
             pr[:, 0, 2 + C:2 + 2 * C] = (p * oh).astype(np.float64).sum(1)
-            fo = -(1 - pt) ** 2 * (xt - lse)
+            fo = -(1 - pt) ** 2 * ((xt - m1) - ls)
             pr[:, 0, 2 + 2 * C:] = (fo[..., None] * oh).astype(np.float64).sum(1)
             c = mem(cnt, B * 3 * C, np.int64).reshape(B, 3, C)
             ph = np.eye(C, dtype=np.int64)[pred]
@@ -328,7 +328,7 @@ class Emulator:
             gk = b + a * oh
             dot = (gk * p).sum(-1, keepdims=True)
             ft = (f * oh).sum(-1)
-            om, logpt = 1 - pt, xt - lse
+            om, logpt = 1 - pt, (xt - m1) - ls
             fterm = ft * (2 * om * pt * logpt - om * om)
             d = cf[:, None, 0:1] * w[..., None] * (p - oh) + p * (gk - dot) + fterm[..., None] * (oh - p)
             o = cl_view(dlogits, B, S, 1, 1, g_ld, g_ld).reshape(B, S, g_ld)

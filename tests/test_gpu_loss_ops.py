@@ -26,7 +26,25 @@ Every test prints its worst error / bound before it asserts.  Measured on an MI3
   ctseg_reduce_partials_f64 0.13; fused head (ce, weight) sums 0.06, gradient bf16 0.99, fp16 0.50.
 The fused-head cases of three samples found a bug, fixed with them: a workgroup that walks the tiles with a stride above one
 (a grid that is no multiple of 8, as under CTSEG_MAX_WG = 3, or 6 tiles on 6 workgroups) wrote no record for a sample lying between
-or behind the samples of its tiles, where the host expects zeros; only a buffer that was zero before the launch hid it."""
+or behind the samples of its tiles, where the host expects zeros; only a buffer that was zero before the launch hid it.
+
+The regimes (loss_cases.py).  The cases above are the first step of training: logits a few units around zero.  A trained network
+is confident on most voxels (the label's logit 6 to 10 above the rest, cross-entropy 1e-3 and below, "confident"), its head bias
+has moved off zero ("shifted+64", "shifted+250", "shifted-64"), and some voxels saturate the softmax ("saturated": leads of 30 to
+120 and of 3e4, a row of equal logits at -3e4, a label probability of exactly 1.0); the fused head has a variant with every bias
+64 higher and one with a block that predicts class 0 with a lead of about 6.  That is where log-sum-exp code loses digits: the
+kernels formed the cross-entropy as (m + log(sum)) - x_t, a sum rounded at the magnitude of m before the subtraction cancels it.
+Worst error / bound on an MI355X, the parent commit's library -> this one:
+  ctseg_seg_loss record sums: confident 0.24 -> 0.07, shifted+64 0.50 -> 0.07, shifted+250 0.77 -> 0.07, shifted-64 0.22 -> 0.07,
+  saturated 0.06 -> 0.04; ctseg_seg_loss_pair: confident 0.015 -> 0.013, shifted+64 0.019 -> 0.005;
+  gradients, cross-entropy only: fp32 0.10 -> 0.10 (that path has no logarithm), bf16 0.99; soft path, confident and shifted: fp32
+  0.43 -> 0.08, bf16 0.99 -> 0.99; soft path, saturated: fp32 52.3 -> 0.12, bf16 3.4 -> 0.96;
+  fused head (ce, weight) sums: shifted 0.19 -> 0.02, confident 0.03 -> 0.04; gradients bf16 0.98, fp16 0.50, unchanged.
+The sums of the parent are inside the bound: sum_bound takes torch's float32 sum of the terms as its measure, whose own error
+(1e-8) is above that of the rounding at m.  Seven of the twelve saturated soft-path gradient cases are outside it.
+Fixed here: log p_t = x_t - (m + log(sum)) of the row of equal logits at -3e4 carried the rounding of -3e4 + log C (up to 1e-3)
+into the focal gradient term f (2 (1 - p_t) p_t log p_t - (1 - p_t)^2).  All three kernels now form log(sum) + (m - x_t) and
+(x_t - m) - log(sum), the order of torch's float32 cross_entropy, with the same instructions."""
 import math
 
 import numpy as np
@@ -39,8 +57,9 @@ from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd import segloss  # noqa: E402
 from capstone_amd._native import BF16, F16, F32  # noqa: E402
 from helpers import ACT_SENTINEL, CAP_IDS, CAPS, HALO_X, ConvPassDriver, cap_env, check_elems, sum_bound  # noqa: E402
-from loss_cases import (HEAD_CASES, HEAD_EMPTY_WG_CASE, HEAD_IDS, HEAD_LOSS_SCALE, SEG_B, SEG_S, SEG_SHAPES, head_reference,  # noqa: E402
-                        partials_case, partials_reference, seg_class_weight, seg_loss_case, seg_stats_reference)
+from loss_cases import (HEAD_CASES, HEAD_EMPTY_WG_CASE, HEAD_IDS, HEAD_LOSS_SCALE, HEAD_VARIANT_CASES, HEAD_VARIANT_IDS, SEG_B,  # noqa: E402
+                        SEG_REGIME_SHAPES, SEG_REGIMES, SEG_S, SEG_SHAPES, head_reference, partials_case, partials_reference,
+                        seg_class_weight, seg_loss_case, seg_stats_reference)
 from reference_ops import conv_module, dice_count_table, seg_loss_grad, seg_loss_records, seg_loss_terms  # noqa: E402
 
 DEV = "cuda:0"
@@ -110,6 +129,23 @@ def test_seg_loss_statistics_vs_float64(C, ld, S, weighted, do_stats):
 
 
 @pytest.mark.parametrize("do_stats", [1, 2], ids=["full", "ce-only"])
+@pytest.mark.parametrize("weighted", [False, True], ids=["plain", "weighted"])
+@pytest.mark.parametrize("S", SEG_S)
+@pytest.mark.parametrize("C,ld", SEG_REGIME_SHAPES)
+@pytest.mark.parametrize("regime", SEG_REGIMES)
+def test_seg_loss_statistics_by_regime_vs_float64(regime, C, ld, S, weighted, do_stats):
+    """the logits of a trained network (loss_cases.py: confident, shifted, saturated).  Saturated: every record entry finite; an
+    entry whose float64 terms are all zero is exactly 0 (_sum_ratio asserts that of every case)"""
+    ref = seg_stats_reference(C, ld, S, weighted, do_stats == 2, regime=regime)
+    case = ref["case"]
+    P = 3 if S == 4221 else 1
+    part, cnt, pred = _seg_loss(_dev(case["x"]), ld, _dev(case["labels"]), SEG_B, S, C, _dev(ref["cw"]), do_stats, P)
+    assert bool(torch.isfinite(part).all()), "a record entry that is not finite"
+    _check_stats(f"seg_loss statistics {regime} C={C} ld={ld} S={S} weighted={weighted} do_stats={do_stats}", ref, part, cnt, pred, SEG_B,
+                 P, C, do_stats == 2)
+
+
+@pytest.mark.parametrize("do_stats", [1, 2], ids=["full", "ce-only"])
 def test_seg_loss_workgroups_without_voxels_write_zero_records(do_stats):
     """S = 10 over P = 7 workgroups of two voxels: workgroups 5 and 6 start at or behind the end of the sample"""
     C, ld, S, P = 10, 12, 10, 7
@@ -124,10 +160,21 @@ def test_seg_loss_workgroups_without_voxels_write_zero_records(do_stats):
 def test_seg_loss_pair_statistics_at_13_classes_vs_two_float64_sides():
     """seg_loss_pair_kernel<float, 16, false>: side 0 of sample b is labels[b], side 1 labels[perm[b]].  Its records are 2 x 41
     doubles, more than ctseg_reduce_partials_f64 takes, so the P = 3 partial records are added in float64 on the host"""
+    _pair_statistics("initial")
+
+
+@pytest.mark.parametrize("regime", ["confident", "shifted+64"])
+def test_seg_loss_pair_statistics_by_regime(regime):
+    """the same launch on the logits of a trained network.  Confident: the logits lead at the labels of side 0, so side 1 (the labels
+    of another sample) is wrong on most voxels: one side with a cross-entropy of 1e-3, one of about 10 per voxel"""
+    _pair_statistics(regime)
+
+
+def _pair_statistics(regime):
     C, ld, S, B, P = 13, 16, 4221, SEG_B, 3
     R = 2 + 3 * C
     perm = [1, 1, 0]
-    case = seg_loss_case(C, ld, S)
+    case = seg_loss_case(C, ld, S, regime=regime)
     cw2 = torch.stack([seg_class_weight(C), seg_class_weight(C).flip(0)])
     x, labels = _dev(case["x"]), _dev(case["labels"])
     part = torch.full((B, P, 2, R), PART_SENTINEL, dtype=torch.float64, device=DEV)
@@ -140,9 +187,9 @@ def test_seg_loss_pair_statistics_at_13_classes_vs_two_float64_sides():
     for s, lab in enumerate((case["labels"], case["labels"][perm])):
         t64 = seg_loss_terms(case["x"].double(), lab, C, cw2[s].double())
         t32 = seg_loss_terms(case["x"], lab, C, cw2[s])
-        s64, norm, live, bound = sum_bound(f"pair side {s}", seg_loss_records(t64), seg_loss_records(t32), (1,), rows=S)
+        s64, norm, live, bound = sum_bound(f"pair side {s} {regime}", seg_loss_records(t64), seg_loss_records(t32), (1,), rows=S)
         assert torch.equal(cnt[:, s].cpu(), t64["cnt"]), ("Dice counts", s)
-        _sum_ratio(f"seg_loss_pair statistics C=13 side {s}", part[:, :, s].cpu().sum(1), dict(sums=s64, norm=norm, live=live, bound=bound))
+        _sum_ratio(f"seg_loss_pair statistics {regime} C=13 side {s}", part[:, :, s].cpu().sum(1), dict(sums=s64, norm=norm, live=live, bound=bound))
 
 
 # ---- ctseg_seg_loss: gradients -----------------------------------------------------------------------------------------------------
@@ -167,9 +214,33 @@ GRAD_CASES = [(10, 12, F32), (8, 8, BF16), (10, 12, BF16), (10, 16, BF16), (13, 
 @pytest.mark.parametrize("S", SEG_S)
 @pytest.mark.parametrize("C,g_ld,gdt", GRAD_CASES, ids=[f"C{c}-g{g}-{'fp32' if d == F32 else 'bf16'}" for c, g, d in GRAD_CASES])
 def test_seg_loss_gradient_vs_float64(C, g_ld, gdt, S, path):
+    _gradient(C, g_ld, gdt, S, path, "initial")
+
+
+# every (C, ld) of SEG_REGIME_SHAPES in fp32 and bf16, 12- and 16-wide gradient rows
+REGIME_GRAD_CASES = [(10, 12, F32), (10, 16, BF16), (13, 16, F32), (13, 16, BF16), (2, 12, BF16), (2, 16, F32)]
+
+
+@pytest.mark.parametrize("path", ["ce-only", "full"])
+@pytest.mark.parametrize("S", SEG_S)
+@pytest.mark.parametrize("C,g_ld,gdt", REGIME_GRAD_CASES, ids=[f"C{c}-g{g}-{'fp32' if d == F32 else 'bf16'}" for c, g, d in REGIME_GRAD_CASES])
+@pytest.mark.parametrize("regime", SEG_REGIMES)
+def test_seg_loss_gradient_by_regime_vs_float64(regime, C, g_ld, gdt, S, path):
+    """the logits of a trained network through both gradient paths; every stored element is finite.  A voxel whose label has the
+    float32 probability 1.0 (the right voxels of the saturated regime), as measured on an MI355X: with fp32 stores the row has
+    exactly the zero pattern of the float32 evaluation (every such row of all twelve cases); with bf16 stores it has not (a fifth
+    to a quarter of the rows differ: the conversion rounds an element below the bf16 subnormals to 0, where the evaluation keeps
+    1e-40).  What holds for both, and is asserted: the row lies within the element bound, as every row does (check_elems), and on
+    the cross-entropy-only path the label's own element, s w (p_t - 1), is exactly 0.  The fp32 zero pattern is printed, not
+    asserted: which elements are zero rests on how the host's float32 exp rounds a subnormal (8e-40 at a lead of 90), a property
+    of the reference, not of the kernel."""
+    _gradient(C, g_ld, gdt, S, path, regime)
+
+
+def _gradient(C, g_ld, gdt, S, path, regime):
     ld = (C + 3) // 4 * 4
     assert (C, ld) in SEG_SHAPES
-    case = seg_loss_case(C, ld, S)
+    case = seg_loss_case(C, ld, S, regime=regime)
     B = SEG_B
     if path == "ce-only":            # what fused_ce launches: do_stats = 2 and do_grad = 2 in one pass, one scale per sample
         coef = torch.zeros(B, 1 + 3 * C)
@@ -184,12 +255,23 @@ def test_seg_loss_gradient_vs_float64(C, g_ld, gdt, S, path):
     part, cnt, pred = _seg_loss(_dev(case["x"]), ld, _dev(case["labels"]), B, S, C, _dev(cw), do_stats, P, do_grad, _dev(coef), dl_ptr, g_ld,
                                 gdt)
     got = buf[GUARD:-GUARD].float().cpu().double().reshape(B, S, g_ld)
-    check_elems(f"seg_loss gradient {path} C={C} g_ld={g_ld} dtype={gdt} S={S}", got[..., :C], ref64, ref32, gdt)
+    assert bool(torch.isfinite(got).all()), "a stored element that is not finite"
+    tag = f"seg_loss gradient {path} C={C} g_ld={g_ld} dtype={gdt} S={S}" + ("" if regime == "initial" else " " + regime)
+    check_elems(tag, got[..., :C], ref64, ref32, gdt)
     if g_ld > C:
         assert float(got[..., C:].abs().max()) == 0.0, "the padding columns of every written row read 0"
     _check_guards(buf)
     if do_stats:
-        assert torch.equal(cnt.cpu(), seg_stats_reference(C, ld, S, False, True)["cnt"])
+        assert torch.equal(cnt.cpu(), seg_stats_reference(C, ld, S, False, True, regime=regime)["cnt"])
+    if regime == "saturated":
+        lab = case["labels"].long()
+        one = seg_loss_terms(case["x"], lab, C)["py"].sum(-1) == 1.0
+        assert bool(one[case["label_leads"]].all()) and int(one.sum()) > S // 2
+        same = ((got[..., :C] == 0) == (ref32 == 0)).all(-1)[one]
+        print(f"{tag}: {int(one.sum())} rows with a float32 label probability of 1.0, zero pattern of the float32 evaluation on "
+              f"{int(same.sum())} of them")
+        if path == "ce-only":
+            assert float(got[..., :C].gather(-1, lab[..., None])[..., 0][one].abs().max()) == 0.0, "s w (p_t - 1) at p_t = 1.0"
 
 
 # ---- ctseg_squash_masks / ctseg_squash_masks_present ------------------------------------------------------------------------------
@@ -335,13 +417,15 @@ def test_loss_dice_summary_vs_the_torch_expressions(C, absent_all, absent_one):
 
 # ---- ctseg_conv_logits_ce -----------------------------------------------------------------------------------------------------------
 def _fused_head(case, monkeypatch, max_wg):
-    C, cin, residual, g_ld, dtn, weighted, shape = case
+    C, cin, residual, g_ld, dtn, weighted, shape = case[:7]
+    variant = case[7] if len(case) > 7 else "base"
     cap_env(monkeypatch, max_wg)
     dt = DT[dtn]
-    ref = head_reference(C, cin, residual, weighted, shape, HEAD_LOSS_SCALE[dtn])
+    ref = head_reference(C, cin, residual, weighted, shape, HEAD_LOSS_SCALE[dtn], variant)
     hc = ref["case"]
     N, S, R = shape[0], shape[1] * shape[2] * shape[3], 2 + 3 * C
     tag = f"fused head C={C} cin={cin} residual={residual} g_ld={g_ld} {dtn} weighted={weighted} N={N} max_wg={max_wg}"
+    tag += "" if variant == "base" else " " + variant
     mod = conv_module("conv", cin, C)
     with torch.no_grad():
         mod.weight.copy_(hc.w)
@@ -391,6 +475,13 @@ def _fused_head(case, monkeypatch, max_wg):
 @pytest.mark.parametrize("max_wg", CAPS, ids=CAP_IDS)
 @pytest.mark.parametrize("case", HEAD_CASES, ids=HEAD_IDS)
 def test_fused_head_cross_entropy_vs_float64(monkeypatch, case, max_wg):
+    _fused_head(case, monkeypatch, max_wg)
+
+
+@pytest.mark.parametrize("max_wg", CAPS, ids=CAP_IDS)
+@pytest.mark.parametrize("case", HEAD_VARIANT_CASES, ids=HEAD_VARIANT_IDS)
+def test_fused_head_cross_entropy_of_a_trained_head_vs_float64(monkeypatch, case, max_wg):
+    """every bias 64 higher / a block that predicts class 0 with a lead of about 6 (loss_cases.py): the same checks"""
     _fused_head(case, monkeypatch, max_wg)
 
 

@@ -6,8 +6,9 @@ import torch.nn.functional as F
 
 from capstone_amd._native import BF16, F32
 from helpers import check_elems, elem_bound, sum_bound
-from loss_cases import (HEAD_CASES, HEAD_EMPTY_WG_CASE, HEAD_IDS, HEAD_LOSS_SCALE, SEG_S, SEG_SHAPES, head_case, head_reference, partials_case,
-                        partials_reference, seg_class_weight, seg_loss_case, seg_stats_reference, top_margin)
+from loss_cases import (HEAD_CASES, HEAD_EMPTY_WG_CASE, HEAD_IDS, HEAD_LOSS_SCALE, HEAD_VARIANT_CASES, HEAD_VARIANT_IDS, PAD_LOGIT, SAT_BIG,
+                        SAT_EQUAL_ROW, SAT_RIGHT_ROW, SAT_WRONG_ROWS, SEG_REGIME_SHAPES, SEG_REGIMES, SEG_S, SEG_SHAPES, SEG_SHIFT, head_case,
+                        head_reference, partials_case, partials_reference, seg_class_weight, seg_loss_case, seg_stats_reference, top_margin)
 from reference_ops import (boundary64, boundary_weights64, conv_dgrad, conv_fwd, conv_module, conv_out_shape, conv_wgrad, dice_count_table,
                            first_max_index, norm_prelu_dy, norm_prelu_terms, seg_loss_grad, seg_loss_records, seg_loss_terms)
 
@@ -217,7 +218,72 @@ def test_seg_loss_grad_equals_autograd_of_cross_entropy_and_the_closed_form():
 
 @pytest.mark.parametrize("C,ld,S", [(C, ld, S) for C, ld in SEG_SHAPES for S in SEG_S] + [(10, 12, 10)])      # S = 10: the direct call
 def test_seg_loss_case_preconditions(C, ld, S):
-    case = seg_loss_case(C, ld, S)
+    _seg_case_preconditions(C, ld, S, "initial")
+
+
+@pytest.mark.parametrize("regime", SEG_REGIMES)
+@pytest.mark.parametrize("C,ld,S", [(C, ld, S) for C, ld in SEG_REGIME_SHAPES for S in SEG_S])
+def test_seg_loss_regime_preconditions(C, ld, S, regime):
+    """the promises of the initial draw hold in every regime, and each regime is in the state its name says"""
+    _seg_case_preconditions(C, ld, S, regime)
+    base, case = seg_loss_case(C, ld, S), seg_loss_case(C, ld, S, regime=regime)
+    for k in ("labels", "coef", "cw"):
+        assert torch.equal(case[k], base[k]), k
+    assert case["tie_rows"] == base["tie_rows"]
+    x, labels = case["x"][..., :C], case["labels"].long()
+    assert bool((case["x"][..., C:] == PAD_LOGIT).all())
+    if regime in SEG_SHIFT:
+        # x is float32: the shifted logit IS a float32 number; that the addition did not round is what is asserted
+        assert torch.equal(x.double(), base["x"][..., :C].double() + SEG_SHIFT[regime]), "the offset is exact"
+        return
+    lead_ok = case["label_leads"]
+    tie = torch.zeros(S, dtype=torch.bool)
+    tie[[r for r, _ in case["tie_rows"]]] = True
+    special = tie.clone()
+    if regime == "saturated":
+        special[4:9] = True
+    body = ~special[None, :].expand_as(lead_ok)
+    share = float(lead_ok[body].float().mean())
+    assert (0.95 if S > 1000 else 0.80) <= share <= 0.98, share
+    top = x.double().topk(2, dim=-1).values
+    lead = top[..., 0] - top[..., 1]
+    t64 = seg_loss_terms(x.double(), labels, C)
+    t32 = seg_loss_terms(x, labels, C)
+    right, wrong = body & lead_ok, body & ~lead_ok
+    assert torch.equal(t64["pred"][right], labels[right]) and bool((t64["pred"][wrong] != labels[wrong]).all())
+    hist_wrong = F.one_hot(labels, C) * wrong[..., None]
+    assert bool(((hist_wrong.sum(1) > 0) | (F.one_hot(labels, C).sum(1) == 0)).all()), "a wrong voxel for every class of a sample's labels"
+    pt32 = t32["py"].sum(-1)
+    rows_wrong = list(SAT_WRONG_ROWS)
+    if regime == "confident":
+        assert 6.0 <= float(lead[body].min()) and float(lead[body].max()) <= 10.0
+        assert float(t64["ce"][right].median()) < 2e-3 and float(t64["ce"][right].max()) < 9 * 2.5e-3
+        # the lead over the largest other logit, plus what the label's logit lies below that one
+        assert 6.0 < float(t64["ce"][wrong].min()) and float(t64["ce"][wrong].median()) < 13.0 and float(t64["ce"][wrong].max()) < 30.0
+        assert bool((pt32[right] < 1.0).all())
+    else:
+        assert 30.0 <= float(lead[body].min()) and float(lead[body].max()) <= 124.0
+        e32 = torch.exp(-lead[body].float())
+        tiny = float(torch.finfo(torch.float32).tiny)
+        assert bool(((e32 > 1e-20) & (e32 < 2.0 ** -23)).any()) and bool(((e32 > tiny) & (e32 < 1e-20)).any())
+        assert bool(((e32 > 0) & (e32 < tiny)).any()) and bool((e32 == 0).any()), "below epsilon, a subnormal, 0"
+        assert bool((pt32[lead_ok] == 1.0).all()), "the label's probability is exactly 1.0 in float32"
+        assert bool(lead_ok[:, SAT_RIGHT_ROW].all()) and not bool(lead_ok[:, [4] + rows_wrong].any())
+        rows = rows_wrong
+        assert bool((x[:, rows].max(-1).values == SAT_BIG).all()) and bool((t64["pred"][:, rows] != labels[:, rows]).all())
+        assert bool((t64["ce"][:, rows] > SAT_BIG - 16).all()) and bool((t64["p"][:, rows].sort(-1).values[..., :-1] == 0).all())
+        r = SAT_RIGHT_ROW
+        assert bool((t64["ce"][:, r] == 0).all()) and bool((t64["py"][:, r].sum(-1) == 1).all())
+        b, r = SAT_EQUAL_ROW
+        assert bool((x[b, r] == -SAT_BIG).all()) and int(t64["pred"][b, r]) == 0
+        assert abs(float(t64["ce"][b, r]) - float(torch.log(torch.tensor(float(C), dtype=F64)))) < 1e-15
+        for t in (t64, t32):
+            for k in ("ce", "p", "py", "fo"):
+                assert bool(torch.isfinite(t[k]).all()), k
+
+
+def _seg_case_preconditions(C, ld, S, regime):
+    case = seg_loss_case(C, ld, S, regime=regime)
     x, labels = case["x"], case["labels"].long()
     assert x.shape == (3, S, ld) and x.dtype == torch.float32
     assert torch.equal(torch.round(x * 1024.0), x * 1024.0), "multiples of 2^-10"
@@ -232,7 +298,7 @@ def test_seg_loss_case_preconditions(C, ld, S):
     assert bool((hist[1:] > 0).all()) and int(hist[0, C - 1]) == 0 and bool((hist[0, :C - 1] > 0).all() or S < 100)
     for weighted in (False, True):
         for ce_only in (False, True):
-            ref = seg_stats_reference(C, ld, S, weighted, ce_only)          # asserts 0 < bound < 1 / (4 S)
+            ref = seg_stats_reference(C, ld, S, weighted, ce_only, regime=regime)          # asserts 0 < bound < 1 / (4 S)
             assert 0.0 < ref["bound"] < 1.0 / (4 * S)
             assert torch.equal(ref["pred"], ref["pred32"]), "float32 and float64 softmax order the classes alike"
             assert torch.equal(ref["pred"], first_max_index(x[..., :C])), "softmax keeps the order and the ties of the logits"
@@ -244,7 +310,31 @@ HEAD_ALL = HEAD_CASES + [HEAD_EMPTY_WG_CASE]
 
 @pytest.mark.parametrize("C,cin,residual,g_ld,dtn,weighted,shape", HEAD_ALL, ids=HEAD_IDS + ["empty-workgroups"])
 def test_head_case_preconditions(C, cin, residual, g_ld, dtn, weighted, shape):
-    hc = head_case(C, cin, shape, residual)
+    _head_case_preconditions(C, cin, residual, g_ld, dtn, weighted, shape, "base")
+
+
+@pytest.mark.parametrize("C,cin,residual,g_ld,dtn,weighted,shape,variant", HEAD_VARIANT_CASES, ids=HEAD_VARIANT_IDS)
+def test_head_variant_preconditions(C, cin, residual, g_ld, dtn, weighted, shape, variant):
+    """regions (a) to (d) keep their meaning; shifted: the biases of the base case + 64, the logits still exact and below 2^24 units;
+    confident: the second block's core predicts class 0 with a lead of about 6, label 0 but for two voxels per sample"""
+    r = _head_case_preconditions(C, cin, residual, g_ld, dtn, weighted, shape, variant)
+    hc, base = head_case(C, cin, shape, residual, variant), head_case(C, cin, shape, residual)
+    assert torch.equal(hc.w, base.w)
+    if variant == "shifted":
+        assert torch.equal(hc.b, base.b + 64.0) and torch.equal(hc.x, base.x) and torch.equal(hc.labels, base.labels)
+        assert torch.equal(hc.logits(F64), base.logits(F64) + 64.0)
+        assert float(hc.logits(F64).abs().max()) / 2.0 ** -11 < 2.0 ** 20 < 2.0 ** 24
+        assert r["confident"] == r["confident_wrong"] == 0
+    else:
+        assert torch.equal(hc.b, base.b)
+        n_core = shape[0] * shape[1] * 4 * 3
+        assert r["confident"] == n_core - 2 * shape[0] and r["confident_wrong"] == 2 * shape[0], "the confident block is not empty"
+        assert 5.0 < r["confident_lead"] < 8.0
+        assert r["tile0"] == r["background"], "the block lies outside the first tile"
+
+
+def _head_case_preconditions(C, cin, residual, g_ld, dtn, weighted, shape, variant):
+    hc = head_case(C, cin, shape, residual, variant)
     st = torch.bfloat16 if dtn == "bf16" else torch.float16
     unit = 2.0 ** -11
     assert torch.equal(hc.x, torch.round(hc.x)) and torch.equal(hc.x.to(st).float(), hc.x), "activations: integers of the storage type"
@@ -264,7 +354,7 @@ def test_head_case_preconditions(C, cin, residual, g_ld, dtn, weighted, shape):
     assert r["ordinary"] > r["tile0"] // 2, "(d)"
     spread = y64.max(-1).values - y64.min(-1).values
     assert 0.25 < float(spread.median()) < 8.0, "logits spread of order 1: no saturated softmax"
-    ref = head_reference(C, cin, residual, weighted, shape, HEAD_LOSS_SCALE[dtn])
+    ref = head_reference(C, cin, residual, weighted, shape, HEAD_LOSS_SCALE[dtn], variant)
     S = shape[1] * shape[2] * shape[3]
     if dtn == "fp16":
         mag = ref["g64"].abs()
@@ -274,6 +364,7 @@ def test_head_case_preconditions(C, cin, residual, g_ld, dtn, weighted, shape):
     hist = F.one_hot(hc.labels.long().reshape(shape[0], -1), C).sum(1)
     assert bool((hist > 0).all()), "labels cover every class in every sample"
     assert float((ref["g32"].double() - ref["g64"]).abs().max()) > 0
+    return r
 
 
 def test_head_cases_take_both_directions_of_a_near_tie():
