@@ -6,6 +6,7 @@ strides and slices, the forward/backward graph, gradient placement) can be check
 oracle WITHOUT a GPU.  fp32 storage only.  It is also the per-kernel specification the GPU tests
 compare the HIP kernels with.  Never imported by the product.
 """
+import contextlib
 import ctypes
 import os
 
@@ -476,3 +477,21 @@ def patch_native(nat, emu):
     def undo():
         nat.call, nat.stream_ptr, nat.require_gpu, nat.query = orig_call, orig_stream, orig_req, orig_query
     return undo
+
+
+@contextlib.contextmanager
+def emulated(e, plan_run=True):
+    """the C ABI routed through emulator ``e``: direct engine calls (patch_native) and, with ``plan_run``, recorded programs too
+    (Plan.run); yields ``e`` and restores both in reverse order"""
+    from capstone_amd import _native as nat
+    from capstone_amd import plan as plan_mod
+    undo = patch_native(nat, e)
+    if plan_run:
+        orig = plan_mod.Plan.__dict__["run"]         # the staticmethod itself: restoring the bare function would bind self
+        plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
+    try:
+        yield e
+    finally:
+        if plan_run:
+            plan_mod.Plan.run = orig
+        undo()

@@ -336,6 +336,46 @@ def ulp32(s):
     return torch.where(s == 0, torch.full_like(s, 2.0 ** -149), torch.pow(2.0, (e - 24).double()))
 
 
+DEV = "cuda:0"
+
+
+def on_device(*arrays):
+    """numpy arrays (read-only ones too) -> tensors on the GPU: one for one array, a tuple for several"""
+    t = tuple(torch.from_numpy(np.array(a)).to(DEV) for a in arrays)
+    return t[0] if len(t) == 1 else t
+
+
+def as_numpy(out):
+    """a tuple of tensors -> a tuple of arrays; a result object -> the dict of its fields as arrays"""
+    if isinstance(out, (tuple, list)):
+        return tuple(t.cpu().numpy() for t in out)
+    return {k: v.cpu().numpy() for k, v in vars(out).items()}
+
+
+def check_bit_exact(got, ref):
+    """a 2-D pipeline's outputs (nine masks and squashing) against its oracle's, array_equal on every one"""
+    assert got["image"].dtype == np.float32 and ref["image"].dtype == np.float32
+    diff = np.abs(got["image"].astype(np.float64) - ref["image"])
+    print("image: max |diff|", float(diff.max()), "differing", int((got["image"] != ref["image"]).sum()), "of", diff.size)
+    assert np.array_equal(got["image"], ref["image"])
+    assert np.array_equal(got["image_sq"], ref["image"])
+    assert np.array_equal(got["masks"], ref["masks"])
+    assert np.array_equal(got["labels"], ref["labels"]) and np.array_equal(got["flat"], ref["labels"].reshape(len(ref["labels"]), -1))
+    assert np.array_equal(got["hist"], ref["hist"])
+    assert np.array_equal(got["hist"], np.stack([np.bincount(l.reshape(-1), minlength=10) for l in got["labels"]]))
+    assert np.array_equal(got["present"], ref["present"]) and np.array_equal(got["present_sq"], ref["present"])
+
+
+def swapped_oracle(dims, cin, cout, channels, strides, nres):
+    """MONAI's UNet with norm=Norm.BATCH: the oracle with each Convolution's InstanceNorm replaced by BatchNorm (same place)"""
+    from oracle.monai_unet import Convolution, UNet
+    net = UNet(dims, cin, cout, channels, strides, num_res_units=nres)
+    for m in net.modules():
+        if isinstance(m, Convolution) and "norm" in m._modules:
+            m.norm = {2: torch.nn.BatchNorm2d, 3: torch.nn.BatchNorm3d}[dims](m.norm.num_features)
+    return net
+
+
 def rel_err(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-12))

@@ -6,103 +6,20 @@ import pytest
 import torch
 import torch.nn as nn
 
-from abi_emulator import Emulator, mem, patch_native
+from abi_emulator import Emulator, emulated
 from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
 from capstone_amd.models import UNet
-from oracle.monai_unet import Convolution as OracleConvolution
-from oracle.monai_unet import UNet as OracleUNet
+from feature_emulators import BatchNormEntries
+from helpers import swapped_oracle
 
-_BN = {2: nn.BatchNorm2d, 3: nn.BatchNorm3d}
-
-
-def swapped_oracle(dims, cin, cout, channels, strides, nres):
-    """MONAI's UNet with norm=Norm.BATCH: the oracle with each Convolution's InstanceNorm replaced by BatchNorm (same place)"""
-    net = OracleUNet(dims, cin, cout, channels, strides, num_res_units=nres)
-    for m in net.modules():
-        if isinstance(m, OracleConvolution) and "norm" in m._modules:
-            m.norm = _BN[dims](m.norm.num_features)
-    return net
-
-
-class BNEmulator(Emulator):
-    """the BatchNorm entry points of include/ctseg_hip.h on host memory (fp32 storage), in their specified arithmetic"""
-
-    def batchnorm_finalize(self, partials, N, P, ld, col0, C, count, eps, momentum, gamma, beta, rm, rv, nbt, mean_rstd, ss):
-        p = mem(partials, N * P * 2 * ld).reshape(N * P, 2, ld).astype(np.float64).sum(0)
-        mean = p[0, col0:col0 + C] / count
-        var = np.maximum(p[1, col0:col0 + C] / count - mean * mean, 0)
-        rstd = 1.0 / np.sqrt(var + eps)
-        g, b = mem(gamma, C).astype(np.float64), mem(beta, C).astype(np.float64)
-        mr, t = mem(mean_rstd, 2 * C).reshape(C, 2), mem(ss, 2 * C).reshape(C, 2)
-        mr[:, 0], mr[:, 1] = mean, rstd
-        t[:, 0], t[:, 1] = g * rstd, b - mean * g * rstd
-        r_m, r_v = mem(rm, C), mem(rv, C)
-        r_m[:] = (1 - momentum) * r_m + momentum * mean
-        r_v[:] = (1 - momentum) * r_v + momentum * var * count / (count - 1)
-        mem(nbt, 1, np.int64)[0] += 1
-
-    def batchnorm_eval_table(self, rm, rv, gamma, beta, C, eps, ss):
-        sc = mem(gamma, C).astype(np.float64) / np.sqrt(mem(rv, C).astype(np.float64) + eps)
-        t = mem(ss, 2 * C).reshape(C, 2)
-        t[:, 0], t[:, 1] = sc, mem(beta, C) - mem(rm, C) * sc
-
-    def scale_shift_prelu_fwd(self, dtype, y, y_ld, ss, alpha, res, res_ld, out, out_ld, N, S, C):
-        assert dtype == nat.F32
-        t = mem(ss, 2 * C).reshape(C, 2)
-        z = self._rows(y, N, S, C, y_ld) * t[:, 0] + t[:, 1]
-        z = np.where(z > 0, z, mem(alpha, 1)[0] * z)
-        if res:
-            z = z + self._rows(res, N, S, C, res_ld)
-        o = self._rows(out, N, S, (C + 3) // 4 * 4, out_ld)
-        o[..., :C] = z
-        o[..., C:] = 0
-
-    def _bn(self, g, g_ld, y, y_ld, mean_rstd, gamma, beta, alpha, N, S, C):
-        mr = mem(mean_rstd, 2 * C).reshape(C, 2)
-        xh = (self._rows(y, N, S, C, y_ld) - mr[:, 0]) * mr[:, 1]
-        z = mem(gamma, C) * xh + mem(beta, C)
-        gv = self._rows(g, N, S, C, g_ld)
-        return xh, z, gv, gv * np.where(z > 0, 1.0, mem(alpha, 1)[0]).astype(np.float32), mr[:, 1]
-
-    def batchnorm_prelu_bwd_reduce(self, dtype, g, g_ld, y, y_ld, mean_rstd, gamma, beta, alpha, partials, P, ld, N, S, C):
-        xh, z, gv, dz, _ = self._bn(g, g_ld, y, y_ld, mean_rstd, gamma, beta, alpha, N, S, C)
-        p = mem(partials, N * P * 3 * ld).reshape(N, P, 3, ld)
-        p[:] = 0
-        p[:, 0, 0, :C] = dz.sum(1)
-        p[:, 0, 1, :C] = (dz * xh).sum(1)
-        p[:, 0, 2, :C] = np.where(z > 0, 0, gv * z).sum(1)
-
-    def batchnorm_prelu_bwd_finalize(self, partials, N, P, ld, C, count, sums, dgamma, dbeta, da_part):
-        p = mem(partials, N * P * 3 * ld).reshape(N * P, 3, ld).astype(np.float64).sum(0)
-        s = mem(sums, 2 * C).reshape(C, 2)
-        s[:, 0], s[:, 1] = p[0, :C] / count, p[1, :C] / count
-        mem(dbeta, C)[:], mem(dgamma, C)[:] = p[0, :C], p[1, :C]
-        mem(da_part, C, np.float64)[:] = p[2, :C]
-
-    def batchnorm_prelu_bwd_apply(self, dtype, g, g_ld, y, y_ld, mean_rstd, gamma, beta, alpha, sums, dy, dy_ld, g_copy, g_copy_ld,
-                                  N, S, C, da_part, n_da, dalpha):
-        if da_part:
-            mem(dalpha, 1)[0] = mem(da_part, n_da, np.float64).sum()
-        xh, z, gv, dz, rstd = self._bn(g, g_ld, y, y_ld, mean_rstd, gamma, beta, alpha, N, S, C)
-        s = mem(sums, 2 * C).reshape(C, 2)
-        Cp = (C + 3) // 4 * 4
-        o = self._rows(dy, N, S, Cp, dy_ld)
-        o[..., :C] = mem(gamma, C) * rstd * (dz - s[:, 0] - xh * s[:, 1])
-        o[..., C:] = 0
-        if g_copy:
-            self._rows(g_copy, N, S, Cp, g_copy_ld)[:] = self._rows(g, N, S, Cp, g_ld)
+class E(BatchNormEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = BNEmulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(E()) as e:
+        yield e
 
 
 def _pair(dims, cin, cout, chans, strides, nres, seed=0):

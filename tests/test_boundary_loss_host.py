@@ -1,7 +1,7 @@
 """CPU: the host side of the Boundary loss (capstone/models/losses.py:127-157 on the device).  The argument checks of
 ctseg_boundary_stats / ctseg_boundary_grad run in the library itself (they return before any launch); the opt-in switch, the
 weights, the ``bw`` table and the dict assembly of capstone_amd.segloss / models.losses / the two trainers run with the C ABI
-routed through the emulator, whose two new entries are emulated here in numpy (a subclass: tests/abi_emulator.py is not edited).
+routed through the emulator, whose two new entries are emulated in numpy (tests/feature_emulators.BoundaryEntries).
 
 The comparison target is the reference's formula restated in float64 torch:
     T[b, c] = mean_v softmax(x)[b, c + 1, v] * D[b, c, v];  "mean": T.mean();  exclude_missing: apply_missing_mask's non-Focal branch
@@ -13,10 +13,9 @@ import numpy as np
 import pytest
 import torch
 
-from abi_emulator import cl_view, mem, patch_native
-from test_mixup_host import MixupEmulator
+from abi_emulator import Emulator, emulated
 from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
+from feature_emulators import BoundaryEntries, MixupEntries
 from oracle import losses as OL
 
 F32, BF16 = 0, 1
@@ -41,51 +40,14 @@ def ref_scalar(x, D, exclude_missing=False, ind=None):
     return ref_missing(T, ind.to(T.dtype)) if exclude_missing else T.mean()
 
 
-# ---- numpy emulation of the two entry points --------------------------------------------------------------------------------
-class BoundaryEmulator(MixupEmulator):
-    @staticmethod
-    def _inputs(logits, ld, maps, perm, B, S, C):
-        x = cl_view(logits, B, S, 1, 1, C, ld).reshape(B, S, C).astype(np.float64)
-        e = np.exp(x - x.max(-1, keepdims=True))
-        p = e / e.sum(-1, keepdims=True)
-        D = mem(maps, B * (C - 1) * S).reshape(B, C - 1, S).astype(np.float64)
-        sides = [D] if not perm else [D, D[np.clip(mem(perm, B, np.int32), 0, B - 1)]]
-        return p, sides
-
-    def boundary_stats(self, logits, ld, maps, perm, B, S, C, part, P):
-        p, sides = self._inputs(logits, ld, maps, perm, B, S, C)
-        ns = len(sides)
-        pr = mem(part, B * P * ns * (C - 1), np.float64).reshape(B, P, ns, C - 1)
-        pr[:] = 0
-        for s, D in enumerate(sides):
-            pr[:, 0, s] = (np.transpose(p[..., 1:], (0, 2, 1)) * D).sum(-1)
-
-    def boundary_grad(self, logits, ld, maps, perm, B, S, C, bw, P, dlogits, g_ld, gdtype, accumulate):
-        assert gdtype == F32
-        p, sides = self._inputs(logits, ld, maps, perm, B, S, C)
-        ns = len(sides)
-        w = mem(bw, B * ns * (C - 1)).reshape(B, ns, C - 1).astype(np.float64)
-        g = np.zeros((B, S, C))
-        for s, D in enumerate(sides):
-            g[..., 1:] += np.transpose(w[:, s, :, None] * D, (0, 2, 1))
-        d = p * (g - (g * p).sum(-1, keepdims=True))
-        o = cl_view(dlogits, B, S, 1, 1, g_ld, g_ld).reshape(B, S, g_ld)
-        if accumulate:
-            o[..., :C] += d.astype(np.float32)
-        else:
-            o[..., :C] = d
-            o[..., C:] = 0
+class E(BoundaryEntries, MixupEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = BoundaryEmulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(E()) as e:
+        yield e
 
 
 # ---- argument validation: the library itself, no launch -----------------------------------------------------------------------

@@ -1,11 +1,8 @@
 """Connected components on the device: ctseg_components_label, ctseg_components_keep, capstone_amd.components
 (connected_components, keep_largest_component, KeepLargestConnectedComponent) and the BaseUNet3D switch ``largest_component``.
 
-The oracle is numpy and plain Python, independent of scipy and of the product: a flood fill with an explicit stack over the
-neighbour offsets of the given connectivity and axes, started at every unvisited voxel in raster order, so that the first voxel of
-a component is its representative.  It gives the canonical ``ids`` (smallest linear index of the component within the sample, -1
-off the classes) and ``sizes`` (voxel count at the representative, 0 elsewhere); the table and the cleaned map follow from those by
-the rules of include/ctseg_hip.h.  That form is unique, so every comparison is ``array_equal``: there are no tolerances here.
+Held to tests/component_oracles.py, a flood fill in numpy and plain Python that gives the canonical ``ids`` and ``sizes``; that form
+is unique, so every comparison is ``array_equal``: there are no tolerances here.
 
 CPU tests route the two entries through an emulator that IS the oracle; GPU tests hold the kernels to the oracle.
 
@@ -14,7 +11,6 @@ The kernels' tiles: the local pass labels tiles of 8 x 16 x 32 voxels (X, Y, Z) 
 consecutive voxels of a sample.  (9, 17, 33) is one tile plus one voxel on every side; (40, 24, 40) is 5 x 2 x 2 tiles.  No kernel
 is persistent, so CTSEG_MAX_WG does not bear on them.  Every volume here has at most 1e5 voxels.
 """
-import itertools
 import os
 import re
 
@@ -22,129 +18,29 @@ import numpy as np
 import pytest
 import torch
 
-from abi_emulator import mem, patch_native
+from abi_emulator import Emulator, emulated
 from capstone_amd import STRUCTURES, components, segloss, surface
 from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
 from capstone_amd.training.utils import _squash_predictions
 from capstone_amd.volumetric.metrics import DiceMetricWrapper3D
-from test_surface_distance import SurfaceEmulator, as_numpy, ball_labels, check_tables, nan_reduce
-from test_surface_distance import oracle as surface_oracle
+from component_oracles import ALL, C, full_oracle, keep_oracle, label_oracle, neighbour_offsets
+from distance_oracles import ball_labels, check_tables, nan_reduce
+from distance_oracles import surface_oracle
+from feature_emulators import ComponentsEntries, SurfaceEntries
+from helpers import as_numpy
 
 DEV = "cuda:0"
-C = 10
-ALL = (1 << C) - 2
 TILE = (8, 16, 32)
 
 
-# ---- the oracle --------------------------------------------------------------------------------------------------------------
-def neighbour_offsets(connectivity, axes=7):
-    return [d for d in itertools.product((-1, 0, 1), repeat=3)
-            if any(d) and all((axes >> a) & 1 or d[a] == 0 for a in range(3)) and sum(map(abs, d)) <= connectivity]
-
-
-_LABEL_CACHE = {}
-
-
-def label_oracle(L, connectivity, n_classes=C, axes=7):
-    """(B, X, Y, Z) uint8 -> (ids, sizes) int32 of that shape"""
-    key = (L.tobytes(), L.shape, connectivity, n_classes, axes)
-    if key in _LABEL_CACHE:
-        return _LABEL_CACHE[key]
-    B, X, Y, Z = L.shape
-    ids, sizes = np.full(L.shape, -1, np.int32), np.zeros(L.shape, np.int32)
-    sx, sy = (Y + 2) * (Z + 2), Z + 2
-    steps = [dx * sx + dy * sy + dz for dx, dy, dz in neighbour_offsets(connectivity, axes)]
-    for b in range(B):
-        P = np.zeros((X + 2, Y + 2, Z + 2), np.uint8)                      # a border of zeros: no bounds checks, no wrap-around
-        P[1:-1, 1:-1, 1:-1] = np.where(L[b] < n_classes, L[b], 0)
-        flat = P.ravel().tolist()
-        seen = bytearray(len(flat))
-        idb, szb = ids[b].reshape(-1), sizes[b].reshape(-1)
-        for start in np.flatnonzero(P.ravel()).tolist():                  # raster order of the padded and of the plain volume
-            if seen[start]:
-                continue
-            v, stack, members = flat[start], [start], [start]
-            seen[start] = 1
-            while stack:
-                p = stack.pop()
-                for s in steps:
-                    q = p + s
-                    if flat[q] == v and not seen[q]:
-                        seen[q] = 1
-                        stack.append(q)
-                        members.append(q)
-            m = np.asarray(members)
-            lin = ((m // sx - 1) * Y + (m % sx) // sy - 1) * Z + m % sy - 1
-            rep = int(lin.min())
-            assert rep == lin[0]
-            idb[lin] = rep
-            szb[rep] = len(lin)
-    _LABEL_CACHE[key] = (ids, sizes)
-    return ids, sizes
-
-
-def keep_oracle(L, ids, sizes, n_classes=C, class_mask=ALL, keep_largest=True, min_size=0):
-    """-> (cleaned map, table (B, C-1, 4) int32) by the rules of the header"""
-    B = L.shape[0]
-    out, table = L.copy(), np.zeros((B, n_classes - 1, 4), np.int32)
-    table[:, :, 2] = -1
-    for b in range(B):
-        lb, ib, sb = L[b].reshape(-1), ids[b].reshape(-1), sizes[b].reshape(-1)
-        ob = out[b].reshape(-1)
-        for c in range(1, n_classes):
-            reps = np.flatnonzero((sb > 0) & (lb == c))
-            if not len(reps):
-                continue
-            winner = int(reps[np.argmax(sb[reps])])                        # the first of the largest: the smallest representative
-            table[b, c - 1, :3] = [len(reps), sb[winner], winner]
-            if (class_mask >> c) & 1:
-                of_c = np.flatnonzero(lb == c)
-                keep = sb[ib[of_c]] >= min_size
-                if keep_largest:
-                    keep &= ib[of_c] == winner
-                ob[of_c[~keep]] = 0
-                table[b, c - 1, 3] = int((~keep).sum())
-    return out, table
-
-
-def full_oracle(L, connectivity, n_classes=C, class_mask=ALL, keep_largest=True, min_size=0, axes=7):
-    ids, sizes = label_oracle(L, connectivity, n_classes, axes)
-    return (ids, sizes) + keep_oracle(L, ids, sizes, n_classes, class_mask, keep_largest, min_size)
-
-
-# ---- the emulated entries ----------------------------------------------------------------------------------------------------
-class ComponentsEmulator(SurfaceEmulator):
-    def components_label(self, labels, B, X, Y, Z, n_classes, connectivity, axes, ids, sizes):
-        assert labels and ids and sizes and 1 <= connectivity <= 3 and 1 <= axes <= 7 and B * X * Y * Z < 1 << 31
-        n = B * X * Y * Z
-        i, s = label_oracle(mem(labels, n, np.uint8).reshape(B, X, Y, Z).copy(), connectivity, n_classes, axes)
-        mem(ids, n, np.int32)[:] = i.reshape(-1)
-        mem(sizes, n, np.int32)[:] = s.reshape(-1)
-        self.calls += 1
-
-    def components_keep(self, labels, ids, sizes, B, X, Y, Z, n_classes, class_mask, keep_largest, min_size, workspace,
-                        workspace_bytes, out, table):
-        n, K = B * X * Y * Z, n_classes - 1
-        assert labels and ids and sizes and workspace and out and table and workspace_bytes >= B * K * components.KEEP_ROW_BYTES
-        assert keep_largest in (0, 1) and min_size >= 0 and class_mask & ~((1 << n_classes) - 2) == 0
-        L = mem(labels, n, np.uint8).reshape(B, X, Y, Z)
-        o, t = keep_oracle(L, mem(ids, n, np.int32).reshape(L.shape), mem(sizes, n, np.int32).reshape(L.shape), n_classes, class_mask,
-                           bool(keep_largest), min_size)
-        mem(out, n, np.uint8)[:] = o.reshape(-1)
-        mem(table, B * K * 4, np.int32)[:] = t.reshape(-1)
-        self.calls += 1
+class E(ComponentsEntries, SurfaceEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = ComponentsEmulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(E()) as e:
+        yield e
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------

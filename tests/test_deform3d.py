@@ -2,20 +2,16 @@
 (Deform3D, Augment3D(deform=...), augment3d_to_hwd(deform=...), InstancePipeline3D, augmented_degree_2) and the refusal of deformed
 views by TestTimeAugmenter3D.
 
-The oracle is a numpy restatement of the rules in include/ctseg_hip.h: the control lattice from the splitmix64 counter hash in
-uint64 / float64, the cubic B-spline weights and the displacement sum in float32 with the header's order (h innermost, then w, then
-d; every sum from its first product, left to right), added to the affine coordinate.  From that coordinate on it IS the oracle of
-tests/test_augment3d.py: ``deformed`` swaps that module's ``coordinates`` for one that adds the displacement and calls its
-``oracle`` unchanged.  Every device comparison is ``array_equal``.
-
-CPU tests route the two new entries through an emulator that is this oracle; GPU tests hold the kernels to it.
+Held to ``lattice_oracle`` / ``deform_oracle`` of tests/resample_oracles.py, which from the deformed coordinate on ARE its affine
+oracle.  Every device comparison is ``array_equal``.  CPU tests route the two new entries through an emulator that is this oracle;
+GPU tests hold the kernels to it.
 
 The tile is one h, 64 along w, 32 along d, and a workgroup keeps the lattice rows its tile touches in an LDS slab of at most 12 x 20
 rows.  Output (33, 6, 70) has ragged tiles and Gh = 1; (32, 4, 64) with cells (8, 1, 16) has cells of exactly 4 voxels, the largest
 slab; (70, 3, 130) has several tiles on both tiled axes, so slabs that do not start at lattice row 0.  Every output has fewer than
 1e5 voxels.
 
-Two sets of affine parameters.  GENERAL is test_augment3d's.  On the three outputs with 3 to 6 voxels along h its quarter-radian turn
+Two sets of affine parameters.  GENERAL is resample_oracles'.  On the three outputs with 3 to 6 voxels along h its quarter-radian turn
 about d and its h shift of -2.3 voxels alone send 65 %, 75 % and 91 % of the output voxels outside the volume, whatever the lattice
 (figures of the undeformed oracle, border 0; (9, 33, 33): 21 %), so a comparison under it is mostly a comparison of ``cval``.
 LONG_AXES is GENERAL with that turn about h instead, in the plane of the two long axes, no other turn and an h shift of 0.2: under
@@ -24,19 +20,22 @@ to the oracle under both; the two conditions that keep the comparison from being
 and under GENERAL where GENERAL can meet them.
 """
 import ctypes
-from unittest import mock
+import functools
 
 import numpy as np
 import pytest
 import torch
 
-import test_augment3d as A3
-from abi_emulator import mem, patch_native
+import resample_oracles as A3
+from abi_emulator import Emulator, emulated
 from capstone_amd import _native as nat
 from capstone_amd.volumetric import datasets as DS
 from capstone_amd.volumetric import transforms as T
 from capstone_amd.volumetric import tta as TTA
-from test_augment3d import GENERAL, K, SWAPPED, assert_same, inputs
+from feature_emulators import Augment3dEntries, Deform3dEntries, Distmap3dEntries
+from helpers import as_numpy
+from resample_oracles import GENERAL, K, SWAPPED, assert_same, deform_oracle, displacement, inputs, lattice_axis, lattice_oracle, splitmix_scalar
+from resample_oracles import inputs_on_device as on_device
 
 DEV = "cuda:0"
 # (source D, H, W), (output D', H', W'), cells, magnitude: the magnitudes are those under which the two conditions of
@@ -54,78 +53,15 @@ GENERAL_CAN_MEET_THE_CONDITIONS = ((9, 33, 33),)
 
 def matrix(size, which):
     return T.Augment3D.matrix(size, PARAMS[which])
-M64 = (1 << 64) - 1
 
 
-# ---- the oracle --------------------------------------------------------------------------------------------------------------
-def lattice_oracle(seed, cells, magnitude):
-    """[3][Gd+3][Gh+3][Gw+3] float32: (float)((2 u - 1) * (double)magnitude[c]), u from the splitmix64 mix of the counter"""
-    n = [g + 3 for g in cells]
-    c, i, j, k = np.meshgrid(np.arange(3, dtype=np.uint64), *(np.arange(v, dtype=np.uint64) for v in n), indexing="ij")
-    counter = (c << np.uint64(60)) | (i << np.uint64(40)) | (j << np.uint64(20)) | k
-    z = np.uint64(seed & M64) + (counter + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
-    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    z = z ^ (z >> np.uint64(31))
-    u = (z >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
-    mag = np.asarray(magnitude, dtype=np.float32).astype(np.float64).reshape(3, 1, 1, 1)
-    return ((2.0 * u - 1.0) * mag).astype(np.float32)
+def unit_scalar(seed, c, i, j, k):
+    """the uniform of one control point, from the scalar hash of its packed counter"""
+    return (splitmix_scalar(seed, (c << 60) | (i << 40) | (j << 20) | k) >> 11) * 2.0 ** -53
 
 
-def splitmix_scalar(seed, c, i, j, k):
-    """the same hash on Python integers, for one control point"""
-    z = (seed + ((((c << 60) | (i << 40) | (j << 20) | k) + 1) * 0x9E3779B97F4A7C15)) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    z ^= z >> 31
-    return (z >> 11) * 2.0 ** -53
+parent_draw = functools.partial(A3.parent_draw, with_deform=False)           # Augment3D.draw as it was before ``deform`` existed
 
-
-def lattice_axis(n_out, G):
-    """output indices 0..n_out-1 of one axis -> (cell index i, the four float32 B-spline weights of t = u - i)"""
-    f = np.float32
-    g = f(G) / f(n_out)
-    u = np.arange(n_out, dtype=f) * g
-    i = np.minimum(np.floor(u).astype(np.int64), G - 1)
-    t = u - i.astype(f)
-    s = f(1) - t
-    B = [((s * s) * s) / f(6), ((((f(3) * t - f(6)) * t) * t) + f(4)) / f(6),
-         (((((f(-3) * t + f(3)) * t) + f(3)) * t) + f(1)) / f(6), ((t * t) * t) / f(6)]
-    assert all(b.dtype == f for b in B)
-    return i, B
-
-
-def displacement(size, cells, L):
-    """the three float32 (D', H', W') displacement components: sum_a Bd[a] (sum_b Bw[b] (sum_e Bh[e] L[c][id+a][ih+e][iw+b]))"""
-    (idd, Bd), (ih, Bh), (iw, Bw) = (lattice_axis(n, g) for n, g in zip(size, cells))
-    I, J, Kk = idd[:, None, None], ih[None, :, None], iw[None, None, :]
-
-    def total(terms):
-        acc = next(terms)
-        for term in terms:
-            acc = acc + term
-        return acc
-    out = []
-    for c in range(3):
-        out.append(total(Bd[a][:, None, None] * total(Bw[b][None, None, :] * total(
-            Bh[e][None, :, None] * L[c][I + a, J + e, Kk + b] for e in range(4)) for b in range(4)) for a in range(4)))
-        assert out[-1].dtype == np.float32 and out[-1].shape == tuple(size)
-    return out
-
-
-_PLAIN_COORDINATES = A3.coordinates
-
-
-def deformed(s):
-    """a context in which test_augment3d's oracle samples at its affine coordinate + s"""
-    def coordinates(size, A, dtype=np.float32):
-        return [q + d.astype(dtype) for q, d in zip(_PLAIN_COORDINATES(size, A, dtype), s)]
-    return mock.patch.object(A3, "coordinates", coordinates)
-
-
-def deform_oracle(image, masks, size, A, L, cells, **kw):
-    with deformed(displacement(size, cells, L)):
-        return A3.oracle(image, masks, size, A, **kw)
 
 
 _ORACLE = {}
@@ -149,29 +85,14 @@ def conditions(case, which):
     return got[4], float((got[2] != plain[2]).mean())
 
 
-# ---- the emulated entries ------------------------------------------------------------------------------------------------------
-class DeformEmulator(A3.AugmentEmulator):
-    def deform3d_lattice(self, seed, cells, magnitude, lattice, lattice_elems):
-        G, m = mem(cells, 3, np.int32).tolist(), mem(magnitude, 3).tolist()
-        assert all(g >= 1 for g in G) and all(np.isfinite(v) and v >= 0 for v in m)
-        L = lattice_oracle(seed, G, m)
-        assert lattice_elems == L.size
-        mem(lattice, L.size)[:] = L.reshape(-1)
-
-    def augment3d_deform_to_hwd(self, *args):
-        *affine, lattice, cells = args
-        size, G = tuple(affine[7:10]), mem(cells, 3, np.int32).tolist()
-        assert lattice and all(g >= 1 and (1 if a == 1 else 4) * g <= n for a, (g, n) in enumerate(zip(G, size)))
-        n = [g + 3 for g in G]
-        with deformed(displacement(size, G, mem(lattice, 3 * n[0] * n[1] * n[2]).reshape(3, *n).copy())):
-            self.augment3d_to_hwd(*affine)
+class E(Deform3dEntries, Augment3dEntries, Distmap3dEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    undo = patch_native(nat, DeformEmulator())
-    yield
-    undo()
+    with emulated(E(), plan_run=False) as e:
+        yield e
 
 
 @pytest.fixture()
@@ -192,7 +113,7 @@ def test_lattice_oracle_equals_the_scalar_hash():
         L = lattice_oracle(seed, (2, 1, 5), (3.0, 0.0, 0.25))
         assert L.shape == (3, 5, 4, 8) and L.dtype == np.float32 and np.abs(L[0]).max() <= 3.0 and not L[1].any()
         for c, i, j, k in ((0, 0, 0, 0), (0, 4, 3, 7), (2, 1, 2, 3), (2, 4, 0, 6)):
-            want = np.float32((2.0 * splitmix_scalar(seed, c, i, j, k) - 1.0) * (3.0, 0.0, 0.25)[c])
+            want = np.float32((2.0 * unit_scalar(seed, c, i, j, k) - 1.0) * (3.0, 0.0, 0.25)[c])
             assert L[c, i, j, k] == want
     assert len(np.unique(lattice_oracle(0, (8, 1, 16), (1.0, 1.0, 1.0)))) == 3 * 11 * 4 * 19
 
@@ -272,21 +193,6 @@ def test_deform3d_validation():
     T.InstancePipeline3D((96, 256, 256), augment=aug)
     with pytest.raises(ValueError):
         T.InstancePipeline3D((8, 16, 12), augment=aug)
-
-
-def parent_draw(aug, g):
-    """Augment3D.draw as it was before ``deform`` existed, restated"""
-    u = g.random(15)
-    if not u[0] < aug.p:
-        return {"applied": False, "angles": (0.0, 0.0, 0.0), "scales": (1.0, 1.0, 1.0), "shifts": (0.0, 0.0, 0.0),
-                "flips": (False, False, False), "gain": 1.0, "bias": 0.0}
-    sym = 2.0 * u[1:10] - 1.0
-    lo, hi = aug.scale[:, 0], aug.scale[:, 1]
-    gain = 1.0 if aug.gain is None else aug.gain[0] + (aug.gain[1] - aug.gain[0]) * u[13]
-    bias = 0.0 if aug.bias is None else aug.bias[0] + (aug.bias[1] - aug.bias[0]) * u[14]
-    return {"applied": True, "angles": tuple((sym[0:3] * aug.rotate).tolist()), "scales": tuple((lo + (hi - lo) * u[4:7]).tolist()),
-            "shifts": tuple((sym[6:9] * aug.translate).tolist()), "flips": tuple(bool(v) for v in u[10:13] < aug.flip_prob),
-            "gain": float(gain), "bias": float(bias)}
 
 
 AFFINE = dict(rotate=(0.26, 0.05, 0.05), scale=(0.9, 1.1), translate=(2, 8, 8), flip_prob=(0, 0, 0.5), gain=(0.9, 1.1),
@@ -457,15 +363,6 @@ def test_shared_refusals_name_their_own_entry(entry):
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------------
-def on_device(shape, code):
-    image, masks = inputs(shape, code)
-    return torch.from_numpy(np.array(image)).to(DEV), torch.from_numpy(np.array(masks)).to(DEV)
-
-
-def as_numpy(out):
-    return tuple(t.cpu().numpy() for t in out)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=IDS)
 def test_gpu_lattice_equals_the_oracle(case):

@@ -1,179 +1,53 @@
 """Device distance maps of the 2-D pipeline: ctseg_distmap2d_batch, capstone_amd.data.utils.compute_distance_map,
 EnhancedMiccaiDataset2D and the data modules with ``enhanced=True, device_maps=True``.
 
-The oracle is brute force in numpy: for every pixel the minimum of dy^2 + dx^2 over all foreground / background pixels, then the
-byte the reference stores in its uint8 result array
-
-    k = isqrt(d2_fg) & 255 outside, (-(isqrt(d2_bg) - 1)) & 255 inside, 0 on a plane without foreground
-
-and the map k / 255.0.  It is independent of scipy and of the kernel's separable algorithm.  tests/golden/distmap2d_reference.npz
-holds mask stacks and the float64 output of the reference's own compute_distance_map for them (written by
-tools/make_distmap2d_fixture.py); the oracle equals it exactly.  A plane without any background pixel has no defined reference value:
-the product writes 0 there, so does the oracle, and the fixture holds no such plane.
-
-CPU tests route the new entry through an emulator whose ctseg_distmap2d_batch IS the oracle; GPU tests hold the kernel to the
-oracle by array_equal.
+Held to ``distance_oracles.oracle`` on planes (nd = 2) and, through it, to tests/golden/distmap2d_reference.npz.  CPU tests route the
+entry through an emulator whose ctseg_distmap2d_batch IS the oracle; GPU tests hold the kernel to the oracle by array_equal.
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from abi_emulator import Emulator, mem, patch_native
+import distance_oracles as DO
+from abi_emulator import Emulator, emulated
 from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
 from capstone_amd.data import data_module as DM
 from capstone_amd.data import datasets as DS
 from capstone_amd.data import utils as DU
 from capstone_amd.transforms import BatchPipeline2D, ElasticTransform, GridDistortion, SliceStore2D, WarpPipeline2D, predefined
-from test_pipeline2d import DEV, MEAN3, STD3, WINDOWS3, _write_npz, make_masks, make_raw
-from test_warp2d import Warp2dEmulator
+from distance_oracles import DEV, isqrt, pattern_planes, separable_d2_to
+from distance_oracles import blobs as discs
+from feature_emulators import Distmap2dEntries, MixupEntries, Pipeline2dEntries, Warp2dEntries
+from plane_oracles import MEAN3, STD3, WINDOWS3, _write_npz, make_masks, make_raw
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "distmap2d_reference.npz")
 STACKS = ("discs", "discs_small", "long", "patterns")
 
 
-# ---- the oracle --------------------------------------------------------------------------------------------------------------
-def isqrt(v):
-    """floor(sqrt(v)) of a non-negative integer array, exactly"""
-    v = np.asarray(v, dtype=np.int64)
-    r = np.floor(np.sqrt(v.astype(np.float64))).astype(np.int64)
-    r -= r * r > v
-    r += (r + 1) * (r + 1) <= v
-    assert ((r * r <= v) & ((r + 1) * (r + 1) > v)).all()
-    return r
-
-
-def brute_d2_to(sel):
-    """(H, W) bool -> int64 (H, W): min over the set pixels of dy^2 + dx^2; -1 everywhere when there is none"""
-    H, W = sel.shape
-    if not sel.any():
-        return np.full((H, W), -1, np.int64)
-    py, px = np.nonzero(sel)
-    dy2 = (np.arange(H)[:, None] - py[None, :]).astype(np.int32) ** 2             # (H, N)
-    dx2 = (np.arange(W)[:, None] - px[None, :]).astype(np.int32) ** 2             # (W, N)
-    return np.stack([(dx2 + dy2[y][None, :]).min(axis=1) for y in range(H)]).astype(np.int64)
-
-
-def separable_d2_to(sel):
-    """the two-pass exact form (for planes too large for brute force): the vertical distance to the set per column, then
-    min over x' of (x - x')^2 + g[y][x']^2 per row"""
-    H, W = sel.shape
-    if not sel.any():
-        return np.full((H, W), -1, np.int64)
-    big = 1 << 20
-    rows = np.arange(H)
-    dist = np.abs(rows[:, None, None] - rows[None, :, None])                      # (y, y', 1)
-    g = np.where(sel[None, :, :], dist, big).min(axis=1).astype(np.int64)         # (y, x')
-    g2 = np.where(g >= big, np.int64(1) << 40, g * g)
-    dx2 = (np.arange(W)[:, None] - np.arange(W)[None, :]).astype(np.int64) ** 2   # (x, x')
-    return np.stack([(dx2 + g2[y][None, :]).min(axis=1) for y in range(H)])
-
-
-def bytes_of(fg, d2_fg, d2_bg):
-    if not fg.any() or fg.all():
-        return np.zeros(fg.shape, np.int64)
-    return np.where(fg, (-(isqrt(np.maximum(d2_bg, 0)) - 1)) & 255, isqrt(np.maximum(d2_fg, 0)) & 255)
-
-
-_CACHE = {}
-
-
-def oracle(planes, d2_to=brute_d2_to):
-    """(..., H, W) uint8 -> d2_fg, d2_bg int64 and the float64 map k / 255.0, plane by plane (results are shared between tests)"""
-    planes = np.asarray(planes)
-    flat = planes.reshape((-1,) + planes.shape[-2:])
-    out = []
-    for p in flat:
-        key = (d2_to.__name__, p.shape, p.tobytes())
-        if key not in _CACHE:
-            fg = p != 0
-            d2f, d2b = d2_to(fg), d2_to(~fg)
-            _CACHE[key] = (d2f, d2b, bytes_of(fg, d2f, d2b) / 255.0)
-        out.append(_CACHE[key])
-    return tuple(np.stack([o[i] for o in out]).reshape(planes.shape) for i in range(3))
-
-
-def signed_map(planes, d2_fg, d2_bg):
-    """float64: d_out / 255 outside, -(d_in - 1) / 255 inside; 0 on a plane without foreground or without background"""
-    fg = np.asarray(planes) != 0
-    v = np.where(fg, -(np.sqrt(np.maximum(d2_bg, 0).astype(np.float64)) - 1.0), np.sqrt(np.maximum(d2_fg, 0).astype(np.float64))) / 255.0
-    defined = fg.any(axis=(-2, -1), keepdims=True) & ~fg.all(axis=(-2, -1), keepdims=True)
-    return np.where(defined, v, 0.0)
-
-
-# ---- CPU: the emulated entry -------------------------------------------------------------------------------------------------
-class DistmapEmulator(Warp2dEmulator):
-    calls = 0
-
-    def distmap2d_batch(self, masks, P, H, W, mode, table, workspace, workspace_bytes, out, d2_fg, d2_bg):
-        assert masks and table and workspace and out and workspace_bytes >= 4 * P * H * W and mode in (0, 1)
-        assert np.array_equal(mem(table, 256), np.float32(np.arange(256) / 255.0))
-        planes = mem(masks, P * H * W, np.uint8).reshape(P, H, W)
-        d2f, d2b, ref = oracle(planes)
-        mem(out, P * H * W).reshape(P, H, W)[:] = ref if mode == 0 else signed_map(planes, d2f, d2b)
-        if d2_fg:
-            mem(d2_fg, P * H * W, np.int32).reshape(P, H, W)[:] = d2f
-        if d2_bg:
-            mem(d2_bg, P * H * W, np.int32).reshape(P, H, W)[:] = d2b
-        self.calls += 1
-
-
-assert issubclass(DistmapEmulator, Emulator)
+class E(Distmap2dEntries, Warp2dEntries, Pipeline2dEntries, MixupEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = DistmapEmulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(E()) as e:
+        yield e
 
 
-# ---- inputs ------------------------------------------------------------------------------------------------------------------
-def discs(shape, seed, n=3, value=1):
-    rng = np.random.default_rng(seed)
-    H, W = shape
-    yy, xx = np.mgrid[:H, :W]
-    m = np.zeros(shape, np.uint8)
-    for _ in range(n):
-        cy, cx, r = rng.uniform(0, H), rng.uniform(0, W), rng.uniform(0.8, max(1.5, min(H, W) / 3))
-        m[(yy - cy) ** 2 + (xx - cx) ** 2 <= r * r] = value
-    return m
+def oracle(planes, d2_to=None):
+    return DO.oracle(planes, 2, d2_to)
 
 
-def pattern_planes(shape):
-    """random discs; one foreground pixel in each corner in turn; everything foreground but one pixel; an empty and a full plane;
-    horizontal and vertical stripes; a checkerboard; a foreground only in the last row / the last column"""
-    H, W = shape
-    z = lambda: np.zeros(shape, np.uint8)
-    planes = [discs(shape, 1), discs(shape, 2, n=2, value=200)]
-    for y, x in ((0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1)):
-        p = z()
-        p[y, x] = 1
-        planes.append(p)
-    p = np.ones(shape, np.uint8)
-    p[H // 2, (2 * W) // 3] = 0
-    planes += [p, z(), np.full(shape, 3, np.uint8)]
-    p = z()
-    p[::2, :] = 1
-    planes.append(p)
-    p = z()
-    p[:, 1::2] = 1
-    planes.append(p)
-    planes.append((np.add.outer(np.arange(H), np.arange(W)) % 2).astype(np.uint8))
-    p = z()
-    p[H - 1, :] = 1
-    planes.append(p)
-    p = z()
-    p[:, W - 1] = 255
-    planes.append(p)
-    return np.stack(planes)
+def check_reference_mode(planes, d2_to=None):
+    return DO.check_reference_mode(planes, 2, d2_to)
+
+
+signed_map = functools.partial(DO.signed_map, nd=2)
+run_gpu = functools.partial(DO.run_gpu, nd=2)
 
 
 # ---- CPU tests ---------------------------------------------------------------------------------------------------------------
@@ -302,10 +176,10 @@ def test_enhanced_false_is_unchanged(emu, tmp_path):
     out = ds.batch([1, 2], params=params)
     direct = pipe(ds.store, [1, 2], params=params)
     assert len(out) == 3 and torch.equal(out[0], direct[0]) and torch.equal(out[1], direct[1])
-    assert torch.equal(out[2], ds.mask_indicator[[1, 2]]) and not hasattr(out[1], "_ctseg_masks") and emu.calls == 0
+    assert torch.equal(out[2], ds.mask_indicator[[1, 2]]) and not hasattr(out[1], "_ctseg_masks") and emu.distmap2d_calls == 0
     assert len(ds[0]) == 3
     enhanced = DS.get_miccai_2d("train", transform=pipe, enhanced=True, device_maps=True, root=str(tmp_path), device="cpu").batch([1, 2], params=params)
-    assert all(torch.equal(a, b) for a, b in zip(out, enhanced[:3])) and emu.calls == 1
+    assert all(torch.equal(a, b) for a, b in zip(out, enhanced[:3])) and emu.distmap2d_calls == 1
 
 
 def test_data_modules_yield_four_tuples(emu, tmp_path, monkeypatch):
@@ -364,21 +238,6 @@ def test_the_trainers_still_refuse_the_boundary_loss():
 
 
 # ---- GPU tests: the kernel against the oracle, bit for bit -------------------------------------------------------------------
-def run_gpu(planes, **kw):
-    out = DU.compute_distance_map(torch.from_numpy(np.ascontiguousarray(planes)).to(DEV), return_d2=True, **kw)
-    torch.cuda.synchronize()
-    return tuple(o.cpu().numpy() for o in out)
-
-
-def check_reference_mode(planes, d2_to=brute_d2_to):
-    got, d2f, d2b = run_gpu(planes)
-    ref_f, ref_b, ref = oracle(planes, d2_to)
-    assert d2f.dtype == np.int32 and d2b.dtype == np.int32 and got.dtype == np.float32 and got.shape == planes.shape
-    assert np.array_equal(d2f, ref_f), int((d2f != ref_f).sum())
-    assert np.array_equal(d2b, ref_b), int((d2b != ref_b).sum())
-    assert np.array_equal(got, ref.astype(np.float32)), int((got != ref.astype(np.float32)).sum())
-
-
 GPU_SHAPES = [(1, 1), (1, 9), (9, 1), (5, 7), (33, 65), (40, 330)]
 
 

@@ -16,7 +16,7 @@ from capstone_amd.engine import BufferStore, GemmLayer  # noqa: E402
 from capstone_amd.models import UNet  # noqa: E402
 from capstone_amd.plan import _BatchNormAct  # noqa: E402
 from helpers import REL_TOL, MiniPlan, cap_env, from_cl, rel_err, to_cl  # noqa: E402
-from test_batch_norm import swapped_oracle  # noqa: E402
+from helpers import swapped_oracle  # noqa: E402
 
 DEV = "cuda:0"
 

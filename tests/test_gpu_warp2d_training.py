@@ -6,7 +6,7 @@ import torch
 
 from capstone_amd.data import data_module as DM
 from capstone_amd.transforms import ElasticTransform, GridDistortion, WarpPipeline2D, predefined
-from test_pipeline2d import DEV, MEAN3, SOFT, STD3, make_raw
+from plane_oracles import DEV, MEAN3, SOFT, STD3, make_raw
 
 
 def _write_tree(root, split, n, seed):

@@ -5,9 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from abi_emulator import Emulator, patch_native
-from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
+from abi_emulator import Emulator, emulated
 from capstone_amd.models import UNet
 from oracle.monai_unet import UNet as OracleUNet
 from oracle import losses as OL
@@ -16,13 +14,8 @@ from oracle import metrics as OM
 
 @pytest.fixture()
 def emu():
-    e = Emulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]         # the staticmethod itself: restoring the bare function would bind self
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(Emulator()) as e:
+        yield e
 
 
 def _tol(key, ref):

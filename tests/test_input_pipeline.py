@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 import torch
 
-from capstone_amd import _native as nat
 from capstone_amd.volumetric import datasets as DS
 from capstone_amd.volumetric import transforms as T
 from capstone_amd.volumetric.utils import _squash_masks_3D
@@ -64,10 +63,9 @@ def _check_product(gold, tag, dev):
 
 @pytest.fixture()
 def emu():
-    from abi_emulator import Emulator, patch_native
-    undo = patch_native(nat, Emulator())
-    yield
-    undo()
+    from abi_emulator import Emulator, emulated
+    with emulated(Emulator(), plan_run=False):
+        yield
 
 
 @pytest.mark.parametrize("tag", CASES)

@@ -6,18 +6,19 @@ from argparse import ArgumentParser
 import pytest
 import torch
 
-from abi_emulator import patch_native
-from test_boundary_loss_host import BoundaryEmulator
-from capstone_amd import _native as nat
+from abi_emulator import Emulator, emulated
 from capstone_amd import segloss
+from feature_emulators import BoundaryEntries, MixupEntries
+
+
+class E(BoundaryEntries, MixupEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = BoundaryEmulator()
-    undo = patch_native(nat, e)
-    yield e
-    undo()
+    with emulated(E(), plan_run=False) as e:
+        yield e
 
 
 def test_dice_from_counts_is_one_function():

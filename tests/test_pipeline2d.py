@@ -1,13 +1,7 @@
 """The 2-D device input pipeline: capstone_amd.transforms / capstone_amd.data and ctseg_pipeline2d_batch.
 
-The oracle below is a plain numpy restatement of the reference's arithmetic, written from its formulas and not imported from
-the product: apply_window (capstone/transforms/transforms_2d.py:97-107), A.RandomCrop -> np.rot90 -> [:, ::-1], A.Resize (bilinear
-with half-pixel centres on the float64 windowed image, nearest for masks), A.Normalize(max_pixel_value=1.0), _squash_masks and
-weighted_mixup's structure indicator.  OpenCV and albumentations are not available, so parity with them is unpinned; this oracle
-is what the kernel is held to, bit for bit.
-
-CPU tests route the C ABI through a subclass of tests/abi_emulator.Emulator whose pipeline entry IS the oracle; GPU tests compare
-the HIP kernel with the oracle by array_equal.
+Held to the ``o_*`` oracle of tests/plane_oracles.py.  CPU tests route the C ABI through an emulator whose pipeline entry IS the
+oracle; GPU tests compare the HIP kernel with the oracle by array_equal.
 """
 import ctypes
 import itertools
@@ -16,174 +10,24 @@ import numpy as np
 import pytest
 import torch
 
-from abi_emulator import Emulator, mem, patch_native
+from abi_emulator import Emulator, emulated
 from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
 from capstone_amd.data import data_module as DM
 from capstone_amd.data import datasets as DS
 from capstone_amd.transforms import BatchPipeline2D, SliceStore2D, predefined
 from capstone_amd.transforms import transforms_2d as T2
+from feature_emulators import MixupEntries, Pipeline2dEntries
+from helpers import check_bit_exact
+from plane_oracles import DEV, MEAN3, SOFT, STD3, WINDOWS3, _write_npz, make_masks, make_raw, o_normalize, o_window, oracle_batch
 
-DEV = "cuda:0"
-WINDOWS3 = [(80, 40), (350, 20), (2800, 600)]
-SOFT = [(350, 20)]
-MEAN3, STD3 = (0.107, 0.135, 0.085), (0.271, 0.267, 0.152)
-NP_OF_CODE = {0: np.float32, 2: np.int16, 3: np.uint8}
-
-
-# ---- the oracle --------------------------------------------------------------------------------------------------------------
-def o_window(raw, width, level, shift):
-    lo, hi = level - width // 2, level + width // 2
-    if raw.dtype == np.float32:                            # numpy keeps a float32 array in float32
-        v = np.clip(raw, np.float32(lo), np.float32(hi))
-        if shift:
-            v = (v - np.float32(lo)) / np.float32(hi - lo + 1e-8)
-        assert v.dtype == np.float32
-        return v.astype(np.float64)
-    v = np.clip(raw.astype(np.float64), lo, hi)
-    if shift:
-        v = (v - lo) / (hi - lo + 1e-8)
-    return v
-
-
-def o_geometry_crop(x, Ho, Wo, y0, x0, k, flip):
-    r = np.rot90(x[y0:y0 + Ho, x0:x0 + Wo], k)
-    return r[:, ::-1] if flip else r
-
-
-def o_lin_src(out, inn):
-    f = ((np.arange(out, dtype=np.float64) + 0.5) * (inn / out) - 0.5).astype(np.float32)
-    s = np.floor(f).astype(np.int64)
-    w = (f - s.astype(np.float32)).astype(np.float32)
-    low, high = s < 0, s >= inn - 1
-    s[low], w[low] = 0, 0
-    s[high], w[high] = inn - 1, 0
-    return s, np.minimum(s + 1, inn - 1), w
-
-
-def o_resize_linear(x, Ho, Wo):
-    assert x.dtype == np.float64
-    sy, sy1, wy = o_lin_src(Ho, x.shape[0])
-    sx, sx1, wx = o_lin_src(Wo, x.shape[1])
-    h = x[:, sx] * (1 - wx)[None, :] + x[:, sx1] * wx[None, :]              # 1 - w stays float32; the products are float64
-    v = h[sy] * (1 - wy)[:, None] + h[sy1] * wy[:, None]
-    assert v.dtype == np.float64 and (1 - wx).dtype == np.float32
-    return v
-
-
-def o_near_src(out, inn):
-    return np.minimum(np.floor(np.arange(out, dtype=np.float64) * (inn / out)).astype(np.int64), inn - 1)
-
-
-def o_normalize(v, mean, denom):
-    v = v.astype(np.float32)
-    if mean is not None:
-        v = v - np.float32(mean)
-        v = v * np.float32(denom)
-    return v
-
-
-def oracle_batch(raws, masks, rows, mode, size, windows, shift, mean, denom):
-    """raws: list of (H,W) arrays, masks: list of (K,H,W) u8 (or None), rows: (B,5) slice index, y0, x0, k, flip"""
-    Ho, Wo = size
-    images, mouts = [], []
-    for i, y0, x0, k, flip in rows:
-        chans = []
-        for c, (width, level) in enumerate(windows):
-            v = o_window(raws[i], width, level, shift)
-            v = o_geometry_crop(v, Ho, Wo, y0, x0, k, flip) if mode == "crop" else o_resize_linear(v, Ho, Wo)
-            chans.append(o_normalize(v, None if mean is None else mean[c], None if mean is None else denom[c]))
-        images.append(np.stack(chans))
-        if masks is not None:
-            m = masks[i]
-            if mode == "crop":
-                mouts.append(np.stack([o_geometry_crop(p, Ho, Wo, y0, x0, k, flip) for p in m]))
-            else:
-                mouts.append(m[:, o_near_src(Ho, m.shape[1])][:, :, o_near_src(Wo, m.shape[2])])
-    out = {"image": np.stack(images)}
-    if masks is not None:
-        mo = np.stack(mouts)
-        K = mo.shape[1]
-        labels = (mo.astype(np.int64) * np.arange(1, K + 1)[None, :, None, None]).max(1)
-        out.update(masks=mo, labels=labels.astype(np.uint8), present=(mo == 1).any(axis=(2, 3)).astype(np.int32),
-                   hist=np.stack([np.bincount(l.reshape(-1), minlength=K + 1) for l in labels]))
-    return out
-
-
-# ---- CPU: the emulated entry -------------------------------------------------------------------------------------------------
-class Pipeline2dEmulator(Emulator):
-    def squash_masks_present(self, masks, B, K, S, labels, labels_i64, hist, present):
-        self.squash_masks(masks, B, K, S, labels, labels_i64, hist)
-        m = mem(masks, B * K * S, np.uint8).reshape(B, K, S)
-        mem(present, B * K, np.int32).reshape(B, K)[:] |= (m == 1).any(2)
-
-    def mixup_images(self, x, perm, B, n, lam, out):
-        xs = mem(x, B * n).reshape(B, n)
-        mem(out, B * n).reshape(B, n)[:] = np.float32(lam) * xs + np.float32(1.0 - lam) * xs[np.clip(mem(perm, B, np.int32), 0, B - 1)]
-
-    def pipeline2d_batch(self, image_store, dtype, image_elems, mask_store, mask_bytes, table, table_host, B, K, mode, Ho, Wo, C,
-                         win_lo, win_hi, shift, mean, denom, image_out, masks_out, labels_out, hist, present):
-        t = mem(table_host, B * 8, np.int64).reshape(B, 8)
-        assert np.array_equal(t, mem(table, B * 8, np.int64).reshape(B, 8))
-        if mode == 0 and Ho != Wo and (t[:, 6] & 1).any():
-            raise nat.NativeError("pipeline2d_batch: rot90 by an odd k needs a square output")
-        store = mem(image_store, image_elems, NP_OF_CODE[dtype]) if image_store else None
-        mstore = mem(mask_store, mask_bytes, np.uint8) if mask_store else None
-        raws, masks = [], ([] if mask_store else None)
-        for io, mo, H, W in t[:, :4]:
-            raws.append(store[io:io + H * W].reshape(H, W) if store is not None else np.zeros((H, W), np.float32))
-            if mask_store:
-                masks.append(mstore[mo:mo + K * H * W].reshape(K, H, W))
-        # windows back from (lo, hi): width = hi - lo (even in every preset), level = lo + width // 2
-        windows = [(int(h - l), int(l) + int(h - l) // 2) for l, h in zip(list(win_lo or []), list(win_hi or []))] or [(2, 1)]
-        rows = [(b,) + tuple(int(v) for v in t[b, 4:]) for b in range(B)]
-        o = oracle_batch(raws, masks, rows, "crop" if mode == 0 else "resize", (Ho, Wo), windows, bool(shift),
-                         list(mean) if mean else None, list(denom) if mean else None)
-        if image_out:
-            mem(image_out, B * C * Ho * Wo).reshape(B, C, Ho, Wo)[:] = o["image"]
-        if masks_out:
-            mem(masks_out, B * K * Ho * Wo, np.uint8).reshape(B, K, Ho, Wo)[:] = o["masks"]
-        if labels_out:
-            mem(labels_out, B * Ho * Wo, np.uint8).reshape(B, Ho, Wo)[:] = o["labels"]
-        if hist:
-            mem(hist, B * (K + 1), np.int64).reshape(B, K + 1)[:] += o["hist"][:, :K + 1]
-        if present:
-            mem(present, B * K, np.int32).reshape(B, K)[:] |= o["present"]
+class E(Pipeline2dEntries, MixupEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = Pipeline2dEmulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
-
-
-# ---- inputs ------------------------------------------------------------------------------------------------------------------
-def make_raw(shape, dtype, seed):
-    """values straddling every bound of the three windows ([0, 80], [-155, 195], [-800, 2000]) and the type's extremes"""
-    rng = np.random.default_rng(seed)
-    edges = np.array([-801, -800, -799, -156, -155, -154, -1, 0, 1, 79, 80, 81, 194, 195, 196, 1999, 2000, 2001], dtype=np.float64)
-    if dtype == np.int16:
-        pool = np.concatenate([edges, [-32768, 32767], rng.integers(-1100, 2300, 30)])
-    elif dtype == np.uint8:
-        pool = np.concatenate([edges[(edges >= 0) & (edges <= 255)], [255], rng.integers(0, 256, 30)])
-    else:
-        pool = np.concatenate([edges, edges + 0.5, edges - 0.25, [-3.0e4, 6.5e4, 1e-3], rng.normal(100, 700, 30)])
-    return rng.choice(pool, size=shape).astype(dtype)
-
-
-def make_masks(shape, seed, as_bool=False):
-    """9 overlapping structures; structure 2 (index 1) lies wholly under structure 6 (index 5): present, but gone from the label
-    histogram; structure 5 (index 4) is empty"""
-    rng = np.random.default_rng(seed)
-    m = rng.random((9,) + shape) < 0.2
-    m[1] = m[5] & (rng.random(shape) < 0.6)
-    m[4] = False
-    return m if as_bool else m.astype(np.uint8)
+    with emulated(E()) as e:
+        yield e
 
 
 def run_pipeline(raws, masks, rows, mode, size, windows, shift, normalize, device):
@@ -200,16 +44,6 @@ def run_pipeline(raws, masks, rows, mode, size, windows, shift, normalize, devic
                present=pres_a.cpu().numpy(), present_sq=pres_b.cpu().numpy(), hist=lab_b._ctseg_labels[1].cpu().numpy(),
                flat=lab_b._ctseg_labels[0].cpu().numpy())
     return got, ref
-
-
-def check_bit_exact(got, ref):
-    assert got["image"].dtype == np.float32 and ref["image"].dtype == np.float32
-    assert np.array_equal(got["image"], ref["image"]), float(np.abs(got["image"].astype(np.float64) - ref["image"]).max())
-    assert np.array_equal(got["image_sq"], ref["image"])
-    assert np.array_equal(got["masks"], ref["masks"])
-    assert np.array_equal(got["labels"], ref["labels"]) and np.array_equal(got["flat"], ref["labels"].reshape(len(ref["labels"]), -1))
-    assert np.array_equal(got["hist"], ref["hist"])
-    assert np.array_equal(got["present"], ref["present"]) and np.array_equal(got["present_sq"], ref["present"])
 
 
 CROP_SHAPES = [(37, 29), (20, 20), (21, 40)]
@@ -313,21 +147,6 @@ def test_drawn_params_stay_in_range_and_follow_the_reference_probabilities():
     assert np.array_equal(p, pipe.draw_params(sizes, np.random.default_rng(7)))
     q = BatchPipeline2D(WINDOWS3, "crop", (7, 9)).draw_params(sizes, np.random.default_rng(7))
     assert set(q[:, 2]) == {0, 2}                                           # a non-square size is never turned by an odd k
-
-
-def _write_npz(root, split, n, seed, bool_masks):
-    d = root / "miccai_2d" / split
-    d.mkdir(parents=True)
-    rng = np.random.default_rng(seed)
-    raws, masks, inds = [], [], []
-    for i in range(n):
-        shape = (int(rng.integers(12, 20)), int(rng.integers(12, 20)))
-        raws.append(make_raw(shape, np.int16, seed + i))
-        masks.append(make_masks(shape, seed + i, as_bool=bool_masks and i % 2 == 0))
-        inds.append((rng.random(9) < 0.8).astype(np.float64))
-        # written out of order: the dataset sorts by name
-        np.savez(d / f"case{(n - 1 - i):03d}.npz", image=raws[-1][None], masks=masks[-1], mask_indicator=inds[-1])
-    return raws[::-1], masks[::-1], inds[::-1]
 
 
 def test_dataset_store_and_items(emu, tmp_path):

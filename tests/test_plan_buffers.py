@@ -36,10 +36,9 @@ import functools
 import pytest
 import torch
 
-from abi_emulator import Emulator, patch_native
+from abi_emulator import Emulator, emulated
 from capstone_amd import _native as nat
 from capstone_amd import engine as E
-from capstone_amd import plan as plan_mod
 from capstone_amd import segloss
 from capstone_amd.engine import SCRATCH, STATE, ZERO_PAD, ZERO_RESTORED, ZERO_UNWRITTEN, Act, default_ld
 from helpers import ACT_SENTINEL
@@ -240,13 +239,8 @@ def check_pads(plan, entries):
 # ---- CPU: the registry of every configuration's plans ------------------------------------------------------------------------------
 @pytest.fixture()
 def emu():
-    e = Emulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(Emulator()) as e:
+        yield e
 
 
 def _cpu_plan(cfg, inference):

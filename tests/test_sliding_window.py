@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from capstone_amd import _native as nat
-from capstone_amd import inferers, plan as plan_mod
+from capstone_amd import inferers
 from capstone_amd.models import UNet
 from oracle import sliding_window as OS
 from oracle.monai_unet import UNet as OracleUNet
@@ -43,14 +43,9 @@ def test_gaussian_importance_closed_form_equals_filtered_impulse(roi):
 
 @pytest.fixture()
 def emu():
-    from abi_emulator import Emulator, patch_native
-    e = Emulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]         # the staticmethod itself: restoring the bare function would bind self
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    from abi_emulator import Emulator, emulated
+    with emulated(Emulator()) as e:
+        yield e
 
 
 @pytest.mark.parametrize("mode,img,roi,swb", [("constant", (20, 12, 8), (8, 8, 4), 3), ("gaussian", (12, 20, 8), (8, 8, 8), 2),

@@ -1,7 +1,7 @@
 """Surface metrics in physical units: ctseg_distmap3d_weighted, ctseg_surface_select_f32, ``surface_distances(spacing=...)``, the
 wrappers' ``spacing`` and the BaseUNet3D switch ``surface_spacing``.
 
-The oracle is numpy and independent of the product.  Surfaces come from ``surface_of`` of tests/test_surface_distance.py.  With
+The oracle is numpy and independent of the product.  Surfaces come from ``surface_of`` of tests/distance_oracles.py.  With
 w = the float32 squares of the float32 voxel sizes, the squared distance of a voxel to a set is the brute-force minimum over the
 set's voxels, offsets (dx, dy, dz), of the float32 expression the header pins,
 
@@ -29,15 +29,16 @@ import numpy as np
 import pytest
 import torch
 
-from abi_emulator import mem, patch_native
+from abi_emulator import Emulator, emulated
 from capstone_amd import STRUCTURES, surface
 from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
 from capstone_amd.models.metrics import SurfaceDistanceMetricWrapper
 from capstone_amd.training.utils import _squash_predictions
 from capstone_amd.volumetric.metrics import SurfaceDistanceMetricWrapper3D
-from test_surface_distance import (BRUTE_PAIRS, C, DEV, MAX_ROW, SurfaceEmulator, absent_batch, as_numpy, ball_labels, batch_of,
-                                   nan_reduce, oracle, ranks, surface_of)
+from distance_oracles import BRUTE_PAIRS, C, DEV, MAX_ROW, absent_batch, ball_labels, batch_of, d2w_between, d2w_to, nan_reduce, ranks, surface_of
+from distance_oracles import surface_oracle as oracle
+from feature_emulators import SpacingEntries, SurfaceEntries
+from helpers import as_numpy
 
 SPACING = (0.9765625, 1.1, 3.0)
 ROWS3 = ((0.9765625, 1.1, 3.0), (3.0, 0.9765625, 1.1), (1.1, 2.5, 0.7))
@@ -56,37 +57,11 @@ def table_for(spacing, B):
     return np.broadcast_to(w, (B, 3)).copy() if w.ndim == 1 else w
 
 
-def pair_min(a, b, w, dtype=F32):
-    """(n, 3), (m, 3) integer points, w (3,) -> (n,) the minimum over b of the pinned expression, in `dtype` arithmetic"""
-    w = w.astype(dtype)
-    out = np.empty(len(a), dtype)
-    for i in range(0, len(a), 256):
-        d = ((a[i:i + 256, None, :] - b[None, :, :]) ** 2).astype(dtype)             # integer squares below 2^24: exact
-        out[i:i + 256] = (w[1] * d[..., 1] + (w[2] * d[..., 2] + w[0] * d[..., 0])).min(1)
-    return out
-
-
-def d2w_between(src, dst, w, dtype=F32):
-    a, b = np.argwhere(src).astype(np.int64), np.argwhere(dst).astype(np.int64)
-    assert len(a) * len(b) <= BRUTE_PAIRS
-    return pair_min(a, b, w, dtype)
-
-
-def d2w_to(dst, w):
-    """the weighted transform of one volume: 0 on `dst`, the minimum elsewhere, -1 everywhere when `dst` is empty"""
-    out = np.zeros(dst.shape, F32)
-    if not dst.any():
-        out[:] = -1.0
-    elif not dst.all():
-        out[~dst] = d2w_between(~dst, dst, w)
-    return out
-
-
 _CACHE = {}
 
 
 def oracle_w(pred, target, spacing, q=95.0, axes=7, dtype=F32):
-    """as ``oracle`` of tests/test_surface_distance.py with per-sample voxel sizes; dtype = float64: the second tier"""
+    """as ``surface_oracle`` of tests/distance_oracles.py with per-sample voxel sizes; dtype = float64: the second tier"""
     w = table_for(spacing, pred.shape[0])
     key = (pred.tobytes(), target.tobytes(), pred.shape, w.tobytes(), q, axes, np.dtype(dtype).str)
     if key in _CACHE:
@@ -159,46 +134,14 @@ def check_second_tier(got, true):
         assert (err <= 2.0 ** -23).all(), (k, float(err.max()))
 
 
-# ---- the emulated entries ----------------------------------------------------------------------------------------------------
-class SpacingEmulator(SurfaceEmulator):
-    def distmap3d_weighted(self, masks, P, X, Y, Z, w, workspace, workspace_bytes, d2_fg, d2_bg):
-        n = P * X * Y * Z
-        assert masks and w and workspace and d2_fg and not d2_bg and workspace_bytes >= 6 * n
-        vols = mem(masks, n, np.uint8).reshape(P, X, Y, Z) != 0
-        wt = mem(w, P * 3, F32).reshape(P, 3)
-        assert np.isfinite(wt).all() and (wt > 0).all()
-        mem(d2_fg, n, F32).reshape(P, X, Y, Z)[:] = np.stack([d2w_to(v, wt[p]) for p, v in enumerate(vols)])
-        self.calls += 1
-
-    def surface_select_f32(self, edges, d2, counts, B, X, Y, Z, n_classes, q, workspace, workspace_bytes, stats, fstats):
-        rows, S = 2 * B * (n_classes - 1), X * Y * Z
-        assert workspace and workspace_bytes >= rows * surface.SELECT_F32_ROW_BYTES and 0 <= q <= 100
-        e = mem(edges, rows * S, np.uint8).reshape(rows, S) != 0
-        d = mem(d2, rows * S, F32).reshape(rows, S)
-        n = mem(counts, rows, np.int32)
-        st, fs = mem(stats, rows * 4, np.int32).reshape(rows, 4), mem(fstats, rows * 2, F64).reshape(rows, 2)
-        for r in range(rows):
-            o = (r + rows // 2) % rows
-            st[r], fs[r] = 0, 0.0
-            if n[r] > 0 and n[o] > 0:
-                v = np.sort(d[o][e[r]])
-                assert len(v) == n[r] and v[0] >= 0
-                lo, hi, g = ranks(len(v), q)
-                st[r, :3] = np.array([v[lo], v[hi], v[-1]], F32).view(np.int32)
-                st[r, 3] = 1
-                fs[r] = [np.sqrt(v.astype(F64)).sum(), g]
-        self.calls += 1
+class E(SpacingEntries, SurfaceEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = SpacingEmulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(E()) as e:
+        yield e
 
 
 def call(pred, target, dev="cpu", **kw):

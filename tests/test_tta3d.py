@@ -2,11 +2,8 @@
 capstone_amd.volumetric.tta (tta_accumulate, tta_finish, view_to_target_matrix, class_channel_src, mirror_views,
 TestTimeAugmenter3D) and BaseUNet3D(tta=...).
 
-The oracle is a numpy restatement of the rules in include/ctseg_hip.h, independent of torch and of the product: every operation on
-float32 arrays is one float32 rounding, as in the kernel (numpy fuses nothing).  Run with ``dtype=np.float64`` the same functions
-are the float64 form of the interpolation, the softmax and the sums; WHICH voxels a view covers (and the nearest index) stays the
-float32 rule, which is part of the definition of the view, not of the arithmetic.  Every mode-0 comparison is ``array_equal``;
-mode 1 goes through expf, whose last bit numpy does not share, and is held per element to ``helpers.check_elems``.
+Held to ``oracle_accumulate`` / ``oracle_finish`` / ``oracle_run`` of tests/resample_oracles.py.  Every mode-0 comparison is
+``array_equal``; mode 1 goes through expf, whose last bit numpy does not share, and is held per element to ``helpers.check_elems``.
 
 CPU tests route the two entries through an emulator that IS the oracle; GPU tests hold the kernels to the oracle.  Every check is
 one function of the device, run by a CPU test (emulated) and by a GPU test.
@@ -22,15 +19,15 @@ import numpy as np
 import pytest
 import torch
 
-from abi_emulator import mem, patch_native
+from abi_emulator import Emulator, emulated
 from capstone_amd import STRUCTURES
 from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
 from capstone_amd.training.utils import _squash_predictions
 from capstone_amd.volumetric import transforms as T
 from capstone_amd.volumetric import tta
+from feature_emulators import Augment3dEntries, Distmap3dEntries, Tta3dEntries
 from helpers import F32, check_elems, elem_bound
-from test_augment3d import GENERAL, SWAPPED, AugmentEmulator, coordinates, flip_matrix, identity, quarter_turn
+from resample_oracles import GENERAL, SWAPPED, flip_matrix, identity, oracle_finish, oracle_run, quarter_turn
 
 DEV = "cuda:0"
 VIEW_GRIDS = [(33, 6, 70), (9, 33, 33), (32, 4, 64)]                 # (D', H', W'): ragged, square, exact
@@ -57,114 +54,14 @@ CASES = _cases()
 CASE_IDS = [f"{c[0]}->{c[1]} C{c[3][0]}/{c[3][1]}/{c[3][2]}" for c in CASES]
 
 
-# ---- the oracle --------------------------------------------------------------------------------------------------------------
-def softmax_in_order(z):
-    """m = max_c z_c, e_c = exp(z_c - m), s = the sum of e_c in channel order, e_c / s; z (..., C)"""
-    m = z[..., 0]
-    for c in range(1, z.shape[-1]):
-        m = np.maximum(m, z[..., c])
-    e = np.exp(z - m[..., None])
-    s = e[..., 0]
-    for c in range(1, z.shape[-1]):
-        s = s + e[..., c]
-    out = e / s[..., None]
-    assert out.dtype == z.dtype
-    return out
-
-
-def oracle_accumulate(acc, logits, M, chan_src=None, weight=1.0, mode=1, interp=1, target=None, layout=0, dtype=np.float32):
-    """acc (St, >= C + 1) of ``dtype``, updated in place in columns 0..C; logits (H, W, D, C) float32: one view's block.
-    -> the number of target voxels the view covers"""
-    H, W, D, C = logits.shape
-    shape = (D, H, W)
-    target = shape if target is None else tuple(target)
-    q32 = coordinates(target, M, np.float32)
-    q = q32 if dtype == np.float32 else coordinates(target, M, dtype)
-    r = [np.clip(np.floor(q32[a] + np.float32(0.5)), -1, shape[a]).astype(np.int64) for a in range(3)]
-    covered = np.ones(target, dtype=bool)
-    for a in range(3):
-        covered &= (r[a] >= 0) & (r[a] < shape[a])
-    if interp == 0:
-        i = [np.clip(r[a], 0, shape[a] - 1) for a in range(3)]
-        z = logits[i[1], i[2], i[0]].astype(dtype)
-    else:
-        b = [np.floor(q[a]) for a in range(3)]
-        f = [(q[a] - b[a])[..., None] for a in range(3)]
-        corner = [[np.clip(np.clip(b[a], -2, shape[a]).astype(np.int64) + c, 0, shape[a] - 1) for c in (0, 1)] for a in range(3)]
-
-        def lerp(x, y, t):
-            return x + t * (y - x)
-        along_d = []
-        for cd in (0, 1):
-            along_h = []
-            for ch in (0, 1):
-                x, y = (logits[corner[1][ch], corner[2][cw], corner[0][cd]].astype(dtype) for cw in (0, 1))
-                along_h.append(lerp(x, y, f[2]))
-            along_d.append(lerp(along_h[0], along_h[1], f[1]))
-        z = lerp(along_d[0], along_d[1], f[0])
-    assert z.dtype == dtype and z.shape == target + (C,)
-    v = z if mode == 0 else softmax_in_order(z)
-    if chan_src is not None:
-        v = v[..., list(chan_src)]
-    add = dtype(weight) * v
-    if layout == 0:
-        add, covered = np.transpose(add, (1, 2, 0, 3)), np.transpose(covered, (1, 2, 0))
-    add, covered = add.reshape(-1, C), covered.reshape(-1)
-    assert acc.dtype == dtype and acc.shape[0] == covered.size
-    acc[covered, :C] = acc[covered, :C] + add[covered]
-    acc[covered, C] = acc[covered, C] + dtype(weight)
-    return int(covered.sum())
-
-
-def oracle_finish(acc, C, mode):
-    """acc (St, >= C + 1) -> labels (St,) uint8, probs (St, C) of acc's dtype, hist (C,) int64, the number of uncovered voxels"""
-    wsum = acc[:, C]
-    live = wsum != 0
-    labels = np.where(live, np.argmax(acc[:, :C], axis=1), 0).astype(np.uint8)          # (argmax: the first maximal index)
-    u = acc[:, :C] / np.where(live, wsum, 1)[:, None]
-    probs = np.where(live[:, None], u if mode == 1 else softmax_in_order(u), 0).astype(acc.dtype)
-    return labels, probs, np.bincount(labels, minlength=C).astype(np.int64), int((~live).sum())
-
-
-def oracle_run(views, C, target, layout, mode, interp, dtype=np.float32):
-    """views: (logits block (H, W, D, >= C), matrix, chan_src, weight) in order -> acc (St, C + 1) of ``dtype``"""
-    acc = np.zeros((int(np.prod(target)), C + 1), dtype=dtype)
-    for block, M, src, weight in views:
-        oracle_accumulate(acc, block[..., :C], M, src, weight, mode, interp, target, layout, dtype)
-    return acc
-
-
-# ---- the emulated entries ----------------------------------------------------------------------------------------------------
-class TtaEmulator(AugmentEmulator):
-    def tta_accumulate(self, logits, ld, C, D, H, W, matrix, chan_src, weight, mode, interp, Dt, Ht, Wt, layout, acc, acc_ld):
-        M = mem(matrix, 12).reshape(3, 4).copy()
-        src = mem(chan_src, C, np.int32).tolist() if chan_src else None
-        assert logits and acc and np.isfinite(M).all() and np.isfinite(weight) and weight > 0 and mode in (0, 1) and interp in (0, 1)
-        assert layout in (0, 1) and ld % 4 == 0 and 1 <= C <= min(ld, 16) and acc_ld % 4 == 0 and acc_ld >= C + 1
-        assert src is None or sorted(src) == list(range(C))
-        block = mem(logits, H * W * D * ld).reshape(H, W, D, ld)[..., :C]
-        rows = mem(acc, Dt * Ht * Wt * acc_ld).reshape(-1, acc_ld)
-        oracle_accumulate(rows, block, M, src, weight, mode, interp, (Dt, Ht, Wt), layout)
-
-    def tta_finish(self, acc, acc_ld, C, St, mode, labels, probs, hist):
-        assert acc and labels and mode in (0, 1) and acc_ld % 4 == 0 and acc_ld >= C + 1
-        lab, pr, hs, _ = oracle_finish(mem(acc, St * acc_ld).reshape(St, acc_ld), C, mode)
-        mem(labels, St, np.uint8)[:] = lab
-        if probs:
-            mem(probs, St * C).reshape(St, C)[:] = pr
-        if hist:
-            mem(hist, C, np.int64)[:] += hs
+class E(Tta3dEntries, Augment3dEntries, Distmap3dEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = TtaEmulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(E()) as e:
+        yield e
 
 
 @pytest.fixture()

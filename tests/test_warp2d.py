@@ -1,14 +1,8 @@
 """The warping 2-D presets on the device: capstone_amd.transforms.warp2d, predefined.warped and ctseg_pipeline2d_warp_batch.
 
-The restatement below is plain numpy, written from the formulas and not imported from the product.  It is the contract the three
-kernels are held to, bit for bit:
-  * displacement noise: u = (z >> 11) * 2**-53, z = splitmix64 mix of seed + ((f << 40 | i << 20 | j) + 1) * 0x9E3779B97F4A7C15
-    (albumentations' random stream is not reproduced anywhere);
-  * the blur: scipy.ndimage.gaussian_filter's arithmetic (mode "reflect", truncate 4.0, axis 0 then axis 1) in a FIXED summation
-    order; this one is pinned against scipy itself, to summation-order noise;
-  * cv2.warpAffine / cv2.remap / BORDER_REFLECT_101 in OpenCV's fixed point as this project understands it.  OpenCV and
-    albumentations are not available, so parity with them is unpinned, as for A.Resize in tests/test_pipeline2d.py.
-CPU tests route the C ABI through an emulator whose entry IS the restatement; GPU tests compare the kernels with it by array_equal.
+Held to the ``r_*`` restatement of tests/plane_oracles.py, the contract of the three kernels, bit for bit; its blur is pinned against
+scipy here.  CPU tests route the C ABI through an emulator whose entry IS the restatement; GPU tests compare the kernels with it by
+array_equal.
 """
 import ctypes
 
@@ -16,259 +10,26 @@ import numpy as np
 import pytest
 import torch
 
-from abi_emulator import mem, patch_native
+from abi_emulator import Emulator, emulated
 from capstone_amd import _native as nat
-from capstone_amd import plan as plan_mod
 from capstone_amd.data import data_module as DM
 from capstone_amd.transforms import BatchPipeline2D, ElasticTransform, GridDistortion, SliceStore2D, WarpPipeline2D, predefined
 from capstone_amd.transforms import warp2d as W2
-from test_pipeline2d import (DEV, MEAN3, NP_OF_CODE, SOFT, STD3, WINDOWS3, Pipeline2dEmulator, _write_npz, make_masks, make_raw, o_normalize,
-                             o_window)
-
-NONE, ELASTIC, GRID = 0, 1, 2
-F32, F64, I64 = np.float32, np.float64, np.int64
-
-
-# ---- the restatement ---------------------------------------------------------------------------------------------------------
-def r_noise(seed, f, H, W):
-    i, j = np.meshgrid(np.arange(H, dtype=np.uint64), np.arange(W, dtype=np.uint64), indexing="ij")
-    with np.errstate(over="ignore"):
-        ctr = (np.uint64(f) << np.uint64(40)) | (i << np.uint64(20)) | j
-        z = np.uint64(seed) + (ctr + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15)
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z = z ^ (z >> np.uint64(31))
-    u = (z >> np.uint64(11)).astype(F64) * 2.0 ** -53
-    return 2.0 * u - 1.0
+from feature_emulators import MixupEntries, Pipeline2dEntries, Warp2dEntries
+from helpers import check_bit_exact
+from plane_oracles import (DEV, ELASTIC, F32, F64, GRID, I64, MEAN3, NONE, SOFT, STD3, WINDOWS3, _write_npz, make_masks, make_raw, no_ties,
+                           r_batch, r_blur, r_elastic_maps, r_elastic_matrix, r_fields, r_gauss_w, r_grid_table, r_invert, r_noise,
+                           r_reflect_101, r_reflect_sym)
 
 
-def r_reflect_sym(p, n):                                   # d c b a | a b c d
-    p = np.mod(p, 2 * n)
-    return np.where(p < n, p, 2 * n - 1 - p)
-
-
-def r_reflect_101(p, n):                                   # d c b | a b c d: -1 -> 1, n -> n - 2, repeated
-    if n == 1:
-        return np.zeros_like(p)
-    p = np.mod(p, 2 * n - 2)
-    return np.where(p < n, p, 2 * n - 2 - p)
-
-
-def r_gauss_w(sigma):
-    radius = int(4.0 * sigma + 0.5)
-    k = np.arange(-radius, radius + 1)
-    w = np.exp(-0.5 / (sigma * sigma) * k ** 2)
-    return (w / w.sum())[radius:]
-
-
-def r_blur(a, w):
-    """axis 0, then axis 1; per element the centre term first, then k = 1..radius: + (in[l-k] + in[l+k]) * w[k]"""
-    for axis in (0, 1):
-        n = a.shape[axis]
-        idx = np.arange(n)
-        out = np.take(a, idx, axis) * w[0]
-        for k in range(1, len(w)):
-            out = out + (np.take(a, r_reflect_sym(idx - k, n), axis) + np.take(a, r_reflect_sym(idx + k, n), axis)) * w[k]
-        a = out
-    return a
-
-
-def r_fields(seed, H, W, w, alpha):
-    return [np.float32(r_blur(r_noise(seed, f, H, W), w) * alpha) for f in (0, 1)]
-
-
-def r_sat_rint(v):
-    return np.rint(np.clip(v, -2147483648.0, 2147483647.0)).astype(I64)
-
-
-def r_affine_fixed(M, H, W, delta, shift):
-    """(X, Y) of every destination pixel: AB_BITS = 10"""
-    y, x = np.arange(H, dtype=F64)[:, None], np.arange(W, dtype=F64)[None, :]
-    X = (r_sat_rint((M[1] * y + M[2]) * 1024.0) + delta + r_sat_rint(M[0] * x * 1024.0)) >> shift
-    Y = (r_sat_rint((M[4] * y + M[5]) * 1024.0) + delta + r_sat_rint(M[3] * x * 1024.0)) >> shift
-    return X, Y
-
-
-def r_bilinear(img, sx, sy, fx, fy, seen=None):
-    H, W = img.shape
-    if seen is not None:
-        seen.append((sx.min(), (sx + 1).max() - (W - 1), sy.min(), (sy + 1).max() - (H - 1)))
-    c0, c1, r0, r1 = r_reflect_101(sx, W), r_reflect_101(sx + 1, W), r_reflect_101(sy, H), r_reflect_101(sy + 1, H)
-    gx, gy = F32(1) - fx, F32(1) - fy
-    w = [gx * gy, fx * gy, gx * fy, fx * fy]
-    assert all(t.dtype == F32 for t in w) and img.dtype == F64
-    return img[r0, c0] * w[0].astype(F64) + img[r0, c1] * w[1].astype(F64) + img[r1, c0] * w[2].astype(F64) + img[r1, c1] * w[3].astype(F64)
-
-
-def r_warp_affine(img, M, seen=None):
-    X, Y = r_affine_fixed(M, *img.shape, 16, 5)
-    return r_bilinear(img, X >> 5, Y >> 5, (X & 31).astype(F32) / F32(32), (Y & 31).astype(F32) / F32(32), seen)
-
-
-def r_warp_affine_nearest(m, M):
-    X, Y = r_affine_fixed(M, *m.shape[-2:], 512, 10)
-    return m[..., r_reflect_101(Y, m.shape[-2]), r_reflect_101(X, m.shape[-1])]
-
-
-def no_ties(map_v):
-    """no float32 map value within 1e-6 of a rounding tie of lrint(map * 32) or lrint(map)"""
-    t = map_v.astype(F64)
-    return bool((np.abs(t * 32 - np.floor(t * 32) - 0.5) / 32 > 1e-6).all() and (np.abs(t - np.floor(t) - 0.5) > 1e-6).all())
-
-
-def r_elastic_maps(seed, Ho, Wo, gw, alpha):
-    dx, dy = r_fields(seed, Ho, Wo, gw, alpha)
-    yy_, xx_ = np.meshgrid(np.arange(Ho), np.arange(Wo), indexing="ij")
-    return F32(xx_ + dx), F32(yy_ + dy)
-
-
-def r_remap(img, map_x, map_y, seen=None):
-    assert map_x.dtype == F32 and map_y.dtype == F32
-    sx, sy = np.rint(map_x * F32(32)).astype(I64), np.rint(map_y * F32(32)).astype(I64)
-    return r_bilinear(img, sx >> 5, sy >> 5, (sx & 31).astype(F32) / F32(32), (sy & 31).astype(F32) / F32(32), seen)
-
-
-def r_remap_nearest(m, map_x, map_y):
-    ix, iy = np.rint(map_x).astype(I64), np.rint(map_y).astype(I64)
-    return m[..., r_reflect_101(iy, m.shape[-2]), r_reflect_101(ix, m.shape[-1])]
-
-
-def r_invert(M):
-    """cv2.warpAffine's inversion of the forward matrix"""
-    M = np.asarray(M, F64).reshape(6)
-    D = M[0] * M[4] - M[1] * M[3]
-    D = 1.0 / D if D != 0 else 0.0
-    a11, a22 = M[4] * D, M[0] * D
-    m0, m1, m3, m4 = a11, M[1] * -D, M[3] * -D, a22
-    return np.array([m0, m1, -m0 * M[2] - m1 * M[5], m3, m4, -m3 * M[2] - m4 * M[5]])
-
-
-def r_elastic_matrix(size, delta):
-    h, w = size
-    c = F32((h, w)) // 2
-    s = min(h, w) // 3
-    pts1 = F32([c + s, [c[0] + s, c[1] - s], c - s])
-    pts2 = pts1 + F32(delta)
-    return np.linalg.solve(np.concatenate([pts1.astype(F64), np.ones((3, 1))], 1), pts2.astype(F64)).T
-
-
-def r_grid_table(width, num_steps, steps):
-    """the reference's loop (albumentations F.grid_distortion), transcribed"""
-    x_step = width // num_steps
-    xx = np.zeros(width, np.float32)
-    prev = 0
-    for idx in range(num_steps + 1):
-        x = idx * x_step
-        start = int(x)
-        end = int(x) + x_step
-        if end > width:
-            end = width
-            cur = width
-        else:
-            cur = prev + x_step * steps[idx]
-        xx[start:end] = np.linspace(prev, cur, end - start)
-        prev = cur
-    return xx
-
-
-def r_batch(raws, masks, samples, size, windows, shift, mean, denom, gw, alpha, seen=None, check_ties=False):
-    """samples: dicts of i, y0, x0, k, flip, kind and, per kind, minv (6,) + seed, or xx + yy.  -> image, masks, labels, hist, present"""
-    Ho, Wo = size
-    images, mouts = [], []
-    for s in samples:
-        y0, x0 = s["y0"], s["x0"]
-        crop = raws[s["i"]][y0:y0 + Ho, x0:x0 + Wo]
-        m = masks[s["i"]][:, y0:y0 + Ho, x0:x0 + Wo] if masks is not None else None
-        map_x = map_y = None
-        if s["kind"] == ELASTIC:
-            map_x, map_y = r_elastic_maps(s["seed"], Ho, Wo, gw, alpha)
-        elif s["kind"] == GRID:
-            map_x, map_y = np.meshgrid(F32(s["xx"]), F32(s["yy"]))
-        if map_x is not None and check_ties:
-            assert no_ties(map_x) and no_ties(map_y)         # a tie would put the inputs at fault, not the tolerance
-        chans = []
-        for c, (width, level) in enumerate(windows):
-            v = o_window(crop, width, level, shift)
-            if s["kind"] == ELASTIC:
-                v = r_warp_affine(v, s["minv"], seen)
-            if map_x is not None:
-                v = r_remap(v, map_x, map_y, seen)
-            v = np.rot90(v, s["k"])
-            v = v[:, ::-1] if s["flip"] else v
-            chans.append(o_normalize(v, None if mean is None else mean[c], None if mean is None else denom[c]))
-        images.append(np.stack(chans))
-        if m is not None:
-            if s["kind"] == ELASTIC:
-                m = r_warp_affine_nearest(m, s["minv"])
-            if map_x is not None:
-                m = r_remap_nearest(m, map_x, map_y)
-            m = np.rot90(m, s["k"], axes=(1, 2))
-            mouts.append(m[:, :, ::-1] if s["flip"] else m)
-    out = {"image": np.stack(images)}
-    if masks is not None:
-        mo = np.stack(mouts)
-        K = mo.shape[1]
-        labels = (mo.astype(I64) * np.arange(1, K + 1)[None, :, None, None]).max(1)
-        out.update(masks=mo, labels=labels.astype(np.uint8), present=(mo == 1).any(axis=(2, 3)).astype(np.int32),
-                   hist=np.stack([np.bincount(l.reshape(-1), minlength=K + 1) for l in labels]))
-    return out
-
-
-# ---- CPU: the emulated entry -------------------------------------------------------------------------------------------------
-class Warp2dEmulator(Pipeline2dEmulator):
-    def pipeline2d_warp_batch(self, image_store, dtype, image_elems, mask_store, mask_bytes, table, table_host, B, K, Ho, Wo, C, win_lo,
-                              win_hi, shift, mean, denom, gauss_w, radius, alpha, xx, xx_elems, yy, yy_elems, fields, field_tmp, n_slots,
-                              inter, inter_bytes, image_out, masks_out, labels_out, hist, present, launches):
-        t = mem(table_host, B * 19, I64).reshape(B, 19)
-        assert np.array_equal(t, mem(table, B * 19, I64).reshape(B, 19))
-        assert inter and inter_bytes >= B * (C * 8 + (K if mask_store else 0)) * Ho * Wo
-        if Ho != Wo and (t[:, 6] & 1).any():
-            raise nat.NativeError("pipeline2d_warp_batch: rot90 by an odd k needs a square output")
-        if ((t[:, 4] < 0) | (t[:, 5] < 0) | (t[:, 4] + Ho > t[:, 2]) | (t[:, 5] + Wo > t[:, 3])).any():
-            raise nat.NativeError("pipeline2d_warp_batch: crop leaves the slice")
-        store = mem(image_store, image_elems, NP_OF_CODE[dtype])
-        mstore = mem(mask_store, mask_bytes, np.uint8) if mask_store else None
-        gw = mem(gauss_w, radius + 1, F64) if gauss_w else None
-        xs, ys = mem(xx, xx_elems, F32), mem(yy, yy_elems, F32)
-        raws, masks, samples = [], ([] if mask_store else None), []
-        for b, r in enumerate(t):
-            io, mo, H, W = r[:4]
-            raws.append(store[io:io + H * W].reshape(H, W))
-            if mask_store:
-                masks.append(mstore[mo:mo + K * H * W].reshape(K, H, W))
-            s = dict(i=b, y0=int(r[4]), x0=int(r[5]), k=int(r[6]), flip=int(r[7]), kind=int(r[8]))
-            if s["kind"] == ELASTIC:
-                s.update(minv=r[10:16].copy().view(F64), seed=int(r[9:10].view(np.uint64)[0]))
-                if launches & 1:
-                    f = mem(fields, n_slots * 2 * Ho * Wo, F32).reshape(n_slots, 2, Ho, Wo)
-                    f[r[18]] = np.stack(r_fields(s["seed"], Ho, Wo, gw, alpha))
-            elif s["kind"] == GRID:
-                s.update(xx=xs[r[16]:r[16] + Wo], yy=ys[r[17]:r[17] + Ho])
-            samples.append(s)
-        if not launches & 4:
-            return
-        windows = [(int(h - l), int(l) + int(h - l) // 2) for l, h in zip(list(win_lo), list(win_hi))]
-        o = r_batch(raws, masks, samples, (Ho, Wo), windows, bool(shift), list(mean) if mean else None, list(denom) if mean else None, gw, alpha)
-        mem(image_out, B * C * Ho * Wo).reshape(B, C, Ho, Wo)[:] = o["image"]
-        if masks_out:
-            mem(masks_out, B * K * Ho * Wo, np.uint8).reshape(B, K, Ho, Wo)[:] = o["masks"]
-        if labels_out:
-            mem(labels_out, B * Ho * Wo, np.uint8).reshape(B, Ho, Wo)[:] = o["labels"]
-        if hist:
-            mem(hist, B * (K + 1), I64).reshape(B, K + 1)[:] += o["hist"][:, :K + 1]
-        if present:
-            mem(present, B * K, np.int32).reshape(B, K)[:] |= o["present"]
+class E(Warp2dEntries, Pipeline2dEntries, MixupEntries, Emulator):
+    pass
 
 
 @pytest.fixture()
 def emu():
-    e = Warp2dEmulator()
-    undo = patch_native(nat, e)
-    orig = plan_mod.Plan.__dict__["run"]
-    plan_mod.Plan.run = staticmethod(lambda prog, stream, lo=0, hi=None: e.run(prog[lo:hi]))
-    yield e
-    plan_mod.Plan.run = orig
-    undo()
+    with emulated(E()) as e:
+        yield e
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------------
@@ -320,19 +81,6 @@ def run_warp(raws, rows, size, windows, normalize, elastic=None, grid=None, devi
                flat=lab_b._ctseg_labels[0].cpu().numpy())
     assert lab_b._ctseg_present is pres_b and m_a._ctseg_present is pres_a
     return got, ref
-
-
-def check_bit_exact(got, ref):
-    assert got["image"].dtype == np.float32 and ref["image"].dtype == np.float32
-    diff = np.abs(got["image"].astype(F64) - ref["image"])
-    print("image: max |diff|", float(diff.max()), "differing", int((got["image"] != ref["image"]).sum()), "of", diff.size)
-    assert np.array_equal(got["image"], ref["image"])
-    assert np.array_equal(got["image_sq"], ref["image"])
-    assert np.array_equal(got["masks"], ref["masks"])
-    assert np.array_equal(got["labels"], ref["labels"]) and np.array_equal(got["flat"], ref["labels"].reshape(len(ref["labels"]), -1))
-    assert np.array_equal(got["hist"], ref["hist"])
-    assert np.array_equal(got["hist"], np.stack([np.bincount(l.reshape(-1), minlength=10) for l in got["labels"]]))
-    assert np.array_equal(got["present"], ref["present"]) and np.array_equal(got["present_sq"], ref["present"])
 
 
 def elastic_rows(size, el, seed, n=4):
