@@ -177,6 +177,9 @@ _SIGS = {
                                       [_vp] * 7),
     "ctseg_intensity3d": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _f32, _i64, _i32, _f32, _f32, _f32, _vp]),
     "ctseg_intensity3d_launches": (C.c_int, [_vp, _f32, _i32, _f32]),
+    "ctseg_patch_centres": (C.c_int, [_vp] + [_i32] * 4 + [_vp, _i32, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "ctseg_patch_centres_workspace": (_i64, [_i32] * 4),
+    "ctseg_patch3d_to_hwd": (C.c_int, [_vp, _i32, _vp] + [_i32] * 7 + [_vp, _vp, _i32, _i32, _f32, _vp, _i32] + [_f32] * 4 + [_vp] * 5),
     "ctseg_tta_accumulate": (C.c_int, [_vp] + [_i32] * 5 + [_vp, _vp, _f32] + [_i32] * 6 + [_vp, _i32, _vp]),
     "ctseg_tta_finish": (C.c_int, [_vp, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _vp]),
     "ctseg_pipeline2d_batch": (C.c_int, [_vp, _i32, _i64, _vp, _i64, _vp, _vp] + [_i32] * 6 + [_vp, _vp, _i32] + [_vp] * 8),

@@ -29,7 +29,8 @@ class BaseUNet3D(_TrainerBase):
     def __init__(self, filters: List = [16, 32, 64, 128, 256], use_res_units: bool = False, downsample: bool = False,
                  lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
                  surface_metrics: bool = False, surface_percentile: float = 95.0, surface_spacing=None,
-                 largest_component: bool = False, largest_component_connectivity=None, tta=None, **kwargs) -> None:
+                 largest_component: bool = False, largest_component_connectivity=None, tta=None, val_inferer=None,
+                 **kwargs) -> None:
         """``device_boundary``: opt in to the Boundary loss on volumes; the batch then carries the distance maps as its fourth
         element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise.
         ``surface_metrics``: ``validation_step`` also scores the batch with the percentile Hausdorff distance (``surface_percentile``,
@@ -51,7 +52,11 @@ class BaseUNet3D(_TrainerBase):
         every sample once per view, merges the views (``predict_batch``) and scores the ensemble label map IN ADDITION to the plain
         one: its Dice under the prefix ``"val TTA"`` (``"{structure} Dice (val TTA)"``, ``"Mean Dice Score (val TTA)"``) and, with
         ``surface_metrics``, its surface metrics, kept under ``"val TTA"`` and logged as ``"{structure} HD95 (val TTA)"`` and so
-        on.  ``predict_volume`` is the inference call.  Per rank, and never in a training step."""
+        on.  ``predict_volume`` is the inference call.  Per rank, and never in a training step.
+        ``val_inferer``: an ``inferers.SlidingWindowInferer``.  ``validation_step`` then gets its logits from
+        ``val_inferer(images[i:i+1], self)`` per sample instead of one forward pass over the whole grid, so a model trained on
+        patches (``MiccaiDataModule3D(patch_size=...)``) is validated on whole volumes; the losses and the Dice scores come from
+        the same wrappers (``loss_func``, ``dice_score`` on the squashed logits) under the same keys."""
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
@@ -71,6 +76,7 @@ class BaseUNet3D(_TrainerBase):
         self._components_kept = []
         self.tta = tta                                              # (kept out of hparams too)
         self.tta_dice_score = DiceMetricWrapper3D() if tta is not None else None
+        self.val_inferer = val_inferer                              # (kept out of hparams too)
 
     def _construct_model(self):
         # reference :58-72 — in_channels=1, strides for a 5-entry filter list, num_res_units hard-wired to 2
@@ -166,7 +172,10 @@ class BaseUNet3D(_TrainerBase):
         return _StepLossFn.apply(loss, eng, plan, self, *eng.store.params)
 
     def validation_step(self, batch, batch_idx=0):
-        images, masks, _, prediction, _ = self._shared_step(batch, is_training=False)
+        if self.val_inferer is not None:
+            images, masks, prediction = self._inferer_step(batch)
+        else:
+            images, masks, _, prediction, _ = self._shared_step(batch, is_training=False)
         if not (self.surface_metrics or self.largest_component or self.tta is not None):
             return
         with torch.no_grad():
@@ -186,6 +195,21 @@ class BaseUNet3D(_TrainerBase):
                 self._log_dice("val TTA", *self.tta_dice_score(merged, masks))
                 if self.surface_metrics:
                     self._score_surfaces(merged, masks, "val TTA")
+
+    def _inferer_step(self, batch):
+        """``_shared_step`` for validation with ``val_inferer``: the logits of every sample come from the sliding-window inferer
+        (whose result is a view of its own storage, so each is copied into the batch's block), then the same wrappers score them"""
+        images, masks, mask_indicator, dist_maps = self._split_batch(batch)
+        masks = _squash_masks_3D(masks, self._n_classes, self.device)
+        mask_indicator = mask_indicator.type_as(images)
+        with torch.no_grad():
+            prediction = torch.cat([self.val_inferer(images[i:i + 1], self) for i in range(images.shape[0])])
+            loss_dict = self.loss_func(input=prediction, target=masks, mask_indicator=mask_indicator, dist_maps=dist_maps)
+            self._log_losses("val", loss_dict)
+            dice_mean, dice_per_class = self.dice_score(_squash_predictions(prediction), masks)
+            self._keep_dice_counts(self.dice_score.last_counts, "val")
+            self._log_dice("val", dice_mean, dice_per_class)
+        return images, masks, prediction
 
     def predict_volume(self, image, native: bool = True, want_probs: bool = False):
         """the inference call: a raw (D, H, W) scan on the device -> ``TestTimeAugmenter3D.predict``'s namespace, whose ``labels``

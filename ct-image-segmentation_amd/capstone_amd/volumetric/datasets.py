@@ -79,9 +79,55 @@ def collate_3d(samples):
     return images, masks, indicator
 
 
+class MiccaiPatchDataset3D:
+    """The same ``.npz`` instances through a ``transforms.PatchSampler3D``: one item is the list of the sampler's P patches of
+    one volume, each a ``MiccaiDataset3D`` triple at the patch's size: ``(image (1,h,w,d), masks (9,h,w,d), mask_indicator (9,))``,
+    or, with a squashing sampler, ``masks`` = the (h,w,d) uint8 label map carrying its class counts.  ``mask_indicator`` is
+    repeated per patch and permuted by that patch's ``channel_src`` (a left-right mirror swaps the paired structures).
+    ``generator`` (a ``numpy.random.Generator``) feeds the sampler's draws.  ``collate_patches_3d`` makes the trainer's batch."""
+
+    def __init__(self, path: str, sampler, device="cuda", generator=None):
+        self.path = Path(path).absolute()
+        self.sampler, self.generator = sampler, generator
+        self.device = torch.device(device)
+        self.instance_paths = sorted(p.as_posix() for p in self.path.iterdir())
+
+    def __len__(self) -> int:
+        return len(self.instance_paths)
+
+    def __getitem__(self, index: int):
+        instance = np.load(self.instance_paths[index])
+        image, masks, mask_indicator = instance["image"], instance["masks"], instance["mask_indicator"]
+        assert len(mask_indicator) == len(STRUCTURES)
+        assert masks.shape[0] == len(STRUCTURES)
+        image = torch.from_numpy(np.ascontiguousarray(image)).to(self.device, non_blocking=True)
+        masks = torch.from_numpy(np.ascontiguousarray(masks).view(np.uint8) if masks.dtype == np.bool_ else np.ascontiguousarray(masks))
+        masks = masks.to(self.device, non_blocking=True)
+        res = self.sampler(image, masks, generator=self.generator)
+        samples = []
+        for i, src in enumerate(res["channel_src"]):
+            m = res["masks"][i]
+            if res.get("hist") is not None:
+                m._ctseg_hist = res["hist"][i]
+            indicator = torch.from_numpy(mask_indicator[np.asarray(src, dtype=np.int64)]).to(self.device)
+            samples.append((res["image"][i], m, indicator))
+        return samples
+
+
+def collate_patches_3d(items):
+    """list of ``MiccaiPatchDataset3D`` items (each the list of one volume's patches) -> ``collate_3d`` of all their patches, volume
+    by volume: a batch of ``len(items) * P`` samples"""
+    return collate_3d([s for item in items for s in item])
+
+
 def get_miccai_3d(split: str = "train", transform=None, root: str = "storage", device="cuda", dist_maps: bool = False,
-                  signed: bool = False, generator=None):
+                  signed: bool = False, generator=None, patches=None):
+    """``patches`` = a ``transforms.PatchSampler3D``: the split as a ``MiccaiPatchDataset3D`` (no ``transform``, no distance maps)"""
     assert split in ["train", "valid", "test"], "Invalid data split passed"
+    if patches is not None:
+        if transform is not None or dist_maps:
+            raise ValueError("get_miccai_3d(patches=...) takes neither a transform nor dist_maps")
+        return MiccaiPatchDataset3D(f"{root}/miccai_3d/{split}", patches, device=device, generator=generator)
     if transform is None:
         transform = InstancePipeline3D(dist_maps=dist_maps, signed=signed)
     return MiccaiDataset3D(f"{root}/miccai_3d/{split}", transform=transform, device=device, dist_maps=dist_maps, signed=signed,

@@ -19,6 +19,9 @@ device fills from a drawn seed (``ctseg_deform3d_lattice``, then ``ctseg_augment
 ``Intensity3D`` is the second, small stage on that pass' (H', W', D') output: Gaussian blur, additive Gaussian noise and a gamma
 curve (``intensity3d`` -> ``ctseg_intensity3d``), which cannot go into the gather pass: a blur needs a voxel's neighbours on the
 output grid, and noise and gamma come after the window.
+``PatchSampler3D`` is the other route into the trainer: fixed-size patches of the raw volume at its own resolution, most of them
+centred on a voxel of a randomly chosen structure.  The device picks the centres (``patch_centres`` -> ``ctseg_patch_centres``) and
+the crop pass reads them there (``patch3d_to_hwd`` -> ``ctseg_patch3d_to_hwd``, the affine pass about a device-side centre).
 There is no CPU fallback: CPU tensors raise ``NativeError``.
 """
 import ctypes
@@ -49,9 +52,10 @@ def _window_args(window):
     return (2 if shift else 1), float(level - (width // 2)), float(level + (width // 2))
 
 
-def _prepare_call(image, masks, size, who, want_masks, want_labels):
+def _prepare_call(image, masks, size, who, want_masks, want_labels, outs=None):
     """the inputs and outputs of one resample call -> image (D,H,W) contiguous and its dtype code, masks (K,D,H,W) uint8
-    contiguous and K, (D, H, W, D', H', W'), and the outputs (image, masks, labels, hist), None where not asked for"""
+    contiguous and K, (D, H, W, D', H', W'), and the outputs (image, masks, labels, hist), None where not asked for.
+    ``outs``: the caller's own outputs in that order (contiguous, ``hist`` zeroed) instead of new tensors"""
     ref = image if image is not None else masks
     nat.require_gpu(ref, who)
     D, H, W = ref.shape[-3:]
@@ -61,18 +65,25 @@ def _prepare_call(image, masks, size, who, want_masks, want_labels):
     code, K = nat.F32, 0
     if image is not None:
         image, code = _image_code(image.reshape(D, H, W))
-        img_out = torch.empty((Ho, Wo, Do), dtype=torch.float32, device=dev)
+        if outs is None:
+            img_out = torch.empty((Ho, Wo, Do), dtype=torch.float32, device=dev)
     if masks is not None:
         masks = masks.reshape(-1, D, H, W)
         if masks.dtype != torch.uint8:
             masks = masks.to(torch.uint8)
         masks = masks.contiguous()
         K = masks.shape[0]
-        if want_masks:
+        if want_masks and outs is None:
             m_out = torch.empty((K, Ho, Wo, Do), dtype=torch.uint8, device=dev)
-        if want_labels:
+        if want_labels and outs is None:
             lab = torch.empty((Ho, Wo, Do), dtype=torch.uint8, device=dev)
             hist = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    if outs is not None:
+        img_out, m_out, lab, hist = outs
+        for t, shape, dtype in ((img_out, (Ho, Wo, Do), torch.float32), (m_out, (K, Ho, Wo, Do), torch.uint8),
+                                (lab, (Ho, Wo, Do), torch.uint8), (hist, (K + 1,), torch.int64)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
+                raise ValueError(f"{who}: an output is a contiguous {dtype} tensor of shape {shape} on the inputs' device")
     return image, code, masks, K, (D, H, W, Do, Ho, Wo), (img_out, m_out, lab, hist)
 
 
@@ -155,6 +166,87 @@ def augment3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor
     else:
         lattice, cells = _lattice(deform, (image if image is not None else masks).device)
         nat.call("ctseg_augment3d_deform_to_hwd", *args, nat.ptr(lattice), ctypes.addressof(cells))
+    return outs
+
+
+# the block counts of the centre pick: one int32 buffer per (device, stream), grown on demand, reused as the lattice above is (the
+# next call's count pass is ordered behind this call's select pass on the same stream)
+_PATCH_WORKSPACES = {}
+_MAX_PATCHES = 16
+
+
+def _c_draws(draws):
+    """P rows (fg, a, b) as the P x 3 uint32 the centre pick reads: fg is any truth value, a and b are integers in [0, 2^32)"""
+    rows = [(1 if fg else 0, int(a), int(b)) for fg, a, b in draws]
+    if not 1 <= len(rows) <= _MAX_PATCHES:
+        raise ValueError(f"patch_centres: {len(rows)} draws, 1 to {_MAX_PATCHES} patches are taken per call")
+    if not all(0 <= v < 2 ** 32 for row in rows for v in row[1:]):
+        raise ValueError("patch_centres: a and b are integers in [0, 2^32)")
+    return (ctypes.c_uint32 * (3 * len(rows)))(*(v for row in rows for v in row)), len(rows)
+
+
+def patch_centres(masks: torch.Tensor, draws, patch=None, class_mask: Optional[int] = None,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """P patch centres on the device (``ctseg_patch_centres``; include/ctseg_hip.h has the rule word for word).  ``masks``
+    (K,D,H,W) uint8 on the device, K <= 15; ``draws`` = P <= 16 host rows (fg, a, b): with fg set, the class is the
+    ``a * m >> 32``-th of the m eligible classes (bit k of ``class_mask`` set, default all, and mask k not empty) and the centre
+    the ``b * n >> 32``-th of its n set voxels in raster order; otherwise (or with no eligible class) the class is -1 and the
+    centre is voxel ``b * D*H*W >> 32``.  ``patch`` = (d, h, w) clamps the centre so that a patch starting at ``c - patch // 2``
+    stays inside the volume.  ``workspace``: the caller's int32 scratch of ``ctseg_patch_centres_workspace`` bytes, any content
+    (default: a cached one per device and stream).  -> (P, 4) int32 device tensor, rows (d, h, w, class); nothing is read back"""
+    nat.require_gpu(masks, "patch_centres")
+    if masks.dim() != 4 or masks.dtype != torch.uint8:
+        raise ValueError("patch_centres: masks is a (K, D, H, W) uint8 tensor")
+    masks = masks.contiguous()
+    K, D, H, W = masks.shape
+    c_draws, P = _c_draws(draws)
+    need = nat.lib().ctseg_patch_centres_workspace(K, D, H, W)
+    if need < 0:
+        nat.check(-1, "ctseg_patch_centres_workspace")
+    if workspace is None:
+        key = (masks.device, nat.stream_ptr())
+        workspace = _PATCH_WORKSPACES.get(key)
+        if workspace is None or workspace.numel() * 4 < need:
+            _PATCH_WORKSPACES[key] = workspace = torch.empty(need // 4, dtype=torch.int32, device=masks.device)
+    elif workspace.dtype != torch.int32 or not workspace.is_contiguous() or workspace.device != masks.device:
+        raise ValueError("patch_centres: workspace is a contiguous int32 tensor on the masks' device")
+    c_patch = None if patch is None else (ctypes.c_int32 * 3)(*(int(v) for v in patch))
+    centres = torch.empty((P, 4), dtype=torch.int32, device=masks.device)
+    nat.call("ctseg_patch_centres", nat.ptr(masks), K, D, H, W, ctypes.addressof(c_draws), P,
+             (1 << K) - 1 if class_mask is None else int(class_mask), ctypes.addressof(c_patch) if c_patch is not None else None,
+             nat.ptr(workspace), workspace.numel() * 4, nat.ptr(centres))
+    return centres
+
+
+def patch_matrix(patch, matrix=None) -> np.ndarray:
+    """the (3, 4) float32 matrix of a patch of ``patch`` = (d, h, w) voxels about its centre: ``matrix`` (a float64 map of the
+    patch grid onto itself such as ``Augment3D.matrix(patch, params, np.float64)``; None: the identity) with ``patch // 2``
+    subtracted from its translation, rounded to float32 once.  The identity gives whole sampling coordinates: an exact crop"""
+    out = np.eye(3, 4, dtype=np.float64) if matrix is None else np.array(matrix, dtype=np.float64).reshape(3, 4)
+    out[:, 3] -= np.asarray([int(v) // 2 for v in patch], dtype=np.float64)
+    return out.astype(np.float32)
+
+
+def patch3d_to_hwd(image: Optional[torch.Tensor], masks: Optional[torch.Tensor], patch: Sequence[int], matrix, centre: torch.Tensor,
+                   interp=1, border="constant", cval: float = 0.0, mask_src=None, window=None, gain: float = 1.0, bias: float = 0.0,
+                   want_masks: bool = True, want_labels: bool = False, outs=None):
+    """``augment3d_to_hwd`` on a patch about a centre that stays on the device (``ctseg_patch3d_to_hwd``): ``matrix`` maps an
+    output voxel of the ``patch`` = (d, h, w) grid to a point of the SOURCE grid, relative to ``centre``, an int32 device tensor
+    whose first three entries are (d, h, w), such as a row of ``patch_centres``' table; the kernel adds the centre to the
+    translation column, one float32 add per axis, and is the affine pass with that matrix from there on.  There is no resize: the
+    patch has the source's resolution.  ``patch_matrix(patch)`` is the exact crop ``src[c - patch // 2 + o]``.  ``outs``: the
+    caller's own output tensors (image, masks, labels, hist; ``hist`` zeroed) instead of new ones.
+    -> image (h,w,d) fp32, masks (K,h,w,d) u8, labels (h,w,d) u8, hist (K+1)"""
+    image, code, masks, K, dims, outs = _prepare_call(image, masks, patch, "patch3d_to_hwd", want_masks, want_labels, outs)
+    ref = image if image is not None else masks
+    if centre.dtype != torch.int32 or centre.numel() < 3 or not centre.is_contiguous() or centre.device != ref.device:
+        raise ValueError("patch3d_to_hwd: centre is a contiguous int32 tensor of at least 3 entries (d, h, w) on the inputs' device")
+    mat = _c_matrix(matrix)
+    src = _c_permutation(mask_src, K, "patch3d_to_hwd: mask_src", "mask channels")
+    nat.call("ctseg_patch3d_to_hwd", nat.ptr(image), code, nat.ptr(masks), K, *dims, ctypes.addressof(mat), nat.ptr(centre),
+             _INTERPS.get(interp, interp), _BORDERS.get(border, border), float(cval),
+             ctypes.addressof(src) if src is not None else None, *_window_args(window), float(gain), float(bias),
+             *(nat.ptr(t) for t in outs))
     return outs
 
 
@@ -484,6 +576,94 @@ class InstancePipeline3D:
             out["hist"] = hist
         if self.dist_maps:
             out["dist_maps"] = compute_distance_map(m, signed=self.signed, spatial_dims=3)
+        return out
+
+
+class PatchSampler3D:
+    """Foreground-biased patches of a raw volume at its own resolution (MONAI's ``RandCropByPosNegLabel``, nnU-Net's foreground
+    oversampling), which the reference's 3-D path lacks: ``num_patches`` patches of ``patch`` = (D', H', W') voxels (the order of
+    ``InstancePipeline3D.size``), each with probability ``fg_prob`` centred on a voxel of a structure drawn with equal chance per
+    class among those of ``class_mask`` (bit k = mask k; default all) that the volume has, otherwise on a uniform voxel.  The
+    device picks the centres (``patch_centres``) and every patch is one ``patch3d_to_hwd`` launch reading its centre there: nothing
+    in the call reads device memory back.  ``squash`` / ``window`` as ``InstancePipeline3D``.
+    ``augment`` = an ``Augment3D`` that contributes rotation, zoom, mirrors and gain / bias about the patch centre (its matrix on
+    the patch grid, composed in float64, moved by ``patch // 2`` and rounded once: ``patch_matrix``), its ``interp`` / ``border`` /
+    ``cval``, and its ``intensity`` stage after the pass; ``translate`` (the centre is the translation) and ``deform`` raise
+    ``ValueError``.  Without one the matrix is the identity with translation ``-(patch // 2)``: an exact crop.
+
+    ``draw`` takes, per patch and in this order, a fixed number of values from the ``numpy.random.Generator``: one uniform (the fg
+    chance), two integers in [0, 2^32) (``a``: the class, ``b``: the rank), then ``Augment3D.draw``'s own values when there is
+    an ``augment`` (15 uniforms, 7 more values with an ``intensity``).  A seed therefore reproduces an epoch."""
+
+    def __init__(self, patch, num_patches: int = 2, fg_prob: float = 2 / 3, class_mask: Optional[int] = None, squash: bool = False,
+                 window: Optional[Tuple] = None, augment: Optional[Augment3D] = None):
+        self.patch = tuple(int(v) for v in patch)
+        self.num_patches, self.fg_prob, self.class_mask = int(num_patches), float(fg_prob), class_mask
+        if len(self.patch) != 3 or min(self.patch) < 1:
+            raise ValueError("PatchSampler3D: patch is (D', H', W'), every side at least 1")
+        if not 1 <= self.num_patches <= _MAX_PATCHES:
+            raise ValueError(f"PatchSampler3D: num_patches lies in [1, {_MAX_PATCHES}]")
+        if not 0.0 <= self.fg_prob <= 1.0:
+            raise ValueError("PatchSampler3D: fg_prob is a probability")
+        if augment is not None and (augment.translate != 0).any():
+            raise ValueError("PatchSampler3D: augment.translate must be 0 (the patch centre is the translation)")
+        if augment is not None and augment.deform is not None:
+            raise ValueError("PatchSampler3D: an augment with a deform is not supported on patches")
+        self.squash, self.window, self.augment = squash, window, augment
+        self._rng = np.random.default_rng()
+
+    def draw(self, generator=None) -> list:
+        """one volume's draws: ``num_patches`` tuples (fg, a, b, params), ``params`` = ``Augment3D.draw``'s dict or None"""
+        g = generator if generator is not None else self._rng
+        out = []
+        for _ in range(self.num_patches):
+            chance, a, b = g.random(), int(g.integers(0, 2 ** 32)), int(g.integers(0, 2 ** 32))
+            out.append((chance < self.fg_prob, a, b, self.augment.draw(g) if self.augment is not None else None))
+        return out
+
+    def matrix(self, params=None) -> np.ndarray:
+        """the (3, 4) float32 matrix of one patch: see ``patch_matrix``"""
+        return patch_matrix(self.patch, None if params is None else Augment3D.matrix(self.patch, params, np.float64))
+
+    def __call__(self, image: torch.Tensor, masks, generator=None, draws=None) -> dict:
+        """image (1,D,H,W) or (D,H,W), masks (K,D,H,W) on the device; ``draws`` = ``draw``'s list (rows (fg, a, b) alone mean no
+        augmentation), drawn from ``generator`` when None -> {"image": (P,1,h,w,d) fp32, "masks": (P,K,h,w,d) uint8 or, squashing,
+        the (P,h,w,d) label maps with "hist": (P,K+1), "centres": the (P,4) int32 device table, "channel_src": one list per
+        patch, "draws"}"""
+        if isinstance(masks, (list, tuple)):
+            masks = torch.stack(list(masks))
+        masks = masks.reshape((-1,) + tuple(masks.shape[-3:]))
+        if masks.dtype != torch.uint8:
+            masks = masks.to(torch.uint8)
+        masks = masks.contiguous()
+        if draws is None:
+            draws = self.draw(generator)
+        draws = [tuple(d) + (None,) * (4 - len(d)) for d in draws]
+        P, K, dev = len(draws), masks.shape[0], masks.device
+        Do, Ho, Wo = self.patch
+        centres = patch_centres(masks, [d[:3] for d in draws], self.patch, self.class_mask)
+        img = torch.empty((P, 1, Ho, Wo, Do), dtype=torch.float32, device=dev)
+        m = lab = hist = None
+        if self.squash:
+            lab = torch.empty((P, Ho, Wo, Do), dtype=torch.uint8, device=dev)
+            hist = torch.zeros((P, K + 1), dtype=torch.int64, device=dev)
+        else:
+            m = torch.empty((P, K, Ho, Wo, Do), dtype=torch.uint8, device=dev)
+        aug, srcs = self.augment, []
+        for i, (_, _, _, params) in enumerate(draws):
+            src = aug.channel_src(params, K) if aug is not None and params is not None else list(range(K))
+            srcs.append(src)
+            outs = (img[i, 0], None if m is None else m[i], None if lab is None else lab[i], None if hist is None else hist[i])
+            if aug is None or params is None:
+                patch3d_to_hwd(image, masks, self.patch, self.matrix(), centres[i], 0, window=self.window, outs=outs)
+                continue
+            patch3d_to_hwd(image, masks, self.patch, self.matrix(params), centres[i], aug.interp, aug.border, aug.cval, src,
+                           self.window, params["gain"], params["bias"], outs=outs)
+            if params.get("intensity") is not None:
+                intensity3d(img[i, 0], **params["intensity"], out=img[i, 0])
+        out = {"image": img, "masks": lab if self.squash else m, "centres": centres, "channel_src": srcs, "draws": draws}
+        if self.squash:
+            out["hist"] = hist
         return out
 
 

@@ -1,9 +1,9 @@
-// The tile of the 3-D resample passes of the input pipeline, shared by resize3d.hip (nearest resize), augment3d.hip (affine) and
-// deform3d.hip (affine + B-spline lattice): the arguments, the entries' shared validation and the two-phase workgroup body.  One
-// workgroup = one h, a 64-wide w tile and a 32-deep d tile.  Phase 1 has lanes along output w (the resize, and the small rotations
+// The tile of the 3-D resample passes of the input pipeline, shared by resize3d.hip (nearest resize), augment3d.hip (affine),
+// deform3d.hip (affine + B-spline lattice) and patch3d.hip (affine on the source grid, about a device-side centre): the arguments,
+// the entries' shared validation and the two-phase workgroup body.  One workgroup = one h, a 64-wide w tile and a 32-deep d tile.  Phase 1 has lanes along output w (the resize, and the small rotations
 // of an augmentation, make neighbouring lanes read neighbouring source w, the source's contiguous axis), phase 2 has lanes along d,
 // the output's contiguous axis; the transposition goes through LDS, rows padded to an odd dword count.  Where the source voxel
-// comes from is a compile-time choice (Coord); from the fetched value on the three passes are one text.
+// comes from is a compile-time choice (Coord); from the fetched value on the passes are one text.
 // Every float operation is one float32 rounding: nothing may be contracted into an FMA.
 #pragma once
 #pragma clang fp contract(off)
@@ -23,7 +23,9 @@ constexpr int DF_RD = 12, DF_RW = 20;
 //   RESIZE   the separable nearest index of the output voxel itself, 64-bit offsets: no limit on the volumes
 //   AFFINE   the output voxel goes through a 3 x 4 matrix first; 32-bit per-lane offsets (the entry checks 2^31 voxels)
 //   LATTICE  AFFINE, and the sampling coordinate gains the displacement of a control lattice
-enum class Coord { RESIZE, AFFINE, LATTICE };
+//   PATCH    AFFINE with the matrix addressing the SOURCE grid itself (D x H x W, every scale 1): the output dims only tile the
+//            pass and lay out its stores (patch3d.hip, whose kernel moves the translation column by a centre it reads)
+enum class Coord { RESIZE, AFFINE, LATTICE, PATCH };
 
 // everything a lane needs besides pointers, in the kernel's arguments (scalar registers): no table in memory
 struct Resize3dArgs {
@@ -33,7 +35,8 @@ struct Resize3dArgs {
 };
 struct Aug3dArgs : Resize3dArgs {
   int border, apply_gain;
-  Affine3d m;                        // output voxel -> the point of the virtual resized volume it samples
+  Affine3d m;                        // output voxel -> the point it samples, on the grid the matrix addresses: the virtual resized
+                                     // volume (Do x Ho x Wo), or the source grid itself for Coord::PATCH
   float cval, gain, bias;
   unsigned long long perm;           // 4 bits per output channel: its input channel
 };
@@ -87,7 +90,7 @@ __device__ __forceinline__ void resample3d_tile(const TI* __restrict__ image, co
                                                 float* __restrict__ image_out, uint8_t* __restrict__ masks_out,
                                                 uint8_t* __restrict__ labels_out, unsigned long long* __restrict__ hist,
                                                 const float* __restrict__ lattice, const Deform3dArgs dg) {
-  constexpr bool RESIZE = SRC == Coord::RESIZE, DEFORM = SRC == Coord::LATTICE;
+  constexpr bool RESIZE = SRC == Coord::RESIZE, DEFORM = SRC == Coord::LATTICE, PATCH = SRC == Coord::PATCH;
   static_assert(std::is_same<Args, std::conditional_t<RESIZE, Resize3dArgs, Aug3dArgs>>::value, "the argument block of the source");
   using Off = std::conditional_t<RESIZE, int64_t, int>;          // an offset into a volume
   using SrcOff = std::conditional_t<RESIZE, int64_t, unsigned>;   // the source voxel's, zero-extended where it is 32-bit
@@ -100,6 +103,7 @@ __device__ __forceinline__ void resample3d_tile(const TI* __restrict__ image, co
   __shared__ float s_slab[DEFORM ? 3 : 1][DEFORM ? DF_RD : 1][DEFORM ? DF_RW : 1];
   const int t = threadIdx.x;
   const int K = p.K, D = p.D, H = p.H, W = p.W, Do = p.Do, Ho = p.Ho, Wo = p.Wo;
+  const int Vd = PATCH ? D : Do, Vh = PATCH ? H : Ho, Vw = PATCH ? W : Wo;      // the grid the matrix addresses
   const int ndt = (Do + RS_TD - 1) / RS_TD;
   const int d0 = (blockIdx.x % ndt) * RS_TD, w0 = (blockIdx.x / ndt) * RS_TW, h = blockIdx.y;
   if (t <= RS_KMAX) s_h[t] = 0;
@@ -157,9 +161,9 @@ __device__ __forceinline__ void resample3d_tile(const TI* __restrict__ image, co
           }
           qd = qd + s[0], qh = qh + s[1], qw = qw + s[2];
         }
-        const int nd = ag_axis(affine3d_whole(qd), Do, D, p.sD, p.border, okd);
-        const int nh = ag_axis(affine3d_whole(qh), Ho, H, p.sH, p.border, okh);
-        const int nw = ag_axis(affine3d_whole(qw), Wo, W, p.sW, p.border, okw);
+        const int nd = ag_axis(affine3d_whole(qd), Vd, D, p.sD, p.border, okd);
+        const int nh = ag_axis(affine3d_whole(qh), Vh, H, p.sH, p.border, okh);
+        const int nw = ag_axis(affine3d_whole(qw), Vw, W, p.sW, p.border, okw);
         src = (unsigned)((nd * H + nh) * W + nw);             // < 2^31: the entry checks D * H * W
       }
       const bool inside = okd && okh && okw;
@@ -175,9 +179,9 @@ __device__ __forceinline__ void resample3d_tile(const TI* __restrict__ image, co
           bool od[2], oh[2], ow[2];
           int id[2], ih[2], iw[2];
           for (int c = 0; c < 2; ++c) {
-            id[c] = ag_axis(affine3d_corner(bd, Do) + (float)c, Do, D, p.sD, p.border, od[c]) * HW;
-            ih[c] = ag_axis(affine3d_corner(bh, Ho) + (float)c, Ho, H, p.sH, p.border, oh[c]) * W;
-            iw[c] = ag_axis(affine3d_corner(bw, Wo) + (float)c, Wo, W, p.sW, p.border, ow[c]);
+            id[c] = ag_axis(affine3d_corner(bd, Vd) + (float)c, Vd, D, p.sD, p.border, od[c]) * HW;
+            ih[c] = ag_axis(affine3d_corner(bh, Vh) + (float)c, Vh, H, p.sH, p.border, oh[c]) * W;
+            iw[c] = ag_axis(affine3d_corner(bw, Vw) + (float)c, Vw, W, p.sW, p.border, ow[c]);
           }
           float cd[2];
           for (int a = 0; a < 2; ++a) {

@@ -532,6 +532,56 @@ int ctseg_intensity3d(const float* image, float* image_out, int32_t Do, int32_t 
                       float gamma, void* stream);
 int ctseg_intensity3d_launches(const int32_t* radius /* host, 3 */, float noise_std, int32_t has_range, float gamma);
 
+/* Foreground-biased patch sampling for training at native resolution (MONAI's RandCropByPosNegLabel, nnU-Net's foreground
+ * oversampling): ctseg_patch_centres picks P patch centres on the device, most of them on a voxel of a structure drawn with equal
+ * chance per class, and ctseg_patch3d_to_hwd crops (or resamples) a patch around a centre that only the device knows.
+ *
+ * ctseg_patch_centres.  masks is the raw [K][D][H][W] u8 block (DEVICE); a voxel is set where its byte is nonzero; structures may
+ * overlap.  Limits: 1 <= K <= 15, 1 <= P <= 16, D * H * W < 2^31.  draws (HOST, P x 3 uint32: fg, a, b per patch) and patch (HOST,
+ * 3 ints ordered d, h, w, or NULL) are copied into the kernel's arguments: no upload, no synchronisation.  Everything is integer
+ * arithmetic; there is no float operation and no host round trip.
+ *   - n_k is the number of set voxels of mask k.
+ *   - The eligible classes are those with bit k set in class_mask and n_k > 0, in ascending k; m is their number.
+ *   - If fg != 0 and m > 0: class = eligible[(uint64)a * m >> 32], rank r = (uint64)b * n_class >> 32, and the centre is the r-th
+ *     set voxel of that mask in raster (d, h, w) order (r = 0 is the first).
+ *   - Otherwise class = -1 and the centre is voxel (uint64)b * (D * H * W) >> 32 of the volume, in raster order.
+ *   - Clamp, applied when patch is given: along each axis a with dim_a >= patch_a, c_a is clamped into
+ *     [patch_a / 2, dim_a - (patch_a - patch_a / 2)] (integer division); along an axis with dim_a < patch_a, c_a = dim_a / 2.
+ *     A patch that starts at c_a - patch_a / 2 then lies inside the volume wherever the volume is large enough.
+ *   - centres (DEVICE, P x 4 int32): centres[p] = (d, h, w, class).
+ * Two launches.  The count pass reads every mask byte once with 16-byte loads and writes one int32 count per (class, block of 16384
+ * voxels) to the workspace; the select pass, one workgroup per patch, sums each class's counts in a fixed order (the K totals,
+ * which it also stores behind the counts: workspace word K * nb + k, nb = ceil(D * H * W / 16384)), finds the block by a prefix
+ * scan over the class's counts and the voxel inside it by per-lane byte counts and a second scan.  Every workspace word that is
+ * read has been written by the count pass of the same call, so the workspace may arrive with any content, and nothing is summed
+ * by atomics: two runs give the same bits.
+ * ctseg_patch_centres_workspace returns the bytes needed, 4 * (K * ceil(D * H * W / 16384) + 16), or a negative value where the
+ * entry refuses the geometry; it touches no device.
+ * Rejected before any launch: a null masks, draws, workspace or centres; P outside [1, 16]; K outside [1, 15]; a side < 1;
+ * D * H * W >= 2^31; workspace_bytes below the query's answer; a patch side < 1. */
+int ctseg_patch_centres(const uint8_t* masks, int32_t K, int32_t D, int32_t H, int32_t W, const uint32_t* draws /* host, P x 3 */,
+                        int32_t P, int32_t class_mask, const int32_t* patch /* host, 3 (d,h,w), or NULL */, void* workspace,
+                        int64_t workspace_bytes, int32_t* centres /* device, P x 4 */, void* stream);
+int64_t ctseg_patch_centres_workspace(int32_t K, int32_t D, int32_t H, int32_t W);
+
+/* The crop pass: ctseg_augment3d_to_hwd on a patch of Pd x Ph x Pw output voxels, about a centre read from the device.  Dtypes,
+ * layouts (image_out fp32 [Ph][Pw][Pd], masks_out [K][Ph][Pw][Pd], labels_out [Ph][Pw][Pd]), nearest / trilinear, constant / edge
+ * border, window, gain / bias, label map, hist and mask_src are those of ctseg_augment3d_to_hwd, and so is what is rejected (with
+ * a null centre in addition).  Two things differ:
+ *   - The grid the matrix addresses is the SOURCE grid itself, D x H x W: there is no virtual resized volume, rz is the identity,
+ *     and "outside" means outside [0, dim_a).
+ *   - The kernel reads centre (DEVICE, 3 int32: d, h, w; row p of ctseg_patch_centres' table) and forms
+ *     t'_a = A[a][3] + (float)c_a, one float32 add per axis; the sampling coordinate of output voxel o is then
+ *     q_a = ((A[a][0]*od + A[a][1]*oh) + A[a][2]*ow) + t'_a.
+ * This entry IS the affine pass with that translated matrix.  With A = the identity and A[a][3] = -(P_a / 2) every q is a whole
+ * number and the patch is the exact crop src[c - P/2 + o] (cval / 0 / the edge voxel where that leaves the volume), with either
+ * interp.  One launch per patch; the host never waits for the centre. */
+int ctseg_patch3d_to_hwd(const void* image, int32_t image_dtype, const uint8_t* masks, int32_t K, int32_t D, int32_t H, int32_t W,
+                         int32_t Pd, int32_t Ph, int32_t Pw, const float* matrix /* host */, const int32_t* centre /* DEVICE, 3 */,
+                         int32_t interp, int32_t border, float cval, const int32_t* mask_src /* host */, int32_t window,
+                         float win_lo, float win_hi, float gain, float bias, float* image_out, uint8_t* masks_out,
+                         uint8_t* labels_out, int64_t* hist, void* stream);
+
 /* Test-time augmentation of the 3-D network: the prediction of one VIEW (the network's logits for an augmented copy of the scan)
  * is resampled onto a TARGET grid and added into an accumulator there; ctseg_tta_finish turns the accumulator into labels.
  * Inputs and layout:
