@@ -191,6 +191,7 @@ _SIGS = {
     "ctseg_surface_select": (C.c_int, [_vp, _vp, _vp] + [_i32] * 5 + [_f64, _vp, _i64, _vp, _vp, _vp]),
     "ctseg_distmap3d_weighted": (C.c_int, [_vp] + [_i32] * 4 + [_vp, _vp, _i64, _vp, _vp, _vp]),
     "ctseg_surface_select_f32": (C.c_int, [_vp, _vp, _vp] + [_i32] * 5 + [_f64, _vp, _i64, _vp, _vp, _vp]),
+    "ctseg_surface_dice": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp] * 6),
     "ctseg_components_label": (C.c_int, [_vp] + [_i32] * 7 + [_vp, _vp, _vp]),
     "ctseg_components_keep": (C.c_int, [_vp, _vp, _vp] + [_i32] * 8 + [_vp, _i64, _vp, _vp, _vp]),
     "ctseg_window_gather": (C.c_int, [_vp] + [_i32] * 10 + [_f32, _vp, _i32, _i32, _vp]),

@@ -55,3 +55,22 @@ class SurfaceDistanceMetricWrapper(object):
         if self.last is None:
             raise RuntimeError("SurfaceDistanceMetricWrapper.assd(): call the wrapper on a batch first")
         return surface.reduce_nan_mean(self.last.assd)
+
+
+class SurfaceDiceMetricWrapper(object):
+    """``SurfaceDiceMetricWrapper(tolerance)(pred_labels, true_labels) -> (mean, per-class (9,))`` of the surface Dice at tolerance
+    (normalised surface Dice, ``capstone_amd.surface.surface_dice``), called like ``SurfaceDistanceMetricWrapper``.  ``tolerance``:
+    one value or one per class, in voxels or in the unit of ``spacing``.  A class in neither map of a sample has no value there
+    (NaN) and is skipped by the means; a class in only one of them scores 0.  ``last`` keeps the full tables of the call."""
+
+    def __init__(self, tolerance, spacing=None):
+        self.n_classes = N_CLASSES
+        self.tolerance = tolerance
+        self.spacing = spacing
+        self.last = None
+
+    def __call__(self, input, target, spacing=None):
+        nat.require_gpu(input, "SurfaceDiceMetricWrapper")
+        self.last = surface.surface_dice(input, target, self.tolerance, self.n_classes,
+                                         spacing=self.spacing if spacing is None else spacing)
+        return surface.reduce_nan_mean(self.last.nsd)

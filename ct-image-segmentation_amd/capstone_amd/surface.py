@@ -35,7 +35,17 @@ relative of the real squared distance, so within 2^-23 of the distance after the
 set that sizes the launch groups is 11 bytes per voxel and volume on this path (1 mask + 4 squared distances + 6 transform
 workspace, ``BYTES_PER_VOXEL_WEIGHTED``): 1.25 GB for the same sample.  The select orders those floats by their bit patterns.
 ``spacing=(1, 1, 1)`` reproduces the voxel path exactly (``fl(1 * d^2)`` is exact).
+
+``surface_dice`` is the third figure, the surface Dice at tolerance (normalised surface Dice, NSD): the share of the two surfaces
+that lies within ``tau`` of the other surface.  It needs no distances, only whether something lies within a few voxels, so it runs
+none of the stages above: ``ctseg_surface_dice`` is one launch for the whole batch, without a workspace, that stages tiles of both
+label maps in LDS and searches a box bounded by the tolerance.  Its acceptance rule is pinned like the distances: a voxel v of
+one surface is *within* iff some voxel u of the other surface of the same class has ``dx^2 + dy^2 + dz^2 <= floor(tau^2)`` in
+integers, or with ``spacing=`` the float32 expression above ``<= float32(tau^2)``, which is the weighted distance compared with
+that limit (float32 addition of non-negative terms is monotone).  A class that only one of the two maps holds scores 0.0 there,
+the formula's value and what MONAI's ``SurfaceDiceMetric`` and Dice give; the distance tables have NaN in that place.
 """
+import math
 from types import SimpleNamespace
 
 import torch
@@ -52,20 +62,21 @@ SELECT_F32_ROW_BYTES = 41480                              # CTSEG_SURFACE_SELECT
 MIN_SPACING, MAX_SPACING = 1e-3, 1e3
 MAX_CLASSES = 16
 MAX_WORKING_SET = 2 << 30
+SURFACE_DICE_MAX_RADIUS = 8                               # CTSEG_SURFACE_DICE_MAX_RADIUS: voxels searched along an axis
 
 
-def _label_maps(pred, target):
+def _label_maps(pred, target, who="surface_distances"):
     if pred.shape != target.shape or pred.dim() not in (3, 4):
-        raise ValueError(f"surface_distances: two label maps of one shape, (B, H, W, D) or (B, H, W); got {tuple(pred.shape)} and "
+        raise ValueError(f"{who}: two label maps of one shape, (B, H, W, D) or (B, H, W); got {tuple(pred.shape)} and "
                          f"{tuple(target.shape)}")
     if pred.is_floating_point() or target.is_floating_point() or pred.dtype == torch.bool or target.dtype == torch.bool:
-        raise ValueError(f"surface_distances: integer label maps, not {pred.dtype} / {target.dtype}")
+        raise ValueError(f"{who}: integer label maps, not {pred.dtype} / {target.dtype}")
     if pred.device != target.device:
-        raise ValueError(f"surface_distances: the label maps are on {pred.device} and {target.device}")
+        raise ValueError(f"{who}: the label maps are on {pred.device} and {target.device}")
     sides = tuple(int(s) for s in pred.shape[1:]) + ((1,) if pred.dim() == 3 else ())
     axes = AXIS_X | AXIS_Y | (AXIS_Z if pred.dim() == 4 else 0)
     if pred.shape[0] < 1 or min(sides) < 1 or max(sides) > DU.MAX_SIDE:
-        raise nat.NativeError(f"surface_distances: at least one sample with sides in 1..{DU.MAX_SIDE} (got {tuple(pred.shape)})")
+        raise nat.NativeError(f"{who}: at least one sample with sides in 1..{DU.MAX_SIDE} (got {tuple(pred.shape)})")
     return pred.to(torch.uint8).contiguous(), target.to(torch.uint8).contiguous(), sides, axes
 
 
@@ -167,3 +178,77 @@ def reduce_nan_mean(table):
     none has), then the mean over the classes that have one (NaN if none has)"""
     per_class = torch.nanmean(table, dim=0)
     return torch.nanmean(per_class), per_class
+
+
+def _dice_tables(tolerance, K, w, active, spacing):
+    """the host tables of ``surface_dice``: tolerances (K,) float64, the limits (B, K) and the radii (B, K, 3) int32.  ``w``: the
+    (B, 3) float32 squared voxel sizes, or None for voxel units with B = 1 row; ``active``: the number of leading active axes"""
+    if not torch.is_tensor(tolerance):
+        tolerance = torch.as_tensor(tolerance, dtype=torch.float64)                           # (Python floats are float64)
+    tau = tolerance.detach().to("cpu", torch.float64)
+    if tau.dim() == 0:
+        tau = tau.expand(K)
+    if tuple(tau.shape) != (K,):
+        raise ValueError(f"surface_dice: one tolerance or one per class ({K},), not {tuple(tau.shape)}")
+    if not bool((torch.isfinite(tau) & (tau >= 0)).all()):
+        raise ValueError(f"surface_dice: finite tolerances >= 0, not {tau.tolist()}")
+    sq = tau * tau
+    over = SURFACE_DICE_MAX_RADIUS + 1
+    if w is None:
+        limit = sq.clamp(max=float(1 << 30)).floor().to(torch.int32)[None]                    # (1, K): T2
+        radius = torch.tensor([[min(math.isqrt(int(v)), over)] * 3 for v in limit[0].tolist()], dtype=torch.int32)[None]
+    else:
+        limit = sq.to(torch.float32)[None].expand(w.shape[0], K)                              # (B, K): t2
+        dd = torch.arange(over + 1, dtype=torch.float32) ** 2                                 # d^2, exact
+        ok = (w[:, None, :, None] * dd) <= limit[:, :, None, None]                            # fl(w_a * d^2) <= t2: (B, K, 3, d)
+        radius = (ok.sum(-1) - 1).to(torch.int32)                                             # monotone in d: the largest accepted
+    radius = radius.clone()
+    radius[..., active:] = 0
+    if int(radius.max()) > SURFACE_DICE_MAX_RADIUS:
+        b, k, a = (int(i) for i in (radius > SURFACE_DICE_MAX_RADIUS).nonzero()[0])
+        unit = "voxel units" if spacing is None else f"spacing {torch.as_tensor(spacing).tolist()}"
+        raise ValueError(f"surface_dice: class {k + 1} with tolerance {tau[k].item():g} in {unit} needs a search radius above "
+                         f"{SURFACE_DICE_MAX_RADIUS} voxels along axis {a} (sample {b}); the limit is {SURFACE_DICE_MAX_RADIUS}")
+    return tau, limit, radius
+
+
+def surface_dice(pred, target, tolerance, n_classes=N_CLASSES, spacing=None):
+    """The surface Dice at tolerance (normalised surface Dice) of integer label maps ``(B, H, W, D)`` or ``(B, H, W)`` on the
+    device -> a namespace, C = ``n_classes``, direction 0 = pred -> target, 1 = target -> pred:
+
+    ``nsd`` (B, C-1) float64 = (within[0] + within[1]) / (counts[0] + counts[1]), ``nsd_directed`` (2, B, C-1) = within / counts,
+    ``within`` and ``counts`` (2, B, C-1) int64: the surface voxels with a voxel of the other map's surface of the same class
+    within the tolerance, and all surface voxels; ``limit`` (B, C-1), the table the kernel compared with, and ``radius`` (B, C-1, 3)
+    int32 on the host, the search radii per axis.
+
+    ``tolerance``: one value or one per class ``(C-1,)``, finite and >= 0, in voxels or, with ``spacing``, in its unit; 0 counts
+    coinciding surface voxels.  The rule is exact: squared voxel offsets against ``floor(tolerance^2)`` in integers, or the float32
+    expression of the weighted distances against ``float32(tolerance^2)`` (module docstring).  ``spacing`` as in
+    ``surface_distances``.  No radius may exceed ``SURFACE_DICE_MAX_RADIUS`` = 8 voxels (``ValueError``): clinical tolerances of
+    1 to 3 mm on CT grids need at most 6.
+
+    ``nsd`` is NaN only where both surfaces are empty.  A class that one map holds and the other lacks scores 0.0, as in MONAI's
+    ``SurfaceDiceMetric`` and as Dice does; this differs from ``surface_distances``, where such a class is NaN.  ``nsd_directed``
+    is NaN where that direction's surface is empty.  One launch for the whole batch; there is no CPU fallback."""
+    nat.require_gpu(pred, "surface_dice")
+    nat.require_gpu(target, "surface_dice")
+    C = int(n_classes)
+    if not 2 <= C <= MAX_CLASSES:
+        raise ValueError(f"surface_dice: 2 <= n_classes <= {MAX_CLASSES}, not {n_classes!r}")
+    p, t, (X, Y, Z), axes = _label_maps(pred, target, "surface_dice")
+    B, K, dev = p.shape[0], C - 1, p.device
+    w = None if spacing is None else _squared_spacing(spacing, B, pred.dim() - 1)
+    _, limit, radius = _dice_tables(tolerance, K, w, pred.dim() - 1, spacing)
+    limit = limit.expand(B, K).contiguous().to(dev)
+    radius = radius.expand(B, K, 3).contiguous()
+    w_dev = None if w is None else w.to(dev)
+    tables = torch.zeros((2, 2, B, K), dtype=torch.int32, device=dev)                         # counts, within
+    nat.call("ctseg_surface_dice", nat.ptr(p), nat.ptr(t), B, X, Y, Z, C, axes, nat.ptr(radius), nat.ptr(limit), nat.ptr(w_dev),
+             nat.ptr(tables[0]), nat.ptr(tables[1]))
+    counts, within = tables[0].to(torch.int64), tables[1].to(torch.int64)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    both = counts[0] + counts[1]
+    return SimpleNamespace(
+        nsd=torch.where(both > 0, (within[0] + within[1]).double() / both.clamp(min=1).double(), nan),
+        nsd_directed=torch.where(counts > 0, within.double() / counts.clamp(min=1).double(), nan),
+        within=within, counts=counts, limit=limit, radius=radius)

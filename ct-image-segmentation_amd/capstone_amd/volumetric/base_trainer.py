@@ -19,7 +19,7 @@ from ..models.losses import _as_cl
 from ..training.module_base import _TrainerBase, _precision, pl
 from ..training.utils import _squash_predictions  # noqa: F401  (same import the reference has)
 from .losses import MultipleLossWrapper3D
-from .metrics import DiceMetricWrapper3D, SurfaceDistanceMetricWrapper3D
+from .metrics import DiceMetricWrapper3D, SurfaceDiceMetricWrapper3D, SurfaceDistanceMetricWrapper3D
 from .utils import _squash_masks_3D
 
 SEED = 12342
@@ -30,7 +30,7 @@ class BaseUNet3D(_TrainerBase):
                  lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
                  surface_metrics: bool = False, surface_percentile: float = 95.0, surface_spacing=None,
                  largest_component: bool = False, largest_component_connectivity=None, tta=None, val_inferer=None,
-                 **kwargs) -> None:
+                 surface_dice=None, **kwargs) -> None:
         """``device_boundary``: opt in to the Boundary loss on volumes; the batch then carries the distance maps as its fourth
         element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise.
         ``surface_metrics``: ``validation_step`` also scores the batch with the percentile Hausdorff distance (``surface_percentile``,
@@ -56,7 +56,13 @@ class BaseUNet3D(_TrainerBase):
         ``val_inferer``: an ``inferers.SlidingWindowInferer``.  ``validation_step`` then gets its logits from
         ``val_inferer(images[i:i+1], self)`` per sample instead of one forward pass over the whole grid, so a model trained on
         patches (``MiccaiDataModule3D(patch_size=...)``) is validated on whole volumes; the losses and the Dice scores come from
-        the same wrappers (``loss_func``, ``dice_score`` on the squashed logits) under the same keys."""
+        the same wrappers (``loss_func``, ``dice_score`` on the squashed logits) under the same keys.
+        ``surface_dice``: a tolerance, or one per class, in voxels or, with ``surface_spacing``, in millimetres.
+        ``validation_step`` then also scores the surface Dice at that tolerance (``capstone_amd.surface.surface_dice``) of the raw
+        labels, of the cleaned ones with ``largest_component`` and of the merged ones with ``tta``; the tables are kept per step,
+        reduced by ``epoch_surface_dice`` and logged by ``on_validation_epoch_end`` as ``"{structure} NSD (val)"`` and ``"Mean NSD
+        (val)"``, and under ``(val LCC)`` / ``(val TTA)``.  Independent of ``surface_metrics``; per rank, and never in a training
+        step."""
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
@@ -77,6 +83,9 @@ class BaseUNet3D(_TrainerBase):
         self.tta = tta                                              # (kept out of hparams too)
         self.tta_dice_score = DiceMetricWrapper3D() if tta is not None else None
         self.val_inferer = val_inferer                              # (kept out of hparams too)
+        self.surface_dice = surface_dice                            # (kept out of hparams too)
+        self.surface_dice_score = SurfaceDiceMetricWrapper3D(surface_dice, surface_spacing) if surface_dice is not None else None
+        self._surface_dice_kept = {}
 
     def _construct_model(self):
         # reference :58-72 — in_channels=1, strides for a 5-entry filter list, num_res_units hard-wired to 2
@@ -176,13 +185,16 @@ class BaseUNet3D(_TrainerBase):
             images, masks, prediction = self._inferer_step(batch)
         else:
             images, masks, _, prediction, _ = self._shared_step(batch, is_training=False)
-        if not (self.surface_metrics or self.largest_component or self.tta is not None):
+        nsd = self.surface_dice_score is not None
+        if not (self.surface_metrics or self.largest_component or self.tta is not None or nsd):
             return
         with torch.no_grad():
-            if self.surface_metrics or self.largest_component:
+            if self.surface_metrics or self.largest_component or nsd:
                 labels = _squash_predictions(prediction)
             if self.surface_metrics:
                 self._score_surfaces(labels, masks, "val")
+            if nsd:
+                self._score_surface_dice(labels, masks, "val")
             if self.largest_component:
                 kept = components.keep_largest_component(labels, self._n_classes,
                                                          connectivity=self.largest_component_connectivity)
@@ -190,11 +202,15 @@ class BaseUNet3D(_TrainerBase):
                 self._log_dice("val LCC", *self.lcc_dice_score(kept.labels, masks))
                 if self.surface_metrics:
                     self._score_surfaces(kept.labels, masks, "val LCC")
+                if nsd:
+                    self._score_surface_dice(kept.labels, masks, "val LCC")
             if self.tta is not None:        # last: the views' forward passes overwrite the storage behind ``prediction``
                 merged = self.tta.predict_batch(self, images).labels
                 self._log_dice("val TTA", *self.tta_dice_score(merged, masks))
                 if self.surface_metrics:
                     self._score_surfaces(merged, masks, "val TTA")
+                if nsd:
+                    self._score_surface_dice(merged, masks, "val TTA")
 
     def _inferer_step(self, batch):
         """``_shared_step`` for validation with ``val_inferer``: the logits of every sample come from the sliding-window inferer
@@ -224,6 +240,21 @@ class BaseUNet3D(_TrainerBase):
         last = self.surface_score.last
         self._surface_kept.setdefault(prefix, []).append((last.hd, last.assd))
 
+    def _score_surface_dice(self, labels, masks, prefix):
+        self.surface_dice_score(labels, masks)
+        self._surface_dice_kept.setdefault(prefix, []).append(self.surface_dice_score.last.nsd)
+
+    def epoch_surface_dice(self, prefix="val", reset=True):
+        """(NSD mean, NSD per class (9,)) over all samples scored since the last reset: per class the mean over the samples where
+        the class is in the prediction or in the truth, then the mean over the classes that have a value; NaN where nothing has.
+        None without ``surface_dice`` or when nothing was kept.  The values of this rank."""
+        kept = self._surface_dice_kept.get(prefix)
+        if self.surface_dice_score is None or not kept:
+            return None
+        if reset:
+            self._surface_dice_kept[prefix] = []
+        return surface.reduce_nan_mean(torch.cat(kept))
+
     def epoch_surface_metrics(self, prefix="val", reset=True):
         """(HD mean, HD per class (9,), ASSD mean, ASSD per class (9,)) over all samples scored since the last reset: per class the
         mean over the samples where the class is in both the prediction and the truth, then the mean over the classes that have a
@@ -240,11 +271,18 @@ class BaseUNet3D(_TrainerBase):
         """logs the epoch's surface metrics that have a value: "{structure} HD95 (val)", "Mean HD95 (val)", "{structure} ASSD
         (val)", "Mean ASSD (val)" (``HD`` and the percentile); with ``surface_spacing`` the unit follows the name, as in "{structure}
         HD95 mm (val)" and "Mean ASSD mm (val)", and the keys without it are not logged.  With ``largest_component`` the same
-        keys under "(val LCC)" for the cleaned predictions, and "{structure} components (val)" besides"""
+        keys under "(val LCC)" for the cleaned predictions, and "{structure} components (val)" besides.  With ``surface_dice``:
+        "{structure} NSD (val)" and "Mean NSD (val)" for the classes that have a value, and the same under "(val LCC)" / "(val TTA)"
+        (the tolerance's unit is that of ``surface_spacing``; the score has none)"""
         if self.surface_metrics:
             for prefix, on in (("val", True), ("val LCC", self.largest_component), ("val TTA", self.tta is not None)):
                 if on:
                     self._log_surface_epoch(prefix)
+        if self.surface_dice_score is not None:
+            for prefix, on in (("val", True), ("val LCC", self.largest_component), ("val TTA", self.tta is not None)):
+                res = self.epoch_surface_dice(prefix) if on else None
+                if res is not None:
+                    self._log_per_structure("NSD", prefix, *res)
         if self.largest_component and self._components_kept:
             mean = torch.cat(self._components_kept).double().mean(dim=0)
             self._components_kept = []
@@ -258,12 +296,15 @@ class BaseUNet3D(_TrainerBase):
         unit = "" if self.surface_spacing is None else " mm"
         hd = f"HD{self.surface_score.percentile:g}"
         for name, mean, per_class in ((hd + unit, res[0], res[1]), ("ASSD" + unit, res[2], res[3])):
-            finite = torch.isfinite(per_class).tolist()
-            for structure, value, ok in zip(STRUCTURES, per_class, finite):
-                if ok:
-                    self.log(f"{structure} {name} ({prefix})", value, on_step=False, on_epoch=True)
-            if any(finite):
-                self.log(f"Mean {name} ({prefix})", mean, on_step=False, on_epoch=True)
+            self._log_per_structure(name, prefix, mean, per_class)
+
+    def _log_per_structure(self, name, prefix, mean, per_class):
+        finite = torch.isfinite(per_class).tolist()
+        for structure, value, ok in zip(STRUCTURES, per_class, finite):
+            if ok:
+                self.log(f"{structure} {name} ({prefix})", value, on_step=False, on_epoch=True)
+        if any(finite):
+            self.log(f"Mean {name} ({prefix})", mean, on_step=False, on_epoch=True)
 
     def _shared_step(self, batch, is_training: bool):
         images, masks, mask_indicator, dist_maps = self._split_batch(batch)

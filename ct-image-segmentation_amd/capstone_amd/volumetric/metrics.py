@@ -1,5 +1,5 @@
 """Mirror of reference capstone/volumetric/metrics.py: the 3-D metric wrapper (rank-agnostic here)."""
-from ..models.metrics import DiceMetricWrapper, SurfaceDistanceMetricWrapper
+from ..models.metrics import DiceMetricWrapper, SurfaceDiceMetricWrapper, SurfaceDistanceMetricWrapper
 
 
 class DiceMetricWrapper3D(DiceMetricWrapper):
@@ -7,4 +7,8 @@ class DiceMetricWrapper3D(DiceMetricWrapper):
 
 
 class SurfaceDistanceMetricWrapper3D(SurfaceDistanceMetricWrapper):
+    pass
+
+
+class SurfaceDiceMetricWrapper3D(SurfaceDiceMetricWrapper):
     pass

@@ -749,6 +749,24 @@ int ctseg_surface_select_f32(const uint8_t* edges, const float* d2, const int32_
                              int32_t C, double q, void* workspace, int64_t workspace_bytes, int32_t* stats, double* fstats,
                              void* stream);
 
+/* Surface Dice at tolerance (normalised surface Dice): one launch, no workspace.  pred, target uint8 [B][X][Y][Z] and `axes` as for
+ * ctseg_surface_edges, whose surface rule this is.  For side 0 = pred -> target and 1 = target -> pred, sample b and class c = 1..C-1:
+ *     counts[side][b][c-1] += the voxels on the surface of c in that side's map
+ *     within[side][b][c-1] += those of them with a voxel u on the surface of c in the OTHER map at an accepted offset (d0, d1, d2)
+ * (both int32, zeroed by the caller; integer atomics: the same bits every run).  An offset is accepted
+ *   without w2: when d0^2 + d1^2 + d2^2 <= limit[b][c-1], limit int32 [B][C-1] on the device;
+ *   with w2:    when fl(fl(w1 * d1^2) + fl(fl(w2 * d2^2) + fl(w0 * d0^2))) <= limit[b][c-1], limit float32 [B][C-1] and w2 float32
+ *               [B][3] on the device, the squared voxel sizes of the sample along X, Y, Z; every fl() one float32 rounding, the
+ *               expression of ctseg_distmap3d_weighted.
+ * radius int32 [B][C-1][3] ON THE HOST: per sample, class and axis a bound of |d_a| over the accepted offsets, each in
+ *   0..CTSEG_SURFACE_DICE_MAX_RADIUS.  Their maxima per axis size the search box and the halo of the launch: an accepted offset
+ *   outside them is not found.  The table is read before the call returns.
+ * B in 1..65535, sides in 1..1024, 2 <= C <= 16; validated on the host before the launch. */
+#define CTSEG_SURFACE_DICE_MAX_RADIUS 8
+int ctseg_surface_dice(const uint8_t* pred, const uint8_t* target, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t C,
+                       int32_t axes, const int32_t* radius, const void* limit, const float* w2, int32_t* counts, int32_t* within,
+                       void* stream);
+
 /* Connected components of a label map, and the keep-largest / minimum-size clean-up of a prediction on top of them (what MONAI
  * ships as KeepLargestConnectedComponent).  Two calls in stream order, no host synchronisation between them:
  *   ctseg_components_label -> ctseg_components_keep(labels, ids, sizes as the first call left them).
