@@ -194,6 +194,8 @@ _SIGS = {
     "ctseg_surface_dice": (C.c_int, [_vp, _vp] + [_i32] * 6 + [_vp] * 6),
     "ctseg_components_label": (C.c_int, [_vp] + [_i32] * 7 + [_vp, _vp, _vp]),
     "ctseg_components_keep": (C.c_int, [_vp, _vp, _vp] + [_i32] * 8 + [_vp, _i64, _vp, _vp, _vp]),
+    "ctseg_fill_holes": (C.c_int, [_vp] + [_i32] * 9 + [_vp, _i64, _vp, _vp, _vp]),
+    "ctseg_fill_holes_workspace_bytes": (_i64, [_i32] * 5),
     "ctseg_window_gather": (C.c_int, [_vp] + [_i32] * 10 + [_f32, _vp, _i32, _i32, _vp]),
     "ctseg_window_gather_batch": (C.c_int, [_vp] + [_i32] * 4 + [_vp] + [_i32] * 4 + [_f32, _vp, _i32, _i32, _vp]),
     "ctseg_window_blend": (C.c_int, [_vp] + [_i32] * 8 + [_vp, _vp, _vp] + [_i32] * 4 + [_vp]),

@@ -30,7 +30,8 @@ class BaseUNet3D(_TrainerBase):
                  lr: float = 1e-3, loss_fx: list = ["CrossEntropy"], exclude_missing: bool = False, device_boundary: bool = False,
                  surface_metrics: bool = False, surface_percentile: float = 95.0, surface_spacing=None,
                  largest_component: bool = False, largest_component_connectivity=None, tta=None, val_inferer=None,
-                 surface_dice=None, **kwargs) -> None:
+                 surface_dice=None, fill_holes: bool = False, fill_holes_connectivity=None, fill_holes_max_size: int = 0,
+                 **kwargs) -> None:
         """``device_boundary``: opt in to the Boundary loss on volumes; the batch then carries the distance maps as its fourth
         element (``MiccaiDataset3D(dist_maps=True)``).  Without it a ``"Boundary"`` entry and a 4-tuple batch raise.
         ``surface_metrics``: ``validation_step`` also scores the batch with the percentile Hausdorff distance (``surface_percentile``,
@@ -62,7 +63,14 @@ class BaseUNet3D(_TrainerBase):
         labels, of the cleaned ones with ``largest_component`` and of the merged ones with ``tta``; the tables are kept per step,
         reduced by ``epoch_surface_dice`` and logged by ``on_validation_epoch_end`` as ``"{structure} NSD (val)"`` and ``"Mean NSD
         (val)"``, and under ``(val LCC)`` / ``(val TTA)``.  Independent of ``surface_metrics``; per rank, and never in a training
-        step."""
+        step.
+        ``fill_holes``: ``validation_step`` also fills the enclosed holes of the predicted label map
+        (``capstone_amd.components.fill_holes``; ``fill_holes_connectivity``: 1, 2, 3 or ``None`` for the full 26 neighbours;
+        ``fill_holes_max_size``: the largest hole filled, 0 for no limit) and scores the filled map IN ADDITION: its Dice under the
+        prefix ``"val filled"`` and, with ``surface_metrics`` / ``surface_dice``, its surface metrics and NSD under ``"(val
+        filled)"``.  With ``largest_component`` it fills the keep-largest result, the order of a MONAI post-processing chain.
+        ``on_validation_epoch_end`` also logs ``"{structure} holes (val)"``, the mean number of holes filled per class over the
+        epoch's samples.  Per rank, and never in a training step."""
         super().__init__()
         assert isinstance(loss_fx, list), "This module expects a list of loss functions"
         loss_fx.sort()  # consistent order of loss functions (reference :35)
@@ -86,6 +94,11 @@ class BaseUNet3D(_TrainerBase):
         self.surface_dice = surface_dice                            # (kept out of hparams too)
         self.surface_dice_score = SurfaceDiceMetricWrapper3D(surface_dice, surface_spacing) if surface_dice is not None else None
         self._surface_dice_kept = {}
+        self.fill_holes = fill_holes                                # (kept out of hparams too)
+        self.fill_holes_connectivity = fill_holes_connectivity
+        self.fill_holes_max_size = fill_holes_max_size
+        self.filled_dice_score = DiceMetricWrapper3D() if fill_holes else None
+        self._holes_kept = []
 
     def _construct_model(self):
         # reference :58-72 — in_channels=1, strides for a 5-entry filter list, num_res_units hard-wired to 2
@@ -186,10 +199,10 @@ class BaseUNet3D(_TrainerBase):
         else:
             images, masks, _, prediction, _ = self._shared_step(batch, is_training=False)
         nsd = self.surface_dice_score is not None
-        if not (self.surface_metrics or self.largest_component or self.tta is not None or nsd):
+        if not (self.surface_metrics or self.largest_component or self.tta is not None or nsd or self.fill_holes):
             return
         with torch.no_grad():
-            if self.surface_metrics or self.largest_component or nsd:
+            if self.surface_metrics or self.largest_component or nsd or self.fill_holes:
                 labels = _squash_predictions(prediction)
             if self.surface_metrics:
                 self._score_surfaces(labels, masks, "val")
@@ -204,6 +217,15 @@ class BaseUNet3D(_TrainerBase):
                     self._score_surfaces(kept.labels, masks, "val LCC")
                 if nsd:
                     self._score_surface_dice(kept.labels, masks, "val LCC")
+            if self.fill_holes:
+                filled = components.fill_holes(kept.labels if self.largest_component else labels, self._n_classes,
+                                               connectivity=self.fill_holes_connectivity, max_size=self.fill_holes_max_size)
+                self._holes_kept.append(filled.holes)
+                self._log_dice("val filled", *self.filled_dice_score(filled.labels, masks))
+                if self.surface_metrics:
+                    self._score_surfaces(filled.labels, masks, "val filled")
+                if nsd:
+                    self._score_surface_dice(filled.labels, masks, "val filled")
             if self.tta is not None:        # last: the views' forward passes overwrite the storage behind ``prediction``
                 merged = self.tta.predict_batch(self, images).labels
                 self._log_dice("val TTA", *self.tta_dice_score(merged, masks))
@@ -273,13 +295,14 @@ class BaseUNet3D(_TrainerBase):
         HD95 mm (val)" and "Mean ASSD mm (val)", and the keys without it are not logged.  With ``largest_component`` the same
         keys under "(val LCC)" for the cleaned predictions, and "{structure} components (val)" besides.  With ``surface_dice``:
         "{structure} NSD (val)" and "Mean NSD (val)" for the classes that have a value, and the same under "(val LCC)" / "(val TTA)"
-        (the tolerance's unit is that of ``surface_spacing``; the score has none)"""
+        (the tolerance's unit is that of ``surface_spacing``; the score has none).  With ``fill_holes`` the same keys under "(val
+        filled)" for the filled predictions, and "{structure} holes (val)" besides"""
         if self.surface_metrics:
-            for prefix, on in (("val", True), ("val LCC", self.largest_component), ("val TTA", self.tta is not None)):
+            for prefix, on in self._scored_prefixes():
                 if on:
                     self._log_surface_epoch(prefix)
         if self.surface_dice_score is not None:
-            for prefix, on in (("val", True), ("val LCC", self.largest_component), ("val TTA", self.tta is not None)):
+            for prefix, on in self._scored_prefixes():
                 res = self.epoch_surface_dice(prefix) if on else None
                 if res is not None:
                     self._log_per_structure("NSD", prefix, *res)
@@ -288,6 +311,15 @@ class BaseUNet3D(_TrainerBase):
             self._components_kept = []
             for structure, value in zip(STRUCTURES, mean):
                 self.log(f"{structure} components (val)", value, on_step=False, on_epoch=True)
+        if self.fill_holes and self._holes_kept:
+            mean = torch.cat(self._holes_kept).double().mean(dim=0)
+            self._holes_kept = []
+            for structure, value in zip(STRUCTURES, mean):
+                self.log(f"{structure} holes (val)", value, on_step=False, on_epoch=True)
+
+    def _scored_prefixes(self):
+        return (("val", True), ("val LCC", self.largest_component), ("val TTA", self.tta is not None),
+                ("val filled", self.fill_holes))
 
     def _log_surface_epoch(self, prefix):
         res = self.epoch_surface_metrics(prefix)

@@ -335,16 +335,6 @@ __global__ __launch_bounds__(256) void components_table_kernel(const CcRow* __re
 
 using namespace ctseg;
 
-static int check_components_dims(const char* who, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t C) {
-  CTSEG_REQUIRE(B >= 1 && X >= 1 && Y >= 1 && Z >= 1, "%s: B, X, Y, Z >= 1 (got %d samples of %d x %d x %d)", who, B, X, Y, Z);
-  CTSEG_REQUIRE(X <= 1024 && Y <= 1024 && Z <= 1024, "%s: sides up to 1024 (got %d x %d x %d)", who, X, Y, Z);
-  CTSEG_REQUIRE((int64_t)B * X * Y * Z < ((int64_t)1 << 31) && B <= 65535,
-                "%s: %d samples of %d x %d x %d are too many for one launch (fewer than 2^31 voxels, at most 65535 samples)", who, B, X,
-                Y, Z);
-  CTSEG_REQUIRE(C >= 2 && C <= SD_MAX_CLASSES, "%s: 2 <= C <= %d classes (got %d)", who, SD_MAX_CLASSES, C);
-  return 0;
-}
-
 extern "C" int ctseg_components_label(const uint8_t* labels, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t C,
                                       int32_t connectivity, int32_t axes, int32_t* ids, int32_t* sizes, void* stream) {
   CTSEG_REQUIRE(labels && ids && sizes, "components_label: null pointer (labels, ids and sizes are required)");

@@ -801,6 +801,28 @@ int ctseg_components_keep(const uint8_t* labels, const int32_t* ids, const int32
                           int32_t C, int32_t class_mask, int32_t keep_largest, int32_t min_size, void* workspace,
                           int64_t workspace_bytes, uint8_t* out, int32_t* table, void* stream);
 
+/* Enclosed holes of a label map filled (what MONAI ships as FillHoles): one call, six launches in stream order, no host
+ * synchronisation.  labels, out uint8 [B][X][Y][Z]; neighbours, `connectivity`, `axes` and the limits as for ctseg_components_label.
+ *   A background component is a maximal set of voxels of label exactly 0 joined by neighbour steps inside its sample.  It touches
+ *   the boundary when one of its voxels has coordinate 0 or side - 1 along an ACTIVE axis.  Its border set holds the labels of all
+ *   neighbours of its voxels that are not 0, every label >= C counting as one foreign label.  The component is a hole of class c when
+ *   it does not touch the boundary, its border set is exactly {c} with 1 <= c < C, bit c of class_mask (bits 1..C-1 only) is set
+ *   and max_size == 0 or the component has at most max_size voxels.  The voxels of a hole become c in `out`; every other voxel,
+ *   labels >= C included, is copied: every byte of `out` is written.  One pass: a component bordered by two classes stays.
+ *   table int32 [B][C-1][2], every word written: {holes filled, voxels filled} of every class.
+ *   Launches: the background map (which also clears the border words and the table), the three of ctseg_components_label on that
+ *   map, the border pass (integer atomic OR at the component's representative, reduced per lane and per tile of 8 x 16 x 32 first),
+ *   the rewrite (integer atomic adds into the table).  OR and integer sums commute: the same bits every run.
+ *   workspace: ctseg_fill_holes_workspace_bytes(B, X, Y, Z, C) bytes = CTSEG_FILL_HOLES_BYTES_PER_VOXEL per voxel (ids 4 + sizes 4 +
+ *   border word 4 + map 1), 16-byte aligned, any content on entry; the query returns -1 for dimensions that the call refuses.
+ *   With X * Y * Z a multiple of 16, labels and out are 16-byte aligned.  Every argument is validated on the host before the first
+ *   launch. */
+#define CTSEG_FILL_HOLES_BYTES_PER_VOXEL 13
+int ctseg_fill_holes(const uint8_t* labels, int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t C, int32_t connectivity, int32_t axes,
+                     int32_t class_mask, int32_t max_size, void* workspace, int64_t workspace_bytes, uint8_t* out, int32_t* table,
+                     void* stream);
+int64_t ctseg_fill_holes_workspace_bytes(int32_t B, int32_t X, int32_t Y, int32_t Z, int32_t C);
+
 /* Sliding-window inference (BASELINE.json configs[4]).  The reference has no inferer (grep: 0 hits); the
  * semantics are those of MONAI 0.3 `monai.inferers.sliding_window_inference`, the companion of the `monai.networks.nets.UNet`
  * the reference builds at capstone/volumetric/base_trainer.py:65-72.
