@@ -3,6 +3,7 @@ driven through the C ABI exactly as the UNet plan drives them (same packing, tap
 bounds the op-level tests share (the float64 references themselves: reference_ops.py)."""
 import json
 import os
+import zlib
 
 import numpy as np
 import torch
@@ -11,7 +12,7 @@ from capstone_amd import _native as nat
 from capstone_amd._native import BF16, F16, F32
 from capstone_amd.engine import Act, GemmLayer, Packer, ParamStore, new_act, rup
 from capstone_amd.plan import Plan, _NormAct
-from reference_ops import rounded
+from reference_ops import conv_dgrad, conv_fwd, conv_module, conv_out_shape, rounded
 
 
 class MiniPlan:
@@ -117,13 +118,18 @@ class ConvPassDriver:
     def __init__(self, mod, dt, device, extra_params=(), cg=None, dims=3, guard_params=()):
         """cg: gathered channel stride of the input when it is not the default (16 for a <= 12-channel input in 12-wide rows);
         guard_params: a (before, after) pair of parameters laid around the layer's own in the flat buffers"""
-        self.mod, self.dt, self.device = mod, dt, device
+        # ``mod``: one conv module, or the (residual, unit0) pair of a strided residual unit: same input and geometry, ONE GemmLayer of
+        # two parts whose columns are [residual | unit0], as plan._ResUnit builds it.  self.mod is the first part
+        self.mods = mods = list(mod) if isinstance(mod, (list, tuple)) else [mod]
+        self.mod = mod = mods[0]
+        self.dt, self.device = dt, device
         transposed = isinstance(mod, (torch.nn.ConvTranspose2d, torch.nn.ConvTranspose3d))
-        self.plan = MiniPlan([*guard_params[:1], mod.weight, mod.bias, *guard_params[1:], *extra_params], device, dt, dims)
+        own = [p for m in mods for p in (m.weight, m.bias)]
+        self.plan = MiniPlan([*guard_params[:1], *own, *guard_params[1:], *extra_params], device, dt, dims)
         e = nat.epc(dt)
         cin = mod.in_channels
         self.layer = GemmLayer(self.plan, "t", transposed, mod.kernel_size[0], mod.stride[0], cin,
-                               [(mod.weight, mod.bias, mod.out_channels)], cg or (cin if cin % e else rup(cin, e)),
+                               [(m.weight, m.bias, m.out_channels) for m in mods], cg or (cin if cin % e else rup(cin, e)),
                                need_dgrad=(cin % e == 0))
         self.plan.packer.finalize()
         self.desc = self.prog = None
@@ -185,6 +191,182 @@ def wide_act(x, dt, device, c0, tail, fill):
     return buf.slice(c0, C)
 
 
+# ---- one forward / input-gradient pass of one layer against the float64 convolution (test_gpu_conv_exact.py, test_gpu_conv2d_exact.py) ----
+CONV_ENV_KEYS = ("CTSEG_MAX_WG", "CTSEG_NO_HALO_X", "CTSEG_NO_DOWN_R")
+
+
+class ConvCase:
+    """one pass ("fwd" / "dgrad") of one layer, on the kernel family it is written for.  shape: (N, *spatial) of the layer's INPUT;
+    wd: P(nonzero) of the {-1, 0, 1} weights; g_ld / o_ld: row width of the gathered / written tensor where not the default;
+    cg: gathered channel stride of the layer's input where not the default; wide: largest integer of the large-magnitude run"""
+
+    def __init__(self, name, pas, family, kind, cin, cout, shape, dt=BF16, k=3, wd=2 / 3, env=None, g_ld=None, o_ld=None, cg=None,
+                 out_f32=False, wide=4):
+        self.name, self.pas, self.family, self.kind, self.cin, self.cout, self.shape = name, pas, family, kind, cin, cout, tuple(shape)
+        self.dt, self.k, self.wd, self.env, self.g_ld, self.o_ld, self.cg = dt, k, wd, env or {}, g_ld, o_ld, cg
+        self.out_f32, self.wide = out_f32, wide
+        self.dims = len(shape) - 1
+
+    @property
+    def persistent(self):
+        """every family but the generic / ring tiles sizes its grid with persistent_grid: CTSEG_MAX_WG caps it"""
+        return not self.family.startswith("generic")
+
+    @property
+    def id(self):
+        st = {BF16: "", F16: " fp16", F32: " fp32"}[self.dt]
+        return f"{self.name} | {self.pas} {self.kind} {self.cin}->{self.cout} {self.shape}{st}".replace(" ", "_")
+
+    def with_dt(self, dt):
+        return ConvCase(self.name, self.pas, self.family, self.kind, self.cin, self.cout, self.shape, dt, self.k, self.wd, self.env, self.g_ld,
+                     self.o_ld, self.cg, self.out_f32, self.wide)
+
+    def setenv(self, monkeypatch, cap=None):
+        for k in CONV_ENV_KEYS:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in self.env.items():
+            monkeypatch.setenv(k, v)
+        cap_env(monkeypatch, cap)
+
+
+class ConvOps:
+    """seeded operands of a case's LAYER (kind, channels, shape, kernel size) in one mode, with the CPU references of both passes:
+    made once per (layer, mode), shared by every test and cap, never written to.
+    mode: "unit" ({-1, 0, 1}, integer bias in [-2, 2]), "wide" (integers in [-wide, wide], same bias), ("randn", dt) (normal values
+    rounded to the storage type, the bias kept in fp32 as the library keeps it)"""
+    _cache = {}
+
+    @classmethod
+    def of(cls, case, mode):
+        key = (case.kind, case.cin, case.cout, case.shape, case.k, mode, case.wd if mode == "unit" else None,
+               case.wide if mode == "wide" else None)
+        if key not in cls._cache:
+            cls._cache[key] = cls(case, mode, zlib.crc32(repr(key).encode()))
+        return cls._cache[key]
+
+    def __init__(self, case, mode, seed):
+        g = torch.Generator().manual_seed(seed)
+        self.kind, self.k = case.kind, case.k
+        mod = conv_module(case.kind, case.cin, case.cout, case.k, case.dims)
+        N, sp = case.shape[0], case.shape[1:]
+        xs = (N, case.cin) + sp
+        ys = (N, case.cout) + conv_out_shape(case.kind, case.k, sp)
+        ws = tuple(mod.weight.shape)
+        if mode == "unit":
+            def tern(shape, p):
+                return ((torch.randint(0, 2, shape, generator=g) * 2 - 1) * (torch.rand(shape, generator=g) < p)).float()
+            self.x, self.w, self.gy = tern(xs, 2 / 3), tern(ws, case.wd), tern(ys, 2 / 3)
+            self.b = torch.randint(-2, 3, (case.cout,), generator=g).float()
+        elif mode == "wide":
+            m = case.wide
+            self.x, self.w, self.gy = (torch.randint(-m, m + 1, s, generator=g).float() for s in (xs, ws, ys))
+            self.b = torch.randint(-2, 3, (case.cout,), generator=g).float()
+        else:
+            tdt = nat.torch_dtype(mode[1])
+            fan = case.cin * case.k ** case.dims
+            self.x, self.gy = (torch.randn(s, generator=g).to(tdt).float() for s in (xs, ys))
+            self.w = (torch.randn(ws, generator=g) * fan ** -0.5).to(tdt).float()
+            self.b = torch.randn(case.cout, generator=g) * 0.5
+        self._ref = {}
+
+    def module(self, case):
+        mod = conv_module(case.kind, case.cin, case.cout, case.k, case.dims)
+        with torch.no_grad():
+            mod.weight.copy_(self.w)
+            mod.bias.copy_(self.b)
+        return mod
+
+    def ref(self, pas, f32=False):
+        """float64 (``f32``: torch float32) evaluation of the pass on the CPU"""
+        key = (pas, f32)
+        if key not in self._ref:
+            x, w, b, gy = ((t if f32 else t.double()) for t in (self.x, self.w, self.b, self.gy))
+            with torch.no_grad():
+                self._ref[key] = conv_fwd(self.kind, self.k, x, w, b) if pas == "fwd" else conv_dgrad(self.kind, self.k, gy, w, self.x.shape)
+        return self._ref[key]
+
+
+class ConvRun:
+    """one recorded and executed pass over an output buffer the test prepared (every element ACT_SENTINEL before the pass)"""
+
+    def __init__(self, case, ops, layout="padded"):
+        """layout: "padded" (the written columns, then one more 16-byte chunk of the buffer), "dense" (rows exactly Cn_store wide, the
+        gathered operand in rows of its own), "sliced" (the output a column slice at c0 > 0 of a buffer with a further chunk behind
+        it, the gathered operand a column slice of a wider buffer whose other columns hold the integer 3)"""
+        dt = case.dt
+        self.case = case
+        drv = self.drv = ConvPassDriver(ops.module(case), dt, DEV, cg=case.cg, dims=case.dims)
+        e = nat.epc(dt)
+        N, sp = case.shape[0], case.shape[1:] + (1,) * (3 - case.dims)
+        xd = (N,) + sp
+        odt = F32 if case.out_f32 else dt
+        eo = nat.epc(odt)
+        fwd = case.pas == "fwd"
+        src = ops.x if fwd else ops.gy
+        sliced_in = layout == "sliced" and case.g_ld is None and src.shape[1] % e == 0
+        if sliced_in:
+            ga = wide_act(src, dt, DEV, e, e, 3.0)
+        elif fwd:
+            ga = drv.act(src, ld=case.g_ld)
+        else:
+            ga = to_cl(src, dt, DEV, ld=case.g_ld)
+        self.sliced_in = sliced_in
+        Cn = case.cout if fwd else case.cin
+        od = drv.layer.out_dims(xd) if fwd else xd
+        narrow = case.o_ld == 12
+        Cs = rup(Cn, 4 if (case.out_f32 or narrow) else eo)
+        self.c0 = c0 = eo if layout == "sliced" else 0
+        ld = case.o_ld if narrow else c0 + Cs + (0 if layout == "dense" else eo)
+        self.out = out = sentinel_act(od, Cn, odt, DEV, ld, c0)
+        if fwd:
+            drv.fwd(case.family, ga, out=out, out_f32=case.out_f32)
+        else:
+            drv.set_input_dims(xd)
+            drv.dgrad(case.family, ga, out=out)
+        d = drv.desc
+        assert d.Cn == Cn and d.Cn_store == Cs and d.o_ld == ld and d.g_ld == ga.ld, (d.Cn, d.Cn_store, d.o_ld, d.g_ld)
+        self.Cn, self.Cs, self.ld = Cn, Cs, ld
+
+    def buffer(self):
+        """the whole output buffer as float64 on the CPU: (N, X, Y, Z, ld)"""
+        return self.out.t.cpu().double()
+
+    def check_columns(self, want, what):
+        """``want``: (N, Cn, *spatial) float64, the values columns [0, Cn) of the pass must hold bit for bit; columns [Cn, Cn_store)
+        must be zero and every other column of the buffer must still hold the sentinel"""
+        T = self.buffer()
+        if want.ndim == 4:
+            want = want.unsqueeze(-1)
+        c0, Cn, Cs = self.c0, self.Cn, self.Cs
+        got = T[..., c0:c0 + Cn].permute(0, 4, 1, 2, 3)
+        bad = got != want
+        nbad = int(bad.sum())
+        if nbad:
+            i = tuple(int(v) for v in bad.nonzero()[0])
+            raise AssertionError(f"{what}: {nbad} of {bad.numel()} elements differ from the reference; first at (n, c, x, y, z) = {i}: "
+                                 f"got {float(got[i])}, expected {float(want[i])}")
+        pad = T[..., c0 + Cn:c0 + Cs]
+        assert bool((pad == 0).all()), f"{what}: pad columns [Cn, Cn_store) = [{Cn}, {Cs}) are not zero: {pad.unique()[:8].tolist()}"
+        for lo, hi in ((0, c0), (c0 + Cs, self.ld)):
+            rest = T[..., lo:hi]
+            assert bool((rest == ACT_SENTINEL).all()), f"{what}: columns [{lo}, {hi}) outside the pass changed: {rest.unique()[:8].tolist()}"
+        return T
+
+
+def conv_exact_run(case, mode, layout="padded", ops=None):
+    """the integer run of a case -> (ConvRun, float64 reference); asserts the exactness condition of the storage type on the reference.
+    ``ops``: the case's operands where they are not ConvOps.of(case, mode)"""
+    ops = ops or ConvOps.of(case, mode)
+    ref = ops.ref(case.pas)
+    cap = EXACT_CAP[F32 if case.out_f32 else case.dt]
+    top = float(ref.abs().max())
+    nz = float((ref != 0).double().mean())
+    print(f"{case.id} [{mode}]: max |ref| {top:.0f} (cap {cap:.0f}), nonzero {100 * nz:.1f} %")
+    if mode == "unit" or case.dt == F32 or case.out_f32:
+        assert top <= cap if cap < 2.0 ** 24 else top < cap, ("the reference leaves the exactly representable integers", top, cap)
+    return ConvRun(case, ops, layout), ref
+
+
 GRAD_SENTINEL = -12345.0
 
 
@@ -197,7 +379,8 @@ class WgradPassDriver(ConvPassDriver):
 
     def __init__(self, mod, dt, device, cg=None, extra_params=()):
         self.guards = (torch.nn.Parameter(torch.zeros(8)), torch.nn.Parameter(torch.zeros(8)))
-        super().__init__(mod, dt, device, extra_params=extra_params, cg=cg, dims=3 if mod.weight.ndim == 5 else 2,
+        first = mod[0] if isinstance(mod, (list, tuple)) else mod
+        super().__init__(mod, dt, device, extra_params=extra_params, cg=cg, dims=3 if first.weight.ndim == 5 else 2,
                          guard_params=self.guards)
         self.prog = self.ws = None
 
@@ -236,6 +419,11 @@ class WgradPassDriver(ConvPassDriver):
         torch.cuda.synchronize()
         return (st.grad_view(self.mod.weight).cpu().clone(), st.grad_view(self.mod.bias).cpu().clone(), self.desc, st.flat_g.cpu().clone())
 
+    def part_grads(self, flat_g):
+        """[(weight gradient, bias gradient)] of every part of the layer, cut out of the flat gradient ``go`` returned"""
+        st = self.plan.store
+        return [tuple(flat_g[st.off(p):st.off(p) + p.numel()].reshape(p.shape).clone() for p in (m.weight, m.bias)) for m in self.mods]
+
     def outside_untouched(self, flat_g):
         """no entry of the flat gradient outside the layer's weight and bias views changed from the sentinel"""
         return self.outside_untouched_but(flat_g)
@@ -244,7 +432,7 @@ class WgradPassDriver(ConvPassDriver):
         """the same, with further parameters (``also``) whose gradient the recorded program may write"""
         st = self.plan.store
         keep = torch.ones(flat_g.numel(), dtype=torch.bool)
-        for p in (self.mod.weight, self.mod.bias, *also):
+        for p in (*(q for m in self.mods for q in (m.weight, m.bias)), *also):
             keep[st.off(p):st.off(p) + p.numel()] = False
         return int(keep.sum()) >= 16 and bool((flat_g[keep] == GRAD_SENTINEL).all())
 

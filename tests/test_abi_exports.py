@@ -455,3 +455,17 @@ def test_wgrad_reduce_batch_ok_conditions():
     assert ok(4096, 18, 0, 10) == 0                 # cn_pad % 4
     assert ok(4100, 16, 0, 10) == 0                 # ws at a 4-byte offset
     assert ok(4096, 16, 8, 10) == 0                 # col0 + roundup(nb, 4) > cn_pad
+
+
+def test_default_2d_unet_conv_passes_by_name():
+    """every conv pass the default BaseUNet2D (filters 64 .. 1024, residual units, bf16) records, with the kernel the selector names
+    for it, against the committed table (tests/unet2d_passes.py): a selector or recorder change shows as a named diff, row by row.
+    At Z = 1 only the generic tiles and the ring kernel may appear: every other family needs 4 rows along z, 27 taps or 8 classes."""
+    from unet2d_passes import UNET2D_PASSES, recorded_passes
+    got = recorded_passes()
+    diff = [(i, g, w) for i, (g, w) in enumerate(zip(got, UNET2D_PASSES)) if g != w]
+    assert not diff, "\n".join(f"row {i}: recorded {g}\n        table    {w}" for i, g, w in diff)
+    assert len(got) == len(UNET2D_PASSES) == 56, (len(got), len(UNET2D_PASSES))
+    for pas, layer, *_, name in got:
+        assert name is not None, (pas, layer, "the selector names no kernel")
+        assert name.startswith("generic ") if pas != "wgrad" else name.startswith(("generic ", "ring ")), (pas, layer, name)

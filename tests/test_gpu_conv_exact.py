@@ -70,194 +70,18 @@ Not covered, with the reason the library gives:
   * statistics, addend, split output, backward statistics, operand normalisation: test_gpu_conv_extras.py (per family, by name);
   * fp16 under CTSEG_MAX_WG caps and in the degenerate shapes: the cap and the tile walk are storage-independent code, run in bf16.
 """
-import zlib
-
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from capstone_amd import _native as nat  # noqa: E402
 from capstone_amd._native import BF16, F16, F32  # noqa: E402
-from capstone_amd.engine import rup  # noqa: E402
-from helpers import (ACT_SENTINEL, CAP_IDS, CAPS, DOWN_HALO, DOWN_R, EXACT_CAP, G16, G32, G64, G128, G256, HALO, HALO_SW,  # noqa: E402
-                     HALO_X, RING128, RING256, STEM, ULP, UP, UP8, ConvPassDriver, cap_env, elem_bound, sentinel_act, to_cl, wide_act)
-from reference_ops import conv_dgrad, conv_fwd, conv_module, conv_out_shape  # noqa: E402
+from helpers import (ACT_SENTINEL, CAP_IDS, CAPS, DOWN_HALO, DOWN_R, G16, G32, G64, G128, G256, HALO, HALO_SW, HALO_X, RING128, RING256,  # noqa: E402
+                     STEM, ULP, UP, UP8, elem_bound)
+from helpers import ConvCase as _Case, ConvOps as _Ops, ConvRun as _Run, conv_exact_run as _exact  # noqa: E402
 
 DEV = "cuda:0"
 NO_X = {"CTSEG_NO_HALO_X": "1"}      # conv_halo_x_eligible turns every pass down: 16-bit storage on the "halo" kernel
-ENV_KEYS = ("CTSEG_MAX_WG", "CTSEG_NO_HALO_X", "CTSEG_NO_DOWN_R")
-
-
-class _Case:
-    """one pass ("fwd" / "dgrad") of one layer, on the kernel family it is written for.  shape: (N, *spatial) of the layer's INPUT;
-    wd: P(nonzero) of the {-1, 0, 1} weights; g_ld / o_ld: row width of the gathered / written tensor where not the default;
-    cg: gathered channel stride of the layer's input where not the default; wide: largest integer of the large-magnitude run"""
-
-    def __init__(self, name, pas, family, kind, cin, cout, shape, dt=BF16, k=3, wd=2 / 3, env=None, g_ld=None, o_ld=None, cg=None,
-                 out_f32=False, wide=4):
-        self.name, self.pas, self.family, self.kind, self.cin, self.cout, self.shape = name, pas, family, kind, cin, cout, tuple(shape)
-        self.dt, self.k, self.wd, self.env, self.g_ld, self.o_ld, self.cg = dt, k, wd, env or {}, g_ld, o_ld, cg
-        self.out_f32, self.wide = out_f32, wide
-        self.dims = len(shape) - 1
-
-    @property
-    def persistent(self):
-        """every family but the generic / ring tiles sizes its grid with persistent_grid: CTSEG_MAX_WG caps it"""
-        return not self.family.startswith("generic")
-
-    @property
-    def id(self):
-        st = {BF16: "", F16: " fp16", F32: " fp32"}[self.dt]
-        return f"{self.name} | {self.pas} {self.kind} {self.cin}->{self.cout} {self.shape}{st}".replace(" ", "_")
-
-    def with_dt(self, dt):
-        return _Case(self.name, self.pas, self.family, self.kind, self.cin, self.cout, self.shape, dt, self.k, self.wd, self.env, self.g_ld,
-                     self.o_ld, self.cg, self.out_f32, self.wide)
-
-    def setenv(self, monkeypatch, cap=None):
-        for k in ENV_KEYS:
-            monkeypatch.delenv(k, raising=False)
-        for k, v in self.env.items():
-            monkeypatch.setenv(k, v)
-        cap_env(monkeypatch, cap)
-
-
-class _Ops:
-    """seeded operands of a case's LAYER (kind, channels, shape, kernel size) in one mode, with the CPU references of both passes:
-    made once per (layer, mode), shared by every test and cap, never written to.
-    mode: "unit" ({-1, 0, 1}, integer bias in [-2, 2]), "wide" (integers in [-wide, wide], same bias), ("randn", dt) (normal values
-    rounded to the storage type, the bias kept in fp32 as the library keeps it)"""
-    _cache = {}
-
-    @classmethod
-    def of(cls, case, mode):
-        key = (case.kind, case.cin, case.cout, case.shape, case.k, mode, case.wd if mode == "unit" else None,
-               case.wide if mode == "wide" else None)
-        if key not in cls._cache:
-            cls._cache[key] = cls(case, mode, zlib.crc32(repr(key).encode()))
-        return cls._cache[key]
-
-    def __init__(self, case, mode, seed):
-        g = torch.Generator().manual_seed(seed)
-        self.kind, self.k = case.kind, case.k
-        mod = conv_module(case.kind, case.cin, case.cout, case.k, case.dims)
-        N, sp = case.shape[0], case.shape[1:]
-        xs = (N, case.cin) + sp
-        ys = (N, case.cout) + conv_out_shape(case.kind, case.k, sp)
-        ws = tuple(mod.weight.shape)
-        if mode == "unit":
-            def tern(shape, p):
-                return ((torch.randint(0, 2, shape, generator=g) * 2 - 1) * (torch.rand(shape, generator=g) < p)).float()
-            self.x, self.w, self.gy = tern(xs, 2 / 3), tern(ws, case.wd), tern(ys, 2 / 3)
-            self.b = torch.randint(-2, 3, (case.cout,), generator=g).float()
-        elif mode == "wide":
-            m = case.wide
-            self.x, self.w, self.gy = (torch.randint(-m, m + 1, s, generator=g).float() for s in (xs, ws, ys))
-            self.b = torch.randint(-2, 3, (case.cout,), generator=g).float()
-        else:
-            tdt = nat.torch_dtype(mode[1])
-            fan = case.cin * case.k ** case.dims
-            self.x, self.gy = (torch.randn(s, generator=g).to(tdt).float() for s in (xs, ys))
-            self.w = (torch.randn(ws, generator=g) * fan ** -0.5).to(tdt).float()
-            self.b = torch.randn(case.cout, generator=g) * 0.5
-        self._ref = {}
-
-    def module(self, case):
-        mod = conv_module(case.kind, case.cin, case.cout, case.k, case.dims)
-        with torch.no_grad():
-            mod.weight.copy_(self.w)
-            mod.bias.copy_(self.b)
-        return mod
-
-    def ref(self, pas, f32=False):
-        """float64 (``f32``: torch float32) evaluation of the pass on the CPU"""
-        key = (pas, f32)
-        if key not in self._ref:
-            x, w, b, gy = ((t if f32 else t.double()) for t in (self.x, self.w, self.b, self.gy))
-            with torch.no_grad():
-                self._ref[key] = conv_fwd(self.kind, self.k, x, w, b) if pas == "fwd" else conv_dgrad(self.kind, self.k, gy, w, self.x.shape)
-        return self._ref[key]
-
-
-class _Run:
-    """one recorded and executed pass over an output buffer the test prepared (every element ACT_SENTINEL before the pass)"""
-
-    def __init__(self, case, ops, layout="padded"):
-        """layout: "padded" (the written columns, then one more 16-byte chunk of the buffer), "dense" (rows exactly Cn_store wide, the
-        gathered operand in rows of its own), "sliced" (the output a column slice at c0 > 0 of a buffer with a further chunk behind
-        it, the gathered operand a column slice of a wider buffer whose other columns hold the integer 3)"""
-        dt = case.dt
-        self.case = case
-        drv = self.drv = ConvPassDriver(ops.module(case), dt, DEV, cg=case.cg, dims=case.dims)
-        e = nat.epc(dt)
-        N, sp = case.shape[0], case.shape[1:] + (1,) * (3 - case.dims)
-        xd = (N,) + sp
-        odt = F32 if case.out_f32 else dt
-        eo = nat.epc(odt)
-        fwd = case.pas == "fwd"
-        src = ops.x if fwd else ops.gy
-        sliced_in = layout == "sliced" and case.g_ld is None and src.shape[1] % e == 0
-        if sliced_in:
-            ga = wide_act(src, dt, DEV, e, e, 3.0)
-        elif fwd:
-            ga = drv.act(src, ld=case.g_ld)
-        else:
-            ga = to_cl(src, dt, DEV, ld=case.g_ld)
-        self.sliced_in = sliced_in
-        Cn = case.cout if fwd else case.cin
-        od = drv.layer.out_dims(xd) if fwd else xd
-        narrow = case.o_ld == 12
-        Cs = rup(Cn, 4 if (case.out_f32 or narrow) else eo)
-        self.c0 = c0 = eo if layout == "sliced" else 0
-        ld = case.o_ld if narrow else c0 + Cs + (0 if layout == "dense" else eo)
-        self.out = out = sentinel_act(od, Cn, odt, DEV, ld, c0)
-        if fwd:
-            drv.fwd(case.family, ga, out=out, out_f32=case.out_f32)
-        else:
-            drv.set_input_dims(xd)
-            drv.dgrad(case.family, ga, out=out)
-        d = drv.desc
-        assert d.Cn == Cn and d.Cn_store == Cs and d.o_ld == ld and d.g_ld == ga.ld, (d.Cn, d.Cn_store, d.o_ld, d.g_ld)
-        self.Cn, self.Cs, self.ld = Cn, Cs, ld
-
-    def buffer(self):
-        """the whole output buffer as float64 on the CPU: (N, X, Y, Z, ld)"""
-        return self.out.t.cpu().double()
-
-    def check_columns(self, want, what):
-        """``want``: (N, Cn, *spatial) float64, the values columns [0, Cn) of the pass must hold bit for bit; columns [Cn, Cn_store)
-        must be zero and every other column of the buffer must still hold the sentinel"""
-        T = self.buffer()
-        if want.ndim == 4:
-            want = want.unsqueeze(-1)
-        c0, Cn, Cs = self.c0, self.Cn, self.Cs
-        got = T[..., c0:c0 + Cn].permute(0, 4, 1, 2, 3)
-        bad = got != want
-        nbad = int(bad.sum())
-        if nbad:
-            i = tuple(int(v) for v in bad.nonzero()[0])
-            raise AssertionError(f"{what}: {nbad} of {bad.numel()} elements differ from the reference; first at (n, c, x, y, z) = {i}: "
-                                 f"got {float(got[i])}, expected {float(want[i])}")
-        pad = T[..., c0 + Cn:c0 + Cs]
-        assert bool((pad == 0).all()), f"{what}: pad columns [Cn, Cn_store) = [{Cn}, {Cs}) are not zero: {pad.unique()[:8].tolist()}"
-        for lo, hi in ((0, c0), (c0 + Cs, self.ld)):
-            rest = T[..., lo:hi]
-            assert bool((rest == ACT_SENTINEL).all()), f"{what}: columns [{lo}, {hi}) outside the pass changed: {rest.unique()[:8].tolist()}"
-        return T
-
-
-def _exact(case, mode, layout="padded"):
-    """the integer run of a case -> (_Run, float64 reference); asserts the exactness condition of the storage type on the reference"""
-    ops = _Ops.of(case, mode)
-    ref = ops.ref(case.pas)
-    cap = EXACT_CAP[F32 if case.out_f32 else case.dt]
-    top = float(ref.abs().max())
-    nz = float((ref != 0).double().mean())
-    print(f"{case.id} [{mode}]: max |ref| {top:.0f} (cap {cap:.0f}), nonzero {100 * nz:.1f} %")
-    if mode == "unit" or case.dt == F32 or case.out_f32:
-        assert top <= cap if cap < 2.0 ** 24 else top < cap, ("the reference leaves the exactly representable integers", top, cap)
-    return _Run(case, ops, layout), ref
 
 
 # ---- case matrix -------------------------------------------------------------------------------------------------------------

@@ -49,6 +49,10 @@ Not covered, with the reason the library gives:
     as for the forward; on the stem: the layer has no input gradient; on the many-channel 8-class pass:
     test_many_channel_8_class_kernel_statistics_and_addend has it; on the stride-2 halo pass: not a case here;
   * a norm narrower than the pass at bst_col0 == 0: GemmLayer._try_bst only asks when the column range equals the norm.
+
+More than one column block (grid.y > 0 of the 256-column tile, as the 2-D U-Net's 512- to 1536-column passes run it): the 64 -> 512
+cases of STATS_CASES, DGRAD_ADD_CASES and BST_CASES, 3-D layers like every case of these tables (the epilogue code is the same for a
+2-D pass: tests/test_gpu_conv2d_exact.py holds those layers' outputs).
 """
 import ctypes
 
@@ -181,6 +185,8 @@ STATS_CASES = [
     ("generic 192x256 40->160", "generic 192x256", "conv", 40, 160, 3, (2, 7, 9, 11), BF16, 0.0),
     ("generic ring 128->128", "generic ring 192x128", "conv", 128, 128, 3, (2, 7, 9, 11), BF16, 0.0),
     ("generic fp32 128x64 24->48", "generic 128x64", "conv", 24, 48, 3, (2, 7, 9, 11), F32, 0.0),
+    # two column blocks of the 256-column tile (the widths of the 2-D U-Net's down units): partial slots and stats_ld = 512
+    ("generic ring 192x256 64->512", "generic ring 192x256", "conv", 64, 512, 3, (2, 5, 6, 7), BF16, 0.0),
 ]
 
 
@@ -261,6 +267,7 @@ DGRAD_ADD_CASES = [
     ("generic 128x128 dgrad 96->40", "generic 128x128", "conv", 96, 40, (2, 7, 9, 11), BF16),
     ("generic 192x256 dgrad 160->40", "generic 192x256", "conv", 160, 40, (2, 7, 9, 11), BF16),
     ("generic fp32 128x64 dgrad 48->24", "generic 128x64", "conv", 48, 24, (2, 7, 9, 11), F32),
+    ("ring 192x256 dgrad 512->64, two column blocks", "generic ring 192x256", "conv", 512, 64, (2, 5, 6, 7), BF16),
 ]
 
 
@@ -368,6 +375,10 @@ BST_CASES = [
      True, None),
     ("ring 192x128 dgrad 128->128", "generic ring 192x128", "conv", 128, 128, (2, 7, 9, 11), 128, 0, False, None),
     ("ring 192x128, norm on columns 64..127 + addend", "generic ring 192x128", "conv", 128, 128, (2, 7, 9, 11), 64, 64, True, None),
+    # the second column block of the 256-column tile alone (the 2-D U-Net's skip-concat gradients: norm on the upper columns)
+    ("ring 192x256 dgrad 512->64, norm on columns 256..511 + addend", "generic ring 192x256", "conv", 512, 64, (2, 5, 6, 7), 256, 256,
+     True, None),
+    ("ring 192x256 dgrad 512->64, norm on all 512 columns", "generic ring 192x256", "conv", 512, 64, (2, 5, 6, 7), 512, 0, False, None),
 ]
 
 

@@ -34,6 +34,18 @@ Shapes that differ from the plain list, and why:
   * an empty last split cannot come out of GemmLayer._wgrad_splits (at least 512 rows per split, 32-row rounding); the C ABI takes
     any split count, so the case forces splits = 12 over 585 rows (64-row ranges: range 9 holds 9 rows, ranges 10 and 11 none).
 
+The 2-D U-Net at its real widths (UNET2D_CASES, UNET2D_FUSED: every weight-gradient row of tests/unet2d_passes.py): up to 1536 columns
+(six column blocks of "ring 256x256"), K up to 9 * 1024, the fused down units' single pass held to the gradients of its two layers.
+Oracle A on every row; Oracle B on one row per distinct pass name, the long-K ConvTranspose2d 1536 -> 256 and 1024 -> 1024 and two
+fused units (each half with its own layer's bound).  Measured on an MI355X (weight / bias error, bounds in brackets):
+  generic 16 (10 -> 10)  3.5e-08 (6.0e-07), bias 0 (torch's float32 column sums came out exact: the one-rounding bound 6.0e-08 applied)
+  generic 128 (convT 128 -> 10)  5.1e-08 / 1.3e-09 (2.7e-06 / 2.0e-08);  ring 512x64 (64 -> 64)  5.6e-08 / 2.3e-09 (1.6e-06 / 3.6e-08)
+  ring 256x128 (128 -> 128)  6.3e-08 / 1.2e-09 (2.4e-06 / 7.9e-08)
+  ring 256x256: convT 1536 -> 256  7.7e-08 / 2.5e-09 (3.1e-06 / 7.8e-08);  1024 -> 1024  1.4e-07 / 6.9e-09 (3.1e-06 / 1.6e-07)
+  fused 1 -> 2 x 64 (generic 128 element-wise), residual / unit0:  2.9e-08 / 3.2e-08 (7.3e-07 / 5.7e-07), bias <= 3.0e-09 (>= 2.3e-08)
+  fused 256 -> 2 x 512 (ring 256x256), residual / unit0:  6.7e-08 / 7.6e-08 (3.0e-06 / 2.9e-06), bias <= 1.2e-08 (>= 1.1e-07)
+  caps 1 / (4 * N * rows): 5.1e-04 .. 1.0e-03, far above every bound
+
 Not covered, with the reason the library gives:
   * "head 12/16" and "head 16/12" (conv_wgrad_head_kernel, the head kernel without the x-column reuse): wgrad_halo_variant picks
     that kernel only for taps out of canonical order, which GemmLayer never records; "head 16/16" and "head 12/12" run below from
@@ -41,8 +53,8 @@ Not covered, with the reason the library gives:
     named on the CPU from a hand-made descriptor (tests/test_abi_exports.py);
   * "halo 32x32": 16 -> <= 16 channels with rows neither 12 nor 16 wide (g_ld = 24, ...), which no activation of the host mirror
     has; named on the CPU likewise;
-  * "generic 32/64/128 element-wise": named on the CPU; the element-wise staging code is the same template branch as the 16-column
-    tile's, which the three first-layer cases run;
+  * "generic 32/64 element-wise": named on the CPU; the element-wise staging code is the same template branch as the 16-column
+    tile's, which the three first-layer cases run, and the 128-column tile's, which the 2-D U-Net's fused first layer runs;
   * in_mean_rstd on anything but the x-column head kernel and dyn_* on anything but the stem kernel: the launch refuses
     ("... is not implemented for this pass"), asserted below;
   * CTSEG_WGRAD_ADDR64: its own bit-equality test (test_gpu_round3.py).
@@ -216,6 +228,75 @@ def test_split_k_kernels_are_exact_on_integers(case, monkeypatch):
     _exact_run(case, monkeypatch)
 
 
+# ---- the 2-D U-Net at its real widths ----------------------------------------------------------------------------------------
+# The weight-gradient rows of tests/unet2d_passes.py (BaseUNet2D, filters 64 .. 1024, residual units; the CPU test of
+# tests/test_abi_exports.py holds the names against the plan recorder): up to 1536 columns (6 column blocks of "ring 256x256"), K up
+# to 9 * 1024, the transposed layers with their roles swapped (gathered = dOut).  (2, 13, 19) stride-1 / transposed input, (2, 28, 30)
+# stride-2 input; the bottom unit gathers the lower 512 columns of the 1536-wide skip concat.
+P1, P2 = (2, 13, 19, 1), (2, 28, 30, 1)
+UNET2D_CASES = [
+    _Case("generic 16", "conv2d", 10, 10, P1, cg=16, x_ld=16, dy_ld=16), _Case("generic 128", "convT2d", 128, 10, P1),
+    _Case("ring 512x64", "conv2d", 64, 64, P1), _Case("ring 256x256", "convT2d", 256, 64, P1),
+    _Case("ring 256x128", "conv2d", 128, 128, P1), _Case("ring 256x256", "convT2d", 512, 128, P1),
+    _Case("ring 256x256", "conv2d", 256, 256, P1), _Case("ring 256x256", "convT2d", 1536, 256, P1),
+    _Case("ring 256x256", "conv2d", 1024, 1024, (1, 13, 19, 1)), _Case("ring 256x256", "conv2d", 512, 1024, P1, x_ld=1536),
+    _Case("ring 256x256", "conv2d", 512, 1024, P1, k=1, x_ld=1536), _Case("ring 256x256", "conv2d", 512, 512, P1),
+]
+# the fused [residual | unit0] GEMM of the strided residual units: (name, cin, C of each half)
+UNET2D_FUSED = [("generic 128 element-wise", 1, 64), ("ring 256x256", 64, 128), ("ring 256x256", 128, 256), ("ring 256x256", 256, 512)]
+
+
+def test_unet2d_cases_are_the_recorded_weight_gradient_passes():
+    from unet2d_passes import UNET2D_PASSES
+    table = {(kind, cin, cout, k, fused): (name, Cg, Cn) for pas, _, kind, cin, cout, k, fused, Cg, Cn, _, name in UNET2D_PASSES if pas == "wgrad"}
+    cases = {(c.op, c.cin, c.cout, c.k, False): (c.name, c.cg or (c.cout if c.op == "convT" else c.cin), c.cin if c.op == "convT" else c.cout)
+             for c in UNET2D_CASES}
+    cases.update({("conv_s2", cin, 2 * C, 3, True): (name, cin, 2 * C) for name, cin, C in UNET2D_FUSED})
+    # (a transposed layer gathers dOut in 16-byte chunked rows: 16 channels for the 10 classes)
+    cases[("convT", 128, 10, 3, False)] = ("generic 128", 16, 128)
+    assert cases == table
+
+
+@pytest.mark.parametrize("case", UNET2D_CASES, ids=[c.id for c in UNET2D_CASES])
+def test_unet2d_layers_are_exact_on_integers(case, monkeypatch):
+    _exact_run(case, monkeypatch)
+
+
+@pytest.mark.parametrize("name,cin,C", UNET2D_FUSED, ids=[f"{n}_{ci}->2x{c}".replace(" ", "_") for n, ci, c in UNET2D_FUSED])
+def test_unet2d_fused_down_unit_equals_the_two_layers(name, cin, C, monkeypatch):
+    """ONE weight-gradient pass over the 2 * C columns of [d_res | d_y0], two slab reduces at col0 = 0 and C: each half must equal
+    the float64 gradient of its own layer (residual, unit0) bit for bit, bias gradient included; Oracle A as in _exact_run (NaN slabs,
+    untouched guards, replay over stale slabs with other operands)"""
+    case = _Case(name, "conv2d_s2", cin, 2 * C, P2)
+    case.setenv(monkeypatch)
+    xs, ys, _ = case.sizes()
+    assert 16 * xs[0] * ys[2] * ys[3] < 2 ** 24, "the integer oracle is exact only below 2^24"
+    gen = torch.Generator().manual_seed(case.seed)
+    torch.manual_seed(1)
+    mods = [conv_module("conv_s2", cin, C, 3, 2) for _ in range(2)]
+    drv = WgradPassDriver(mods, BF16, DEV)
+    for rnd in range(2):
+        x, dy = _ints(xs, gen), _ints(ys, gen)
+        refs = [conv_wgrad("conv_s2", 3, x, dy[:, h * C:(h + 1) * C], tuple(mods[h].weight.shape), torch.float64) for h in (0, 1)]
+        if rnd == 0:
+            xa, ga = case.acts(drv, x, dy)
+            d = drv.record(name, xa, ga)
+            assert d.Cn == 2 * C and sum(1 for p in drv.prog or drv.plan.prog if p[0] == "ctseg_conv_wgrad_reduce") == 2
+            flat = drv.go(poison=float("nan"))[3]
+        else:
+            xa.t[..., :cin].copy_(x.unsqueeze(-1).permute(0, 2, 3, 4, 1))
+            ga.t[..., :2 * C].copy_(dy.unsqueeze(-1).permute(0, 2, 3, 4, 1))
+            flat = drv.go()[3]
+        tag = "poisoned slabs" if rnd == 0 else "replay over stale slabs"
+        for (gw, gb), (rw, rb), half in zip(drv.part_grads(flat), refs, ("residual", "unit0")):
+            assert bool((rw.abs().flatten(1).sum(1) > 0).all()) and bool((rw.abs().transpose(0, 1).flatten(1).sum(1) > 0).all()), \
+                "an all-zero channel slice of the reference: a skipped column or K block would pass"
+            assert bool((rb != 0).any())
+            assert torch.equal(gw, rw.float()), (name, tag, half, "weight gradient", int((gw != rw.float()).sum()))
+            assert torch.equal(gb, rb.float()), (name, tag, half, "bias gradient")
+        assert drv.outside_untouched(flat), (name, tag, "flat gradient outside the two layers' views")
+
+
 # (case, expected splits, flat XCD-ordered grid?)
 GRID_CASES = [
     (_Case("generic 64", "conv", 48, 48, BIG, target=88), 4, True),          # N * splits = 8, 11 K blocks per slab
@@ -319,6 +400,11 @@ NORMAL_CASES = [
     _Case("ring 256x256", "conv", 64, 256, (2, 6, 6, 6)),
     _Case("generic 64", "conv", 48, 48, S1), _Case("generic 64", "conv", 48, 48, S1, dt=F32),
     _Case("generic 16 element-wise", "conv2d", 3, 16, (2, 33, 45, 1)),
+    # the 2-D U-Net at its real widths: one row per distinct weight-gradient pass name of tests/unet2d_passes.py, the six column blocks
+    # of ConvTranspose2d 1536 -> 256 and K = 9 * 1024 ("generic 128 element-wise": the fused first layer, below)
+    _Case("generic 16", "conv2d", 10, 10, (2, 13, 19, 1), cg=16, x_ld=16, dy_ld=16), _Case("generic 128", "convT2d", 128, 10, (2, 13, 19, 1)),
+    _Case("ring 512x64", "conv2d", 64, 64, (2, 13, 19, 1)), _Case("ring 256x128", "conv2d", 128, 128, (2, 13, 19, 1)),
+    _Case("ring 256x256", "convT2d", 1536, 256, (2, 13, 19, 1)), _Case("ring 256x256", "conv2d", 1024, 1024, (1, 13, 19, 1)),
 ]
 
 
@@ -355,6 +441,25 @@ def test_normal_valued_operands_within_the_float32_bound(case, monkeypatch):
     if case.bias_done:
         gb = conv_wgrad(case.op, case.k, x, dy, wshape, torch.float64)[1].float()       # (not computed by this pass)
     _normalised_check(case.id, gw, gb, x, dy, case.op, case.k, wshape, d.N * d.Xr * d.Yr * d.Zr)
+
+
+@pytest.mark.parametrize("name,cin,C", [UNET2D_FUSED[0], UNET2D_FUSED[3]], ids=["generic_128_element-wise_1->2x64", "ring_256x256_256->2x512"])
+def test_unet2d_fused_down_unit_normal_valued_within_the_float32_bound_of_each_layer(name, cin, C, monkeypatch):
+    """Oracle B on the single pass of a fused [residual | unit0] unit: each half against the float64 gradient of its own layer, with
+    that layer's own bound (_normalised_check, unchanged)"""
+    case = _Case(name, "conv2d_s2", cin, 2 * C, P2)
+    case.setenv(monkeypatch)
+    xs, ys, _ = case.sizes()
+    torch.manual_seed(case.seed)
+    x, dy = torch.randn(xs).bfloat16().float(), torch.randn(ys).bfloat16().float()
+    mods = [conv_module("conv_s2", cin, C, 3, 2) for _ in range(2)]
+    drv = WgradPassDriver(mods, BF16, DEV)
+    xa, ga = case.acts(drv, x, dy)
+    d = drv.record(name, xa, ga)
+    flat = drv.go(poison=float("nan"))[3]
+    assert drv.outside_untouched(flat)
+    for h, ((gw, gb), half) in enumerate(zip(drv.part_grads(flat), ("residual", "unit0"))):
+        _normalised_check(f"{case.id} {half}", gw, gb, x, dy[:, h * C:(h + 1) * C], "conv_s2", 3, tuple(mods[h].weight.shape), d.N * d.Xr * d.Yr * d.Zr)
 
 
 # ---- operand normalised on load (in_mean_rstd): the x-column head kernel -----------------------------------------------------
